@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: component table resident in HBM -> solution x.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
+
+A plain run sets up the headline workload, warms up, times K steps and prints the result line
+(`ms_per_step` = milliseconds of one timed step).  Everything else it measures -- `roofline` (with the
+kernel-trace child behind `roofline.by_class`), `cpu_baseline`, `reuse_symbolic`, `concurrent`,
+`print_1e6_s` and `also` -- is reported only with `--full`.  `--dump-outputs DIR` writes what the timed
+path returned in its last step (the solution x of the step's last circuit; cfg4: the rank's [members, n]
+block) as DIR/x.npy in float64, rank 0 only; the inputs are generated with fixed seeds, so two builds can
+be compared output for output.
 
 A step is one pass of the hot path over one batch of synthetic circuits per GPU: for every
 circuit symbolic + numeric assembly + solve, the equivalent of the reference's
@@ -24,9 +32,9 @@ every finished circuit is all-gathered over RCCL inside the timed region (8 MB p
 rank, overlapped with the next solve: nodal_amd.batch.ShardedCircuits), `value` = circuits all
 ranks solved / the slowest rank's time -- weak scaling in the number of circuits.  At N = 1
 there is no process group: the line is BENCH's.  cfg4, the value sweep that shards as one
-block system per rank, is measured in `also` at every N.
+block system per rank, is measured in `also` at every N (with --full).
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel of the workload,
+Rank 0 prints ONE JSON line.  With --full, `roofline` describes the dominant kernel of the workload,
 timed with HIP events on the library's stream, plus the end-to-end figure of SURVEY.md
 section 8d; `cpu_baseline` is the oracle (the reference's algorithm restated, same numpy /
 scipy calls) timed on this box's host cores; `also` carries the other configurations, each
@@ -188,6 +196,8 @@ class SingleCircuits:
         self.kern_ms = self.kern_n = 0
         self.kern_alg = 0.0
         self.circuits_done = 0
+        self.keep_outputs = False  # True: finish() keeps a copy of the last circuit's x in self.outputs
+        self.outputs = None
 
     def step(self):
         h = self.h
@@ -228,6 +238,8 @@ class SingleCircuits:
         d2h_ms = (time.perf_counter() - t0) * 1e3
         if gathered_ok:
             gathered_ok = bool(np.array_equal(self.sc.latest()[self.sc.rank], x))
+        if self.keep_outputs:  # (x is a recycled page-locked block: copied before the handle goes)
+            self.outputs = {"x": np.array(x, dtype=np.float64, copy=True)}
         iterations, levels, _ = h.solve_info()
         out = dict(resid=h.residual(), x0=float(x[0]), n=h.n, nnz=h.nnz, iterations=iterations,
                    amg_levels=levels, d2h_ms=d2h_ms, h2d_ms=self.h2d_ms, h2d_first_ms=self.h2d_first_ms,
@@ -278,6 +290,8 @@ class BatchShard:
         self.circuits_done = 0
         self.reuse = False  # True: the block system's symbolic phases (one member's lists, replicated; the
         # hierarchy's patterns) are kept from step to step: a long value sweep on one topology
+        self.keep_outputs = False  # True: finish() keeps this rank's [members, n] results in self.outputs
+        self.outputs = None
 
     @property
     def gather_ms(self):
@@ -305,6 +319,8 @@ class BatchShard:
         t0 = time.perf_counter()
         x = self.shard.own_block()
         d2h_ms = (time.perf_counter() - t0) * 1e3
+        if self.keep_outputs:
+            self.outputs = {"x": np.array(x, dtype=np.float64, copy=True)}
         iterations, levels, _ = h.solve_info()
         # every rank must hold every member after the gather
         gathered_ok = None
@@ -486,11 +502,13 @@ def make_workload(name, rank, world, device, dist, per_step, force_collective=Fa
     return SingleCircuits(name, rank, per_step, device, dist, force_collective)
 
 
-def time_workload(name, rank, world, device, dist, steps, warmup, per_step, force_collective=False, reuse=False):
+def time_workload(name, rank, world, device, dist, steps, warmup, per_step, force_collective=False, reuse=False,
+                  keep_outputs=False):
     import torch
     wl = make_workload(name, rank, world, device, dist, per_step, force_collective)
     if reuse:
         wl.reuse = True
+    wl.keep_outputs = keep_outputs
     for _ in range(max(warmup, 1)):  # at least one untimed pass: buffers grow to their final size
         wl.step()
     wl.reset_stats()
@@ -515,7 +533,28 @@ def time_workload(name, rank, world, device, dist, steps, warmup, per_step, forc
               kern_ms=wl.kern_ms, kern_n=wl.kern_n, kern_alg=wl.kern_alg, table=wl.table,
               gather_ms=getattr(wl, "gather_ms", 0.0) / max(steps, 1))
     st.update(wl.finish())
+    st["outputs"] = wl.outputs
     return st
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, arrays):
+    """Write every array as DIRECTORY/<name>.npy (float64).  An output above DUMP_LIMIT_BYTES in all is cut to a
+    fixed sample of its rows (seed 0, sorted), whose indices go to <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 1024  # (less the .npy headers)
+    for key, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > budget:
+            rows = a.shape[0] if a.ndim > 1 else a.size
+            keep = max(1, budget // (a.nbytes // rows + 8))  # (sample rows + their float64 indices)
+            idx = np.sort(np.random.RandomState(0).choice(rows, size=min(keep, rows), replace=False))
+            a = np.ascontiguousarray(a[idx])
+            np.save(os.path.join(directory, f"{key}_rows.npy"), idx.astype(np.float64))
+        np.save(os.path.join(directory, f"{key}.npy"), a)
 
 
 # ---------------------------------------------------------------------------------
@@ -662,7 +701,7 @@ def cpu_baseline(name, table):
             "solve_only_circuits_per_s": members / t_solve, "seconds": t_asm + t_solve, "x0": x0}
 
 
-def summary(st, world, with_cpu):
+def summary(st, world, with_cpu, with_roofline=True):
     circuits = st["circuits"] * world
     value = circuits / st["elapsed"]
     out = {"workload": f"{st['name']}: {st['desc']}", "circuits_per_sec": value,
@@ -670,8 +709,9 @@ def summary(st, world, with_cpu):
            "phase_ms": {"symbolic": st["phase_ms"][0], "numeric": st["phase_ms"][1], "solve": st["phase_ms"][2]},
            "h2d_ms": st["h2d_ms"], "d2h_ms": st["d2h_ms"], "h2d_bytes": st["h2d_bytes"],
            "d2h_bytes": st["d2h_bytes"], "scaled_residual": st["resid"],
-           "solver": {"iterations": st["iterations"], "amg_levels": st["amg_levels"]},
-           "roofline": roofline_of(st, value / world)}
+           "solver": {"iterations": st["iterations"], "amg_levels": st["amg_levels"]}}
+    if with_roofline:
+        out["roofline"] = roofline_of(st, value / world)
     if not st["dense"] and st["name"] != "cfg4":
         b_asm, _ = alg_bytes(st["table"], st["n"], st["nnz"])
         asm_ms = st["phase_ms"][0] + st["phase_ms"][1]
@@ -750,21 +790,29 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=None, choices=["cfg2", "cfg3", "cfg4", "cfg5"])
     ap.add_argument("--per-step", type=int, default=0, help="circuits per GPU per step")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline (and its kernel-trace child), "
+                         "cpu_baseline, reuse_symbolic, concurrent, print_1e6_s and the other workloads in `also`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs (--full)")
+    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads (--full)")
     ap.add_argument("--force-collective", action="store_true",
                     help="cfg4 with the process group initialised and the all_gather run even at N = 1 "
                          "(backend nccl = RCCL, world_size 1: the collective path on a one-GPU box)")
     ap.add_argument("--concurrent", type=int, default=4,
-                    help="streams of the extra concurrent-throughput figure (0: skip it)")
+                    help="streams of the extra concurrent-throughput figure (--full; 0: skip it)")
     ap.add_argument("--no-classes", action="store_true",
-                    help="skip the kernel-trace child that measures roofline.by_class (it is one itself)")
+                    help="skip the kernel-trace child that measures roofline.by_class (--full; it is one itself)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if (args.gpus > 1 or args.force_collective) and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus, sys.argv[1:])
 
-    if args.gpus == 1 and not args.force_collective and not args.no_classes and "WORLD_SIZE" not in os.environ:
+    if (args.full and args.gpus == 1 and not args.force_collective and not args.no_classes
+            and "WORLD_SIZE" not in os.environ):
         # BEFORE this process touches the GPU: the same workload in a child under the kernel tracer
         wname = args.workload or "cfg3"
         if wname in ("cfg3", "cfg5"):
@@ -808,8 +856,13 @@ def main():
     # 1/2/4/8" -- one workload); --force-collective keeps config 4 as its default (the block gather on one GPU)
     name = args.workload or ("cfg4" if args.force_collective else "cfg3")
     per_step = args.per_step or CIRCUITS_PER_STEP[name]
-    st = time_workload(name, rank, world, local, dist, args.steps, args.warmup, per_step, args.force_collective)
-    head = summary(st, world, with_cpu=(rank == 0 and world == 1 and not args.no_cpu))
+    dump = args.dump_outputs is not None and rank == 0
+    st = time_workload(name, rank, world, local, dist, args.steps, args.warmup, per_step, args.force_collective,
+                       keep_outputs=dump)
+    if dump:
+        dump_outputs(args.dump_outputs, st["outputs"])
+    head = summary(st, world, with_cpu=(args.full and rank == 0 and world == 1 and not args.no_cpu),
+                   with_roofline=args.full)
     out = {
         "metric": "circuits_per_sec",
         "value": head["circuits_per_sec"],
@@ -843,7 +896,7 @@ def main():
                 "gather_ms_per_step", "gathered_ok"):
         if key in head:
             out[key] = head[key]
-    if rank == 0 and world == 1 and name in ("cfg3", "cfg5") and not args.no_also:
+    if args.full and rank == 0 and world == 1 and name in ("cfg3", "cfg5") and not args.no_also:
         # the same circuits with the symbolic phases of the previous one kept (nodal_run(reuse_symbolic = 1):
         # stamping lists and, keyed on the same struct_epoch, the multigrid hierarchy's aggregates and
         # patterns; values, Galerkin sums and the solve are redone) -- a value sweep on one topology
@@ -851,7 +904,7 @@ def main():
         r3 = summary(s3, 1, with_cpu=False)
         out["reuse_symbolic"] = {k: r3[k] for k in ("circuits_per_sec", "ms_per_solve", "phase_ms", "solver",
                                                     "scaled_residual")}
-    if rank == 0 and world == 1 and name != "cfg4" and args.concurrent > 1:
+    if args.full and rank == 0 and world == 1 and name != "cfg4" and args.concurrent > 1:
         per_stream = 12 if name != "cfg2" else 8
         conc = [concurrent_throughput(name, local, args.concurrent, per_stream)]
         if name in ("cfg3", "cfg5"):
@@ -860,16 +913,16 @@ def main():
         out["concurrent"] = max(conc, key=lambda c: c["circuits_per_sec"])
         out["concurrent"]["all"] = [{k: c[k] for k in ("streams", "symbolic_phases_kept", "circuits_per_sec")}
                                     for c in conc]
-    if rank == 0 and world == 1 and name == "cfg3" and not args.no_also:
+    if args.full and rank == 0 and world == 1 and name == "cfg3" and not args.no_also:
         out["print_1e6_s"], out["netlist_read_1e6_s"] = print_solution_seconds(local)
-    if world > 1 and name != "cfg4" and not args.no_also:
+    if args.full and world > 1 and name != "cfg4" and not args.no_also:
         # config 4 -- the value sweep that shards as one block system per rank, 128 members per GPU, gathered over
         # RCCL -- measured at every N beside the headline (every rank takes part; rank 0 reports)
         s4 = time_workload("cfg4", rank, world, local, dist, 6, 1, 128, False)
         r4 = summary(s4, world, with_cpu=False)
         out["also"] = {"cfg4": {k: r4[k] for k in ("workload", "circuits_per_sec", "ms_per_solve", "phase_ms", "solver",
                                                     "scaled_residual", "gather_ms_per_step", "gathered_ok") if k in r4}}
-    if rank == 0 and world == 1 and not args.no_also and not args.force_collective:
+    if args.full and rank == 0 and world == 1 and not args.no_also and not args.force_collective:
         also = {}
         for other in ("cfg4", "cfg5", "cfg2"):
             if other == name:

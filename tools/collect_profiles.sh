@@ -11,7 +11,7 @@ mkdir -p $O
 timeout -k 10 300 rocprofv3 --kernel-trace -d $O/classes -- python3 bench.py --workload cfg3 --steps 2 --warmup 1 --no-cpu --no-also --concurrent 0 --no-classes > $O/classes.log 2>&1
 python3 tools/prof_classes.py $O/classes cfg3 999999 4995995 > $O/classes.json
 rm -rf $O/classes
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/default -o default -- python3 bench.py --concurrent 0 --no-classes > $O/bench_default.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/default -o default -- python3 bench.py --full --concurrent 0 --no-classes > $O/bench_default.log 2>&1
 for w in cfg2 cfg3 cfg4 cfg5; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $O/pmc_${w}_$c -- python3 bench.py --workload $w --steps 1 --warmup 1 --no-cpu --no-also --concurrent 0 --no-classes > $O/pmc_${w}_$c.log 2>&1
@@ -25,4 +25,4 @@ python3 tools/pmc_summary.py $O/pmc_traffic.json cfg2:$O/pmc_cfg2_FETCH_SIZE:$O/
   cfg5:$O/pmc_cfg5_FETCH_SIZE:$O/pmc_cfg5_WRITE_SIZE > $O/pmc_summary.log 2>&1
 cp $O/default/default_kernel_stats.csv $O/bench_default_kernel_stats.csv
 rm -rf $O/default $O/pmc_cfg*_FETCH_SIZE $O/pmc_cfg*_WRITE_SIZE
-# (a plain `python bench.py > gpurun_out/bench_plain.log` gives profiles/<round>_bench_default.json)
+# (the line of `python bench.py --full`, kept as it prints, gives profiles/<round>_bench_default.json)
