@@ -144,6 +144,19 @@ int nodal_download_x(nodal_handle h, double *x);
 int nodal_solve_pairs(nodal_handle h, int32_t dense, int32_t npairs, const int32_t *ia,
                       const int32_t *ib, double *resistance, int32_t *info);
 
+/* ---- source sweep (replaces a loop of Circuit(netlist with other source values) + .solve(), reference
+ *      nodal/nodal.py:306-336: a .dc sweep of a supply, the load vectors of an IR-drop study) ---------------
+ * Members m in [0, count): the system of the last nodal_assemble_numeric with the value of table row
+ * rows[j] (type A or E) replaced by values[m * nsrc + j].  G is shared; only the rhs differs.
+ * x_out [count][n] row-major, resid_out [count], info_out [count]; x_out / resid_out may be NULL.
+ * resid_out[m] = ||G x_m - A_m||_inf / (||G||_inf ||x_m||_inf + ||A_m||_inf), computed on the device.
+ * info_out[m] > 0: singular network (row of NaNs, status OK) -- except with dense != 0, where a singular G
+ * returns NODAL_E_SINGULAR, as nodal_solve_dense does.  NODAL_E_INVALID: a row out of range, a row that is
+ * not of type A or E, a repeated row, or no nodal_assemble_numeric before.  Neither the table nor the
+ * assembled rhs changes; the solution of the last single solve is not kept (nodal_download_x needs a new one). */
+int nodal_solve_sources(nodal_handle h, int32_t dense, int32_t count, int32_t nsrc, const int64_t *rows,
+                        const double *values, double *x_out, double *resid_out, int32_t *info_out);
+
 /* scaled residual ||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the
  * solution currently on the device, computed on the device from the CSR form */
 int nodal_residual(nodal_handle h, double *scaled_residual);
@@ -216,6 +229,9 @@ int nodal_set_option(nodal_handle h, int32_t option, int32_t value);
  * kernel; host buffers, column-major, leading dimensions M, K, M. */
 int nodal_debug_gemm(nodal_handle h, int32_t M, int32_t N, int32_t K, const double *A,
                      const double *B, double *C);
+/* the rhs columns nodal_solve_sources builds for the same arguments, [count][n] row-major */
+int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const int64_t *rows,
+                            const double *values, double *rhs_out);
 
 #ifdef __cplusplus
 }

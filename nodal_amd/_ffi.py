@@ -46,6 +46,8 @@ SIGNATURES = {
     "nodal_solve_sparse": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _i32p, _i32p, _f64p]),
     "nodal_download_x": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_solve_pairs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p]),
+    "nodal_solve_sources": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i64p, _f64p, _f64p, _f64p,
+                                      _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
     "nodal_run_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _i32p]),
@@ -57,6 +59,7 @@ SIGNATURES = {
     "nodal_synchronize": (C.c_int, [C.c_void_p]),
     "nodal_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "nodal_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
+    "nodal_debug_sources_rhs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i64p, _f64p, _f64p]),
 }
 
 _lib = None
@@ -265,6 +268,32 @@ class Handle:
                                                _ptr(ib, C.c_int32), _ptr(out, C.c_double),
                                                C.byref(info)), allow=(E_SINGULAR,))
         return out, info.value
+
+    def solve_sources(self, rows, values, dense):
+        """Source sweep: values [M, nsrc] replace the values of table rows `rows` (type A or E) member by
+        member.  Returns (x [M, n], info [M], scaled residual [M]); with dense, a singular G raises
+        NodalHipError(E_SINGULAR)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.ndim == 2 and values.shape[1] == len(rows)
+        count = values.shape[0]
+        x = np.empty((count, self.n), dtype=np.float64)
+        info = np.zeros(count, dtype=np.int32)
+        resid = np.zeros(count, dtype=np.float64)
+        self._check(self.lib.nodal_solve_sources(self._h, int(dense), count, len(rows), _ptr(rows, C.c_int64),
+                                                 _ptr(values, C.c_double), _ptr(x, C.c_double),
+                                                 _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
+        return x, info, resid
+
+    def debug_sources_rhs(self, rows, values):
+        """The right-hand sides solve_sources builds, [M, n] (testing hook)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.ndim == 2 and values.shape[1] == len(rows)
+        out = np.empty((values.shape[0], self.n), dtype=np.float64)
+        self._check(self.lib.nodal_debug_sources_rhs(self._h, values.shape[0], len(rows), _ptr(rows, C.c_int64),
+                                                     _ptr(values, C.c_double), _ptr(out, C.c_double)))
+        return out
 
     def download_x(self):
         x = host_empty(self.n, np.float64)

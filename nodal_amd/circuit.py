@@ -204,6 +204,36 @@ class Circuit:
                 raise np.linalg.LinAlgError("Singular matrix")
         return Solution(e, self.netlist, self.currents)
 
+    def solve_sources(self, sources):
+        """Solve the circuit for many settings of its independent sources at once.
+
+        `sources` maps names of A / E components to sequences of M values (every sequence the same
+        length).  Member m is the circuit with those components' values replaced by their m-th
+        values; G is shared, so the members share one factorisation or one multigrid hierarchy on
+        the device.  Returns a SourceSweep (sweep.py): `result` [M, K+B], `sw[m]` the Solution of
+        member m, `info`, `scaled_residual`.  Singular networks behave as in solve(): the dense path
+        raises LinAlgError / UnconnectedCircuitError once, the sparse path returns NaN rows with
+        info > 0 and warns once.  The circuit itself (its table, G, A) is left as it was."""
+        from .sweep import SourceSweep, resolve_sources
+        rows, values = resolve_sources(self.netlist, sources)
+        h = self._handle
+        if values.shape[0] == 0:
+            return SourceSweep(np.zeros((0, h.n)), np.zeros(0, dtype=np.int32), np.zeros(0), self.netlist,
+                               self.currents)
+        try:
+            x, info, resid = h.solve_sources(rows, values, dense=not self.sparse)
+        except _ffi.NodalHipError as exc:
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            if not is_connected(self.netlist):
+                logging.error("Model error: unconnected circuit")
+                raise UnconnectedCircuitError
+            logging.error("Model error: matrix is singular")
+            raise np.linalg.LinAlgError("Singular matrix")
+        if (info > 0).any():
+            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        return SourceSweep(x, info, resid, self.netlist, self.currents)
+
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last
         solution, computed on the device."""

@@ -5,6 +5,7 @@
 #include "ctx.h"
 #include <algorithm>
 #include <atomic>
+#include <vector>
 
 int dense_prepare(nodal_ctx *h);  // sparse.hip
 int pair_read_host(nodal_ctx *h, const double *x, int32_t ia, int32_t ib, double *out);  // sparse.hip
@@ -261,7 +262,8 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->data, &h->rhs, &h->status, &h->x, &h->dense, &h->piv, &h->work,
                       &h->work2, &h->work3, &h->solver, &h->krylov, &h->gn_indptr, &h->gn_indices,
                       &h->gn_rowidx, &h->gn_data, &h->gn_diag, &h->schur, &h->ps_buf, &h->ps_newidx,
-                      &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none};
+                      &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none,
+                      &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     h->evpool.clear();
@@ -274,7 +276,7 @@ void nodal_free_buffers(nodal_ctx *h) {
 void nodal_poison_scratch(nodal_ctx *h) {
     if (nodal_poison_level() < 2 || !h) return;
     DevBuf *bufs[] = {&h->x, &h->dense, &h->piv, &h->work, &h->work2, &h->work3, &h->solver, &h->krylov,
-                      &h->ld_work, &h->schur, &h->batch_x, &h->batch_scale, &h->rhs_none};
+                      &h->ld_work, &h->schur, &h->batch_x, &h->batch_scale, &h->rhs_none, &h->sw_blk};
     for (DevBuf *b : bufs) b->poison(h->stream);
     slu_poison(h);
     nodal_poison_scratch(h->reduced);
@@ -720,6 +722,67 @@ int nodal_solve_pairs(nodal_handle h, int32_t dense, int32_t npairs, const int32
                                     h->stream));
     NODAL_WAIT_STREAM(h, h->stream);
     return NODAL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// Arguments of a source sweep: rows in range, values uploaded, the slot map built -- and the rows checked on the device
+// to be independent sources, each named once (one read-back)
+int sweep_prepare(nodal_ctx *h, int32_t count, int32_t nsrc, const int64_t *rows, const double *values) {
+    if (count < 0 || nsrc < 0 || (nsrc > 0 && !rows) || (count > 0 && nsrc > 0 && !values))
+        return nodal_fail(h, NODAL_E_INVALID, "source sweep: bad count, rows or values");
+    if (!h->have_numeric || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "assemble_numeric not called");
+    std::vector<int32_t> r32((size_t)nsrc + 1);
+    for (int32_t j = 0; j < nsrc; ++j) {
+        if (rows[j] < 0 || rows[j] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "source sweep: row out of range");
+        r32[j] = (int32_t)rows[j];
+    }
+    NODAL_HIP_TRY(h, h->sw_rows.reserve((size_t)(nsrc + 16) * 4));
+    NODAL_HIP_TRY(h, h->sw_slot.reserve((size_t)h->ncomp * 4 + 64));
+    NODAL_HIP_TRY(h, h->sw_vals.reserve((size_t)count * nsrc * 8 + 64));
+    int32_t *rows_dev = h->sw_rows.as<int32_t>(), *bad_dev = rows_dev + ((nsrc + 15) & ~15);
+    if (nsrc > 0)
+        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nsrc * 4, hipMemcpyHostToDevice, h->stream));
+    if ((int64_t)count * nsrc > 0)
+        NODAL_HIP_TRY(h, hipMemcpyAsync(h->sw_vals.p, values, (size_t)count * nsrc * 8, hipMemcpyHostToDevice, h->stream));
+    NODAL_TRY(stamp_sweep_slots(h, rows_dev, nsrc, h->sw_slot.as<int32_t>(), bad_dev));
+    int32_t bad = 0;
+    NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the host copies above are done too)
+    if (bad & 1) return nodal_fail(h, NODAL_E_INVALID, "source sweep: a row that is not an independent source (A or E)");
+    if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, "source sweep: a row named twice");
+    return NODAL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nodal_solve_sources(nodal_handle h, int32_t dense, int32_t count, int32_t nsrc, const int64_t *rows,
+                        const double *values, double *x_out, double *resid_out, int32_t *info_out) {
+    if (!h || (count > 0 && !info_out)) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    NODAL_TRY(sweep_prepare(h, count, nsrc, rows, values));
+    if (count == 0) return NODAL_OK;
+    h->amg_levels = 0;
+    h->last_batch_block = false;
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    const int s = sparse_solve_sources(h, dense != 0, count, nsrc, h->sw_vals.as<double>(), h->sw_slot.as<int32_t>(),
+                                       x_out, resid_out, info_out);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
+int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const int64_t *rows, const double *values,
+                            double *rhs_out) {
+    if (!h || (count > 0 && !rhs_out)) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    NODAL_TRY(sweep_prepare(h, count, nsrc, rows, values));
+    return sparse_sources_rhs(h, count, nsrc, h->sw_vals.as<double>(), h->sw_slot.as<int32_t>(), rhs_out);
 }
 
 int nodal_residual(nodal_handle h, double *scaled_residual) {

@@ -188,6 +188,9 @@ struct nodal_ctx {
     bool use_presolve = true;
     bool use_graphs = false;       // hipGraph replay of the FCG iteration: measured no gain (kernels are not host-bound)
     DevBuf ps_buf, ps_newidx, ps_hits, ps_stage;
+    // source sweeps (nodal_solve_sources, sparse.hip): swept rows, their slot map, the members' values, the
+    // right-hand-side / solution blocks
+    DevBuf sw_rows, sw_slot, sw_vals, sw_blk;
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
     // matrix-only context (no component table) that inherits the grounded-node flags
     nodal_ctx *lowdeg = nullptr;
@@ -345,6 +348,16 @@ int scan_exclusive_u32(nodal_ctx *h, const uint32_t *in, uint32_t *out, int64_t 
 int stamp_symbolic(nodal_ctx *h);
 int stamp_numeric(nodal_ctx *h, int32_t member, int64_t *bad_component);
 int stamp_to_dense(nodal_ctx *h, double *G_dev, int64_t ld, bool col_major);
+// source sweeps (nodal_solve_sources): slot_dev[comp] = index of comp among the swept rows, else -1 (*bad_dev: 1 a row
+// that is not an A / E source, 2 a repeated row); then the right-hand sides of `cols` (<= 16) members whose swept
+// values are swept_dev[y * nsrc + j], element (row, y) at out[row * rs + y * cs] (rows without a source untouched)
+int stamp_sweep_slots(nodal_ctx *h, const int32_t *rows_dev, int32_t nsrc, int32_t *slot_dev, int32_t *bad_dev);
+int stamp_rhs_multi(nodal_ctx *h, const int32_t *slot_dev, const double *swept_dev, int32_t nsrc, int32_t cols,
+                    double *out, int64_t rs, int64_t cs);
+int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
+                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out);
+int sparse_sources_rhs(nodal_ctx *h, int32_t count, int32_t nsrc, const double *swept_dev, const int32_t *slot_dev,
+                       double *rhs_out);
 
 // ---- fp64 MFMA GEMM (gemm_f64.hip), column-major ----
 enum { GEMM_SUB = 0, GEMM_SET = 1, GEMM_SETNEG = 2 };  // C -= A B | C = A B | C = -A B
@@ -401,6 +414,10 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
 bool sagg_ready(nodal_ctx *h, int64_t n);  // a hierarchy for n unknowns is set up
 // up to 16 probe pairs per iteration on that hierarchy (sagg_multi.h); -1: breakdown / no convergence
 int sagg_pairs_block_width();  // pairs the block iteration takes per call (sagg_multi.h: MK)
+// up to 16 general right-hand sides B (interleaved by row, unused columns zero) on that hierarchy; each column stops on
+// |r| <= 1e-13 |b|, an all-zero one at once with x = 0; X receives the solutions in the same layout.  -1: breakdown /
+// no convergence
+int sagg_fcg_solve_block(nodal_ctx *h, int32_t count, const double *B, double *X, int32_t *iters);
 int sagg_fcg_solve_pairs_block(nodal_ctx *h, int32_t count, const int32_t *ia_host, const int32_t *ib_host,
                                double *res_dev, int32_t *iters);
 void sagg_invalidate(nodal_ctx *h);  // the hierarchy is not to be used again until the next setup

@@ -348,6 +348,24 @@ __global__ __launch_bounds__(TB) void m_init(int64_t n, const int32_t *__restric
     column_partials<2>(a, part, cap);
 }
 
+// b_y = column y of a general right-hand-side block B, interleaved by row (source sweeps, nodal_solve_sources)
+__global__ __launch_bounds__(TB) void m_init_b(int64_t n, const double *__restrict__ b, double *__restrict__ x,
+                                               double *__restrict__ r, double *__restrict__ Ap,
+                                               const double *__restrict__ dinv, cyc_t *__restrict__ x0,
+                                               double *__restrict__ part, int cap) {
+    double a[2] = {0.0, 0.0};  // r.r, x.r (x = 0)
+    const int64_t total = n * MK;
+    for (int64_t t = (int64_t)xcd_block() * TB + threadIdx.x; t < total; t += (int64_t)gridDim.x * TB) {
+        const double ri = b[t];
+        x[t] = 0.0;
+        r[t] = ri;
+        x0[t] = (cyc_t)(OMEGA * dinv[t >> MK_SHIFT] * ri);
+        Ap[t] = 0.0;
+        a[0] = fma(ri, ri, a[0]);
+    }
+    column_partials<2>(a, part, cap);
+}
+
 // tot: [0] z.r, [1] z.Ap, [2] r.r, [3] x.r per column ([4] p.Ap)
 __global__ __launch_bounds__(TB) void m_direction(const cyc_t *__restrict__ z, double *__restrict__ p,
                                                   const double *__restrict__ tot, double *__restrict__ scs, int parity,
@@ -605,18 +623,11 @@ int m_cycle(nodal_ctx *h, SHierarchy *H, const MBufs &M, int l, const TBV *b, co
 
 int sagg_pairs_block_width() { return MK; }
 
-// Pairs [0, count), count <= MK, on the hierarchy of the last setup: res_dev[q] = e(ia[q]) - e(ib[q]) for a
-// 1 A probe.  Return NODAL_OK (all columns converged), -1 breakdown / no convergence (the caller falls back
-// to the single-vector iteration and what stands behind it), > 0 a status.
-int sagg_fcg_solve_pairs_block(nodal_ctx *h, int32_t count, const int32_t *ia_host, const int32_t *ib_host,
-                               double *res_dev, int32_t *iters) {
-    const bool trace = getenv("NODAL_TRACE") != nullptr;  // (per call: tests switch it on for one sweep)
-    SHierarchy *H = hierarchy_of(h);
+namespace {
+
+// the block's buffers: one allocation in the hierarchy, grown on demand
+int m_layout(nodal_ctx *h, SHierarchy *H, MBufs &M) {
     const int64_t n = h->n;
-    hipStream_t st = h->stream;
-    if (!H->ready || H->pool[0]->n != n || count < 1 || count > MK) return -1;
-    if (H->nlev < 2 || H->tail == 0) return -1;  // (no level outside the tail: the single-vector iteration's case)
-    // ---- buffers: one allocation in the hierarchy, grown on demand ----
     size_t bytes = 0;
     auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) & ~(size_t)255; return at; };
     size_t o_vec[MAX_LEVELS], o_part[MAX_LEVELS], o_tot[MAX_LEVELS];
@@ -633,7 +644,6 @@ int sagg_fcg_solve_pairs_block(nodal_ctx *h, int32_t count, const int32_t *ia_ho
     const size_t o_pairs = take((size_t)2 * MK * 4);
     NODAL_HIP_TRY(h, H->mvec.reserve(bytes + 256));
     char *base = H->mvec.as<char>();
-    MBufs M;
     for (int l = 0; l <= last_outside && l < H->nlev; ++l) {
         M.lv[l].vec = reinterpret_cast<double *>(base + o_vec[l]);
         M.lv[l].part = reinterpret_cast<double *>(base + o_part[l]);
@@ -650,27 +660,20 @@ int sagg_fcg_solve_pairs_block(nodal_ctx *h, int32_t count, const int32_t *ia_ho
     M.ia = reinterpret_cast<int32_t *>(base + o_pairs);
     M.ib = M.ia + MK;
     M.g0 = (int)mgrid(n, MPARTS);
-    // pairs: unused columns get the pair (-1, -1): a zero right-hand side, converged at once
-    int32_t pairs[2 * MK];
-    for (int y = 0; y < MK; ++y) {
-        pairs[y] = y < count ? ia_host[y] : -1;
-        pairs[MK + y] = y < count ? ib_host[y] : -1;
-    }
-    int32_t *pin = static_cast<int32_t *>(nodal_pinned(h));
-    if (pin) memcpy(pin, pairs, sizeof pairs);
-    NODAL_HIP_TRY(h, hipMemcpyAsync(M.ia, pin ? pin : pairs, sizeof pairs, hipMemcpyHostToDevice, st));
-    if (!pin) NODAL_WAIT_STREAM(h, st);
+    return NODAL_OK;
+}
 
+// The iterations of a block whose start (x, r, x0, the r.r partials) m_init / m_init_b has left: *status 1 every column
+// converged, 2 breakdown, 3 the cap.  `what` names the block in the trace.
+int m_iterate(nodal_ctx *h, SHierarchy *H, const MBufs &M, int32_t count, bool functional, const char *what,
+              int32_t *iters, int *status_out) {
+    const bool trace = getenv("NODAL_TRACE") != nullptr;  // (per call: tests switch it on for one sweep)
+    const int64_t n = h->n;
+    hipStream_t st = h->stream;
     const SLevel *L0 = H->pool[0];
     const Ell A0 = L0->A();
     const double *dinv0 = L0->dinv.as<double>();
-    const double tol = 1e-13;
-    const bool functional = !(getenv("NODAL_PAIRS_FUNCTIONAL") && atoi(getenv("NODAL_PAIRS_FUNCTIONAL")) == 0);
     double *part_rr = M.part + (int64_t)2 * MPARTS * MK, *part_pap = M.part + (int64_t)4 * MPARTS * MK;
-    m_set_scalars<<<1, 64, 0, st>>>(M.sc, tol * tol);
-    m_init<<<M.g0, TB, 0, st>>>(n, M.ia, M.ib, M.x, M.r, M.Ap, dinv0, M.x0, part_rr, MPARTS);
-    NODAL_HIP_TRY(h, hipGetLastError());
-
     auto iteration = [&](int it) -> int {
         kcycle_schedule(H, it);  // (the K-cycle's coefficients, per column: calibrated, then frozen -- sagg.hip)
         const int mrc = m_cycle<double>(h, H, M, 0, M.r, M.x0, M.z, true);  // leaves z.r, z.Ap partials in part[0..1]
@@ -718,12 +721,75 @@ int sagg_fcg_solve_pairs_block(nodal_ctx *h, int32_t count, const int32_t *ia_ho
     if (iters) *iters = its;
     if (status == 1) H->mblock_iters = (int)enqueued, H->mblock_n = n;
     if (trace)
-        fprintf(stderr, "[sagg] block of %d pairs: %d iterations (%lld enqueued, %d polls), status %d\n", count, its,
+        fprintf(stderr, "[sagg] block of %d %s: %d iterations (%lld enqueued, %d polls), status %d\n", count, what, its,
                 (long long)enqueued, polls, status);
+    *status_out = status;
+    return NODAL_OK;
+}
+
+}  // namespace
+
+// Pairs [0, count), count <= MK, on the hierarchy of the last setup: res_dev[q] = e(ia[q]) - e(ib[q]) for a
+// 1 A probe.  Return NODAL_OK (all columns converged), -1 breakdown / no convergence (the caller falls back
+// to the single-vector iteration and what stands behind it), > 0 a status.
+int sagg_fcg_solve_pairs_block(nodal_ctx *h, int32_t count, const int32_t *ia_host, const int32_t *ib_host,
+                               double *res_dev, int32_t *iters) {
+    SHierarchy *H = hierarchy_of(h);
+    const int64_t n = h->n;
+    hipStream_t st = h->stream;
+    if (!H->ready || H->pool[0]->n != n || count < 1 || count > MK) return -1;
+    if (H->nlev < 2 || H->tail == 0) return -1;  // (no level outside the tail: the single-vector iteration's case)
+    MBufs M;
+    NODAL_TRY(m_layout(h, H, M));
+    // pairs: unused columns get the pair (-1, -1): a zero right-hand side, converged at once
+    int32_t pairs[2 * MK];
+    for (int y = 0; y < MK; ++y) {
+        pairs[y] = y < count ? ia_host[y] : -1;
+        pairs[MK + y] = y < count ? ib_host[y] : -1;
+    }
+    int32_t *pin = static_cast<int32_t *>(nodal_pinned(h));
+    if (pin) memcpy(pin, pairs, sizeof pairs);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(M.ia, pin ? pin : pairs, sizeof pairs, hipMemcpyHostToDevice, st));
+    if (!pin) NODAL_WAIT_STREAM(h, st);
+
+    const SLevel *L0 = H->pool[0];
+    const double *dinv0 = L0->dinv.as<double>();
+    const double tol = 1e-13;
+    const bool functional = !(getenv("NODAL_PAIRS_FUNCTIONAL") && atoi(getenv("NODAL_PAIRS_FUNCTIONAL")) == 0);
+    double *part_rr = M.part + (int64_t)2 * MPARTS * MK;
+    m_set_scalars<<<1, 64, 0, st>>>(M.sc, tol * tol);
+    m_init<<<M.g0, TB, 0, st>>>(n, M.ia, M.ib, M.x, M.r, M.Ap, dinv0, M.x0, part_rr, MPARTS);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    int status = 0;
+    NODAL_TRY(m_iterate(h, H, M, count, functional, "pairs", iters, &status));
     if (status != 1) return -1;
     // (x.r of the final iterates: the partials of the last m_update, every column's vectors at rest by then)
     if (functional) m_reduce_kernel<<<1, MR, 0, st>>>(part_rr + (int64_t)MPARTS * MK, MPARTS, M.g0, M.tot + 3 * MK);
     m_read_pairs<<<1, 64, 0, st>>>(count, M.ia, M.ib, M.x, functional ? M.tot + 3 * MK : nullptr, res_dev);
     NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+// Up to MK general right-hand sides (a source sweep, nodal_solve_sources) on the hierarchy of the last setup.  The
+// residual rule |r| <= 1e-13 |b| of the single-vector iteration decides every column (the functional rule stops on an
+// energy estimate, which suits a probe's one number, not a whole solution vector).  Return as above; X (interleaved,
+// n * MK doubles) is written only on NODAL_OK.
+int sagg_fcg_solve_block(nodal_ctx *h, int32_t count, const double *B, double *X, int32_t *iters) {
+    SHierarchy *H = hierarchy_of(h);
+    const int64_t n = h->n;
+    hipStream_t st = h->stream;
+    if (!H->ready || H->pool[0]->n != n || count < 1 || count > MK) return -1;
+    if (H->nlev < 2 || H->tail == 0) return -1;
+    MBufs M;
+    NODAL_TRY(m_layout(h, H, M));
+    const double tol = 1e-13;
+    double *part_rr = M.part + (int64_t)2 * MPARTS * MK;
+    m_set_scalars<<<1, 64, 0, st>>>(M.sc, tol * tol);
+    m_init_b<<<M.g0, TB, 0, st>>>(n, B, M.x, M.r, M.Ap, H->pool[0]->dinv.as<double>(), M.x0, part_rr, MPARTS);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    int status = 0;
+    NODAL_TRY(m_iterate(h, H, M, count, false, "right-hand sides", iters, &status));
+    if (status != 1) return -1;
+    NODAL_HIP_TRY(h, hipMemcpyAsync(X, M.x, (size_t)n * MK * 8, hipMemcpyDeviceToDevice, st));
     return NODAL_OK;
 }

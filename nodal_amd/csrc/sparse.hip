@@ -18,6 +18,7 @@
 // quirk 3).
 #include <chrono>
 #include <utility>
+#include <vector>
 #include <cstdio>
 #include <cstdlib>
 
@@ -681,6 +682,70 @@ __global__ __launch_bounds__(TB) void add_into(int64_t count, const double *__re
     for (int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x; e < count; e += (int64_t)gridDim.x * TB) x[e] += d[e];
 }
 
+// ---- source sweeps (sparse_solve_sources below) ----
+// NaN-keeping maximum: once a NaN is seen it stays (fmax would drop it)
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+// Per column y < cols of a block whose element (i, y) sits at [i * rs + y * cs]: r = b - G x row by row (the lanes of a
+// row share every matrix entry, as in csr_residual_multi), and the maxima out[y * 4 + 0] = |r|, [1] = |x|, [2] = |b|;
+// out[3] (column 0's slot) = max row sum |G|.  out is zeroed by the caller; non-negative doubles order like their bits
+// and a NaN's bits above every number, so the atomics keep a NaN too.
+__global__ __launch_bounds__(TB) void resid_norms_multi(int64_t n, const int32_t *__restrict__ indptr,
+                                                        const int32_t *__restrict__ indices,
+                                                        const double *__restrict__ data, const double *__restrict__ x,
+                                                        const double *__restrict__ b, int64_t rs, int64_t cs, int cols,
+                                                        double *__restrict__ out) {
+    __shared__ double red[TB / 64][SLU_MULTI][4];
+    const int y = (int)(threadIdx.x % SLU_MULTI);  // (fixed per thread: the grid stride is a multiple of 16)
+    double m[4] = {0.0, 0.0, 0.0, 0.0};
+    if (y < cols)
+        for (int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x; t < n * SLU_MULTI; t += (int64_t)gridDim.x * TB) {
+            const int64_t i = t / SLU_MULTI;
+            const double bi = b[i * rs + (int64_t)y * cs], xi = x[i * rs + (int64_t)y * cs];
+            double acc = bi, an = 0.0;
+            for (int32_t q = indptr[i]; q < indptr[i + 1]; ++q) {
+                acc = fma(-data[q], x[(int64_t)indices[q] * rs + (int64_t)y * cs], acc);
+                an += fabs(data[q]);
+            }
+            m[0] = nan_max(m[0], fabs(acc));
+            m[1] = nan_max(m[1], fabs(xi));
+            m[2] = nan_max(m[2], fabs(bi));
+            m[3] = fmax(m[3], an);
+        }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (int off = SLU_MULTI; off < 64; off <<= 1) m[k] = nan_max(m[k], __shfl_xor(m[k], off, 64));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane < SLU_MULTI)
+        for (int k = 0; k < 4; ++k) red[wave][lane][k] = m[k];
+    __syncthreads();
+    if (threadIdx.x < SLU_MULTI && (int)threadIdx.x < cols) {
+        double v[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int w = 0; w < TB / 64; ++w)
+            for (int k = 0; k < 4; ++k) v[k] = nan_max(v[k], red[w][threadIdx.x][k]);
+        for (int k = 0; k < 3; ++k) atomic_max_nonneg(&out[threadIdx.x * 4 + k], v[k]);
+        if (threadIdx.x == 0) atomic_max_nonneg(&out[3], v[3]);
+    }
+}
+// scaled[y] = |G x - b|_inf / (|G|_inf |x|_inf + |b|_inf) of column y, as csr_scaled_residual
+__global__ void scaled_from_norms(const double *__restrict__ out, int cols, double *__restrict__ scaled) {
+    const int y = threadIdx.x;
+    if (y >= cols) return;
+    const double r = out[y * 4], den = out[3] * out[y * 4 + 1] + out[y * 4 + 2];
+    scaled[y] = den > 0 ? r / den : (r == r ? 0.0 : r);
+}
+// rows[y * n + i] = X[i * 16 + y], y < cols: an interleaved block as [cols][n] rows
+__global__ __launch_bounds__(TB) void deinterleave_rows(int64_t n, int cols, const double *__restrict__ X,
+                                                        double *__restrict__ rows) {
+    for (int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x; t < n * cols; t += (int64_t)gridDim.x * TB) {
+        const int64_t y = t / n, i = t - y * n;
+        rows[t] = X[i * SLU_MULTI + y];
+    }
+}
+__global__ __launch_bounds__(TB) void fill_nan_rows(int64_t count, double *__restrict__ x) {
+    for (int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x; t < count; t += (int64_t)gridDim.x * TB)
+        x[t] = __builtin_nan("");
+}
+
 __global__ __launch_bounds__(TB) void copy_rhs_column(const double *__restrict__ rhs,
                                                       double *__restrict__ col, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB)
@@ -867,6 +932,259 @@ int sparse_solve_pairs(nodal_ctx *h, int32_t npairs, const int32_t *ia, const in
         ++q;
     }
     NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+// ---- source sweeps (nodal_solve_sources) ----------------------------------------------------------------------
+// A .dc sweep of a supply, the load vectors of an IR-drop study: G is fixed and only the independent sources change, so
+// every member is the same matrix with its own right-hand side (stamp_rhs_multi folds them, sixteen per launch).  The
+// routes mirror sparse_solve and nodal_solve_pairs, every member is judged on its own scaled residual, and at most one
+// block of work (sixteen members, or one dense chunk) sits behind any host wait.
+namespace {
+
+struct SweepCtx {
+    nodal_ctx *h;
+    int32_t nsrc;
+    const double *swept;
+    const int32_t *slot;
+    double *x_out, *resid;
+    int32_t *info;
+    double *norms;  // [16][4] maxima + [16] scaled residuals (device)
+
+    // member m0 .. m0 + cols - 1 (cols <= 16) into out[row * rs + y * cs], zeros elsewhere in an n x cols block
+    int fold(int32_t m0, int cols, double *out, int64_t rs, int64_t cs, size_t block_bytes) const {
+        NODAL_HIP_TRY(h, hipMemsetAsync(out, 0, block_bytes, h->stream));
+        return stamp_rhs_multi(h, slot, swept + (int64_t)m0 * nsrc, nsrc, cols, out, rs, cs);
+    }
+    // resid[m0 + y] for the cols columns of x / b (layout as in fold): one read-back, i.e. one wait
+    int judge(int32_t m0, int cols, const double *x, const double *b, int64_t rs, int64_t cs) const {
+        const int64_t n = h->n;
+        NODAL_HIP_TRY(h, hipMemsetAsync(norms, 0, (size_t)(4 + 1) * SLU_MULTI * 8, h->stream));
+        const unsigned g = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 1024);
+        resid_norms_multi<<<g, TB, 0, h->stream>>>(n, h->indptr.as<int32_t>(), h->indices.as<int32_t>(),
+                                                  h->data.as<double>(), x, b, rs, cs, cols, norms);
+        scaled_from_norms<<<1, 64, 0, h->stream>>>(norms, cols, norms + 4 * SLU_MULTI);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return nodal_read_words(h, resid + m0, norms + 4 * SLU_MULTI, (size_t)cols * 8);
+    }
+    // rows [cols][n] of members m0 .. to the caller, and wait
+    int hand_over(int32_t m0, int cols, const double *rows) const {
+        const int64_t n = h->n;
+        if (x_out)
+            NODAL_HIP_TRY(h, hipMemcpyAsync(x_out + (int64_t)m0 * n, rows, (size_t)cols * n * 8, hipMemcpyDeviceToHost,
+                                            h->stream));
+        NODAL_WAIT_STREAM(h, h->stream);
+        return NODAL_OK;
+    }
+    int nan_rows(double *rows, int cols) const {
+        fill_nan_rows<<<grid_rows(h->n * cols, 1), TB, 0, h->stream>>>(h->n * cols, rows);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return NODAL_OK;
+    }
+};
+
+// every member singular (a floating island, a singular G): NaN rows, info 1, as sparse_solve answers
+void sweep_all_singular(const SweepCtx &c, int32_t count) {
+    const int64_t n = c.h->n;
+    for (int32_t m = 0; m < count; ++m) {
+        c.info[m] = 1;
+        c.resid[m] = __builtin_nan("");
+    }
+    if (c.x_out)
+        for (int64_t t = 0; t < (int64_t)count * n; ++t) c.x_out[t] = __builtin_nan("");
+}
+
+}  // namespace
+
+int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
+                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out) {
+    const int64_t n = h->n;
+    hipStream_t st = h->stream;
+    std::vector<double> resid_host(resid_out ? 0 : (size_t)count);
+    for (int32_t m = 0; m < count; ++m) info_out[m] = 0;
+    h->have_x = false;
+    h->last_iterations = 0;
+    SweepCtx c{h, nsrc, swept_dev, slot_dev, x_out, resid_out ? resid_out : resid_host.data(), info_out, nullptr};
+    if (n == 0) {
+        for (int32_t m = 0; m < count; ++m) c.resid[m] = 0.0;
+        return NODAL_OK;
+    }
+    const bool passive = h->B == 0 && h->passive_network;
+    const int64_t densify_max = 4096;        // passive networks: sparse_solve's bound for the dense LU
+    const int64_t dense_general_max = 8192;  // the rest: nodal_solve_pairs' bound
+    const size_t vb = (size_t)n * SLU_MULTI * 8;
+
+    if (dense || n <= 64 || (passive && n <= densify_max) || (!passive && n <= dense_general_max)) {
+        // one LU per chunk of up to 512 members: they are extra right-hand-side columns of the augmented panel
+        const int32_t CHUNK = 512;
+        const int64_t lda = dense_lda(n);
+        const int32_t first = count < CHUNK ? count : CHUNK;
+        NODAL_HIP_TRY(h, h->sw_blk.reserve((size_t)n * first * 8 + 5 * SLU_MULTI * 8 + 256));
+        double *Bc = h->sw_blk.as<double>();  // the same columns, kept for the judgement ([m][n])
+        c.norms = Bc + (size_t)n * first;
+        for (int32_t q0 = 0; q0 < count; q0 += CHUNK) {
+            const int32_t m = count - q0 < CHUNK ? count - q0 : CHUNK;
+            NODAL_HIP_TRY(h, h->dense.reserve((size_t)lda * (size_t)(n + m) * 8 + 64));
+            NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
+            double *cols = h->dense.as<double>() + n * lda;
+            NODAL_HIP_TRY(h, hipMemsetAsync(cols, 0, (size_t)lda * m * 8, st));
+            for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
+                const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
+                NODAL_TRY(stamp_rhs_multi(h, slot_dev, swept_dev + (int64_t)(q0 + g0) * nsrc, nsrc, k, cols + g0 * lda, 1, lda));
+                NODAL_TRY(c.fold(q0 + g0, k, Bc + g0 * n, 1, n, (size_t)n * k * 8));
+            }
+            NODAL_HIP_TRY(h, h->solver.reserve((size_t)n * m * 8 + 64));
+            double *X = h->solver.as<double>();
+            int32_t inf = 0;
+            NODAL_TRY(dense_factor_solve_multi(h, m, X, n, &inf));
+            if (inf > 0) {
+                if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+                sweep_all_singular(c, count);
+                return NODAL_OK;
+            }
+            for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
+                const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
+                NODAL_TRY(c.judge(q0 + g0, k, X + g0 * n, Bc + g0 * n, 1, n));
+            }
+            NODAL_TRY(c.hand_over(q0, m, X));
+        }
+        return NODAL_OK;
+    }
+
+    // blocks interleaved by row: B, X, R, D; then [16][n] rows, one vector b, the norms
+    NODAL_HIP_TRY(h, h->sw_blk.reserve(5 * vb + (size_t)n * 8 + 5 * SLU_MULTI * 8 + 256));
+    double *Bil = h->sw_blk.as<double>(), *Xil = Bil + (size_t)n * SLU_MULTI, *Ril = Xil + (size_t)n * SLU_MULTI,
+           *Dil = Ril + (size_t)n * SLU_MULTI, *rows = Dil + (size_t)n * SLU_MULTI, *bvec = rows + (size_t)n * SLU_MULTI;
+    c.norms = bvec + n;
+    const unsigned gv = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 65536);
+
+    if (passive) {
+        // member 0 sets the multigrid hierarchy up; the others go sixteen at a time through the block iteration
+        // (sagg_multi.h).  A block that breaks down or hits its cap is redone member by member, and a member the
+        // iteration fails on -- with every later one -- by the sparse direct solve.
+        bool direct = n < h->amg_min_n, block_ok = true;
+        auto one = [&](int32_t m) -> int {  // member m alone into rows[0, n); false: singular network
+            NODAL_TRY(c.fold(m, 1, bvec, 1, 0, (size_t)n * 8));
+            int32_t inf = 0, it = 0;
+            double rs = 0.0;
+            bool done = false;
+            if (!direct) {
+                const int s = amg_fcg_solve_ex(h, bvec, m == 0, &inf, &it, &rs);
+                if (s == -2) return -2;  // floating island: every member is singular
+                if (s == NODAL_OK) {
+                    NODAL_HIP_TRY(h, hipMemcpyAsync(rows, h->x.as<double>(), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+                    done = true;
+                } else if (s < 0) {
+                    direct = true;
+                } else {
+                    return s;
+                }
+            }
+            if (!done) {
+                NODAL_TRY(sparse_direct_solve(h, bvec, rows, &inf, &it, &rs));
+                if (inf > 0) {
+                    info_out[m] = 1;
+                    NODAL_TRY(c.nan_rows(rows, 1));
+                }
+            }
+            h->last_iterations = it;
+            NODAL_TRY(c.judge(m, 1, rows, bvec, 1, 0));
+            return c.hand_over(m, 1, rows);
+        };
+        for (int32_t m0 = 0; m0 < count;) {
+            const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
+            if (m0 > 0 && !direct && block_ok && cnt >= 2 && sagg_ready(h, n)) {
+                NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
+                int32_t it = 0;
+                const int s = sagg_fcg_solve_block(h, cnt, Bil, Xil, &it);
+                if (s == NODAL_OK) {
+                    h->last_iterations = it;
+                    NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
+                    deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
+                    NODAL_HIP_TRY(h, hipGetLastError());
+                    NODAL_TRY(c.hand_over(m0, cnt, rows));
+                    m0 += cnt;
+                    continue;
+                }
+                if (s > 0) return s;
+                block_ok = false;  // (latched: a second failing block would cost its cap again for nothing)
+            }
+            const int s = one(m0);
+            if (s == -2) {
+                sweep_all_singular(c, count);
+                return NODAL_OK;
+            }
+            NODAL_TRY(s);
+            ++m0;
+        }
+        return NODAL_OK;
+    }
+
+    // Branch unknowns or a non-passive G: ONE sparse LU of the full system (no presolve), then per block of sixteen
+    // members two substitutions, one refinement step and the judgement; a member above the bar -- and every member when
+    // the factorisation had to replace pivots -- is redone alone by the sparse direct solve, which judges its own.
+    int32_t inf = 0;
+    NODAL_TRY(slu_factor(h, &inf));
+    if (inf > 0) {
+        sweep_all_singular(c, count);
+        return NODAL_OK;
+    }
+    bool all_direct = slu_perturbed(h) > 0;
+    const double bar = 1e-14;  // the backward-error bar of the refinement (sparse_general.hip)
+    for (int32_t m0 = 0; m0 < count; m0 += SLU_MULTI) {
+        const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
+        if (!all_direct) {
+            NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
+            NODAL_TRY(slu_apply_multi(h, Bil, Xil));
+            csr_residual_multi<<<gv, TB, 0, st>>>(n, h->indptr.as<int32_t>(), h->indices.as<int32_t>(), h->data.as<double>(),
+                                                 Xil, Bil, Ril);
+            NODAL_TRY(slu_apply_multi(h, Ril, Dil));
+            add_into<<<gv, TB, 0, st>>>(n * SLU_MULTI, Dil, Xil);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
+            deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            h->last_iterations = 1;
+        }
+        bool redone = false;
+        for (int y = 0; y < cnt; ++y) {
+            if (!all_direct && c.resid[m0 + y] <= bar) continue;
+            NODAL_TRY(c.fold(m0 + y, 1, bvec, 1, 0, (size_t)n * 8));
+            int32_t inf1 = 0, it = 0;
+            double rs = 0.0;
+            NODAL_TRY(sparse_direct_solve(h, bvec, rows + (size_t)y * n, &inf1, &it, &rs));
+            if (inf1 > 0) {
+                info_out[m0 + y] = 1;
+                NODAL_TRY(c.nan_rows(rows + (size_t)y * n, 1));
+            }
+            NODAL_TRY(c.judge(m0 + y, 1, rows + (size_t)y * n, bvec, 1, 0));
+            redone = true;
+        }
+        NODAL_TRY(c.hand_over(m0, cnt, rows));
+        if (redone && !all_direct) {  // (the direct solve may have factored anew, with another pivot bar)
+            NODAL_TRY(slu_factor(h, &inf));
+            all_direct = inf > 0 || slu_perturbed(h) > 0;
+        }
+    }
+    return NODAL_OK;
+}
+
+// testing hook (nodal_debug_sources_rhs): the right-hand sides the sweep builds, through the interleaved block
+int sparse_sources_rhs(nodal_ctx *h, int32_t count, int32_t nsrc, const double *swept_dev, const int32_t *slot_dev,
+                       double *rhs_out) {
+    const int64_t n = h->n;
+    if (n == 0 || count == 0) return NODAL_OK;
+    const size_t vb = (size_t)n * SLU_MULTI * 8;
+    NODAL_HIP_TRY(h, h->sw_blk.reserve(2 * vb + 256));
+    double *Bil = h->sw_blk.as<double>(), *rows = Bil + (size_t)n * SLU_MULTI;
+    SweepCtx c{h, nsrc, swept_dev, slot_dev, rhs_out, nullptr, nullptr, nullptr};
+    for (int32_t m0 = 0; m0 < count; m0 += SLU_MULTI) {
+        const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
+        NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
+        deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, h->stream>>>(n, cnt, Bil, rows);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        NODAL_TRY(c.hand_over(m0, cnt, rows));
+    }
     return NODAL_OK;
 }
 

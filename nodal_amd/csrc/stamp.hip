@@ -278,6 +278,48 @@ __global__ __launch_bounds__(TB) void fold_rhs(Table tb, const double *__restric
     }
 }
 
+// fold_rhs for up to SWEEP_COLS members of a source sweep (nodal_solve_sources): lane t folds entry t / 16 for column
+// t % 16, so the 16 lanes of an entry share each contribution read.  A component's value is the member's swept value
+// when slot[comp] >= 0 (its index among the swept rows) and the table value otherwise; the additions run in list
+// order from 0.0 with rhs_value, exactly as fold_rhs does, so column y is bit-identical to the rhs that
+// nodal_assemble_numeric builds for a table carrying member y's values.  Element (row, y) goes to out[row * rs + y * cs]
+// (rs = 16, cs = 1: interleaved by row; rs = 1, cs = ld: column-major); rows without an entry are left as they are.
+constexpr int SWEEP_COLS = 16;
+__global__ __launch_bounds__(TB) void fold_rhs_multi(Table tb, const double *__restrict__ value,
+                                                     const int32_t *__restrict__ slot, const double *__restrict__ swept,
+                                                     int32_t nsrc, int32_t cols, const int32_t *__restrict__ rhs_row,
+                                                     const int32_t *__restrict__ cptr,
+                                                     const uint32_t *__restrict__ contrib, double *__restrict__ out,
+                                                     int64_t rs, int64_t cs, int64_t nent) {
+    for (int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x; t < nent * SWEEP_COLS; t += (int64_t)gridDim.x * TB) {
+        const int64_t e = t / SWEEP_COLS;
+        const int y = (int)(t % SWEEP_COLS);
+        if (y >= cols) continue;
+        const int32_t p0 = cptr[e], p1 = cptr[e + 1];
+        double x = 0.0;
+        for (int32_t p = p0; p < p1; ++p) {
+            const uint32_t u = contrib[p];
+            const int64_t comp = u >> 3;
+            const int32_t j = slot[comp];
+            const double v = j >= 0 ? swept[(int64_t)y * nsrc + j] : value[comp];
+            x += rhs_value(tb.type[comp], (int)(u & 7u), v);
+        }
+        out[(int64_t)rhs_row[e] * rs + (int64_t)y * cs] = x;
+    }
+}
+
+// slot[rows[j]] = j for the swept rows (slot filled with -1 before); bad[0] |= 1 for a row that is not an independent
+// source, |= 2 for a row named twice
+__global__ __launch_bounds__(TB) void sweep_slots(Table tb, const int32_t *__restrict__ rows, int32_t nsrc,
+                                                  int32_t *__restrict__ slot, int32_t *__restrict__ bad) {
+    for (int32_t j = blockIdx.x * TB + threadIdx.x; j < nsrc; j += gridDim.x * TB) {
+        const int32_t r = rows[j];
+        const int t = tb.type[r];
+        if (t != NODAL_T_A && t != NODAL_T_E) atomicOr(bad, 1);
+        if (atomicExch(&slot[r], j) != -1) atomicOr(bad, 2);
+    }
+}
+
 __global__ __launch_bounds__(TB) void scatter_dense(const int32_t *__restrict__ rowidx,
                                                     const int32_t *__restrict__ indices,
                                                     const double *__restrict__ data,
@@ -422,6 +464,32 @@ int stamp_numeric(nodal_ctx *h, int32_t member, int64_t *bad_component) {
                           zero_first ? "resistor with null resistance"
                                      : "stamp collision: entry asserted zero was already written");
     }
+    return NODAL_OK;
+}
+
+int stamp_sweep_slots(nodal_ctx *h, const int32_t *rows_dev, int32_t nsrc, int32_t *slot_dev, int32_t *bad_dev) {
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "assemble_numeric not called");
+    NODAL_HIP_TRY(h, hipMemsetAsync(slot_dev, 0xFF, (size_t)h->ncomp * 4, h->stream));
+    NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, h->stream));
+    if (nsrc > 0) {
+        sweep_slots<<<grid_for(nsrc), TB, 0, h->stream>>>(table_of(h), rows_dev, nsrc, slot_dev, bad_dev);
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    return NODAL_OK;
+}
+
+int stamp_rhs_multi(nodal_ctx *h, const int32_t *slot_dev, const double *swept_dev, int32_t nsrc, int32_t cols,
+                    double *out, int64_t rs, int64_t cs) {
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "assemble_numeric not called");
+    if (cols < 1 || cols > SWEEP_COLS) return nodal_fail(h, NODAL_E_INVALID, "rhs fold: 1 to 16 columns per launch");
+    if (h->nrhs == 0) return NODAL_OK;
+    const Table tb = table_of(h);
+    // (the values of the last numeric assembly: stamp_numeric's choice)
+    const double *value = h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : tb.value;
+    fold_rhs_multi<<<grid_for(h->nrhs * SWEEP_COLS), TB, 0, h->stream>>>(
+        tb, value, slot_dev, swept_dev, nsrc, cols, h->rhs_row.as<int32_t>(), h->rhs_cptr.as<int32_t>(),
+        h->rhs_contrib.as<uint32_t>(), out, rs, cs, h->nrhs);
+    NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }
 

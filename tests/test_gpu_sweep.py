@@ -1,0 +1,249 @@
+"""Source sweeps on the GPU (Circuit.solve_sources / nodal_solve_sources): every member against the
+oracle's solve of the netlist rebuilt with that member's source values."""
+import random
+import warnings
+
+import numpy as np
+import pytest
+import scipy.sparse.linalg as spla
+
+import nodal_amd as n
+from nodal_amd import generators as gen
+from nodal_amd.circuit import MatrixRankWarning
+from nodal_amd.sweep import resolve_sources
+from oracle import nodal_oracle as oracle
+from tests.conftest import load_golden
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-9
+
+
+def normwise(x, ref):
+    x, ref = np.asarray(x, float), np.asarray(ref, float)
+    scale = np.abs(ref).max()
+    return np.abs(x - ref).max() / (scale if scale > 0 else 1.0)
+
+
+def rebuilt(rows, sources, m):
+    """rows with member m's source values (every row of a swept name)"""
+    return [[r[0], r[1], repr(float(sources[r[0]][m])), *r[3:]] if r and r[0] in sources else r for r in rows]
+
+
+def sweep_of(rows, names, M, seed):
+    rng = random.Random(seed)
+    return {name: [rng.uniform(-5.0, 5.0) for _ in range(M)] for name in names}
+
+
+def _golden_with_sources():
+    out = []
+    for case in load_golden("cases.json"):
+        if not case.get("rows") or "x" not in case.get("dense", {}) or "x" not in case.get("sparse", {}):
+            continue
+        names = sorted({r[0] for r in case["rows"] if len(r) > 1 and r[1] in ("A", "E")})
+        if names:
+            out.append((case, names))
+    return out
+
+
+GOLDEN = _golden_with_sources()
+
+
+def _random_rows(seed):
+    """a small random network: resistors on a ring with chords, A and E sources, a VCVS"""
+    rng = random.Random(seed)
+    nodes = [str(k) for k in range(1, 9)] + ["g"]
+    rows = [[f"r{k}", "R", repr(rng.uniform(0.5, 5.0)), nodes[k], nodes[(k + 1) % len(nodes)]]
+            for k in range(len(nodes))]
+    rows += [[f"c{k}", "R", repr(rng.uniform(0.5, 5.0)), nodes[rng.randrange(8)], "g"] for k in range(3)]
+    rows += [[f"a{k}", "A", repr(rng.uniform(-2, 2)), *rng.sample(nodes, 2)] for k in range(3)]
+    rows += [["e0", "E", "1.5", "s0", "g"], ["rs0", "R", "2", "s0", nodes[3]],
+             ["v0", "VCVS", "0.3", "s1", "g", nodes[1], nodes[2]], ["rs1", "R", "1", "s1", nodes[5]]]
+    return rows
+
+
+RANDOM = [_random_rows(s) for s in range(4)]
+
+
+def _oracle_x(rows, sparse):
+    G, A, _ = oracle.build_model(n.Netlist.from_rows(rows), sparse)
+    return oracle.solve(G, A, sparse)[0]
+
+
+@pytest.mark.parametrize("k", range(len(GOLDEN)), ids=[g[0]["name"] for g in GOLDEN])
+def test_rhs_fold_is_bit_identical_golden(k):
+    case, names = GOLDEN[k]
+    _check_fold(case["rows"], names, M=19, seed=k)
+
+
+@pytest.mark.parametrize("k", range(len(RANDOM)))
+def test_rhs_fold_is_bit_identical_random(k):
+    _check_fold(RANDOM[k], ["a0", "a2", "e0"], M=17, seed=100 + k)
+
+
+def _check_fold(rows, names, M, seed):
+    sources = sweep_of(rows, names, M, seed)
+    sources[names[0]][3] = 0.0
+    nl = n.Netlist.from_rows(rows)
+    c = n.Circuit(nl, sparse=True)
+    tab_rows, values = resolve_sources(nl, sources)
+    got = c._handle.debug_sources_rhs(tab_rows, values)
+    for m in range(M):
+        want = n.Circuit(n.Netlist.from_rows(rebuilt(rows, sources, m)), sparse=True).A
+        assert np.array_equal(got[m], want), m
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+def test_golden_and_random_members_match_the_oracle(sparse):
+    cases = [(case["rows"], names) for case, names in GOLDEN] + [(r, ["a0", "a1", "e0"]) for r in RANDOM]
+    for k, (rows, names) in enumerate(cases):
+        M = 5
+        sources = sweep_of(rows, names, M, 7 + k)
+        c = n.Circuit(n.Netlist.from_rows(rows), sparse=sparse)
+        sw = c.solve_sources(sources)
+        assert len(sw) == M and sw.result.shape == (M, c._handle.n)
+        assert (sw.info == 0).all()
+        for m in range(M):
+            member = rebuilt(rows, sources, m)
+            assert normwise(sw.result[m], _oracle_x(member, sparse)) <= TOL, (k, m)
+            assert sw.scaled_residual[m] <= 1e-14, (k, m, sw.scaled_residual[m])
+            alone = n.Circuit(n.Netlist.from_rows(member), sparse=sparse).solve()
+            got_lines = [line.split("\t")[0] for line in str(sw[m]).splitlines()]
+            assert got_lines == [line.split("\t")[0] for line in str(alone).splitlines()]
+
+
+def _grid_with_loads(N, nload, seed):
+    rng = random.Random(seed)
+    rows = list(gen.grid_rows(N))
+    last = N * N - 1
+    picks = rng.sample(range(1, last), nload)
+    rows += [[f"ld{j}", "A", "1", str(k + 1), "g"] for j, k in enumerate(picks)]
+    return rows, ["a1"] + [f"ld{j}" for j in range(nload)]
+
+
+@pytest.fixture(scope="module")
+def grid300():
+    rows, names = _grid_with_loads(300, 6, 3)
+    nl = n.Netlist.from_rows(rows)
+    G, A, _ = oracle.build_model(nl, True)
+    return rows, names, nl, G.tocsc()
+
+
+def _spsolve_members(G, c, tab_rows, values):
+    """spsolve of every member"""
+    out = []
+    for m in range(values.shape[0]):
+        # (the sweep's own right-hand sides: the hook is pinned bit-exact against rebuilt netlists above)
+        out.append(spla.spsolve(G, c._handle.debug_sources_rhs(tab_rows, values[m:m + 1])[0]))
+    return out
+
+
+@pytest.mark.parametrize("M", [1, 15, 16, 17, 33])
+def test_block_edges_on_a_passive_grid(grid300, M):
+    rows, names, nl, G = grid300
+    sources = sweep_of(rows, names, M, M)
+    for name in names:
+        sources[name][M // 2] = 0.0  # an all-zero member
+    c = n.Circuit(nl, sparse=True)
+    sw = c.solve_sources(sources)
+    assert (sw.info == 0).all()
+    tab_rows, values = resolve_sources(nl, sources)
+    for m, xo in enumerate(_spsolve_members(G, c, tab_rows, values)):
+        assert normwise(sw.result[m], xo) <= TOL, m
+    assert np.array_equal(sw.result[M // 2], np.zeros(c._handle.n))
+    assert (sw.scaled_residual <= 1e-12).all()
+
+
+def test_block_failure_falls_back(grid300, monkeypatch):
+    rows, names, nl, G = grid300
+    M = 20
+    sources = sweep_of(rows, names, M, 11)
+    c = n.Circuit(nl, sparse=True)
+    monkeypatch.setenv("NODAL_FCG_MAXIT", "3")
+    sw = c.solve_sources(sources)
+    monkeypatch.delenv("NODAL_FCG_MAXIT")
+    assert (sw.info == 0).all()
+    tab_rows, values = resolve_sources(nl, sources)
+    for m, xo in enumerate(_spsolve_members(G, c, tab_rows, values)):
+        assert normwise(sw.result[m], xo) <= TOL, m
+
+
+def test_lu_route_on_a_network_with_branches():
+    rows = gen.cfg5_rows(95)  # 9025 grid nodes plus branches: above 8192 unknowns, not passive
+    nl = n.Netlist.from_rows(rows)
+    names = sorted(r[0] for r in rows if r[1] == "E")
+    M = 18
+    sources = sweep_of(rows, names, M, 5)
+    c = n.Circuit(nl, sparse=True)
+    assert c._handle.n > 8192
+    sw = c.solve_sources(sources)
+    assert (sw.info == 0).all()
+    assert (sw.scaled_residual <= 1e-14).all(), sw.scaled_residual.max()
+    G, _, _ = oracle.build_model(nl, True)
+    G = G.tocsc()
+    tab_rows, values = resolve_sources(nl, sources)
+    for m, xo in enumerate(_spsolve_members(G, c, tab_rows, values)):
+        assert normwise(sw.result[m], xo) <= TOL, m
+    # the members' A really are the rebuilt netlists' (two of them through the front end)
+    for m in (0, M - 1):
+        A = n.Circuit(n.Netlist.from_rows(rebuilt(rows, sources, m)), sparse=True).A
+        assert normwise(sw.result[m], spla.spsolve(G, A)) <= TOL
+
+
+def test_floating_island():
+    rows = list(gen.grid_rows(70))
+    rows += [[f"f{i}", "R", "1", f"x{i}", f"x{i + 1}"] for i in range(40)]
+    rows += [["fa", "A", "1", "x3", "x17"]]
+    sources = {"a1": [1.0, 2.0, 3.0], "fa": [0.5, 0.0, 1.0]}
+    nl = n.Netlist.from_rows(rows)
+    c = n.Circuit(nl, sparse=True)
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        sw = c.solve_sources(sources)
+    assert np.isnan(sw.result).all() and (sw.info > 0).all()
+    assert sum(issubclass(i.category, MatrixRankWarning) for i in w) == 1
+    small = list(gen.grid_rows(6)) + rows[-41:]  # a small version for the dense path
+    cd = n.Circuit(n.Netlist.from_rows(small), sparse=False)
+    with pytest.raises((np.linalg.LinAlgError, n.UnconnectedCircuitError)):
+        cd.solve_sources({"fa": [1.0, 2.0]})
+
+
+@pytest.mark.parametrize("sparse,N", [(False, 10), (True, 10), (True, 120)])
+def test_state_is_untouched(sparse, N):
+    rows, names = _grid_with_loads(N, 3, N)
+    c = n.Circuit(n.Netlist.from_rows(rows), sparse=sparse)
+    x0 = c.solve().result.copy()
+    A0 = np.array(c.A, copy=True)
+    sw = c.solve_sources(sweep_of(rows, names, 18, 1))
+    assert len(sw) == 18
+    assert np.array_equal(c.solve().result, x0)
+    c2 = n.Circuit(n.Netlist.from_rows(rows), sparse=sparse)
+    assert np.array_equal(np.asarray(c2.A), A0)
+    assert np.array_equal(np.asarray(c._handle.export_csr()[3]), A0)
+
+
+def test_invalid_rows_are_refused_by_the_library():
+    from nodal_amd import _ffi
+    c = n.Circuit(n.Netlist.from_rows(_random_rows(0)), sparse=True)
+    h = c._handle
+    ok = resolve_sources(c.netlist, {"a0": [1.0]})[0]
+    for bad in ([0], [ok[0], ok[0]], [10 ** 6]):  # a resistor, a repeated row, out of range
+        with pytest.raises(_ffi.NodalHipError) as exc:
+            h.solve_sources(np.array(bad), np.ones((1, len(bad))), dense=False)
+        assert exc.value.status == _ffi.E_INVALID
+    assert c.solve_sources({"a0": []}).result.shape == (0, h.n)
+
+
+def test_full_size_grid1000_sixteen_load_vectors():
+    N = 1000
+    rows, names = _grid_with_loads(N, 8, 1000)
+    nl = n.Netlist.from_rows(rows)
+    M = 16
+    sources = sweep_of(rows, names, M, 2)
+    c = n.Circuit(nl, sparse=True)
+    sw = c.solve_sources(sources)
+    assert (sw.info == 0).all()
+    assert (sw.scaled_residual <= 1e-12).all(), sw.scaled_residual.max()
+    for m in (0, M - 1):
+        x = n.Circuit(n.Netlist.from_rows(rebuilt(rows, sources, m)), sparse=True).solve().result
+        assert normwise(sw.result[m], x) <= TOL, m
