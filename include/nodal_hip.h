@@ -157,6 +157,38 @@ int nodal_solve_pairs(nodal_handle h, int32_t dense, int32_t npairs, const int32
 int nodal_solve_sources(nodal_handle h, int32_t dense, int32_t count, int32_t nsrc, const int64_t *rows,
                         const double *values, double *x_out, double *resid_out, int32_t *info_out);
 
+/* ---- branch currents and power (replaces a Python loop over Solution.result after Circuit.solve, reference
+ *      nodal/nodal.py:313-336: the reference answers with potentials and branch unknowns only) ---------------
+ * For the solution on the device, per table row i (the order of nodal_upload_components), e(-1) = +0.0:
+ *   voltage[i] = e(a_i) - e(b_i);
+ *   current[i] = voltage[i] / value_i for a resistor (one division; it flows from lead a to lead b), value_i for a
+ *                current source, x[K + k_i] for the rows that own a branch unknown (E, VCVS, CCVS, CCCS).  For
+ *                every type but R it flows from b to a inside the component, into node a (the reference's stamps:
+ *                A[a] += J, G[a, K + k] = -1);
+ *   power[i]   = what the row absorbs: voltage * current for a resistor, -(voltage * current) otherwise.
+ * value_i is the value the last nodal_assemble_numeric used (its member of an uploaded value table).
+ * totals2 = {sum of power over the resistors, sum over every other row}: Tellegen's theorem makes them cancel.
+ * The sums have a fixed shape and use no atomics: a repeated call gives the same bits.  Each array may be NULL.
+ * Where x holds NaN (a singular sparse system) so does everything that reads it.  NODAL_E_INVALID: no solution
+ * on the handle (no solve yet, or a sweep since), or no component table. */
+int nodal_branches(nodal_handle h, double *voltage, double *current, double *power, double *totals2);
+
+/* ---- worst-case envelope of a source sweep (replaces the same loop over every member's Solution.result, reference
+ *      nodal/nodal.py:313-336, per member of the loop nodal_solve_sources replaces) ---------------------------
+ * The arguments and results of nodal_solve_sources, plus, over the members m with info_out[m] == 0:
+ *   current_absmax [ncomp] = max_m |current_m[i]| (current as in nodal_branches; a swept current source counts
+ *                            with its member's value), current_member [ncomp] a member that attains it;
+ *   potential_min / potential_max [K] over x_m[j], j < K, with potential_min_member / potential_max_member [K];
+ *   power_out [count][2]   = {dissipated, absorbed by the sources} of member m; NaN for a member that is left out.
+ * Among exact ties the lowest member index is reported.  With every member left out (or count == 0): NaN and -1.
+ * Each output may be NULL; with x_out == NULL no count x n array exists on the host at all -- the envelope is
+ * accumulated on the device as each block of up to sixteen members is finished. */
+int nodal_solve_sources_branches(nodal_handle h, int32_t dense, int32_t count, int32_t nsrc, const int64_t *rows,
+                                 const double *values, double *x_out, double *resid_out, int32_t *info_out,
+                                 double *current_absmax, int32_t *current_member, double *potential_min,
+                                 int32_t *potential_min_member, double *potential_max, int32_t *potential_max_member,
+                                 double *power_out);
+
 /* scaled residual ||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the
  * solution currently on the device, computed on the device from the CSR form */
 int nodal_residual(nodal_handle h, double *scaled_residual);

@@ -14,3 +14,4 @@ from nodal_amd import (  # noqa: F401  (the names the reference's `from .nodal i
     find_ground_node,
     is_connected,
 )
+from nodal_amd import Branches, Envelope  # noqa: F401  (additions the reference does not have: nodal_amd/branches.py)

@@ -9,3 +9,4 @@ from .netlist import (  # noqa: F401
     is_connected,
 )
 from .circuit import Circuit, Solution  # noqa: E402,F401
+from .branches import Branches, Envelope  # noqa: E402,F401

@@ -48,6 +48,9 @@ SIGNATURES = {
     "nodal_solve_pairs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p]),
     "nodal_solve_sources": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i64p, _f64p, _f64p, _f64p,
                                       _i32p]),
+    "nodal_branches": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p, _f64p]),
+    "nodal_solve_sources_branches": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i64p, _f64p, _f64p, _f64p,
+                                               _i32p, _f64p, _i32p, _f64p, _i32p, _f64p, _i32p, _f64p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
     "nodal_run_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _i32p]),
@@ -166,6 +169,7 @@ class Handle:
                 status, f"nodal_create(device={device}) failed: no usable MI355X "
                 "(HIP device) is visible; nodal_amd has no CPU fallback")
         self.n = self.nnz = self.ncontrib = 0
+        self._ncomp = self._K = 0
         # upload() keeps the table's columns alive (self._keep) until the next upload: the library may read them in place
         self.lib.nodal_set_option(self._h, OPT_BORROW_TABLE, 1)
         _live.add(self)
@@ -195,6 +199,7 @@ class Handle:
         t, v, a, b = cols[:4]
         rest = [_ptr(x, C.c_int32) for x in cols[4:]] or [None] * 4
         self.n_members = table.K + table.B
+        self._ncomp, self._K = int(table.ncomp), int(table.K)
         self._check(self.lib.nodal_upload_components(
             self._h, table.ncomp, _ptr(t, C.c_uint8), _ptr(v, C.c_double),
             _ptr(a, C.c_int32), _ptr(b, C.c_int32), *rest, table.K, table.B))
@@ -284,6 +289,39 @@ class Handle:
                                                  _ptr(values, C.c_double), _ptr(x, C.c_double),
                                                  _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
         return x, info, resid
+
+    def solve_sources_branches(self, rows, values, dense, keep_solutions=True):
+        """solve_sources plus the sweep's worst-case envelope, accumulated on the device.  Returns
+        (x [M, n] or None, info, scaled residual, envelope dict: current_absmax / current_member [ncomp],
+        potential_min / potential_min_member / potential_max / potential_max_member [K], power [M, 2]).  With
+        keep_solutions False no [M, n] array is allocated anywhere on the host."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.ndim == 2 and values.shape[1] == len(rows)
+        count = values.shape[0]
+        ncomp, K = self._ncomp, self._K
+        x = np.empty((count, self.n), dtype=np.float64) if keep_solutions else None
+        info = np.zeros(count, dtype=np.int32)
+        resid = np.zeros(count, dtype=np.float64)
+        env = {"current_absmax": np.empty(ncomp), "current_member": np.empty(ncomp, dtype=np.int32),
+               "potential_min": np.empty(K), "potential_min_member": np.empty(K, dtype=np.int32),
+               "potential_max": np.empty(K), "potential_max_member": np.empty(K, dtype=np.int32),
+               "power": np.empty((count, 2))}
+        self._check(self.lib.nodal_solve_sources_branches(
+            self._h, int(dense), count, len(rows), _ptr(rows, C.c_int64), _ptr(values, C.c_double),
+            _ptr(x, C.c_double) if keep_solutions else None, _ptr(resid, C.c_double), _ptr(info, C.c_int32),
+            *(_ptr(env[key], C.c_int32 if key.endswith("member") else C.c_double) for key in env)))
+        return x, info, resid, env
+
+    def branches(self, voltage=True, current=True, power=True):
+        """Branch quantities of the solution on the device, in table row order: (voltage, current, power,
+        dissipated, absorbed_by_sources); an array that is not asked for is None.  NodalHipError(E_INVALID) when
+        the handle holds no solution."""
+        out = [host_empty(self._ncomp, np.float64) if want else None for want in (voltage, current, power)]
+        totals = np.zeros(2)
+        self._check(self.lib.nodal_branches(self._h, *(_ptr(a, C.c_double) if a is not None else None for a in out),
+                                            _ptr(totals, C.c_double)))
+        return out[0], out[1], out[2], float(totals[0]), float(totals[1])
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

@@ -204,7 +204,21 @@ class Circuit:
                 raise np.linalg.LinAlgError("Singular matrix")
         return Solution(e, self.netlist, self.currents)
 
-    def solve_sources(self, sources):
+    def branches(self):
+        """Voltage, current and absorbed power of every component for the last solve()'s solution, computed
+        on the device (nodal_branches): a Branches (branches.py), arrays in the order of
+        `netlist.component_keys`.  Raises ValueError when there is no solution on the device: before the
+        first solve(), or after a solve_sources() (a sweep does not keep the single solve's solution)."""
+        from .branches import Branches
+        try:
+            v, i, p, dissipated, absorbed = self._handle.branches()
+        except _ffi.NodalHipError as exc:
+            if exc.status != _ffi.E_INVALID:
+                raise
+            raise ValueError("no solution: call solve() first") from None
+        return Branches(self.netlist, v, i, p, dissipated, absorbed, table=self.table)
+
+    def solve_sources(self, sources, branches=False, keep_solutions=True):
         """Solve the circuit for many settings of its independent sources at once.
 
         `sources` maps names of A / E components to sequences of M values (every sequence the same
@@ -213,15 +227,30 @@ class Circuit:
         the device.  Returns a SourceSweep (sweep.py): `result` [M, K+B], `sw[m]` the Solution of
         member m, `info`, `scaled_residual`.  Singular networks behave as in solve(): the dense path
         raises LinAlgError / UnconnectedCircuitError once, the sparse path returns NaN rows with
-        info > 0 and warns once.  The circuit itself (its table, G, A) is left as it was."""
-        from .sweep import SourceSweep, resolve_sources
+        info > 0 and warns once.  The circuit itself (its table, G, A) is left as it was.
+
+        branches=True adds `sw.envelope` (branches.Envelope): per component the largest |current| any solved
+        member drives through it, per node the lowest and highest potential, each with a member that attains
+        it, and the members' power totals -- accumulated on the device block by block.  With
+        keep_solutions=False (needs branches=True) the members' solutions are not brought to the host at
+        all: `sw.result` is None and the envelope is the answer."""
+        from .sweep import SourceSweep, check_sweep_options, resolve_sources
+        check_sweep_options(branches, keep_solutions)
         rows, values = resolve_sources(self.netlist, sources)
         h = self._handle
-        if values.shape[0] == 0:
-            return SourceSweep(np.zeros((0, h.n)), np.zeros(0, dtype=np.int32), np.zeros(0), self.netlist,
-                               self.currents)
+        M = values.shape[0]
+        if M == 0:
+            from .branches import Envelope
+            return SourceSweep(np.zeros((0, h.n)) if keep_solutions else None, np.zeros(0, dtype=np.int32), np.zeros(0),
+                               self.netlist, self.currents,
+                               envelope=Envelope.empty(self.netlist, self.table.ncomp) if branches else None)
+        env = None
         try:
-            x, info, resid = h.solve_sources(rows, values, dense=not self.sparse)
+            if branches:
+                x, info, resid, env = h.solve_sources_branches(rows, values, dense=not self.sparse,
+                                                               keep_solutions=keep_solutions)
+            else:
+                x, info, resid = h.solve_sources(rows, values, dense=not self.sparse)
         except _ffi.NodalHipError as exc:
             if exc.status != _ffi.E_SINGULAR or self.sparse:
                 raise
@@ -232,7 +261,12 @@ class Circuit:
             raise np.linalg.LinAlgError("Singular matrix")
         if (info > 0).any():
             warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
-        return SourceSweep(x, info, resid, self.netlist, self.currents)
+        if env is not None:
+            from .branches import Envelope
+            env = Envelope(self.netlist, env["current_absmax"], env["current_member"], env["potential_min"],
+                           env["potential_min_member"], env["potential_max"], env["potential_max_member"],
+                           env["power"][:, 0].copy(), env["power"][:, 1].copy())
+        return SourceSweep(x, info, resid, self.netlist, self.currents, envelope=env)
 
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last

@@ -263,7 +263,8 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->work2, &h->work3, &h->solver, &h->krylov, &h->gn_indptr, &h->gn_indices,
                       &h->gn_rowidx, &h->gn_data, &h->gn_diag, &h->schur, &h->ps_buf, &h->ps_newidx,
                       &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none,
-                      &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk};
+                      &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk, &h->br_out, &h->br_part, &h->br_tot,
+                      &h->br_env};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     h->evpool.clear();
@@ -759,21 +760,51 @@ extern "C" {
 
 int nodal_solve_sources(nodal_handle h, int32_t dense, int32_t count, int32_t nsrc, const int64_t *rows,
                         const double *values, double *x_out, double *resid_out, int32_t *info_out) {
+    return nodal_solve_sources_branches(h, dense, count, nsrc, rows, values, x_out, resid_out, info_out, nullptr, nullptr,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int nodal_solve_sources_branches(nodal_handle h, int32_t dense, int32_t count, int32_t nsrc, const int64_t *rows,
+                                 const double *values, double *x_out, double *resid_out, int32_t *info_out,
+                                 double *current_absmax, int32_t *current_member, double *potential_min,
+                                 int32_t *potential_min_member, double *potential_max, int32_t *potential_max_member,
+                                 double *power_out) {
     if (!h || (count > 0 && !info_out)) return NODAL_E_INVALID;
     DeviceGuard g(h);
     if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
     nodal_poison_scratch(h);
     NODAL_TRY(sweep_prepare(h, count, nsrc, rows, values));
-    if (count == 0) return NODAL_OK;
+    BranchSweep env;
+    env.out_absmax = current_absmax;
+    env.out_absmax_member = current_member;
+    env.out_pmin = potential_min;
+    env.out_pmin_member = potential_min_member;
+    env.out_pmax = potential_max;
+    env.out_pmax_member = potential_max_member;
+    env.out_power = power_out;
+    const bool want_env = current_absmax || current_member || potential_min || potential_min_member || potential_max ||
+                          potential_max_member || power_out;
+    if (count == 0) return want_env ? branch_sweep_finish(h, &env, 0, info_out) : NODAL_OK;  // (NaN and -1 throughout)
     h->amg_levels = 0;
     h->last_batch_block = false;
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
-    const int s = sparse_solve_sources(h, dense != 0, count, nsrc, h->sw_vals.as<double>(), h->sw_slot.as<int32_t>(),
-                                       x_out, resid_out, info_out);
+    if (want_env) NODAL_TRY(branch_sweep_begin(h, &env, count));
+    int s = sparse_solve_sources(h, dense != 0, count, nsrc, h->sw_vals.as<double>(), h->sw_slot.as<int32_t>(), x_out,
+                                 resid_out, info_out, want_env ? &env : nullptr);
+    if (s == NODAL_OK && want_env) s = branch_sweep_finish(h, &env, count, info_out);
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[2] = elapsed(h, 0, 1);
     return s;
+}
+
+int nodal_branches(nodal_handle h, double *voltage, double *current, double *power, double *totals2) {
+    if (!h) return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "branches: no component table on the handle");
+    if (!h->have_numeric || !h->have_x) return nodal_fail(h, NODAL_E_INVALID, "branches: no solution on the handle");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    return branch_single(h, voltage, current, power, totals2);
 }
 
 int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const int64_t *rows, const double *values,

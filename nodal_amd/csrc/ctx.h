@@ -191,6 +191,9 @@ struct nodal_ctx {
     // source sweeps (nodal_solve_sources, sparse.hip): swept rows, their slot map, the members' values, the
     // right-hand-side / solution blocks
     DevBuf sw_rows, sw_slot, sw_vals, sw_blk;
+    // branch quantities (branch.hip): voltage / current / power on their way to the host, the workgroups' power
+    // partials (+ the two totals of a single solution), a sweep's totals [count][2], a sweep's envelope arrays
+    DevBuf br_out, br_part, br_tot, br_env;
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
     // matrix-only context (no component table) that inherits the grounded-node flags
     nodal_ctx *lowdeg = nullptr;
@@ -354,10 +357,27 @@ int stamp_to_dense(nodal_ctx *h, double *G_dev, int64_t ld, bool col_major);
 int stamp_sweep_slots(nodal_ctx *h, const int32_t *rows_dev, int32_t nsrc, int32_t *slot_dev, int32_t *bad_dev);
 int stamp_rhs_multi(nodal_ctx *h, const int32_t *slot_dev, const double *swept_dev, int32_t nsrc, int32_t cols,
                     double *out, int64_t rs, int64_t cs);
+// (env: the worst-case envelope of the sweep is kept on the device as the blocks are handed over, branch.hip; may be null)
+struct BranchSweep;
 int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
-                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out);
+                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out,
+                         const BranchSweep *env = nullptr);
 int sparse_sources_rhs(nodal_ctx *h, int32_t count, int32_t nsrc, const double *swept_dev, const int32_t *slot_dev,
                        double *rhs_out);
+
+// ---- branch currents, power, sweep envelopes (branch.hip) ----
+// the envelope of one source sweep: device arrays (branch_sweep_begin sets them) and the caller's host arrays (any null)
+struct BranchSweep {
+    double *absmax = nullptr, *pmin = nullptr, *pmax = nullptr, *partials = nullptr, *totals = nullptr;
+    int32_t *absmax_member = nullptr, *pmin_member = nullptr, *pmax_member = nullptr;
+    double *out_absmax = nullptr, *out_pmin = nullptr, *out_pmax = nullptr, *out_power = nullptr;
+    int32_t *out_absmax_member = nullptr, *out_pmin_member = nullptr, *out_pmax_member = nullptr;
+};
+int branch_single(nodal_ctx *h, double *voltage, double *current, double *power, double *totals2);
+int branch_sweep_begin(nodal_ctx *h, BranchSweep *env, int32_t count);
+int branch_sweep_block(nodal_ctx *h, const BranchSweep *env, int32_t m0, int cols, const double *rows,
+                       const int32_t *info, const double *swept_dev, const int32_t *slot_dev, int32_t nsrc);
+int branch_sweep_finish(nodal_ctx *h, const BranchSweep *env, int32_t count, const int32_t *info);
 
 // ---- fp64 MFMA GEMM (gemm_f64.hip), column-major ----
 enum { GEMM_SUB = 0, GEMM_SET = 1, GEMM_SETNEG = 2 };  // C -= A B | C = A B | C = -A B

@@ -950,6 +950,7 @@ struct SweepCtx {
     double *x_out, *resid;
     int32_t *info;
     double *norms;  // [16][4] maxima + [16] scaled residuals (device)
+    const BranchSweep *env = nullptr;  // the sweep's envelope (branch.hip), fed block by block below
 
     // member m0 .. m0 + cols - 1 (cols <= 16) into out[row * rs + y * cs], zeros elsewhere in an n x cols block
     int fold(int32_t m0, int cols, double *out, int64_t rs, int64_t cs, size_t block_bytes) const {
@@ -967,9 +968,11 @@ struct SweepCtx {
         NODAL_HIP_TRY(h, hipGetLastError());
         return nodal_read_words(h, resid + m0, norms + 4 * SLU_MULTI, (size_t)cols * 8);
     }
-    // rows [cols][n] of members m0 .. to the caller, and wait
+    // rows [cols][n] of members m0 .. to the caller, and wait.  Every route ends here with the members' final rows
+    // on the device and their info flags settled: the one place the envelope looks at them.
     int hand_over(int32_t m0, int cols, const double *rows) const {
         const int64_t n = h->n;
+        if (env) NODAL_TRY(branch_sweep_block(h, env, m0, cols, rows, info, swept, slot, nsrc));
         if (x_out)
             NODAL_HIP_TRY(h, hipMemcpyAsync(x_out + (int64_t)m0 * n, rows, (size_t)cols * n * 8, hipMemcpyDeviceToHost,
                                             h->stream));
@@ -997,14 +1000,15 @@ void sweep_all_singular(const SweepCtx &c, int32_t count) {
 }  // namespace
 
 int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
-                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out) {
+                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out,
+                         const BranchSweep *env) {
     const int64_t n = h->n;
     hipStream_t st = h->stream;
     std::vector<double> resid_host(resid_out ? 0 : (size_t)count);
     for (int32_t m = 0; m < count; ++m) info_out[m] = 0;
     h->have_x = false;
     h->last_iterations = 0;
-    SweepCtx c{h, nsrc, swept_dev, slot_dev, x_out, resid_out ? resid_out : resid_host.data(), info_out, nullptr};
+    SweepCtx c{h, nsrc, swept_dev, slot_dev, x_out, resid_out ? resid_out : resid_host.data(), info_out, nullptr, env};
     if (n == 0) {
         for (int32_t m = 0; m < count; ++m) c.resid[m] = 0.0;
         return NODAL_OK;

@@ -69,24 +69,34 @@ def resolve_sources(netlist, sources):
     return np.asarray(rows, dtype=np.int64), values
 
 
+def check_sweep_options(branches, keep_solutions):
+    """The argument rule of Circuit.solve_sources: without the members' solutions the envelope is the only answer."""
+    if not keep_solutions and not branches:
+        raise ValueError("keep_solutions=False needs branches=True: the sweep would return nothing")
+
+
 class SourceSweep:
     """Result of Circuit.solve_sources: `result[m]` is what `Circuit(netlist with member m's source
     values).solve().result` gives; `sw[m]` is that Solution; `info[m]` 0 solved, > 0 singular
     (sparse path: a NaN row); `scaled_residual[m]` = ||G x_m - A_m||_inf / (||G||_inf ||x_m||_inf +
-    ||A_m||_inf), computed on the device."""
+    ||A_m||_inf), computed on the device.  `envelope` (solve_sources(branches=True)): the worst case over
+    the members, a branches.Envelope, else None.  A sweep made with keep_solutions=False has `result` None."""
 
-    def __init__(self, result, info, scaled_residual, netlist, currents):
+    def __init__(self, result, info, scaled_residual, netlist, currents, envelope=None):
         self.result = result
         self.info = info
         self.scaled_residual = scaled_residual
+        self.envelope = envelope
         self._netlist = netlist
         self._currents = currents
 
     def __len__(self):
-        return len(self.result)
+        return len(self.info)
 
     def __getitem__(self, m):
         from .circuit import Solution
+        if self.result is None:
+            raise ValueError("the sweep was made with keep_solutions=False: no member solutions were kept")
         return Solution(self.result[m], self._netlist, self._currents)
 
     def __iter__(self):
