@@ -189,6 +189,23 @@ int nodal_solve_sources_branches(nodal_handle h, int32_t dense, int32_t count, i
                                  int32_t *potential_min_member, double *potential_max, int32_t *potential_max_member,
                                  double *power_out);
 
+/* ---- adjoint sensitivities (replaces a finite-difference loop of Circuit(netlist with one value nudged) + .solve(),
+ *      reference nodal/nodal.py:306-336, two solves per component; the reference has no derivative of its own) ----
+ * For the solution on the device and `count` outputs y_q = c_q^T x, the derivative of every output with respect to the
+ * value of EVERY table row (the values the last nodal_assemble_numeric used): one solve with G^T per output, sixteen
+ * outputs to a block, and one pass over the component table per block (csrc/sensitivity.hip states the per-row formulas).
+ * kind[q] 0: y = e(p[q]) - e(q2[q]) (node indices, -1 ground); 1: y = current of table row p[q] (as nodal_branches;
+ *            q2[q] is ignored).  The current of a current source is its value: NODAL_E_INVALID.
+ * sens_out [count][ncomp] row-major; value_out [count] = y itself (may be NULL); adjoint_out [count][n] = the lambda of
+ * G^T lambda = c (may be NULL); resid_out [count] = ||G^T lambda - c||_inf / (||G||_1 ||lambda||_inf + ||c||_inf),
+ * computed on the device (may be NULL); info_out [count] as nodal_solve_sources: > 0 a singular network (rows of
+ * NaNs, status OK) -- except with dense != 0, where a singular G returns NODAL_E_SINGULAR.
+ * Needs the solution of a single solve on the handle (NODAL_E_INVALID otherwise, as nodal_branches) and leaves the handle
+ * as it found it: the solution, the table, G, A.  No floating-point atomics: a repeated call gives the same bits. */
+int nodal_sensitivities(nodal_handle h, int32_t dense, int32_t count, const int32_t *kind, const int32_t *p,
+                        const int32_t *q2, double *sens_out, double *value_out, double *adjoint_out,
+                        double *resid_out, int32_t *info_out);
+
 /* scaled residual ||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the
  * solution currently on the device, computed on the device from the CSR form */
 int nodal_residual(nodal_handle h, double *scaled_residual);

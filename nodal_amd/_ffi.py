@@ -51,6 +51,8 @@ SIGNATURES = {
     "nodal_branches": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p, _f64p]),
     "nodal_solve_sources_branches": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i64p, _f64p, _f64p, _f64p,
                                                _i32p, _f64p, _i32p, _f64p, _i32p, _f64p, _i32p, _f64p]),
+    "nodal_sensitivities": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p,
+                                      _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
     "nodal_run_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _i32p]),
@@ -322,6 +324,31 @@ class Handle:
         self._check(self.lib.nodal_branches(self._h, *(_ptr(a, C.c_double) if a is not None else None for a in out),
                                             _ptr(totals, C.c_double)))
         return out[0], out[1], out[2], float(totals[0]), float(totals[1])
+
+    def sensitivities(self, kind, p, q2, dense, adjoints=False, out=None):
+        """Adjoint sensitivities of the outputs (kind, p, q2) (sensitivity.resolve_outputs) for the solution on the
+        device.  Returns (values [M, ncomp], output values [M], adjoints [M, n] or None, scaled residual [M], info
+        [M]); NodalHipError(E_INVALID) when the handle holds no solution, with dense a singular G raises
+        NodalHipError(E_SINGULAR).  `out`: a C-contiguous float64 [M, ncomp] array to receive the values (a caller
+        that repeats the call keeps one page-locked array instead of locking a new one every time)."""
+        kind, p, q2 = (np.ascontiguousarray(v, dtype=np.int32) for v in (kind, p, q2))
+        count = len(kind)
+        assert len(p) == count and len(q2) == count
+        if out is not None:
+            assert out.shape == (count, self._ncomp) and out.dtype == np.float64 and out.flags.c_contiguous
+            sens = out
+        else:
+            # (page-locked when large: the blocks come down by plain DMA)
+            sens = host_empty(count * self._ncomp, np.float64).reshape(count, self._ncomp)
+        lam = host_empty(count * self.n, np.float64).reshape(count, self.n) if adjoints else None
+        y = np.zeros(count, dtype=np.float64)
+        resid = np.zeros(count, dtype=np.float64)
+        info = np.zeros(count, dtype=np.int32)
+        self._check(self.lib.nodal_sensitivities(
+            self._h, int(dense), count, _ptr(kind, C.c_int32), _ptr(p, C.c_int32), _ptr(q2, C.c_int32),
+            _ptr(sens, C.c_double), _ptr(y, C.c_double), _ptr(lam, C.c_double) if adjoints else None,
+            _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
+        return sens, y, lam, resid, info
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

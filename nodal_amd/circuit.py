@@ -268,6 +268,38 @@ class Circuit:
                            env["power"][:, 0].copy(), env["power"][:, 1].copy())
         return SourceSweep(x, info, resid, self.netlist, self.currents, envelope=env)
 
+    def sensitivities(self, outputs, adjoints=False):
+        """Derivatives of chosen outputs of the last solve()'s solution with respect to the value of every
+        component, by the adjoint method on the device (nodal_sensitivities): one solve with G^T per
+        output, sixteen outputs to a block, and one pass over the component table per block.
+
+        `outputs` is a sequence of ("e", node), ("v", node_plus, node_minus) or ("i", component)
+        (sensitivity.resolve_outputs).  Returns a Sensitivities (sensitivity.py): `values` [M, ncomp] in
+        the order of `netlist.component_keys`, `output_values` [M], `info`, `scaled_residual`, and with
+        adjoints=True `adjoints` [M, K+B].  Raises ValueError when there is no solution on the device, as
+        branches() does.  Singular networks behave as in solve_sources(): the dense path raises
+        LinAlgError / UnconnectedCircuitError, the sparse path returns NaN rows with info > 0 and warns
+        once.  The circuit itself -- its solution, table, G, A -- is left as it was."""
+        from .sensitivity import Sensitivities, resolve_outputs
+        outputs = list(outputs)
+        kind, p, q2 = resolve_outputs(self.netlist, outputs)
+        h = self._handle
+        try:
+            values, y, lam, resid, info = h.sensitivities(kind, p, q2, dense=not self.sparse, adjoints=adjoints)
+        except _ffi.NodalHipError as exc:
+            if exc.status == _ffi.E_INVALID and "no solution" in str(exc):
+                raise ValueError("no solution: call solve() first") from None
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            if not is_connected(self.netlist):
+                logging.error("Model error: unconnected circuit")
+                raise UnconnectedCircuitError
+            logging.error("Model error: matrix is singular")
+            raise np.linalg.LinAlgError("Singular matrix")
+        if (info > 0).any():
+            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        return Sensitivities(self.netlist, outputs, values, y, info, resid, adjoints=lam, table=self.table)
+
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last
         solution, computed on the device."""

@@ -246,6 +246,7 @@ void nodal_free_buffers(nodal_ctx *h) {
     slu_destroy(h);
     presolve_free_plan(h);
     nodal_free_block_child(h);
+    sens_free_child(h);
     if (h->reduced) {
         nodal_free_buffers(h->reduced);
         delete h->reduced;
@@ -264,7 +265,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->gn_rowidx, &h->gn_data, &h->gn_diag, &h->schur, &h->ps_buf, &h->ps_newidx,
                       &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none,
                       &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk, &h->br_out, &h->br_part, &h->br_tot,
-                      &h->br_env};
+                      &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     h->evpool.clear();
@@ -283,6 +284,7 @@ void nodal_poison_scratch(nodal_ctx *h) {
     nodal_poison_scratch(h->reduced);
     nodal_poison_scratch(h->lowdeg);
     nodal_poison_scratch(h->blocksys);
+    nodal_poison_scratch(h->adjoint);
 }
 
 void nodal_nan_probe(nodal_ctx *h, const double *dev, int64_t n, const char *tag) {
@@ -805,6 +807,18 @@ int nodal_branches(nodal_handle h, double *voltage, double *current, double *pow
     DeviceGuard g(h);
     if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
     return branch_single(h, voltage, current, power, totals2);
+}
+
+int nodal_sensitivities(nodal_handle h, int32_t dense, int32_t count, const int32_t *kind, const int32_t *p,
+                        const int32_t *q2, double *sens_out, double *value_out, double *adjoint_out,
+                        double *resid_out, int32_t *info_out) {
+    if (!h || count < 0 || (count > 0 && (!kind || !p || !q2 || !sens_out || !info_out))) return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "sensitivities: no component table on the handle");
+    if (!h->have_numeric || !h->have_x) return nodal_fail(h, NODAL_E_INVALID, "sensitivities: no solution on the handle");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    if (count == 0) return NODAL_OK;
+    return sens_run(h, dense != 0, count, kind, p, q2, sens_out, value_out, adjoint_out, resid_out, info_out);
 }
 
 int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const int64_t *rows, const double *values,

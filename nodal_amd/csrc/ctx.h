@@ -194,6 +194,15 @@ struct nodal_ctx {
     // branch quantities (branch.hip): voltage / current / power on their way to the host, the workgroups' power
     // partials (+ the two totals of a single solution), a sweep's totals [count][2], a sweep's envelope arrays
     DevBuf br_out, br_part, br_tot, br_env;
+    // adjoint sensitivities (sensitivity.hip): the solution set aside during the call, the outputs' specification and
+    // values, one block of results on its way to the host, the CCVS / CCCS rows grouped by their driving resistor
+    // (kept per table_epoch); the child context holding G^T as CSR (networks that are not passive), the parent
+    // struct_epoch its pattern was transposed from and the permutation that gathers its values from `data`
+    DevBuf sn_x, sn_spec, sn_out, sn_cross, sn_perm;
+    uint64_t sn_cross_epoch = 0;
+    int64_t sn_ndrivers = 0, sn_ncross = 0;
+    nodal_ctx *adjoint = nullptr;
+    uint64_t adjoint_epoch = 0;
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
     // matrix-only context (no component table) that inherits the grounded-node flags
     nodal_ctx *lowdeg = nullptr;
@@ -378,6 +387,28 @@ int branch_sweep_begin(nodal_ctx *h, BranchSweep *env, int32_t count);
 int branch_sweep_block(nodal_ctx *h, const BranchSweep *env, int32_t m0, int cols, const double *rows,
                        const int32_t *info, const double *swept_dev, const int32_t *slot_dev, int32_t nsrc);
 int branch_sweep_finish(nodal_ctx *h, const BranchSweep *env, int32_t count, const int32_t *info);
+
+// ---- adjoint sensitivities (sensitivity.hip; the transposed solves: sparse_solve_adjoint in sparse.hip) ----
+// one call of nodal_sensitivities: the outputs' specification (device, [count]), the single solve's solution set aside
+// (device, [n]) and the caller's host arrays
+struct SensCall {
+    const int32_t *kind = nullptr, *p = nullptr, *q2 = nullptr;
+    const int32_t *kind_host = nullptr, *p_host = nullptr;  // the caller's own arrays
+    const double *x = nullptr;
+    double *sens_out = nullptr, *adjoint_out = nullptr, *resid_out = nullptr;
+    int32_t *info_out = nullptr;
+};
+// adds the entries of the columns c of outputs m0 .. m0 + cols - 1 (cols <= 16) into a zeroed block, element (row, y) at
+// out[row * rs + y * cs]
+int sens_rhs_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, double *out, int64_t rs, int64_t cs);
+// the table kernels for those outputs from their adjoints lam (same addressing), results to the host, and the wait
+int sens_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, const double *lam, int64_t rs, int64_t cs);
+// G^T lambda = c for every output, routed as sparse_solve_sources routes its members; s = h itself (a passive network:
+// G is symmetric) or the child context holding G^T
+int sparse_solve_adjoint(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, const SensCall *call);
+int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const int32_t *p, const int32_t *q2,
+             double *sens_out, double *value_out, double *adjoint_out, double *resid_out, int32_t *info_out);
+void sens_free_child(nodal_ctx *h);
 
 // ---- fp64 MFMA GEMM (gemm_f64.hip), column-major ----
 enum { GEMM_SUB = 0, GEMM_SET = 1, GEMM_SETNEG = 2 };  // C -= A B | C = A B | C = -A B

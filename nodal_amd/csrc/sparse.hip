@@ -1469,3 +1469,251 @@ int sparse_residual(nodal_ctx *h, double *scaled) {
         return nodal_fail(h, NODAL_E_INVALID, "no assembled system / solution on the device");
     return csr_scaled_residual(h, h->x.as<double>(), h->rhs.as<double>(), scaled);
 }
+
+// ---- adjoint solves (nodal_sensitivities, sensitivity.hip) ------------------------------------------------------
+// G^T lambda = c for every output of the call: the routes of sparse_solve_sources over right-hand sides that
+// sens_rhs_block writes, on `s` -- the handle itself when the network is passive (G is symmetric bit for bit), else the
+// child context that holds G^T as CSR.  Every column is judged on its own scaled residual, at most one block of sixteen
+// sits behind any host wait, and each finished block goes to sens_block (the table kernels and the way down).  The
+// driver logic is restated here on purpose: the sweeps' own drivers stay as they are.
+namespace {
+
+struct AdjointCtx {
+    nodal_ctx *h, *s;
+    const SensCall *call;
+    double *resid;
+    int32_t *info;
+    double *norms;  // [16][4] maxima + [16] scaled residuals (device)
+
+    int fold(int32_t m0, int cols, double *out, int64_t rs, int64_t cs, size_t block_bytes) const {
+        NODAL_HIP_TRY(h, hipMemsetAsync(out, 0, block_bytes, h->stream));
+        return sens_rhs_block(h, call, m0, cols, out, rs, cs);
+    }
+    int judge(int32_t m0, int cols, const double *x, const double *b, int64_t rs, int64_t cs) const {
+        const int64_t n = h->n;
+        NODAL_HIP_TRY(h, hipMemsetAsync(norms, 0, (size_t)(4 + 1) * SLU_MULTI * 8, h->stream));
+        const unsigned g = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 1024);
+        resid_norms_multi<<<g, TB, 0, h->stream>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(),
+                                                  s->data.as<double>(), x, b, rs, cs, cols, norms);
+        scaled_from_norms<<<1, 64, 0, h->stream>>>(norms, cols, norms + 4 * SLU_MULTI);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return nodal_read_words(h, resid + m0, norms + 4 * SLU_MULTI, (size_t)cols * 8);
+    }
+    // adjoints of outputs m0 .. (element (row, y) at lam[row * rs + y * cs]) through the table kernels, to the caller,
+    // and the wait; `rows` != null: the same adjoints as [cols][n] rows for adjoint_out
+    int hand_over(int32_t m0, int cols, const double *lam, int64_t rs, int64_t cs, const double *rows) const {
+        const int64_t n = h->n;
+        if (call->adjoint_out && rows)
+            NODAL_HIP_TRY(h, hipMemcpyAsync(call->adjoint_out + (int64_t)m0 * n, rows, (size_t)cols * n * 8,
+                                            hipMemcpyDeviceToHost, h->stream));
+        return sens_block(h, call, m0, cols, lam, rs, cs);  // (waits)
+    }
+    int nan_rows(double *rows, int cols) const {
+        fill_nan_rows<<<grid_rows(h->n * cols, 1), TB, 0, h->stream>>>(h->n * cols, rows);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return NODAL_OK;
+    }
+    // every output singular: NaN throughout, info 1
+    void all_singular(int32_t count) const {
+        const int64_t n = h->n, ncomp = h->ncomp;
+        const double nan = __builtin_nan("");
+        for (int32_t m = 0; m < count; ++m) {
+            info[m] = 1;
+            resid[m] = nan;
+        }
+        for (int64_t t = 0; t < (int64_t)count * ncomp; ++t) call->sens_out[t] = nan;
+        if (call->adjoint_out)
+            for (int64_t t = 0; t < (int64_t)count * n; ++t) call->adjoint_out[t] = nan;
+    }
+};
+
+// a call on the solve context: its error text is the handle's
+#define ADJ_TRY(expr)                               \
+    do {                                            \
+        const int _as = (expr);                     \
+        if (_as != NODAL_OK) {                      \
+            if (s != h) h->err = s->err;            \
+            return _as;                             \
+        }                                           \
+    } while (0)
+
+}  // namespace
+
+int sparse_solve_adjoint(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, const SensCall *call) {
+    const int64_t n = h->n;
+    hipStream_t st = h->stream;
+    std::vector<double> resid_host(call->resid_out ? 0 : (size_t)count);
+    for (int32_t m = 0; m < count; ++m) call->info_out[m] = 0;
+    AdjointCtx c{h, s, call, call->resid_out ? call->resid_out : resid_host.data(), call->info_out, nullptr};
+    const bool passive = s == h;
+    const int64_t densify_max = 4096;        // the bounds of sparse_solve_sources
+    const int64_t dense_general_max = 8192;
+    const size_t vb = (size_t)n * SLU_MULTI * 8;
+
+    if (dense || n <= 64 || (passive && n <= densify_max) || (!passive && n <= dense_general_max)) {
+        // one LU per chunk of up to 512 outputs: their columns c ride along as right-hand sides of the augmented panel
+        const int32_t CHUNK = 512;
+        const int64_t lda = dense_lda(n);
+        const int32_t first = count < CHUNK ? count : CHUNK;
+        NODAL_HIP_TRY(h, h->sw_blk.reserve((size_t)n * first * 8 + 5 * SLU_MULTI * 8 + 256));
+        double *Bc = h->sw_blk.as<double>();  // the same columns, kept for the judgement ([m][n])
+        c.norms = Bc + (size_t)n * first;
+        for (int32_t q0 = 0; q0 < count; q0 += CHUNK) {
+            const int32_t m = count - q0 < CHUNK ? count - q0 : CHUNK;
+            NODAL_HIP_TRY(h, s->dense.reserve((size_t)lda * (size_t)(n + m) * 8 + 64));
+            if (s->csr_only) ADJ_TRY(csr_to_dense(s, s->dense.as<double>(), lda));
+            else NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
+            double *cols = s->dense.as<double>() + n * lda;
+            NODAL_HIP_TRY(h, hipMemsetAsync(cols, 0, (size_t)lda * m * 8, st));
+            for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
+                const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
+                NODAL_TRY(sens_rhs_block(h, call, q0 + g0, k, cols + g0 * lda, 1, lda));
+                NODAL_TRY(c.fold(q0 + g0, k, Bc + g0 * n, 1, n, (size_t)n * k * 8));
+            }
+            NODAL_HIP_TRY(h, s->solver.reserve((size_t)n * m * 8 + 64));
+            double *X = s->solver.as<double>();
+            int32_t inf = 0;
+            ADJ_TRY(dense_factor_solve_multi(s, m, X, n, &inf));
+            if (inf > 0) {
+                if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+                c.all_singular(count);
+                return NODAL_OK;
+            }
+            for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
+                const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
+                NODAL_TRY(c.judge(q0 + g0, k, X + g0 * n, Bc + g0 * n, 1, n));
+                NODAL_TRY(c.hand_over(q0 + g0, k, X + g0 * n, 1, n, X + g0 * n));
+            }
+        }
+        return NODAL_OK;
+    }
+
+    // blocks interleaved by row: B, X, R, D; then [16][n] rows, one vector b, the norms
+    NODAL_HIP_TRY(h, h->sw_blk.reserve(5 * vb + (size_t)n * 8 + 5 * SLU_MULTI * 8 + 256));
+    double *Bil = h->sw_blk.as<double>(), *Xil = Bil + (size_t)n * SLU_MULTI, *Ril = Xil + (size_t)n * SLU_MULTI,
+           *Dil = Ril + (size_t)n * SLU_MULTI, *rows = Dil + (size_t)n * SLU_MULTI, *bvec = rows + (size_t)n * SLU_MULTI;
+    c.norms = bvec + n;
+    const unsigned gv = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 65536);
+    // the block's adjoints as rows, when the caller wants them
+    auto rows_of = [&](int cnt) -> const double * {
+        if (!call->adjoint_out) return nullptr;
+        deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
+        return rows;
+    };
+
+    if (passive) {
+        // output 0 sets the multigrid hierarchy up (or finds it); the others go sixteen at a time through the block
+        // iteration.  A block that breaks down or hits its cap is redone column by column, and a column the iteration
+        // fails on -- with every later one -- by the sparse direct solve.
+        bool direct = n < h->amg_min_n, block_ok = true;
+        auto one = [&](int32_t m) -> int {
+            NODAL_TRY(c.fold(m, 1, bvec, 1, 0, (size_t)n * 8));
+            int32_t inf = 0, it = 0;
+            double rs = 0.0;
+            bool done = false;
+            if (!direct) {
+                const int sv = amg_fcg_solve_ex(h, bvec, m == 0, &inf, &it, &rs);  // (writes h->x: the caller has set the solution aside)
+                if (sv == -2) return -2;  // floating island: every output is singular
+                if (sv == NODAL_OK) {
+                    NODAL_HIP_TRY(h, hipMemcpyAsync(rows, h->x.as<double>(), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+                    done = true;
+                } else if (sv < 0) {
+                    direct = true;
+                } else {
+                    return sv;
+                }
+            }
+            if (!done) {
+                NODAL_TRY(sparse_direct_solve(h, bvec, rows, &inf, &it, &rs));
+                if (inf > 0) {
+                    call->info_out[m] = 1;
+                    NODAL_TRY(c.nan_rows(rows, 1));
+                }
+            }
+            NODAL_TRY(c.judge(m, 1, rows, bvec, 1, 0));
+            return c.hand_over(m, 1, rows, 1, 0, rows);
+        };
+        for (int32_t m0 = 0; m0 < count;) {
+            const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
+            if (m0 > 0 && !direct && block_ok && cnt >= 2 && sagg_ready(h, n)) {
+                NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
+                int32_t it = 0;
+                const int sv = sagg_fcg_solve_block(h, cnt, Bil, Xil, &it);
+                if (sv == NODAL_OK) {
+                    NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
+                    const double *r = rows_of(cnt);
+                    NODAL_HIP_TRY(h, hipGetLastError());
+                    NODAL_TRY(c.hand_over(m0, cnt, Xil, SLU_MULTI, 1, r));
+                    m0 += cnt;
+                    continue;
+                }
+                if (sv > 0) return sv;
+                block_ok = false;  // (latched: a second failing block would cost its cap again for nothing)
+            }
+            const int sv = one(m0);
+            if (sv == -2) {
+                c.all_singular(count);
+                return NODAL_OK;
+            }
+            NODAL_TRY(sv);
+            ++m0;
+        }
+        return NODAL_OK;
+    }
+
+    // G^T of a network with branch unknowns or controlled sources: ONE sparse LU of the child, then per block of sixteen
+    // outputs two substitutions, one refinement step and the judgement; a column above the bar -- and every column when
+    // the factorisation had to replace pivots -- is redone alone by the sparse direct solve on the child.
+    int32_t inf = 0;
+    ADJ_TRY(slu_factor(s, &inf));
+    if (inf > 0) {
+        c.all_singular(count);
+        return NODAL_OK;
+    }
+    bool all_direct = slu_perturbed(s) > 0;
+    const double bar = 1e-14;  // the backward-error bar of the refinement, as the sweep's
+    for (int32_t m0 = 0; m0 < count; m0 += SLU_MULTI) {
+        const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
+        bool good = !all_direct;
+        if (!all_direct) {
+            NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
+            ADJ_TRY(slu_apply_multi(s, Bil, Xil));
+            csr_residual_multi<<<gv, TB, 0, st>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(), s->data.as<double>(),
+                                                 Xil, Bil, Ril);
+            ADJ_TRY(slu_apply_multi(s, Ril, Dil));
+            add_into<<<gv, TB, 0, st>>>(n * SLU_MULTI, Dil, Xil);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
+            for (int y = 0; y < cnt; ++y) good = good && c.resid[m0 + y] <= bar;
+        }
+        if (good) {  // the usual case: the block stays interleaved for the table kernel
+            const double *r = rows_of(cnt);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            NODAL_TRY(c.hand_over(m0, cnt, Xil, SLU_MULTI, 1, r));
+            continue;
+        }
+        if (!all_direct) {
+            deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
+            NODAL_HIP_TRY(h, hipGetLastError());
+        }
+        for (int y = 0; y < cnt; ++y) {
+            if (!all_direct && c.resid[m0 + y] <= bar) continue;
+            NODAL_TRY(c.fold(m0 + y, 1, bvec, 1, 0, (size_t)n * 8));
+            int32_t inf1 = 0, it = 0;
+            double rs = 0.0;
+            ADJ_TRY(sparse_direct_solve(s, bvec, rows + (size_t)y * n, &inf1, &it, &rs));
+            if (inf1 > 0) {
+                call->info_out[m0 + y] = 1;
+                NODAL_TRY(c.nan_rows(rows + (size_t)y * n, 1));
+            }
+            NODAL_TRY(c.judge(m0 + y, 1, rows + (size_t)y * n, bvec, 1, 0));
+        }
+        NODAL_TRY(c.hand_over(m0, cnt, rows, 1, n, rows));
+        if (!all_direct) {  // (the direct solve may have factored anew, with another pivot bar)
+            ADJ_TRY(slu_factor(s, &inf));
+            all_direct = inf > 0 || slu_perturbed(s) > 0;
+        }
+    }
+    return NODAL_OK;
+}
+#undef ADJ_TRY
