@@ -187,6 +187,10 @@ struct SHierarchy {
                                  // Two at level 1 as well ("222") is slower (22 iterations, 7.6 ms).
     bool dense_coarsest = true;  // last level: dense inverse; false: nothing but isolated nodes (diagonal)
     DevBuf tail_stamps, tail_image, apcol, apval, aplen, bstat;
+    // T = the tail's cycle as one dense operator, n_t x n_t row-major, formed behind the image by every setup and
+    // refresh (k_tail_pack_op); tail_dense: the cycles apply it (k_tail_apply) instead of walking the tail (k_tail)
+    DevBuf tail_op;
+    bool tail_dense = false;
     DevBuf mvec;  // vectors, partials and scalars of the block iteration (sagg_multi.h)
     hipEvent_t ev_copy = nullptr;  // behind the statistics read-back of a level (build_level)
     // R = P^T (count, scan, fill, two sorts, blocked layout: seven latency-bound launches) and A P (one long one) need
@@ -253,6 +257,7 @@ struct SHierarchy {
             delete l;
         }
         tail_image.release();
+        tail_op.release();
         mvec.release();
         tail_stamps.release();
         bstat.release();
@@ -1515,8 +1520,111 @@ const void *tail_kernel(int slots) {
                                     : reinterpret_cast<const void *>(k_tail<32>);
 }
 
+const void *tail_op_kernel(int slots) {
+    return slots <= 8 ? reinterpret_cast<const void *>(k_tail_pack_op<8>)
+                      : slots <= 16 ? reinterpret_cast<const void *>(k_tail_pack_op<16>)
+                                    : reinterpret_cast<const void *>(k_tail_pack_op<32>);
+}
+
+// out = (tail cycle) b by the kernel that walks the cycle: NV = 1, or a block of NV interleaved right-hand sides
+int tail_walk(nodal_ctx *h, SHierarchy *H, const double *b, double *out, int nv) {
+    const TailDesc &d = H->td;
+    const char *img = H->tail_image.as<char>();
+    if (d.slots <= 8) k_tail<8><<<nv, 1024, (size_t)d.lds_bytes, h->stream>>>(d, img, b, out, nv);
+    else if (d.slots <= 16) k_tail<16><<<nv, 1024, (size_t)d.lds_bytes, h->stream>>>(d, img, b, out, nv);
+    else k_tail<32><<<nv, 1024, (size_t)d.lds_bytes, h->stream>>>(d, img, b, out, nv);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+// the same by the dense operator (H->tail_dense)
+template <int NV>
+int tail_apply(nodal_ctx *h, SHierarchy *H, const double *b, double *out) {
+    const int n = H->td.lv[0].n;
+    const double *T = H->tail_op.as<double>();
+    const unsigned gr = (unsigned)((n + 3) / 4);
+    if (n <= 256) k_tail_apply<4, NV><<<gr, 256, 0, h->stream>>>(n, T, b, out);
+    else if (n <= 512) k_tail_apply<8, NV><<<gr, 256, 0, h->stream>>>(n, T, b, out);
+    else k_tail_apply<16, NV><<<gr, 256, 0, h->stream>>>(n, T, b, out);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+// NODAL_TRACE with NODAL_SA_TAIL_CHECK=1: both forms of the tail applied to one fixed vector of both signs,
+// d = max_i |y_dense - y_cycle|_i / sum_j |T_ij| |b_j|; the dense product alone against the same product in long double
+int tail_self_check(nodal_ctx *h, SHierarchy *H) {
+    const int n = H->td.lv[0].n;
+    std::vector<double> b((size_t)n), yc((size_t)n), yd((size_t)n), T((size_t)n * n);
+    uint64_t seed = 0x9e3779b97f4a7c15ull;
+    for (int i = 0; i < n; ++i) {  // (splitmix64: uniform in (-1, 1))
+        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        b[i] = (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
+    }
+    DevBuf v;
+    hipError_t e = v.reserve((size_t)3 * n * 8);
+    double *db = v.as<double>(), *dc = db + n, *dd = dc + n;
+    int rc = NODAL_OK;
+    if (e == hipSuccess) e = hipMemcpyAsync(db, b.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) rc = tail_walk(h, H, db, dc, 1);
+    if (e == hipSuccess && rc == NODAL_OK) rc = tail_apply<1>(h, H, db, dd);
+    if (e == hipSuccess && rc == NODAL_OK) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(yc.data(), dc, (size_t)n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(yd.data(), dd, (size_t)n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(T.data(), H->tail_op.p, (size_t)n * n * 8, hipMemcpyDeviceToHost);
+    v.release();
+    if (rc != NODAL_OK) return rc;
+    NODAL_HIP_TRY(h, e);
+    double d = 0.0, dp = 0.0;
+    for (int i = 0; i < n; ++i) {
+        long double y = 0.0L, a = 0.0L;
+        for (int j = 0; j < n; ++j) {
+            y += (long double)T[(size_t)i * n + j] * b[j];
+            a += fabsl((long double)T[(size_t)i * n + j] * b[j]);
+        }
+        const double den = (double)a;
+        const double q = fabs(yd[i] - yc[i]) / den, qp = (double)(fabsl((long double)yd[i] - y) / a);
+        d = !(q <= d) ? q : d;  // (a NaN stays)
+        dp = !(qp <= dp) ? qp : dp;
+    }
+    fprintf(stderr, "[sagg] tail check: n_t %d, dense operator against the cycle d = %.3e (product alone %.3e)\n", n, d, dp);
+    return NODAL_OK;
+}
+
+// T behind the image (fresh setup and values-only refresh)
+int form_tail_op(nodal_ctx *h, SHierarchy *H) {
+    static const bool on = !(getenv("NODAL_SA_TAIL_DENSE") && atoi(getenv("NODAL_SA_TAIL_DENSE")) == 0);
+    H->tail_dense = false;
+    if (!on || H->tail < 0) return NODAL_OK;
+    const TailDesc &d = H->td;
+    const int n = d.lv[0].n;
+    static std::atomic<int> cus[64];  // compute units of the device: a workgroup of this launch fills one
+    const int dev = h->device >= 0 && h->device < 64 ? h->device : 0;
+    int ncu = cus[dev].load(std::memory_order_acquire);
+    if (ncu == 0) {
+        NODAL_HIP_TRY(h, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device >= 0 ? h->device : 0));
+        if (ncu < 1) ncu = 1;
+        cus[dev].store(ncu, std::memory_order_release);
+    }
+    NODAL_HIP_TRY(h, H->tail_op.reserve((size_t)n * n * 8 + 64));
+    const unsigned gr = (unsigned)(n < ncu ? n : ncu);  // (columns blockIdx.x, + gridDim.x, ... behind one image load)
+    double *T = H->tail_op.as<double>();
+    const char *img = H->tail_image.as<char>();
+    if (d.slots <= 8) k_tail_pack_op<8><<<gr, 1024, (size_t)d.lds_bytes, h->stream>>>(d, img, T);
+    else if (d.slots <= 16) k_tail_pack_op<16><<<gr, 1024, (size_t)d.lds_bytes, h->stream>>>(d, img, T);
+    else k_tail_pack_op<32><<<gr, 1024, (size_t)d.lds_bytes, h->stream>>>(d, img, T);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    H->tail_dense = true;
+    static const bool check = getenv("NODAL_TRACE") && getenv("NODAL_SA_TAIL_CHECK") && atoi(getenv("NODAL_SA_TAIL_CHECK")) != 0;
+    if (check) NODAL_TRY(tail_self_check(h, H));
+    return NODAL_OK;
+}
+
 int build_tail(nodal_ctx *h, SHierarchy *H, const unsigned long long *hs) {
     H->tail = -1;
+    H->tail_dense = false;
     const int last = H->nlev - 1;
     auto up16 = [](int x) { return (x + 15) & ~15; };
     for (int t = 1; t <= last; ++t) {
@@ -1580,6 +1688,8 @@ int build_tail(nodal_ctx *h, SHierarchy *H, const unsigned long long *hs) {
             if (!lds_allowed[dev][which].load(std::memory_order_acquire)) {
                 NODAL_HIP_TRY(h, hipFuncSetAttribute(tail_kernel(d.slots), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                      TAIL_LDS_BUDGET));
+                NODAL_HIP_TRY(h, hipFuncSetAttribute(tail_op_kernel(d.slots), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     TAIL_LDS_BUDGET));
                 lds_allowed[dev][which].store(true, std::memory_order_release);
             }
         }
@@ -1588,6 +1698,7 @@ int build_tail(nodal_ctx *h, SHierarchy *H, const unsigned long long *hs) {
         NODAL_HIP_TRY(h, hipGetLastError());
         H->td = d;
         H->tail = t;
+        NODAL_TRY(form_tail_op(h, H));
         break;
     }
     return NODAL_OK;
@@ -1650,6 +1761,7 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
         coarsest_inverse<<<1, 256, 0, st>>>(H->pool[last]->A(), H->coarse_inv.as<double>(), dstats + (size_t)last * ST_COUNT);
     if (H->tail >= 0) k_tail_pack<<<1, 1024, 0, st>>>(H->td, H->tail_image.as<char>());
     NODAL_HIP_TRY(h, hipGetLastError());
+    NODAL_TRY(form_tail_op(h, H));
     NODAL_HIP_TRY(h, hipMemcpyAsync(hs, dstats, (size_t)MAX_LEVELS * ST_COUNT * 8, hipMemcpyDeviceToHost, st));
     NODAL_WAIT_STREAM(h, st);
     const int64_t bar = n0 / 100 < 32 ? (n0 / 100 > 0 ? n0 / 100 : 1) : 32;
@@ -1925,14 +2037,9 @@ int last_level(nodal_ctx *h, SHierarchy *H, int l, const double *b, double *out)
     hipStream_t st = h->stream;
     SLevel *L = H->pool[l];
     const int64_t n = L->n;
-    if (l == H->tail) {
-        if (H->td.slots <= 8) k_tail<8><<<1, 1024, (size_t)H->td.lds_bytes, st>>>(H->td, H->tail_image.as<char>(), b, out, 1);
-        else if (H->td.slots <= 16) k_tail<16><<<1, 1024, (size_t)H->td.lds_bytes, st>>>(H->td, H->tail_image.as<char>(), b, out, 1);
-        else k_tail<32><<<1, 1024, (size_t)H->td.lds_bytes, st>>>(H->td, H->tail_image.as<char>(), b, out, 1);
-    } else {
-        k_coarsest<<<grid_for(n), TB, 0, st>>>(n, H->dense_coarsest ? H->coarse_inv.as<double>() : nullptr,
-                                               L->dinv.as<double>(), b, out);
-    }
+    if (l == H->tail) return H->tail_dense ? tail_apply<1>(h, H, b, out) : tail_walk(h, H, b, out, 1);
+    k_coarsest<<<grid_for(n), TB, 0, st>>>(n, H->dense_coarsest ? H->coarse_inv.as<double>() : nullptr,
+                                           L->dinv.as<double>(), b, out);
     NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }
@@ -2267,6 +2374,7 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
         mix((uint64_t)H->nlev); mix((uint64_t)(H->tail + 1)); mix((uint64_t)H->kcycle); mix((uint64_t)H->klevels);
         mix((uint64_t)(H->nu[0] * 100 + H->nu[1] * 10 + H->nu[2])); mix((uint64_t)H->td.lds_bytes);
         mix((uint64_t)(uintptr_t)H->tail_image.p); mix((uint64_t)(uintptr_t)H->coarse_inv.p);
+        mix((uint64_t)(uintptr_t)(H->tail_dense ? H->tail_op.p : nullptr));
         for (int k = 0; k < H->nlev; ++k) {
             const SLevel *L = H->pool[k];
             const void *ps[] = {L->acol.p, L->aval.p, L->avalf.p, L->alen.p, L->dinv.p, L->pcol.p, L->pvalf.p,
@@ -2376,7 +2484,7 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
     if (trace)
         fprintf(stderr, "[sagg] %d iterations (%lld enqueued, %d polls), relative residual %.2e, status %d\n", *iters,
                 (long long)enqueued, polls, *resid, status);
-    if (trace && H->tail >= 0 && H->td.stamps) {
+    if (trace && H->tail >= 0 && H->td.stamps && !H->tail_dense) {
         long long ts[64];
         if (hipMemcpy(ts, H->td.stamps, sizeof ts, hipMemcpyDeviceToHost) == hipSuccess) {
             fprintf(stderr, "[sagg] tail phases (us):");

@@ -524,15 +524,15 @@ __device__ __forceinline__ double reg_row(const double (&v)[SLOTS], const uint32
     return s;
 }
 
-// SLOTS >= ceil(width / lpr) of the first tail level (8, 16 or 32)
-template <int SLOTS>
-__global__ __launch_bounds__(1024) void k_tail(TailDesc d, const char *__restrict__ image,
-                                               const double *__restrict__ rc, double *__restrict__ out, int vs) {
-    // vs: stride of the vectors' elements; vs > 1 = a block of interleaved right-hand sides (sagg_multi.h), one
-    // workgroup per column
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// The tail cycle of one workgroup: out = T rc for column `voff` of vectors strided by `vs`.
+// SLOTS >= ceil(width / lpr) of the first tail level (8, 16 or 32).
+// UNIT: the right-hand sides are unit vectors generated here (rc is not read) -- columns voff, voff + gridDim.x, ...
+// one after the other behind ONE load of the image: with vs = n the stores write T itself, row-major
+// (k_tail_pack_op below).
+template <int SLOTS, bool UNIT>
+__device__ __forceinline__ void tail_cycle(const TailDesc &d, char *smem, const char *__restrict__ image,
+                                           const double *__restrict__ rc, double *__restrict__ out, int vs, int voff) {
     const int tid = threadIdx.x;
-    const int voff = vs > 1 ? (int)blockIdx.x : 0;
     const int last = d.nlev - 1;
     const int TAIL_NU = d.nu;
     // LDS holds the image from d.skip on (the first level's matrix, which leads the image, goes to
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(1024) void k_tail(TailDesc d, const char *__restric
     auto u16 = [&](int off) { return reinterpret_cast<uint16_t *>(smem + (off - d.skip)); };
     int stamp_no = 0;
     auto stamp = [&]() {
-        if (d.stamps && tid == 0) d.stamps[stamp_no] = wall_clock64();
+        if (!UNIT && d.stamps && tid == 0) d.stamps[stamp_no] = wall_clock64();
         ++stamp_no;
     };
     stamp();
@@ -579,124 +579,205 @@ __global__ __launch_bounds__(1024) void k_tail(TailDesc d, const char *__restric
         for (int u = 0; u < FLY; ++u)
             if (tid + u * 1024 < pieces) dst[tid + u * 1024] = v[u];
     }
-    for (int i = tid; i < d.lv[0].n; i += 1024) f64(d.lv[0].o_B)[i] = rc[(int64_t)i * vs + voff];
-    __syncthreads();
-    stamp();
-    // ---- down ----
-    for (int k = 0; k < last; ++k) {
-        const TailLevelDesc &L = d.lv[k];
-        const double *aval = f64(L.o_aval), *dinv = f64(L.o_dinv), *B = f64(L.o_B);
-        const uint16_t *acol = u16(L.o_acol);
-        double *X = f64(L.o_X), *Y = f64(L.o_Y), *R = f64(L.o_R);
-        const int lpr = L.lpr, sub = tid & (lpr - 1), rows = 1024 / lpr;  // lpr lanes share a row
-        for (int i = tid; i < L.n; i += 1024) X[i] = OMEGA * dinv[i] * B[i];
+    for (;;) {  // (once unless UNIT)
+        for (int i = tid; i < d.lv[0].n; i += 1024)
+            f64(d.lv[0].o_B)[i] = UNIT ? (i == voff ? 1.0 : 0.0) : rc[(int64_t)i * vs + voff];
         __syncthreads();
-        for (int sweep = 1; sweep < TAIL_NU; ++sweep) {
-            for (int i0 = 0; i0 < L.n; i0 += rows) {  // (one pass at the first level: n * lpr <= 1024)
+        stamp();
+        // ---- down ----
+        for (int k = 0; k < last; ++k) {
+            const TailLevelDesc &L = d.lv[k];
+            const double *aval = f64(L.o_aval), *dinv = f64(L.o_dinv), *B = f64(L.o_B);
+            const uint16_t *acol = u16(L.o_acol);
+            double *X = f64(L.o_X), *Y = f64(L.o_Y), *R = f64(L.o_R);
+            const int lpr = L.lpr, sub = tid & (lpr - 1), rows = 1024 / lpr;  // lpr lanes share a row
+            for (int i = tid; i < L.n; i += 1024) X[i] = OMEGA * dinv[i] * B[i];
+            __syncthreads();
+            for (int sweep = 1; sweep < TAIL_NU; ++sweep) {
+                for (int i0 = 0; i0 < L.n; i0 += rows) {  // (one pass at the first level: n * lpr <= 1024)
+                    const int i = i0 + tid / lpr, ii = i < L.n ? i : L.n - 1;
+                    const double ax = k == 0 ? reg_row<SLOTS>(v0, c0, lpr, X)
+                                             : lds_row(aval, acol, L.n, L.width, ii, sub, lpr, X);
+                    if (i < L.n && sub == 0) Y[i] = fma(OMEGA * dinv[i], B[i] - ax, X[i]);
+                }
+                __syncthreads();
+                double *t = X; X = Y; Y = t;
+            }
+            for (int i0 = 0; i0 < L.n; i0 += rows) {
                 const int i = i0 + tid / lpr, ii = i < L.n ? i : L.n - 1;
                 const double ax = k == 0 ? reg_row<SLOTS>(v0, c0, lpr, X)
                                          : lds_row(aval, acol, L.n, L.width, ii, sub, lpr, X);
-                if (i < L.n && sub == 0) Y[i] = fma(OMEGA * dinv[i], B[i] - ax, X[i]);
+                if (i < L.n && sub == 0) R[i] = B[i] - ax;
             }
             __syncthreads();
-            double *t = X; X = Y; Y = t;
-        }
-        for (int i0 = 0; i0 < L.n; i0 += rows) {
-            const int i = i0 + tid / lpr, ii = i < L.n ? i : L.n - 1;
-            const double ax = k == 0 ? reg_row<SLOTS>(v0, c0, lpr, X)
-                                     : lds_row(aval, acol, L.n, L.width, ii, sub, lpr, X);
-            if (i < L.n && sub == 0) R[i] = B[i] - ax;
-        }
-        __syncthreads();
-        stamp();
-        // (X holds the smoothed iterate: remember which buffer via the parity of TAIL_NU below)
-        const double *rval = f64(L.o_rval);
-        const uint16_t *rcol = u16(L.o_rcol);
-        double *Bc = f64(d.lv[k + 1].o_B);
-        for (int I0 = 0; I0 < L.nc; I0 += 1024 / RL) {  // eight lanes per coarse row
-            const int I = I0 + tid / RL, r8 = tid & (RL - 1);
-            double s = 0.0;
-            if (I < L.nc) {
-                double s1 = 0.0;
-                const int e0 = I * RL + r8, step = L.nc * RL;
-                int q = 0;
-                for (; q + 3 < L.nq; q += 4) {  // (four blocks in flight)
-                    const int ea = e0 + q * step, eb = ea + step, ec = eb + step, ed = ec + step;
-                    const double va = rval[ea], vb = rval[eb], vc = rval[ec], vd = rval[ed];
-                    const int ca = rcol[ea], cb = rcol[eb], cc = rcol[ec], cd = rcol[ed];
-                    s = fma(va, R[ca], s);
-                    s1 = fma(vb, R[cb], s1);
-                    s = fma(vc, R[cc], s);
-                    s1 = fma(vd, R[cd], s1);
+            stamp();
+            // (X holds the smoothed iterate: remember which buffer via the parity of TAIL_NU below)
+            const double *rval = f64(L.o_rval);
+            const uint16_t *rcol = u16(L.o_rcol);
+            double *Bc = f64(d.lv[k + 1].o_B);
+            for (int I0 = 0; I0 < L.nc; I0 += 1024 / RL) {  // eight lanes per coarse row
+                const int I = I0 + tid / RL, r8 = tid & (RL - 1);
+                double s = 0.0;
+                if (I < L.nc) {
+                    double s1 = 0.0;
+                    const int e0 = I * RL + r8, step = L.nc * RL;
+                    int q = 0;
+                    for (; q + 3 < L.nq; q += 4) {  // (four blocks in flight)
+                        const int ea = e0 + q * step, eb = ea + step, ec = eb + step, ed = ec + step;
+                        const double va = rval[ea], vb = rval[eb], vc = rval[ec], vd = rval[ed];
+                        const int ca = rcol[ea], cb = rcol[eb], cc = rcol[ec], cd = rcol[ed];
+                        s = fma(va, R[ca], s);
+                        s1 = fma(vb, R[cb], s1);
+                        s = fma(vc, R[cc], s);
+                        s1 = fma(vd, R[cd], s1);
+                    }
+                    for (; q < L.nq; ++q) s = fma(rval[e0 + q * step], R[rcol[e0 + q * step]], s);
+                    s += s1;
                 }
-                for (; q < L.nq; ++q) s = fma(rval[e0 + q * step], R[rcol[e0 + q * step]], s);
-                s += s1;
-            }
 #pragma unroll
-            for (int off = RL >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            if (I < L.nc && r8 == 0) Bc[I] = s;
-        }
-        __syncthreads();
-        stamp();
-    }
-    {
-        const TailLevelDesc &L = d.lv[last];
-        const double *inv = f64(L.o_aval), *B = f64(L.o_B);
-        double *E = f64(L.o_X);
-        for (int i = tid; i < L.n; i += 1024) {
-            double s = 0.0;
-            if (d.inv) {
-                double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-                const double *row = inv + i * L.n;
-                int j = 0;
-                for (; j + 3 < L.n; j += 4) {
-                    s = fma(row[j], B[j], s);
-                    s1 = fma(row[j + 1], B[j + 1], s1);
-                    s2 = fma(row[j + 2], B[j + 2], s2);
-                    s3 = fma(row[j + 3], B[j + 3], s3);
-                }
-                for (; j < L.n; ++j) s = fma(row[j], B[j], s);
-                s = (s + s1) + (s2 + s3);
-            } else {
-                s = inv[i] * B[i];
-            }
-            E[i] = s;
-        }
-        __syncthreads();
-        stamp();
-    }
-    // ---- up ----
-    const double *Ec = f64(d.lv[last].o_X);
-    for (int k = last - 1; k >= 0; --k) {
-        const TailLevelDesc &L = d.lv[k];
-        const double *aval = f64(L.o_aval), *dinv = f64(L.o_dinv), *B = f64(L.o_B), *pval = f64(L.o_pval);
-        const uint16_t *acol = u16(L.o_acol), *pcol = u16(L.o_pcol);
-        double *X = f64((TAIL_NU & 1) ? L.o_X : L.o_Y), *Y = f64((TAIL_NU & 1) ? L.o_Y : L.o_X);  // X: pre-smoothed iterate
-        for (int i = tid; i < L.n; i += 1024) {
-            double s = X[i];
-#pragma unroll
-            for (int q = 0; q < PW; ++q) s = fma(pval[q * L.n + i], Ec[pcol[q * L.n + i]], s);
-            Y[i] = s;
-        }
-        __syncthreads();
-        stamp();
-        const int lpr = L.lpr, sub = tid & (lpr - 1), rows = 1024 / lpr;
-        for (int sweep = 0; sweep < TAIL_NU; ++sweep) {
-            for (int i0 = 0; i0 < L.n; i0 += rows) {
-                const int i = i0 + tid / lpr, ii = i < L.n ? i : L.n - 1;
-                const double ax = k == 0 ? reg_row<SLOTS>(v0, c0, lpr, Y)
-                                         : lds_row(aval, acol, L.n, L.width, ii, sub, lpr, Y);
-                if (i < L.n && sub == 0) X[i] = fma(OMEGA * dinv[i], B[i] - ax, Y[i]);
+                for (int off = RL >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+                if (I < L.nc && r8 == 0) Bc[I] = s;
             }
             __syncthreads();
-            double *t = X; X = Y; Y = t;
+            stamp();
         }
-        Ec = Y;  // the last sweep's result
+        {
+            const TailLevelDesc &L = d.lv[last];
+            const double *inv = f64(L.o_aval), *B = f64(L.o_B);
+            double *E = f64(L.o_X);
+            for (int i = tid; i < L.n; i += 1024) {
+                double s = 0.0;
+                if (d.inv) {
+                    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+                    const double *row = inv + i * L.n;
+                    int j = 0;
+                    for (; j + 3 < L.n; j += 4) {
+                        s = fma(row[j], B[j], s);
+                        s1 = fma(row[j + 1], B[j + 1], s1);
+                        s2 = fma(row[j + 2], B[j + 2], s2);
+                        s3 = fma(row[j + 3], B[j + 3], s3);
+                    }
+                    for (; j < L.n; ++j) s = fma(row[j], B[j], s);
+                    s = (s + s1) + (s2 + s3);
+                } else {
+                    s = inv[i] * B[i];
+                }
+                E[i] = s;
+            }
+            __syncthreads();
+            stamp();
+        }
+        // ---- up ----
+        const double *Ec = f64(d.lv[last].o_X);
+        for (int k = last - 1; k >= 0; --k) {
+            const TailLevelDesc &L = d.lv[k];
+            const double *aval = f64(L.o_aval), *dinv = f64(L.o_dinv), *B = f64(L.o_B), *pval = f64(L.o_pval);
+            const uint16_t *acol = u16(L.o_acol), *pcol = u16(L.o_pcol);
+            double *X = f64((TAIL_NU & 1) ? L.o_X : L.o_Y), *Y = f64((TAIL_NU & 1) ? L.o_Y : L.o_X);  // X: pre-smoothed iterate
+            for (int i = tid; i < L.n; i += 1024) {
+                double s = X[i];
+#pragma unroll
+                for (int q = 0; q < PW; ++q) s = fma(pval[q * L.n + i], Ec[pcol[q * L.n + i]], s);
+                Y[i] = s;
+            }
+            __syncthreads();
+            stamp();
+            const int lpr = L.lpr, sub = tid & (lpr - 1), rows = 1024 / lpr;
+            for (int sweep = 0; sweep < TAIL_NU; ++sweep) {
+                for (int i0 = 0; i0 < L.n; i0 += rows) {
+                    const int i = i0 + tid / lpr, ii = i < L.n ? i : L.n - 1;
+                    const double ax = k == 0 ? reg_row<SLOTS>(v0, c0, lpr, Y)
+                                             : lds_row(aval, acol, L.n, L.width, ii, sub, lpr, Y);
+                    if (i < L.n && sub == 0) X[i] = fma(OMEGA * dinv[i], B[i] - ax, Y[i]);
+                }
+                __syncthreads();
+                double *t = X; X = Y; Y = t;
+            }
+            Ec = Y;  // the last sweep's result
+            stamp();
+        }
+        for (int i = tid; i < d.lv[0].n; i += 1024) out[(int64_t)i * vs + voff] = Ec[i];
         stamp();
+        voff += (int)gridDim.x;
+        if (!UNIT || voff >= d.lv[0].n) break;
+        __syncthreads();  // (the next column's right-hand side goes where this one's was)
     }
-    for (int i = tid; i < d.lv[0].n; i += 1024) out[(int64_t)i * vs + voff] = Ec[i];
-    stamp();
-    if (d.stamps && tid == 0) d.stamps[63] = stamp_no;
+    if (!UNIT && d.stamps && tid == 0) d.stamps[63] = stamp_no;
+}
+
+template <int SLOTS>
+__global__ __launch_bounds__(1024) void k_tail(TailDesc d, const char *__restrict__ image,
+                                               const double *__restrict__ rc, double *__restrict__ out, int vs) {
+    // vs: stride of the vectors' elements; vs > 1 = a block of interleaved right-hand sides (sagg_multi.h), one
+    // workgroup per column
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    tail_cycle<SLOTS, false>(d, smem, image, rc, out, vs, vs > 1 ? (int)blockIdx.x : 0);
+}
+
+// The tail is a fixed linear map for fixed hierarchy values: T = the cycle applied to the n unit vectors, formed once
+// per setup (T[i * n + j], a row contiguous) and applied as a dense matrix-vector product (k_tail_apply) instead of
+// 2 x iterations walks of the cycle on one compute unit.  Part of the setup, like the image it reads.
+template <int SLOTS>
+__global__ __launch_bounds__(1024) void k_tail_pack_op(TailDesc d, const char *__restrict__ image,
+                                                       double *__restrict__ T) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    tail_cycle<SLOTS, true>(d, smem, image, nullptr, T, d.lv[0].n, (int)blockIdx.x);
+}
+
+// out = T rc in fp64: one wavefront per row, lane l takes the columns l, l + 64, ... (every load a contiguous
+// 512-byte segment), all CH loads of the row and of rc in flight before the first use, two accumulators per lane,
+// wave_sum: one order of summation.  NV > 1: a block of NV interleaved right-hand sides (vectors strided by NV,
+// sagg_multi.h); the row's loads serve all of them.  A zero of T takes nothing from rc (a block-diagonal T keeps a
+// NaN inside its block, as the cycle does).
+template <int CH, int NV>
+__global__ __launch_bounds__(256) void k_tail_apply(int n, const double *__restrict__ T,
+                                                    const double *__restrict__ rc, double *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int i = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const double *row = T + (int64_t)i * n;
+    double t[CH];
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+        const int j = lane + 64 * u;
+        t[u] = row[j < n ? j : 0];
+    }
+    if constexpr (NV == 1) {
+        double r[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int j = lane + 64 * u;
+            r[u] = rc[j < n ? j : 0];
+        }
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int u = 0; u < CH; u += 2) {
+            if (lane + 64 * u < n && t[u] != 0.0) s0 = fma(t[u], r[u], s0);
+            if (lane + 64 * (u + 1) < n && t[u + 1] != 0.0) s1 = fma(t[u + 1], r[u + 1], s1);
+        }
+        const double s = wave_sum(s0 + s1);
+        if (lane == 0) out[i] = s;
+    } else {
+        double s[NV];
+#pragma unroll
+        for (int c = 0; c < NV; ++c) s[c] = 0.0;
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int j = lane + 64 * u;
+            const double *rj = rc + (int64_t)(j < n ? j : 0) * NV;
+            const bool use = j < n && t[u] != 0.0;
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+                const double v = rj[c];
+                if (use) s[c] = fma(t[u], v, s[c]);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            const double v = wave_sum(s[c]);
+            if (lane == 0) out[(int64_t)i * NV + c] = v;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------

@@ -14,7 +14,8 @@
 //     Krylov processes that merely travel together; a converged column's updates are predicated off;
 //   * dot products leave per-workgroup partials laid out [quantity][block][column]; a one-workgroup-per-
 //     quantity kernel folds them in a fixed order (deterministic), the consumers read 16 totals;
-//   * the tail levels run in one launch of MK workgroups (k_tail, one column each).
+//   * the tail levels are one launch: the dense operator of sagg_cycle.h applied to all MK columns (k_tail_apply<CH, MK>)
+//     or, with NODAL_SA_TAIL_DENSE=0, MK workgroups that walk the cycle (k_tail, one column each).
 // The single-vector kernels of sagg_cycle.h are untouched: the headline path does not go through here.
 #pragma once
 
@@ -512,15 +513,10 @@ int m_last_level(nodal_ctx *h, SHierarchy *H, int l, const double *b, double *ou
     hipStream_t st = h->stream;
     SLevel *L = H->pool[l];
     const int64_t n = L->n;
-    if (l == H->tail) {
-        // vectors strided by MK
-        if (H->td.slots <= 8) k_tail<8><<<MK, 1024, (size_t)H->td.lds_bytes, st>>>(H->td, H->tail_image.as<char>(), b, out, MK);
-        else if (H->td.slots <= 16) k_tail<16><<<MK, 1024, (size_t)H->td.lds_bytes, st>>>(H->td, H->tail_image.as<char>(), b, out, MK);
-        else k_tail<32><<<MK, 1024, (size_t)H->td.lds_bytes, st>>>(H->td, H->tail_image.as<char>(), b, out, MK);
-    } else {
-        m_coarsest<<<mgrid(n), TB, 0, st>>>(n, H->dense_coarsest ? H->coarse_inv.as<double>() : nullptr,
-                                            L->dinv.as<double>(), b, out);
-    }
+    if (l == H->tail)  // (vectors strided by MK)
+        return H->tail_dense ? tail_apply<MK>(h, H, b, out) : tail_walk(h, H, b, out, MK);
+    m_coarsest<<<mgrid(n), TB, 0, st>>>(n, H->dense_coarsest ? H->coarse_inv.as<double>() : nullptr,
+                                        L->dinv.as<double>(), b, out);
     NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }
