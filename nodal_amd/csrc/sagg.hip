@@ -85,6 +85,7 @@ inline unsigned grid_for(int64_t n, unsigned cap = 8192) {  // (caps are multipl
     return (unsigned)(g > cap ? cap : g);
 }
 inline int64_t pad64(int64_t n) { return (n + 63) & ~(int64_t)63; }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Workgroups are handed to the eight XCDs round-robin (workgroup b runs on XCD b % 8, each with its own
 // L2).  The row kernels walk virtual block numbers instead: XCD k gets the contiguous eighth
@@ -111,7 +112,9 @@ struct Ell {
 
 enum { ST_MAXLEN = 0, ST_GRADED = 1, ST_BADDIAG = 2, ST_OVERFLOW = 3, ST_NNZ = 4, ST_UNASSIGNED = 5,
        ST_MAXR = 6, ST_NC = 7 /* aggregates of the level (the scan's total) */,
-       ST_FARCOL = 8 /* level 0: some column lies further than 32767 from its row */, ST_COUNT = 9 };
+       ST_FARCOL = 8 /* level 0: some column lies further than 32767 from its row */,
+       ST_FOLDMISS = 9 /* a column of P's row is missing from the row of A P (a row without a stored diagonal): no W */,
+       ST_COUNT = 10 };
 
 struct SLevel {
     int64_t n = 0, ld = 0, nc = 0;
@@ -127,6 +130,12 @@ struct SLevel {
     int64_t rld = 0;
     DevBuf vec, part, gflag;
     DevBuf avalf, pvalf, rvalf;  // f32 copies of A, P, R for the cycle kernels (levels outside the tail)
+    // W = P - w D^-1 (A P): prolongation and the first post-smoothing sweep as one operator on the coarse correction
+    // (k_prolong_post, sagg_cycle.h).  Column-major ELL like P, `wslots` slots (the A P row's), f32 values; written by
+    // ap_rows / ap_rows_lds beside A P.  fold_want: the setup emits it; fold: the cycle uses it.
+    DevBuf wcol, wval, wlen;
+    int32_t wslots = 0;
+    bool fold_want = false, fold = false;
     Ell A() const {
         Ell e;
         e.n = n; e.ld = ld; e.width = width;
@@ -252,7 +261,8 @@ struct SHierarchy {
         if (aux) (void)hipStreamDestroy(aux);
         for (SLevel *l : pool) {
             DevBuf *b[] = {&l->acol, &l->aval, &l->alen, &l->dinv, &l->agg, &l->pcol, &l->pval, &l->rcol,
-                           &l->rval, &l->rlen, &l->vec, &l->part, &l->gflag, &l->avalf, &l->pvalf, &l->rvalf, &l->adcol};
+                           &l->rval, &l->rlen, &l->vec, &l->part, &l->gflag, &l->avalf, &l->pvalf, &l->rvalf, &l->adcol,
+                           &l->wcol, &l->wval, &l->wlen};
             for (DevBuf *x : b) x->release();
             delete l;
         }
@@ -796,14 +806,29 @@ __device__ __forceinline__ int wave_excl_scan(int v, int *total) {
 // A_c an aggregate ends up with is the union of its members' AP rows, so APW = the coarse row
 // cap is always enough; the classes below are picked from the fine row length).  Duplicates are
 // merged in registers (compare chains, no dynamic indexing), in (A slot, P slot) order.
-template <int APW>
+template <int APW, bool EMIT>
 __global__ __launch_bounds__(TB) void ap_rows(Ell A, const int32_t *__restrict__ pcol, const double *__restrict__ pval,
                                               int32_t *__restrict__ apcol, double *__restrict__ apval,
-                                              int32_t *__restrict__ aplen, unsigned long long *__restrict__ stats) {
-    bool overflow = false;
+                                              int32_t *__restrict__ aplen, unsigned long long *__restrict__ stats,
+                                              const double *__restrict__ dinv, int32_t *__restrict__ wcol,
+                                              float *__restrict__ wval, int32_t *__restrict__ wlen) {
+    // EMIT: W = P - w D^-1 (A P) of the row goes out beside it (SLevel::wcol), slot q under column c[q].  (A template
+    // parameter, not a test of the pointer: the level-0 kernel of a hierarchy that does not fold there stays the code
+    // it was -- with the test it took 231 instead of 200 us at 1e6 rows.)
+    bool overflow = false, miss = false;
     for (int64_t i = (int64_t)xcd_block() * TB + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * TB) {
         int32_t c[APW];
         double v[APW];
+        [[maybe_unused]] int32_t Jo[PW];  // the row's own entries of P
+        [[maybe_unused]] double po[PW], wd = 0.0;
+        if constexpr (EMIT) {
+#pragma unroll
+            for (int sp = 0; sp < PW; ++sp) {
+                Jo[sp] = pcol[(int64_t)sp * A.ld + i];
+                po[sp] = pval[(int64_t)sp * A.ld + i];
+            }
+            wd = OMEGA * dinv[i];
+        }
 #pragma unroll
         for (int q = 0; q < APW; ++q) { c[q] = -1; v[q] = 0.0; }
         int cnt = 0;
@@ -839,23 +864,43 @@ __global__ __launch_bounds__(TB) void ap_rows(Ell A, const int32_t *__restrict__
                 apval[(int64_t)q * A.ld + i] = v[q];
             }
         aplen[i] = cnt;
+        if constexpr (EMIT) {
+            int have = 0, found = 0;
+#pragma unroll
+            for (int sp = 0; sp < PW; ++sp) have += Jo[sp] >= 0 ? 1 : 0;
+#pragma unroll
+            for (int q = 0; q < APW; ++q)
+                if (q < cnt) {
+                    double pv = 0.0;
+#pragma unroll
+                    for (int sp = 0; sp < PW; ++sp)
+                        if (Jo[sp] == c[q]) { pv += po[sp]; ++found; }
+                    wcol[(int64_t)q * A.ld + i] = c[q];
+                    wval[(int64_t)q * A.ld + i] = (float)(pv - wd * v[q]);
+                }
+            wlen[i] = cnt;
+            if (found != have) miss = true;
+        }
     }
     if (overflow) atomicOr(&stats[ST_OVERFLOW], 4ull);
+    if (miss) stats[ST_FOLDMISS] = 1ull;  // (every writer stores the same word)
 }
 
 // The same for the coarser levels, whose rows reach up to 64 aggregates: compare chains over 64
 // register slots cost 128 predicated operations per product (400 us for 1.4e5 rows); here every
 // lane keeps an open-addressing table of APW slots in LDS (slot-major: the lanes of a wavefront
 // never share a bank), filled in (A slot, P slot) order and written out in slot order.
-template <int APW>
+template <int APW, bool EMIT>
 __global__ __launch_bounds__(64) void ap_rows_lds(Ell A, const int32_t *__restrict__ pcol,
                                                   const double *__restrict__ pval, int32_t *__restrict__ apcol,
                                                   double *__restrict__ apval, int32_t *__restrict__ aplen,
-                                                  unsigned long long *__restrict__ stats) {
+                                                  unsigned long long *__restrict__ stats,
+                                                  const double *__restrict__ dinv, int32_t *__restrict__ wcol,
+                                                  float *__restrict__ wval, int32_t *__restrict__ wlen) {
     __shared__ int32_t tc[APW * 64];
     __shared__ double tv[APW * 64];
     const int lane = threadIdx.x;
-    bool overflow = false;
+    bool overflow = false, miss = false;
     for (int64_t i0 = (int64_t)xcd_block() * 64; i0 < A.n; i0 += (int64_t)gridDim.x * 64) {
         const int64_t i = i0 + lane;
 #pragma unroll 8
@@ -863,6 +908,16 @@ __global__ __launch_bounds__(64) void ap_rows_lds(Ell A, const int32_t *__restri
         int cnt = 0;
         if (i < A.n) {
             const int32_t l = A.len[i];
+            [[maybe_unused]] int32_t Jo[PW];  // the row's own entries of P, for W (see ap_rows)
+            [[maybe_unused]] double po[PW], wd = 0.0;
+            if constexpr (EMIT) {
+#pragma unroll
+                for (int sp = 0; sp < PW; ++sp) {
+                    Jo[sp] = pcol[(int64_t)sp * A.ld + i];
+                    po[sp] = pval[(int64_t)sp * A.ld + i];
+                }
+                wd = OMEGA * dinv[i];
+            }
             // Four entries of the row at a time: their columns and values, then the four P rows they name, are
             // requested together (unconditional loads: a slot past the row's end re-reads the row's first one and is
             // skipped below) -- two dependent round trips per four entries instead of per entry (a row of 27 entries on
@@ -913,19 +968,36 @@ __global__ __launch_bounds__(64) void ap_rows_lds(Ell A, const int32_t *__restri
                     }
                 }
             }
-            int o = 0;
+            int o = 0, found = 0;
             for (int q = 0; q < APW; ++q) {
                 const int32_t c = tc[q * 64 + lane];
                 if (c >= 0) {
+                    const double t = tv[q * 64 + lane];
                     apcol[(int64_t)o * A.ld + i] = c;
-                    apval[(int64_t)o * A.ld + i] = tv[q * 64 + lane];
+                    apval[(int64_t)o * A.ld + i] = t;
+                    if constexpr (EMIT) {
+                        double pv = 0.0;
+#pragma unroll
+                        for (int sp = 0; sp < PW; ++sp)
+                            if (Jo[sp] == c) { pv += po[sp]; ++found; }
+                        wcol[(int64_t)o * A.ld + i] = c;
+                        wval[(int64_t)o * A.ld + i] = (float)(pv - wd * t);
+                    }
                     ++o;
                 }
             }
             aplen[i] = cnt;
+            if constexpr (EMIT) {
+                int have = 0;
+#pragma unroll
+                for (int sp = 0; sp < PW; ++sp) have += Jo[sp] >= 0 ? 1 : 0;
+                wlen[i] = cnt;
+                if (found != have) miss = true;
+            }
         }
     }
     if (overflow) atomicOr(&stats[ST_OVERFLOW], 4ull);
+    if (miss) stats[ST_FOLDMISS] = 1ull;  // (every writer stores the same word)
 }
 
 // Step 2: A_c = R (AP), one wavefront (= one 64-thread workgroup) per coarse row.  The products
@@ -1260,13 +1332,18 @@ int galerkin_product(nodal_ctx *h, SHierarchy *H, int l, hipEvent_t r_ready = nu
     unsigned long long *lst = dstats + (size_t)l * ST_COUNT;
     const unsigned g = grid_for(n);
     if (phase != 2) {
-        switch (apw) {
-        case 16: ap_rows<16><<<g, TB, 0, st>>>(A, L->pcol.as<int32_t>(), L->pval.as<double>(), apcol, apval, aplen, lst); break;
-        default: {
-            const unsigned gl = (unsigned)((n + 63) / 64 < 4096 ? (n + 63) / 64 : 4096);
-            ap_rows_lds<64><<<gl, 64, 0, st>>>(A, L->pcol.as<int32_t>(), L->pval.as<double>(), apcol, apval, aplen, lst);
-        } break;
-        }
+        // (W beside A P where the level folds its first post-smoothing sweep: build_level reserved the buffers)
+        const bool w = L->fold_want && L->wslots == apw;
+        int32_t *wcol = w ? L->wcol.as<int32_t>() : nullptr, *wlen = w ? L->wlen.as<int32_t>() : nullptr;
+        float *wval = w ? L->wval.as<float>() : nullptr;
+        const double *dinv = L->dinv.as<double>();
+        const int32_t *pc = L->pcol.as<int32_t>();
+        const double *pv = L->pval.as<double>();
+        const unsigned gl = (unsigned)((n + 63) / 64 < 4096 ? (n + 63) / 64 : 4096);
+        if (apw == 16 && w) ap_rows<16, true><<<g, TB, 0, st>>>(A, pc, pv, apcol, apval, aplen, lst, dinv, wcol, wval, wlen);
+        else if (apw == 16) ap_rows<16, false><<<g, TB, 0, st>>>(A, pc, pv, apcol, apval, aplen, lst, dinv, wcol, wval, wlen);
+        else if (w) ap_rows_lds<64, true><<<gl, 64, 0, st>>>(A, pc, pv, apcol, apval, aplen, lst, dinv, wcol, wval, wlen);
+        else ap_rows_lds<64, false><<<gl, 64, 0, st>>>(A, pc, pv, apcol, apval, aplen, lst, dinv, wcol, wval, wlen);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
     if (phase == 1) return NODAL_OK;
@@ -1313,6 +1390,57 @@ double omega_p(int level) {
         w[0] = a > 0.0 && a < 1.0 ? a : OMEGA_P;
     }
     return w[level > 0 ? 1 : 0];
+}
+
+// Which levels fold their first post-smoothing sweep into the prolongation (SLevel::wcol, k_prolong_post).
+// NODAL_SA_FOLD_POST, read once per process: unset = by the level's rows (below); 0 = none; 1 = every level outside
+// the tail; "l0,l2" = exactly the levels named (the A/B of DESIGN.md section 8).
+// Default: levels of at most FOLD_MAX_ROWS rows.  Those are latency-bound -- a launch costs its dependent round trips
+// whatever it moves, so a launch less is time less -- while a level of 1e6 rows is bandwidth-bound and its W row
+// (9-13 slots of 8 bytes) is as many bytes as the P row and the matrix row it replaces (measured: DESIGN.md section 8).
+// A level small enough for the tail never runs cycle(): no W for it.
+constexpr int64_t FOLD_MAX_ROWS = 1 << 19;
+struct FoldSetting { int mode = 0; unsigned mask = 0; };  // mode 0: by size, 1: none, 2: all, 3: the mask's levels
+const FoldSetting &fold_setting() {
+    static const FoldSetting s = [] {
+        FoldSetting f;
+        const char *e = getenv("NODAL_SA_FOLD_POST");
+        if (!e || !*e) return f;
+        if (strchr(e, 'l')) {
+            f.mode = 3;
+            for (const char *q = e; (q = strchr(q, 'l')) != nullptr; ++q) {
+                const int k = atoi(q + 1);
+                if (q[1] >= '0' && q[1] <= '9' && k < MAX_LEVELS) f.mask |= 1u << k;
+            }
+        } else {
+            f.mode = atoi(e) == 0 ? 1 : 2;
+        }
+        return f;
+    }();
+    return s;
+}
+bool fold_wanted(int level, int64_t n) {
+    if (level > 0 && n <= TAIL_MAX_N) return false;
+    const FoldSetting &f = fold_setting();
+    switch (f.mode) {
+    case 1: return false;
+    case 2: return true;
+    case 3: return (f.mask >> level & 1u) != 0;
+    default: return n <= FOLD_MAX_ROWS;
+    }
+}
+// after the setup's (or the refresh's) last statistics read-back: the levels whose cycle uses W
+void decide_folds(SHierarchy *H, const unsigned long long *hs, bool trace) {
+    for (int k = 0; k < H->nlev; ++k) {
+        SLevel *L = H->pool[k];
+        const bool runs_cycle = k + 1 < H->nlev && (H->tail < 0 || k < H->tail);
+        const bool miss = hs[(size_t)k * ST_COUNT + ST_FOLDMISS] != 0;
+        L->fold = L->fold_want && runs_cycle && !miss;
+        if (trace && L->fold_want && runs_cycle)
+            fprintf(stderr, "[sagg] level %d (%lld rows): first post-smoothing sweep %s\n", k, (long long)L->n,
+                    miss ? "NOT folded: a row of A P lacks a column of its P row (no stored diagonal)"
+                         : "folded into the prolongation");
+    }
 }
 
 int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool *declined, bool *stop) {
@@ -1457,6 +1585,14 @@ int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool
         NODAL_HIP_TRY(h, H->apcol.reserve((size_t)apw * ld * 4 + 64));
         NODAL_HIP_TRY(h, H->apval.reserve((size_t)apw * ld * 8 + 64));
         NODAL_HIP_TRY(h, H->aplen.reserve((size_t)ld * 4 + 64));
+        L->fold = false;
+        L->fold_want = fold_wanted(l, n);
+        L->wslots = apw;
+        if (L->fold_want) {  // (W of the level, written beside A P)
+            NODAL_HIP_TRY(h, L->wcol.reserve((size_t)apw * ld * 4 + 64));
+            NODAL_HIP_TRY(h, L->wval.reserve((size_t)apw * ld * 4 + 64));
+            NODAL_HIP_TRY(h, L->wlen.reserve((size_t)ld * 4 + 64));
+        }
     }
     hipStream_t main_st = h->stream;
     struct StreamGuard {  // (whatever way this function is left, the context gets its stream back)
@@ -1622,6 +1758,85 @@ int form_tail_op(nodal_ctx *h, SHierarchy *H) {
     return NODAL_OK;
 }
 
+// NODAL_TRACE with NODAL_SA_FOLD_CHECK=1: per folded level both forms of the end of a visit -- k_prolong + k_post
+// against k_prolong_post -- on fixed vectors of both signs (x, b and the coarse correction uniform in (-1, 1), the
+// residual by k_smooth_residual as in the cycle).  Prints the level, its rows and
+//   d = max_i |m_fused - m_two|_i / (|x_i| + w dinv_i (|b_i| + sum_j |a_ij| |xp_j|) + sum_s |w_is| |e|),
+// and q = the largest d_i over the row's own bound (slots + width + 8) 2^-23 (operands stored f32, sums in f64).
+template <typename TC>
+int fold_check_level(nodal_ctx *h, SHierarchy *H, int l, bool two) {
+    hipStream_t st = h->stream;
+    const SLevel *L = H->pool[l];
+    const int64_t n = L->n, nc = H->pool[l + 1]->n;
+    const Ell A = L->A();
+    uint64_t seed = 0x9e3779b97f4a7c15ull + (uint64_t)l;
+    auto unit = [&]() {  // (splitmix64: uniform in (-1, 1))
+        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        return (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
+    };
+    std::vector<cyc_t> hx((size_t)n), hb((size_t)n);
+    std::vector<TC> he((size_t)2 * nc);
+    for (auto &v : hx) v = (cyc_t)unit();
+    for (auto &v : hb) v = (cyc_t)unit();
+    for (auto &v : he) v = (TC)unit();
+    const double hcoef[2] = {0.9, 0.4};
+    const size_t vb = align256((size_t)n * sizeof(cyc_t)), eb = align256((size_t)nc * sizeof(TC)), db = align256((size_t)n * 8);
+    DevBuf buf;
+    hipError_t e = buf.reserve(6 * vb + 2 * eb + 2 * db + 256);
+    char *p = buf.as<char>();
+    cyc_t *x = reinterpret_cast<cyc_t *>(p), *b = reinterpret_cast<cyc_t *>(p + vb), *r = reinterpret_cast<cyc_t *>(p + 2 * vb),
+          *xp = reinterpret_cast<cyc_t *>(p + 3 * vb), *mt = reinterpret_cast<cyc_t *>(p + 4 * vb),
+          *mf = reinterpret_cast<cyc_t *>(p + 5 * vb);
+    TC *c1 = reinterpret_cast<TC *>(p + 6 * vb), *c2 = reinterpret_cast<TC *>(p + 6 * vb + eb);
+    double *d = reinterpret_cast<double *>(p + 6 * vb + 2 * eb), *q = reinterpret_cast<double *>(p + 6 * vb + 2 * eb + db);
+    double *coef = reinterpret_cast<double *>(p + 6 * vb + 2 * eb + 2 * db);
+    std::vector<double> hd((size_t)n), hq((size_t)n);
+    if (e == hipSuccess) e = hipMemcpyAsync(x, hx.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(b, hb.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c1, he.data(), (size_t)nc * sizeof(TC), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c2, he.data() + nc, (size_t)nc * sizeof(TC), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(coef, hcoef, sizeof hcoef, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        const unsigned g = grid_for(n), tb = L->wfix ? TB : TB * LPR_RAGGED;
+        const double *dinv = L->dinv.as<double>(), *cf = two ? coef : nullptr;
+        const int32_t *wcol = L->wcol.as<int32_t>(), *wlen = L->wlen.as<int32_t>();
+        const float *wval = L->wval.as<float>();
+        SAGG_DISPATCH_W(L->wfix, (k_smooth_residual<W, cyc_t><<<g, tb, 0, st>>>(A, b, x, r)));
+        k_prolong<TC><<<g, TB, 0, st>>>(n, L->ld, L->pcol.as<int32_t>(), L->pvalf.as<float>(), x, c1, two ? c2 : nullptr, cf, xp);
+        SAGG_DISPATCH_W(L->wfix, (k_post<W, false, cyc_t, cyc_t><<<g, tb, 0, st>>>(A, dinv, b, xp, mt, nullptr, nullptr, nullptr)));
+        k_prolong_post<TC, cyc_t><<<g, TB, 0, st>>>(n, L->ld, wcol, wval, wlen, x, r, dinv, c1, two ? c2 : nullptr, cf, mf);
+        k_fold_check<TC><<<g, TB, 0, st>>>(A, dinv, b, x, xp, wcol, wval, wlen, c1, two ? c2 : nullptr, cf, mt, mf, d, q);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(hd.data(), d, (size_t)n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hq.data(), q, (size_t)n * 8, hipMemcpyDeviceToHost);
+    buf.release();
+    NODAL_HIP_TRY(h, e);
+    double dm = 0.0, qm = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        dm = !(hd[i] <= dm) ? hd[i] : dm;  // (a NaN stays)
+        qm = !(hq[i] <= qm) ? hq[i] : qm;
+    }
+    fprintf(stderr, "[sagg] fold check: level %d, rows %lld, slots %d, width %d, fused launch against the two d = %.3e "
+                    "(worst row against its own bound: %.3e)\n", l, (long long)n, (int)L->wslots, (int)L->maxlen, dm, qm);
+    return NODAL_OK;
+}
+int fold_self_check(nodal_ctx *h, SHierarchy *H) {
+    static const bool check = getenv("NODAL_TRACE") && getenv("NODAL_SA_FOLD_CHECK") && atoi(getenv("NODAL_SA_FOLD_CHECK")) != 0;
+    if (!check) return NODAL_OK;
+    for (int l = 0; l + 1 < H->nlev; ++l) {
+        if (!H->pool[l]->fold) continue;
+        const bool last = l + 1 == H->tail || l + 1 == H->nlev - 1;  // (as cycle() tells the two hand-overs apart)
+        if (last) NODAL_TRY(fold_check_level<double>(h, H, l, false));
+        else NODAL_TRY(fold_check_level<cyc_t>(h, H, l, true));
+    }
+    return NODAL_OK;
+}
+
 int build_tail(nodal_ctx *h, SHierarchy *H, const unsigned long long *hs) {
     H->tail = -1;
     H->tail_dense = false;
@@ -1768,6 +1983,8 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
     if (hs[ST_BADDIAG] || (int64_t)hs[ST_GRADED] >= bar) return NODAL_OK;
     for (int k = 1; k < H->nlev; ++k)
         if (hs[(size_t)k * ST_COUNT + ST_BADDIAG] || hs[(size_t)k * ST_COUNT + ST_OVERFLOW]) return NODAL_OK;
+    decide_folds(H, hs, false);
+    NODAL_TRY(fold_self_check(h, H));
     *ok = true;
     return NODAL_OK;
 }
@@ -1924,6 +2141,7 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
     }
     H->nlev = l + 1;
     SLevel *last = H->level(l);
+    last->fold_want = last->fold = false;  // (build_level did not get to it)
     if (H->nlev < 2) return NODAL_OK;  // too small for a hierarchy: the caller's other paths
     // statistics of the last level (its Galerkin kernel ran after the last round trip)
     NODAL_HIP_TRY(h, hipMemcpyAsync(hs, dstats, (size_t)MAX_LEVELS * ST_COUNT * 8, hipMemcpyDeviceToHost, st));
@@ -2010,6 +2228,8 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
         fprintf(stderr, "  tail %d (%d register slots)  coarsest %s\n", H->tail, H->tail >= 0 ? H->td.slots : 0,
                 H->dense_coarsest ? "dense" : "diagonal");
     }
+    decide_folds(H, hs, trace);
+    NODAL_TRY(fold_self_check(h, H));
     H->ready = true;
     *accepted = true;
     H->sym_valid = true;
@@ -2081,6 +2301,21 @@ int cycle(nodal_ctx *h, SHierarchy *H, int l, const TBV *b, const cyc_t *x0, TOU
     const unsigned g = sb ? (unsigned)sb->g0 : grid_for(n);
     const unsigned tb = L->wfix ? TB : TB * LPR_RAGGED;  // (ragged rows: LPR_RAGGED lanes each, same rows per workgroup)
     const int nu = H->nu[l < 2 ? l : 2];
+    // Prolongation and the first post-smoothing sweep in one launch, m = x + w D^-1 r + W e (SLevel::wcol): r = b - A x
+    // is the residual k_smooth_residual leaves below.  One sweep with the outer iteration's dot products (reachable
+    // through NODAL_SA_NU only) keeps the two launches: k_post<W, true> forms the dots.
+    const bool fold = L->fold && !(sb && nu == 1);
+    auto hand_up = [&](const auto *c1, const auto *c2, const double *cf) {  // the coarse correction goes up into xp
+        using TC = std::remove_cv_t<std::remove_pointer_t<decltype(c1)>>;
+        if (!fold)
+            k_prolong<TC><<<grid_for(n), TB, 0, st>>>(n, L->ld, L->pcol.as<int32_t>(), L->pvalf.as<float>(), x, c1, c2, cf, xp);
+        else if (nu == 1)  // the visit's only post-smoothing sweep: straight into its result
+            k_prolong_post<TC, TOUT><<<grid_for(n), TB, 0, st>>>(n, L->ld, L->wcol.as<int32_t>(), L->wval.as<float>(),
+                                                               L->wlen.as<int32_t>(), x, r, dinv, c1, c2, cf, out);
+        else
+            k_prolong_post<TC, cyc_t><<<grid_for(n), TB, 0, st>>>(n, L->ld, L->wcol.as<int32_t>(), L->wval.as<float>(),
+                                                                L->wlen.as<int32_t>(), x, r, dinv, c1, c2, cf, xp);
+    };
     if (nu >= 2) {  // second pre-smoothing sweep: x1 = x0 + w D^-1 (b - A x0)
         cyc_t *x1 = L->v<cyc_t>(V_X1);
         SAGG_DISPATCH_W(L->wfix, (k_post<W, false, TBV, cyc_t><<<g, tb, 0, st>>>(A, dinv, b, x0, x1, nullptr, nullptr, nullptr)));
@@ -2100,8 +2335,7 @@ int cycle(nodal_ctx *h, SHierarchy *H, int l, const TBV *b, const cyc_t *x0, TOU
                                                             L->rlen.as<int32_t>(), r, rc, C->dinv.as<double>(), nullptr);
         NODAL_HIP_TRY(h, hipGetLastError());
         NODAL_TRY(last_level(h, H, l + 1, rc, c1));
-        k_prolong<double><<<grid_for(n), TB, 0, st>>>(n, L->ld, L->pcol.as<int32_t>(), L->pvalf.as<float>(), x, c1,
-                                                     (const double *)nullptr, nullptr, xp);
+        hand_up((const double *)c1, (const double *)nullptr, nullptr);
     } else {
         cyc_t *rc = C->v<cyc_t>(V_RC), *c1 = C->v<cyc_t>(V_C1), *c2 = C->v<cyc_t>(V_C2), *x0c = C->v<cyc_t>(V_X);
         k_restrict<cyc_t><<<grid_for(nc * RL), TB, 0, st>>>(nc, L->rld, L->rcol.as<int32_t>(), L->rvalf.as<float>(),
@@ -2148,16 +2382,20 @@ int cycle(nodal_ctx *h, SHierarchy *H, int l, const TBV *b, const cyc_t *x0, TOU
             k_kcoef<<<1, 320, 0, st>>>(C->part.as<double>(), nparts, cf, sample ? H->kslot : -1, sample ? H->kcount : 0);
             coef = cf;
         }
-        k_prolong<cyc_t><<<grid_for(n), TB, 0, st>>>(n, L->ld, L->pcol.as<int32_t>(), L->pvalf.as<float>(), x, c1, c2, coef,
-                                                    xp);
+        hand_up((const cyc_t *)c1, (const cyc_t *)c2, coef);
     }
     const cyc_t *cur = xp;
-    if (nu >= 2) {  // first of two post-smoothing sweeps
+    const int left = fold ? nu - 1 : nu;  // post-smoothing sweeps still to run on `cur`
+    if (left == 0) {  // (the folded launch wrote `out`)
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return NODAL_OK;
+    }
+    if (left >= 2) {  // first of two post-smoothing sweeps
         cyc_t *mid = L->v<cyc_t>(V_T);
         SAGG_DISPATCH_W(L->wfix, (k_post<W, false, TBV, cyc_t><<<g, tb, 0, st>>>(A, dinv, b, cur, mid, nullptr, nullptr, nullptr)));
         cur = mid;
     }
-    if (nu >= 3) {  // second of three
+    if (left >= 3) {  // second of three
         cyc_t *mid2 = L->v<cyc_t>(V_X1);
         SAGG_DISPATCH_W(L->wfix, (k_post<W, false, TBV, cyc_t><<<g, tb, 0, st>>>(A, dinv, b, cur, mid2, nullptr, nullptr, nullptr)));
         cur = mid2;
@@ -2380,6 +2618,8 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
             const void *ps[] = {L->acol.p, L->aval.p, L->avalf.p, L->alen.p, L->dinv.p, L->pcol.p, L->pvalf.p,
                                 L->rcol.p, L->rvalf.p, L->rlen.p, L->vec.p, L->part.p};
             for (const void *q : ps) mix((uint64_t)(uintptr_t)q);
+            mix((uint64_t)(L->fold ? 1 + L->wslots : 0));
+            if (L->fold) { mix((uint64_t)(uintptr_t)L->wcol.p); mix((uint64_t)(uintptr_t)L->wval.p); mix((uint64_t)(uintptr_t)L->wlen.p); }
             mix((uint64_t)L->n); mix((uint64_t)L->ld); mix((uint64_t)L->wfix); mix((uint64_t)L->rld);
         }
         if (H->it_exec && H->it_key != key) H->drop_graph();

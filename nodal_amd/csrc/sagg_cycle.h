@@ -373,6 +373,80 @@ __global__ __launch_bounds__(TB * RowLanes<W>::value) void k_post(Ell A, const d
     }
 }
 
+// k_prolong and the first k_post behind it in one launch.  With xp = x + P e and r = b - A x (k_smooth_residual's, a few
+// launches earlier, of the same x):
+//     xp + w D^-1 (b - A xp) = (x + w D^-1 r) + (P - w D^-1 (A P)) e = m0 + W e.
+// m0 is row-local; W has the pattern of the row of A P and is written beside it by the setup (SLevel::wcol: `len[i]`
+// slots, column-major like P, f32).  The launch gathers from the small coarse vector only: the pass over the level's
+// matrix is gone, and so is one launch.  No symmetry is used.  One thread per row; a batch's Q columns and values are
+// requested before the first gather (unconditional loads: a slot past the end re-reads the batch's first one).
+// e = c1, or s1 c1 + s2 c2 at the K-cycle level (coef), as in k_prolong.
+template <typename TC, typename TOUT>
+__global__ __launch_bounds__(TB) void k_prolong_post(int64_t n, int64_t ld, const int32_t *__restrict__ wcol,
+                                                     const float *__restrict__ wval, const int32_t *__restrict__ wlen,
+                                                     const cyc_t *__restrict__ x, const cyc_t *__restrict__ r,
+                                                     const double *__restrict__ dinv, const TC *__restrict__ c1,
+                                                     const TC *__restrict__ c2, const double *__restrict__ coef,
+                                                     TOUT *__restrict__ out) {
+    constexpr int Q = 8;
+    const bool two = coef != nullptr;
+    const double s1 = two ? coef[0] : 1.0, s2 = two ? coef[1] : 0.0;
+    for (int64_t i = (int64_t)xcd_block() * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+        const int32_t len = wlen[i];
+        const cyc_t xi = x[i], ri = r[i];
+        const double di = dinv[i];
+        double acc = 0.0;
+        for (int32_t s0 = 0; s0 < len; s0 += Q) {
+            int32_t J[Q];
+            double w[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const bool ok = s0 + q < len;
+                const int64_t at = (int64_t)(ok ? s0 + q : s0) * ld + i;
+                J[q] = wcol[at];
+                const float loaded = wval[at];
+                w[q] = ok ? (double)loaded : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const double e = two ? s1 * (double)c1[J[q]] + s2 * (double)c2[J[q]] : (double)c1[J[q]];
+                acc = fma(w[q], e, acc);
+            }
+        }
+        out[i] = (TOUT)(fma(OMEGA * di, (double)ri, (double)xi) + acc);
+    }
+}
+
+// NODAL_SA_FOLD_CHECK (sagg.hip, fold_self_check): per row the difference of the two forms over the sum of the
+// magnitudes that enter either of them, d[i], and the same over the row's own bound (slots + width + 8) 2^-23, q[i]
+template <typename TC>
+__global__ __launch_bounds__(TB) void k_fold_check(Ell A, const double *__restrict__ dinv, const cyc_t *__restrict__ b,
+                                                   const cyc_t *__restrict__ x, const cyc_t *__restrict__ xp,
+                                                   const int32_t *__restrict__ wcol, const float *__restrict__ wval,
+                                                   const int32_t *__restrict__ wlen, const TC *__restrict__ c1,
+                                                   const TC *__restrict__ c2, const double *__restrict__ coef,
+                                                   const cyc_t *__restrict__ m_two, const cyc_t *__restrict__ m_fused,
+                                                   double *__restrict__ d, double *__restrict__ q) {
+    const bool two = coef != nullptr;
+    const double s1 = two ? coef[0] : 1.0, s2 = two ? coef[1] : 0.0;
+    for (int64_t i = (int64_t)xcd_block() * TB + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * TB) {
+        double ax = 0.0, we = 0.0;
+        const int32_t la = A.len[i], lw = wlen[i];
+        for (int32_t s = 0; s < la; ++s)
+            ax += fabs((double)A.valf[(int64_t)s * A.ld + i]) * fabs((double)xp[A.col[(int64_t)s * A.ld + i]]);
+        for (int32_t s = 0; s < lw; ++s) {
+            const int32_t j = wcol[(int64_t)s * A.ld + i];
+            const double e = two ? s1 * (double)c1[j] + s2 * (double)c2[j] : (double)c1[j];
+            we += fabs((double)wval[(int64_t)s * A.ld + i]) * fabs(e);
+        }
+        const double den = fabs((double)x[i]) + OMEGA * dinv[i] * (fabs((double)b[i]) + ax) + we;
+        const double diff = fabs((double)m_fused[i] - (double)m_two[i]);
+        const double di = diff / den;  // (0 / 0: a NaN, which the host's maximum keeps)
+        d[i] = di;
+        q[i] = di / ((double)(lw + la + 8) * 0x1p-23);
+    }
+}
+
 // v = A c and the partial dot products c.v, c.u1 (and c.u2 when given)
 template <int W>
 __global__ __launch_bounds__(TB * RowLanes<W>::value) void k_spmv_dots(Ell A, const cyc_t *__restrict__ c, cyc_t *__restrict__ v,

@@ -5,7 +5,7 @@ bench.py for `roofline.by_class` / `top_kernel_by_time`).
     python tools/prof_classes.py DIR cfg3 1000000 4995995 > profiles/r03_classes_cfg3.json
 
 Dispatches are told apart by kernel name AND grid size: the level-0 launches of the cycle kernels
-(k_restrict, k_prolong, ...) are the ones whose grid covers the 1e6 rows; the row kernels of level 0
+(k_restrict, k_prolong, k_prolong_post, ...) are the ones whose grid covers the 1e6 rows; the row kernels of level 0
 run on a grid capped at 1024 workgroups and are recognised by their width class (<5, ...>).  Algorithmic bytes of the
 level-0 passes: rows x bytes per row of what the kernel reads and writes.
 """
@@ -21,6 +21,9 @@ LEVEL0_BYTES = {
     "k_restrict": 4 * 8 + 4 + 8 / 7.0,                   # R entries (col + f32 val) of the 4 P slots per fine row, r, rc
     "k_prolong": 4 * 8 + 4 + 4 + 8 / 7.0,                # P (col + f32 val) x 4, x, xp, coarse gathers
     "k_post": _F32ROW + 8 + 4 + 4 + 4 + 8 + 8,           # A, b (f64), xp gather + own, out (z), u (Ap, f64), dinv
+    # (level 0 folds its first post-smoothing sweep only under NODAL_SA_FOLD_POST=1 / l0: off by default at 1e6 rows)
+    "k_prolong_post": 11 * 8 + 4 + 4 + 4 + 8 + 4 + 2 * 8 / 7.0,  # W (col + f32 val) x ~11 of 9-13 slots, its length, x, r,
+                                                         # dinv, out, coarse gathers (two vectors at the K-cycle level)
     "f_spmv": _F64ROW + 8 + 8 + 8,                       # A (f64), p gather + own, Ap
     "f_dir_spmv": _F64ROW + 8 + 4 + 8 + 8,               # A (f64), p_old and z gathered, the new direction, Ap
     "f_direction": 4 + 8 + 8,                            # z, p, p
