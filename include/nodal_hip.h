@@ -281,6 +281,20 @@ int nodal_debug_gemm(nodal_handle h, int32_t M, int32_t N, int32_t K, const doub
 /* the rhs columns nodal_solve_sources builds for the same arguments, [count][n] row-major */
 int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const int64_t *rows,
                             const double *values, double *rhs_out);
+/* The library's two residual judges -- the code behind nodal_residual and behind every resid_out / info_out of the
+ * sweeps and the sensitivities -- on host vectors of the caller's choosing, which need not solve anything.
+ * cols == 0: the single-vector judge on x[n], b[n] (b == NULL: the assembled right-hand side; layout must be 0).
+ *   scaled_out[1]; norms_out[5] = {max|Gx-b|, max row sum |G|, max|x|, max|b|, poison flag} as the kernel leaves them.
+ * cols 1 .. 16: the block judge on `cols` columns, element (i, y) of x and of b at [i * rs + y * cs]:
+ *   layout 0: [cols][n] rows (rs 1, cs n); 1: interleaved [n][16] (rs 16, cs 1); 2: one shared column (rs 1, cs 0;
+ *   cols must be 1).  scaled_out[cols]; norms_out[16 * 4]: per column y {max|b-Gx|, max|x|, max|b|} at [4y .. 4y+2],
+ *   and the max row sum |G| at [3].
+ * transposed != 0: against the G^T that the last nodal_sensitivities left on a handle whose network is not passive
+ *   (its values are those of that call); b must be given.  NODAL_E_INVALID when the handle holds none.
+ * Needs nodal_assemble_numeric (NODAL_E_INVALID otherwise, as for any other combination of cols and layout).  Leaves
+ * the handle as it found it: solution, right-hand side, table, hierarchies and factorisations; scratch of its own. */
+int nodal_debug_residual(nodal_handle h, int32_t transposed, int32_t cols, int32_t layout, const double *x,
+                         const double *b, double *scaled_out, double *norms_out);
 
 #ifdef __cplusplus
 }

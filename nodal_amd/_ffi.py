@@ -65,6 +65,7 @@ SIGNATURES = {
     "nodal_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "nodal_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
     "nodal_debug_sources_rhs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i64p, _f64p, _f64p]),
+    "nodal_debug_residual": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p]),
 }
 
 _lib = None
@@ -359,6 +360,26 @@ class Handle:
         self._check(self.lib.nodal_debug_sources_rhs(self._h, values.shape[0], len(rows), _ptr(rows, C.c_int64),
                                                      _ptr(values, C.c_double), _ptr(out, C.c_double)))
         return out
+
+    def debug_residual(self, x, b=None, cols=0, layout=0, transposed=False):
+        """The library's residual judges on vectors of the caller's choosing (testing hook).  cols 0: the
+        single-vector judge on x [n], b [n] (None: the assembled right-hand side); returns (scaled residual,
+        norms [5] = max|Gx-b|, max row sum |G|, max|x|, max|b|, poison flag).  cols 1..16: the block judge on x, b of
+        shape [cols, n] (layout 0), [n, 16] (layout 1) or [n] (layout 2, cols 1); returns (scaled [cols], norms
+        [16, 4]: per column max|b-Gx|, max|x|, max|b|; [0, 3] = max row sum |G|).  transposed: against the G^T the
+        last sensitivities() call left on the handle."""
+        shape = (self.n,) if cols == 0 or layout == 2 else (cols, self.n) if layout == 0 else (self.n, 16)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.shape == shape, (x.shape, shape)
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float64)
+            assert b.shape == shape, (b.shape, shape)
+        scaled = np.zeros(max(cols, 1), dtype=np.float64)
+        norms = np.zeros(5 if cols == 0 else 64, dtype=np.float64)
+        self._check(self.lib.nodal_debug_residual(self._h, int(bool(transposed)), cols, layout, _ptr(x, C.c_double),
+                                                  _ptr(b, C.c_double) if b is not None else None,
+                                                  _ptr(scaled, C.c_double), _ptr(norms, C.c_double)))
+        return (float(scaled[0]), norms) if cols == 0 else (scaled, norms.reshape(16, 4))
 
     def download_x(self):
         x = host_empty(self.n, np.float64)

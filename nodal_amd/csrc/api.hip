@@ -265,7 +265,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->gn_rowidx, &h->gn_data, &h->gn_diag, &h->schur, &h->ps_buf, &h->ps_newidx,
                       &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none,
                       &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk, &h->br_out, &h->br_part, &h->br_tot,
-                      &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm};
+                      &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->dbg_resid};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     h->evpool.clear();
@@ -828,6 +828,14 @@ int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const i
     if (h->hung) return NODAL_E_HIP;
     NODAL_TRY(sweep_prepare(h, count, nsrc, rows, values));
     return sparse_sources_rhs(h, count, nsrc, h->sw_vals.as<double>(), h->sw_slot.as<int32_t>(), rhs_out);
+}
+
+int nodal_debug_residual(nodal_handle h, int32_t transposed, int32_t cols, int32_t layout, const double *x,
+                         const double *b, double *scaled_out, double *norms_out) {
+    if (!h) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return sparse_debug_residual(h, transposed != 0, cols, layout, x, b, scaled_out, norms_out);
 }
 
 int nodal_residual(nodal_handle h, double *scaled_residual) {

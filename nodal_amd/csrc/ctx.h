@@ -203,6 +203,7 @@ struct nodal_ctx {
     int64_t sn_ndrivers = 0, sn_ncross = 0;
     nodal_ctx *adjoint = nullptr;
     uint64_t adjoint_epoch = 0;
+    DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
     // matrix-only context (no component table) that inherits the grounded-node flags
     nodal_ctx *lowdeg = nullptr;
@@ -501,6 +502,12 @@ int lowdeg_solve(nodal_ctx *h, int min_share, bool *done, int32_t *info, int32_t
 // ---- sparse solvers (sparse_*.hip) ----
 int sparse_solve(nodal_ctx *h, int32_t method, int32_t *info, int32_t *iters, double *resid);
 int sparse_residual(nodal_ctx *h, double *scaled);
+// |G x - b|_inf / (|G|_inf |x|_inf + |b|_inf) for any device vectors x, b with the context's CSR matrix; norms5 (host, may
+// be null) receives the five words residual_kernel leaves
+int csr_scaled_residual(nodal_ctx *h, const double *x, const double *b, double *scaled, double *norms5 = nullptr);
+// testing hook (nodal_debug_residual): the single-vector judge (cols 0) or the block judge (cols 1 .. 16) on host vectors
+int sparse_debug_residual(nodal_ctx *h, bool transposed, int32_t cols, int32_t layout, const double *x, const double *b,
+                          double *scaled_out, double *norms_out);
 // dense_child: solve the reduced system by the dense block elimination (only if it is passive)
 void presolve_plan_ahead(nodal_ctx *h);  // host-only; called by stamp_numeric while its kernels run
 void presolve_free_plan(nodal_ctx *h);

@@ -754,6 +754,21 @@ __global__ __launch_bounds__(TB) void copy_rhs_column(const double *__restrict__
 
 }  // namespace
 
+// The block judgement: scaled residuals of the `cols` (<= 16) columns of x against b (element (i, y) at [i * rs + y * cs])
+// with the CSR matrix of context `m`, on m's stream.  norms (device): [16][4] maxima as resid_norms_multi leaves them, then
+// [16] scaled residuals.  Nothing is read back.  The one body of SweepCtx::judge, AdjointCtx::judge and
+// nodal_debug_residual.
+int csr_judge_block(nodal_ctx *m, const double *x, const double *b, int64_t rs, int64_t cs, int cols, double *norms) {
+    const int64_t n = m->n;
+    NODAL_HIP_TRY(m, hipMemsetAsync(norms, 0, (size_t)(4 + 1) * SLU_MULTI * 8, m->stream));
+    const unsigned g = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 1024);
+    resid_norms_multi<<<g, TB, 0, m->stream>>>(n, m->indptr.as<int32_t>(), m->indices.as<int32_t>(),
+                                              m->data.as<double>(), x, b, rs, cs, cols, norms);
+    scaled_from_norms<<<1, 64, 0, m->stream>>>(norms, cols, norms + 4 * SLU_MULTI);
+    NODAL_HIP_TRY(m, hipGetLastError());
+    return NODAL_OK;
+}
+
 int dense_prepare(nodal_ctx *h) {
     const int64_t n = h->n, lda = dense_lda(n);
     NODAL_HIP_TRY(h, h->dense.reserve((size_t)lda * (size_t)(n + 1) * 8 + 64));
@@ -959,13 +974,7 @@ struct SweepCtx {
     }
     // resid[m0 + y] for the cols columns of x / b (layout as in fold): one read-back, i.e. one wait
     int judge(int32_t m0, int cols, const double *x, const double *b, int64_t rs, int64_t cs) const {
-        const int64_t n = h->n;
-        NODAL_HIP_TRY(h, hipMemsetAsync(norms, 0, (size_t)(4 + 1) * SLU_MULTI * 8, h->stream));
-        const unsigned g = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 1024);
-        resid_norms_multi<<<g, TB, 0, h->stream>>>(n, h->indptr.as<int32_t>(), h->indices.as<int32_t>(),
-                                                  h->data.as<double>(), x, b, rs, cs, cols, norms);
-        scaled_from_norms<<<1, 64, 0, h->stream>>>(norms, cols, norms + 4 * SLU_MULTI);
-        NODAL_HIP_TRY(h, hipGetLastError());
+        NODAL_TRY(csr_judge_block(h, x, b, rs, cs, cols, norms));
         return nodal_read_words(h, resid + m0, norms + 4 * SLU_MULTI, (size_t)cols * 8);
     }
     // rows [cols][n] of members m0 .. to the caller, and wait.  Every route ends here with the members' final rows
@@ -1439,11 +1448,13 @@ int csr_spmv(nodal_ctx *h, const double *x, double *y) {
     return NODAL_OK;
 }
 
-// |G x - b|_inf / (|G|_inf |x|_inf + |b|_inf) for any device vectors (NaN if x holds one)
-int csr_scaled_residual(nodal_ctx *h, const double *x, const double *b, double *scaled) {
+// |G x - b|_inf / (|G|_inf |x|_inf + |b|_inf) for any device vectors (NaN if x holds one); norms5 (host, may be null)
+// receives the five words residual_kernel leaves
+int csr_scaled_residual(nodal_ctx *h, const double *x, const double *b, double *scaled, double *norms5) {
     const int64_t n = h->n;
     if (n == 0) {
         *scaled = 0.0;
+        if (norms5) memset(norms5, 0, 40);
         return NODAL_OK;
     }
     NODAL_HIP_TRY(h, h->status.reserve(64));
@@ -1455,6 +1466,7 @@ int csr_scaled_residual(nodal_ctx *h, const double *x, const double *b, double *
     NODAL_HIP_TRY(h, hipGetLastError());
     double o[5];
     NODAL_TRY(nodal_read_words(h, o, out, 40));
+    if (norms5) memcpy(norms5, o, 40);
     if (o[4] != 0.0) {
         *scaled = __builtin_nan("");
         return NODAL_OK;
@@ -1468,6 +1480,55 @@ int sparse_residual(nodal_ctx *h, double *scaled) {
     if (!h->have_numeric || !h->have_x)
         return nodal_fail(h, NODAL_E_INVALID, "no assembled system / solution on the device");
     return csr_scaled_residual(h, h->x.as<double>(), h->rhs.as<double>(), scaled);
+}
+
+// testing hook (nodal_debug_residual): the two judges above on the caller's own vectors.  Scratch of its own
+// (dbg_resid); x, rhs, the solution flag, the table, the hierarchies and the factorisations stay as they are.
+int sparse_debug_residual(nodal_ctx *h, bool transposed, int32_t cols, int32_t layout, const double *x, const double *b,
+                          double *scaled_out, double *norms_out) {
+    if (h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "debug_residual: a matrix-only context");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "assemble_numeric not called");
+    const bool shape_ok = cols == 0 ? layout == 0
+                                    : cols >= 1 && cols <= SLU_MULTI && (layout == 0 || layout == 1 || (layout == 2 && cols == 1));
+    if (!shape_ok || !x || !scaled_out || !norms_out || (!b && (cols != 0 || transposed)))
+        return nodal_fail(h, NODAL_E_INVALID, "debug_residual: bad cols, layout or vectors");
+    nodal_ctx *m = h;
+    if (transposed) {
+        m = h->adjoint;
+        if (!m || !m->have_numeric || h->adjoint_epoch != h->struct_epoch || m->n != h->n || m->nnz != h->nnz)
+            return nodal_fail(h, NODAL_E_INVALID, "debug_residual: the handle holds no transposed matrix");
+    }
+    const int64_t n = h->n;
+    const int nwords = cols == 0 ? 5 : 4 * SLU_MULTI;
+    for (int k = 0; k < nwords; ++k) norms_out[k] = 0.0;
+    for (int y = 0; y < (cols == 0 ? 1 : cols); ++y) scaled_out[y] = 0.0;
+    if (n == 0) return NODAL_OK;
+    // element (i, y) at [i * rs + y * cs]; the caller's arrays hold `count` doubles in exactly that layout
+    const int64_t rs = layout == 1 ? SLU_MULTI : 1, cs = layout == 0 ? n : layout == 1 ? 1 : 0;
+    const size_t count = cols == 0 || layout == 2 ? (size_t)n : layout == 0 ? (size_t)n * cols : (size_t)n * SLU_MULTI;
+    const size_t vec = align_up(count * 8);
+    NODAL_HIP_TRY(h, h->dbg_resid.reserve(2 * vec + 5 * SLU_MULTI * 8 + 256));
+    double *dx = h->dbg_resid.as<double>(), *db = dx + vec / 8, *norms = db + vec / 8;
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dx, x, count * 8, hipMemcpyHostToDevice, h->stream));
+    if (b) NODAL_HIP_TRY(h, hipMemcpyAsync(db, b, count * 8, hipMemcpyHostToDevice, h->stream));
+    int st;
+    if (cols == 0) {
+        st = csr_scaled_residual(m, dx, b ? db : h->rhs.as<double>(), scaled_out, norms_out);  // (waits)
+    } else {
+        st = csr_judge_block(m, dx, db, rs, cs, cols, norms);
+    }
+    if (st != NODAL_OK) {  // (a call on the matrix context: its error text is the handle's)
+        if (m != h) h->err = m->err;
+        (void)nodal_wait_stream(h, h->stream, NODAL_SITE);  // the copies above read the caller's arrays: not past this return
+        return st;
+    }
+    if (cols > 0) {
+        double words[5 * SLU_MULTI];
+        NODAL_TRY(nodal_read_words(h, words, norms, sizeof words));  // (waits)
+        memcpy(norms_out, words, (size_t)4 * SLU_MULTI * 8);
+        memcpy(scaled_out, words + 4 * SLU_MULTI, (size_t)cols * 8);
+    }
+    return NODAL_OK;
 }
 
 // ---- adjoint solves (nodal_sensitivities, sensitivity.hip) ------------------------------------------------------
@@ -1490,13 +1551,11 @@ struct AdjointCtx {
         return sens_rhs_block(h, call, m0, cols, out, rs, cs);
     }
     int judge(int32_t m0, int cols, const double *x, const double *b, int64_t rs, int64_t cs) const {
-        const int64_t n = h->n;
-        NODAL_HIP_TRY(h, hipMemsetAsync(norms, 0, (size_t)(4 + 1) * SLU_MULTI * 8, h->stream));
-        const unsigned g = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 1024);
-        resid_norms_multi<<<g, TB, 0, h->stream>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(),
-                                                  s->data.as<double>(), x, b, rs, cs, cols, norms);
-        scaled_from_norms<<<1, 64, 0, h->stream>>>(norms, cols, norms + 4 * SLU_MULTI);
-        NODAL_HIP_TRY(h, hipGetLastError());
+        const int st = csr_judge_block(s, x, b, rs, cs, cols, norms);  // (s: G^T, or the handle itself)
+        if (st != NODAL_OK) {
+            if (s != h) h->err = s->err;
+            return st;
+        }
         return nodal_read_words(h, resid + m0, norms + 4 * SLU_MULTI, (size_t)cols * 8);
     }
     // adjoints of outputs m0 .. (element (row, y) at lam[row * rs + y * cs]) through the table kernels, to the caller,

@@ -432,7 +432,6 @@ size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
 int csr_spmv(nodal_ctx *h, const double *x, double *y);  // sparse.hip
-int csr_scaled_residual(nodal_ctx *h, const double *x, const double *b, double *scaled);  // sparse.hip
 bool general_source_loop(const nodal_ctx *h);                // sparse.hip
 bool general_floating_island(const nodal_ctx *h);            // sparse.hip
 int grounded_flags(nodal_ctx *h, uint8_t *flags_dev);         // lowdeg.hip
