@@ -206,6 +206,29 @@ int nodal_sensitivities(nodal_handle h, int32_t dense, int32_t count, const int3
                         const int32_t *q2, double *sens_out, double *value_out, double *adjoint_out,
                         double *resid_out, int32_t *info_out);
 
+/* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
+ *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
+ *      reference has no equivalent of an active network and no coupling between ports) ----
+ * Port q is the ordered node pair (ia[q], ib[q]), either may be the ground node (-1, potential +0.0).  With G the matrix
+ * of the last nodal_assemble_numeric and s_q = e(ia[q]) - e(ib[q]) (zeros in the branch rows), x_q solves G x_q = s_q --
+ * G itself, not its transpose; the independent sources are off, the dependent ones stay -- and
+ *   z_out[p][q] = x_q[ia[p]] - x_q[ib[p]]   volts at port p per ampere entering ia[q] and leaving ib[q] (the sign of
+ *                                           nodal_solve_pairs), [nports][nports] row-major;
+ *   voc_out[p]  = x[ia[p]] - x[ib[p]]       for the solution x of the single solve on the handle (may be NULL),
+ * so that v = voc + z i for any currents i driven into the ports from outside.  A port with ia == ib has an all-zero row
+ * and column, exactly.  The solves are those of nodal_solve_sources (one factorisation or one multigrid hierarchy, sixteen
+ * ports to a block) and the finished blocks are read at the port nodes on the device (csrc/ports.hip): nports^2 numbers
+ * come down, not nports x n.
+ * resid_out [nports] = the scaled residual of column q as nodal_solve_sources defines it (may be NULL); info_out [nports]:
+ * > 0 a singular network (column q is NaN in every row, status OK) -- except with dense != 0, where a singular G
+ * returns NODAL_E_SINGULAR.  NODAL_E_INVALID: a node index outside [-1, K), no nodal_assemble_numeric before the call,
+ * voc_out without a solution on the handle (as nodal_branches).  nports == 0 does nothing; n == 0 gives zeros.
+ * Leaves the handle as it found it: the solution (if any), the table, G, A and what the last solve reported.  No
+ * floating-point atomics: a repeated call gives the same bits. */
+int nodal_port_matrix(nodal_handle h, int32_t dense, int32_t nports, const int32_t *ia, const int32_t *ib,
+                      double *z_out /* [nports][nports] row-major */, double *voc_out /* [nports], may be NULL */,
+                      double *resid_out /* [nports], may be NULL */, int32_t *info_out /* [nports] */);
+
 /* scaled residual ||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the
  * solution currently on the device, computed on the device from the CSR form */
 int nodal_residual(nodal_handle h, double *scaled_residual);

@@ -16,3 +16,4 @@ from nodal_amd import (  # noqa: F401  (the names the reference's `from .nodal i
 )
 from nodal_amd import Branches, Envelope  # noqa: F401  (additions the reference does not have: nodal_amd/branches.py)
 from nodal_amd import Sensitivities, resolve_outputs  # noqa: F401  (likewise: nodal_amd/sensitivity.py)
+from nodal_amd import PortEquivalent, resolve_ports  # noqa: F401  (likewise: nodal_amd/ports.py)

@@ -53,6 +53,7 @@ SIGNATURES = {
                                                _i32p, _f64p, _i32p, _f64p, _i32p, _f64p, _i32p, _f64p]),
     "nodal_sensitivities": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p,
                                       _i32p]),
+    "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
     "nodal_run_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _i32p]),
@@ -350,6 +351,24 @@ class Handle:
             _ptr(sens, C.c_double), _ptr(y, C.c_double), _ptr(lam, C.c_double) if adjoints else None,
             _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
         return sens, y, lam, resid, info
+
+    def port_matrix(self, ia, ib, dense, voc=True):
+        """The open-circuit impedance matrix seen from the ports (ia[q], ib[q]) (node indices, -1 ground;
+        ports.resolve_ports) and, with voc, their open-circuit voltages for the solution on the device.  Returns
+        (Z [P, P], V_oc [P] or None, info [P], scaled residual [P]); NodalHipError(E_INVALID) for an index out of
+        range or, with voc, when the handle holds no solution; with dense a singular G raises
+        NodalHipError(E_SINGULAR)."""
+        ia, ib = (np.ascontiguousarray(v, dtype=np.int32) for v in (ia, ib))
+        count = len(ia)
+        assert ia.ndim == 1 and ib.shape == ia.shape
+        z = np.zeros((count, count), dtype=np.float64)
+        v_oc = np.zeros(count, dtype=np.float64) if voc else None
+        resid = np.zeros(count, dtype=np.float64)
+        info = np.zeros(count, dtype=np.int32)
+        self._check(self.lib.nodal_port_matrix(
+            self._h, int(dense), count, _ptr(ia, C.c_int32), _ptr(ib, C.c_int32), _ptr(z, C.c_double),
+            _ptr(v_oc, C.c_double) if voc else None, _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
+        return z, v_oc, info, resid
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

@@ -300,6 +300,40 @@ class Circuit:
             warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
         return Sensitivities(self.netlist, outputs, values, y, info, resid, adjoints=lam, table=self.table)
 
+    def thevenin(self, ports, sources=True):
+        """The multiport Thevenin equivalent of the circuit seen from `ports`: a sequence of
+        (node_plus, node_minus) labels or of single labels (that node against ground;
+        ports.resolve_ports).  Returns a PortEquivalent (ports.py): `z` [P, P], the open-circuit
+        impedance matrix with the independent sources switched off and the dependent ones in place,
+        `v_oc` [P], the port voltages of the last solve()'s solution, `info`, `scaled_residual`, and
+        from them norton(), loaded(resistances), rows() (the reduced netlist).  The P solves are those
+        of solve_sources -- one factorisation or one multigrid hierarchy, sixteen ports to a block --
+        and only P x P numbers come to the host (nodal_port_matrix).
+
+        With sources=True there must be a solution on the device: ValueError otherwise, as branches().
+        With sources=False `v_oc` is None and no solve is needed.  Singular networks behave as in
+        solve_sources(): the dense path raises LinAlgError / UnconnectedCircuitError, the sparse path
+        returns NaN columns with info > 0 and warns once.  The circuit itself -- its solution, table,
+        G, A -- is left as it was."""
+        from .ports import PortEquivalent, _as_pair, resolve_ports
+        ports = [_as_pair(self.netlist, port) for port in ports]
+        ia, ib = resolve_ports(self.netlist, ports)
+        try:
+            z, v_oc, info, resid = self._handle.port_matrix(ia, ib, dense=not self.sparse, voc=bool(sources))
+        except _ffi.NodalHipError as exc:
+            if exc.status == _ffi.E_INVALID and "no solution" in str(exc):
+                raise ValueError("no solution: call solve() first") from None
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            if not is_connected(self.netlist):
+                logging.error("Model error: unconnected circuit")
+                raise UnconnectedCircuitError
+            logging.error("Model error: matrix is singular")
+            raise np.linalg.LinAlgError("Singular matrix")
+        if (info > 0).any():
+            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        return PortEquivalent(self.netlist, ports, z, v_oc, info, resid)
+
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last
         solution, computed on the device."""

@@ -265,7 +265,8 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->gn_rowidx, &h->gn_data, &h->gn_diag, &h->schur, &h->ps_buf, &h->ps_newidx,
                       &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none,
                       &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk, &h->br_out, &h->br_part, &h->br_tot,
-                      &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->dbg_resid};
+                      &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->pt_buf,
+                      &h->dbg_resid};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     h->evpool.clear();
@@ -819,6 +820,18 @@ int nodal_sensitivities(nodal_handle h, int32_t dense, int32_t count, const int3
     if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
     if (count == 0) return NODAL_OK;
     return sens_run(h, dense != 0, count, kind, p, q2, sens_out, value_out, adjoint_out, resid_out, info_out);
+}
+
+int nodal_port_matrix(nodal_handle h, int32_t dense, int32_t nports, const int32_t *ia, const int32_t *ib, double *z_out,
+                      double *voc_out, double *resid_out, int32_t *info_out) {
+    if (!h || nports < 0 || (nports > 0 && (!ia || !ib || !z_out || !info_out))) return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "port matrix: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "port matrix: assemble_numeric not called");
+    if (voc_out && !h->have_x) return nodal_fail(h, NODAL_E_INVALID, "port matrix: no solution on the handle");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    if (nports == 0) return NODAL_OK;
+    return port_run(h, dense != 0, nports, ia, ib, z_out, voc_out, resid_out, info_out);
 }
 
 int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const int64_t *rows, const double *values,

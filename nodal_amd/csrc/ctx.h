@@ -203,6 +203,9 @@ struct nodal_ctx {
     int64_t sn_ndrivers = 0, sn_ncross = 0;
     nodal_ctx *adjoint = nullptr;
     uint64_t adjoint_epoch = 0;
+    // multiport equivalents (ports.hip): the ports' nodes, Z [P][P] and V_oc [P] until they go down (the solution set
+    // aside during the call borrows sn_x)
+    DevBuf pt_buf;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
     // matrix-only context (no component table) that inherits the grounded-node flags
@@ -368,10 +371,13 @@ int stamp_sweep_slots(nodal_ctx *h, const int32_t *rows_dev, int32_t nsrc, int32
 int stamp_rhs_multi(nodal_ctx *h, const int32_t *slot_dev, const double *swept_dev, int32_t nsrc, int32_t cols,
                     double *out, int64_t rs, int64_t cs);
 // (env: the worst-case envelope of the sweep is kept on the device as the blocks are handed over, branch.hip; may be null)
+// (ports: the members are the unit injections of a port call, ports.hip -- their right-hand sides replace the folded
+// sources and their finished blocks are read at the port nodes on the device; may be null)
 struct BranchSweep;
+struct PortCall;
 int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
                          const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out,
-                         const BranchSweep *env = nullptr);
+                         const BranchSweep *env = nullptr, const PortCall *ports = nullptr);
 int sparse_sources_rhs(nodal_ctx *h, int32_t count, int32_t nsrc, const double *swept_dev, const int32_t *slot_dev,
                        double *rhs_out);
 
@@ -410,6 +416,22 @@ int sparse_solve_adjoint(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, 
 int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const int32_t *p, const int32_t *q2,
              double *sens_out, double *value_out, double *adjoint_out, double *resid_out, int32_t *info_out);
 void sens_free_child(nodal_ctx *h);
+
+// ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: sparse_solve_sources in sparse.hip) ----
+// one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])
+struct PortCall {
+    int32_t nports = 0;
+    const int32_t *ia = nullptr, *ib = nullptr;
+    double *z = nullptr;
+};
+// adds the entries of s_q = e(a_q) - e(b_q) of ports m0 .. m0 + cols - 1 (cols <= 16) into a zeroed block, element
+// (row, y) at out[row * rs + y * cs]
+int port_rhs_block(nodal_ctx *h, const PortCall *call, int32_t m0, int cols, double *out, int64_t rs, int64_t cs);
+// z[p][m0 + y] = X(a_p, y) - X(b_p, y) for the finished rows [cols][n] of those ports (cols <= 512); a column whose
+// info (host, indexed by port) is > 0 becomes NaN in every row
+int port_gather_block(nodal_ctx *h, const PortCall *call, int32_t m0, int cols, const double *rows, const int32_t *info);
+int port_run(nodal_ctx *h, bool dense, int32_t nports, const int32_t *ia, const int32_t *ib, double *z_out,
+             double *voc_out, double *resid_out, int32_t *info_out);
 
 // ---- fp64 MFMA GEMM (gemm_f64.hip), column-major ----
 enum { GEMM_SUB = 0, GEMM_SET = 1, GEMM_SETNEG = 2 };  // C -= A B | C = A B | C = -A B

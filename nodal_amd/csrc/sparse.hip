@@ -966,11 +966,17 @@ struct SweepCtx {
     int32_t *info;
     double *norms;  // [16][4] maxima + [16] scaled residuals (device)
     const BranchSweep *env = nullptr;  // the sweep's envelope (branch.hip), fed block by block below
+    const PortCall *ports = nullptr;   // a port call (ports.hip): the members are its unit injections
 
+    // the right-hand sides of members m0 .. m0 + cols - 1 (cols <= 16) added into a zeroed block
+    int build(int32_t m0, int cols, double *out, int64_t rs, int64_t cs) const {
+        if (ports) return port_rhs_block(h, ports, m0, cols, out, rs, cs);
+        return stamp_rhs_multi(h, slot, swept + (int64_t)m0 * nsrc, nsrc, cols, out, rs, cs);
+    }
     // member m0 .. m0 + cols - 1 (cols <= 16) into out[row * rs + y * cs], zeros elsewhere in an n x cols block
     int fold(int32_t m0, int cols, double *out, int64_t rs, int64_t cs, size_t block_bytes) const {
         NODAL_HIP_TRY(h, hipMemsetAsync(out, 0, block_bytes, h->stream));
-        return stamp_rhs_multi(h, slot, swept + (int64_t)m0 * nsrc, nsrc, cols, out, rs, cs);
+        return build(m0, cols, out, rs, cs);
     }
     // resid[m0 + y] for the cols columns of x / b (layout as in fold): one read-back, i.e. one wait
     int judge(int32_t m0, int cols, const double *x, const double *b, int64_t rs, int64_t cs) const {
@@ -982,6 +988,7 @@ struct SweepCtx {
     int hand_over(int32_t m0, int cols, const double *rows) const {
         const int64_t n = h->n;
         if (env) NODAL_TRY(branch_sweep_block(h, env, m0, cols, rows, info, swept, slot, nsrc));
+        if (ports) NODAL_TRY(port_gather_block(h, ports, m0, cols, rows, info));
         if (x_out)
             NODAL_HIP_TRY(h, hipMemcpyAsync(x_out + (int64_t)m0 * n, rows, (size_t)cols * n * 8, hipMemcpyDeviceToHost,
                                             h->stream));
@@ -1010,14 +1017,14 @@ void sweep_all_singular(const SweepCtx &c, int32_t count) {
 
 int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
                          const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out,
-                         const BranchSweep *env) {
+                         const BranchSweep *env, const PortCall *ports) {
     const int64_t n = h->n;
     hipStream_t st = h->stream;
     std::vector<double> resid_host(resid_out ? 0 : (size_t)count);
     for (int32_t m = 0; m < count; ++m) info_out[m] = 0;
     h->have_x = false;
     h->last_iterations = 0;
-    SweepCtx c{h, nsrc, swept_dev, slot_dev, x_out, resid_out ? resid_out : resid_host.data(), info_out, nullptr, env};
+    SweepCtx c{h, nsrc, swept_dev, slot_dev, x_out, resid_out ? resid_out : resid_host.data(), info_out, nullptr, env, ports};
     if (n == 0) {
         for (int32_t m = 0; m < count; ++m) c.resid[m] = 0.0;
         return NODAL_OK;
@@ -1043,7 +1050,7 @@ int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, 
             NODAL_HIP_TRY(h, hipMemsetAsync(cols, 0, (size_t)lda * m * 8, st));
             for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
                 const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
-                NODAL_TRY(stamp_rhs_multi(h, slot_dev, swept_dev + (int64_t)(q0 + g0) * nsrc, nsrc, k, cols + g0 * lda, 1, lda));
+                NODAL_TRY(c.build(q0 + g0, k, cols + g0 * lda, 1, lda));
                 NODAL_TRY(c.fold(q0 + g0, k, Bc + g0 * n, 1, n, (size_t)n * k * 8));
             }
             NODAL_HIP_TRY(h, h->solver.reserve((size_t)n * m * 8 + 64));

@@ -117,6 +117,50 @@ def equivalent_resistance_sweep(netlist, pairs, sparse=False):
     return [np.float64(r) for r in res]
 
 
+def resistance_matrix(netlist, terminals, sparse=False):
+    """The equivalent resistance between every two of K terminals of one resistive network, as a
+    K x K ndarray (zero diagonal, symmetric): R[i][j] is what `equivalent_resistance(netlist,
+    terminals[i], terminals[j])` gives, with the same exceptions for a non-resistive network or an
+    unknown node and the same literal-"g" rule for ground.
+
+    K - 1 solves instead of the K (K - 1) / 2 of a sweep over the pairs: with the ports
+    (t_i, t_0), i = 1 .. K-1, against the FIRST terminal, R_ij = Z'_ii + Z'_jj - Z'_ij - Z'_ji (row and
+    column 0 of Z' are zero).  Against the first terminal and not against ground: a network tied to
+    ground through a large resistance would lose the difference to cancellation.  One
+    nodal_port_matrix call (csrc/ports.hip); the dense path raises on a singular network as the sweep
+    does, the sparse path returns NaNs."""
+    import numpy as np
+    from . import _ffi
+    if not check_resistive(netlist):
+        raise ValueError("Network is not resistive")
+    index = []
+    for node in terminals:
+        if node not in netlist.nodenum and node != netlist.ground:
+            raise KeyError(f"Node `{node}` not found in netlist")
+        # the reference treats a node as grounded only if it is literally "g"
+        index.append(-1 if node == "g" else netlist.nodenum[node])
+    count = len(index)
+    out = np.zeros((count, count))
+    if count < 2:
+        return out
+    circuit = n.Circuit(netlist, sparse=sparse)
+    try:
+        z, _, info, _ = circuit._handle.port_matrix(index[1:], [index[0]] * (count - 1), dense=not sparse, voc=False)
+    except _ffi.NodalHipError as exc:
+        if exc.status != _ffi.E_SINGULAR or sparse:
+            raise
+        if not n.is_connected(netlist):
+            raise n.UnconnectedCircuitError
+        raise np.linalg.LinAlgError("Singular matrix")
+    zp = np.zeros((count, count))
+    zp[1:, 1:] = z
+    d = np.diag(zp)
+    out = d[:, None] + d[None, :] - zp - zp.T
+    out = 0.5 * (out + out.T)
+    np.fill_diagonal(out, 0.0)
+    return out
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     try:
