@@ -757,6 +757,37 @@ int sweep_prepare(nodal_ctx *h, int32_t count, int32_t nsrc, const int64_t *rows
     if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, "source sweep: a row named twice");
     return NODAL_OK;
 }
+
+// multi_rhs_solve's client for a source sweep: the columns are the members' folded sources, a finished block feeds the
+// envelope (branch.hip, when one is kept) and goes down to the caller as rows
+struct SweepClient final : MultiRhsClient {
+    nodal_ctx *h;
+    int32_t nsrc;
+    const double *swept;
+    const int32_t *slot;
+    double *x_out;        // host, [count][n]; may be null
+    const int32_t *info;  // the driver's flags (host), settled for a block by the time it is handed over
+    const BranchSweep *env;
+    SweepClient(nodal_ctx *h_, int32_t nsrc_, double *x_out_, const int32_t *info_, const BranchSweep *env_)
+        : h(h_), nsrc(nsrc_), swept(h_->sw_vals.as<double>()), slot(h_->sw_slot.as<int32_t>()), x_out(x_out_),
+          info(info_), env(env_) {}
+    int build(int32_t m0, int cols, double *out, int64_t rs, int64_t cs) override {
+        return stamp_rhs_multi(h, slot, swept + (int64_t)m0 * nsrc, nsrc, cols, out, rs, cs);
+    }
+    int hand_over(int32_t m0, int cols, const double *, int64_t, int64_t, const double *rows) override {
+        const int64_t n = h->n;
+        if (env) NODAL_TRY(branch_sweep_block(h, env, m0, cols, rows, info, swept, slot, nsrc));
+        if (x_out)
+            NODAL_HIP_TRY(h, hipMemcpyAsync(x_out + (int64_t)m0 * n, rows, (size_t)cols * n * 8, hipMemcpyDeviceToHost,
+                                            h->stream));
+        NODAL_WAIT_STREAM(h, h->stream);
+        return NODAL_OK;
+    }
+    void all_singular(int32_t count) override {
+        if (x_out)
+            for (int64_t t = 0; t < (int64_t)count * h->n; ++t) x_out[t] = __builtin_nan("");
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -792,8 +823,8 @@ int nodal_solve_sources_branches(nodal_handle h, int32_t dense, int32_t count, i
     h->last_batch_block = false;
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
     if (want_env) NODAL_TRY(branch_sweep_begin(h, &env, count));
-    int s = sparse_solve_sources(h, dense != 0, count, nsrc, h->sw_vals.as<double>(), h->sw_slot.as<int32_t>(), x_out,
-                                 resid_out, info_out, want_env ? &env : nullptr);
+    SweepClient client(h, nsrc, x_out, info_out, want_env ? &env : nullptr);
+    int s = multi_rhs_solve(h, h, dense != 0, count, resid_out, info_out, client);
     if (s == NODAL_OK && want_env) s = branch_sweep_finish(h, &env, count, info_out);
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
@@ -840,7 +871,8 @@ int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const i
     DeviceGuard g(h);
     if (h->hung) return NODAL_E_HIP;
     NODAL_TRY(sweep_prepare(h, count, nsrc, rows, values));
-    return sparse_sources_rhs(h, count, nsrc, h->sw_vals.as<double>(), h->sw_slot.as<int32_t>(), rhs_out);
+    SweepClient client(h, nsrc, rhs_out, nullptr, nullptr);
+    return sparse_sources_rhs(h, count, client);
 }
 
 int nodal_debug_residual(nodal_handle h, int32_t transposed, int32_t cols, int32_t layout, const double *x,

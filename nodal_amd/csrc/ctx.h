@@ -370,16 +370,75 @@ int stamp_to_dense(nodal_ctx *h, double *G_dev, int64_t ld, bool col_major);
 int stamp_sweep_slots(nodal_ctx *h, const int32_t *rows_dev, int32_t nsrc, int32_t *slot_dev, int32_t *bad_dev);
 int stamp_rhs_multi(nodal_ctx *h, const int32_t *slot_dev, const double *swept_dev, int32_t nsrc, int32_t cols,
                     double *out, int64_t rs, int64_t cs);
-// (env: the worst-case envelope of the sweep is kept on the device as the blocks are handed over, branch.hip; may be null)
-// (ports: the members are the unit injections of a port call, ports.hip -- their right-hand sides replace the folded
-// sources and their finished blocks are read at the port nodes on the device; may be null)
-struct BranchSweep;
-struct PortCall;
-int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
-                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out,
-                         const BranchSweep *env = nullptr, const PortCall *ports = nullptr);
-int sparse_sources_rhs(nodal_ctx *h, int32_t count, int32_t nsrc, const double *swept_dev, const int32_t *slot_dev,
-                       double *rhs_out);
+// ---- same G, many right-hand sides (multi_rhs_solve in sparse.hip) ----
+// What a front end tells the one driver of source sweeps, port matrices and adjoint sensitivities.  Columns are
+// addressed as element (row, y) at [row * rs + y * cs] throughout.
+struct MultiRhsClient {
+    bool wants_rows = true;  // hand_over gets the finished columns as [cols][n] rows as well
+    int32_t max_cols = 512;  // the widest block hand_over accepts (the dense route hands a whole chunk over at 512)
+    // adds the right-hand sides of columns m0 .. m0 + cols - 1 (cols <= 16) into a zeroed block
+    virtual int build(int32_t m0, int cols, double *out, int64_t rs, int64_t cs) = 0;
+    // takes the finished columns m0 .. m0 + cols - 1 (`rows`: the same as [cols][n] rows, null unless wants_rows): the
+    // client's device work, its copies down, and the stream wait
+    virtual int hand_over(int32_t m0, int cols, const double *x, int64_t rs, int64_t cs, const double *rows) = 0;
+    // every column is singular: NaN into the client's own host arrays (info and resid are the driver's)
+    virtual void all_singular(int32_t count) = 0;
+protected:
+    ~MultiRhsClient() = default;
+};
+// s: the context whose matrix is solved -- h itself, or the csr_only child that holds G^T
+int multi_rhs_solve(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, double *resid_out /* may be null */,
+                    int32_t *info_out, MultiRhsClient &client);
+// testing hook: the right-hand sides `client` builds, through the interleaved block, handed over as rows
+int sparse_sources_rhs(nodal_ctx *h, int32_t count, MultiRhsClient &client);
+// a call on the solve context s: on failure its error text becomes the handle's
+static inline int nodal_lift_error(nodal_ctx *h, nodal_ctx *s, int status) {
+    if (status != NODAL_OK && s != h) h->err = s->err;
+    return status;
+}
+
+// "The handle is left as it was found": the solution (set aside in sn_x) and what the last solve reported about itself,
+// around an analysis that solves on the handle.  save before, restore after; the caller waits for the stream.
+struct HandleKeeper {
+    int32_t iterations = 0, levels = 0;
+    double relres = 0, kern_ms = 0, kern_alg = 0;
+    int64_t kern_launches = 0;
+    bool copied = false;
+    int save(nodal_ctx *h, bool copy_x) {
+        iterations = h->last_iterations;
+        levels = h->amg_levels;
+        relres = h->last_relres;
+        kern_ms = h->kern_ms;
+        kern_alg = h->kern_alg;
+        kern_launches = h->kern_launches;
+        copied = copy_x;
+        if (!copy_x) return NODAL_OK;
+        NODAL_HIP_TRY(h, h->sn_x.reserve((size_t)h->n * 8 + 64));
+        if (h->n > 0)
+            NODAL_HIP_TRY(h, hipMemcpyAsync(h->sn_x.p, h->x.p, (size_t)h->n * 8, hipMemcpyDeviceToDevice, h->stream));
+        return NODAL_OK;
+    }
+    // `what`: the analysis, as its error texts begin ("sensitivities", "port matrix")
+    int restore(nodal_ctx *h, int status, const char *what) {
+        h->last_iterations = iterations;
+        h->amg_levels = levels;
+        h->last_relres = relres;
+        h->kern_ms = kern_ms;
+        h->kern_alg = kern_alg;
+        h->kern_launches = kern_launches;
+        h->have_x = false;
+        if (!copied) return status;
+        if (hipMemcpyAsync(h->x.p, h->sn_x.p, (size_t)h->n * 8, hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
+            if (status == NODAL_OK) {
+                h->err = std::string(what) + ": could not put the solution back";
+                status = NODAL_E_HIP;
+            }
+        } else {
+            h->have_x = !h->hung;
+        }
+        return status;
+    }
+};
 
 // ---- branch currents, power, sweep envelopes (branch.hip) ----
 // the envelope of one source sweep: device arrays (branch_sweep_begin sets them) and the caller's host arrays (any null)
@@ -395,29 +454,25 @@ int branch_sweep_block(nodal_ctx *h, const BranchSweep *env, int32_t m0, int col
                        const int32_t *info, const double *swept_dev, const int32_t *slot_dev, int32_t nsrc);
 int branch_sweep_finish(nodal_ctx *h, const BranchSweep *env, int32_t count, const int32_t *info);
 
-// ---- adjoint sensitivities (sensitivity.hip; the transposed solves: sparse_solve_adjoint in sparse.hip) ----
+// ---- adjoint sensitivities (sensitivity.hip; the transposed solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_sensitivities: the outputs' specification (device, [count]), the single solve's solution set aside
 // (device, [n]) and the caller's host arrays
 struct SensCall {
     const int32_t *kind = nullptr, *p = nullptr, *q2 = nullptr;
     const int32_t *kind_host = nullptr, *p_host = nullptr;  // the caller's own arrays
     const double *x = nullptr;
-    double *sens_out = nullptr, *adjoint_out = nullptr, *resid_out = nullptr;
-    int32_t *info_out = nullptr;
+    double *sens_out = nullptr, *adjoint_out = nullptr;
 };
 // adds the entries of the columns c of outputs m0 .. m0 + cols - 1 (cols <= 16) into a zeroed block, element (row, y) at
 // out[row * rs + y * cs]
 int sens_rhs_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, double *out, int64_t rs, int64_t cs);
 // the table kernels for those outputs from their adjoints lam (same addressing), results to the host, and the wait
 int sens_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, const double *lam, int64_t rs, int64_t cs);
-// G^T lambda = c for every output, routed as sparse_solve_sources routes its members; s = h itself (a passive network:
-// G is symmetric) or the child context holding G^T
-int sparse_solve_adjoint(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, const SensCall *call);
 int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const int32_t *p, const int32_t *q2,
              double *sens_out, double *value_out, double *adjoint_out, double *resid_out, int32_t *info_out);
 void sens_free_child(nodal_ctx *h);
 
-// ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: sparse_solve_sources in sparse.hip) ----
+// ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])
 struct PortCall {
     int32_t nports = 0;

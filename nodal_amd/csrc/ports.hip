@@ -11,9 +11,9 @@
 //     V_oc[p] = x[a_p] - x[b_p]             for the solution x of the last single solve
 // so that v = V_oc + Z i for any external currents i.  A port with a_q == b_q has an all-zero column and row.
 //
-// The solves are the source sweep's (sparse_solve_sources, sparse.hip) with two of its steps exchanged through
-// SweepCtx::ports: k_port_rhs builds a block of right-hand sides where stamp_rhs_multi folds the members' sources, and
-// k_port_gather reads a finished block at the port nodes into Z on the device where the rows would go down to the host.
+// The solves are multi_rhs_solve's (sparse.hip), as the source sweep's, with the PortClient below: k_port_rhs builds a
+// block of right-hand sides where a sweep folds its members' sources, and k_port_gather reads a finished block at the
+// port nodes into Z on the device where a sweep's rows would go down to the host.
 // Z comes down once, P x P numbers instead of P x n.  No floating-point atomics: a repeated call returns the same bits.
 #include "ctx.h"
 
@@ -86,6 +86,27 @@ int port_gather_block(nodal_ctx *h, const PortCall *call, int32_t m0, int cols, 
     return NODAL_OK;
 }
 
+namespace {
+// the driver's client: the columns are the ports' unit injections, a finished block is read at the port nodes
+struct PortClient final : MultiRhsClient {
+    nodal_ctx *h;
+    const PortCall *call;
+    const int32_t *info;  // the driver's flags (host), settled for a block by the time it is handed over
+    PortClient(nodal_ctx *h_, const PortCall *call_, const int32_t *info_) : h(h_), call(call_), info(info_) {
+        max_cols = PORT_CHUNK;
+    }
+    int build(int32_t m0, int cols, double *out, int64_t rs, int64_t cs) override {
+        return port_rhs_block(h, call, m0, cols, out, rs, cs);
+    }
+    int hand_over(int32_t m0, int cols, const double *, int64_t, int64_t, const double *rows) override {
+        NODAL_TRY(port_gather_block(h, call, m0, cols, rows, info));
+        NODAL_WAIT_STREAM(h, h->stream);
+        return NODAL_OK;
+    }
+    void all_singular(int32_t) override {}  // (port_run fills the columns of Z from info)
+};
+}  // namespace
+
 int port_run(nodal_ctx *h, bool dense, int32_t nports, const int32_t *ia, const int32_t *ib, double *z_out,
              double *voc_out, double *resid_out, int32_t *info_out) {
     const int64_t n = h->n, P = nports;
@@ -109,12 +130,10 @@ int port_run(nodal_ctx *h, bool dense, int32_t nports, const int32_t *ia, const 
     double *z_dev = reinterpret_cast<double *>(ia_dev + words), *voc_dev = z_dev + P * P;
     NODAL_HIP_TRY(h, hipMemcpyAsync(ia_dev, ia, (size_t)P * 4, hipMemcpyHostToDevice, st));
     NODAL_HIP_TRY(h, hipMemcpyAsync(ib_dev, ib, (size_t)P * 4, hipMemcpyHostToDevice, st));
-    // the single solve's solution is set aside (the multigrid route writes h->x) and V_oc read from the copy
-    const bool had_x = h->have_x;
-    if (had_x) {
-        NODAL_HIP_TRY(h, h->sn_x.reserve((size_t)n * 8 + 64));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(h->sn_x.p, h->x.p, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-    }
+    // the handle is left as it was found: the single solve's solution is set aside (the multigrid route writes h->x)
+    // and V_oc read from the copy
+    HandleKeeper keep;
+    NODAL_TRY(keep.save(h, h->have_x));
     if (voc_out) {
         k_port_gather<<<groups_of(P), PTB, 0, st>>>(nports, 1, 0, ia_dev, ib_dev, h->sn_x.as<double>(), 1, n, PortFlags{},
                                                    voc_dev, 1);
@@ -128,25 +147,8 @@ int port_run(nodal_ctx *h, bool dense, int32_t nports, const int32_t *ia, const 
     call.ia = ia_dev;
     call.ib = ib_dev;
     call.z = z_dev;
-    // the handle is left as it was found: the solution, and what the last solve reported about itself
-    const int32_t iterations = h->last_iterations, levels = h->amg_levels;
-    const double relres = h->last_relres, kern_ms = h->kern_ms, kern_alg = h->kern_alg;
-    const int64_t kern_launches = h->kern_launches;
-    int status = sparse_solve_sources(h, dense, nports, 0, nullptr, nullptr, nullptr, resid_out, info_out, nullptr, &call);
-    h->last_iterations = iterations;
-    h->amg_levels = levels;
-    h->last_relres = relres;
-    h->kern_ms = kern_ms;
-    h->kern_alg = kern_alg;
-    h->kern_launches = kern_launches;
-    h->have_x = false;
-    if (had_x) {
-        if (hipMemcpyAsync(h->x.p, h->sn_x.p, (size_t)n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            if (status == NODAL_OK) status = nodal_fail(h, NODAL_E_HIP, "port matrix: could not put the solution back");
-        } else {
-            h->have_x = !h->hung;
-        }
-    }
+    PortClient client(h, &call, info_out);
+    int status = keep.restore(h, multi_rhs_solve(h, h, dense, nports, resid_out, info_out, client), "port matrix");
     if (status == NODAL_OK && hipMemcpyAsync(z_out, z_dev, (size_t)(P * P) * 8, hipMemcpyDeviceToHost, st) != hipSuccess)
         status = nodal_fail(h, NODAL_E_HIP, "port matrix: could not bring Z down");
     const int w = nodal_wait_stream(h, st, NODAL_SITE);

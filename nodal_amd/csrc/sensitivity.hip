@@ -18,8 +18,9 @@
 // row and then walks the sixteen columns of the block.  No floating-point atomics: the cross terms of a resistor are
 // added by one thread in table order, so a repeated call returns the same bits.
 //
-// The transposed solves are sparse_solve_adjoint (sparse.hip).  A passive network solves on the handle itself; any
-// other gets a child context that holds G^T as CSR: its pattern is transposed on the host by a stable counting sort
+// The transposed solves are multi_rhs_solve (sparse.hip) with the AdjointClient below.  A passive network solves on the
+// handle itself; any other gets a child context that holds G^T as CSR: its pattern is transposed on the host by a stable
+// counting sort
 // over the columns (rows come out with sorted columns, and the same input gives the same pattern), once per
 // struct_epoch of the parent, and its values are gathered from the parent's `data` through the kept permutation on
 // every call.
@@ -421,6 +422,34 @@ int sens_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, const d
     return NODAL_OK;
 }
 
+namespace {
+// the driver's client: the columns are the outputs' c, a finished block goes through the table kernels.  It reads the
+// interleaved block as it stands (k_sensitivity_block<true>) and asks for rows only when the caller wants the adjoints.
+struct AdjointClient final : MultiRhsClient {
+    nodal_ctx *h;
+    const SensCall *call;
+    AdjointClient(nodal_ctx *h_, const SensCall *call_) : h(h_), call(call_) {
+        wants_rows = call->adjoint_out != nullptr;
+        max_cols = SCOLS;
+    }
+    int build(int32_t m0, int cols, double *out, int64_t rs, int64_t cs) override {
+        return sens_rhs_block(h, call, m0, cols, out, rs, cs);
+    }
+    int hand_over(int32_t m0, int cols, const double *lam, int64_t rs, int64_t cs, const double *rows) override {
+        if (rows)
+            NODAL_HIP_TRY(h, hipMemcpyAsync(call->adjoint_out + (int64_t)m0 * h->n, rows, (size_t)cols * h->n * 8,
+                                            hipMemcpyDeviceToHost, h->stream));
+        return sens_block(h, call, m0, cols, lam, rs, cs);  // (waits)
+    }
+    void all_singular(int32_t count) override {
+        const double nan = __builtin_nan("");
+        for (int64_t t = 0; t < (int64_t)count * h->ncomp; ++t) call->sens_out[t] = nan;
+        if (call->adjoint_out)
+            for (int64_t t = 0; t < (int64_t)count * h->n; ++t) call->adjoint_out[t] = nan;
+    }
+};
+}  // namespace
+
 int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const int32_t *p, const int32_t *q2,
              double *sens_out, double *value_out, double *adjoint_out, double *resid_out, int32_t *info_out) {
     const int64_t n = h->n, ncomp = h->ncomp;
@@ -445,9 +474,10 @@ int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const
     NODAL_HIP_TRY(h, hipMemcpyAsync(p_dev, p, (size_t)count * 4, hipMemcpyHostToDevice, st));
     NODAL_HIP_TRY(h, hipMemcpyAsync(q2_dev, q2, (size_t)count * 4, hipMemcpyHostToDevice, st));
     NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
-    // the single solve's solution is set aside: the kernels read it, and the multigrid route writes h->x
-    NODAL_HIP_TRY(h, h->sn_x.reserve((size_t)n * 8 + 64));
-    if (n > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(h->sn_x.p, h->x.p, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    // the handle is left as it was found.  The single solve's solution is set aside: the kernels read it, and the
+    // multigrid route writes h->x
+    HandleKeeper keep;
+    NODAL_TRY(keep.save(h, true));
     k_sens_values<<<(unsigned)groups_of(count), STB, 0, st>>>(count, h->K, kind_dev, p_dev, q2_dev, h->type.as<uint8_t>(),
                                                              assembled_values(h), h->a.as<int32_t>(), h->b.as<int32_t>(),
                                                              h->k.as<int32_t>(), h->sn_x.as<double>(), value_dev, bad_dev);
@@ -467,8 +497,6 @@ int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const
     call.x = h->sn_x.as<double>();
     call.sens_out = sens_out;
     call.adjoint_out = adjoint_out;
-    call.resid_out = resid_out;
-    call.info_out = info_out;
     if (n == 0) {  // (every lead is ground: nothing depends on anything)
         for (int64_t t = 0; t < (int64_t)count * ncomp; ++t) sens_out[t] = 0.0;
         for (int32_t q = 0; q < count; ++q) {
@@ -483,24 +511,9 @@ int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const
         NODAL_TRY(ensure_transposed_child(h));
         s = h->adjoint;
     }
-    // the handle is left as it was found: the solution, and what the last solve reported about itself
-    const int32_t iterations = h->last_iterations, levels = h->amg_levels;
-    const double relres = h->last_relres, kern_ms = h->kern_ms, kern_alg = h->kern_alg;
-    const int64_t kern_launches = h->kern_launches;
-    int status = sparse_solve_adjoint(h, s, dense, count, &call);
-    h->last_iterations = iterations;
-    h->amg_levels = levels;
-    h->last_relres = relres;
-    h->kern_ms = kern_ms;
-    h->kern_alg = kern_alg;
-    h->kern_launches = kern_launches;
-    if (hipMemcpyAsync(h->x.p, h->sn_x.p, (size_t)n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        if (status == NODAL_OK) status = nodal_fail(h, NODAL_E_HIP, "sensitivities: could not put the solution back");
-        h->have_x = false;
-    } else {
-        h->have_x = !h->hung;
-        const int w = nodal_wait_stream(h, st, NODAL_SITE);
-        if (status == NODAL_OK) status = w;
-    }
+    AdjointClient client(h, &call);
+    int status = keep.restore(h, multi_rhs_solve(h, s, dense, count, resid_out, info_out, client), "sensitivities");
+    const int w = nodal_wait_stream(h, st, NODAL_SITE);
+    if (status == NODAL_OK) status = w;
     return status;
 }

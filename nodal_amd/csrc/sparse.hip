@@ -682,7 +682,7 @@ __global__ __launch_bounds__(TB) void add_into(int64_t count, const double *__re
     for (int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x; e < count; e += (int64_t)gridDim.x * TB) x[e] += d[e];
 }
 
-// ---- source sweeps (sparse_solve_sources below) ----
+// ---- same G, many right-hand sides (multi_rhs_solve below) ----
 // NaN-keeping maximum: once a NaN is seen it stays (fmax would drop it)
 __device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
 // Per column y < cols of a block whose element (i, y) sits at [i * rs + y * cs]: r = b - G x row by row (the lanes of a
@@ -756,7 +756,7 @@ __global__ __launch_bounds__(TB) void copy_rhs_column(const double *__restrict__
 
 // The block judgement: scaled residuals of the `cols` (<= 16) columns of x against b (element (i, y) at [i * rs + y * cs])
 // with the CSR matrix of context `m`, on m's stream.  norms (device): [16][4] maxima as resid_norms_multi leaves them, then
-// [16] scaled residuals.  Nothing is read back.  The one body of SweepCtx::judge, AdjointCtx::judge and
+// [16] scaled residuals.  Nothing is read back.  The one body of multi_rhs_solve's judge and
 // nodal_debug_residual.
 int csr_judge_block(nodal_ctx *m, const double *x, const double *b, int64_t rs, int64_t cs, int cols, double *norms) {
     const int64_t n = m->n;
@@ -950,49 +950,40 @@ int sparse_solve_pairs(nodal_ctx *h, int32_t npairs, const int32_t *ia, const in
     return NODAL_OK;
 }
 
-// ---- source sweeps (nodal_solve_sources) ----------------------------------------------------------------------
-// A .dc sweep of a supply, the load vectors of an IR-drop study: G is fixed and only the independent sources change, so
-// every member is the same matrix with its own right-hand side (stamp_rhs_multi folds them, sixteen per launch).  The
-// routes mirror sparse_solve and nodal_solve_pairs, every member is judged on its own scaled residual, and at most one
-// block of work (sixteen members, or one dense chunk) sits behind any host wait.
+// ---- same G, many right-hand sides (multi_rhs_solve) -------------------------------------------------------------
+// A .dc sweep of a supply, the load vectors of an IR-drop study, the unit injections of a port matrix, the adjoint
+// columns of a sensitivity call: the matrix is fixed and only the right-hand side changes, so every column is the same
+// matrix with its own right-hand side (the client's build writes them, sixteen per launch).  The routes mirror
+// sparse_solve and nodal_solve_pairs, every column is judged on its own scaled residual, and at most one block of work
+// (sixteen columns, or one dense chunk) sits behind any host wait.  What differs between the front ends is in their
+// MultiRhsClient (ctx.h; DESIGN 3.6a has the table).
 namespace {
 
-struct SweepCtx {
-    nodal_ctx *h;
-    int32_t nsrc;
-    const double *swept;
-    const int32_t *slot;
-    double *x_out, *resid;
+// one call of the driver: the handle, the context whose matrix is solved, and where the judgements go
+struct MultiRhs {
+    nodal_ctx *h, *s;
+    MultiRhsClient &client;
+    double *resid;
     int32_t *info;
     double *norms;  // [16][4] maxima + [16] scaled residuals (device)
-    const BranchSweep *env = nullptr;  // the sweep's envelope (branch.hip), fed block by block below
-    const PortCall *ports = nullptr;   // a port call (ports.hip): the members are its unit injections
 
-    // the right-hand sides of members m0 .. m0 + cols - 1 (cols <= 16) added into a zeroed block
-    int build(int32_t m0, int cols, double *out, int64_t rs, int64_t cs) const {
-        if (ports) return port_rhs_block(h, ports, m0, cols, out, rs, cs);
-        return stamp_rhs_multi(h, slot, swept + (int64_t)m0 * nsrc, nsrc, cols, out, rs, cs);
-    }
-    // member m0 .. m0 + cols - 1 (cols <= 16) into out[row * rs + y * cs], zeros elsewhere in an n x cols block
+    // columns m0 .. m0 + cols - 1 (cols <= 16) into out[row * rs + y * cs], zeros elsewhere in an n x cols block
     int fold(int32_t m0, int cols, double *out, int64_t rs, int64_t cs, size_t block_bytes) const {
         NODAL_HIP_TRY(h, hipMemsetAsync(out, 0, block_bytes, h->stream));
-        return build(m0, cols, out, rs, cs);
+        return client.build(m0, cols, out, rs, cs);
     }
     // resid[m0 + y] for the cols columns of x / b (layout as in fold): one read-back, i.e. one wait
     int judge(int32_t m0, int cols, const double *x, const double *b, int64_t rs, int64_t cs) const {
-        NODAL_TRY(csr_judge_block(h, x, b, rs, cs, cols, norms));
+        NODAL_TRY(nodal_lift_error(h, s, csr_judge_block(s, x, b, rs, cs, cols, norms)));
         return nodal_read_words(h, resid + m0, norms + 4 * SLU_MULTI, (size_t)cols * 8);
     }
-    // rows [cols][n] of members m0 .. to the caller, and wait.  Every route ends here with the members' final rows
-    // on the device and their info flags settled: the one place the envelope looks at them.
-    int hand_over(int32_t m0, int cols, const double *rows) const {
-        const int64_t n = h->n;
-        if (env) NODAL_TRY(branch_sweep_block(h, env, m0, cols, rows, info, swept, slot, nsrc));
-        if (ports) NODAL_TRY(port_gather_block(h, ports, m0, cols, rows, info));
-        if (x_out)
-            NODAL_HIP_TRY(h, hipMemcpyAsync(x_out + (int64_t)m0 * n, rows, (size_t)cols * n * 8, hipMemcpyDeviceToHost,
-                                            h->stream));
-        NODAL_WAIT_STREAM(h, h->stream);
+    // Every route ends here with the columns final on the device and their info flags settled; the client waits.
+    int hand_over(int32_t m0, int cols, const double *x, int64_t rs, int64_t cs, const double *rows) const {
+        return client.hand_over(m0, cols, x, rs, cs, client.wants_rows ? rows : nullptr);
+    }
+    int deinterleave(int cols, const double *X, double *rows) const {
+        deinterleave_rows<<<grid_rows(h->n * cols, 1), TB, 0, h->stream>>>(h->n, cols, X, rows);
+        NODAL_HIP_TRY(h, hipGetLastError());
         return NODAL_OK;
     }
     int nan_rows(double *rows, int cols) const {
@@ -1000,42 +991,40 @@ struct SweepCtx {
         NODAL_HIP_TRY(h, hipGetLastError());
         return NODAL_OK;
     }
-};
-
-// every member singular (a floating island, a singular G): NaN rows, info 1, as sparse_solve answers
-void sweep_all_singular(const SweepCtx &c, int32_t count) {
-    const int64_t n = c.h->n;
-    for (int32_t m = 0; m < count; ++m) {
-        c.info[m] = 1;
-        c.resid[m] = __builtin_nan("");
+    // every column singular (a floating island, a singular G): info 1, NaN, and the client's own arrays
+    int all_singular(int32_t count) const {
+        for (int32_t m = 0; m < count; ++m) {
+            info[m] = 1;
+            resid[m] = __builtin_nan("");
+        }
+        client.all_singular(count);
+        return NODAL_OK;
     }
-    if (c.x_out)
-        for (int64_t t = 0; t < (int64_t)count * n; ++t) c.x_out[t] = __builtin_nan("");
-}
+};
 
 }  // namespace
 
-int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, const double *swept_dev,
-                         const int32_t *slot_dev, double *x_out, double *resid_out, int32_t *info_out,
-                         const BranchSweep *env, const PortCall *ports) {
+int multi_rhs_solve(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, double *resid_out, int32_t *info_out,
+                    MultiRhsClient &client) {
     const int64_t n = h->n;
-    hipStream_t st = h->stream;
+    hipStream_t st = h->stream;  // (s shares it: one ordered timeline)
     std::vector<double> resid_host(resid_out ? 0 : (size_t)count);
     for (int32_t m = 0; m < count; ++m) info_out[m] = 0;
+    // (right for the adjoint call too: sens_run restores both once the driver returns)
     h->have_x = false;
     h->last_iterations = 0;
-    SweepCtx c{h, nsrc, swept_dev, slot_dev, x_out, resid_out ? resid_out : resid_host.data(), info_out, nullptr, env, ports};
+    MultiRhs c{h, s, client, resid_out ? resid_out : resid_host.data(), info_out, nullptr};
     if (n == 0) {
         for (int32_t m = 0; m < count; ++m) c.resid[m] = 0.0;
         return NODAL_OK;
     }
-    const bool passive = h->B == 0 && h->passive_network;
+    const bool passive = s == h && h->B == 0 && h->passive_network;  // (a child holds G^T of a network that is not)
     const int64_t densify_max = 4096;        // passive networks: sparse_solve's bound for the dense LU
     const int64_t dense_general_max = 8192;  // the rest: nodal_solve_pairs' bound
     const size_t vb = (size_t)n * SLU_MULTI * 8;
 
     if (dense || n <= 64 || (passive && n <= densify_max) || (!passive && n <= dense_general_max)) {
-        // one LU per chunk of up to 512 members: they are extra right-hand-side columns of the augmented panel
+        // one LU per chunk of up to 512 columns: they are extra right-hand-side columns of the augmented panel
         const int32_t CHUNK = 512;
         const int64_t lda = dense_lda(n);
         const int32_t first = count < CHUNK ? count : CHUNK;
@@ -1044,29 +1033,33 @@ int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, 
         c.norms = Bc + (size_t)n * first;
         for (int32_t q0 = 0; q0 < count; q0 += CHUNK) {
             const int32_t m = count - q0 < CHUNK ? count - q0 : CHUNK;
-            NODAL_HIP_TRY(h, h->dense.reserve((size_t)lda * (size_t)(n + m) * 8 + 64));
-            NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
-            double *cols = h->dense.as<double>() + n * lda;
+            NODAL_HIP_TRY(h, s->dense.reserve((size_t)lda * (size_t)(n + m) * 8 + 64));
+            if (s->csr_only) NODAL_TRY(nodal_lift_error(h, s, csr_to_dense(s, s->dense.as<double>(), lda)));
+            else NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
+            double *cols = s->dense.as<double>() + n * lda;
             NODAL_HIP_TRY(h, hipMemsetAsync(cols, 0, (size_t)lda * m * 8, st));
             for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
                 const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
-                NODAL_TRY(c.build(q0 + g0, k, cols + g0 * lda, 1, lda));
+                NODAL_TRY(client.build(q0 + g0, k, cols + g0 * lda, 1, lda));
                 NODAL_TRY(c.fold(q0 + g0, k, Bc + g0 * n, 1, n, (size_t)n * k * 8));
             }
-            NODAL_HIP_TRY(h, h->solver.reserve((size_t)n * m * 8 + 64));
-            double *X = h->solver.as<double>();
+            NODAL_HIP_TRY(h, s->solver.reserve((size_t)n * m * 8 + 64));
+            double *X = s->solver.as<double>();
             int32_t inf = 0;
-            NODAL_TRY(dense_factor_solve_multi(h, m, X, n, &inf));
+            NODAL_TRY(nodal_lift_error(h, s, dense_factor_solve_multi(s, m, X, n, &inf)));
             if (inf > 0) {
                 if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
-                sweep_all_singular(c, count);
-                return NODAL_OK;
+                return c.all_singular(count);
             }
-            for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
+            // every group of sixteen is judged; the judged columns go over once the client's width has gathered
+            // (a whole chunk behind one wait, or group by group) or the chunk ends
+            for (int32_t g0 = 0, from = 0; g0 < m; g0 += SLU_MULTI) {
                 const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
                 NODAL_TRY(c.judge(q0 + g0, k, X + g0 * n, Bc + g0 * n, 1, n));
+                if (g0 + k - from < client.max_cols && g0 + k < m) continue;
+                NODAL_TRY(c.hand_over(q0 + from, g0 + k - from, X + from * n, 1, n, X + from * n));
+                from = g0 + k;
             }
-            NODAL_TRY(c.hand_over(q0, m, X));
         }
         return NODAL_OK;
     }
@@ -1079,25 +1072,25 @@ int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, 
     const unsigned gv = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 65536);
 
     if (passive) {
-        // member 0 sets the multigrid hierarchy up; the others go sixteen at a time through the block iteration
-        // (sagg_multi.h).  A block that breaks down or hits its cap is redone member by member, and a member the
-        // iteration fails on -- with every later one -- by the sparse direct solve.
+        // column 0 sets the multigrid hierarchy up (or finds it); the others go sixteen at a time through the block
+        // iteration (sagg_multi.h).  A block that breaks down or hits its cap is redone column by column, and a column
+        // the iteration fails on -- with every later one -- by the sparse direct solve.
         bool direct = n < h->amg_min_n, block_ok = true;
-        auto one = [&](int32_t m) -> int {  // member m alone into rows[0, n); false: singular network
+        auto one = [&](int32_t m) -> int {  // column m alone into rows[0, n); -2: singular network
             NODAL_TRY(c.fold(m, 1, bvec, 1, 0, (size_t)n * 8));
             int32_t inf = 0, it = 0;
             double rs = 0.0;
             bool done = false;
             if (!direct) {
-                const int s = amg_fcg_solve_ex(h, bvec, m == 0, &inf, &it, &rs);
-                if (s == -2) return -2;  // floating island: every member is singular
-                if (s == NODAL_OK) {
+                const int sv = amg_fcg_solve_ex(h, bvec, m == 0, &inf, &it, &rs);  // (writes h->x)
+                if (sv == -2) return -2;  // floating island: every column is singular
+                if (sv == NODAL_OK) {
                     NODAL_HIP_TRY(h, hipMemcpyAsync(rows, h->x.as<double>(), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
                     done = true;
-                } else if (s < 0) {
+                } else if (sv < 0) {
                     direct = true;
                 } else {
-                    return s;
+                    return sv;
                 }
             }
             if (!done) {
@@ -1109,101 +1102,99 @@ int sparse_solve_sources(nodal_ctx *h, bool dense, int32_t count, int32_t nsrc, 
             }
             h->last_iterations = it;
             NODAL_TRY(c.judge(m, 1, rows, bvec, 1, 0));
-            return c.hand_over(m, 1, rows);
+            return c.hand_over(m, 1, rows, 1, 0, rows);
         };
         for (int32_t m0 = 0; m0 < count;) {
             const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
             if (m0 > 0 && !direct && block_ok && cnt >= 2 && sagg_ready(h, n)) {
                 NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
                 int32_t it = 0;
-                const int s = sagg_fcg_solve_block(h, cnt, Bil, Xil, &it);
-                if (s == NODAL_OK) {
+                const int sv = sagg_fcg_solve_block(h, cnt, Bil, Xil, &it);
+                if (sv == NODAL_OK) {
                     h->last_iterations = it;
                     NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
-                    deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
-                    NODAL_HIP_TRY(h, hipGetLastError());
-                    NODAL_TRY(c.hand_over(m0, cnt, rows));
+                    if (client.wants_rows) NODAL_TRY(c.deinterleave(cnt, Xil, rows));
+                    NODAL_TRY(c.hand_over(m0, cnt, Xil, SLU_MULTI, 1, rows));
                     m0 += cnt;
                     continue;
                 }
-                if (s > 0) return s;
+                if (sv > 0) return sv;
                 block_ok = false;  // (latched: a second failing block would cost its cap again for nothing)
             }
-            const int s = one(m0);
-            if (s == -2) {
-                sweep_all_singular(c, count);
-                return NODAL_OK;
-            }
-            NODAL_TRY(s);
+            const int sv = one(m0);
+            if (sv == -2) return c.all_singular(count);
+            NODAL_TRY(sv);
             ++m0;
         }
         return NODAL_OK;
     }
 
-    // Branch unknowns or a non-passive G: ONE sparse LU of the full system (no presolve), then per block of sixteen
-    // members two substitutions, one refinement step and the judgement; a member above the bar -- and every member when
-    // the factorisation had to replace pivots -- is redone alone by the sparse direct solve, which judges its own.
+    // Branch unknowns or a non-passive G (or the transpose of one): ONE sparse LU of the full system (no presolve), then
+    // per block of sixteen columns two substitutions, one refinement step and the judgement; a column above the bar --
+    // and every column when the factorisation had to replace pivots -- is redone alone by the sparse direct solve,
+    // which judges its own.
     int32_t inf = 0;
-    NODAL_TRY(slu_factor(h, &inf));
-    if (inf > 0) {
-        sweep_all_singular(c, count);
-        return NODAL_OK;
-    }
-    bool all_direct = slu_perturbed(h) > 0;
-    const double bar = 1e-14;  // the backward-error bar of the refinement (sparse_general.hip)
+    NODAL_TRY(nodal_lift_error(h, s, slu_factor(s, &inf)));
+    if (inf > 0) return c.all_singular(count);
+    bool all_direct = slu_perturbed(s) > 0;
+    // the backward-error bar of the refinement (sparse_general.hip); NODAL_MULTI_BAR (per call: tests switch it) below 0
+    // sends every column through the redo
+    const double bar = getenv("NODAL_MULTI_BAR") ? atof(getenv("NODAL_MULTI_BAR")) : 1e-14;
     for (int32_t m0 = 0; m0 < count; m0 += SLU_MULTI) {
         const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
+        bool redo = all_direct;
         if (!all_direct) {
             NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
-            NODAL_TRY(slu_apply_multi(h, Bil, Xil));
-            csr_residual_multi<<<gv, TB, 0, st>>>(n, h->indptr.as<int32_t>(), h->indices.as<int32_t>(), h->data.as<double>(),
+            NODAL_TRY(nodal_lift_error(h, s, slu_apply_multi(s, Bil, Xil)));
+            csr_residual_multi<<<gv, TB, 0, st>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(), s->data.as<double>(),
                                                  Xil, Bil, Ril);
-            NODAL_TRY(slu_apply_multi(h, Ril, Dil));
+            NODAL_TRY(nodal_lift_error(h, s, slu_apply_multi(s, Ril, Dil)));
             add_into<<<gv, TB, 0, st>>>(n * SLU_MULTI, Dil, Xil);
             NODAL_HIP_TRY(h, hipGetLastError());
             NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
-            deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
-            NODAL_HIP_TRY(h, hipGetLastError());
+            for (int y = 0; y < cnt; ++y) redo = redo || !(c.resid[m0 + y] <= bar);
+            // (rows: where a redone column lands among its block's, and what a client that wants rows reads)
+            if (redo || client.wants_rows) NODAL_TRY(c.deinterleave(cnt, Xil, rows));
             h->last_iterations = 1;
         }
-        bool redone = false;
+        if (!redo) {  // the usual case: the block is handed over interleaved as well
+            NODAL_TRY(c.hand_over(m0, cnt, Xil, SLU_MULTI, 1, rows));
+            continue;
+        }
         for (int y = 0; y < cnt; ++y) {
             if (!all_direct && c.resid[m0 + y] <= bar) continue;
             NODAL_TRY(c.fold(m0 + y, 1, bvec, 1, 0, (size_t)n * 8));
             int32_t inf1 = 0, it = 0;
             double rs = 0.0;
-            NODAL_TRY(sparse_direct_solve(h, bvec, rows + (size_t)y * n, &inf1, &it, &rs));
+            NODAL_TRY(nodal_lift_error(h, s, sparse_direct_solve(s, bvec, rows + (size_t)y * n, &inf1, &it, &rs)));
             if (inf1 > 0) {
                 info_out[m0 + y] = 1;
                 NODAL_TRY(c.nan_rows(rows + (size_t)y * n, 1));
             }
             NODAL_TRY(c.judge(m0 + y, 1, rows + (size_t)y * n, bvec, 1, 0));
-            redone = true;
         }
-        NODAL_TRY(c.hand_over(m0, cnt, rows));
-        if (redone && !all_direct) {  // (the direct solve may have factored anew, with another pivot bar)
-            NODAL_TRY(slu_factor(h, &inf));
-            all_direct = inf > 0 || slu_perturbed(h) > 0;
+        NODAL_TRY(c.hand_over(m0, cnt, rows, 1, n, rows));
+        if (!all_direct) {  // (the direct solve may have factored anew, with another pivot bar)
+            NODAL_TRY(nodal_lift_error(h, s, slu_factor(s, &inf)));
+            all_direct = inf > 0 || slu_perturbed(s) > 0;
         }
     }
     return NODAL_OK;
 }
 
-// testing hook (nodal_debug_sources_rhs): the right-hand sides the sweep builds, through the interleaved block
-int sparse_sources_rhs(nodal_ctx *h, int32_t count, int32_t nsrc, const double *swept_dev, const int32_t *slot_dev,
-                       double *rhs_out) {
+// testing hook (nodal_debug_sources_rhs): the right-hand sides a client builds, through the interleaved block
+int sparse_sources_rhs(nodal_ctx *h, int32_t count, MultiRhsClient &client) {
     const int64_t n = h->n;
     if (n == 0 || count == 0) return NODAL_OK;
     const size_t vb = (size_t)n * SLU_MULTI * 8;
     NODAL_HIP_TRY(h, h->sw_blk.reserve(2 * vb + 256));
     double *Bil = h->sw_blk.as<double>(), *rows = Bil + (size_t)n * SLU_MULTI;
-    SweepCtx c{h, nsrc, swept_dev, slot_dev, rhs_out, nullptr, nullptr, nullptr};
+    MultiRhs c{h, h, client, nullptr, nullptr, nullptr};
     for (int32_t m0 = 0; m0 < count; m0 += SLU_MULTI) {
         const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
         NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
-        deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, h->stream>>>(n, cnt, Bil, rows);
-        NODAL_HIP_TRY(h, hipGetLastError());
-        NODAL_TRY(c.hand_over(m0, cnt, rows));
+        NODAL_TRY(c.deinterleave(cnt, Bil, rows));
+        NODAL_TRY(c.hand_over(m0, cnt, Bil, SLU_MULTI, 1, rows));
     }
     return NODAL_OK;
 }
@@ -1537,249 +1528,3 @@ int sparse_debug_residual(nodal_ctx *h, bool transposed, int32_t cols, int32_t l
     }
     return NODAL_OK;
 }
-
-// ---- adjoint solves (nodal_sensitivities, sensitivity.hip) ------------------------------------------------------
-// G^T lambda = c for every output of the call: the routes of sparse_solve_sources over right-hand sides that
-// sens_rhs_block writes, on `s` -- the handle itself when the network is passive (G is symmetric bit for bit), else the
-// child context that holds G^T as CSR.  Every column is judged on its own scaled residual, at most one block of sixteen
-// sits behind any host wait, and each finished block goes to sens_block (the table kernels and the way down).  The
-// driver logic is restated here on purpose: the sweeps' own drivers stay as they are.
-namespace {
-
-struct AdjointCtx {
-    nodal_ctx *h, *s;
-    const SensCall *call;
-    double *resid;
-    int32_t *info;
-    double *norms;  // [16][4] maxima + [16] scaled residuals (device)
-
-    int fold(int32_t m0, int cols, double *out, int64_t rs, int64_t cs, size_t block_bytes) const {
-        NODAL_HIP_TRY(h, hipMemsetAsync(out, 0, block_bytes, h->stream));
-        return sens_rhs_block(h, call, m0, cols, out, rs, cs);
-    }
-    int judge(int32_t m0, int cols, const double *x, const double *b, int64_t rs, int64_t cs) const {
-        const int st = csr_judge_block(s, x, b, rs, cs, cols, norms);  // (s: G^T, or the handle itself)
-        if (st != NODAL_OK) {
-            if (s != h) h->err = s->err;
-            return st;
-        }
-        return nodal_read_words(h, resid + m0, norms + 4 * SLU_MULTI, (size_t)cols * 8);
-    }
-    // adjoints of outputs m0 .. (element (row, y) at lam[row * rs + y * cs]) through the table kernels, to the caller,
-    // and the wait; `rows` != null: the same adjoints as [cols][n] rows for adjoint_out
-    int hand_over(int32_t m0, int cols, const double *lam, int64_t rs, int64_t cs, const double *rows) const {
-        const int64_t n = h->n;
-        if (call->adjoint_out && rows)
-            NODAL_HIP_TRY(h, hipMemcpyAsync(call->adjoint_out + (int64_t)m0 * n, rows, (size_t)cols * n * 8,
-                                            hipMemcpyDeviceToHost, h->stream));
-        return sens_block(h, call, m0, cols, lam, rs, cs);  // (waits)
-    }
-    int nan_rows(double *rows, int cols) const {
-        fill_nan_rows<<<grid_rows(h->n * cols, 1), TB, 0, h->stream>>>(h->n * cols, rows);
-        NODAL_HIP_TRY(h, hipGetLastError());
-        return NODAL_OK;
-    }
-    // every output singular: NaN throughout, info 1
-    void all_singular(int32_t count) const {
-        const int64_t n = h->n, ncomp = h->ncomp;
-        const double nan = __builtin_nan("");
-        for (int32_t m = 0; m < count; ++m) {
-            info[m] = 1;
-            resid[m] = nan;
-        }
-        for (int64_t t = 0; t < (int64_t)count * ncomp; ++t) call->sens_out[t] = nan;
-        if (call->adjoint_out)
-            for (int64_t t = 0; t < (int64_t)count * n; ++t) call->adjoint_out[t] = nan;
-    }
-};
-
-// a call on the solve context: its error text is the handle's
-#define ADJ_TRY(expr)                               \
-    do {                                            \
-        const int _as = (expr);                     \
-        if (_as != NODAL_OK) {                      \
-            if (s != h) h->err = s->err;            \
-            return _as;                             \
-        }                                           \
-    } while (0)
-
-}  // namespace
-
-int sparse_solve_adjoint(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, const SensCall *call) {
-    const int64_t n = h->n;
-    hipStream_t st = h->stream;
-    std::vector<double> resid_host(call->resid_out ? 0 : (size_t)count);
-    for (int32_t m = 0; m < count; ++m) call->info_out[m] = 0;
-    AdjointCtx c{h, s, call, call->resid_out ? call->resid_out : resid_host.data(), call->info_out, nullptr};
-    const bool passive = s == h;
-    const int64_t densify_max = 4096;        // the bounds of sparse_solve_sources
-    const int64_t dense_general_max = 8192;
-    const size_t vb = (size_t)n * SLU_MULTI * 8;
-
-    if (dense || n <= 64 || (passive && n <= densify_max) || (!passive && n <= dense_general_max)) {
-        // one LU per chunk of up to 512 outputs: their columns c ride along as right-hand sides of the augmented panel
-        const int32_t CHUNK = 512;
-        const int64_t lda = dense_lda(n);
-        const int32_t first = count < CHUNK ? count : CHUNK;
-        NODAL_HIP_TRY(h, h->sw_blk.reserve((size_t)n * first * 8 + 5 * SLU_MULTI * 8 + 256));
-        double *Bc = h->sw_blk.as<double>();  // the same columns, kept for the judgement ([m][n])
-        c.norms = Bc + (size_t)n * first;
-        for (int32_t q0 = 0; q0 < count; q0 += CHUNK) {
-            const int32_t m = count - q0 < CHUNK ? count - q0 : CHUNK;
-            NODAL_HIP_TRY(h, s->dense.reserve((size_t)lda * (size_t)(n + m) * 8 + 64));
-            if (s->csr_only) ADJ_TRY(csr_to_dense(s, s->dense.as<double>(), lda));
-            else NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
-            double *cols = s->dense.as<double>() + n * lda;
-            NODAL_HIP_TRY(h, hipMemsetAsync(cols, 0, (size_t)lda * m * 8, st));
-            for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
-                const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
-                NODAL_TRY(sens_rhs_block(h, call, q0 + g0, k, cols + g0 * lda, 1, lda));
-                NODAL_TRY(c.fold(q0 + g0, k, Bc + g0 * n, 1, n, (size_t)n * k * 8));
-            }
-            NODAL_HIP_TRY(h, s->solver.reserve((size_t)n * m * 8 + 64));
-            double *X = s->solver.as<double>();
-            int32_t inf = 0;
-            ADJ_TRY(dense_factor_solve_multi(s, m, X, n, &inf));
-            if (inf > 0) {
-                if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
-                c.all_singular(count);
-                return NODAL_OK;
-            }
-            for (int32_t g0 = 0; g0 < m; g0 += SLU_MULTI) {
-                const int k = m - g0 < SLU_MULTI ? m - g0 : SLU_MULTI;
-                NODAL_TRY(c.judge(q0 + g0, k, X + g0 * n, Bc + g0 * n, 1, n));
-                NODAL_TRY(c.hand_over(q0 + g0, k, X + g0 * n, 1, n, X + g0 * n));
-            }
-        }
-        return NODAL_OK;
-    }
-
-    // blocks interleaved by row: B, X, R, D; then [16][n] rows, one vector b, the norms
-    NODAL_HIP_TRY(h, h->sw_blk.reserve(5 * vb + (size_t)n * 8 + 5 * SLU_MULTI * 8 + 256));
-    double *Bil = h->sw_blk.as<double>(), *Xil = Bil + (size_t)n * SLU_MULTI, *Ril = Xil + (size_t)n * SLU_MULTI,
-           *Dil = Ril + (size_t)n * SLU_MULTI, *rows = Dil + (size_t)n * SLU_MULTI, *bvec = rows + (size_t)n * SLU_MULTI;
-    c.norms = bvec + n;
-    const unsigned gv = (unsigned)std::min<int64_t>((n * SLU_MULTI + TB - 1) / TB, 65536);
-    // the block's adjoints as rows, when the caller wants them
-    auto rows_of = [&](int cnt) -> const double * {
-        if (!call->adjoint_out) return nullptr;
-        deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
-        return rows;
-    };
-
-    if (passive) {
-        // output 0 sets the multigrid hierarchy up (or finds it); the others go sixteen at a time through the block
-        // iteration.  A block that breaks down or hits its cap is redone column by column, and a column the iteration
-        // fails on -- with every later one -- by the sparse direct solve.
-        bool direct = n < h->amg_min_n, block_ok = true;
-        auto one = [&](int32_t m) -> int {
-            NODAL_TRY(c.fold(m, 1, bvec, 1, 0, (size_t)n * 8));
-            int32_t inf = 0, it = 0;
-            double rs = 0.0;
-            bool done = false;
-            if (!direct) {
-                const int sv = amg_fcg_solve_ex(h, bvec, m == 0, &inf, &it, &rs);  // (writes h->x: the caller has set the solution aside)
-                if (sv == -2) return -2;  // floating island: every output is singular
-                if (sv == NODAL_OK) {
-                    NODAL_HIP_TRY(h, hipMemcpyAsync(rows, h->x.as<double>(), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-                    done = true;
-                } else if (sv < 0) {
-                    direct = true;
-                } else {
-                    return sv;
-                }
-            }
-            if (!done) {
-                NODAL_TRY(sparse_direct_solve(h, bvec, rows, &inf, &it, &rs));
-                if (inf > 0) {
-                    call->info_out[m] = 1;
-                    NODAL_TRY(c.nan_rows(rows, 1));
-                }
-            }
-            NODAL_TRY(c.judge(m, 1, rows, bvec, 1, 0));
-            return c.hand_over(m, 1, rows, 1, 0, rows);
-        };
-        for (int32_t m0 = 0; m0 < count;) {
-            const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
-            if (m0 > 0 && !direct && block_ok && cnt >= 2 && sagg_ready(h, n)) {
-                NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
-                int32_t it = 0;
-                const int sv = sagg_fcg_solve_block(h, cnt, Bil, Xil, &it);
-                if (sv == NODAL_OK) {
-                    NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
-                    const double *r = rows_of(cnt);
-                    NODAL_HIP_TRY(h, hipGetLastError());
-                    NODAL_TRY(c.hand_over(m0, cnt, Xil, SLU_MULTI, 1, r));
-                    m0 += cnt;
-                    continue;
-                }
-                if (sv > 0) return sv;
-                block_ok = false;  // (latched: a second failing block would cost its cap again for nothing)
-            }
-            const int sv = one(m0);
-            if (sv == -2) {
-                c.all_singular(count);
-                return NODAL_OK;
-            }
-            NODAL_TRY(sv);
-            ++m0;
-        }
-        return NODAL_OK;
-    }
-
-    // G^T of a network with branch unknowns or controlled sources: ONE sparse LU of the child, then per block of sixteen
-    // outputs two substitutions, one refinement step and the judgement; a column above the bar -- and every column when
-    // the factorisation had to replace pivots -- is redone alone by the sparse direct solve on the child.
-    int32_t inf = 0;
-    ADJ_TRY(slu_factor(s, &inf));
-    if (inf > 0) {
-        c.all_singular(count);
-        return NODAL_OK;
-    }
-    bool all_direct = slu_perturbed(s) > 0;
-    const double bar = 1e-14;  // the backward-error bar of the refinement, as the sweep's
-    for (int32_t m0 = 0; m0 < count; m0 += SLU_MULTI) {
-        const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
-        bool good = !all_direct;
-        if (!all_direct) {
-            NODAL_TRY(c.fold(m0, cnt, Bil, SLU_MULTI, 1, vb));
-            ADJ_TRY(slu_apply_multi(s, Bil, Xil));
-            csr_residual_multi<<<gv, TB, 0, st>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(), s->data.as<double>(),
-                                                 Xil, Bil, Ril);
-            ADJ_TRY(slu_apply_multi(s, Ril, Dil));
-            add_into<<<gv, TB, 0, st>>>(n * SLU_MULTI, Dil, Xil);
-            NODAL_HIP_TRY(h, hipGetLastError());
-            NODAL_TRY(c.judge(m0, cnt, Xil, Bil, SLU_MULTI, 1));
-            for (int y = 0; y < cnt; ++y) good = good && c.resid[m0 + y] <= bar;
-        }
-        if (good) {  // the usual case: the block stays interleaved for the table kernel
-            const double *r = rows_of(cnt);
-            NODAL_HIP_TRY(h, hipGetLastError());
-            NODAL_TRY(c.hand_over(m0, cnt, Xil, SLU_MULTI, 1, r));
-            continue;
-        }
-        if (!all_direct) {
-            deinterleave_rows<<<grid_rows(n * cnt, 1), TB, 0, st>>>(n, cnt, Xil, rows);
-            NODAL_HIP_TRY(h, hipGetLastError());
-        }
-        for (int y = 0; y < cnt; ++y) {
-            if (!all_direct && c.resid[m0 + y] <= bar) continue;
-            NODAL_TRY(c.fold(m0 + y, 1, bvec, 1, 0, (size_t)n * 8));
-            int32_t inf1 = 0, it = 0;
-            double rs = 0.0;
-            ADJ_TRY(sparse_direct_solve(s, bvec, rows + (size_t)y * n, &inf1, &it, &rs));
-            if (inf1 > 0) {
-                call->info_out[m0 + y] = 1;
-                NODAL_TRY(c.nan_rows(rows + (size_t)y * n, 1));
-            }
-            NODAL_TRY(c.judge(m0 + y, 1, rows + (size_t)y * n, bvec, 1, 0));
-        }
-        NODAL_TRY(c.hand_over(m0, cnt, rows, 1, n, rows));
-        if (!all_direct) {  // (the direct solve may have factored anew, with another pivot bar)
-            ADJ_TRY(slu_factor(s, &inf));
-            all_direct = inf > 0 || slu_perturbed(s) > 0;
-        }
-    }
-    return NODAL_OK;
-}
-#undef ADJ_TRY

@@ -234,6 +234,16 @@ def test_envelope_small_networks(sparse, M):
         check_envelope(nl, sources, sw, tag=(name, sparse, M))
 
 
+def test_envelope_dense_chunk_edge():
+    """513 members on the dense route: the envelope is fed one full chunk of 512 and a chunk of one"""
+    rows, names = _grid_with_loads(6, 3, 6)
+    sources = sweep_of(rows, names, 513, 513)
+    nl = n.Netlist.from_rows(rows)
+    sw = n.Circuit(nl, sparse=False).solve_sources(sources, branches=True)
+    assert sw.result.shape[0] == 513
+    check_envelope(nl, sources, sw, tag=("grid(6) with loads", 513))
+
+
 @pytest.fixture(scope="module")
 def grid300():
     rows, names = _grid_with_loads(300, 6, 3)

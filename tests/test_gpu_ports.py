@@ -135,6 +135,24 @@ def test_sparse_lu_route_and_the_matrix_is_not_transposed(cfg5_95):
     assert miss > 100.0
 
 
+def test_redo_branch_of_the_sparse_lu_route(cfg5_95, monkeypatch):
+    """NODAL_MULTI_BAR=-1: every column fails the bar, is redone alone and the factors are made anew; then the same
+    call with the switch off, on the same Circuit, meets the refinement's own bar again"""
+    rows, nl, r0 = cfg5_95
+    c = n.Circuit(nl, sparse=True)
+    assert c._handle.n > 8192
+    c.solve()
+    ports = ref.sample_ports(nl, 18, CFG5_SEED)
+    r = ref.PortReference(r0, ports)
+    monkeypatch.setenv("NODAL_MULTI_BAR", "-1")
+    redone = c.thevenin(ports)
+    monkeypatch.delenv("NODAL_MULTI_BAR")
+    check_parity(redone, r, ("cfg5(95), every column redone", 18))
+    check_parity(c.thevenin(ports), r, ("cfg5(95), after the redo", 18), resid_bar=1e-14)
+    wrong = ref.PortReference(ref.Reference(nl, sparse=True, transposed=True), ports)
+    assert wrong.worst_miss(redone.z) > 100.0
+
+
 # ---- 5, 6: the dense switch on a grid, a low-degree network -----------------------------------------------------------
 def test_dense_switch_on_a_grid():
     nl = n.Netlist.from_rows(list(gen.grid_rows(40)))
@@ -143,6 +161,26 @@ def test_dense_switch_on_a_grid():
     ports = _with_ground(nl, 19, 40)
     eq = c.thevenin(ports)
     check_parity(eq, ref.PortReference(ref.Reference(nl, sparse=True, transposed=False), ports), ("grid(40) dense", 19))
+
+
+def test_dense_chunk_edge():
+    """513 ports on the dense route: Z is gathered from one full chunk of 512 columns and a chunk of one"""
+    rows, _ = _grid_with_loads(6, 3, 6)
+    nl = n.Netlist.from_rows(rows)
+    c = n.Circuit(nl, sparse=False)
+    c.solve()
+    ports = ref.sample_ports(nl, 513, 513)  # (drawn with repetition from 36 nodes and ground)
+    ports[512], ports[511] = ports[0], ports[3]  # equal ports on both sides of the chunk edge
+    eq = c.thevenin(ports)
+    check_parity(eq, ref.PortReference(ref.Reference(nl, sparse=False, transposed=False), ports), ("grid(6) dense", 513))
+    first = {}
+    repeated = 0
+    for q, port in enumerate(ports):
+        p = first.setdefault(port, q)
+        if p != q:
+            repeated += 1
+            assert np.array_equal(eq.z[:, q], eq.z[:, p]), (p, q)
+    assert repeated > 100 and first[ports[0]] == 0
 
 
 def test_low_degree_network():

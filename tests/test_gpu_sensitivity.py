@@ -2,6 +2,7 @@
 numpy restatement of tests/sensitivity_reference.py (the oracle's G, an LU of G^T, the per-row formulas), never from
 product code; every bar is a multiple of the formulas' own scale F^abs (see that module)."""
 import math
+import types
 import warnings
 
 import numpy as np
@@ -169,6 +170,49 @@ def test_dense_switch_on_a_grid():
     specs = _with_ground(nl, r.table, 19, 40)
     sens = c.sensitivities(specs, adjoints=True)
     check_against_reference(c, nl, r, specs, sens, ("grid(40) dense", 19))
+
+
+@pytest.mark.parametrize("adjoints", [True, False], ids=["adjoints", "plain"])
+def test_redo_branch_of_the_sparse_lu_route(cfg5_95, monkeypatch, adjoints):
+    """NODAL_MULTI_BAR=-1: every column fails the bar, is redone alone on the child and the factors are made anew; then
+    the same call with the switch off, on the same Circuit, meets the refinement's own bar again"""
+    rows, nl, r = cfg5_95
+    c = n.Circuit(nl, sparse=True)
+    assert c._handle.n > 8192
+    c.solve()
+    specs = ref.sample_outputs(nl, r.table, 18, 18)
+    monkeypatch.setenv("NODAL_MULTI_BAR", "-1")
+    redone = c.sensitivities(specs, adjoints=adjoints)
+    monkeypatch.delenv("NODAL_MULTI_BAR")
+    again = c.sensitivities(specs, adjoints=adjoints)
+    for sens, bar in ((redone, 1e-12), (again, 1e-14)):
+        # (without the adjoints the reference check reads their shape alone)
+        lam = sens.adjoints if adjoints else np.empty((18, r.table.K + r.table.B))
+        part = types.SimpleNamespace(values=sens.values, adjoints=lam, info=sens.info, output_values=sens.output_values,
+                                     scaled_residual=sens.scaled_residual)
+        check_against_reference(c, nl, r, specs, part, ("cfg5(95), redo", bar), residual_check=adjoints)
+        assert (sens.scaled_residual <= bar).all(), sens.scaled_residual.max()
+
+
+@pytest.mark.parametrize("which", ["random0", "grid(6)"])
+def test_dense_chunk_edge(which):
+    """513 outputs on the dense route -- one full chunk of 512 and a chunk of one -- on the transposed child (random0)
+    and on the handle itself (a passive grid)"""
+    rows = _random_rows(0) if which == "random0" else list(gen.grid_rows(6))
+    nl = n.Netlist.from_rows(rows)
+    c = n.Circuit(nl, sparse=False)
+    c.solve()
+    r = ref.Reference(nl, sparse=False)
+    outputs = ref.all_outputs(nl, r.table)
+    specs = [outputs[q % len(outputs)] for q in range(513)]
+    sens = c.sensitivities(specs, adjoints=True)
+    assert sens.values.shape == (513, r.table.ncomp) and (sens.info == 0).all()
+    for lo, hi in ((0, 33), (496, 513)):
+        part = types.SimpleNamespace(values=sens.values[lo:hi], adjoints=sens.adjoints[lo:hi], info=sens.info[lo:hi],
+                                     output_values=sens.output_values[lo:hi], scaled_residual=sens.scaled_residual[lo:hi])
+        check_against_reference(c, nl, r, specs[lo:hi], part, (which, lo, hi))
+    for q in range(len(outputs), 513):
+        assert np.array_equal(sens.values[q], sens.values[q % len(outputs)]), q
 
 
 def _ladder_rows(sections):

@@ -190,6 +190,55 @@ def test_lu_route_on_a_network_with_branches():
         assert normwise(sw.result[m], spla.spsolve(G, A)) <= TOL
 
 
+def test_redo_branch_of_the_lu_route(monkeypatch):
+    """NODAL_MULTI_BAR=-1: every member fails the bar, is redone alone and the factors are made anew; then the same
+    call with the switch off, on the same Circuit, meets the refinement's own bar again"""
+    rows = gen.cfg5_rows(95)
+    nl = n.Netlist.from_rows(rows)
+    names = sorted(r[0] for r in rows if r[1] == "E")
+    M = 18
+    sources = sweep_of(rows, names, M, 5)
+    c = n.Circuit(nl, sparse=True)
+    assert c._handle.n > 8192
+    G, _, _ = oracle.build_model(nl, True)
+    G = G.tocsc()
+    tab_rows, values = resolve_sources(nl, sources)
+    want = _spsolve_members(G, c, tab_rows, values)
+    monkeypatch.setenv("NODAL_MULTI_BAR", "-1")
+    redone = c.solve_sources(sources)
+    monkeypatch.delenv("NODAL_MULTI_BAR")
+    again = c.solve_sources(sources)
+    for sw, bar in ((redone, 1e-12), (again, 1e-14)):
+        assert (sw.info == 0).all()
+        print("largest scaled residual", sw.scaled_residual.max(), "bar", bar)
+        assert (sw.scaled_residual <= bar).all(), sw.scaled_residual.max()
+        for m, xo in enumerate(want):
+            assert normwise(sw.result[m], xo) <= TOL, m
+        # the members' A really are the rebuilt netlists' (two of them through the front end)
+        for m in (0, M - 1):
+            A = n.Circuit(n.Netlist.from_rows(rebuilt(rows, sources, m)), sparse=True).A
+            assert normwise(sw.result[m], spla.spsolve(G, A)) <= TOL
+
+
+def test_dense_chunk_edge():
+    """513 members on the dense route: one full chunk of 512 and a chunk of one"""
+    rows, names = _grid_with_loads(6, 3, 6)
+    nl = n.Netlist.from_rows(rows)
+    M = 513
+    sources = sweep_of(rows, names, M, 513)
+    c = n.Circuit(nl, sparse=False)
+    sw = c.solve_sources(sources)
+    assert sw.result.shape == (M, c._handle.n)
+    assert (sw.info == 0).all()
+    assert (sw.scaled_residual <= 1e-12).all(), sw.scaled_residual.max()
+    G, _, _ = oracle.build_model(nl, True)
+    tab_rows, values = resolve_sources(nl, sources)
+    picks = [0, 511, 512] + random.Random(513).sample(range(1, 511), 3)
+    want = _spsolve_members(G.tocsc(), n.Circuit(nl, sparse=True), tab_rows, values[picks])
+    for m, xo in zip(picks, want):
+        assert normwise(sw.result[m], xo) <= TOL, m
+
+
 def test_floating_island():
     rows = list(gen.grid_rows(70))
     rows += [[f"f{i}", "R", "1", f"x{i}", f"x{i + 1}"] for i in range(40)]
