@@ -22,7 +22,7 @@ $(LIB): $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--wrap=hipLaunchKernel -Wl,--wrap=hipExtLaunchKernel -o $@ $(OBJ)
 
 # host-side netlist tokenizer (front-end, optional: fastparse.py falls back to pandas without it)
-$(CSVLIB): nodal_amd/csrc/fastcsv.cpp
+$(CSVLIB): nodal_amd/csrc/fastcsv.cpp nodal_amd/csrc/knobs.h
 	g++ -O2 -std=c++17 -fPIC -shared -pthread -Wall -o $@ $<
 
 oracle:

@@ -1046,7 +1046,7 @@ int build_blocks(nodal_ctx *h, Level *L, double *flag) {
                                                      L->binv.as<double>(), flag);
     NODAL_HIP_TRY(h, hipGetLastError());
     L->block = true;
-    if (getenv("NODAL_TRACE")) {
+    if (knob::TRACE.now()) {
         uint32_t *st3 = reinterpret_cast<uint32_t *>(h->work.as<char>());
         NODAL_HIP_TRY(h, hipMemsetAsync(st3, 0, 12, st));
         block_stats<<<grid_for(nc), TB, 0, st>>>(nc, L->memptr.as<int32_t>(), st3);
@@ -1206,9 +1206,9 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
         h->amg = H;
     }
     H->begin_setup();
-    if (const char *e = getenv("NODAL_AMG_PASSES0")) { H->passes0 = atoi(e); H->passes_forced = true; }
-    if (const char *e = getenv("NODAL_AMG_SWEEPS0")) H->sweeps0 = atoi(e);
-    if (const char *e = getenv("NODAL_AMG_PASSES1")) { H->passes1 = atoi(e); H->passes_forced = true; }
+    if (const auto v = knob::AMG_PASSES0.now()) { H->passes0 = *v; H->passes_forced = true; }
+    if (const auto v = knob::AMG_SWEEPS0.now()) H->sweeps0 = *v;
+    if (const auto v = knob::AMG_PASSES1.now()) { H->passes1 = *v; H->passes_forced = true; }
     hipStream_t st = h->stream;
 
     Level *l0 = H->take(0);
@@ -1225,8 +1225,8 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
     // a decade or more -- 5 % of the nodes at one decade, 75 % at two -- or anisotropy) -- Jacobi
     // over the aggregates' diagonal blocks.
     // NODAL_AMG_BLOCK=0 / 1 forces the choice.
-    if (const char *e = getenv("NODAL_AMG_BLOCK")) {
-        H->block_smoother = atoi(e) != 0;
+    if (const auto v = knob::AMG_BLOCK.now()) {
+        H->block_smoother = *v != 0;
     } else {
         NODAL_HIP_TRY(h, h->work.reserve(256));
         uint32_t *cnt = h->work.as<uint32_t>();
@@ -1240,7 +1240,7 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
         // find by itself -- 100 near-shorts in a 90 000-node grid cost point Jacobi 880 iterations)
         const int64_t bar = n0 / 100 < 32 ? (n0 / 100 > 0 ? n0 / 100 : 1) : 32;
         H->block_smoother = (int64_t)dominated >= bar;
-        if (getenv("NODAL_TRACE"))
+        if (knob::TRACE.now())
             fprintf(stderr, "[amg] %u of %lld nodes have graded links (one > 0.9 of the diagonal, or > 8 x the weakest): %s smoother\n", dominated,
                     (long long)n0, H->block_smoother ? "aggregate-block" : "point Jacobi");
     }
@@ -1250,7 +1250,7 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
     // the smoother's blocks) at ~8 nodes.  300 x 300 grid over 4 / 6 decades: 76 / 220
     // iterations with plain matching and three passes, 40 / 68 with this.
     H->theta = H->block_smoother ? 0.1 : 0.0;
-    if (const char *e = getenv("NODAL_AMG_THETA")) H->theta = atof(e);
+    if (const auto v = knob::AMG_THETA.now()) H->theta = *v;
 
     while ((int)H->levels.size() < MAX_LEVELS) {
         Level *fine = H->levels.back();
@@ -1312,8 +1312,8 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
         if (H->levels.size() == 1 && coarse->A.n > 0) {
             const double fine_row = (double)fine->A.nnz / (double)n;
             const double coarse_row = (double)coarse->A.nnz / (double)coarse->A.n;
-            if (coarse_row > 32.0 && coarse_row > 4.0 * fine_row && !getenv("NODAL_AMG_KEEP_DENSE")) {
-                if (getenv("NODAL_TRACE"))
+            if (coarse_row > 32.0 && coarse_row > 4.0 * fine_row && !knob::AMG_KEEP_DENSE.now()) {
+                if (knob::TRACE.now())
                     fprintf(stderr, "[amg] first coarse level has %.0f entries per row (fine: %.1f): expander-like, "
                                     "Jacobi preconditioner only\n", coarse_row, fine_row);
                 fine->nc = 0;
@@ -1330,9 +1330,9 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
         NODAL_HIP_TRY(h, H->coarse_inv.reserve((size_t)last->A.n * last->A.n * 8 + 8));
         coarsest_inverse<<<1, 256, 0, st>>>(last->A, H->coarse_inv.as<double>(), flag);
         NODAL_HIP_TRY(h, hipGetLastError());
-        if (!getenv("NODAL_AMG_NOTAIL")) NODAL_TRY(build_tail(h, H));
+        if (!knob::AMG_NOTAIL.now()) NODAL_TRY(build_tail(h, H));
     }
-    if (const char *e = getenv("NODAL_AMG_KMAX")) H->kmax = atoi(e);
+    if (const auto v = knob::AMG_KMAX.now()) H->kmax = *v;
     else {
         // K-cycle on the coarse levels that are still large (>= K_MIN_ROWS rows), plain V
         // hand-over below, where a V-cycle over a few thousand rows (and the tail's own two
@@ -1346,7 +1346,7 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
         const int upto = H->tail >= 0 ? H->tail : nl - 1;  // levels [0, upto) run through cycle()
         for (int l = 0; l < upto; ++l) NODAL_TRY(build_blocks(h, H->levels[l], flag));
     }
-    if (getenv("NODAL_TRACE")) {
+    if (knob::TRACE.now()) {
         fprintf(stderr, "[amg] levels (rows/entries):");
         for (const Level *l : H->levels) fprintf(stderr, " %lld/%lld", (long long)l->A.n, (long long)l->A.nnz);
         fprintf(stderr, "  kmax %d tail %d\n", H->kmax, H->tail);

@@ -134,7 +134,7 @@ int nodal_create(int device_id, nodal_handle *out) {
     // factorisation, multigrid cycles)
     int lo = 0, hi = 0;  // least / greatest priority
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (const char *e = getenv("NODAL_STREAM_PRIORITY"))  // "normal": the default priority instead of the highest
+    if (const char *e = knob::STREAM_PRIORITY.now())  // "normal": the default priority instead of the highest
         if (e[0] == 'n') hi = 0;
     if (hipSetDevice(device_id) != hipSuccess ||
         hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, hi) != hipSuccess) {
@@ -146,11 +146,11 @@ int nodal_create(int device_id, nodal_handle *out) {
             delete h;
             return NODAL_E_HIP;
         }
-    if (const char *e = getenv("NODAL_DENSE_BLOCKINV")) h->dense_blockinv = atoi(e) != 0;
-    if (const char *e = getenv("NODAL_GJ_SCALAR")) h->gj_scalar = atoi(e);
-    if (const char *e = getenv("NODAL_GEPP_PANEL")) h->gepp_panel = atoi(e) != 0;
-    if (const char *e = getenv("NODAL_PRESOLVE")) h->use_presolve = atoi(e) != 0;  // 0: branch equations stay in the system
-    if (const char *e = getenv("NODAL_EXTRA_STREAMS")) h->extra_streams = atoi(e) != 0;
+    if (const auto v = knob::DENSE_BLOCKINV.now()) h->dense_blockinv = *v != 0;
+    if (const auto v = knob::GJ_SCALAR.now()) h->gj_scalar = *v;
+    if (const auto v = knob::GEPP_PANEL.now()) h->gepp_panel = *v != 0;
+    if (const auto v = knob::PRESOLVE.now()) h->use_presolve = *v != 0;  // 0: branch equations stay in the system
+    if (const auto v = knob::EXTRA_STREAMS.now()) h->extra_streams = *v != 0;
     g_live_handles.fetch_add(1, std::memory_order_relaxed);
     *out = h;
     return NODAL_OK;
@@ -208,8 +208,7 @@ int nodal_ensure_aux_streams(nodal_ctx *ctx) {
         // fall back to a low-priority stream.)
         if (!h->stream2) {
             uint32_t mask[8];
-            int reserve = 32;  // CUs kept free for the main stream (NODAL_PANEL_CUS to tune)
-            if (const char *e = getenv("NODAL_PANEL_CUS")) reserve = atoi(e);
+            int reserve = knob::PANEL_CUS.now();  // CUs kept free for the main stream
             if (reserve < 0) reserve = 0;
             if (reserve > 224) reserve = 224;
             for (int i = 0; i < 8; ++i) mask[i] = 0xFFFFFFFFu;
@@ -289,7 +288,7 @@ void nodal_poison_scratch(nodal_ctx *h) {
 }
 
 void nodal_nan_probe(nodal_ctx *h, const double *dev, int64_t n, const char *tag) {
-    static const bool on = getenv("NODAL_NANCHECK") != nullptr;
+    static const bool on = knob::NANCHECK.now();
     if (!on || !dev || n <= 0) return;
     std::vector<double> host((size_t)n);
     if (nodal_wait_stream(h, h->stream, NODAL_SITE) != NODAL_OK ||

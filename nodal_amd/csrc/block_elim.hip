@@ -506,7 +506,7 @@ int invert_diag(nodal_ctx *h, hipStream_t sp, double *D, int64_t lda, int w, dou
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, GJ16_LDS));
                 lds_allowed[dev].store(true, std::memory_order_release);
             }
-            static const bool gj_dpp = !(getenv("NODAL_GJ_DPP") && atoi(getenv("NODAL_GJ_DPP")) == 0);
+            static const bool gj_dpp = knob::GJ_DPP.now();
             if (gj_dpp) gj128_mfma16<true><<<1, 1024, GJ16_LDS, sp>>>(D, lda, w, Q, ldq, dinfo, base);
             else gj128_mfma16<false><<<1, 1024, GJ16_LDS, sp>>>(D, lda, w, Q, ldq, dinfo, base);
         }
@@ -550,13 +550,13 @@ int factor_blockinv(nodal_ctx *h, double *A, int64_t n, int64_t lda, int64_t nco
     // since the symmetric form halved the bulk work the chain bounds 30 of config 2's 39 blocks, and its
     // workgroups no longer queue behind 58-us GEMM workgroups (14.37 -> 13.92 ms; 8 / 16 / 64 CUs: 14.15 /
     // 14.12 / 14.69).  NODAL_BI_MASKED=0: bulk updates on all CUs (the default until the symmetric form).
-    static const bool full_mask = getenv("NODAL_BI_MASKED") != nullptr && atoi(getenv("NODAL_BI_MASKED")) == 0;
+    static const bool full_mask = knob::BI_MASKED.now();
     // NODAL_BI_UNMASK_ROWS=r (round 5, measured, off): the bulk update on ALL compute units while more than r rows are
     // left, on the masked stream afterwards (the two side streams swap roles at that block).  The idea -- the bulk update
     // bounds the first two thirds of the solve and the mask costs it an eighth of the chip -- did not survive the
     // measurement: config 2 13.65 ms without, 14.28 / 13.98 / 13.70 / 13.85 ms for r = 4000 / 5632 / 7000 / 8500: the chain's
     // small kernels queueing behind 58-us GEMM workgroups cost more than the 32 CUs give, in every phase.
-    static const int64_t unmask_rows = getenv("NODAL_BI_UNMASK_ROWS") ? atoll(getenv("NODAL_BI_UNMASK_ROWS")) : 0;
+    static const int64_t unmask_rows = knob::BI_UNMASK_ROWS.now();
     const bool adaptive = !full_mask && unmask_rows > 0 && unmask_rows < n;
     hipStream_t sp = h->stream, sg = (full_mask || adaptive) ? h->stream3 : h->stream2;
     hipStream_t s3 = (full_mask || adaptive) ? h->stream2 : h->stream3;
@@ -599,7 +599,7 @@ int factor_blockinv(nodal_ctx *h, double *A, int64_t n, int64_t lda, int64_t nco
         NODAL_HIP_TRY(h, hipGetLastError());
         return NODAL_OK;
     };
-    static const bool early_copy_env = !(getenv("NODAL_BI_EARLY_COPY") && atoi(getenv("NODAL_BI_EARLY_COPY")) == 0);
+    static const bool early_copy_env = knob::BI_EARLY_COPY.now();
     const bool early_copy = sym && early_copy_env;
     // sym: Lt(k) = (first w_next columns of V(k))^T, the rows J1:J2 of the never-formed block column k
     auto head_transpose = [&](hipStream_t st, int k) -> int {
@@ -611,7 +611,7 @@ int factor_blockinv(nodal_ctx *h, double *A, int64_t n, int64_t lda, int64_t nco
         return NODAL_OK;
     };
     // W(k)'s first columns: those the next two diagonal blocks (k + 1, k + 2) read
-    static const int first_blocks = getenv("NODAL_BI_FIRST_BLOCKS") ? atoi(getenv("NODAL_BI_FIRST_BLOCKS")) : 2;
+    static const int first_blocks = knob::BI_FIRST_BLOCKS.now();
     auto first_end = [&](int k) {
         const int to = k + 1 + (first_blocks < 1 ? 1 : (first_blocks > 2 ? 2 : first_blocks));
         const int64_t e = bnd[to < nb ? to : nb];
@@ -724,13 +724,13 @@ int dense_block_elimination(nodal_ctx *h, double *A, int64_t n, int64_t lda, int
     std::vector<int64_t> bnd;
     {
         int64_t sw = 4608;
-        if (const char *e = getenv("NODAL_BI_SWITCH")) sw = atoll(e);
+        if (const char *e = knob::BI_SWITCH.now()) sw = atoll(e);
         // below sw2 rows left the chain of small kernels is far longer than the bulk update: 128-wide blocks need
         // ONE Gauss-Jordan inversion each instead of the 2 x 2 Schur formula's two inversions + four products
         int64_t sw2 = 0;
-        if (const char *e = getenv("NODAL_BI_SWITCH2")) sw2 = atoll(e);
+        if (const char *e = knob::BI_SWITCH2.now()) sw2 = atoll(e);
         int forced = 0;
-        if (const char *e = getenv("NODAL_BI_WIDTH")) {
+        if (const char *e = knob::BI_WIDTH.now()) {
             const int v = atoi(e);
             forced = v == 512 ? 512 : (v == 128 ? 128 : 256);
         }
@@ -744,9 +744,9 @@ int dense_block_elimination(nodal_ctx *h, double *A, int64_t n, int64_t lda, int
     }
     // a passive network's matrix is symmetric bit for bit (every off-diagonal pair is the same sum of the
     // same -1/R terms in the same order); a presolved system with transconductance stamps is not
-    static const bool sym_env = !(getenv("NODAL_BI_SYM") && atoi(getenv("NODAL_BI_SYM")) == 0);
+    static const bool sym_env = knob::BI_SYM.now();
     const bool sym = sym_env && h->passive_network && !h->optimistic_nopivot;
-    if (sym && getenv("NODAL_TRACE")) {
+    if (sym && knob::TRACE.now()) {
         NODAL_HIP_TRY(h, h->work3.reserve(256));
         unsigned long long *o = h->work3.as<unsigned long long>();
         NODAL_HIP_TRY(h, hipMemsetAsync(o, 0, 16, st));

@@ -6,11 +6,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/nodal_hip.h"
+#include "knobs.h"
 
 // A device allocation that grows on demand and is reused across calls, so the
 // launch path never calls hipMalloc once sizes have settled.
@@ -28,12 +30,7 @@ struct FillStreamScope {
 
 // 0: off; 1: growing buffers are filled with 0xFF; 2: scratch buffers too, at every solve entry
 inline int nodal_poison_level() {
-    static const int level = [] {
-        const char *e = getenv("NODAL_POISON");
-        if (!e) return 0;
-        const int v = atoi(e);
-        return v > 1 ? v : 1;
-    }();
+    static const int level = knob::POISON.now();
     return level;
 }
 
@@ -53,7 +50,7 @@ struct DevBuf {
         // NODAL_POISON=1 (debugging) fills with 0xFF bytes instead -- NaNs as doubles, -1 as integers;
         // NODAL_POISON=2 also re-poisons every scratch buffer of the handle at the entry of each solve
         // (nodal_poison_scratch, api.hip): what a pooled handle looks like after somebody else's solve.
-        static const bool nofill = getenv("NODAL_NOFILL") != nullptr;
+        static const bool nofill = knob::NOFILL.now();
         const bool poison = nodal_poison_level() > 0;
         if (e != hipSuccess || nofill) return e;
         if (nodal_fill_stream) return hipMemsetAsync(p, poison ? 0xFF : 0, want, nodal_fill_stream);
@@ -126,7 +123,7 @@ struct HostTable {
 template <class F>
 inline void nodal_parallel_chunks(int64_t n, int64_t min_chunk, int max_threads, F f) {
     unsigned hw = std::thread::hardware_concurrency();
-    if (const char *e = getenv("NODAL_HOST_THREADS")) hw = (unsigned)(atoi(e) > 1 ? atoi(e) : 1);
+    if (const auto t = knob::HOST_THREADS.now()) hw = (unsigned)std::max(1, *t);
     int64_t T = hw ? (int64_t)hw : 1;
     if (T > max_threads) T = max_threads;
     if (min_chunk < 1) min_chunk = 1;

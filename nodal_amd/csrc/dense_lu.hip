@@ -41,7 +41,7 @@ constexpr int NB = 32;          // inner block
 constexpr int W = 256;          // outer panel (K of the trailing update)
 // above this, tournament pivoting (2048 until round 3; with the panel kernel's 1024-row limit the tournament wins
 // from ~1250 unknowns on: n = 1338 6.0 instead of 6.8 ms, n = 1989 9.1 instead of 14.8 ms)
-static const int GEPP_MAX = getenv("NODAL_GEPP_MAX") ? atoi(getenv("NODAL_GEPP_MAX")) : 1280;
+static const int GEPP_MAX = knob::GEPP_MAX.now();
 constexpr int BLOCKINV_MIN = 256;  // passive systems larger than this: block elimination (block_elim.hip)
 constexpr int SLAB = 256;       // rows per tournament workgroup
 
@@ -843,7 +843,7 @@ int trailing_update(nodal_ctx *h, double *A, int64_t n, int64_t lda, int64_t nco
 int factor_gepp(nodal_ctx *h, double *A, int64_t n, int64_t lda, int64_t ncols, int32_t *piv,
                 int32_t *dinfo, GemmTimer &tm) {
     hipStream_t st = h->stream;
-    static const bool probing = getenv("NODAL_GEPP_PROBE") != nullptr;
+    static const bool probing = knob::GEPP_PROBE.now();
     long long *probe = nullptr;
     if (probing) {
         NODAL_HIP_TRY(h, h->work3.reserve(256));
@@ -1078,7 +1078,7 @@ int dense_factor_solve_multi(nodal_ctx *h, int32_t nrhs, double *xout, int64_t l
         j1 = j0;
     }
     NODAL_HIP_TRY(h, hipGetLastError());
-    static const bool trace_enq = getenv("NODAL_TRACE") != nullptr;
+    static const bool trace_enq = knob::TRACE.now();
     const auto t_enq = std::chrono::steady_clock::now();
     int32_t hinfo = 0;
     NODAL_TRY(nodal_read_words(h, &hinfo, dinfo, 4));

@@ -22,6 +22,8 @@
 #include <utility>
 #include <vector>
 
+#include "knobs.h"
+
 extern "C" {
 
 typedef struct {
@@ -314,12 +316,12 @@ int nodal_csv_parse(const char *buf, int64_t len, nodal_csv_result *out) {
     };
     // ---- chunks ----
     int threads = (int)std::thread::hardware_concurrency();
-    if (const char *e = getenv("NODAL_HOST_THREADS")) threads = atoi(e);
+    threads = knob::HOST_THREADS.now().value_or(threads);
     if (threads < 1) threads = 1;
     if (threads > 32) threads = 32;
     // (four chunks per thread: the threads stay level, and a chunk's label table stays in the L2 cache)
     int nchunks = threads > 1 ? 4 * threads : 1;
-    if (const char *e = getenv("NODAL_CSV_CHUNKS")) nchunks = atoi(e);  // (testing: more chunks than a small file deserves)
+    if (const auto c = knob::CSV_CHUNKS.now()) nchunks = *c;  // (testing: more chunks than a small file deserves)
     else if (len < (int64_t)nchunks * (1 << 18)) nchunks = (int)(len >> 18);
     if (nchunks < 1) nchunks = 1;
     if (nchunks > 256) nchunks = 256;
@@ -604,7 +606,7 @@ int nodal_format_lines(const char *labels, int64_t labels_len, int64_t nlabels, 
     *out = nullptr;
     *out_len = 0;
     int threads = (int)std::thread::hardware_concurrency();
-    if (const char *e = getenv("NODAL_HOST_THREADS")) threads = atoi(e);
+    threads = knob::HOST_THREADS.now().value_or(threads);
     if (threads < 1) threads = 1;
     if (threads > 32) threads = 32;
     if (nlabels < 20000) threads = 1;

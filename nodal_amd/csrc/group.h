@@ -513,7 +513,7 @@ int build_lists(nodal_ctx *h, const E &en, int64_t nrows, int64_t *nent_out, int
     {   // (NODAL_COUNT_LDS=1: the rows of a tile aggregated in LDS first.  Measured at config 3, round 5: the symbolic phase
         // 0.216 -> 0.241 ms -- the table's clear, three barriers and the LDS atomics of every tile cost more than the
         // memory-side requests they save; off, kept as the cross-check and for hub-heavy tables)
-        static const bool lds_count = getenv("NODAL_COUNT_LDS") && atoi(getenv("NODAL_COUNT_LDS")) != 0;
+        static const bool lds_count = knob::COUNT_LDS.now();
         if (lds_count) count_rows_lds<E><<<grid_for(en.nitems), TB, 0, st>>>(en, rowstart, pos);
         else count_rows<E><<<grid_for(en.nitems), TB, 0, st>>>(en, rowstart, pos);
     }

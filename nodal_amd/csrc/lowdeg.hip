@@ -322,14 +322,14 @@ int csr_to_dense(nodal_ctx *h, double *G_dev, int64_t ld) {
 // changed and the caller carries on with its own solver (the bar: n / min_share nodes).
 int lowdeg_solve(nodal_ctx *h, int min_share, bool *done, int32_t *info, int32_t *iters, double *resid) {
     *done = false;
-    const bool enabled = !(getenv("NODAL_LOWDEG") && atoi(getenv("NODAL_LOWDEG")) == 0);
-    const bool trace = getenv("NODAL_TRACE") != nullptr;
+    const bool enabled = knob::LOWDEG.now();
+    const bool trace = knob::TRACE.now();
     const int64_t n = h->n;
     if (!enabled || n < 2 || h->nnz >= (1ll << 29)) return NODAL_OK;
     hipStream_t st = h->stream;
     const View A = view_of(h);
     const auto t0 = std::chrono::steady_clock::now();
-    if (const char *e = getenv("NODAL_LOWDEG_SHARE")) min_share = atoi(e) > 0 ? atoi(e) : min_share;
+    if (const auto v = knob::LOWDEG_SHARE.now()) min_share = *v > 0 ? *v : min_share;
     const bool cached = h->ld_state != 0 && h->ld_epoch == h->struct_epoch && h->ld_share == min_share &&
                         h->ld_n == n && h->ld_nnz == A.nnz && (h->ld_state == 1 || h->lowdeg);
     auto remember = [&](int state) {

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(TB) void compact(DevTable t, int64_t nc,
 
 // Host analysis: pivots and expressions from the (few) branch components.
 static void presolve_plan(const nodal_ctx *h, const double *value, PresolvePlan &plan) {
-    static const bool trace_plan = getenv("NODAL_TRACE") != nullptr;
+    static const bool trace_plan = knob::TRACE.now();
     const auto tp0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
         if (trace_plan)
@@ -543,7 +543,7 @@ static void presolve_plan(const nodal_ctx *h, const double *value, PresolvePlan 
         plan.max_level = std::max(plan.max_level, 1 + height[v]);
     }
     if (taken.empty()) return;  // nothing can be eliminated: the full-system solve
-    static const bool keep_allowed = !(getenv("NODAL_PRESOLVE_KEEP") && atoi(getenv("NODAL_PRESOLVE_KEEP")) == 0);
+    static const bool keep_allowed = knob::PRESOLVE_KEEP.now();
     if (!keep_allowed)  // (round 2's behaviour, for comparisons: one stubborn source ends the presolve)
         for (const char b : bad)
             if (b) return;
@@ -701,7 +701,7 @@ static int presolve_build_reduced(nodal_ctx *h, nodal_ctx *r, const double *valu
     NODAL_TRY(nodal_read_words(h, back, flags, 12));
     if (back[0]) return NODAL_OK;  // a dependent source is controlled by a pivot node
     const int64_t nkeep = (uint32_t)back[1], nhit = (uint32_t)back[2];
-    static const bool trace_build = getenv("NODAL_TRACE") != nullptr;
+    static const bool trace_build = knob::TRACE.now();
     const auto tb0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
         if (trace_build)
@@ -893,7 +893,7 @@ int presolve_solve(nodal_ctx *h, bool *done, int32_t *info, int32_t *iters, doub
         if (h->host.values_batch.empty()) return NODAL_OK;
         value = h->host.values_batch.data() + (size_t)h->member * h->ncomp;
     }
-    const bool trace = getenv("NODAL_TRACE") != nullptr;
+    const bool trace = knob::TRACE.now();
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto t0 = now();

@@ -1294,7 +1294,7 @@ int width_class(int maxlen) {
 int choose_wfix(int maxlen, int64_t n, int64_t nnz, int pad_limit) {
     const int c = width_class(maxlen);
     if (c == 0 || c > pad_limit) return 0;
-    static const double slack = getenv("NODAL_SA_PADSLACK") ? atof(getenv("NODAL_SA_PADSLACK")) : 1.3;
+    static const double slack = knob::SA_PADSLACK.now();
     if ((double)c * (double)n <= slack * (double)nnz || n <= 32768) return c;
     return 0;
 }
@@ -1353,14 +1353,14 @@ int galerkin_product(nodal_ctx *h, SHierarchy *H, int l, hipEvent_t r_ready = nu
     // (level 0: 40 instead of 64 R entries per group -- 8.2 instead of 13.4 KB of LDS per wavefront, 19
     // instead of 11 wavefronts per CU; the few rows of R beyond 40 entries take a second group:
     // 8.80 -> 8.66 ms per fresh solve of the 1e6-node grid, 7.45 -> 7.22 ms with the patterns kept)
-    static const int g_env = getenv("NODAL_SA_GG") ? atoi(getenv("NODAL_SA_GG")) : 40;
+    static const int g_env = knob::SA_GG.now();
     if (g_env >= 8 && g_env <= 64 && apw == 16) G = g_env & ~7;
     const int pcap = G * apw + 72;  // (the list is padded with empty products up to the segments' common length)
     const size_t lds = 1024 + (size_t)pcap * 12;
     // (at most 16384 workgroups, each walking several rows: the one-workgroup fold of their statistics
     // reads 2 x 16384 words instead of 2 x 65536 -- 3 instead of 10 us)
-    static const int64_t gcap = getenv("NODAL_SA_GCAP") ? atoll(getenv("NODAL_SA_GCAP")) : 16384;
-    static const int maxseg = getenv("NODAL_SA_GSEG") ? atoi(getenv("NODAL_SA_GSEG")) : 4;
+    static const int64_t gcap = knob::SA_GCAP.now();
+    static const int maxseg = knob::SA_GSEG.now();
     const unsigned gg = (unsigned)(nc < gcap ? nc : (gcap < BSTAT_MAX ? gcap : BSTAT_MAX));
     if (r_ready) NODAL_HIP_TRY(h, hipStreamWaitEvent(st, r_ready, 0));  // (R was built on the hierarchy's other stream)
     galerkin<NUMERIC><<<gg, 64, lds, st>>>(
@@ -1381,7 +1381,7 @@ double omega_p(int level) {
     static double w[2] = {-1.0, -1.0};
     if (w[0] < 0.0) {
         double a = OMEGA_P, b = OMEGA_P_COARSE;
-        if (const char *e = getenv("NODAL_SA_OMEGA_P")) {
+        if (const char *e = knob::SA_OMEGA_P.now()) {
             a = atof(e);
             const char *c = strchr(e, ',');
             b = c ? atof(c + 1) : a;
@@ -1404,7 +1404,7 @@ struct FoldSetting { int mode = 0; unsigned mask = 0; };  // mode 0: by size, 1:
 const FoldSetting &fold_setting() {
     static const FoldSetting s = [] {
         FoldSetting f;
-        const char *e = getenv("NODAL_SA_FOLD_POST");
+        const char *e = knob::SA_FOLD_POST.now();
         if (!e || !*e) return f;
         if (strchr(e, 'l')) {
             f.mode = 3;
@@ -1464,9 +1464,9 @@ int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool
     void *scan_tmp = H->mis_id.as<char>() + (((size_t)(n + 1) * 4 + 63) & ~(size_t)63);
 
     const unsigned g = grid_for(n);
-    static const bool trace_mis = getenv("NODAL_TRACE") != nullptr;
+    static const bool trace_mis = knob::TRACE.now();
     if (trace_mis) NODAL_HIP_TRY(h, hipMemsetAsync(cnt, 0, (MIS_ROUNDS + 2) * 8, st));
-    static const int mis_rounds = getenv("NODAL_SA_MIS") ? std::min(MIS_ROUNDS, std::max(1, atoi(getenv("NODAL_SA_MIS")))) : MIS_ROUNDS;
+    static const int mis_rounds = std::min(MIS_ROUNDS, std::max(1, knob::SA_MIS.now().value_or(MIS_ROUNDS)));
     if (n <= MIS_SMALL_MAX && !trace_mis) {
         mis_small<<<1, 1024, 0, st>>>(A, T, M, flag, mis_rounds);
     } else {
@@ -1534,7 +1534,7 @@ int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool
 
     // R = P^T by coarse row -- on the hierarchy's other stream when there is one (see SHierarchy::aux): every
     // launch of this section, the scans included, goes where h->stream points
-    static const bool fork_allowed = !(getenv("NODAL_SA_FORK") && atoi(getenv("NODAL_SA_FORK")) == 0);
+    static const bool fork_allowed = knob::SA_FORK.now();
     if (H->aux && !nodal_extra_streams_ok(h) && nodal_calls_in_flight() <= 1) {  // (the option was taken back: so is the stream's hardware queue)
         NODAL_WAIT_STREAM(h, H->aux);
         (void)hipStreamDestroy(H->aux);
@@ -1731,7 +1731,7 @@ int tail_self_check(nodal_ctx *h, SHierarchy *H) {
 
 // T behind the image (fresh setup and values-only refresh)
 int form_tail_op(nodal_ctx *h, SHierarchy *H) {
-    static const bool on = !(getenv("NODAL_SA_TAIL_DENSE") && atoi(getenv("NODAL_SA_TAIL_DENSE")) == 0);
+    static const bool on = knob::SA_TAIL_DENSE.now();
     H->tail_dense = false;
     if (!on || H->tail < 0) return NODAL_OK;
     const TailDesc &d = H->td;
@@ -1753,7 +1753,7 @@ int form_tail_op(nodal_ctx *h, SHierarchy *H) {
     else k_tail_pack_op<32><<<gr, 1024, (size_t)d.lds_bytes, h->stream>>>(d, img, T);
     NODAL_HIP_TRY(h, hipGetLastError());
     H->tail_dense = true;
-    static const bool check = getenv("NODAL_TRACE") && getenv("NODAL_SA_TAIL_CHECK") && atoi(getenv("NODAL_SA_TAIL_CHECK")) != 0;
+    static const bool check = knob::TRACE.now() && knob::SA_TAIL_CHECK.now();
     if (check) NODAL_TRY(tail_self_check(h, H));
     return NODAL_OK;
 }
@@ -1826,7 +1826,7 @@ int fold_check_level(nodal_ctx *h, SHierarchy *H, int l, bool two) {
     return NODAL_OK;
 }
 int fold_self_check(nodal_ctx *h, SHierarchy *H) {
-    static const bool check = getenv("NODAL_TRACE") && getenv("NODAL_SA_FOLD_CHECK") && atoi(getenv("NODAL_SA_FOLD_CHECK")) != 0;
+    static const bool check = knob::TRACE.now() && knob::SA_FOLD_CHECK.now();
     if (!check) return NODAL_OK;
     for (int l = 0; l + 1 < H->nlev; ++l) {
         if (!H->pool[l]->fold) continue;
@@ -1847,7 +1847,7 @@ int build_tail(nodal_ctx *h, SHierarchy *H, const unsigned long long *hs) {
         TailDesc d;
         memset(&d, 0, sizeof d);
         d.nlev = last - t + 1;
-        d.nu = getenv("NODAL_SA_TAIL_NU") ? atoi(getenv("NODAL_SA_TAIL_NU")) : 3;
+        d.nu = knob::SA_TAIL_NU.now();
         if (d.nu < 1) d.nu = 1;
         int off = 0;
         for (int k = 0; k < d.nlev; ++k) {  // image part
@@ -1887,7 +1887,7 @@ int build_tail(nodal_ctx *h, SHierarchy *H, const unsigned long long *hs) {
         d.inv = H->dense_coarsest ? H->coarse_inv.as<double>() : nullptr;
         d.skip = d.nlev > 1 ? d.lv[0].o_dinv : 0;
         d.lds_bytes = off - d.skip;
-        if (getenv("NODAL_TAIL_PROBE")) {
+        if (knob::TAIL_PROBE.now()) {
             NODAL_HIP_TRY(h, H->tail_stamps.reserve(64 * sizeof(long long)));
             d.stamps = H->tail_stamps.as<long long>();
         }
@@ -1936,8 +1936,8 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
     const int64_t n0 = L0->n;
     {
         const unsigned gr = grid_for(n0);
-        static const double spread = getenv("NODAL_SA_SPREAD") ? atof(getenv("NODAL_SA_SPREAD")) : 16.0;
-        static const double share = getenv("NODAL_SA_SHARE") ? atof(getenv("NODAL_SA_SHARE")) : 0.9;
+        static const double spread = knob::SA_SPREAD.now();
+        static const double share = knob::SA_SHARE.now();
         row_stats<<<gr, TB, 0, st>>>(n0, indptr0, indices0, data0, share, spread, general, dstats, H->bstat.as<uint32_t>());
         reduce_bstat<<<1, 1024, 0, st>>>((int)gr, H->bstat.as<uint32_t>(), dstats, ST_MAXLEN, ST_GRADED);
     }
@@ -1954,7 +1954,7 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
                                               L->pval.as<double>(), L->pvalf.as<float>(), omega_p(l));
         // (R's values on the hierarchy's other stream while this one computes A P: see build_level)
         const bool forked = H->aux != nullptr && nodal_extra_streams_ok(h) &&
-                            !(getenv("NODAL_SA_FORK") && atoi(getenv("NODAL_SA_FORK")) == 0);
+                            knob::SA_FORK.now();
         hipStream_t rst = st;
         if (forked) {
             NODAL_HIP_TRY(h, hipEventRecord(H->ev_fork, st));
@@ -2028,14 +2028,14 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
                                const double *data0, bool general, bool check_floating, bool *accepted, int32_t *floating) {
     *accepted = false;
     *floating = 0;
-    static const bool enabled = !(getenv("NODAL_SAGG") && atoi(getenv("NODAL_SAGG")) == 0);
-    static const bool trace = getenv("NODAL_TRACE") != nullptr;
+    static const bool enabled = knob::SAGG.now();
+    static const bool trace = knob::TRACE.now();
     if (!enabled) return NODAL_OK;
     SHierarchy *H = hierarchy_of(h);
     H->ready = false;
     hipStream_t st = h->stream;
     if (n0 >= (1ll << 30)) return NODAL_OK;
-    static const bool reuse = !(getenv("NODAL_SA_REUSE") && atoi(getenv("NODAL_SA_REUSE")) == 0);
+    static const bool reuse = knob::SA_REUSE.now();
     if (reuse && H->sym_valid && H->sym_epoch == h->struct_epoch && H->sym_n == n0 && H->sym_nnz == nnz0 &&
         H->sym_general == general && H->sym_check == check_floating) {
         // same pattern as the matrix the hierarchy's symbolic part was built for: values only
@@ -2072,8 +2072,8 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
         // 10) take this hierarchy at half the time of the contrast mode of amg.hip (5.4 vs 10.3 ms, 7.1 vs
         // 17.2 ms); from two decades on the contrast mode wins (three decades: 10.4 vs 16.8 ms, anisotropy
         // 1000: 17 vs 53 ms) -- hence 16, not amg.hip's own trigger of 8.
-        static const double spread = getenv("NODAL_SA_SPREAD") ? atof(getenv("NODAL_SA_SPREAD")) : 16.0;
-        static const double share = getenv("NODAL_SA_SHARE") ? atof(getenv("NODAL_SA_SHARE")) : 0.9;
+        static const double spread = knob::SA_SPREAD.now();
+        static const double share = knob::SA_SHARE.now();
         row_stats<<<gr, TB, 0, st>>>(n0, indptr0, indices0, data0, share, spread, general, dstats, H->bstat.as<uint32_t>());
         reduce_bstat<<<1, 1024, 0, st>>>((int)gr, H->bstat.as<uint32_t>(), dstats, ST_MAXLEN, ST_GRADED);
     }
@@ -2104,7 +2104,7 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
     // instead of 20 bytes of columns per row (W = 5); the same columns, hence the same sums, bit for bit.  Level 0 only
     // (the other levels are latency-bound), rows of fixed width or with their lengths (config 5's reduced system), and
     // only when every column is that close to its row.
-    static const bool d16_env = !(getenv("NODAL_SA_D16") && atoi(getenv("NODAL_SA_D16")) == 0);
+    static const bool d16_env = knob::SA_D16.now();
     L0->d16 = d16_env && hs[ST_FARCOL] == 0;
     if (L0->d16) NODAL_HIP_TRY(h, L0->adcol.reserve((size_t)L0->width * L0->ld * 2 + 64));
     csr_to_ell<<<grid_for(n0), TB, 0, st>>>(n0, L0->ld, indptr0, indices0, data0, L0->acol.as<int32_t>(),
@@ -2269,7 +2269,7 @@ int last_level(nodal_ctx *h, SHierarchy *H, int l, const double *b, double *out)
 // iterations' are not taken: they run high -- in between.  The schedule depends on `it` alone: the same launches every
 // time.  it < 0: an adaptive cycle that leaves no sample (every other caller).
 void kcycle_schedule(SHierarchy *H, int it) {
-    static const bool on = !(getenv("NODAL_SA_KFREEZE") && atoi(getenv("NODAL_SA_KFREEZE")) == 0);
+    static const bool on = knob::SA_KFREEZE.now();
     H->kfrozen = false;
     H->kslot = -1;
     if (!on || it < 0) return;
@@ -2482,7 +2482,7 @@ int sagg_spmv(nodal_ctx *h, const double *x, double *y, hipEvent_t start, hipEve
 // network is structurally singular (caller fills NaNs); -1 breakdown / no convergence (caller
 // falls back); SAGG_DECLINED (-3) the hierarchy does not take this matrix; > 0 a status.
 int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, int32_t *iters, double *resid) {
-    static const bool trace = getenv("NODAL_TRACE") != nullptr;
+    static const bool trace = knob::TRACE.now();
     const int64_t n = h->n;
     hipStream_t st = h->stream;
     SHierarchy *H = hierarchy_of(h);
@@ -2500,10 +2500,10 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
     }
     if (!H->ready || H->pool[0]->n != n) return SAGG_DECLINED;
     h->amg_levels = H->nlev;
-    static const int kc = getenv("NODAL_SA_KCYCLE") ? atoi(getenv("NODAL_SA_KCYCLE")) : 1;
+    static const int kc = knob::SA_KCYCLE.now();
     H->kcycle = kc != 0;
-    H->klevels = getenv("NODAL_SA_KLEVELS") ? atoi(getenv("NODAL_SA_KLEVELS")) : 1;
-    if (const char *e = getenv("NODAL_SA_NU")) {  // e.g. "212": sweeps at level 0, level 1, deeper levels
+    H->klevels = knob::SA_KLEVELS.now();
+    if (const char *e = knob::SA_NU.now()) {  // e.g. "212": sweeps at level 0, level 1, deeper levels
         for (int k = 0; k < 3 && e[k] >= '1' && e[k] <= '3'; ++k) H->nu[k] = e[k] - '0';
     }
 
@@ -2532,7 +2532,7 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
     f_init<<<sb.g0, TB, 0, st>>>(b, x, sb.r, sb.Ap, dinv0, sb.x0, sb.part_rr, n);
     NODAL_HIP_TRY(h, hipGetLastError());
 
-    const int64_t maxit = getenv("NODAL_FCG_MAXIT") ? atoll(getenv("NODAL_FCG_MAXIT")) : 2000;
+    const int64_t maxit = knob::FCG_MAXIT.now().value_or(2000);
     hipEvent_t e0 = h->ev[2], e1 = h->ev[3];
     h->kern_ms = 0;
     h->kern_launches = 0;
@@ -2548,15 +2548,15 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
         if (batch > 32) batch = 32;
     }
     int status = 0;  // 0 running, 1 converged, 2 breakdown, 3 maxit
-    const bool poll_partials = !(getenv("NODAL_FCG_HOST_SUM") && atoi(getenv("NODAL_FCG_HOST_SUM")) == 0);
+    const bool poll_partials = knob::FCG_HOST_SUM.now();
     double rr_prev = -1.0;
     int64_t it_prev = 0;
     int polls = 0;
-    static const bool fuse_dir_env = !(getenv("NODAL_SA_FUSE_DIR") && atoi(getenv("NODAL_SA_FUSE_DIR")) == 0);
+    static const bool fuse_dir_env = knob::SA_FUSE_DIR.now();
     const bool fuse_dir = fuse_dir_env && LPR_RAGGED == 1;
     // one outer iteration (the kernels take its parity only: see f_direction)
     // K-cycle coefficients calibrated, then frozen (kcycle_schedule; not under a replayed graph, whose launches are fixed)
-    static const bool graphs_env = getenv("NODAL_SA_GRAPH") && atoi(getenv("NODAL_SA_GRAPH")) != 0;
+    static const bool graphs_env = knob::SA_GRAPH.now();
     auto iteration = [&](int it, bool timed) -> int {
         kcycle_schedule(H, graphs_env ? -1 : it);
         struct KReset {  // (whatever way this iteration is left: the hierarchy's other users run adaptive cycles)
@@ -2604,7 +2604,7 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
     // (NODAL_SA_GRAPH=1; off by default: measured without gain -- 7.53 instead of 7.28 ms for one stream,
     // and the same 180 / 211 / 182 / 210 circuits/s with 2 / 3 / 4 / 6 solves in flight: what bounds several
     // streams is not the host's launch rate)
-    static const bool graphs = getenv("NODAL_SA_GRAPH") && atoi(getenv("NODAL_SA_GRAPH")) != 0;
+    static const bool graphs = knob::SA_GRAPH.now();
     if (graphs && (H->refreshed || !do_setup)) {
         uint64_t key = 1469598103934665603ull;
         auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
@@ -2706,7 +2706,7 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
             const int64_t it_ref = rr_prev > 0.0 ? it_prev : 0;
             if (hs[F_RR] > 0.0 && hs[F_RR] < rr_ref && enqueued > it_ref) {
                 const double rate = log(hs[F_RR] / rr_ref) / (double)(enqueued - it_ref);  // < 0
-                static const double look = getenv("NODAL_FCG_LOOK") ? atof(getenv("NODAL_FCG_LOOK")) : 0.75;
+                static const double look = knob::FCG_LOOK.now();
                 next = (int)floor(look * log(target / hs[F_RR]) / rate);
             }
             if (next > enqueued) next = (int)enqueued;  // (at most doubling: early rates are pessimistic)

@@ -663,7 +663,7 @@ int m_layout(nodal_ctx *h, SHierarchy *H, MBufs &M) {
 // converged, 2 breakdown, 3 the cap.  `what` names the block in the trace.
 int m_iterate(nodal_ctx *h, SHierarchy *H, const MBufs &M, int32_t count, bool functional, const char *what,
               int32_t *iters, int *status_out) {
-    const bool trace = getenv("NODAL_TRACE") != nullptr;  // (per call: tests switch it on for one sweep)
+    const bool trace = knob::TRACE.now();  // (per call: tests switch it on for one sweep)
     const int64_t n = h->n;
     hipStream_t st = h->stream;
     const SLevel *L0 = H->pool[0];
@@ -689,7 +689,7 @@ int m_iterate(nodal_ctx *h, SHierarchy *H, const MBufs &M, int32_t count, bool f
     // a second, not 2000 iterations, before the sweep goes on pair by pair)
     int64_t maxit = 2000;
     if (H->last_iters > 0) maxit = std::max<int64_t>(64, 4 * (int64_t)H->last_iters);
-    if (getenv("NODAL_FCG_MAXIT")) maxit = atoll(getenv("NODAL_FCG_MAXIT"));
+    maxit = knob::FCG_MAXIT.now().value_or(maxit);
     double hs[MK * MSC];
     int64_t enqueued = 0;
     // A block iteration takes ~1.2 ms at 1e6 rows and a look at the scalars ~50 us: the host looks after one
@@ -751,7 +751,7 @@ int sagg_fcg_solve_pairs_block(nodal_ctx *h, int32_t count, const int32_t *ia_ho
     const SLevel *L0 = H->pool[0];
     const double *dinv0 = L0->dinv.as<double>();
     const double tol = 1e-13;
-    const bool functional = !(getenv("NODAL_PAIRS_FUNCTIONAL") && atoi(getenv("NODAL_PAIRS_FUNCTIONAL")) == 0);
+    const bool functional = knob::PAIRS_FUNCTIONAL.now();
     double *part_rr = M.part + (int64_t)2 * MPARTS * MK;
     m_set_scalars<<<1, 64, 0, st>>>(M.sc, tol * tol);
     m_init<<<M.g0, TB, 0, st>>>(n, M.ia, M.ib, M.x, M.r, M.Ap, dinv0, M.x0, part_rr, MPARTS);

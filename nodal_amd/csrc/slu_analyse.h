@@ -13,6 +13,8 @@
 #include <thread>
 #include <vector>
 
+#include "knobs.h"
+
 namespace slu {
 
 constexpr int LEAF = 32;          // pieces of at most this many vertices are not dissected further
@@ -22,7 +24,7 @@ constexpr int LEAF = 32;          // pieces of at most this many vertices are no
 template <class F>
 inline void parallel_chunks(int64_t n, int64_t min_chunk, F f) {
     unsigned hw = std::thread::hardware_concurrency();
-    if (const char *e = getenv("NODAL_HOST_THREADS")) hw = (unsigned)std::max(1, atoi(e));
+    if (const auto t = knob::HOST_THREADS.now()) hw = (unsigned)std::max(1, *t);
     const int64_t T = std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 1), 16, n / std::max<int64_t>(1, min_chunk)}));
     if (T <= 1) {
         f((int64_t)0, n);
@@ -95,7 +97,7 @@ inline bool row_matching(int64_t n, const int32_t *indptr, const int32_t *indice
             }
         }
         if (!found) return false;
-        if (getenv("SLU_DEBUG")) fprintf(stderr, "  augment row %d: %zu rows visited, ends in column %d\n", (int)r0, queue.size(), end_col);
+        if (knob::SLU_DEBUG.now()) fprintf(stderr, "  augment row %d: %zu rows visited, ends in column %d\n", (int)r0, queue.size(), end_col);
         // flip the path: column end_col <- via row, that row's old column <- its via row, ...
         int32_t j = end_col;
         while (true) {
@@ -171,10 +173,10 @@ inline void symmetrised_graph(int64_t n, const int32_t *indptr, const int32_t *i
 // every piece owns its vertices' `tag` and `lvl` words, and a piece's level marks start above every mark its
 // ancestors left on those vertices.
 inline int64_t nd_par_min() {  // pieces below this are not worth a thread (NODAL_ND_PAR: the tests thread small graphs)
-    static const int64_t m = getenv("NODAL_ND_PAR") ? atoll(getenv("NODAL_ND_PAR")) : 20000;
+    static const int64_t m = knob::ND_PAR.now();
     return m;
 }
-inline int nd_par_depth() { static const int d = getenv("NODAL_ND_DEPTH") ? atoi(getenv("NODAL_ND_DEPTH")) : 4; return d; }
+inline int nd_par_depth() { static const int d = knob::ND_DEPTH.now(); return d; }
 //
 // In place: a piece is a span [lo, hi) of ONE permutation array, its breadth-first queue the same span of ONE
 // scratch array; the split writes A, B, S back into the span in that order, so the finished array IS the
@@ -503,7 +505,7 @@ inline bool analyse(int64_t n, const int32_t *indptr, const int32_t *indices, co
         std::vector<int32_t> peeled;
         std::vector<uint8_t> gone;
         Graph core;
-        static const bool peel = !(getenv("NODAL_DIRECT_PEEL") && atoi(getenv("NODAL_DIRECT_PEEL")) == 0);
+        static const bool peel = knob::DIRECT_PEEL.now();
         if (peel) peel_low_degree(n, g, peeled, gone, core);
         if (peeled.empty()) {
             nested_dissection(n, g, order, S.sn_start);

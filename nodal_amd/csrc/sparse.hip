@@ -508,7 +508,7 @@ int amg_fcg_solve_ex(nodal_ctx *h, const double *b, bool do_setup, int32_t *info
     const unsigned gv = grid_rows(n, 1), gs = stream::grid_for_rows(n, MAX_PARTIALS);
     NODAL_HIP_TRY(h, hipMemsetAsync(sc, 0, F_COUNT * 8, st));
     NODAL_HIP_TRY(h, hipMemsetAsync(part_zap, 0, MAX_PARTIALS * 8, st));
-    static const bool trace = getenv("NODAL_TRACE") != nullptr;
+    static const bool trace = knob::TRACE.now();
     const auto t_begin = std::chrono::steady_clock::now();
     if (do_setup) {
         NODAL_TRY(amg_setup(h, sc + F_FLAG));
@@ -542,7 +542,7 @@ int amg_fcg_solve_ex(nodal_ctx *h, const double *b, bool do_setup, int32_t *info
 
     const double tol = 1e-13;
     // chain-like networks need ~1000 iterations; beyond the cap: Jacobi-CG fallback
-    const int64_t maxit = getenv("NODAL_FCG_MAXIT") ? atoll(getenv("NODAL_FCG_MAXIT")) : 5000;
+    const int64_t maxit = knob::FCG_MAXIT.now().value_or(5000);
     int check = 6;  // iterations before the next look at the residual (first: six; then from the rate seen so far)
     double rr_prev = -1.0;
     int64_t it_prev = 0;
@@ -876,8 +876,8 @@ int sparse_solve_pairs(nodal_ctx *h, int32_t npairs, const int32_t *ia, const in
     // analysis is at hand, eight times as many when it has to be made; always where the multigrid has no business
     // (indefinite: a non-positive resistance).  NODAL_PAIRS_DIRECT=1 forces it, =0 forbids it.
     {
-        const int forced = getenv("NODAL_PAIRS_DIRECT") ? atoi(getenv("NODAL_PAIRS_DIRECT")) : -1;  // (per call: tests switch it)
-        const int64_t min_pairs = getenv("NODAL_PAIRS_DIRECT_MIN") ? atoll(getenv("NODAL_PAIRS_DIRECT_MIN")) : 256;
+        const int forced = knob::PAIRS_DIRECT.now();  // (per call: tests switch it)
+        const int64_t min_pairs = knob::PAIRS_DIRECT_MIN.now();
         const bool worth = npairs >= (slu_analysis_kept(h) ? min_pairs : 8 * min_pairs);
         if (forced != 0 && (forced == 1 || indefinite || worth)) {
             bool taken = false;
@@ -885,7 +885,7 @@ int sparse_solve_pairs(nodal_ctx *h, int32_t npairs, const int32_t *ia, const in
             if (taken) return NODAL_OK;
         }
     }
-    if (indefinite || (getenv("NODAL_PAIRS_DIRECT") && atoi(getenv("NODAL_PAIRS_DIRECT")) == 1)) {  // (pair by pair on the factors)
+    if (indefinite || knob::PAIRS_DIRECT.now() == 1) {  // (pair by pair on the factors)
         int32_t inf = 0;
         NODAL_TRY(slu_factor(h, &inf));
         if (inf > 0) {
@@ -896,7 +896,7 @@ int sparse_solve_pairs(nodal_ctx *h, int32_t npairs, const int32_t *ia, const in
     }
     // (latched off by the first block that breaks down or does not converge: the pairs of that block and every later
     // one go singly -- a second failing block would cost its iteration cap again for nothing)
-    bool block_allowed = !(getenv("NODAL_PAIRS_BLOCK") && atoi(getenv("NODAL_PAIRS_BLOCK")) == 0);
+    bool block_allowed = knob::PAIRS_BLOCK.now();
     for (int32_t q = 0; q < npairs;) {
         // Once the first pair has set the smoothed-aggregation hierarchy up, the others go sixteen at a time
         // through the block iteration (sagg_multi.h: one launch sequence and one pass over every matrix per block
@@ -1139,7 +1139,7 @@ int multi_rhs_solve(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, doubl
     bool all_direct = slu_perturbed(s) > 0;
     // the backward-error bar of the refinement (sparse_general.hip); NODAL_MULTI_BAR (per call: tests switch it) below 0
     // sends every column through the redo
-    const double bar = getenv("NODAL_MULTI_BAR") ? atof(getenv("NODAL_MULTI_BAR")) : 1e-14;
+    const double bar = knob::MULTI_BAR.now();
     for (int32_t m0 = 0; m0 < count; m0 += SLU_MULTI) {
         const int32_t cnt = count - m0 < SLU_MULTI ? count - m0 : SLU_MULTI;
         bool redo = all_direct;
@@ -1335,12 +1335,12 @@ int sparse_solve(nodal_ctx *h, int32_t method, int32_t *info, int32_t *iters, do
     // below this a direct solve costs less than an elimination round.  (1024 until round 4: true of a round that is
     // being BUILT, 0.2-0.4 ms; repeated on kept lists it is two 5-us launches, and the dense solve of the 780 unknowns
     // seven rounds leave of a 1e5-section ladder was 0.75 of that solve's 0.91 ms.  NODAL_LOWDEG_MIN to compare.)
-    static const int64_t lowdeg_min = getenv("NODAL_LOWDEG_MIN") ? atoll(getenv("NODAL_LOWDEG_MIN")) : 32;
+    static const int64_t lowdeg_min = knob::LOWDEG_MIN.now();
     bool auto_passive = false;
     // NODAL_SPARSE_FORCE_DIRECT=1 (testing): every automatic sparse solve through the direct route
-    if (method == NODAL_SPARSE_AUTO && getenv("NODAL_SPARSE_FORCE_DIRECT")) method = NODAL_SPARSE_DIRECT;
+    if (method == NODAL_SPARSE_AUTO && knob::SPARSE_FORCE_DIRECT.now()) method = NODAL_SPARSE_DIRECT;
     // NODAL_SPARSE_CHILD_DIRECT=1 (testing): the same for matrix-only contexts alone (what lowdeg.hip's rounds leave)
-    if (method == NODAL_SPARSE_AUTO && h->csr_only && getenv("NODAL_SPARSE_CHILD_DIRECT")) method = NODAL_SPARSE_DIRECT;
+    if (method == NODAL_SPARSE_AUTO && h->csr_only && knob::SPARSE_CHILD_DIRECT.now()) method = NODAL_SPARSE_DIRECT;
     if (method == NODAL_SPARSE_AUTO) {
         // passive network (B == 0, every R > 0, no transconductance): symmetric M-matrix.
         // Up to densify_max unknowns the direct dense solve is faster than the multigrid
@@ -1396,7 +1396,7 @@ int sparse_solve(nodal_ctx *h, int32_t method, int32_t *info, int32_t *iters, do
     } else if (method == NODAL_SPARSE_DIRECT) {
         NODAL_TRY(sparse_direct_solve(h, h->rhs.as<double>(), h->x.as<double>(), info, iters, resid));
     } else if (method == NODAL_SPARSE_LU) {
-        static const bool trace = getenv("NODAL_TRACE") != nullptr;
+        static const bool trace = knob::TRACE.now();
         // (a matrix-only context -- what an elimination round of lowdeg.hip left -- has no component table
         // for the presolve and the verdicts below: the direct route takes it)
         const int s = h->csr_only ? NODAL_E_UNSUPPORTED : sparse_general_solve(h, info, iters, resid);

@@ -1605,7 +1605,7 @@ void slu_destroy(nodal_ctx *h) {
 // *info = 1: structurally singular (no perfect matching).
 int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_threshold) {
     *info = 0;
-    const bool trace = getenv("NODAL_TRACE") != nullptr;
+    const bool trace = knob::TRACE.now();
     const int64_t n = h->n, nnz = h->nnz;
     hipStream_t st = h->stream;
     if (n >= (1ll << 31) - 2 || nnz >= (1ll << 31) - 2) return nodal_fail(h, NODAL_E_UNSUPPORTED, "direct solve: more than 2^31 rows or entries");
@@ -1656,7 +1656,7 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
             for (int32_t l = 0; l < S->nlev; ++l) {
                 auto b = sym.lvl_sn.begin() + sym.lvl_ptr[(size_t)l], e = sym.lvl_sn.begin() + sym.lvl_ptr[(size_t)l + 1];
                 // (NODAL_DIRECT_BIG_DIM: the front width above which a front is stepped with its level's wide ones)
-                static const int big_dim = getenv("NODAL_DIRECT_BIG_DIM") ? atoi(getenv("NODAL_DIRECT_BIG_DIM")) : BIG_DIM;
+                static const int big_dim = knob::DIRECT_BIG_DIM.now().value_or(BIG_DIM);
                 auto mid = std::stable_partition(b, e, [&](int32_t t) { return S->h_dim[(size_t)t] <= big_dim; });
                 S->lvl_small[(size_t)l] = (int32_t)(mid - b);
                 auto amid = std::stable_partition(mid, e, [&](int32_t t) { return S->h_dim[(size_t)t] <= APPLY_BIG; });
@@ -1693,7 +1693,7 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         double cap = 0.5 * (double)free_b;
-        if (const char *e = getenv("NODAL_DIRECT_MAX_GB")) cap = atof(e) * 1e9;
+        if (const auto gb = knob::DIRECT_MAX_GB.now()) cap = *gb * 1e9;
         if ((double)S->front_doubles * 8.0 > cap) {
             char msg[256];
             snprintf(msg, sizeof msg, "direct solve: the fronts of this matrix need %.1f GB (limit %.1f GB)",
@@ -1762,13 +1762,13 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
     // 270 / 260 ms for 16 / 32 / 48 / 64 -- the single-workgroup panel kernel is what a wider panel makes longer);
     // NODAL_DIRECT_NB = 16 / 32 / 48 / 64
     int panel_nb = 16;
-    if (const char *e = getenv("NODAL_DIRECT_NB")) {
+    if (const char *e = knob::DIRECT_NB.now()) {
         const int v = atoi(e);
         if (v == 16 || v == 32 || v == 48 || v == 64) panel_nb = v;
     }
     // (NODAL_DIRECT_LANES=1: the wide fronts of a level one after the other on the main stream)
-    int want_lanes = 4;  // (config 5's factorisation with 1 / 2 / 3 / 4 / 6 lanes: 93 / 73 / 67 / 65 / 83 ms)
-    if (const char *e = getenv("NODAL_DIRECT_LANES")) want_lanes = atoi(e) < 1 ? 1 : (atoi(e) > SluState::LANES ? SluState::LANES : atoi(e));
+    // (the default of 4: config 5's factorisation with 1 / 2 / 3 / 4 / 6 lanes: 93 / 73 / 67 / 65 / 83 ms)
+    const int want_lanes = std::min((int)SluState::LANES, std::max(1, knob::DIRECT_LANES.now()));
     S->lane_st[0] = st;
     if (S->lanes < want_lanes && nodal_extra_streams_ok(h)) {  // streams and events of the lanes: once per context (a failure leaves fewer lanes)
         if (!S->lane_ev[0] && hipEventCreateWithFlags(&S->lane_ev[0], hipEventDisableTiming) != hipSuccess) S->lane_ev[0] = nullptr;
@@ -1785,11 +1785,11 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
         (void)hipGetLastError();
     }
     const int max_lanes = !nodal_extra_streams_ok(h) ? 1 : (S->lanes < want_lanes ? S->lanes : want_lanes);  // (see api.hip)
-    const bool fronts_in_lds = !(getenv("NODAL_DIRECT_FRONT_LDS") && atoi(getenv("NODAL_DIRECT_FRONT_LDS")) == 0);
-    const bool panel_regs = !(getenv("NODAL_DIRECT_PANEL_REGS") && atoi(getenv("NODAL_DIRECT_PANEL_REGS")) == 0);
-    const bool batched = !(getenv("NODAL_DIRECT_BATCHED") && atoi(getenv("NODAL_DIRECT_BATCHED")) == 0);
+    const bool fronts_in_lds = knob::DIRECT_FRONT_LDS.now();
+    const bool panel_regs = knob::DIRECT_PANEL_REGS.now();
+    const bool batched = knob::DIRECT_BATCHED.now();
     // NODAL_DIRECT_LEVELS=1: an event behind every level, and a table of times, flops and bytes per level on stderr
-    const bool level_table = getenv("NODAL_DIRECT_LEVELS") != nullptr;
+    const bool level_table = knob::DIRECT_LEVELS.now();
     std::vector<hipEvent_t> lev_ev;
     if (level_table) {
         lev_ev.resize((size_t)S->nlev + 1);
@@ -1820,9 +1820,9 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
             else if (fronts_in_lds && (size_t)S->lvl_maxdim[(size_t)l] * S->lvl_maxdim[(size_t)l] * 8 <= 56 * 1024) {
                 // (NODAL_DIRECT_LDS_BS: threads per front of the in-LDS kernel -- one wavefront per front makes its four
                 // barriers per column step next to free; round 5)
-                static const int lds_bs = getenv("NODAL_DIRECT_LDS_BS") ? atoi(getenv("NODAL_DIRECT_LDS_BS")) : 64;
+                static const int lds_bs = knob::DIRECT_LDS_BS.now();
                 const size_t lds = (size_t)S->lvl_maxdim[(size_t)l] * S->lvl_maxdim[(size_t)l] * 8;
-                const bool wave_fronts = !(getenv("NODAL_DIRECT_WAVE") && atoi(getenv("NODAL_DIRECT_WAVE")) == 0);
+                const bool wave_fronts = knob::DIRECT_WAVE.now();
                 if (lds_bs == 64 && wave_fronts && S->lvl_maxdim[(size_t)l] <= 64)
                     factor_fronts_wave<1><<<nsmall, 64, lds, st>>>(T, sns, S->fronts.as<double>(), S->lperm.as<int32_t>(), tiny, repl,
                                                                    S->stats.as<unsigned long long>());
@@ -1986,8 +1986,8 @@ int slu_apply_nr(nodal_ctx *h, SluState *S, const double *r, double *z) {
         S->vec_nr = NR;
     }
     permute_rhs<<<grid_for(n * NR), TB, 0, st>>>(n, NR, S->rowof.as<int32_t>(), S->rs.as<double>(), r, S->xb.as<double>());
-    static const bool stepped = !(getenv("NODAL_DIRECT_APPLY_STEPPED") && atoi(getenv("NODAL_DIRECT_APPLY_STEPPED")) == 0);
-    static const bool super_steps = !(getenv("NODAL_DIRECT_SUPER") && atoi(getenv("NODAL_DIRECT_SUPER")) == 0);
+    static const bool stepped = knob::DIRECT_APPLY_STEPPED.now();
+    static const bool super_steps = knob::DIRECT_SUPER.now();
     constexpr int RT = 256 / ColGroup<NR>::CG;  // rows per workgroup of the stepped kernels
     const double *Fd = S->fronts.as<double>();
     double *xbd = S->xb.as<double>(), *vd = S->vec.as<double>();
@@ -2110,7 +2110,7 @@ static int sparse_direct_solve_once(nodal_ctx *h, const double *b, double *x, in
     const int s2 = general_krylov_direct(h, h->work2.as<double>(), h->work3.as<double>(), &info2, &it2, &rs2);
     h->slu_strict = false;
     NODAL_TRY(s2);
-    if (getenv("NODAL_TRACE"))
+    if (knob::TRACE.now())
         fprintf(stderr, "[direct] %lld replaced pivots: a pseudo-random right-hand side %s\n", (long long)S->perturbed,
                 info2 > 0 ? "does not refine: singular" : "is solved too: regular");
     if (info2 > 0) *info = 1;
@@ -2132,7 +2132,7 @@ int sparse_direct_solve(nodal_ctx *h, const double *b, double *x, int32_t *info,
         NODAL_TRY(sparse_direct_solve_once(h, b, x, info, iters, resid, threshold));
         SluState *S = state_of(h);
         if (!S) return NODAL_OK;
-        const bool trace = getenv("NODAL_TRACE") != nullptr;
+        const bool trace = knob::TRACE.now();
         const bool doubtful = *info > 0 || S->perturbed > 0;
         if (doubtful && S->analysis_kept && !redone) {
             if (trace)

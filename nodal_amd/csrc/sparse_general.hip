@@ -617,7 +617,8 @@ int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_
     // where full orthogonalisation converges in 240.  So: the window only without branch rows, only in the
     // first cycle (a system that needs a restart is a hard one: all vectors from then on), and the true
     // residual at the end of every cycle decides.  NODAL_FGMRES_WINDOW=k forces k everywhere (experiments).
-    static const int window_env = getenv("NODAL_FGMRES_WINDOW") ? std::max(2, atoi(getenv("NODAL_FGMRES_WINDOW"))) : 0;
+    static const std::optional<int> window_set = knob::FGMRES_WINDOW.now();
+    static const int window_env = window_set ? std::max(2, *window_set) : 0;
     const int window_first = window_env ? window_env : ((n == K && !direct) ? 8 : RESTART + 1);
     double rnorm = bnorm;
     int total = 0;
@@ -709,7 +710,7 @@ int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_
             at_prev = enq;
         }
         total += (int)hst[G_COUNT - G_INV_H];
-        if (getenv("NODAL_TRACE")) {
+        if (knob::TRACE.now()) {
             double lg[RESTART];
             NODAL_TRY(nodal_read_words(h, lg, gst + G_LOG, sizeof lg));
             fprintf(stderr, "[fgmres] |w after Gram-Schmidt|^2 / |w|^2 per column:");
@@ -752,7 +753,7 @@ int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_
         // round 4: singular only on positive evidence.)
         double scaled = 1.0;
         NODAL_TRY(csr_scaled_residual(h, x, b, &scaled));
-        if (getenv("NODAL_TRACE"))
+        if (knob::TRACE.now())
             fprintf(stderr, "[direct] refinement stopped at backward error %.3e with no replaced pivot: %s\n", scaled,
                     scaled <= 1e-9 ? "accepted (ill-conditioned, not singular)" : "not a solution");
         if (scaled <= 1e-9) return NODAL_OK;
@@ -761,7 +762,7 @@ int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_
         // Refinement on the LU factors did not reach the residual bar: the statically perturbed pivots stood in
         // for zero ones -- G is singular to working precision.  The reference's spsolve meets the zero pivot
         // and returns NaNs + MatrixRankWarning (reference nodal/nodal.py:323-336); so does the caller.
-        if (getenv("NODAL_TRACE"))
+        if (knob::TRACE.now())
             fprintf(stderr, "[direct] refinement stalled at relative residual %.3e after %d iterations: singular\n",
                     rnorm / bnorm, total);
         *info = 1;

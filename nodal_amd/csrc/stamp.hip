@@ -425,7 +425,7 @@ int stamp_numeric(nodal_ctx *h, int32_t member, int64_t *bad_component) {
     NODAL_HIP_TRY(h, hipGetLastError());
     if (h->nnz > 0) {
         // NODAL_FOLD_STREAM=0: one lane per entry walking its own run (rounds 1-3; kept as the cross-check)
-        const bool stream_fold = !(getenv("NODAL_FOLD_STREAM") && atoi(getenv("NODAL_FOLD_STREAM")) == 0);
+        const bool stream_fold = knob::FOLD_STREAM.now();
         if (stream_fold) {
             const int64_t blocks = (h->nnz + FOLD_EPB - 1) / FOLD_EPB;
             fold_matrix_stream<<<(unsigned)(blocks > 65536 ? 65536 : blocks), TB, 0, st>>>(

@@ -45,12 +45,7 @@ double now_s() {
 }
 
 double wait_bound_s() {
-    static const double bound = [] {
-        const char *e = getenv("NODAL_WAIT_TIMEOUT_S");
-        if (!e) return 60.0;
-        const double v = atof(e);
-        return v > 0.0 ? v : 0.0;
-    }();
+    static const double bound = std::max(0.0, knob::WAIT_TIMEOUT_S.now());
     return bound;
 }
 
