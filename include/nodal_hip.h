@@ -318,6 +318,20 @@ int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const i
  * the handle as it found it: solution, right-hand side, table, hierarchies and factorisations; scratch of its own. */
 int nodal_debug_residual(nodal_handle h, int32_t transposed, int32_t cols, int32_t layout, const double *x,
                          const double *b, double *scaled_out, double *norms_out);
+/* The sparse direct route's factors and substitutions with nothing behind them: slu_factor (which keeps a still-valid
+ * analysis as usual), then exactly ONE application of the factors to the caller's r -- no Krylov step, no refinement,
+ * no redo of a column by another path.  What every public entry point returns has been through one of those.
+ * transposed == 0: the handle's G.  != 0: the G^T that the last nodal_sensitivities left on a handle whose network is
+ *   not passive (the rule and the error of nodal_debug_residual).
+ * cols == 1: slu_apply on r[n], z[n].  cols == 16: slu_apply_multi on sixteen columns interleaved by row, element (i, y)
+ *   of r and of z at [i * 16 + y].  Anything else is NODAL_E_INVALID.
+ * perturbed_out: the pivots the factorisation replaced (static-pivot rule); info_out: slu_factor's verdict (> 0:
+ *   structurally singular; z is not written then).
+ * Needs nodal_assemble_numeric (NODAL_E_INVALID otherwise).  Host vectors, scratch of its own; leaves solution,
+ * right-hand side, table and hierarchies as it found them.  The direct route's cached analysis and factors of the
+ * matrix in question ARE created or refreshed (as any direct solve would leave them). */
+int nodal_debug_direct_apply(nodal_handle h, int32_t transposed, int32_t cols, const double *r, double *z,
+                             int64_t *perturbed_out, int32_t *info_out);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,7 @@ SIGNATURES = {
     "nodal_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
     "nodal_debug_sources_rhs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i64p, _f64p, _f64p]),
     "nodal_debug_residual": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p]),
+    "nodal_debug_direct_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p, _i64p, _i32p]),
 }
 
 _lib = None
@@ -399,6 +400,18 @@ class Handle:
                                                   _ptr(b, C.c_double) if b is not None else None,
                                                   _ptr(scaled, C.c_double), _ptr(norms, C.c_double)))
         return (float(scaled[0]), norms) if cols == 0 else (scaled, norms.reshape(16, 4))
+
+    def debug_direct_apply(self, r, cols=1, transposed=False):
+        """z = (the sparse direct route's factors)^-1 r and nothing else: one factorisation, one substitution, no
+        refinement (testing hook).  cols 1: r [n]; cols 16: r [n, 16], sixteen columns interleaved by row.
+        transposed: the G^T the last sensitivities() call left on the handle.  Returns (z, replaced pivots, info)."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.shape == ((self.n,) if cols == 1 else (self.n, cols)), (r.shape, cols)
+        z = np.full(r.shape, np.nan, dtype=np.float64)
+        perturbed, info = C.c_int64(-1), C.c_int32(-1)
+        self._check(self.lib.nodal_debug_direct_apply(self._h, int(bool(transposed)), cols, _ptr(r, C.c_double),
+                                                      _ptr(z, C.c_double), C.byref(perturbed), C.byref(info)))
+        return z, perturbed.value, info.value
 
     def download_x(self):
         x = host_empty(self.n, np.float64)

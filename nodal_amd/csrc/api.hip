@@ -265,7 +265,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none,
                       &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk, &h->br_out, &h->br_part, &h->br_tot,
                       &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->pt_buf,
-                      &h->dbg_resid};
+                      &h->dbg_resid, &h->dbg_apply};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     h->evpool.clear();
@@ -880,6 +880,14 @@ int nodal_debug_residual(nodal_handle h, int32_t transposed, int32_t cols, int32
     DeviceGuard g(h);
     if (h->hung) return NODAL_E_HIP;
     return sparse_debug_residual(h, transposed != 0, cols, layout, x, b, scaled_out, norms_out);
+}
+
+int nodal_debug_direct_apply(nodal_handle h, int32_t transposed, int32_t cols, const double *r, double *z,
+                             int64_t *perturbed_out, int32_t *info_out) {
+    if (!h) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return sparse_debug_direct_apply(h, transposed != 0, cols, r, z, perturbed_out, info_out);
 }
 
 int nodal_residual(nodal_handle h, double *scaled_residual) {

@@ -204,6 +204,7 @@ struct nodal_ctx {
     // aside during the call borrows sn_x)
     DevBuf pt_buf;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
+    DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
     // matrix-only context (no component table) that inherits the grounded-node flags
     nodal_ctx *lowdeg = nullptr;
@@ -582,6 +583,9 @@ int csr_scaled_residual(nodal_ctx *h, const double *x, const double *b, double *
 // testing hook (nodal_debug_residual): the single-vector judge (cols 0) or the block judge (cols 1 .. 16) on host vectors
 int sparse_debug_residual(nodal_ctx *h, bool transposed, int32_t cols, int32_t layout, const double *x, const double *b,
                           double *scaled_out, double *norms_out);
+// testing hook (nodal_debug_direct_apply): slu_factor + one slu_apply (cols 1) or slu_apply_multi (cols 16) on host vectors
+int sparse_debug_direct_apply(nodal_ctx *h, bool transposed, int32_t cols, const double *r, double *z,
+                              int64_t *perturbed_out, int32_t *info_out);
 // dense_child: solve the reduced system by the dense block elimination (only if it is passive)
 void presolve_plan_ahead(nodal_ctx *h);  // host-only; called by stamp_numeric while its kernels run
 void presolve_free_plan(nodal_ctx *h);

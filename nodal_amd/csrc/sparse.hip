@@ -1528,3 +1528,40 @@ int sparse_debug_residual(nodal_ctx *h, bool transposed, int32_t cols, int32_t l
     }
     return NODAL_OK;
 }
+
+// testing hook (nodal_debug_direct_apply): slu_factor, then ONE slu_apply (cols 1) or slu_apply_multi (cols 16) on the
+// caller's own vector -- no Krylov step, no refinement, no redo.  Scratch of its own (dbg_apply); x, rhs, the solution
+// flag, the table and the hierarchies stay as they are; the direct route's analysis and factors of the context are
+// created or refreshed.
+int sparse_debug_direct_apply(nodal_ctx *h, bool transposed, int32_t cols, const double *r, double *z,
+                              int64_t *perturbed_out, int32_t *info_out) {
+    if (h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "debug_direct_apply: a matrix-only context");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "assemble_numeric not called");
+    if ((cols != 1 && cols != SLU_MULTI) || !r || !z || !perturbed_out || !info_out)
+        return nodal_fail(h, NODAL_E_INVALID, "debug_direct_apply: bad cols or vectors");
+    nodal_ctx *m = h;
+    if (transposed) {
+        m = h->adjoint;
+        if (!m || !m->have_numeric || h->adjoint_epoch != h->struct_epoch || m->n != h->n || m->nnz != h->nnz)
+            return nodal_fail(h, NODAL_E_INVALID, "debug_direct_apply: the handle holds no transposed matrix");
+    }
+    *perturbed_out = 0;
+    *info_out = 0;
+    const int64_t n = h->n;
+    if (n == 0) return NODAL_OK;
+    NODAL_TRY(nodal_lift_error(h, m, slu_factor(m, info_out)));
+    *perturbed_out = slu_perturbed(m);
+    if (*info_out > 0) return NODAL_OK;  // (structurally singular: there are no factors to apply, z is not written)
+    const size_t count = (size_t)n * cols, vec = align_up(count * 8);
+    NODAL_HIP_TRY(h, h->dbg_apply.reserve(2 * vec + 256));
+    double *dr = h->dbg_apply.as<double>(), *dz = dr + vec / 8;
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dr, r, count * 8, hipMemcpyHostToDevice, h->stream));
+    const int st = nodal_lift_error(h, m, cols == 1 ? slu_apply(m, dr, dz) : slu_apply_multi(m, dr, dz));
+    if (st != NODAL_OK) {
+        (void)nodal_wait_stream(h, h->stream, NODAL_SITE);  // the copy above reads the caller's array: not past this return
+        return st;
+    }
+    NODAL_HIP_TRY(h, hipMemcpyAsync(z, dz, count * 8, hipMemcpyDeviceToHost, h->stream));
+    NODAL_WAIT_STREAM(h, h->stream);
+    return NODAL_OK;
+}

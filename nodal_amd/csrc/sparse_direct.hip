@@ -941,19 +941,25 @@ __global__ __launch_bounds__(TB) void unpermute_solution(int64_t n, int nr, cons
     }
 }
 
-// ---- apply: blocked substitution with the diagonal blocks' inverses, any number of right-hand sides -----------
-// After the factorisation every DB x DB diagonal block of a front's pivot part is replaced IN PLACE by its inverses
-// (invert_diag_blocks: the unit lower triangle by inv(L_bb) without its diagonal, the upper triangle by inv(U_bb)), so
-// a substitution is a sequence of small dense products instead of s dependent column steps with a barrier each (round
-// 4: a front of 1000 pivot columns took a millisecond per sweep, the apply of config 5's factors 8 ms):
+// ---- apply: blocked substitution, any number of right-hand sides ---------------------------------------------------
+// After the factorisation the unit lower triangle of every DB x DB diagonal block of a front's pivot part is replaced
+// IN PLACE by inv(L_bb) without its diagonal (invert_diag_blocks), so a forward substitution is a sequence of small dense
+// products instead of s dependent column steps with a barrier each (round 4: a front of 1000 pivot columns took a
+// millisecond per sweep, the apply of config 5's factors 8 ms):
 //   forward   y_b = inv(L_bb) v_b;  v_below -= L[below, b] y_b         block by block down the pivot columns
-//   backward  v_S -= U12 x_B;  x_b = inv(U_bb) v_b;  v_above -= U[above, b] x_b    block by block upwards
+//   backward  v_S -= U12 x_B;  U_bb x_b = v_b;  v_above -= U[above, b] x_b    block by block upwards
+// The upper triangle keeps U_bb itself and the backward sweep SUBSTITUTES through it (upper_block_solve: the 32 rows of a
+// column in 32 lanes of one wavefront, a lane shuffle per step, no barrier).  Up to round 5 it held inv(U_bb) and the
+// sweep multiplied by it: a product with an explicit inverse has a backward error of cond(U_bb) u, not u, and on
+// resistances spread over six decades that put the unrefined solve 10 .. 80 times above SuperLU's residual
+// (tests/test_gpu_direct_unrefined.py; the host emulation with inverted U blocks shows the same loss, with inverted L
+// blocks alone none: the interchanges keep |l| <= 4, so inv(L_bb) is harmless).
 // NR right-hand sides travel together, interleaved by row (element (i, c) at [i * NR + c]): every entry of L and U is
 // read once for all of them.  One workgroup per front; the rows of a product over the threads (coalesced reads of a
 // column of the front), CW columns of the right-hand sides per thread.
 constexpr int DB = 32;
 
-// one wavefront per (front, diagonal block): lanes 0..31 the columns of inv(U_bb), lanes 32..63 those of inv(L_bb)
+// one wavefront per (front, diagonal block): lanes 32..63 the columns of inv(L_bb)
 __global__ __launch_bounds__(64) void invert_diag_blocks(Tree T, int64_t nblocks, const int32_t *__restrict__ blk_sn,
                                                          const int32_t *__restrict__ blk_b0, double *__restrict__ fronts) {
     __shared__ double D[DB][DB + 1];
@@ -975,14 +981,7 @@ __global__ __launch_bounds__(64) void invert_diag_blocks(Tree T, int64_t nblocks
     const int j = lane & 31;
     if (j < nb) {
         double *x = X[lane];
-        if (lane < 32) {  // U x = e_j
-            x[j] = 1.0 / D[j][j];
-            for (int i = j - 1; i >= 0; --i) {
-                double acc = 0.0;
-                for (int k = i + 1; k <= j; ++k) acc = fma(D[i][k], x[k], acc);
-                x[i] = -acc / D[i][i];
-            }
-        } else {          // L x = e_j, unit diagonal
+        if (lane >= 32) {  // L x = e_j, unit diagonal
             x[j] = 1.0;
             for (int i = j + 1; i < nb; ++i) {
                 double acc = 0.0;
@@ -994,7 +993,7 @@ __global__ __launch_bounds__(64) void invert_diag_blocks(Tree T, int64_t nblocks
     __syncthreads();
     for (int e = lane; e < nb * nb; e += 64) {
         const int r = e % nb, c = e / nb;
-        F[r + (int64_t)c * dim] = r <= c ? X[c][r] : X[32 + c][r];
+        if (r > c) F[r + (int64_t)c * dim] = X[32 + c][r];
     }
 }
 
@@ -1014,8 +1013,8 @@ template <int NR> struct ColGroup { static constexpr int CW = NR >= 4 ? 4 : NR; 
 // branch around the load and waits for every load before its LDS store (the level steps spent six dependent round
 // trips, 5 of their 8.6 us, filling Li and Vb).  Here every load is unconditional (the address of an element that is
 // not wanted is clamped to one that is), all of a thread's loads are requested first, and the stores follow.
-// inverse factor of the diagonal block at (b0, b0): LOWER: its strictly lower part (unit diagonal implied), else its
-// upper triangle with the diagonal; zeros elsewhere and beyond nb
+// the diagonal block at (b0, b0) as the factors hold it: LOWER: the strictly lower part of inv(L_bb) (unit diagonal
+// implied), else the upper triangle of U_bb with the diagonal; zeros elsewhere and beyond nb
 template <int BS, bool LOWER>
 __device__ __forceinline__ void stage_diag_block(const double *__restrict__ F, int64_t dim, int b0, int nb,
                                                  double (*D)[DB + 1], int tid) {
@@ -1101,6 +1100,35 @@ __device__ __forceinline__ void chunk_update(const double *__restrict__ Frow, in
     for (int k = 0; k < DB; ++k)
 #pragma unroll
         for (int jj = 0; jj < CW; ++jj) acc[jj] = fma(-l[k], Y[k][col0 + jj], acc[jj]);
+}
+
+// U_bb x_b = v_b for the NR columns of a diagonal block by substitution, last row first.  Ub: the block's upper triangle
+// with its diagonal (zeros elsewhere and beyond nb), V: the block's rows of v (zero rows beyond nb), both in LDS.
+// Lane r of a group of DB = 32 lanes holds row r of one column: step k scales row k by its pivot's reciprocal (as the
+// factorisation scaled L), hands it to the group by a shuffle and the rows above subtract their share.  A group is half
+// a wavefront, so the DB dependent steps need no barrier.  The result goes to Y (LDS, rows beyond nb: zeros) and, where
+// `out` is given, to out[r * NR + c] for r < nb.  Called by every thread of the workgroup, between its barriers.
+template <int BS, int NR>
+__device__ __forceinline__ void upper_block_solve(const double (*Ub)[DB + 1], int nb, const double (*V)[NR], double (*Y)[NR],
+                                                  double *__restrict__ out, int tid) {
+    static_assert(BS % 64 == 0 && DB == 32, "a group of DB lanes is half a wavefront");
+    for (int e0 = 0; e0 < DB * NR; e0 += BS) {
+        if (e0 + (tid & ~63) >= DB * NR) continue;  // (a whole wavefront without an element; the others stay in step)
+        const int e = e0 + tid;
+        const bool on = e < DB * NR;  // (DB * NR is a multiple of DB: a group is on or off as a whole)
+        const int r = e % DB, c = on ? e / DB : 0;
+        double val = on ? V[r][c] : 0.0;
+        const double rd = on && r < nb ? 1.0 / Ub[r][r] : 0.0;
+        for (int k = nb - 1; k >= 0; --k) {
+            if (r == k) val *= rd;
+            const double xk = __shfl(val, k, DB);
+            if (r < k) val = fma(-Ub[r][k], xk, val);
+        }
+        if (on) {
+            Y[r][c] = val;
+            if (out && r < nb) out[(int64_t)r * NR + c] = val;
+        }
+    }
 }
 
 // forward substitution of one level: v = [b'_S ; 0] + children's contributions, rows permuted like the
@@ -1199,7 +1227,7 @@ __global__ __launch_bounds__(BS) void backward_level(Tree T, const int32_t *__re
     constexpr int CW = ColGroup<NR>::CW, CG = ColGroup<NR>::CG;
     __shared__ double Y[DB][NR];
     __shared__ double Vb[DB][NR];
-    __shared__ double Ui[DB][DB + 1];
+    __shared__ double Ub[DB][DB + 1];
     const int32_t t = sns[blockIdx.x];
     const int start = T.sn_start[t];
     const int s = T.sn_start[t + 1] - start;
@@ -1230,18 +1258,11 @@ __global__ __launch_bounds__(BS) void backward_level(Tree T, const int32_t *__re
         const int nb = s - b0 < DB ? s - b0 : DB;
         for (int e = tid; e < DB * DB; e += BS) {
             const int r = e % DB, k = e / DB;
-            Ui[r][k] = (k < nb && r <= k) ? F[(b0 + r) + (int64_t)(b0 + k) * dim] : 0.0;
+            Ub[r][k] = (k < nb && r <= k) ? F[(b0 + r) + (int64_t)(b0 + k) * dim] : 0.0;
         }
         for (int e = tid; e < DB * NR; e += BS) Vb[e / NR][e % NR] = e < nb * NR ? v[(int64_t)b0 * NR + e] : 0.0;
         __syncthreads();
-        for (int e = tid; e < DB * NR; e += BS) {  // x_b = inv(U_bb) v_b
-            const int r = e / NR, c = e % NR;
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < DB; ++k) acc = fma(Ui[r][k], Vb[k][c], acc);
-            Y[r][c] = acc;
-            if (r < nb) v[(int64_t)(b0 + r) * NR + c] = acc;
-        }
+        upper_block_solve<BS, NR>(Ub, nb, Vb, Y, v + (int64_t)b0 * NR, tid);  // U_bb x_b = v_b
         __syncthreads();
         for (int e = tid; e < b0 * CG; e += BS) {  // the rows above
             const int i = e % b0, g = e / b0;
@@ -1388,7 +1409,7 @@ __global__ __launch_bounds__(256) void level_bwd_step(Tree T, const int32_t *__r
     constexpr int CW = ColGroup<NR>::CW, CG = ColGroup<NR>::CG, RT = 256 / CG;
     __shared__ double Y[DB][NR];
     __shared__ double Vb[DB][NR];
-    __shared__ double Ui[DB][DB + 1];
+    __shared__ double Ub[DB][DB + 1];
     const int32_t t = sns[blockIdx.y];
     const int start = T.sn_start[t];
     const int s = T.sn_start[t + 1] - start;
@@ -1400,17 +1421,11 @@ __global__ __launch_bounds__(256) void level_bwd_step(Tree T, const int32_t *__r
     const double *F = fronts + T.front_off[t];
     double *v = vec + T.vec_off[t] * NR;
     const int tid = threadIdx.x;
-    stage_diag_block<256, false>(F, dim, b0, nb, Ui, tid);
+    stage_diag_block<256, false>(F, dim, b0, nb, Ub, tid);
     stage_rows<256, NR, DB>(v + (int64_t)b0 * NR, nb * NR, Vb, tid);
     __syncthreads();
-    for (int e = tid; e < DB * NR; e += 256) {
-        const int r = e / NR, c = e % NR;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < DB; ++k) acc = fma(Ui[r][k], Vb[k][c], acc);
-        Y[r][c] = acc;
-        if (blockIdx.x == 0 && r < nb) xb[(int64_t)(start + b0 + r) * NR + c] = acc;  // (the solution itself)
-    }
+    // U_bb x_b = v_b (the first workgroup of the step writes the solution itself)
+    upper_block_solve<256, NR>(Ub, nb, Vb, Y, blockIdx.x == 0 ? xb + (int64_t)(start + b0) * NR : nullptr, tid);
     __syncthreads();
     const int i = r0 + tid % RT, g = tid / RT;
     if (i < b0) {
@@ -1500,7 +1515,7 @@ __global__ __launch_bounds__(256) void level_bwd_super(Tree T, const int32_t *__
     constexpr int CW = ColGroup<NR>::CW, CG = ColGroup<NR>::CG, RT = 256 / CG;
     __shared__ double Y[SUPER_W][NR];
     __shared__ double Vs[SUPER_W][NR];
-    __shared__ double Ui[DB][DB + 1];
+    __shared__ double Ub[DB][DB + 1];
     const int32_t t = sns[blockIdx.y];
     const int start = T.sn_start[t];
     const int s = T.sn_start[t + 1] - start;
@@ -1517,16 +1532,11 @@ __global__ __launch_bounds__(256) void level_bwd_super(Tree T, const int32_t *__
     for (int k = (sw - 1) / DB; k >= 0; --k) {
         const int b0 = B0 + k * DB, nb = s - b0 < DB ? s - b0 : DB;
         __syncthreads();
-        stage_diag_block<256, false>(F, dim, b0, nb, Ui, tid);
+        stage_diag_block<256, false>(F, dim, b0, nb, Ub, tid);
         __syncthreads();
-        for (int e = tid; e < DB * NR; e += 256) {  // x_b = inv(U_bb) v_b
-            const int r = e / NR, c = e % NR;
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < DB; ++q) acc = fma(Ui[r][q], Vs[k * DB + q][c], acc);
-            Y[k * DB + r][c] = acc;
-            if (blockIdx.x == 0 && r < nb) xb[(int64_t)(start + b0 + r) * NR + c] = acc;  // (the solution itself)
-        }
+        // U_bb x_b = v_b (the first workgroup of the step writes the solution itself)
+        upper_block_solve<256, NR>(Ub, nb, (const double (*)[NR]) & Vs[k * DB], (double (*)[NR]) & Y[k * DB],
+                                   blockIdx.x == 0 ? xb + (int64_t)(start + b0) * NR : nullptr, tid);
         __syncthreads();
         const int ra = k * DB;  // the rows of the super block above this sub-block
         for (int e = tid; e < ra * CG; e += 256) {
@@ -1954,7 +1964,8 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
                 tot_fl * 1e-9, tot_ms > 0 ? tot_fl / tot_ms * 1e-9 : 0.0, tot_by * 1e-6, tot_ms > 0 ? tot_by / tot_ms * 1e-6 : 0.0);
         for (auto &e : lev_ev) (void)hipEventDestroy(e);
     }
-    // the substitutions multiply by the diagonal blocks' inverses (see forward_level): in place, once per factorisation
+    // the forward substitutions multiply by the inverses of the diagonal blocks' lower triangles (see forward_level): in
+    // place, once per factorisation
     if (S->nblocks > 0) {
         invert_diag_blocks<<<(unsigned)S->nblocks, 64, 0, st>>>(T, S->nblocks, S->blk_sn.as<int32_t>(), S->blk_b0.as<int32_t>(),
                                                                 S->fronts.as<double>());

@@ -2,6 +2,7 @@
 factorisation over supernodes) without a GPU: tools/slu_host_check.cpp runs the numeric phase on the host with
 the very structures the HIP kernels use and must reproduce SuperLU's answer (reference nodal/nodal.py:325)."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -12,6 +13,7 @@ from nodal_amd import generators as gen
 from nodal_amd.lowering import lower
 import nodal_amd as n
 from oracle import nodal_oracle as oracle
+from tests.direct_cases import CASES, HOST_GUARD_CASES, width_class
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -63,6 +65,22 @@ def test_host_emulation_of_the_direct_route_matches_superlu(checker, tmp_path, n
     x = np.fromfile(xo, dtype=np.float64)
     ref, _ = oracle.solve(G, A, True)
     assert np.abs(x - ref).max() <= 1e-9 * np.abs(ref).max()
+
+
+@pytest.mark.parametrize("name", HOST_GUARD_CASES)
+def test_tables_of_the_unrefined_device_checks_stay_in_their_kernel_regime(checker, tmp_path, name):
+    """tests/test_gpu_direct_unrefined.py judges the device's unrefined factors on tables chosen for the width of their
+    largest front (which kernels factor and substitute) and for being free of replaced pivots (a replaced pivot alone
+    costs the unrefined answer eight digits).  Both rest on the ordering of csrc/slu_analyse.h: the emulation, which
+    runs that very code, must still report the width class the table is listed under and no replaced pivot."""
+    build, want = CASES[name]
+    r, *_ = _run(checker, tmp_path, build())
+    assert r.returncode == 0, r.stderr[-1500:]
+    front = re.search(r"largest front (\d+)", r.stderr)
+    perturbed = re.search(r"(\d+) perturbed pivots", r.stderr)
+    assert front and perturbed, r.stderr[-600:]
+    assert int(perturbed.group(1)) == 0, r.stderr[-400:]
+    assert width_class(int(front.group(1))) == want, (name, front.group(1))
 
 
 def test_structurally_singular_matrix_is_reported(checker, tmp_path):
