@@ -206,6 +206,34 @@ int nodal_sensitivities(nodal_handle h, int32_t dense, int32_t count, const int3
                         const int32_t *q2, double *sens_out, double *value_out, double *adjoint_out,
                         double *resid_out, int32_t *info_out);
 
+/* ---- loss gradients (replaces one nodal_sensitivities output per unknown a loss touches: one adjoint solve and one
+ *      [ncomp] row each; the reference has no derivative of its own) ----
+ * For a scalar loss L = sum_m L_m(x_m) over `count` members that share G -- the members of a source sweep, or the single
+ * solve -- and the caller's cotangent[m] = dL/dx_m (dense, [n]): lambda_m solves G^T lambda_m = cotangent[m], and
+ *   grad_out[i]            = sum_m s_i(lambda_m, x_m) for EVERY table row i, s_i the per-row formula of
+ *                            nodal_sensitivities without an explicit term (csrc/sensitivity.hip states them; R with the
+ *                            cross terms of resistors that drive CCVS / CCCS rows, A, E, VCVS, CCVS, CCCS).  A loss that
+ *                            reads the values themselves adds that part on its own.
+ *   grad_sources_out[m][j] = s_{rows[j]}(lambda_m, .): member m's derivative with respect to its OWN value of swept row
+ *                            rows[j] (the formula of an A or E row reads neither x nor the value).
+ * grad_out at a swept row holds the same uniform formula, i.e. the sum over the members of grad_sources_out[.][j]: the
+ * derivative with respect to a value all members would share.  G and the value column are those of the last
+ * nodal_assemble_numeric.  x [count][n]: the members' solutions (what nodal_solve_sources returned); NULL: the solution of
+ * the single solve on the handle (count must be 1 and nsrc 0).  rows [nsrc]: the swept table rows (type A or E, each named
+ * once); may be NULL with nsrc 0.  grad_sources_out, adjoint_out [count][n] (the lambdas) and resid_out [count] may be
+ * NULL; resid_out and info_out [count] mean what they mean in nodal_sensitivities.  A singular G with dense != 0 returns
+ * NODAL_E_SINGULAR; otherwise NaN goes into everything a singular member feeds, and -- the sum is not defined with a
+ * member missing -- into the whole of grad_out.  count == 0 writes zeros to grad_out.
+ * NODAL_E_INVALID: no nodal_assemble_numeric before the call; x == NULL without a solution on the handle, with
+ * count != 1 or with nsrc != 0; a swept row out of range, not an A / E row, or repeated.
+ * One adjoint solve per member, sixteen members to a block, one pass over the component table per block; the sum over
+ * the members is formed on the device in member order and nothing of size [count][ncomp] exists anywhere.  Leaves the
+ * handle as it found it: the solution if any, the table, G, A.  No floating-point atomics: a repeated call gives the
+ * same bits. */
+int nodal_gradient(nodal_handle h, int32_t dense, int32_t count, const double *x, const double *cotangent, int32_t nsrc,
+                   const int64_t *rows, double *grad_out, double *grad_sources_out, double *adjoint_out,
+                   double *resid_out, int32_t *info_out);
+
 /* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
  *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
  *      reference has no equivalent of an active network and no coupling between ports) ----

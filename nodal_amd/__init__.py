@@ -11,4 +11,5 @@ from .netlist import (  # noqa: F401
 from .circuit import Circuit, Solution  # noqa: E402,F401
 from .branches import Branches, Envelope  # noqa: E402,F401
 from .sensitivity import Sensitivities, resolve_outputs  # noqa: E402,F401
+from .gradient import Gradient, check_gradient_arguments  # noqa: E402,F401
 from .ports import PortEquivalent, resolve_ports  # noqa: E402,F401

@@ -53,6 +53,8 @@ SIGNATURES = {
                                                _i32p, _f64p, _i32p, _f64p, _i32p, _f64p, _i32p, _f64p]),
     "nodal_sensitivities": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p,
                                       _i32p]),
+    "nodal_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p, C.c_int32, _i64p, _f64p, _f64p, _f64p,
+                                 _f64p, _i32p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
@@ -352,6 +354,31 @@ class Handle:
             _ptr(sens, C.c_double), _ptr(y, C.c_double), _ptr(lam, C.c_double) if adjoints else None,
             _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
         return sens, y, lam, resid, info
+
+    def gradient(self, cotangents, dense, rows=None, solutions=None, adjoints=False):
+        """The gradient of a scalar loss with respect to every component value (nodal_gradient): cotangents [M, n] =
+        dL/dx_m, solutions [M, n] the members' solutions (None: the single solve's solution on the device, M == 1 and
+        no swept rows), rows the swept table rows of the sweep the members come from.  Returns (values [ncomp], source
+        values [M, len(rows)], adjoints [M, n] or None, scaled residual [M], info [M]); NodalHipError(E_INVALID) as
+        the header lists, with dense a singular G raises NodalHipError(E_SINGULAR)."""
+        cot = np.ascontiguousarray(cotangents, dtype=np.float64)
+        assert cot.ndim == 2 and cot.shape[1] == self.n
+        count = cot.shape[0]
+        rows = np.ascontiguousarray(rows if rows is not None else [], dtype=np.int64)
+        x = None
+        if solutions is not None:
+            x = np.ascontiguousarray(solutions, dtype=np.float64)
+            assert x.shape == cot.shape
+        grad = np.zeros(self._ncomp, dtype=np.float64)
+        gsrc = np.zeros((count, len(rows)), dtype=np.float64)
+        lam = host_empty(count * self.n, np.float64).reshape(count, self.n) if adjoints else None
+        resid = np.zeros(count, dtype=np.float64)
+        info = np.zeros(count, dtype=np.int32)
+        self._check(self.lib.nodal_gradient(
+            self._h, int(dense), count, _ptr(x, C.c_double) if x is not None else None, _ptr(cot, C.c_double),
+            len(rows), _ptr(rows, C.c_int64) if len(rows) else None, _ptr(grad, C.c_double), _ptr(gsrc, C.c_double),
+            _ptr(lam, C.c_double) if adjoints else None, _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
+        return grad, gsrc, lam, resid, info
 
     def port_matrix(self, ia, ib, dense, voc=True):
         """The open-circuit impedance matrix seen from the ports (ia[q], ib[q]) (node indices, -1 ground;

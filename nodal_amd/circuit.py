@@ -300,6 +300,80 @@ class Circuit:
             warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
         return Sensitivities(self.netlist, outputs, values, y, info, resid, adjoints=lam, table=self.table)
 
+    def gradient(self, cotangents, sources=None, solutions=None, adjoints=False):
+        """The gradient of a scalar loss L of the solution with respect to the value of every component, by the
+        adjoint method on the device (nodal_gradient): one solve with G^T per member, sixteen members to a block,
+        and the per-row formulas summed over the members on the device -- one number per component comes down.
+
+        Single solve: `cotangents` [K+B] = dL/dx for the last solve()'s solution; ValueError when there is none on
+        the device, as branches() (or pass `solutions` [K+B], a solution kept from an earlier solve()).  Sweep, L = sum_m L_m(x_m): `sources` as passed to solve_sources, `solutions` the
+        SourceSweep.result [M, K+B] and `cotangents` [M, K+B] = dL_m/dx_m; shapes that do not fit raise ValueError.
+        Returns a Gradient (gradient.py): `values` [ncomp] in the order of `netlist.component_keys` -- the part of
+        dL/dvalue that goes through the solution; a loss that reads the values themselves adds its own partial
+        derivative -- `source_values` (name -> [M], member m's derivative with respect to its own swept value),
+        `info`, `scaled_residual`, and with adjoints=True `adjoints` [M, K+B].  Singular networks behave as in
+        sensitivities(): the dense path raises LinAlgError / UnconnectedCircuitError, the sparse path returns NaN
+        with info > 0 and warns once.  The circuit itself -- its solution if any, table, G, A -- is left as it was."""
+        from .gradient import Gradient, check_gradient_arguments
+        h = self._handle
+        cot, rows, x, columns = check_gradient_arguments(self.netlist, h.n, cotangents, sources, solutions)
+        try:
+            values, gsrc, lam, resid, info = h.gradient(cot, dense=not self.sparse, rows=rows, solutions=x,
+                                                        adjoints=adjoints)
+        except _ffi.NodalHipError as exc:
+            if exc.status == _ffi.E_INVALID and "no solution" in str(exc):
+                raise ValueError("no solution: call solve() first") from None
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            if not is_connected(self.netlist):
+                logging.error("Model error: unconnected circuit")
+                raise UnconnectedCircuitError
+            logging.error("Model error: matrix is singular")
+            raise np.linalg.LinAlgError("Singular matrix")
+        if (info > 0).any():
+            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        by_name = {name: gsrc[:, cols].sum(axis=1) for name, cols in columns.items()}
+        return Gradient(self.netlist, values, by_name, info, resid, adjoints=lam, table=self.table)
+
+    # -- new component values on the same topology ---------------------------------
+    @property
+    def values(self):
+        """The value column in force, float64 [ncomp] in the order of `netlist.component_keys`: the lowered
+        netlist's, or what the last set_values() put in its place."""
+        return self.table.value
+
+    def set_values(self, values):
+        """Replace the value of every component and assemble G, A anew on the device, without parsing or lowering
+        the netlist again (nodal_upload_values + nodal_assemble_numeric): the other half of an optimisation loop.
+
+        `values` is float64 [ncomp] in the order of `netlist.component_keys`, in the units the table carries (what
+        `Circuit.values` returns).  Errors are those of building the circuit: ValueError for a null resistance,
+        AssertionError for a stamp collision, ZeroDivisionError for a resistor of value 0 that drives a CCVS /
+        CCCS; after any of them the circuit keeps its previous values and stays usable.  The solution on the
+        device and the cached G / A exports are dropped; `table`, and with it branches(), sensitivities(),
+        gradient() and the sweeps, read the new values.  The Netlist itself is NOT touched: its components keep
+        the values they were read with."""
+        table = self.table
+        new = np.array(values, dtype=np.float64)
+        if new.shape != (table.ncomp,):
+            raise ValueError(f"values must have shape ({table.ncomp},), not {new.shape}")
+        if table.B > 0:
+            drv = np.asarray(table.drv)
+            driven = (drv >= 0) & ((np.asarray(table.c) >= 0) | (np.asarray(table.d) >= 0))
+            if driven.any() and (new[drv[driven]] == 0).any():
+                raise ZeroDivisionError("float division by zero")  # (as lowering.py, as the reference)
+        h = self._handle
+        h.upload_values(new[None, :])
+        status, bad = h.assemble_numeric(0)
+        if status != _ffi.OK:
+            h.upload_values(np.asarray(table.value, dtype=np.float64)[None, :])
+            h.assemble_numeric(0)
+            if status == _ffi.E_ZERO_RESISTANCE:
+                raise ValueError("Model error: resistors can't have null resistance")
+            raise AssertionError  # the reference's bare `assert G[i, j] == 0`
+        self._G = self._A = None
+        self.table = table.with_values(new)
+
     def thevenin(self, ports, sources=True):
         """The multiport Thevenin equivalent of the circuit seen from `ports`: a sequence of
         (node_plus, node_minus) labels or of single labels (that node against ground;

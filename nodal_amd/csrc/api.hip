@@ -265,6 +265,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->ps_hits, &h->ps_stage, &h->grounded, &h->ld_newidx, &h->ld_work, &h->batch_scale, &h->rhs_none,
                       &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk, &h->br_out, &h->br_part, &h->br_tot,
                       &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->pt_buf,
+                      &h->gr_cot, &h->gr_x, &h->gr_spec, &h->gr_acc,
                       &h->dbg_resid, &h->dbg_apply};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
@@ -850,6 +851,22 @@ int nodal_sensitivities(nodal_handle h, int32_t dense, int32_t count, const int3
     if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
     if (count == 0) return NODAL_OK;
     return sens_run(h, dense != 0, count, kind, p, q2, sens_out, value_out, adjoint_out, resid_out, info_out);
+}
+
+int nodal_gradient(nodal_handle h, int32_t dense, int32_t count, const double *x, const double *cotangent, int32_t nsrc,
+                   const int64_t *rows, double *grad_out, double *grad_sources_out, double *adjoint_out,
+                   double *resid_out, int32_t *info_out) {
+    if (!h || count < 0 || nsrc < 0 || (nsrc > 0 && !rows) || (count > 0 && (!cotangent || !info_out))) return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "gradient: no component table on the handle");
+    if (h->ncomp > 0 && !grad_out) return nodal_fail(h, NODAL_E_INVALID, "gradient: no array for the result");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "gradient: assemble_numeric not called");
+    if (!x && !h->have_x) return nodal_fail(h, NODAL_E_INVALID, "gradient: no solution on the handle");
+    if (!x && (count != 1 || nsrc != 0))
+        return nodal_fail(h, NODAL_E_INVALID, "gradient: the solution on the handle serves one member without swept sources");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    return grad_run(h, dense != 0, count, x, cotangent, nsrc, rows, grad_out, grad_sources_out, adjoint_out, resid_out,
+                    info_out);
 }
 
 int nodal_port_matrix(nodal_handle h, int32_t dense, int32_t nports, const int32_t *ia, const int32_t *ib, double *z_out,

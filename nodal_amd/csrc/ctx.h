@@ -196,6 +196,10 @@ struct nodal_ctx {
     // (kept per table_epoch); the child context holding G^T as CSR (networks that are not passive), the parent
     // struct_epoch its pattern was transposed from and the permutation that gathers its values from `data`
     DevBuf sn_x, sn_spec, sn_out, sn_cross, sn_perm;
+    // loss gradients (gradient.hip): sixteen cotangent rows on their way up ([16][n]), sixteen solution rows and the
+    // same block interleaved ([16][n] + [n][16]), the swept rows with their slot map, the sum [ncomp] and one block of
+    // source derivatives [16][nsrc]
+    DevBuf gr_cot, gr_x, gr_spec, gr_acc;
     uint64_t sn_cross_epoch = 0;
     int64_t sn_ndrivers = 0, sn_ncross = 0;
     nodal_ctx *adjoint = nullptr;
@@ -469,6 +473,17 @@ int sens_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, const d
 int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const int32_t *p, const int32_t *q2,
              double *sens_out, double *value_out, double *adjoint_out, double *resid_out, int32_t *info_out);
 void sens_free_child(nodal_ctx *h);
+// what the gradient (gradient.hip) shares with the call above: the CCVS / CCCS rows grouped by their driving resistor
+// (sn_cross, sn_ndrivers, sn_ncross; kept per table_epoch) and the child context that holds G^T (h->adjoint)
+int sens_cross_list(nodal_ctx *h);
+int sens_transposed_child(nodal_ctx *h);
+
+// ---- loss gradients (gradient.hip; the transposed solves: multi_rhs_solve in sparse.hip) ----
+// one adjoint solve per member with the caller's dense cotangent, the per-row formulas summed over the members on the
+// device; the arguments are those of nodal_gradient
+int grad_run(nodal_ctx *h, bool dense, int32_t count, const double *x, const double *cotangent, int32_t nsrc,
+             const int64_t *rows, double *grad_out, double *grad_sources_out, double *adjoint_out, double *resid_out,
+             int32_t *info_out);
 
 // ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])

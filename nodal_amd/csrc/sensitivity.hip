@@ -374,6 +374,9 @@ int ensure_transposed_child(nodal_ctx *h) {
 
 }  // namespace
 
+int sens_cross_list(nodal_ctx *h) { return ensure_cross_list(h); }
+int sens_transposed_child(nodal_ctx *h) { return ensure_transposed_child(h); }
+
 void sens_free_child(nodal_ctx *h) {
     if (!h->adjoint) return;
     nodal_free_buffers(h->adjoint);

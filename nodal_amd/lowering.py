@@ -55,6 +55,14 @@ class ComponentTable:
     def n(self):
         return self.K + self.B
 
+    def with_values(self, value):
+        """A table that shares every column with this one but `value` (Circuit.set_values)."""
+        t = ComponentTable.__new__(ComponentTable)
+        for name in self.__slots__:
+            setattr(t, name, getattr(self, name))
+        t.value = value
+        return t
+
     def truncated(self, ncomp):
         """A copy holding only the first `ncomp` rows (used to let the device
         look for an earlier stamp collision before a host error is raised)."""
