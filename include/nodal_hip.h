@@ -234,6 +234,44 @@ int nodal_gradient(nodal_handle h, int32_t dense, int32_t count, const double *x
                    const int64_t *rows, double *grad_out, double *grad_sources_out, double *adjoint_out,
                    double *resid_out, int32_t *info_out);
 
+/* ---- transient analysis (replaces a host loop of rebuild and solve per time step: with the reference a new netlist
+ *      with companion rows, a new Circuit and a .solve() for every t_k, reference nodal/nodal.py:306-336) ----
+ * The handle holds the circuit WITH one extra R row per capacitor, cap_rows [ncap] (table rows of type R): the companion
+ * resistor of a capacitor C stepped with h, value h / C for backward Euler (method 0) and h / (2 C) for the trapezoidal
+ * rule (method 1); its leads and its conductance g = 1 / value are read from the table on the device.  G is that of the
+ * last nodal_assemble_numeric and does not change; step k = 1 .. steps solves G x_k = A_k + the history currents, J
+ * injected into lead a and drawn from lead b of every capacitor, with v = x(a) - x(b) of x_{k-1} (ground: +0.0):
+ *   method 0:  J_k = g v_{k-1}
+ *   method 1:  J_k = 2 g v_{k-1} - J_{k-1}, J_0 = g v_0 (zero capacitor currents at t_0: x0 must be a DC operating point)
+ * A_k is the right-hand side with the sources src_rows [nsrc] (type A or E, each named once) at src_values[k - 1][.]
+ * ([steps][nsrc]; the other sources keep their table values).  x0 [n]: the state at t_0; only its potentials are read.
+ *   wave_out [steps + 1][nprobe]  x_k(probe_a[p]) - x_k(probe_b[p]) (node indices, -1 ground), row 0 from x0; a probe
+ *                                 with probe_a == probe_b reads exactly +0.0
+ *   x_out [steps / keep_every][n] x_k of every keep_every-th step (keep_every 0: none)
+ *   pot_min, pot_max [K]          lowest / highest potential of each node over the solved steps, pot_min_step,
+ *                                 pot_max_step [K] a step that attains it (among exact ties the lowest); NaN and -1
+ *                                 when no step was solved
+ *   resid_out [steps]             the scaled residual of step k as nodal_solve_sources defines it
+ *   info_out [steps]              > 0: singular (the step and every later one: NaN wherever they land, status OK) --
+ *                                 except with dense != 0, where a singular G returns NODAL_E_SINGULAR
+ *   iters_out [steps]             iterations of the step's solve (multigrid), 1 (sparse LU + refinement), 0 (dense panel)
+ * Each output may be NULL.  Routes: n <= 64 the dense panel, factored anew every step; B == 0, all R > 0 and n > 4096 the
+ * multigrid iteration on the hierarchy of step 1 (a step it gives up on, and every later one: the sparse direct solve);
+ * everything else one sparse LU, per step two substitutions, one refinement step and the judgement (a step above the
+ * bar is redone by the sparse direct solve).  Hierarchy and factors are kept on the handle until the next
+ * nodal_assemble_numeric: a later call repeats neither.  nodal_last_timings afterwards: [0] host ms of the matrix work
+ * this call did once (the factorisation; on the multigrid route step 1 with its setup), exactly 0.0 when it was kept;
+ * [1] 0.0; [2] the whole call.
+ * NODAL_E_INVALID: steps < 0, a method other than 0 / 1, a cap_rows entry out of range or not of type R, the source-row
+ * errors of nodal_solve_sources, a probe node outside [-1, K), x0 == NULL, no nodal_assemble_numeric before the call.
+ * One host wait per kept block of solutions and what the solvers look at; waveforms, envelope and residuals come down
+ * once.  The handle's solution is dropped.  No floating-point atomics: a repeated call gives the same bits. */
+int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                    int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                    const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                    double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                    int32_t *info_out, int32_t *iters_out);
+
 /* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
  *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
  *      reference has no equivalent of an active network and no coupling between ports) ----

@@ -55,6 +55,9 @@ SIGNATURES = {
                                       _i32p]),
     "nodal_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p, C.c_int32, _i64p, _f64p, _f64p, _f64p,
                                  _f64p, _i32p]),
+    "nodal_transient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
+                                  _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p, _i32p,
+                                  _f64p, _i32p, _i32p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
@@ -397,6 +400,41 @@ class Handle:
             self._h, int(dense), count, _ptr(ia, C.c_int32), _ptr(ib, C.c_int32), _ptr(z, C.c_double),
             _ptr(v_oc, C.c_double) if voc else None, _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
         return z, v_oc, info, resid
+
+    def transient(self, cap_rows, rows, values, x0, ia, ib, dense, method=0, keep_every=0, envelope=False):
+        """Time stepping on a handle that holds the circuit with its companion resistors (nodal_transient): cap_rows
+        their table rows, values [steps, len(rows)] the swept sources step by step, x0 [n] the state at t_0, (ia, ib)
+        the probes' node indices.  Returns (waveforms [steps + 1, P], solutions [steps // keep_every, n] or None,
+        envelope dict or None, scaled residual [steps], info [steps], iterations [steps]); NodalHipError(E_INVALID) as
+        the header lists, with dense a singular G raises NodalHipError(E_SINGULAR)."""
+        cap_rows = np.ascontiguousarray(cap_rows, dtype=np.int64)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.ndim == 2 and values.shape[1] == len(rows)
+        steps = values.shape[0]
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        assert x0.shape == (self.n,)
+        ia, ib = (np.ascontiguousarray(v, dtype=np.int32) for v in (ia, ib))
+        assert ia.ndim == 1 and ib.shape == ia.shape
+        wave = np.zeros((steps + 1, len(ia)), dtype=np.float64)
+        kept = steps // keep_every if keep_every > 0 else 0
+        x = host_empty(kept * self.n, np.float64).reshape(kept, self.n) if keep_every > 0 else None
+        K = self._K
+        env = None
+        if envelope:
+            env = {"potential_min": np.empty(K), "potential_min_step": np.empty(K, dtype=np.int32),
+                   "potential_max": np.empty(K), "potential_max_step": np.empty(K, dtype=np.int32)}
+        resid = np.zeros(steps, dtype=np.float64)
+        info = np.zeros(steps, dtype=np.int32)
+        iters = np.zeros(steps, dtype=np.int32)
+        env_ptrs = [_ptr(env[key], C.c_int32 if key.endswith("step") else C.c_double) for key in env] if env else [None] * 4
+        self._check(self.lib.nodal_transient(
+            self._h, int(dense), steps, int(method), len(cap_rows), _ptr(cap_rows, C.c_int64) if len(cap_rows) else None,
+            len(rows), _ptr(rows, C.c_int64) if len(rows) else None, _ptr(values, C.c_double) if values.size else None,
+            _ptr(x0, C.c_double), len(ia), _ptr(ia, C.c_int32) if len(ia) else None, _ptr(ib, C.c_int32) if len(ib) else None,
+            _ptr(wave, C.c_double), int(keep_every), _ptr(x, C.c_double) if x is not None and kept else None, *env_ptrs,
+            _ptr(resid, C.c_double), _ptr(info, C.c_int32), _ptr(iters, C.c_int32)))
+        return wave, x, env, resid, info, iters
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

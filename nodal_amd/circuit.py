@@ -86,17 +86,20 @@ class Circuit:
         self._device = default_device() if device is None else device
         self._handle = None
         self._G = self._A = None
+        self._transient_child = None
         self.currents = self.build_model()
 
     @classmethod
-    def _clone_of(cls, other):
+    def _clone_of(cls, other, table=None):
         """A second device context holding the same assembled system as `other` (no second lowering of the
-        netlist): the lanes of a long equivalent-resistance sweep (equiv.py)."""
+        netlist): the lanes of a long equivalent-resistance sweep (equiv.py).  With `table`: that table in place of
+        `other`'s -- the circuit with its companion resistors (transient())."""
         self = cls.__new__(cls)
         self.netlist, self.sparse, self._device = other.netlist, other.sparse, other._device
         self._handle = None
         self._G = self._A = None
-        self.table = other.table
+        self._transient_child = None
+        self.table = other.table if table is None else table
         self.currents = other.currents
         self._assemble(self.table)
         return self
@@ -372,6 +375,7 @@ class Circuit:
                 raise ValueError("Model error: resistors can't have null resistance")
             raise AssertionError  # the reference's bare `assert G[i, j] == 0`
         self._G = self._A = None
+        self._transient_child = None  # (its matrix carried the old values)
         self.table = table.with_values(new)
 
     def thevenin(self, ports, sources=True):
@@ -407,6 +411,78 @@ class Circuit:
         if (info > 0).any():
             warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
         return PortEquivalent(self.netlist, ports, z, v_oc, info, resid)
+
+    def transient(self, capacitors, dt, steps, sources=None, probes=(), method="euler", initial=None, keep_every=0,
+                  envelope=False):
+        """Step the circuit with capacitors through `steps` time steps of length `dt` on the device (nodal_transient).
+
+        `capacitors` is a sequence of (name, farads, node_a, node_b) on nodes of the netlist; `sources` maps names of
+        A / E components to sequences of `steps` values, entry k-1 in force at t_k = k dt (solve_sources' argument; a
+        source that is not named keeps its netlist value); `probes` are (node_plus, node_minus) pairs or single labels
+        against ground (thevenin's ports).  initial=None starts from the last solve()'s solution -- the DC operating
+        point with the capacitors open; ValueError when there is none on the device, as branches() -- otherwise
+        `initial` is a float64 [K+B] vector of which the potentials are read.  method is "euler" or "trapezoidal"
+        (which needs the DC start: ValueError with `initial`).  keep_every=s > 0 brings the full solution of every
+        s-th step down, envelope=True adds per node the lowest and highest potential over the steps and a step that
+        attains each.  Returns a Transient (transient.py): `t`, `waveforms` [steps+1, P], `solutions`,
+        `solution_steps`, `envelope`, `info`, `scaled_residual`, `iterations`.
+
+        The matrix is that of the netlist with one companion resistor per capacitor, assembled on a second device
+        context that is kept on the circuit, keyed by the capacitors, dt and method, until set_values(): a second call
+        with the same key -- other sources, probes or steps -- repeats no analysis, hierarchy setup or factorisation.
+        Singular networks behave as in solve_sources(): the dense path raises LinAlgError / UnconnectedCircuitError,
+        the sparse path returns NaN steps with info > 0 and warns once.  The circuit itself -- its solution, table,
+        G, A -- is left as it was."""
+        from .ports import _as_pair, resolve_ports
+        from .sweep import resolve_sources
+        from .transient import (Transient, TransientEnvelope, check_transient_arguments, companion_table,
+                                resolve_capacitors)
+        h = self._handle
+        dt, steps, code, x0 = check_transient_arguments(dt, steps, method, initial, h.n)
+        keep_every = int(keep_every)
+        if keep_every < 0:
+            raise ValueError(f"keep_every must not be negative, not {keep_every}")
+        names, farads, ca, cb = resolve_capacitors(self.netlist, capacitors)
+        rows, values = resolve_sources(self.netlist, sources if sources is not None else {})
+        if len(rows) and values.shape[0] != steps:
+            raise ValueError(f"Source waveforms must have {steps} values (one per step), not {values.shape[0]}")
+        if not len(rows):
+            values = np.zeros((steps, 0), dtype=np.float64)
+        probes = [_as_pair(self.netlist, port) for port in probes]
+        pa, pb = resolve_ports(self.netlist, probes)
+        if x0 is None:
+            try:
+                x0 = h.download_x()
+            except _ffi.NodalHipError as exc:
+                if exc.status != _ffi.E_INVALID:
+                    raise
+                raise ValueError("no solution: call solve() first") from None
+        key = (farads.tobytes(), ca.tobytes(), cb.tobytes(), dt, code)
+        if self._transient_child is None or self._transient_child[0] != key:
+            self._transient_child = None  # (its device context goes back to the pool first)
+            table, cap_rows = companion_table(self.table, farads, ca, cb, dt, code)
+            self._transient_child = (key, Circuit._clone_of(self, table), cap_rows)
+        _, child, cap_rows = self._transient_child
+        ch = child._handle
+        try:
+            wave, x, env, resid, info, iters = ch.transient(cap_rows, rows, values, x0, pa, pb, dense=not self.sparse,
+                                                            method=code, keep_every=keep_every, envelope=envelope)
+        except _ffi.NodalHipError as exc:
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            if not is_connected(self.netlist):
+                logging.error("Model error: unconnected circuit")
+                raise UnconnectedCircuitError
+            logging.error("Model error: matrix is singular")
+            raise np.linalg.LinAlgError("Singular matrix")
+        if (info > 0).any():
+            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        if env is not None:
+            env = TransientEnvelope(env["potential_min"], env["potential_min_step"], env["potential_max"],
+                                    env["potential_max_step"])
+        kept = np.arange(1, steps // keep_every + 1, dtype=np.int64) * keep_every if keep_every > 0 else None
+        return Transient(dt * np.arange(steps + 1, dtype=np.float64), wave, probes, info, resid, iters, solutions=x,
+                         solution_steps=kept, envelope=env, timings=ch.timings())
 
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last

@@ -266,6 +266,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->sw_rows, &h->sw_slot, &h->sw_vals, &h->sw_blk, &h->br_out, &h->br_part, &h->br_tot,
                       &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->pt_buf,
                       &h->gr_cot, &h->gr_x, &h->gr_spec, &h->gr_acc,
+                      &h->tr_spec, &h->tr_none, &h->tr_node, &h->tr_ptr, &h->tr_con, &h->tr_vec, &h->tr_out, &h->tr_ring,
                       &h->dbg_resid, &h->dbg_apply};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
@@ -867,6 +868,36 @@ int nodal_gradient(nodal_handle h, int32_t dense, int32_t count, const double *x
     if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
     return grad_run(h, dense != 0, count, x, cotangent, nsrc, rows, grad_out, grad_sources_out, adjoint_out, resid_out,
                     info_out);
+}
+
+int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                    int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                    const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                    double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                    int32_t *info_out, int32_t *iters_out) {
+    if (!h || steps < 0 || (method != 0 && method != 1) || ncap < 0 || (ncap > 0 && !cap_rows) || nprobe < 0 ||
+        (nprobe > 0 && (!probe_a || !probe_b)) || keep_every < 0)
+        return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "transient: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "transient: assemble_numeric not called");
+    if (h->n > 0 && !x0) return nodal_fail(h, NODAL_E_INVALID, "transient: no initial state");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    NODAL_TRY(sweep_prepare(h, steps, nsrc, src_rows, src_values));
+    h->amg_levels = 0;
+    h->last_batch_block = false;
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_matrix = 0.0;
+    const int s = transient_run(h, dense != 0, steps, method, ncap, cap_rows, nsrc, x0, nprobe, probe_a, probe_b, wave_out,
+                                keep_every, x_out, pot_min, pot_min_step, pot_max, pot_max_step, resid_out, info_out,
+                                iters_out, &ms_matrix);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = ms_matrix;
+    h->ms[1] = 0.0;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
 }
 
 int nodal_port_matrix(nodal_handle h, int32_t dense, int32_t nports, const int32_t *ia, const int32_t *ib, double *z_out,

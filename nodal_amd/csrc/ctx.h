@@ -207,6 +207,14 @@ struct nodal_ctx {
     // multiport equivalents (ports.hip): the ports' nodes, Z [P][P] and V_oc [P] until they go down (the solution set
     // aside during the call borrows sn_x)
     DevBuf pt_buf;
+    // transient analysis (transient.hip): the capacitor rows, probes and per-capacitor history words; the node ->
+    // incident-capacitor lists (entries' nodes, their runs, capacitor << 3 | lead); the two solutions, the step's
+    // right-hand side, the refinement's vectors and the judge's norms; waveforms, envelope and residuals until they go
+    // down; the staging ring of kept solutions
+    DevBuf tr_spec, tr_none, tr_node, tr_ptr, tr_con, tr_vec, tr_out, tr_ring;
+    uint64_t numeric_epoch = 1;   // bumped by every numeric assembly (stamp_numeric): the identity of G's values
+    uint64_t tr_mg_epoch = 0;     // numeric_epoch the multigrid hierarchy a transient call set up belongs to (0: none)
+    uint64_t tr_lu_epoch = 0;     // ... and the sparse LU factors a transient call left
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
@@ -485,6 +493,15 @@ int grad_run(nodal_ctx *h, bool dense, int32_t count, const double *x, const dou
              const int64_t *rows, double *grad_out, double *grad_sources_out, double *adjoint_out, double *resid_out,
              int32_t *info_out);
 
+// ---- transient analysis (transient.hip): capacitors stepped in time, one solve per step on the kept matrix work ----
+// the arguments are those of nodal_transient; the source table is already on the device (sw_slot, sw_vals: api.hip's
+// sweep_prepare).  ms_matrix: host milliseconds of the matrix work done once per call, 0.0 when it was kept
+int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                  int32_t nsrc, const double *x0, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
+                  double *wave_out, int32_t keep_every, double *x_out, double *pot_min, int32_t *pot_min_step,
+                  double *pot_max, int32_t *pot_max_step, double *resid_out, int32_t *info_out, int32_t *iters_out,
+                  double *ms_matrix);
+
 // ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])
 struct PortCall {
@@ -590,11 +607,18 @@ int csr_floating_check_small(nodal_ctx *h, int64_t n, const int32_t *indptr, con
 int lowdeg_solve(nodal_ctx *h, int min_share, bool *done, int32_t *info, int32_t *iters, double *resid);
 
 // ---- sparse solvers (sparse_*.hip) ----
+// the multigrid FCG of the passive route with the caller's right-hand side (writes h->x): NODAL_OK, -1 the iteration
+// broke down or hit its cap, -2 a floating island (singular); do_setup false re-uses the hierarchy of an earlier call
+int amg_fcg_solve_rhs(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, int32_t *iters, double *resid);
 int sparse_solve(nodal_ctx *h, int32_t method, int32_t *info, int32_t *iters, double *resid);
 int sparse_residual(nodal_ctx *h, double *scaled);
 // |G x - b|_inf / (|G|_inf |x|_inf + |b|_inf) for any device vectors x, b with the context's CSR matrix; norms5 (host, may
 // be null) receives the five words residual_kernel leaves
 int csr_scaled_residual(nodal_ctx *h, const double *x, const double *b, double *scaled, double *norms5 = nullptr);
+// the block judge of multi_rhs_solve (sparse.hip): scaled residuals of the `cols` (<= 16) columns of x against b, element
+// (i, y) at [i * rs + y * cs], with m's CSR matrix on m's stream; norms (device): [16][4] maxima, then [16] scaled
+// residuals.  Nothing is read back.
+int csr_judge_block(nodal_ctx *m, const double *x, const double *b, int64_t rs, int64_t cs, int cols, double *norms);
 // testing hook (nodal_debug_residual): the single-vector judge (cols 0) or the block judge (cols 1 .. 16) on host vectors
 int sparse_debug_residual(nodal_ctx *h, bool transposed, int32_t cols, int32_t layout, const double *x, const double *b,
                           double *scaled_out, double *norms_out);

@@ -800,6 +800,10 @@ int general_krylov_direct(nodal_ctx *h, const double *b, double *x, int32_t *inf
 int amg_fcg_solve(nodal_ctx *h, int32_t *info, int32_t *iters, double *resid) {
     return amg_fcg_solve_ex(h, h->rhs.as<double>(), true, info, iters, resid);
 }
+// the caller's right-hand side, and with do_setup false the hierarchy of an earlier call on the same matrix (transient.hip)
+int amg_fcg_solve_rhs(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, int32_t *iters, double *resid) {
+    return amg_fcg_solve_ex(h, b, do_setup, info, iters, resid);
+}
 
 // ---- equivalent-resistance sweeps --------------------------
 // The reference rebuilds and re-solves the whole circuit per node pair

@@ -417,6 +417,7 @@ int stamp_numeric(nodal_ctx *h, int32_t member, int64_t *bad_component) {
     if (member < 0 || (h->batch > 0 && member >= h->batch) || (h->batch == 0 && member != 0))
         return nodal_fail(h, NODAL_E_INVALID, "batch member out of range");
     hipStream_t st = h->stream;
+    ++h->numeric_epoch;  // (what a transient call kept of G's values -- hierarchy, factors -- is void)
     const Table tb = table_of(h);
     const double *value =
         h->batch > 0 ? h->values_batch.as<double>() + (int64_t)member * h->ncomp : tb.value;

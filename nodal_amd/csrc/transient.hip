@@ -1,0 +1,400 @@
+// Transient analysis: capacitors stepped in time, every step a solve with the SAME matrix.
+//
+// Replaces a host loop of rebuild and solve per time step (with the reference: a new netlist with companion rows, a new
+// `Circuit` and a `.solve()` for every t_k, reference nodal/nodal.py:306-336).
+//
+// The handle holds the circuit with one extra R row per capacitor, the companion conductance g = C / h (backward Euler)
+// or 2 C / h (trapezoidal rule): the table's value of that row is 1 / g, the existing assembly stamped it, and nothing
+// about G changes from step to step.  What changes is the right-hand side: the sources' values in force at t_k plus, per
+// capacitor, the history current J_k injected into lead a and drawn from lead b,
+//     Euler:        J_k = g v_{k-1}
+//     trapezoidal:  J_k = 2 g v_{k-1} - J_{k-1},  J_0 = g v_0   (the capacitor currents are zero at t_0: a DC point)
+// with v = x(a) - x(b) of the previous solution.  A step is, on the handle's stream,
+//     k_transient_history   one lane per capacitor: J_k from x_{k-1}, one state word per capacitor
+//     stamp_rhs_multi       the sources of step k into a zeroed vector (one column)
+//     k_transient_rhs       one lane per node with capacitors: +-J of its capacitors in list order, no atomics
+//     the solve             multigrid (the hierarchy of step 1), sparse LU (factored once) or the dense panel (n <= 64)
+//     the judgement         the block judge of multi_rhs_solve on one column
+//     k_transient_probe     row k of the waveforms
+//     k_transient_envelope  per node compare-and-update with the step index (when asked for)
+// and every keep_every-th step one device-to-device copy into a staging ring.  Waveforms, envelope and residuals come
+// down once, after the last step.
+#include "group.h"
+
+#include <chrono>
+
+namespace {
+
+constexpr int TTB = 256;
+constexpr int RING = 8;  // kept solutions staged on the device before they go down in one copy
+
+unsigned groups_of(int64_t items) { return (unsigned)((items + TTB - 1) / TTB); }
+
+// the value column the last numeric assembly used (stamp_numeric's choice)
+const double *assembled_values(nodal_ctx *h) {
+    return h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
+}
+
+__device__ __forceinline__ double lead(const double *__restrict__ x, int32_t node) { return node < 0 ? 0.0 : x[node]; }
+
+// grouping enumerator (group.h): capacitor i touches node a (slot 0: +J) and node b (slot 1: -J); one column, so a
+// node's capacitors form ONE entry whose run lists capacitor << 3 | slot in ascending (capacitor, slot) order
+struct CapLeads {
+    static constexpr int SLOTS = 2;
+    const int32_t *rows, *a, *b;
+    int64_t nitems;
+    template <class F>
+    __device__ void for_each(int64_t i, F f) const {
+        const int32_t r = rows[i];
+        const int ia = a[r], ib = b[r];
+        if (ia >= 0) f(0, ia, 0);
+        if (ib >= 0) f(1, ib, 0);
+    }
+};
+
+// bad[0] |= 1 for a capacitor row that is not a resistor
+__global__ __launch_bounds__(TTB) void k_transient_check(int64_t ncap, const int32_t *__restrict__ rows,
+                                                         const uint8_t *__restrict__ type, int32_t *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (i < ncap && type[rows[i]] != NODAL_T_R) atomicOr(bad, 1);
+}
+
+// One lane per capacitor: the history current of the step that follows x.  trapezoidal == 0: J = g v (also the start
+// value of the trapezoidal recurrence); else J = 2 g v - J.
+__global__ __launch_bounds__(TTB) void k_transient_history(int64_t ncap, int trapezoidal, const int32_t *__restrict__ rows,
+                                                           const int32_t *__restrict__ a, const int32_t *__restrict__ b,
+                                                           const double *__restrict__ value, const double *__restrict__ x,
+                                                           double *__restrict__ hist) {
+    const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (i >= ncap) return;
+    const int32_t r = rows[i];
+    const double g = 1.0 / value[r];
+    const double v = lead(x, a[r]) - lead(x, b[r]);
+    hist[i] = trapezoidal ? 2.0 * g * v - hist[i] : g * v;
+}
+
+// One lane per entry of the node list: rhs[node] += the +-J of the node's capacitors, in list order.  The lane is the
+// only writer of its node's row.
+__global__ __launch_bounds__(TTB) void k_transient_rhs(int64_t nent, const int32_t *__restrict__ node,
+                                                       const int32_t *__restrict__ cptr, const uint32_t *__restrict__ contrib,
+                                                       const double *__restrict__ hist, double *__restrict__ rhs) {
+    const int64_t e = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (e >= nent) return;
+    const int32_t row = node[e];
+    double acc = rhs[row];
+    for (int32_t p = cptr[e]; p < cptr[e + 1]; ++p) {
+        const uint32_t u = contrib[p];
+        const double j = hist[u >> 3];
+        acc += (u & 7u) ? -j : j;
+    }
+    rhs[row] = acc;
+}
+
+// out[p] = x(a_p) - x(b_p); a probe between a node and itself reads +0.0 whatever x holds
+__global__ __launch_bounds__(TTB) void k_transient_probe(int32_t nprobe, const int32_t *__restrict__ pa,
+                                                         const int32_t *__restrict__ pb, const double *__restrict__ x,
+                                                         double *__restrict__ out) {
+    const int32_t p = blockIdx.x * TTB + threadIdx.x;
+    if (p >= nprobe) return;
+    out[p] = pa[p] == pb[p] ? 0.0 : lead(x, pa[p]) - lead(x, pb[p]);
+}
+
+// per node: the lowest and highest potential so far and the step that attained it first (strict comparisons: among
+// exact ties the lowest step stays).  first: no step has been taken in yet.
+__global__ __launch_bounds__(TTB) void k_transient_envelope(int32_t K, int32_t step, int first, const double *__restrict__ x,
+                                                            double *__restrict__ pmin, int32_t *__restrict__ pmin_step,
+                                                            double *__restrict__ pmax, int32_t *__restrict__ pmax_step) {
+    const int32_t i = blockIdx.x * TTB + threadIdx.x;
+    if (i >= K) return;
+    const double v = x[i];
+    if (first || v < pmin[i]) {
+        pmin[i] = v;
+        pmin_step[i] = step;
+    }
+    if (first || v > pmax[i]) {
+        pmax[i] = v;
+        pmax_step[i] = step;
+    }
+}
+
+// the refinement step of the sparse LU route: r = b - G x, then x += d
+__global__ __launch_bounds__(TTB) void k_transient_defect(int64_t n, const int32_t *__restrict__ indptr,
+                                                          const int32_t *__restrict__ indices, const double *__restrict__ data,
+                                                          const double *__restrict__ x, const double *__restrict__ b,
+                                                          double *__restrict__ r) {
+    const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (i >= n) return;
+    double acc = b[i];
+    for (int32_t q = indptr[i]; q < indptr[i + 1]; ++q) acc = fma(-data[q], x[indices[q]], acc);
+    r[i] = acc;
+}
+__global__ __launch_bounds__(TTB) void k_transient_correct(int64_t n, const double *__restrict__ d, double *__restrict__ x) {
+    const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (i < n) x[i] += d[i];
+}
+
+enum Route { ROUTE_DENSE, ROUTE_LU, ROUTE_MG };
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                  int32_t nsrc, const double *x0, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
+                  double *wave_out, int32_t keep_every, double *x_out, double *pot_min, int32_t *pot_min_step,
+                  double *pot_max, int32_t *pot_max_step, double *resid_out, int32_t *info_out, int32_t *iters_out,
+                  double *ms_matrix) {
+    const int64_t n = h->n;
+    const int32_t K = h->K;
+    hipStream_t st = h->stream;
+    const double nan = __builtin_nan("");
+    *ms_matrix = 0.0;
+    const bool want_env = pot_min || pot_min_step || pot_max || pot_max_step;
+    const int32_t nkeep = (keep_every > 0 && x_out) ? steps / keep_every : 0;
+    std::vector<double> resid_own(resid_out ? 0 : (size_t)steps);
+    std::vector<int32_t> info_own(info_out ? 0 : (size_t)steps), iters_own(iters_out ? 0 : (size_t)steps);
+    double *resid = resid_out ? resid_out : resid_own.data();
+    int32_t *info = info_out ? info_out : info_own.data(), *iters = iters_out ? iters_out : iters_own.data();
+    for (int32_t k = 0; k < steps; ++k) {
+        info[k] = iters[k] = 0;
+        resid[k] = 0.0;
+    }
+    h->have_x = false;
+    h->last_iterations = 0;
+    if (n == 0) {  // (every lead is ground: nothing moves)
+        if (wave_out)
+            for (int64_t t = 0; t < (int64_t)(steps + 1) * nprobe; ++t) wave_out[t] = 0.0;
+        return NODAL_OK;
+    }
+
+    // ---- once per call: capacitor rows and probes up, the node lists, the buffers ----
+    for (int64_t i = 0; i < ncap; ++i)
+        if (cap_rows[i] < 0 || cap_rows[i] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "transient: capacitor row out of range");
+    for (int32_t p = 0; p < nprobe; ++p)
+        if (probe_a[p] < -1 || probe_a[p] >= K || probe_b[p] < -1 || probe_b[p] >= K)
+            return nodal_fail(h, NODAL_E_INVALID, "transient: probe node out of range");
+    const size_t cap_words = ((size_t)ncap + 15) & ~(size_t)15, probe_words = ((size_t)nprobe + 15) & ~(size_t)15;
+    // tr_spec: cap rows | probe a | probe b | bad flag (16 words) | history [ncap] doubles
+    NODAL_HIP_TRY(h, h->tr_spec.reserve((cap_words + 2 * probe_words + 16) * 4 + (size_t)ncap * 8 + 64));
+    int32_t *rows_dev = h->tr_spec.as<int32_t>(), *pa_dev = rows_dev + cap_words, *pb_dev = pa_dev + probe_words,
+            *bad_dev = pb_dev + probe_words;
+    double *hist = reinterpret_cast<double *>(bad_dev + 16);
+    int64_t nent = 0, ncon = 0;
+    if (ncap > 0) {
+        if (K == 0) return nodal_fail(h, NODAL_E_INVALID, "transient: capacitors on a network without nodes");
+        std::vector<int32_t> r32((size_t)ncap);
+        for (int64_t i = 0; i < ncap; ++i) r32[(size_t)i] = (int32_t)cap_rows[i];
+        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)ncap * 4, hipMemcpyHostToDevice, st));
+        NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
+        k_transient_check<<<groups_of(ncap), TTB, 0, st>>>(ncap, rows_dev, h->type.as<uint8_t>(), bad_dev);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        int32_t bad = 0;
+        NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copy above is done too)
+        if (bad) return nodal_fail(h, NODAL_E_INVALID, "transient: a capacitor row that is not a resistor (R)");
+        NODAL_TRY(grp::build_lists(h, CapLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), ncap}, (int64_t)K, &nent,
+                                   &ncon, h->tr_none, h->tr_node, h->tr_ptr, h->tr_con, nullptr, nullptr));
+    }
+    if (nprobe > 0) {
+        NODAL_HIP_TRY(h, hipMemcpyAsync(pa_dev, probe_a, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(pb_dev, probe_b, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
+    }
+    // tr_vec: two solutions | right-hand side | defect | correction | the judge's norms
+    NODAL_HIP_TRY(h, h->tr_vec.reserve((size_t)5 * n * 8 + 5 * SLU_MULTI * 8 + 256));
+    double *xv[2] = {h->tr_vec.as<double>(), h->tr_vec.as<double>() + n};
+    double *bvec = xv[1] + n, *rvec = bvec + n, *dvec = rvec + n, *norms = dvec + n;
+    // tr_out: waveforms [steps + 1][nprobe] | residuals [steps] | envelope min, max [K] each | their steps [K] each
+    const size_t wave_words = (size_t)(steps + 1) * nprobe, env_words = want_env ? (size_t)K : 0;
+    NODAL_HIP_TRY(h, h->tr_out.reserve((wave_words + (size_t)steps + 3 * env_words + 2) * 8 + 64));
+    double *wave_dev = h->tr_out.as<double>(), *resid_dev = wave_dev + wave_words, *pmin_dev = resid_dev + steps,
+           *pmax_dev = pmin_dev + env_words;
+    int32_t *pmin_step_dev = reinterpret_cast<int32_t *>(pmax_dev + env_words), *pmax_step_dev = pmin_step_dev + env_words;
+    if (want_env) NODAL_HIP_TRY(h, hipMemsetAsync(pmin_dev, 0xFF, 3 * env_words * 8, st));  // (NaN and -1 until a step is taken in)
+    double *ring = nullptr;
+    if (nkeep > 0) {
+        NODAL_HIP_TRY(h, h->tr_ring.reserve((size_t)std::min<int32_t>(RING, nkeep) * n * 8 + 64));
+        ring = h->tr_ring.as<double>();
+    }
+    NODAL_HIP_TRY(h, hipMemcpyAsync(xv[0], x0, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (nprobe > 0) {
+        k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, xv[0], wave_dev);
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    const double *value = assembled_values(h);
+    if (ncap > 0 && method == 1) {  // J_0 = g v_0
+        k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, 0, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), value,
+                                                            xv[0], hist);
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    NODAL_WAIT_STREAM(h, st);  // (x0 and the probes are the caller's, r32 ends here)
+
+    // ---- the route and its matrix work ----
+    const bool passive = h->B == 0 && h->passive_network;
+    const int64_t multigrid_min = 4096;  // multi_rhs_solve's bound for passive systems
+    const Route route = n <= 64 ? ROUTE_DENSE : (passive && n > multigrid_min) ? ROUTE_MG : ROUTE_LU;
+    const int64_t lda = dense_lda(n);
+    bool direct = false;      // multigrid route: the iteration gave up, this step and every later one by the direct solve
+    bool all_direct = false;  // sparse LU route: pivots were replaced, every step by the direct solve (which judges its own)
+    bool mg_setup = false;
+    bool dead = steps == 0;   // a singular verdict: no step from there on has a state to start from
+    const double bar = knob::MULTI_BAR.now();
+    if (route == ROUTE_DENSE) {
+        NODAL_HIP_TRY(h, h->dense.reserve((size_t)lda * (size_t)(n + 1) * 8 + 64));
+    } else if (route == ROUTE_LU && steps > 0) {
+        if (h->tr_lu_epoch != h->numeric_epoch || nodal_poison_level() >= 2) {  // (NODAL_POISON=2 poisons the factors)
+            const auto t0 = std::chrono::steady_clock::now();
+            int32_t inf = 0;
+            NODAL_TRY(slu_factor(h, &inf));
+            NODAL_WAIT_STREAM(h, st);
+            *ms_matrix = ms_since(t0);
+            if (inf > 0) {
+                if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+                dead = true;
+            } else {
+                h->tr_lu_epoch = h->numeric_epoch;
+            }
+        }
+        all_direct = !dead && slu_perturbed(h) > 0;
+    } else if (route == ROUTE_MG) {
+        mg_setup = !(h->tr_mg_epoch == h->numeric_epoch && sagg_ready(h, n)) || nodal_poison_level() >= 2;
+    }
+
+    // ---- the steps ----
+    int32_t first_dead = dead ? 1 : steps + 1;
+    std::vector<uint8_t> on_host((size_t)steps, 0);  // the step's residual was read back already (the sparse LU route)
+    bool env_first = true;
+    int32_t ring_fill = 0, ring_base = 0;  // kept solutions in the ring, and the index of the first of them
+    auto flush_ring = [&]() -> int {
+        if (ring_fill == 0) return NODAL_OK;
+        NODAL_HIP_TRY(h, hipMemcpyAsync(x_out + (int64_t)ring_base * n, ring, (size_t)ring_fill * n * 8,
+                                        hipMemcpyDeviceToHost, st));
+        NODAL_WAIT_STREAM(h, st);  // (the ring is written again by the steps that follow)
+        ring_base += ring_fill;
+        ring_fill = 0;
+        return NODAL_OK;
+    };
+    for (int32_t k = 1; k <= steps && !dead; ++k) {
+        const double *xp = xv[(k - 1) & 1];
+        double *xk = xv[k & 1];
+        // the right-hand side: the sources in force at t_k, then the capacitors' history currents
+        NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)n * 8, st));
+        NODAL_TRY(stamp_rhs_multi(h, h->sw_slot.as<int32_t>(), h->sw_vals.as<double>() + (int64_t)(k - 1) * nsrc, nsrc, 1,
+                                  bvec, 1, 0));
+        if (ncap > 0) {
+            k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, method, rows_dev, h->a.as<int32_t>(),
+                                                                h->b.as<int32_t>(), value, xp, hist);
+            if (nent > 0)
+                k_transient_rhs<<<groups_of(nent), TTB, 0, st>>>(nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(),
+                                                                h->tr_con.as<uint32_t>(), hist, bvec);
+            NODAL_HIP_TRY(h, hipGetLastError());
+        }
+        // the solve
+        int32_t inf = 0, it = 0;
+        double rs = 0.0;
+        bool judged = false;  // resid[k - 1] is on the host already
+        if (route == ROUTE_DENSE) {
+            // (the tiny matrix is factored anew: a panel launch)
+            NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
+            NODAL_HIP_TRY(h, hipMemcpyAsync(h->dense.as<double>() + n * lda, bvec, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            NODAL_TRY(dense_factor_solve_multi(h, 1, xk, n, &inf));
+        } else if (route == ROUTE_MG) {
+            const auto t0 = std::chrono::steady_clock::now();
+            const bool setup = k == 1 && mg_setup;
+            if (!direct) {
+                const int sv = amg_fcg_solve_rhs(h, bvec, setup, &inf, &it, &rs);  // (writes h->x)
+                if (sv == -2) {
+                    inf = 1;  // a floating island: every step is singular
+                } else if (sv == NODAL_OK) {
+                    NODAL_HIP_TRY(h, hipMemcpyAsync(xk, h->x.as<double>(), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+                    if (setup) h->tr_mg_epoch = h->numeric_epoch;
+                } else if (sv < 0) {
+                    direct = true;
+                    h->tr_mg_epoch = 0;  // (the hierarchy was given up and invalidated)
+                } else {
+                    return sv;
+                }
+            }
+            if (direct) NODAL_TRY(sparse_direct_solve(h, bvec, xk, &inf, &it, &rs));
+            if (setup) *ms_matrix = ms_since(t0);
+        } else {
+            bool redo = all_direct;
+            if (!all_direct) {
+                NODAL_TRY(slu_apply(h, bvec, xk));
+                k_transient_defect<<<groups_of(n), TTB, 0, st>>>(n, h->indptr.as<int32_t>(), h->indices.as<int32_t>(),
+                                                                h->data.as<double>(), xk, bvec, rvec);
+                NODAL_HIP_TRY(h, hipGetLastError());
+                NODAL_TRY(slu_apply(h, rvec, dvec));
+                k_transient_correct<<<groups_of(n), TTB, 0, st>>>(n, dvec, xk);
+                NODAL_HIP_TRY(h, hipGetLastError());
+                NODAL_TRY(csr_judge_block(h, xk, bvec, 1, 0, 1, norms));
+                NODAL_TRY(nodal_read_words(h, &resid[k - 1], norms + 4 * SLU_MULTI, 8));
+                judged = true;
+                it = 1;
+                redo = !(resid[k - 1] <= bar);
+            }
+            if (redo) {
+                judged = false;
+                NODAL_TRY(sparse_direct_solve(h, bvec, xk, &inf, &it, &rs));
+                if (!all_direct && inf == 0) {  // (the direct solve may have factored anew, with another pivot bar)
+                    int32_t inf2 = 0;
+                    NODAL_TRY(slu_factor(h, &inf2));
+                    all_direct = inf2 > 0 || slu_perturbed(h) > 0;
+                    if (all_direct) h->tr_lu_epoch = 0;
+                }
+            }
+        }
+        if (inf > 0) {
+            if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+            dead = true;
+            first_dead = k;
+            break;
+        }
+        iters[k - 1] = it;
+        h->last_iterations = it;
+        on_host[(size_t)k - 1] = judged;
+        if (!judged) {
+            NODAL_TRY(csr_judge_block(h, xk, bvec, 1, 0, 1, norms));
+            NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + (k - 1), norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
+        }
+        // what the caller asked for of x_k
+        if (nprobe > 0) k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, xk, wave_dev + (size_t)k * nprobe);
+        if (want_env && K > 0) {
+            k_transient_envelope<<<groups_of(K), TTB, 0, st>>>(K, k, env_first ? 1 : 0, xk, pmin_dev, pmin_step_dev, pmax_dev,
+                                                              pmax_step_dev);
+            env_first = false;
+        }
+        NODAL_HIP_TRY(h, hipGetLastError());
+        if (nkeep > 0 && k % keep_every == 0) {
+            NODAL_HIP_TRY(h, hipMemcpyAsync(ring + (size_t)ring_fill * n, xk, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            if (++ring_fill == std::min<int32_t>(RING, nkeep)) NODAL_TRY(flush_ring());
+        }
+    }
+    NODAL_TRY(flush_ring());
+
+    // ---- after the last step: everything else comes down once ----
+    std::vector<double> resid_dn((size_t)steps);
+    if (wave_out && wave_words > 0)
+        NODAL_HIP_TRY(h, hipMemcpyAsync(wave_out, wave_dev, wave_words * 8, hipMemcpyDeviceToHost, st));
+    if (steps > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dn.data(), resid_dev, (size_t)steps * 8, hipMemcpyDeviceToHost, st));
+    if (want_env && K > 0) {
+        if (pot_min) NODAL_HIP_TRY(h, hipMemcpyAsync(pot_min, pmin_dev, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+        if (pot_max) NODAL_HIP_TRY(h, hipMemcpyAsync(pot_max, pmax_dev, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+        if (pot_min_step) NODAL_HIP_TRY(h, hipMemcpyAsync(pot_min_step, pmin_step_dev, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+        if (pot_max_step) NODAL_HIP_TRY(h, hipMemcpyAsync(pot_max_step, pmax_step_dev, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    }
+    NODAL_WAIT_STREAM(h, st);
+    for (int32_t k = 1; k < first_dead && k <= steps; ++k)
+        if (!on_host[(size_t)k - 1]) resid[k - 1] = resid_dn[(size_t)k - 1];
+    // the steps without a state: info 1, NaN wherever they were to land
+    for (int32_t k = first_dead; k <= steps; ++k) {
+        info[k - 1] = 1;
+        iters[k - 1] = 0;
+        resid[k - 1] = nan;
+        if (wave_out)
+            for (int32_t p = 0; p < nprobe; ++p) wave_out[(size_t)k * nprobe + p] = nan;
+        if (nkeep > 0 && k % keep_every == 0)
+            for (int64_t i = 0; i < n; ++i) x_out[(int64_t)(k / keep_every - 1) * n + i] = nan;
+    }
+    return NODAL_OK;
+}

@@ -63,6 +63,18 @@ class ComponentTable:
         t.value = value
         return t
 
+    def with_rows_appended(self, type, value, a, b):
+        """A copy with len(type) more rows behind the present ones (same K, B: the new rows introduce no unknowns):
+        two-lead components -- the companion resistors of Circuit.transient -- with no control nodes, driver or
+        branch.  The present rows keep their indices."""
+        extra = len(type)
+        t = ComponentTable(self.ncomp + extra, self.K, self.B)
+        for name in ("type", "value", "a", "b", "c", "d", "drv", "k"):
+            getattr(t, name)[:self.ncomp] = getattr(self, name)
+        t.type[self.ncomp:], t.value[self.ncomp:] = type, value
+        t.a[self.ncomp:], t.b[self.ncomp:] = a, b
+        return t
+
     def truncated(self, ncomp):
         """A copy holding only the first `ncomp` rows (used to let the device
         look for an earlier stamp collision before a host error is raised)."""
