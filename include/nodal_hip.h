@@ -272,6 +272,46 @@ int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method
                     double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
                     int32_t *info_out, int32_t *iters_out);
 
+/* ---- gradients through time (replaces finite differences over whole transient runs: two nodal_transient calls per
+ *      component; with the reference each of them a host loop of rebuild and solve, reference nodal/nodal.py:306-336) ----
+ * The adjoint of the backward-Euler run the handle has RECORDED: with NODAL_OPT_TRANSIENT_TAPE set, a nodal_transient call
+ * with method 0 whose every step ended with info 0 leaves x_0 .. x_steps, its capacitor rows and its swept rows on the
+ * handle.  The tape is void after nodal_assemble_numeric, after an upload and after any later nodal_transient call (which
+ * replaces it if it records).  For a scalar loss of the probe waveforms, wave_cot[k][p] = dL / d wave[k][p]
+ * ([steps + 1][nprobe]; the probes (probe_a[p], probe_b[p]) need not be those of the recorded call; a probe with
+ * probe_a == probe_b contributes nothing) gives c_k = sum_p wave_cot[k][p] (e(a_p) - e(b_p)), and with M = G, S the
+ * capacitors' incidence, r_i their companion rows' values, g = 1 / r and lambda_{steps+1} = 0:
+ *   M^T lambda_k = c_k + S (g o S^T lambda_{k+1}),  k = steps .. 1     (the forward step run backwards, transposed)
+ *   grad_out[i]               = sum_k s_i(lambda_k, x_k) for every table row i that is not a companion row, s_i the
+ *                               per-row formula of nodal_gradient (cross terms included); at a swept row the sum over the
+ *                               steps, nodal_gradient's convention
+ *   grad_out[cap_rows[i]]     = sum_k (lambda_k(a) - lambda_k(b)) ((x_k(a) - x_k(b)) - (x_{k-1}(a) - x_{k-1}(b))) / r_i^2:
+ *                               the derivative with respect to the companion value r_i = h / C_i, so that
+ *                               dL/dC_i = -(h / C_i^2) grad_out[cap_rows[i]]
+ *   grad_sources_out[k-1][j]  = s_{src_rows[j]}(lambda_k): the derivative with respect to src_values[k-1][j]
+ *   grad_x0_out               = c_0 + S (g o S^T lambda_1) = dL/dx0 ([n]; zero in the branch rows)
+ *   adjoint_out [steps][n]    lambda_1 .. lambda_steps
+ *   resid_out [steps]         the scaled residual of M^T lambda_k = its right-hand side, as nodal_solve_sources defines it
+ *   info_out [steps]          > 0: singular (the step and every EARLIER one: NaN in everything they feed and in the whole
+ *                             of grad_out and grad_x0_out, status OK) -- except with dense != 0: NODAL_E_SINGULAR
+ * grad_sources_out, grad_x0_out, adjoint_out and resid_out may be NULL.  steps == 0: zeros in grad_out, grad_x0_out = c_0;
+ * n == 0: zeros.  Routes as nodal_transient's; B == 0 and all R > 0 (M symmetric) re-uses the hierarchy or factors the
+ * forward run left, every other network solves with the transposed matrix, factored once and kept like the forward
+ * run's.  The sum over the steps is formed on the device in one fixed order -- descending k, sixteen steps to a block
+ * (csrc/transient_gradient.hip) -- and comes down once.  nodal_last_timings afterwards: [0] host ms of the matrix work
+ * this call did once, exactly 0.0 when it was kept or not needed; [1] 0.0; [2] the whole call.
+ * NODAL_E_INVALID: no valid tape on the handle; a probe node outside [-1, K).
+ * Leaves the handle as it found it: the solution if any, the table, G, A, the tape, the kept hierarchy and factors -- a
+ * second call with other cotangents repeats no matrix work.  No floating-point atomics: a repeated call gives the same
+ * bits. */
+int nodal_transient_gradient(nodal_handle h, int32_t dense, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
+                             const double *wave_cot /* [steps + 1][nprobe] */,
+                             double *grad_out /* [ncomp] of this handle, companion rows included */,
+                             double *grad_sources_out /* [steps][nsrc] of the recorded call, may be NULL */,
+                             double *grad_x0_out /* [n], may be NULL */,
+                             double *adjoint_out /* [steps][n], may be NULL */,
+                             double *resid_out /* [steps], may be NULL */, int32_t *info_out /* [steps] */);
+
 /* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
  *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
  *      reference has no equivalent of an active network and no coupling between ports) ----
@@ -358,8 +398,14 @@ int nodal_synchronize(nodal_handle h);
  *   nodal_upload_components stay valid and unchanged until the next upload or nodal_destroy.  The library then reads
  *   them in place where its host code needs the table (the presolve of systems with branch equations looks at the
  *   branch rows and at the rows touching an eliminated node) instead of keeping a copy of its own: the upload of a
- *   table with branches is DMA only.  nodal_amd/_ffi.py sets it (its Handle keeps the arrays alive). */
-enum { NODAL_OPT_FORCE_PIVOTING = 1, NODAL_OPT_GEPP_PANEL = 2, NODAL_OPT_EXTRA_STREAMS = 3, NODAL_OPT_BORROW_TABLE = 4 };
+ *   table with branches is DMA only.  nodal_amd/_ffi.py sets it (its Handle keeps the arrays alive).
+ * NODAL_OPT_TRANSIENT_TAPE (0/1, default 0): a backward-Euler nodal_transient call keeps its states on the handle for
+ *   nodal_transient_gradient, [steps + 1][n] doubles of device memory (a tape that does not fit is NODAL_E_NOMEM).  With
+ *   0 nodal_transient allocates nothing more and does exactly what it did. */
+enum {
+    NODAL_OPT_FORCE_PIVOTING = 1, NODAL_OPT_GEPP_PANEL = 2, NODAL_OPT_EXTRA_STREAMS = 3, NODAL_OPT_BORROW_TABLE = 4,
+    NODAL_OPT_TRANSIENT_TAPE = 5
+};
 int nodal_set_option(nodal_handle h, int32_t option, int32_t value);
 
 /* ---- testing hooks (not part of the reference-facing surface) -------------

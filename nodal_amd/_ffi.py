@@ -22,6 +22,7 @@ OPT_FORCE_PIVOTING = 1
 OPT_GEPP_PANEL = 2
 OPT_EXTRA_STREAMS = 3
 OPT_BORROW_TABLE = 4
+OPT_TRANSIENT_TAPE = 5
 
 _p = C.POINTER
 _i32p, _i64p, _f64p, _u8p = _p(C.c_int32), _p(C.c_int64), _p(C.c_double), _p(C.c_uint8)
@@ -58,6 +59,8 @@ SIGNATURES = {
     "nodal_transient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
                                   _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p, _i32p,
                                   _f64p, _i32p, _i32p]),
+    "nodal_transient_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
+                                           _f64p, _i32p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
@@ -435,6 +438,29 @@ class Handle:
             _ptr(wave, C.c_double), int(keep_every), _ptr(x, C.c_double) if x is not None and kept else None, *env_ptrs,
             _ptr(resid, C.c_double), _ptr(info, C.c_int32), _ptr(iters, C.c_int32)))
         return wave, x, env, resid, info, iters
+
+    def transient_gradient(self, steps, nsrc, ia, ib, cotangents, dense, adjoints=False):
+        """The adjoint of the transient run this handle recorded (nodal_transient_gradient; OPT_TRANSIENT_TAPE): steps
+        and nsrc those of that run, (ia, ib) the probes' node indices, cotangents [steps + 1, P] = dL / d waveforms.
+        Returns (grad [ncomp] of this handle's table, companion rows included, source derivatives [steps, nsrc], dL/dx0
+        [n], adjoints [steps, n] or None, scaled residual [steps], info [steps]); NodalHipError(E_INVALID) without a
+        valid tape, with dense a singular G raises NodalHipError(E_SINGULAR)."""
+        ia, ib = (np.ascontiguousarray(v, dtype=np.int32) for v in (ia, ib))
+        assert ia.ndim == 1 and ib.shape == ia.shape
+        cot = np.ascontiguousarray(cotangents, dtype=np.float64)
+        assert cot.shape == (steps + 1, len(ia))
+        grad = np.zeros(self._ncomp, dtype=np.float64)
+        gsrc = np.zeros((steps, nsrc), dtype=np.float64)
+        gx0 = np.zeros(self.n, dtype=np.float64)
+        lam = host_empty(steps * self.n, np.float64).reshape(steps, self.n) if adjoints else None
+        resid = np.zeros(steps, dtype=np.float64)
+        info = np.zeros(steps, dtype=np.int32)
+        self._check(self.lib.nodal_transient_gradient(
+            self._h, int(dense), len(ia), _ptr(ia, C.c_int32) if len(ia) else None, _ptr(ib, C.c_int32) if len(ib) else None,
+            _ptr(cot, C.c_double) if cot.size else None, _ptr(grad, C.c_double), _ptr(gsrc, C.c_double),
+            _ptr(gx0, C.c_double), _ptr(lam, C.c_double) if adjoints and steps else None, _ptr(resid, C.c_double),
+            _ptr(info, C.c_int32)))
+        return grad, gsrc, gx0, lam, resid, info
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

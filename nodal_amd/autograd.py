@@ -2,6 +2,7 @@
 
     x = autograd.solve(circuit, values)                                   # [K+B]
     X = autograd.solve_sources(circuit, values, names, source_values)     # [M, K+B]
+    W = autograd.transient(circuit, values, capacitors, dt, steps, ...)   # [steps+1, P]
 
 `values` is a float64 CPU tensor [ncomp] in the order of `netlist.component_keys` (what `Circuit.values` holds),
 `source_values` a float64 CPU tensor [M, len(names)] with the members' values of the swept A / E components
@@ -9,6 +10,10 @@
 cotangents to `Circuit.gradient` (nodal_gradient: one adjoint solve per member, the sum over the members formed on
 the device) and is differentiable once.  The gradient for `values` is zero at the swept rows of solve_sources --
 their table value is not used by any member -- and the swept values get theirs through `source_values`.
+`transient` returns the probe waveforms of `Circuit.transient(..., record=True)`; its backward is
+`Circuit.transient_gradient` (the time stepping run backwards) and hands gradients to `values`, the capacitances and
+`source_values` [steps, len(names)]; at a swept row `values` gets what the DC start owes to the table value, zero when
+the run starts from `initial`.
 
 This module imports torch; `import nodal_amd` does not import it.
 """
@@ -77,6 +82,50 @@ class _SolveSources(torch.autograd.Function):
         return None, torch.from_numpy(values), None, torch.from_numpy(np.ascontiguousarray(swept))
 
 
+class _Transient(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, circuit, values, farads, source_values, leads, dt, steps, names, probes, initial):
+        held, caps = _values_of(values), _values_of(farads)
+        names = list(names)
+        swept = _values_of(source_values) if names else np.zeros((steps, 0))
+        if swept.shape != (steps, len(names)):
+            raise ValueError(f"source_values must have shape ({steps}, {len(names)}), not {tuple(swept.shape)}")
+        if caps.shape != (len(leads),):
+            raise ValueError(f"the farads must have shape ({len(leads)},), not {tuple(caps.shape)}")
+        ctx.circuit, ctx.held, ctx.names = circuit, held, names
+        ctx.call = dict(capacitors=[(name, float(f), a, b) for (name, a, b), f in zip(leads, caps)], dt=dt, steps=steps,
+                        sources={name: swept[:, j] for j, name in enumerate(names)}, probes=list(probes),
+                        initial=None if initial is None else np.array(initial, dtype=np.float64))
+        tr = _Transient.run(ctx)
+        return torch.from_numpy(np.array(tr.waveforms, dtype=np.float64))
+
+    @staticmethod
+    def run(ctx):
+        circuit = ctx.circuit
+        circuit.set_values(ctx.held)
+        if ctx.call["initial"] is None:
+            circuit.solve()
+        tr = circuit.transient(record=True, **ctx.call)
+        ctx.record = circuit._transient_record
+        return tr
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, cotangent):
+        circuit = ctx.circuit
+        if ctx.record is None or circuit._transient_record is not ctx.record:
+            _Transient.run(ctx)  # (the circuit has been used otherwise since the forward pass)
+        grad = circuit.transient_gradient(_values_of(cotangent))
+        from .sweep import resolve_sources
+        values = np.array(grad.values, dtype=np.float64)
+        rows, _ = resolve_sources(circuit.netlist, ctx.call["sources"])
+        # (no step uses the table value of a swept source: it acts through the DC start alone, not at all with `initial`)
+        values[rows] = grad.start_values[rows]
+        swept = np.stack([grad.source_values[name] for name in ctx.names], axis=1) if ctx.names else None
+        return (None, torch.from_numpy(values), torch.from_numpy(np.array(grad.capacitors, dtype=np.float64)),
+                torch.from_numpy(np.ascontiguousarray(swept)) if ctx.names else None, None, None, None, None, None, None)
+
+
 def solve(circuit, values):
     """The solution [K+B] of `circuit` with the component values `values` [ncomp], differentiable in `values`."""
     return _Solve.apply(circuit, values)
@@ -86,3 +135,19 @@ def solve_sources(circuit, values, names, source_values):
     """The solutions [M, K+B] of `circuit` with the component values `values` [ncomp] and, member by member, the
     values `source_values` [M, len(names)] of the independent sources `names`; differentiable in both."""
     return _SolveSources.apply(circuit, values, names, source_values)
+
+
+def transient(circuit, values, capacitors, dt, steps, source_names=(), source_values=None, probes=(), initial=None):
+    """The probe waveforms [steps+1, P] of `Circuit.transient` (backward Euler) with the component values `values`
+    [ncomp], the capacitors `capacitors` -- (name, farads, node_a, node_b) with each farads a float64 CPU scalar
+    tensor, e.g. an element of one [C] tensor -- and, step by step, the values `source_values` [steps,
+    len(source_names)] of the independent sources `source_names`; differentiable in values, farads and source values.
+    initial=None starts from the DC operating point of `values`, whose dependence on them is part of the gradient."""
+    capacitors = list(capacitors)
+    farads = torch.stack([torch.as_tensor(cap[1], dtype=torch.float64) for cap in capacitors]) if capacitors else \
+        torch.zeros(0, dtype=torch.float64)
+    leads = [(cap[0], cap[2], cap[3]) for cap in capacitors]
+    if source_values is None:
+        source_values = torch.zeros((steps, 0), dtype=torch.float64)
+    return _Transient.apply(circuit, values, farads, source_values, leads, dt, steps, tuple(source_names), tuple(probes),
+                            initial)

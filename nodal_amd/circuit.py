@@ -87,6 +87,7 @@ class Circuit:
         self._handle = None
         self._G = self._A = None
         self._transient_child = None
+        self._transient_record = None
         self.currents = self.build_model()
 
     @classmethod
@@ -99,6 +100,7 @@ class Circuit:
         self._handle = None
         self._G = self._A = None
         self._transient_child = None
+        self._transient_record = None
         self.table = other.table if table is None else table
         self.currents = other.currents
         self._assemble(self.table)
@@ -376,6 +378,7 @@ class Circuit:
             raise AssertionError  # the reference's bare `assert G[i, j] == 0`
         self._G = self._A = None
         self._transient_child = None  # (its matrix carried the old values)
+        self._transient_record = None
         self.table = table.with_values(new)
 
     def thevenin(self, ports, sources=True):
@@ -413,7 +416,7 @@ class Circuit:
         return PortEquivalent(self.netlist, ports, z, v_oc, info, resid)
 
     def transient(self, capacitors, dt, steps, sources=None, probes=(), method="euler", initial=None, keep_every=0,
-                  envelope=False):
+                  envelope=False, record=False):
         """Step the circuit with capacitors through `steps` time steps of length `dt` on the device (nodal_transient).
 
         `capacitors` is a sequence of (name, farads, node_a, node_b) on nodes of the netlist; `sources` maps names of
@@ -425,7 +428,9 @@ class Circuit:
         (which needs the DC start: ValueError with `initial`).  keep_every=s > 0 brings the full solution of every
         s-th step down, envelope=True adds per node the lowest and highest potential over the steps and a step that
         attains each.  Returns a Transient (transient.py): `t`, `waveforms` [steps+1, P], `solutions`,
-        `solution_steps`, `envelope`, `info`, `scaled_residual`, `iterations`.
+        `solution_steps`, `envelope`, `info`, `scaled_residual`, `iterations`.  record=True (backward Euler only:
+        ValueError with "trapezoidal") keeps the states x_0 .. x_steps on the device for transient_gradient(), until the
+        next transient() or set_values(); the results are the same bits either way.
 
         The matrix is that of the netlist with one companion resistor per capacitor, assembled on a second device
         context that is kept on the circuit, keyed by the capacitors, dt and method, until set_values(): a second call
@@ -435,10 +440,13 @@ class Circuit:
         G, A -- is left as it was."""
         from .ports import _as_pair, resolve_ports
         from .sweep import resolve_sources
-        from .transient import (Transient, TransientEnvelope, check_transient_arguments, companion_table,
+        from .transient import (METHODS, Transient, TransientEnvelope, check_transient_arguments, companion_table,
                                 resolve_capacitors)
         h = self._handle
+        self._transient_record = None  # (whatever an earlier call recorded: the device drops it as well)
         dt, steps, code, x0 = check_transient_arguments(dt, steps, method, initial, h.n)
+        if record and code != METHODS["euler"]:
+            raise ValueError('record=True needs method="euler": the adjoint of the trapezoidal rule is not implemented')
         keep_every = int(keep_every)
         if keep_every < 0:
             raise ValueError(f"keep_every must not be negative, not {keep_every}")
@@ -465,6 +473,8 @@ class Circuit:
         _, child, cap_rows = self._transient_child
         ch = child._handle
         try:
+            if record:
+                ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 1)
             wave, x, env, resid, info, iters = ch.transient(cap_rows, rows, values, x0, pa, pb, dense=not self.sparse,
                                                             method=code, keep_every=keep_every, envelope=envelope)
         except _ffi.NodalHipError as exc:
@@ -475,14 +485,75 @@ class Circuit:
                 raise UnconnectedCircuitError
             logging.error("Model error: matrix is singular")
             raise np.linalg.LinAlgError("Singular matrix")
+        finally:
+            if record:
+                ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 0)  # (the handle goes back to a pool some day)
         if (info > 0).any():
             warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        elif record:
+            from .sweep import _row_map
+            from .transient_gradient import TransientRecord
+            row_map, columns, at = _row_map(self.netlist), {}, 0
+            for name in (sources or {}):  # (the order resolve_sources lays the rows out in)
+                columns[name] = list(range(at, at + len(row_map[name])))
+                at += len(row_map[name])
+            self._transient_record = TransientRecord(child, dt, farads, cap_rows, columns, len(rows), steps, probes, pa, pb,
+                                                     np.array(x0, dtype=np.float64), initial is None)
         if env is not None:
             env = TransientEnvelope(env["potential_min"], env["potential_min_step"], env["potential_max"],
                                     env["potential_max_step"])
         kept = np.arange(1, steps // keep_every + 1, dtype=np.int64) * keep_every if keep_every > 0 else None
         return Transient(dt * np.arange(steps + 1, dtype=np.float64), wave, probes, info, resid, iters, solutions=x,
                          solution_steps=kept, envelope=env, timings=ch.timings())
+
+    def transient_gradient(self, wave_cotangents, probes=None, adjoints=False):
+        """The gradient of a scalar loss L of the probe waveforms of the last transient(..., record=True), by the adjoint
+        method on the device (nodal_transient_gradient): the same time stepping run backwards with the transposed
+        matrix, on the hierarchy or factors the forward run left -- about the cost of one more transient run.
+
+        `wave_cotangents` [steps+1, P] = dL / d waveforms; `probes` as transient() takes them, None: those of the
+        recorded call.  Returns a TransientGradient (transient_gradient.py): `values` [ncomp] in the order of
+        `netlist.component_keys` -- with the DC start (initial=None) the derivative through that start is included,
+        by Circuit.gradient of dL/dx_0 -- `capacitors` [C] = dL/dC, `source_values` (name -> [steps]), `initial` [K+B] =
+        dL/dx_0, `info`, `scaled_residual`, `timings`, and with adjoints=True `adjoints` [steps, K+B].  ValueError without
+        a recorded transient (none yet, a later transient() without record, or set_values() since), for cotangents of
+        another shape or that are not finite.  Singular networks behave as in gradient().  A second call with other
+        cotangents repeats no matrix work; the circuit, the record and the next transient() are left as they were."""
+        from .ports import _as_pair, resolve_ports
+        from .transient_gradient import TransientGradient, check_transient_gradient_arguments
+        rec = self._transient_record
+        pa, pb = ((), ()) if rec is None else (rec.pa, rec.pb)
+        if rec is not None and probes is not None:
+            pa, pb = resolve_ports(self.netlist, [_as_pair(self.netlist, port) for port in probes])
+        cot = check_transient_gradient_arguments(rec, wave_cotangents, len(pa))  # (raises without a record)
+        ch = rec.child._handle
+        try:
+            grad, gsrc, gx0, lam, resid, info = ch.transient_gradient(rec.steps, rec.nsrc, pa, pb, cot,
+                                                                      dense=not self.sparse, adjoints=adjoints)
+        except _ffi.NodalHipError as exc:
+            if exc.status == _ffi.E_INVALID and "no recorded transient" in str(exc):
+                from .transient_gradient import NO_RECORD
+                raise ValueError(NO_RECORD) from None
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            if not is_connected(self.netlist):
+                logging.error("Model error: unconnected circuit")
+                raise UnconnectedCircuitError
+            logging.error("Model error: matrix is singular")
+            raise np.linalg.LinAlgError("Singular matrix")
+        timings = ch.timings()
+        if (info > 0).any():
+            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        ncomp = self.table.ncomp
+        values = grad[:ncomp].copy()
+        capacitors = -(rec.dt / rec.farads ** 2) * grad[rec.cap_rows]  # (the companion value is dt / C)
+        start = np.zeros(ncomp)
+        if rec.dc_start:  # x_0 = G^-1 A of this circuit: dL/dx_0 goes on through the single solve's adjoint
+            start = np.array(self.gradient(gx0, solutions=rec.x0).values, dtype=np.float64)
+            values += start
+        by_name = {name: gsrc[:, cols].sum(axis=1) for name, cols in rec.columns.items()}
+        return TransientGradient(values, capacitors, by_name, gx0, info, resid, adjoints=lam, timings=timings,
+                                 start_values=start)
 
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last

@@ -267,6 +267,8 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->pt_buf,
                       &h->gr_cot, &h->gr_x, &h->gr_spec, &h->gr_acc,
                       &h->tr_spec, &h->tr_none, &h->tr_node, &h->tr_ptr, &h->tr_con, &h->tr_vec, &h->tr_out, &h->tr_ring,
+                      &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
+                      &h->tg_con,
                       &h->dbg_resid, &h->dbg_apply};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
@@ -884,6 +886,7 @@ int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method
     DeviceGuard g(h);
     if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
     nodal_poison_scratch(h);
+    h->tape_valid = false;  // (whatever an earlier call recorded: this one replaces it, if it records)
     NODAL_TRY(sweep_prepare(h, steps, nsrc, src_rows, src_values));
     h->amg_levels = 0;
     h->last_batch_block = false;
@@ -892,6 +895,30 @@ int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method
     const int s = transient_run(h, dense != 0, steps, method, ncap, cap_rows, nsrc, x0, nprobe, probe_a, probe_b, wave_out,
                                 keep_every, x_out, pot_min, pot_min_step, pot_max, pot_max_step, resid_out, info_out,
                                 iters_out, &ms_matrix);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = ms_matrix;
+    h->ms[1] = 0.0;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
+int nodal_transient_gradient(nodal_handle h, int32_t dense, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
+                             const double *wave_cot, double *grad_out, double *grad_sources_out, double *grad_x0_out,
+                             double *adjoint_out, double *resid_out, int32_t *info_out) {
+    if (!h || nprobe < 0 || (nprobe > 0 && (!probe_a || !probe_b || !wave_cot))) return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "transient gradient: no component table on the handle");
+    if (!h->have_numeric || !h->tape_valid || h->tape_epoch != h->numeric_epoch)
+        return nodal_fail(h, NODAL_E_INVALID, "transient gradient: no recorded transient on the handle");
+    if ((h->ncomp > 0 && !grad_out) || (h->tape_steps > 0 && !info_out))
+        return nodal_fail(h, NODAL_E_INVALID, "transient gradient: no array for the result");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_matrix = 0.0;
+    const int s = tgrad_run(h, dense != 0, nprobe, probe_a, probe_b, wave_cot, grad_out, grad_sources_out, grad_x0_out,
+                            adjoint_out, resid_out, info_out, &ms_matrix);
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_matrix;
@@ -1012,6 +1039,10 @@ int nodal_set_option(nodal_handle h, int32_t option, int32_t value) {
     }
     if (option == NODAL_OPT_BORROW_TABLE) {
         h->borrow_table = value != 0;
+        return NODAL_OK;
+    }
+    if (option == NODAL_OPT_TRANSIENT_TAPE) {
+        h->transient_tape = value != 0;
         return NODAL_OK;
     }
     return nodal_fail(h, NODAL_E_INVALID, "unknown option");

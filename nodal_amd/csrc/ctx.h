@@ -215,6 +215,21 @@ struct nodal_ctx {
     uint64_t numeric_epoch = 1;   // bumped by every numeric assembly (stamp_numeric): the identity of G's values
     uint64_t tr_mg_epoch = 0;     // numeric_epoch the multigrid hierarchy a transient call set up belongs to (0: none)
     uint64_t tr_lu_epoch = 0;     // ... and the sparse LU factors a transient call left
+    // gradients through time (transient_gradient.hip).  NODAL_OPT_TRANSIENT_TAPE: a backward-Euler nodal_transient whose
+    // every step was solved leaves x_0 .. x_steps ([steps + 1][n]) and its swept rows on the handle; the capacitor rows
+    // and node lists stay where they are (tr_spec, tr_node, tr_ptr, tr_con).  The tape belongs to one numeric_epoch and
+    // is void after an upload and after any later nodal_transient.
+    bool transient_tape = false;
+    bool tape_valid = false;
+    uint64_t tape_epoch = 0;
+    int32_t tape_steps = 0, tape_nsrc = 0;
+    int64_t tape_ncap = 0, tape_nent = 0;  // capacitors, and the entries of their node list
+    DevBuf tr_tape, tr_tsrc;
+    // the backward sweep's own buffers: sixteen adjoints [16][n], the one before them, right-hand side, refinement
+    // vectors, norms, the capacitors' history words, the sums and what else goes down once; the probes and cotangents;
+    // the node -> incident-probe lists (as tr_none .. tr_con)
+    DevBuf tg_vec, tg_out, tg_spec, tg_none, tg_node, tg_ptr, tg_con;
+    uint64_t tg_lu_epoch = 0;     // numeric_epoch the sparse LU factors of the transposed child belong to (0: none)
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
@@ -492,6 +507,13 @@ int sens_transposed_child(nodal_ctx *h);
 int grad_run(nodal_ctx *h, bool dense, int32_t count, const double *x, const double *cotangent, int32_t nsrc,
              const int64_t *rows, double *grad_out, double *grad_sources_out, double *adjoint_out, double *resid_out,
              int32_t *info_out);
+// the table kernels of one block of `cols` (<= 16) members, element (j, y) of lam at [j * rs + y * cs] and of x at
+// [j * xrs + y * xcs] (strides may be negative): k_gradient_block and k_gradient_cross add the members' terms, in member
+// order, onto grad_dev [ncomp] (sens_cross_list first); k_gradient_sources writes out[y * nsrc + j] for the swept rows
+int grad_launch_table(nodal_ctx *h, int cols, const double *lam, int64_t rs, int64_t cs, const double *x, int64_t xrs,
+                      int64_t xcs, double *grad_dev);
+int grad_launch_sources(nodal_ctx *h, int cols, int32_t nsrc, const int32_t *swept_dev, const double *lam, int64_t rs,
+                        int64_t cs, double *out);
 
 // ---- transient analysis (transient.hip): capacitors stepped in time, one solve per step on the kept matrix work ----
 // the arguments are those of nodal_transient; the source table is already on the device (sw_slot, sw_vals: api.hip's
@@ -501,6 +523,38 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
                   double *wave_out, int32_t keep_every, double *x_out, double *pot_min, int32_t *pot_min_step,
                   double *pot_max, int32_t *pot_max_step, double *resid_out, int32_t *info_out, int32_t *iters_out,
                   double *ms_matrix);
+// One step's solve, shared by the forward steps and the backward sweep of transient_gradient.hip.  s: the context whose
+// matrix is solved -- h itself, or the csr_only child that holds G^T (never the multigrid route); lu_epoch: where the
+// numeric_epoch of s's kept LU factors is filed; rvec, dvec [n] and norms ([16][4] + [16]) are the caller's scratch.
+enum { TR_ROUTE_DENSE, TR_ROUTE_LU, TR_ROUTE_MG };
+struct TransientSolver {
+    nodal_ctx *s = nullptr;
+    uint64_t *lu_epoch = nullptr;
+    double *rvec = nullptr, *dvec = nullptr, *norms = nullptr;
+    int route = TR_ROUTE_DENSE;
+    bool direct = false;      // multigrid route: the iteration gave up, this step and every later one by the direct solve
+    bool all_direct = false;  // sparse LU route: pivots were replaced, every step by the direct solve (which judges its own)
+    bool mg_setup = false, first = true;
+    double bar = 0.0;
+};
+// the route and its matrix work (the dense panel's room, the factorisation unless kept, whether the hierarchy is to be
+// set up); *dead: a singular factorisation without `dense`; ms_matrix as transient_run's
+int transient_solver_begin(nodal_ctx *h, TransientSolver &ts, bool dense, int32_t steps, bool *dead, double *ms_matrix);
+// xk from bvec: dense panel, multigrid, or sparse LU with one refinement step, with their fall-backs to the sparse direct
+// solve, and the judgement -- *judged: the scaled residual is in *resid_host already, otherwise at norms[4 * 16] on the
+// device.  *inf > 0: singular, nothing was judged.
+int transient_solver_step(nodal_ctx *h, TransientSolver &ts, const double *bvec, double *xk, int32_t *inf, int32_t *it,
+                          double *resid_host, bool *judged, double *ms_matrix);
+// rhs += S (g o S^T x_prev), the capacitors' history currents (k_transient_history with `method`, then k_transient_rhs
+// over the node list of the last transient_run: tr_node, tr_ptr, tr_con); hist [ncap] is scratch
+int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t *rows_dev, int64_t nent, const double *x_prev,
+                          double *hist, double *rhs);
+
+// ---- gradients through time (transient_gradient.hip): the adjoint of the recorded backward-Euler run ----
+// the arguments are those of nodal_transient_gradient; ms_matrix as transient_run's
+int tgrad_run(nodal_ctx *h, bool dense, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
+              const double *wave_cot, double *grad_out, double *grad_sources_out, double *grad_x0_out, double *adjoint_out,
+              double *resid_out, int32_t *info_out, double *ms_matrix);
 
 // ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])

@@ -256,23 +256,9 @@ struct GradientClient final : MultiRhsClient {
                 xrs = SCOLS;
                 xcs = 1;
             }
-            const double *value = assembled_values(h);
-            auto launch = il ? k_gradient_block<true> : k_gradient_block<false>;
-            launch<<<(unsigned)groups_of(ncomp), STB, 0, st>>>(ncomp, h->K, cols, h->type.as<uint8_t>(), value,
-                                                              h->a.as<int32_t>(), h->b.as<int32_t>(), h->c.as<int32_t>(),
-                                                              h->d.as<int32_t>(), h->drv.as<int32_t>(), h->k.as<int32_t>(),
-                                                              lam, rs, cs, x, xrs, xcs, grad_dev);
-            if (h->sn_ncross > 0) {
-                const int32_t *drivers = h->sn_cross.as<int32_t>(), *gptr = drivers + h->sn_ndrivers,
-                              *grows = gptr + h->sn_ndrivers + 1;
-                k_gradient_cross<<<(unsigned)groups_of(h->sn_ndrivers), STB, 0, st>>>(
-                    h->sn_ndrivers, h->K, cols, drivers, gptr, grows, h->type.as<uint8_t>(), value, h->c.as<int32_t>(),
-                    h->d.as<int32_t>(), h->k.as<int32_t>(), lam, rs, cs, x, xrs, xcs, grad_dev);
-            }
+            NODAL_TRY(grad_launch_table(h, cols, lam, rs, cs, x, xrs, xcs, grad_dev));
             if (nsrc > 0 && gsrc_out) {
-                k_gradient_sources<<<(unsigned)groups_of((int64_t)cols * nsrc), STB, 0, st>>>(
-                    cols, nsrc, h->K, swept_dev, h->type.as<uint8_t>(), h->a.as<int32_t>(), h->b.as<int32_t>(),
-                    h->k.as<int32_t>(), lam, rs, cs, gsrc_dev);
+                NODAL_TRY(grad_launch_sources(h, cols, nsrc, swept_dev, lam, rs, cs, gsrc_dev));
                 NODAL_HIP_TRY(h, hipMemcpyAsync(gsrc_out + (int64_t)m0 * nsrc, gsrc_dev, (size_t)cols * nsrc * 8,
                                                 hipMemcpyDeviceToHost, st));
             }
@@ -291,6 +277,37 @@ struct GradientClient final : MultiRhsClient {
 };
 
 }  // namespace
+
+int grad_launch_table(nodal_ctx *h, int cols, const double *lam, int64_t rs, int64_t cs, const double *x, int64_t xrs,
+                      int64_t xcs, double *grad_dev) {
+    const int64_t ncomp = h->ncomp;
+    hipStream_t st = h->stream;
+    const bool il = rs == SCOLS && cs == 1;
+    const double *value = assembled_values(h);
+    auto launch = il ? k_gradient_block<true> : k_gradient_block<false>;
+    launch<<<(unsigned)groups_of(ncomp), STB, 0, st>>>(ncomp, h->K, cols, h->type.as<uint8_t>(), value, h->a.as<int32_t>(),
+                                                      h->b.as<int32_t>(), h->c.as<int32_t>(), h->d.as<int32_t>(),
+                                                      h->drv.as<int32_t>(), h->k.as<int32_t>(), lam, rs, cs, x, xrs, xcs,
+                                                      grad_dev);
+    if (h->sn_ncross > 0) {
+        const int32_t *drivers = h->sn_cross.as<int32_t>(), *gptr = drivers + h->sn_ndrivers,
+                      *grows = gptr + h->sn_ndrivers + 1;
+        k_gradient_cross<<<(unsigned)groups_of(h->sn_ndrivers), STB, 0, st>>>(
+            h->sn_ndrivers, h->K, cols, drivers, gptr, grows, h->type.as<uint8_t>(), value, h->c.as<int32_t>(),
+            h->d.as<int32_t>(), h->k.as<int32_t>(), lam, rs, cs, x, xrs, xcs, grad_dev);
+    }
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+int grad_launch_sources(nodal_ctx *h, int cols, int32_t nsrc, const int32_t *swept_dev, const double *lam, int64_t rs,
+                        int64_t cs, double *out) {
+    k_gradient_sources<<<(unsigned)groups_of((int64_t)cols * nsrc), STB, 0, h->stream>>>(
+        cols, nsrc, h->K, swept_dev, h->type.as<uint8_t>(), h->a.as<int32_t>(), h->b.as<int32_t>(), h->k.as<int32_t>(), lam,
+        rs, cs, out);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
 
 int grad_run(nodal_ctx *h, bool dense, int32_t count, const double *x, const double *cotangent, int32_t nsrc,
              const int64_t *rows, double *grad_out, double *grad_sources_out, double *adjoint_out, double *resid_out,

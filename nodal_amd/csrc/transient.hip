@@ -19,6 +19,10 @@
 //     k_transient_envelope  per node compare-and-update with the step index (when asked for)
 // and every keep_every-th step one device-to-device copy into a staging ring.  Waveforms, envelope and residuals come
 // down once, after the last step.
+//
+// The solve and its matrix work are transient_solver_begin / transient_solver_step: transient_gradient.hip runs the same
+// steps backwards, on this handle or on the child that holds G^T.  With NODAL_OPT_TRANSIENT_TAPE a backward-Euler run
+// writes x_k into row k of tr_tape instead of the two alternating vectors and leaves the tape for that sweep.
 #include "group.h"
 
 #include <chrono>
@@ -133,13 +137,124 @@ __global__ __launch_bounds__(TTB) void k_transient_correct(int64_t n, const doub
     if (i < n) x[i] += d[i];
 }
 
-enum Route { ROUTE_DENSE, ROUTE_LU, ROUTE_MG };
-
 double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace
+
+int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t *rows_dev, int64_t nent, const double *x_prev,
+                          double *hist, double *rhs) {
+    hipStream_t st = h->stream;
+    k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, method, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(),
+                                                        assembled_values(h), x_prev, hist);
+    if (nent > 0)
+        k_transient_rhs<<<groups_of(nent), TTB, 0, st>>>(nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(),
+                                                        h->tr_con.as<uint32_t>(), hist, rhs);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+int transient_solver_begin(nodal_ctx *h, TransientSolver &ts, bool dense, int32_t steps, bool *dead, double *ms_matrix) {
+    nodal_ctx *s = ts.s;
+    const int64_t n = h->n;
+    hipStream_t st = h->stream;  // (s shares it: one ordered timeline)
+    const bool passive = s == h && h->B == 0 && h->passive_network;  // (a child holds G^T of a network that is not)
+    const int64_t multigrid_min = 4096;  // multi_rhs_solve's bound for passive systems
+    ts.route = n <= 64 ? TR_ROUTE_DENSE : (passive && n > multigrid_min) ? TR_ROUTE_MG : TR_ROUTE_LU;
+    ts.direct = ts.all_direct = ts.mg_setup = false;
+    ts.first = true;
+    ts.bar = knob::MULTI_BAR.now();
+    if (ts.route == TR_ROUTE_DENSE) {
+        NODAL_HIP_TRY(h, s->dense.reserve((size_t)dense_lda(n) * (size_t)(n + 1) * 8 + 64));
+    } else if (ts.route == TR_ROUTE_LU && steps > 0) {
+        if (*ts.lu_epoch != h->numeric_epoch || nodal_poison_level() >= 2) {  // (NODAL_POISON=2 poisons the factors)
+            const auto t0 = std::chrono::steady_clock::now();
+            int32_t inf = 0;
+            NODAL_TRY(nodal_lift_error(h, s, slu_factor(s, &inf)));
+            NODAL_WAIT_STREAM(h, st);
+            *ms_matrix = ms_since(t0);
+            if (inf > 0) {
+                if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+                *dead = true;
+            } else {
+                *ts.lu_epoch = h->numeric_epoch;
+            }
+        }
+        ts.all_direct = !*dead && slu_perturbed(s) > 0;
+    } else if (ts.route == TR_ROUTE_MG) {
+        ts.mg_setup = !(h->tr_mg_epoch == h->numeric_epoch && sagg_ready(h, n)) || nodal_poison_level() >= 2;
+    }
+    return NODAL_OK;
+}
+
+int transient_solver_step(nodal_ctx *h, TransientSolver &ts, const double *bvec, double *xk, int32_t *inf_out,
+                          int32_t *it_out, double *resid_host, bool *judged_out, double *ms_matrix) {
+    nodal_ctx *s = ts.s;
+    const int64_t n = h->n, lda = dense_lda(n);
+    hipStream_t st = h->stream;
+    int32_t inf = 0, it = 0;
+    double rs = 0.0;
+    bool judged = false;  // *resid_host is written already
+    if (ts.route == TR_ROUTE_DENSE) {
+        // (the tiny matrix is factored anew: a panel launch)
+        if (s->csr_only) NODAL_TRY(nodal_lift_error(h, s, csr_to_dense(s, s->dense.as<double>(), lda)));
+        else NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(s->dense.as<double>() + n * lda, bvec, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+        NODAL_TRY(nodal_lift_error(h, s, dense_factor_solve_multi(s, 1, xk, n, &inf)));
+    } else if (ts.route == TR_ROUTE_MG) {  // (s == h)
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool setup = ts.first && ts.mg_setup;
+        if (!ts.direct) {
+            const int sv = amg_fcg_solve_rhs(h, bvec, setup, &inf, &it, &rs);  // (writes h->x)
+            if (sv == -2) {
+                inf = 1;  // a floating island: every step is singular
+            } else if (sv == NODAL_OK) {
+                NODAL_HIP_TRY(h, hipMemcpyAsync(xk, h->x.as<double>(), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+                if (setup) h->tr_mg_epoch = h->numeric_epoch;
+            } else if (sv < 0) {
+                ts.direct = true;
+                h->tr_mg_epoch = 0;  // (the hierarchy was given up and invalidated)
+            } else {
+                return sv;
+            }
+        }
+        if (ts.direct) NODAL_TRY(sparse_direct_solve(h, bvec, xk, &inf, &it, &rs));
+        if (setup) *ms_matrix = ms_since(t0);
+    } else {
+        bool redo = ts.all_direct;
+        if (!ts.all_direct) {
+            NODAL_TRY(nodal_lift_error(h, s, slu_apply(s, bvec, xk)));
+            k_transient_defect<<<groups_of(n), TTB, 0, st>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(),
+                                                            s->data.as<double>(), xk, bvec, ts.rvec);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            NODAL_TRY(nodal_lift_error(h, s, slu_apply(s, ts.rvec, ts.dvec)));
+            k_transient_correct<<<groups_of(n), TTB, 0, st>>>(n, ts.dvec, xk);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            NODAL_TRY(nodal_lift_error(h, s, csr_judge_block(s, xk, bvec, 1, 0, 1, ts.norms)));
+            NODAL_TRY(nodal_read_words(h, resid_host, ts.norms + 4 * SLU_MULTI, 8));
+            judged = true;
+            it = 1;
+            redo = !(*resid_host <= ts.bar);
+        }
+        if (redo) {
+            judged = false;
+            NODAL_TRY(nodal_lift_error(h, s, sparse_direct_solve(s, bvec, xk, &inf, &it, &rs)));
+            if (!ts.all_direct && inf == 0) {  // (the direct solve may have factored anew, with another pivot bar)
+                int32_t inf2 = 0;
+                NODAL_TRY(nodal_lift_error(h, s, slu_factor(s, &inf2)));
+                ts.all_direct = inf2 > 0 || slu_perturbed(s) > 0;
+                if (ts.all_direct) *ts.lu_epoch = 0;
+            }
+        }
+    }
+    ts.first = false;
+    *inf_out = inf;
+    *it_out = it;
+    *judged_out = judged;
+    if (inf == 0 && !judged) NODAL_TRY(nodal_lift_error(h, s, csr_judge_block(s, xk, bvec, 1, 0, 1, ts.norms)));
+    return NODAL_OK;
+}
 
 int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
                   int32_t nsrc, const double *x0, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
@@ -163,9 +278,20 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     }
     h->have_x = false;
     h->last_iterations = 0;
+    // NODAL_OPT_TRANSIENT_TAPE: the states stay on the handle for nodal_transient_gradient (backward Euler only)
+    const bool record = h->transient_tape && method == 0;
+    auto keep_tape = [&](int64_t nent_caps) {
+        h->tape_valid = true;
+        h->tape_epoch = h->numeric_epoch;
+        h->tape_steps = steps;
+        h->tape_nsrc = nsrc;
+        h->tape_ncap = ncap;
+        h->tape_nent = nent_caps;
+    };
     if (n == 0) {  // (every lead is ground: nothing moves)
         if (wave_out)
             for (int64_t t = 0; t < (int64_t)(steps + 1) * nprobe; ++t) wave_out[t] = 0.0;
+        if (record) keep_tape(0);
         return NODAL_OK;
     }
 
@@ -204,6 +330,17 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     NODAL_HIP_TRY(h, h->tr_vec.reserve((size_t)5 * n * 8 + 5 * SLU_MULTI * 8 + 256));
     double *xv[2] = {h->tr_vec.as<double>(), h->tr_vec.as<double>() + n};
     double *bvec = xv[1] + n, *rvec = bvec + n, *dvec = rvec + n, *norms = dvec + n;
+    // recording: x_k is written straight into row k of the tape instead (the same kernels, other addresses), and the
+    // swept rows are set aside beside it (sw_rows is the next sweep's)
+    double *tape = nullptr;
+    if (record) {
+        NODAL_HIP_TRY(h, h->tr_tape.reserve((size_t)(steps + 1) * n * 8 + 64));
+        tape = h->tr_tape.as<double>();
+        NODAL_HIP_TRY(h, h->tr_tsrc.reserve((size_t)(nsrc + 16) * 4));
+        if (nsrc > 0)
+            NODAL_HIP_TRY(h, hipMemcpyAsync(h->tr_tsrc.p, h->sw_rows.p, (size_t)nsrc * 4, hipMemcpyDeviceToDevice, st));
+    }
+    auto state = [&](int32_t k) { return tape ? tape + (int64_t)k * n : xv[k & 1]; };
     // tr_out: waveforms [steps + 1][nprobe] | residuals [steps] | envelope min, max [K] each | their steps [K] each
     const size_t wave_words = (size_t)(steps + 1) * nprobe, env_words = want_env ? (size_t)K : 0;
     NODAL_HIP_TRY(h, h->tr_out.reserve((wave_words + (size_t)steps + 3 * env_words + 2) * 8 + 64));
@@ -216,49 +353,28 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         NODAL_HIP_TRY(h, h->tr_ring.reserve((size_t)std::min<int32_t>(RING, nkeep) * n * 8 + 64));
         ring = h->tr_ring.as<double>();
     }
-    NODAL_HIP_TRY(h, hipMemcpyAsync(xv[0], x0, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(state(0), x0, (size_t)n * 8, hipMemcpyHostToDevice, st));
     if (nprobe > 0) {
-        k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, xv[0], wave_dev);
+        k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, state(0), wave_dev);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
     const double *value = assembled_values(h);
     if (ncap > 0 && method == 1) {  // J_0 = g v_0
         k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, 0, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), value,
-                                                            xv[0], hist);
+                                                            state(0), hist);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
     NODAL_WAIT_STREAM(h, st);  // (x0 and the probes are the caller's, r32 ends here)
 
     // ---- the route and its matrix work ----
-    const bool passive = h->B == 0 && h->passive_network;
-    const int64_t multigrid_min = 4096;  // multi_rhs_solve's bound for passive systems
-    const Route route = n <= 64 ? ROUTE_DENSE : (passive && n > multigrid_min) ? ROUTE_MG : ROUTE_LU;
-    const int64_t lda = dense_lda(n);
-    bool direct = false;      // multigrid route: the iteration gave up, this step and every later one by the direct solve
-    bool all_direct = false;  // sparse LU route: pivots were replaced, every step by the direct solve (which judges its own)
-    bool mg_setup = false;
+    TransientSolver ts;
+    ts.s = h;
+    ts.lu_epoch = &h->tr_lu_epoch;
+    ts.rvec = rvec;
+    ts.dvec = dvec;
+    ts.norms = norms;
     bool dead = steps == 0;   // a singular verdict: no step from there on has a state to start from
-    const double bar = knob::MULTI_BAR.now();
-    if (route == ROUTE_DENSE) {
-        NODAL_HIP_TRY(h, h->dense.reserve((size_t)lda * (size_t)(n + 1) * 8 + 64));
-    } else if (route == ROUTE_LU && steps > 0) {
-        if (h->tr_lu_epoch != h->numeric_epoch || nodal_poison_level() >= 2) {  // (NODAL_POISON=2 poisons the factors)
-            const auto t0 = std::chrono::steady_clock::now();
-            int32_t inf = 0;
-            NODAL_TRY(slu_factor(h, &inf));
-            NODAL_WAIT_STREAM(h, st);
-            *ms_matrix = ms_since(t0);
-            if (inf > 0) {
-                if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
-                dead = true;
-            } else {
-                h->tr_lu_epoch = h->numeric_epoch;
-            }
-        }
-        all_direct = !dead && slu_perturbed(h) > 0;
-    } else if (route == ROUTE_MG) {
-        mg_setup = !(h->tr_mg_epoch == h->numeric_epoch && sagg_ready(h, n)) || nodal_poison_level() >= 2;
-    }
+    NODAL_TRY(transient_solver_begin(h, ts, dense, steps, &dead, ms_matrix));
 
     // ---- the steps ----
     int32_t first_dead = dead ? 1 : steps + 1;
@@ -275,75 +391,17 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         return NODAL_OK;
     };
     for (int32_t k = 1; k <= steps && !dead; ++k) {
-        const double *xp = xv[(k - 1) & 1];
-        double *xk = xv[k & 1];
+        const double *xp = state(k - 1);
+        double *xk = state(k);
         // the right-hand side: the sources in force at t_k, then the capacitors' history currents
         NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)n * 8, st));
         NODAL_TRY(stamp_rhs_multi(h, h->sw_slot.as<int32_t>(), h->sw_vals.as<double>() + (int64_t)(k - 1) * nsrc, nsrc, 1,
                                   bvec, 1, 0));
-        if (ncap > 0) {
-            k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, method, rows_dev, h->a.as<int32_t>(),
-                                                                h->b.as<int32_t>(), value, xp, hist);
-            if (nent > 0)
-                k_transient_rhs<<<groups_of(nent), TTB, 0, st>>>(nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(),
-                                                                h->tr_con.as<uint32_t>(), hist, bvec);
-            NODAL_HIP_TRY(h, hipGetLastError());
-        }
+        if (ncap > 0) NODAL_TRY(transient_add_history(h, ncap, method, rows_dev, nent, xp, hist, bvec));
         // the solve
         int32_t inf = 0, it = 0;
-        double rs = 0.0;
         bool judged = false;  // resid[k - 1] is on the host already
-        if (route == ROUTE_DENSE) {
-            // (the tiny matrix is factored anew: a panel launch)
-            NODAL_TRY(stamp_to_dense(h, h->dense.as<double>(), lda, true));
-            NODAL_HIP_TRY(h, hipMemcpyAsync(h->dense.as<double>() + n * lda, bvec, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-            NODAL_TRY(dense_factor_solve_multi(h, 1, xk, n, &inf));
-        } else if (route == ROUTE_MG) {
-            const auto t0 = std::chrono::steady_clock::now();
-            const bool setup = k == 1 && mg_setup;
-            if (!direct) {
-                const int sv = amg_fcg_solve_rhs(h, bvec, setup, &inf, &it, &rs);  // (writes h->x)
-                if (sv == -2) {
-                    inf = 1;  // a floating island: every step is singular
-                } else if (sv == NODAL_OK) {
-                    NODAL_HIP_TRY(h, hipMemcpyAsync(xk, h->x.as<double>(), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-                    if (setup) h->tr_mg_epoch = h->numeric_epoch;
-                } else if (sv < 0) {
-                    direct = true;
-                    h->tr_mg_epoch = 0;  // (the hierarchy was given up and invalidated)
-                } else {
-                    return sv;
-                }
-            }
-            if (direct) NODAL_TRY(sparse_direct_solve(h, bvec, xk, &inf, &it, &rs));
-            if (setup) *ms_matrix = ms_since(t0);
-        } else {
-            bool redo = all_direct;
-            if (!all_direct) {
-                NODAL_TRY(slu_apply(h, bvec, xk));
-                k_transient_defect<<<groups_of(n), TTB, 0, st>>>(n, h->indptr.as<int32_t>(), h->indices.as<int32_t>(),
-                                                                h->data.as<double>(), xk, bvec, rvec);
-                NODAL_HIP_TRY(h, hipGetLastError());
-                NODAL_TRY(slu_apply(h, rvec, dvec));
-                k_transient_correct<<<groups_of(n), TTB, 0, st>>>(n, dvec, xk);
-                NODAL_HIP_TRY(h, hipGetLastError());
-                NODAL_TRY(csr_judge_block(h, xk, bvec, 1, 0, 1, norms));
-                NODAL_TRY(nodal_read_words(h, &resid[k - 1], norms + 4 * SLU_MULTI, 8));
-                judged = true;
-                it = 1;
-                redo = !(resid[k - 1] <= bar);
-            }
-            if (redo) {
-                judged = false;
-                NODAL_TRY(sparse_direct_solve(h, bvec, xk, &inf, &it, &rs));
-                if (!all_direct && inf == 0) {  // (the direct solve may have factored anew, with another pivot bar)
-                    int32_t inf2 = 0;
-                    NODAL_TRY(slu_factor(h, &inf2));
-                    all_direct = inf2 > 0 || slu_perturbed(h) > 0;
-                    if (all_direct) h->tr_lu_epoch = 0;
-                }
-            }
-        }
+        NODAL_TRY(transient_solver_step(h, ts, bvec, xk, &inf, &it, &resid[k - 1], &judged, ms_matrix));
         if (inf > 0) {
             if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
             dead = true;
@@ -353,10 +411,8 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         iters[k - 1] = it;
         h->last_iterations = it;
         on_host[(size_t)k - 1] = judged;
-        if (!judged) {
-            NODAL_TRY(csr_judge_block(h, xk, bvec, 1, 0, 1, norms));
+        if (!judged)
             NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + (k - 1), norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
-        }
         // what the caller asked for of x_k
         if (nprobe > 0) k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, xk, wave_dev + (size_t)k * nprobe);
         if (want_env && K > 0) {
@@ -396,5 +452,6 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         if (nkeep > 0 && k % keep_every == 0)
             for (int64_t i = 0; i < n; ++i) x_out[(int64_t)(k / keep_every - 1) * n + i] = nan;
     }
+    if (record && first_dead == steps + 1) keep_tape(nent);
     return NODAL_OK;
 }
