@@ -272,6 +272,31 @@ int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method
                     double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
                     int32_t *info_out, int32_t *iters_out);
 
+/* ---- transient analysis with inductors: RLC networks (nodal_transient is this call with nind == 0: the same launches at
+ *      the same sizes, the same bits) ----
+ * nodal_transient's arguments and rules, plus: the handle's table holds one more R row per inductor, ind_rows [nind]
+ * (type R, checked on the device as cap_rows are): the companion resistor of an inductor L stepped with h, value L / h
+ * for backward Euler and 2 L / h for the trapezoidal rule, g = 1 / value.  The inductor's current i counts positive from
+ * lead a to lead b through the element; i0 [nind] is the state at t_0 (NULL: zero).  With v = x(a) - x(b):
+ *   method 0:  i_k = i_{k-1} + g v_k,              J_k = -i_{k-1}
+ *   method 1:  i_k = i_{k-1} + g (v_k + v_{k-1}),  J_k = -(i_{k-1} + g v_{k-1})
+ * J_k injected into lead a and drawn from lead b like a capacitor's; in both methods i_k = -J_k + g v_k, formed by one
+ * lane per inductor after the solve of step k.  A node's history currents are summed over its capacitors and then its
+ * inductors, each in ascending order.
+ *   cur_out [steps + 1][ncur]     i_k of the inductors cur_index [ncur] (indices into ind_rows), row 0 = i0
+ *   i_final_out [nind]            every inductor's current after the last step
+ * Each may be NULL.  A step without a state (info_out > 0) has NaN in its cur_out row, and any such step leaves NaN in
+ * i_final_out.  With NODAL_OPT_TRANSIENT_TAPE set and nind > 0 NO tape is kept (the adjoint with inductors is not
+ * implemented): a nodal_transient_gradient afterwards finds no recorded transient.
+ * NODAL_E_INVALID, besides nodal_transient's: an ind_rows entry out of range or not of type R, a cur_index entry outside
+ * [0, nind), inductors on a network without nodes.  The currents come down once, with the waveforms. */
+int nodal_transient_rlc(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                        int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                        const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                        double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                        int32_t *info_out, int32_t *iters_out, int64_t nind, const int64_t *ind_rows, const double *i0,
+                        int32_t ncur, const int32_t *cur_index, double *cur_out, double *i_final_out);
+
 /* ---- gradients through time (replaces finite differences over whole transient runs: two nodal_transient calls per
  *      component; with the reference each of them a host loop of rebuild and solve, reference nodal/nodal.py:306-336) ----
  * The adjoint of the backward-Euler run the handle has RECORDED: with NODAL_OPT_TRANSIENT_TAPE set, a nodal_transient call

@@ -59,6 +59,9 @@ SIGNATURES = {
     "nodal_transient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
                                   _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p, _i32p,
                                   _f64p, _i32p, _i32p]),
+    "nodal_transient_rlc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
+                                      _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p, _i32p,
+                                      _f64p, _i32p, _i32p, C.c_int64, _i64p, _f64p, C.c_int32, _i32p, _f64p, _f64p]),
     "nodal_transient_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
                                            _f64p, _i32p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
@@ -410,6 +413,17 @@ class Handle:
         the probes' node indices.  Returns (waveforms [steps + 1, P], solutions [steps // keep_every, n] or None,
         envelope dict or None, scaled residual [steps], info [steps], iterations [steps]); NodalHipError(E_INVALID) as
         the header lists, with dense a singular G raises NodalHipError(E_SINGULAR)."""
+        return self._transient(cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope)[:6]
+
+    def transient_rlc(self, cap_rows, ind_rows, rows, values, x0, i0, ia, ib, cur_index, dense, method=0, keep_every=0,
+                      envelope=False):
+        """transient() with inductors (nodal_transient_rlc): ind_rows their companion rows, i0 [L] their currents at t_0,
+        cur_index [Q] the inductors whose currents are wanted.  Returns transient()'s six and (currents [steps + 1, Q],
+        final currents [L])."""
+        return self._transient(cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope,
+                               inductors=(ind_rows, i0, cur_index))
+
+    def _transient(self, cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope, inductors=None):
         cap_rows = np.ascontiguousarray(cap_rows, dtype=np.int64)
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         values = np.ascontiguousarray(values, dtype=np.float64)
@@ -431,13 +445,25 @@ class Handle:
         info = np.zeros(steps, dtype=np.int32)
         iters = np.zeros(steps, dtype=np.int32)
         env_ptrs = [_ptr(env[key], C.c_int32 if key.endswith("step") else C.c_double) for key in env] if env else [None] * 4
-        self._check(self.lib.nodal_transient(
-            self._h, int(dense), steps, int(method), len(cap_rows), _ptr(cap_rows, C.c_int64) if len(cap_rows) else None,
-            len(rows), _ptr(rows, C.c_int64) if len(rows) else None, _ptr(values, C.c_double) if values.size else None,
-            _ptr(x0, C.c_double), len(ia), _ptr(ia, C.c_int32) if len(ia) else None, _ptr(ib, C.c_int32) if len(ib) else None,
-            _ptr(wave, C.c_double), int(keep_every), _ptr(x, C.c_double) if x is not None and kept else None, *env_ptrs,
-            _ptr(resid, C.c_double), _ptr(info, C.c_int32), _ptr(iters, C.c_int32)))
-        return wave, x, env, resid, info, iters
+        args = [self._h, int(dense), steps, int(method), len(cap_rows), _ptr(cap_rows, C.c_int64) if len(cap_rows) else None,
+                len(rows), _ptr(rows, C.c_int64) if len(rows) else None, _ptr(values, C.c_double) if values.size else None,
+                _ptr(x0, C.c_double), len(ia), _ptr(ia, C.c_int32) if len(ia) else None, _ptr(ib, C.c_int32) if len(ib) else None,
+                _ptr(wave, C.c_double), int(keep_every), _ptr(x, C.c_double) if x is not None and kept else None, *env_ptrs,
+                _ptr(resid, C.c_double), _ptr(info, C.c_int32), _ptr(iters, C.c_int32)]
+        if inductors is None:
+            self._check(self.lib.nodal_transient(*args))
+            return wave, x, env, resid, info, iters, None, None
+        ind_rows = np.ascontiguousarray(inductors[0], dtype=np.int64)
+        i0 = np.ascontiguousarray(inductors[1], dtype=np.float64)
+        cur_index = np.ascontiguousarray(inductors[2], dtype=np.int32)
+        assert ind_rows.ndim == 1 and i0.shape == ind_rows.shape and cur_index.ndim == 1
+        cur = np.zeros((steps + 1, len(cur_index)), dtype=np.float64)
+        final = np.zeros(len(ind_rows), dtype=np.float64)
+        self._check(self.lib.nodal_transient_rlc(
+            *args, len(ind_rows), _ptr(ind_rows, C.c_int64) if len(ind_rows) else None,
+            _ptr(i0, C.c_double) if len(i0) else None, len(cur_index), _ptr(cur_index, C.c_int32) if len(cur_index) else None,
+            _ptr(cur, C.c_double) if cur.size else None, _ptr(final, C.c_double) if len(final) else None))
+        return wave, x, env, resid, info, iters, cur, final
 
     def transient_gradient(self, steps, nsrc, ia, ib, cotangents, dense, adjoints=False):
         """The adjoint of the transient run this handle recorded (nodal_transient_gradient; OPT_TRANSIENT_TAPE): steps

@@ -87,6 +87,7 @@ class Circuit:
         self._handle = None
         self._G = self._A = None
         self._transient_child = None
+        self._transient_dc = None
         self._transient_record = None
         self.currents = self.build_model()
 
@@ -100,6 +101,7 @@ class Circuit:
         self._handle = None
         self._G = self._A = None
         self._transient_child = None
+        self._transient_dc = None
         self._transient_record = None
         self.table = other.table if table is None else table
         self.currents = other.currents
@@ -378,6 +380,7 @@ class Circuit:
             raise AssertionError  # the reference's bare `assert G[i, j] == 0`
         self._G = self._A = None
         self._transient_child = None  # (its matrix carried the old values)
+        self._transient_dc = None
         self._transient_record = None
         self.table = table.with_values(new)
 
@@ -416,7 +419,7 @@ class Circuit:
         return PortEquivalent(self.netlist, ports, z, v_oc, info, resid)
 
     def transient(self, capacitors, dt, steps, sources=None, probes=(), method="euler", initial=None, keep_every=0,
-                  envelope=False, record=False):
+                  envelope=False, record=False, inductors=(), initial_currents=None, current_probes=()):
         """Step the circuit with capacitors through `steps` time steps of length `dt` on the device (nodal_transient).
 
         `capacitors` is a sequence of (name, farads, node_a, node_b) on nodes of the netlist; `sources` maps names of
@@ -437,11 +440,22 @@ class Circuit:
         with the same key -- other sources, probes or steps -- repeats no analysis, hierarchy setup or factorisation.
         Singular networks behave as in solve_sources(): the dense path raises LinAlgError / UnconnectedCircuitError,
         the sparse path returns NaN steps with info > 0 and warns once.  The circuit itself -- its solution, table,
-        G, A -- is left as it was."""
+        G, A -- is left as it was.
+
+        `inductors` is a sequence of (name, henries, node_a, node_b) on nodes of the netlist (nodal_transient_rlc); an
+        inductor's current counts positive from node_a to node_b through it.  With inductors initial=None starts from
+        the DC operating point in which every inductor is a short: the netlist with one zero-volt `E` row per inductor,
+        solved once on a third device context kept on the circuit, keyed by the inductors' leads, until set_values().
+        The circuit's own solve() is neither needed nor touched then.  With `initial`, `initial_currents` [L] are the
+        inductors' currents at t_0 (None: zero; ValueError without `initial`).  `current_probes` names inductors whose
+        currents are returned as `currents` [steps+1, Q]; `final_currents` [L] is the state after the last step, so
+        that a run continues from `solutions[-1]` and `final_currents`.  ValueError for a loop of inductors alone
+        (the DC start would be singular) and for record=True with inductors (their adjoint is not implemented); a DC
+        start that is singular together with other components behaves as a singular solve()."""
         from .ports import _as_pair, resolve_ports
         from .sweep import resolve_sources
-        from .transient import (METHODS, Transient, TransientEnvelope, check_transient_arguments, companion_table,
-                                resolve_capacitors)
+        from .transient import (METHODS, Transient, TransientEnvelope, check_inductor_arguments, check_transient_arguments,
+                                companion_table, resolve_capacitors, resolve_inductors)
         h = self._handle
         self._transient_record = None  # (whatever an earlier call recorded: the device drops it as well)
         dt, steps, code, x0 = check_transient_arguments(dt, steps, method, initial, h.n)
@@ -451,6 +465,10 @@ class Circuit:
         if keep_every < 0:
             raise ValueError(f"keep_every must not be negative, not {keep_every}")
         names, farads, ca, cb = resolve_capacitors(self.netlist, capacitors)
+        lnames, henries, la, lb = resolve_inductors(self.netlist, inductors)
+        i0, cur_index = check_inductor_arguments(lnames, initial, initial_currents, current_probes)
+        if record and len(lnames):
+            raise ValueError("record=True with inductors: the adjoint of a run with inductors is not implemented")
         rows, values = resolve_sources(self.netlist, sources if sources is not None else {})
         if len(rows) and values.shape[0] != steps:
             raise ValueError(f"Source waveforms must have {steps} values (one per step), not {values.shape[0]}")
@@ -458,7 +476,10 @@ class Circuit:
             values = np.zeros((steps, 0), dtype=np.float64)
         probes = [_as_pair(self.netlist, port) for port in probes]
         pa, pb = resolve_ports(self.netlist, probes)
-        if x0 is None:
+        dc_singular = False
+        if x0 is None and len(lnames):
+            x0, i0, dc_singular = self._transient_dc_start(la, lb)
+        elif x0 is None:
             try:
                 x0 = h.download_x()
             except _ffi.NodalHipError as exc:
@@ -466,17 +487,38 @@ class Circuit:
                     raise
                 raise ValueError("no solution: call solve() first") from None
         key = (farads.tobytes(), ca.tobytes(), cb.tobytes(), dt, code)
+        if len(lnames):
+            key += (henries.tobytes(), la.tobytes(), lb.tobytes())
         if self._transient_child is None or self._transient_child[0] != key:
             self._transient_child = None  # (its device context goes back to the pool first)
-            table, cap_rows = companion_table(self.table, farads, ca, cb, dt, code)
-            self._transient_child = (key, Circuit._clone_of(self, table), cap_rows)
-        _, child, cap_rows = self._transient_child
+            if len(lnames):
+                table, cap_rows, ind_rows = companion_table(self.table, farads, ca, cb, dt, code, henries, la, lb)
+            else:
+                (table, cap_rows), ind_rows = companion_table(self.table, farads, ca, cb, dt, code), None
+            self._transient_child = (key, Circuit._clone_of(self, table), cap_rows, ind_rows)
+        _, child, cap_rows, ind_rows = self._transient_child
         ch = child._handle
+        cur = final = None
         try:
             if record:
                 ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 1)
-            wave, x, env, resid, info, iters = ch.transient(cap_rows, rows, values, x0, pa, pb, dense=not self.sparse,
-                                                            method=code, keep_every=keep_every, envelope=envelope)
+            if dc_singular:  # (sparse: the start is NaN, and with it every step)
+                wave = np.full((steps + 1, len(pa)), np.nan)
+                x = np.full((steps // keep_every, h.n), np.nan) if keep_every > 0 else None
+                env = None
+                if envelope:
+                    K = self.table.K
+                    env = {"potential_min": np.full(K, np.nan), "potential_min_step": np.full(K, -1, dtype=np.int32),
+                           "potential_max": np.full(K, np.nan), "potential_max_step": np.full(K, -1, dtype=np.int32)}
+                resid, info, iters = np.full(steps, np.nan), np.ones(steps, dtype=np.int32), np.zeros(steps, dtype=np.int32)
+                cur, final = np.full((steps + 1, len(cur_index)), np.nan), np.full(len(lnames), np.nan)
+            elif len(lnames):
+                wave, x, env, resid, info, iters, cur, final = ch.transient_rlc(
+                    cap_rows, ind_rows, rows, values, x0, i0, pa, pb, cur_index, dense=not self.sparse, method=code,
+                    keep_every=keep_every, envelope=envelope)
+            else:
+                wave, x, env, resid, info, iters = ch.transient(cap_rows, rows, values, x0, pa, pb, dense=not self.sparse,
+                                                                method=code, keep_every=keep_every, envelope=envelope)
         except _ffi.NodalHipError as exc:
             if exc.status != _ffi.E_SINGULAR or self.sparse:
                 raise
@@ -488,7 +530,7 @@ class Circuit:
         finally:
             if record:
                 ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 0)  # (the handle goes back to a pool some day)
-        if (info > 0).any():
+        if (info > 0).any() or dc_singular:
             warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
         elif record:
             from .sweep import _row_map
@@ -504,7 +546,32 @@ class Circuit:
                                     env["potential_max_step"])
         kept = np.arange(1, steps // keep_every + 1, dtype=np.int64) * keep_every if keep_every > 0 else None
         return Transient(dt * np.arange(steps + 1, dtype=np.float64), wave, probes, info, resid, iters, solutions=x,
-                         solution_steps=kept, envelope=env, timings=ch.timings())
+                         solution_steps=kept, envelope=env, timings=ch.timings(), currents=cur,
+                         current_probes=current_probes, final_currents=final)
+
+    def _transient_dc_start(self, la, lb):
+        """The DC operating point with every inductor a short, of the netlist's own source values: (x_0 [K+B], i_0 [L],
+        singular).  Solved on a clone that holds the table with one zero-volt `E` row per inductor, kept with its
+        solution under the inductors' leads.  Dense and singular: LinAlgError (whether the netlist alone is connected
+        says nothing about this system); sparse and singular: NaN."""
+        from .transient import dc_table
+        key = (la.tobytes(), lb.tobytes())
+        if self._transient_dc is None or self._transient_dc[0] != key:
+            self._transient_dc = None  # (its device context goes back to the pool first)
+            clone = Circuit._clone_of(self, dc_table(self.table, la, lb))
+            dh = clone._handle
+            if self.sparse:
+                e, info = dh.solve_sparse()[:2]
+            else:
+                e, info = dh.solve_dense()
+                if info > 0:
+                    logging.error("Model error: matrix is singular")
+                    raise np.linalg.LinAlgError("Singular matrix")
+            self._transient_dc = (key, clone, np.array(e, dtype=np.float64), info > 0)
+        _, _, e, singular = self._transient_dc
+        n = self.table.n
+        # (an E row's branch unknown is the current into lead a out of the element: from a to b it is the negative)
+        return e[:n].copy(), -e[n:], singular
 
     def transient_gradient(self, wave_cotangents, probes=None, adjoints=False):
         """The gradient of a scalar loss L of the probe waveforms of the last transient(..., record=True), by the adjoint

@@ -267,6 +267,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->pt_buf,
                       &h->gr_cot, &h->gr_x, &h->gr_spec, &h->gr_acc,
                       &h->tr_spec, &h->tr_none, &h->tr_node, &h->tr_ptr, &h->tr_con, &h->tr_vec, &h->tr_out, &h->tr_ring,
+                      &h->tr_ind,
                       &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
                       &h->tg_con,
                       &h->dbg_resid, &h->dbg_apply};
@@ -877,6 +878,18 @@ int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method
                     const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
                     double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
                     int32_t *info_out, int32_t *iters_out) {
+    return nodal_transient_rlc(h, dense, steps, method, ncap, cap_rows, nsrc, src_rows, src_values, x0, nprobe, probe_a,
+                               probe_b, wave_out, keep_every, x_out, pot_min, pot_min_step, pot_max, pot_max_step, resid_out,
+                               info_out, iters_out, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+}
+
+int nodal_transient_rlc(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                        int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                        const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                        double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                        int32_t *info_out, int32_t *iters_out, int64_t nind, const int64_t *ind_rows, const double *i0,
+                        int32_t ncur, const int32_t *cur_index, double *cur_out, double *i_final_out) {
+    if (!h || nind < 0 || (nind > 0 && !ind_rows) || ncur < 0 || (ncur > 0 && (!cur_index || nind == 0))) return NODAL_E_INVALID;
     if (!h || steps < 0 || (method != 0 && method != 1) || ncap < 0 || (ncap > 0 && !cap_rows) || nprobe < 0 ||
         (nprobe > 0 && (!probe_a || !probe_b)) || keep_every < 0)
         return NODAL_E_INVALID;
@@ -892,9 +905,17 @@ int nodal_transient(nodal_handle h, int32_t dense, int32_t steps, int32_t method
     h->last_batch_block = false;
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
     double ms_matrix = 0.0;
+    TransientInductors ind;
+    ind.nind = nind;
+    ind.rows = ind_rows;
+    ind.i0 = i0;
+    ind.ncur = ncur;
+    ind.cur_index = cur_index;
+    ind.cur_out = cur_out;
+    ind.i_final_out = i_final_out;
     const int s = transient_run(h, dense != 0, steps, method, ncap, cap_rows, nsrc, x0, nprobe, probe_a, probe_b, wave_out,
                                 keep_every, x_out, pot_min, pot_min_step, pot_max, pot_max_step, resid_out, info_out,
-                                iters_out, &ms_matrix);
+                                iters_out, &ms_matrix, nind > 0 ? &ind : nullptr);
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_matrix;

@@ -212,6 +212,9 @@ struct nodal_ctx {
     // right-hand side, the refinement's vectors and the judge's norms; waveforms, envelope and residuals until they go
     // down; the staging ring of kept solutions
     DevBuf tr_spec, tr_none, tr_node, tr_ptr, tr_con, tr_vec, tr_out, tr_ring;
+    // ... with inductors (nodal_transient_rlc): their currents, i_0, the probed currents' rows until they go down and the
+    // probed inductors' indices
+    DevBuf tr_ind;
     uint64_t numeric_epoch = 1;   // bumped by every numeric assembly (stamp_numeric): the identity of G's values
     uint64_t tr_mg_epoch = 0;     // numeric_epoch the multigrid hierarchy a transient call set up belongs to (0: none)
     uint64_t tr_lu_epoch = 0;     // ... and the sparse LU factors a transient call left
@@ -518,11 +521,21 @@ int grad_launch_sources(nodal_ctx *h, int cols, int32_t nsrc, const int32_t *swe
 // ---- transient analysis (transient.hip): capacitors stepped in time, one solve per step on the kept matrix work ----
 // the arguments are those of nodal_transient; the source table is already on the device (sw_slot, sw_vals: api.hip's
 // sweep_prepare).  ms_matrix: host milliseconds of the matrix work done once per call, 0.0 when it was kept
+// inductors: nodal_transient_rlc's further arguments, nullptr for nodal_transient (the same run with nind == 0)
+struct TransientInductors {
+    int64_t nind = 0;
+    const int64_t *rows = nullptr;   // [nind] table rows of type R, the companion resistors
+    const double *i0 = nullptr;      // [nind] the currents at t_0 (nullptr: zero)
+    int32_t ncur = 0;
+    const int32_t *cur_index = nullptr;  // [ncur] indices into the inductors
+    double *cur_out = nullptr;           // [steps + 1][ncur]
+    double *i_final_out = nullptr;       // [nind]
+};
 int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
                   int32_t nsrc, const double *x0, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
                   double *wave_out, int32_t keep_every, double *x_out, double *pot_min, int32_t *pot_min_step,
                   double *pot_max, int32_t *pot_max_step, double *resid_out, int32_t *info_out, int32_t *iters_out,
-                  double *ms_matrix);
+                  double *ms_matrix, const TransientInductors *inductors = nullptr);
 // One step's solve, shared by the forward steps and the backward sweep of transient_gradient.hip.  s: the context whose
 // matrix is solved -- h itself, or the csr_only child that holds G^T (never the multigrid route); lu_epoch: where the
 // numeric_epoch of s's kept LU factors is filed; rvec, dvec [n] and norms ([16][4] + [16]) are the caller's scratch.
@@ -546,7 +559,8 @@ int transient_solver_begin(nodal_ctx *h, TransientSolver &ts, bool dense, int32_
 int transient_solver_step(nodal_ctx *h, TransientSolver &ts, const double *bvec, double *xk, int32_t *inf, int32_t *it,
                           double *resid_host, bool *judged, double *ms_matrix);
 // rhs += S (g o S^T x_prev), the capacitors' history currents (k_transient_history with `method`, then k_transient_rhs
-// over the node list of the last transient_run: tr_node, tr_ptr, tr_con); hist [ncap] is scratch
+// over the node list of the last transient_run: tr_node, tr_ptr, tr_con); hist [ncap] is scratch.  A run with inductors
+// passes hist [ncap + nind] whose last nind words it formed itself (transient.hip); ncap == 0 skips the first kernel.
 int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t *rows_dev, int64_t nent, const double *x_prev,
                           double *hist, double *rhs);
 

@@ -17,12 +17,22 @@
 //     the judgement         the block judge of multi_rhs_solve on one column
 //     k_transient_probe     row k of the waveforms
 //     k_transient_envelope  per node compare-and-update with the step index (when asked for)
+//     k_transient_inductor  one lane per inductor (nodal_transient_rlc): i_k from x_k, and the history current J_{k+1}
+//     k_transient_current_probe  row k of the inductor currents asked for
 // and every keep_every-th step one device-to-device copy into a staging ring.  Waveforms, envelope and residuals come
 // down once, after the last step.
 //
 // The solve and its matrix work are transient_solver_begin / transient_solver_step: transient_gradient.hip runs the same
 // steps backwards, on this handle or on the child that holds G^T.  With NODAL_OPT_TRANSIENT_TAPE a backward-Euler run
 // writes x_k into row k of tr_tape instead of the two alternating vectors and leaves the tape for that sweep.
+//
+// Inductors (nodal_transient_rlc) are companion R rows too, g = h / L (Euler) or h / (2 L) (trapezoidal), behind the
+// capacitors' in the row list, the history array and the node lists, so k_transient_rhs serves both.  What differs is
+// the state: the inductor's current i (positive from lead a to lead b through the element),
+//     Euler:        i_k = i_{k-1} + g v_k,              J_k = -i_{k-1}
+//     trapezoidal:  i_k = i_{k-1} + g (v_k + v_{k-1}),  J_k = -(i_{k-1} + g v_{k-1})
+// so that i_k = -J_k + g v_k in both: the lane finishes i_k and forms J_{k+1} from x_k alone, AFTER the solve, where a
+// capacitor's lane forms J_k from x_{k-1} before it.
 #include "group.h"
 
 #include <chrono>
@@ -56,7 +66,7 @@ struct CapLeads {
     }
 };
 
-// bad[0] |= 1 for a capacitor row that is not a resistor
+// bad[0] |= 1 for a capacitor (or inductor) row that is not a resistor
 __global__ __launch_bounds__(TTB) void k_transient_check(int64_t ncap, const int32_t *__restrict__ rows,
                                                          const uint8_t *__restrict__ type, int32_t *__restrict__ bad) {
     const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
@@ -77,8 +87,45 @@ __global__ __launch_bounds__(TTB) void k_transient_history(int64_t ncap, int tra
     hist[i] = trapezoidal ? 2.0 * g * v - hist[i] : g * v;
 }
 
-// One lane per entry of the node list: rhs[node] += the +-J of the node's capacitors, in list order.  The lane is the
-// only writer of its node's row.
+// One lane per inductor, before the first step: the state i_0 and J_1 = -i_0 (Euler) or -(i_0 + g v_0) (trapezoidal).
+__global__ __launch_bounds__(TTB) void k_transient_inductor_start(int64_t nind, int trapezoidal, const int32_t *__restrict__ rows,
+                                                                  const int32_t *__restrict__ a, const int32_t *__restrict__ b,
+                                                                  const double *__restrict__ value, const double *__restrict__ x0,
+                                                                  const double *__restrict__ i0, double *__restrict__ cur,
+                                                                  double *__restrict__ hist) {
+    const int64_t j = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (j >= nind) return;
+    const int32_t r = rows[j];
+    const double i = i0[j];
+    cur[j] = i;
+    const double g = 1.0 / value[r];
+    hist[j] = trapezoidal ? -(i + g * (lead(x0, a[r]) - lead(x0, b[r]))) : -i;
+}
+
+// One lane per inductor, after the solve of step k: i_k = -J_k + g v_k, then J_{k+1} = -i_k (Euler) or -(i_k + g v_k).
+__global__ __launch_bounds__(TTB) void k_transient_inductor(int64_t nind, int trapezoidal, const int32_t *__restrict__ rows,
+                                                            const int32_t *__restrict__ a, const int32_t *__restrict__ b,
+                                                            const double *__restrict__ value, const double *__restrict__ x,
+                                                            double *__restrict__ cur, double *__restrict__ hist) {
+    const int64_t j = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (j >= nind) return;
+    const int32_t r = rows[j];
+    const double g = 1.0 / value[r];
+    const double gv = g * (lead(x, a[r]) - lead(x, b[r]));
+    const double i = gv - hist[j];
+    cur[j] = i;
+    hist[j] = trapezoidal ? -(i + gv) : -i;
+}
+
+// out[q] = the current of inductor index[q]
+__global__ __launch_bounds__(TTB) void k_transient_current_probe(int32_t ncur, const int32_t *__restrict__ index,
+                                                                 const double *__restrict__ cur, double *__restrict__ out) {
+    const int32_t q = blockIdx.x * TTB + threadIdx.x;
+    if (q < ncur) out[q] = cur[index[q]];
+}
+
+// One lane per entry of the node list: rhs[node] += the +-J of the node's capacitors, then of its inductors, in list
+// order.  The lane is the only writer of its node's row.
 __global__ __launch_bounds__(TTB) void k_transient_rhs(int64_t nent, const int32_t *__restrict__ node,
                                                        const int32_t *__restrict__ cptr, const uint32_t *__restrict__ contrib,
                                                        const double *__restrict__ hist, double *__restrict__ rhs) {
@@ -146,8 +193,9 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t *rows_dev, int64_t nent, const double *x_prev,
                           double *hist, double *rhs) {
     hipStream_t st = h->stream;
-    k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, method, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(),
-                                                        assembled_values(h), x_prev, hist);
+    if (ncap > 0)  // (0: inductors alone, whose words of hist are formed after each solve)
+        k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, method, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(),
+                                                            assembled_values(h), x_prev, hist);
     if (nent > 0)
         k_transient_rhs<<<groups_of(nent), TTB, 0, st>>>(nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(),
                                                         h->tr_con.as<uint32_t>(), hist, rhs);
@@ -260,8 +308,12 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
                   int32_t nsrc, const double *x0, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
                   double *wave_out, int32_t keep_every, double *x_out, double *pot_min, int32_t *pot_min_step,
                   double *pot_max, int32_t *pot_max_step, double *resid_out, int32_t *info_out, int32_t *iters_out,
-                  double *ms_matrix) {
+                  double *ms_matrix, const TransientInductors *inductors) {
     const int64_t n = h->n;
+    const TransientInductors none;
+    const TransientInductors &ind = inductors ? *inductors : none;
+    const int64_t nind = ind.nind, nitems = ncap + nind;
+    const int32_t ncur = ind.ncur;
     const int32_t K = h->K;
     hipStream_t st = h->stream;
     const double nan = __builtin_nan("");
@@ -279,7 +331,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     h->have_x = false;
     h->last_iterations = 0;
     // NODAL_OPT_TRANSIENT_TAPE: the states stay on the handle for nodal_transient_gradient (backward Euler only)
-    const bool record = h->transient_tape && method == 0;
+    const bool record = h->transient_tape && method == 0 && nind == 0;  // (no adjoint with inductors: no tape)
     auto keep_tape = [&](int64_t nent_caps) {
         h->tape_valid = true;
         h->tape_epoch = h->numeric_epoch;
@@ -289,6 +341,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         h->tape_nent = nent_caps;
     };
     if (n == 0) {  // (every lead is ground: nothing moves)
+        if (nind > 0) return nodal_fail(h, NODAL_E_INVALID, "transient: inductors on a network without nodes");
         if (wave_out)
             for (int64_t t = 0; t < (int64_t)(steps + 1) * nprobe; ++t) wave_out[t] = 0.0;
         if (record) keep_tape(0);
@@ -298,33 +351,64 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     // ---- once per call: capacitor rows and probes up, the node lists, the buffers ----
     for (int64_t i = 0; i < ncap; ++i)
         if (cap_rows[i] < 0 || cap_rows[i] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "transient: capacitor row out of range");
+    for (int64_t j = 0; j < nind; ++j)
+        if (ind.rows[j] < 0 || ind.rows[j] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "transient: inductor row out of range");
+    for (int32_t q = 0; q < ncur; ++q)
+        if (ind.cur_index[q] < 0 || ind.cur_index[q] >= nind)
+            return nodal_fail(h, NODAL_E_INVALID, "transient: current probe outside the inductors");
     for (int32_t p = 0; p < nprobe; ++p)
         if (probe_a[p] < -1 || probe_a[p] >= K || probe_b[p] < -1 || probe_b[p] >= K)
             return nodal_fail(h, NODAL_E_INVALID, "transient: probe node out of range");
-    const size_t cap_words = ((size_t)ncap + 15) & ~(size_t)15, probe_words = ((size_t)nprobe + 15) & ~(size_t)15;
-    // tr_spec: cap rows | probe a | probe b | bad flag (16 words) | history [ncap] doubles
-    NODAL_HIP_TRY(h, h->tr_spec.reserve((cap_words + 2 * probe_words + 16) * 4 + (size_t)ncap * 8 + 64));
+    const size_t cap_words = ((size_t)nitems + 15) & ~(size_t)15, probe_words = ((size_t)nprobe + 15) & ~(size_t)15;
+    // tr_spec: cap rows, inductor rows | probe a | probe b | bad flag (16 words) | history [ncap + nind] doubles
+    NODAL_HIP_TRY(h, h->tr_spec.reserve((cap_words + 2 * probe_words + 16) * 4 + (size_t)nitems * 8 + 64));
     int32_t *rows_dev = h->tr_spec.as<int32_t>(), *pa_dev = rows_dev + cap_words, *pb_dev = pa_dev + probe_words,
             *bad_dev = pb_dev + probe_words;
     double *hist = reinterpret_cast<double *>(bad_dev + 16);
     int64_t nent = 0, ncon = 0;
-    if (ncap > 0) {
-        if (K == 0) return nodal_fail(h, NODAL_E_INVALID, "transient: capacitors on a network without nodes");
-        std::vector<int32_t> r32((size_t)ncap);
+    if (nitems > 0) {
+        if (K == 0)
+            return nodal_fail(h, NODAL_E_INVALID, ncap > 0 ? "transient: capacitors on a network without nodes"
+                                                           : "transient: inductors on a network without nodes");
+        std::vector<int32_t> r32((size_t)nitems);
         for (int64_t i = 0; i < ncap; ++i) r32[(size_t)i] = (int32_t)cap_rows[i];
-        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)ncap * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
-        k_transient_check<<<groups_of(ncap), TTB, 0, st>>>(ncap, rows_dev, h->type.as<uint8_t>(), bad_dev);
-        NODAL_HIP_TRY(h, hipGetLastError());
+        for (int64_t j = 0; j < nind; ++j) r32[(size_t)(ncap + j)] = (int32_t)ind.rows[j];
+        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nitems * 4, hipMemcpyHostToDevice, st));
         int32_t bad = 0;
-        NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copy above is done too)
-        if (bad) return nodal_fail(h, NODAL_E_INVALID, "transient: a capacitor row that is not a resistor (R)");
-        NODAL_TRY(grp::build_lists(h, CapLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), ncap}, (int64_t)K, &nent,
+        if (ncap > 0) {
+            NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
+            k_transient_check<<<groups_of(ncap), TTB, 0, st>>>(ncap, rows_dev, h->type.as<uint8_t>(), bad_dev);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copy above is done too)
+            if (bad) return nodal_fail(h, NODAL_E_INVALID, "transient: a capacitor row that is not a resistor (R)");
+        }
+        if (nind > 0) {
+            NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
+            k_transient_check<<<groups_of(nind), TTB, 0, st>>>(nind, rows_dev + ncap, h->type.as<uint8_t>(), bad_dev);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));
+            if (bad) return nodal_fail(h, NODAL_E_INVALID, "transient: an inductor row that is not a resistor (R)");
+        }
+        NODAL_TRY(grp::build_lists(h, CapLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), nitems}, (int64_t)K, &nent,
                                    &ncon, h->tr_none, h->tr_node, h->tr_ptr, h->tr_con, nullptr, nullptr));
     }
     if (nprobe > 0) {
         NODAL_HIP_TRY(h, hipMemcpyAsync(pa_dev, probe_a, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
         NODAL_HIP_TRY(h, hipMemcpyAsync(pb_dev, probe_b, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
+    }
+    // tr_ind: the inductor currents [nind] | i_0 as passed [nind] | current rows [steps + 1][ncur] | probed inductors [ncur]
+    const size_t cur_words = (size_t)(steps + 1) * ncur;
+    double *icur = nullptr, *i0_dev = nullptr, *cur_dev = nullptr;
+    int32_t *cidx_dev = nullptr;
+    if (nind > 0) {
+        NODAL_HIP_TRY(h, h->tr_ind.reserve((2 * (size_t)nind + cur_words) * 8 + ((size_t)ncur + 16) * 4 + 64));
+        icur = h->tr_ind.as<double>();
+        i0_dev = icur + nind;
+        cur_dev = i0_dev + nind;
+        cidx_dev = reinterpret_cast<int32_t *>(cur_dev + cur_words);
+        if (ind.i0) NODAL_HIP_TRY(h, hipMemcpyAsync(i0_dev, ind.i0, (size_t)nind * 8, hipMemcpyHostToDevice, st));
+        else NODAL_HIP_TRY(h, hipMemsetAsync(i0_dev, 0, (size_t)nind * 8, st));
+        if (ncur > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(cidx_dev, ind.cur_index, (size_t)ncur * 4, hipMemcpyHostToDevice, st));
     }
     // tr_vec: two solutions | right-hand side | defect | correction | the judge's norms
     NODAL_HIP_TRY(h, h->tr_vec.reserve((size_t)5 * n * 8 + 5 * SLU_MULTI * 8 + 256));
@@ -364,7 +448,13 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
                                                             state(0), hist);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
-    NODAL_WAIT_STREAM(h, st);  // (x0 and the probes are the caller's, r32 ends here)
+    if (nind > 0) {  // i_0 and J_1, row 0 of the currents
+        k_transient_inductor_start<<<groups_of(nind), TTB, 0, st>>>(nind, method, rows_dev + ncap, h->a.as<int32_t>(),
+                                                                   h->b.as<int32_t>(), value, state(0), i0_dev, icur, hist + ncap);
+        if (ncur > 0) k_transient_current_probe<<<groups_of(ncur), TTB, 0, st>>>(ncur, cidx_dev, icur, cur_dev);
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    NODAL_WAIT_STREAM(h, st);  // (x0, i0 and the probes are the caller's, r32 ends here)
 
     // ---- the route and its matrix work ----
     TransientSolver ts;
@@ -397,7 +487,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)n * 8, st));
         NODAL_TRY(stamp_rhs_multi(h, h->sw_slot.as<int32_t>(), h->sw_vals.as<double>() + (int64_t)(k - 1) * nsrc, nsrc, 1,
                                   bvec, 1, 0));
-        if (ncap > 0) NODAL_TRY(transient_add_history(h, ncap, method, rows_dev, nent, xp, hist, bvec));
+        if (nitems > 0) NODAL_TRY(transient_add_history(h, ncap, method, rows_dev, nent, xp, hist, bvec));
         // the solve
         int32_t inf = 0, it = 0;
         bool judged = false;  // resid[k - 1] is on the host already
@@ -413,6 +503,12 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         on_host[(size_t)k - 1] = judged;
         if (!judged)
             NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + (k - 1), norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
+        if (nind > 0) {  // i_k and J_{k+1}
+            k_transient_inductor<<<groups_of(nind), TTB, 0, st>>>(nind, method, rows_dev + ncap, h->a.as<int32_t>(),
+                                                                 h->b.as<int32_t>(), value, xk, icur, hist + ncap);
+            if (ncur > 0)
+                k_transient_current_probe<<<groups_of(ncur), TTB, 0, st>>>(ncur, cidx_dev, icur, cur_dev + (size_t)k * ncur);
+        }
         // what the caller asked for of x_k
         if (nprobe > 0) k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, xk, wave_dev + (size_t)k * nprobe);
         if (want_env && K > 0) {
@@ -432,6 +528,10 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     std::vector<double> resid_dn((size_t)steps);
     if (wave_out && wave_words > 0)
         NODAL_HIP_TRY(h, hipMemcpyAsync(wave_out, wave_dev, wave_words * 8, hipMemcpyDeviceToHost, st));
+    if (ind.cur_out && cur_words > 0)
+        NODAL_HIP_TRY(h, hipMemcpyAsync(ind.cur_out, cur_dev, cur_words * 8, hipMemcpyDeviceToHost, st));
+    if (ind.i_final_out && nind > 0)
+        NODAL_HIP_TRY(h, hipMemcpyAsync(ind.i_final_out, icur, (size_t)nind * 8, hipMemcpyDeviceToHost, st));
     if (steps > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dn.data(), resid_dev, (size_t)steps * 8, hipMemcpyDeviceToHost, st));
     if (want_env && K > 0) {
         if (pot_min) NODAL_HIP_TRY(h, hipMemcpyAsync(pot_min, pmin_dev, (size_t)K * 8, hipMemcpyDeviceToHost, st));
@@ -451,7 +551,11 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
             for (int32_t p = 0; p < nprobe; ++p) wave_out[(size_t)k * nprobe + p] = nan;
         if (nkeep > 0 && k % keep_every == 0)
             for (int64_t i = 0; i < n; ++i) x_out[(int64_t)(k / keep_every - 1) * n + i] = nan;
+        if (ind.cur_out)
+            for (int32_t q = 0; q < ncur; ++q) ind.cur_out[(size_t)k * ncur + q] = nan;
     }
+    if (ind.i_final_out && first_dead <= steps)
+        for (int64_t j = 0; j < nind; ++j) ind.i_final_out[j] = nan;
     if (record && first_dead == steps + 1) keep_tape(nent);
     return NODAL_OK;
 }

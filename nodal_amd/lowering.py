@@ -75,6 +75,20 @@ class ComponentTable:
         t.a[self.ncomp:], t.b[self.ncomp:] = a, b
         return t
 
+    def with_branch_rows_appended(self, type, value, a, b):
+        """A copy with len(type) more rows behind the present ones, each with a branch unknown of its own: row j of the
+        new ones gets k = B + j, and the copy has B + len(type) branch equations (same K).  Two-lead components
+        without control nodes or driver -- the zero-volt `E` rows that stand for inductors at DC (Circuit.transient).
+        The present rows keep their indices and their branches."""
+        extra = len(type)
+        t = ComponentTable(self.ncomp + extra, self.K, self.B + extra)
+        for name in ("type", "value", "a", "b", "c", "d", "drv", "k"):
+            getattr(t, name)[:self.ncomp] = getattr(self, name)
+        t.type[self.ncomp:], t.value[self.ncomp:] = type, value
+        t.a[self.ncomp:], t.b[self.ncomp:] = a, b
+        t.k[self.ncomp:] = np.arange(self.B, self.B + extra, dtype=np.int32)
+        return t
+
     def truncated(self, ncomp):
         """A copy holding only the first `ncomp` rows (used to let the device
         look for an earlier stamp collision before a host error is raised)."""

@@ -1,4 +1,4 @@
-"""Transient analysis: capacitors stepped in time on the device.
+"""Transient analysis: capacitors and inductors stepped in time on the device.
 
 The dynamic counterpart of an IR-drop study: decoupling capacitors hang on the network, the load currents switch, and
 the question is how far each node droops and when.  Under backward Euler a capacitor C between nodes a and b, stepped
@@ -9,8 +9,14 @@ steps to `nodal_transient` (csrc/transient.hip): one multigrid hierarchy or one 
 history currents, probes and envelope are formed on the device.  With the reference the only way to the same numbers is
 a host loop that rebuilds `Circuit(netlist with companion rows)` and solves it per step (reference nodal/nodal.py:306-336).
 
-`check_transient_arguments`, `resolve_capacitors` and `companion_table` need no device, and `Transient` is a plain
-container that can be built from arrays.
+An inductor L between a and b is again a conductance, h / L (Euler) or h / (2 L) (trapezoidal), plus a history current,
+so it is one more companion `R` row behind the capacitors'; its state is its current i, positive from a to b through the
+element, kept per inductor on the device (`nodal_transient_rlc`).  At DC an inductor is a short: with inductors the start
+is the solution of the netlist with one zero-volt `E` row per inductor (`dc_table`), whose branch unknown is the current
+INTO lead a out of the element, so i_0 is its negative.
+
+`check_transient_arguments`, `resolve_capacitors`, `resolve_inductors`, `companion_table` and `dc_table` need no device,
+and `Transient` is a plain container that can be built from arrays.
 """
 
 import math
@@ -69,13 +75,92 @@ def resolve_capacitors(netlist, capacitors):
             np.asarray(ia, dtype=np.int32).reshape(len(names)), np.asarray(ib, dtype=np.int32).reshape(len(names)))
 
 
-def companion_table(table, farads, ia, ib, dt, method_code):
+def resolve_inductors(netlist, inductors):
+    """`inductors`, a sequence of (name, henries, node_a, node_b), as (names, henries float64 [L], ia, ib int32 [L]),
+    -1 for the ground node.  KeyError for a label the netlist does not have (inductors introduce no nodes), ValueError
+    for henries <= 0 or not finite, for node_a == node_b, for a name given twice and for a loop made of inductors alone
+    (ground is one node; two inductors in parallel are such a loop): at DC every inductor is a short, and a loop of
+    shorts makes the start singular whatever the rest of the network is."""
+    names, henries, ia, ib = [], [], [], []
+    parent = {}
+
+    def find(x):  # union-find over the inductors' leads
+        root = x
+        while parent.setdefault(root, root) != root:
+            root = parent[root]
+        while parent[x] != root:
+            parent[x], x = root, parent[x]
+        return root
+
+    for ind in inductors:
+        if len(ind) != 4:
+            raise ValueError(f"Inductor {ind!r} is not (name, henries, node_a, node_b)")
+        name, value, a, b = ind
+        value = float(value)
+        if not (value > 0.0 and math.isfinite(value)):
+            raise ValueError(f"Inductor {name}: henries must be positive and finite, not {value}")
+        na, nb = _port_node(netlist, a), _port_node(netlist, b)
+        if na == nb:
+            raise ValueError(f"Inductor {name}: both leads on node {a}")
+        if name in names:
+            raise ValueError(f"Inductor {name} is given twice")
+        ra, rb = find(na), find(nb)
+        if ra == rb:
+            raise ValueError(f"Inductor {name} closes a loop of inductors: the DC start (every inductor a short) is singular")
+        parent[ra] = rb
+        names.append(name)
+        henries.append(value)
+        ia.append(na)
+        ib.append(nb)
+    return (names, np.asarray(henries, dtype=np.float64).reshape(len(names)),
+            np.asarray(ia, dtype=np.int32).reshape(len(names)), np.asarray(ib, dtype=np.int32).reshape(len(names)))
+
+
+def check_inductor_arguments(names, initial, initial_currents, current_probes):
+    """`initial_currents` and `current_probes` of Circuit.transient.  Returns (i0 float64 [L] or None: the DC start
+    supplies it, cur_index int32 [Q]); ValueError for initial_currents without `initial` or of another shape, KeyError
+    for a probe that is not the name of an inductor."""
+    count = len(names)
+    i0 = None
+    if initial_currents is not None:
+        if initial is None:
+            raise ValueError("initial_currents needs `initial`: the DC start supplies the inductor currents itself")
+        i0 = np.ascontiguousarray(initial_currents, dtype=np.float64)
+        if i0.shape != (count,):
+            raise ValueError(f"initial_currents must have shape ({count},), not {i0.shape}")
+    elif initial is not None:
+        i0 = np.zeros(count, dtype=np.float64)
+    index = {name: j for j, name in enumerate(names)}
+    for name in current_probes:
+        if name not in index:
+            raise KeyError(f"current probe {name!r} is not the name of an inductor")
+    return i0, np.asarray([index[name] for name in current_probes], dtype=np.int32).reshape(len(current_probes))
+
+
+def companion_table(table, farads, ia, ib, dt, method_code, henries=None, la=None, lb=None):
     """The table with one companion `R` row per capacitor appended: value dt / C (Euler) or dt / (2 C) (trapezoidal).
-    Returns (table, rows int64 [C]): the appended rows' indices; the original rows keep theirs."""
+    Returns (table, rows int64 [C]): the appended rows' indices; the original rows keep theirs.  With `henries` [L] (and
+    the inductors' leads la, lb) one row per inductor follows the capacitors': value L / dt or 2 L / dt; then the
+    result is (table, capacitor rows [C], inductor rows [L])."""
     scale = 2.0 if method_code == METHODS["trapezoidal"] else 1.0
     values = dt / (scale * np.asarray(farads, dtype=np.float64))
+    ncap, first = len(values), table.ncomp
+    if henries is not None:
+        values = np.concatenate([values, scale * np.asarray(henries, dtype=np.float64) / dt])
+        ia = np.concatenate([np.asarray(ia, dtype=np.int32).reshape(ncap), np.asarray(la, dtype=np.int32).reshape(-1)])
+        ib = np.concatenate([np.asarray(ib, dtype=np.int32).reshape(ncap), np.asarray(lb, dtype=np.int32).reshape(-1)])
     types = np.full(len(values), c.TYPE_CODE["R"], dtype=np.uint8)
-    return table.with_rows_appended(types, values, ia, ib), np.arange(table.ncomp, table.ncomp + len(values), dtype=np.int64)
+    out, rows = table.with_rows_appended(types, values, ia, ib), np.arange(first, first + len(values), dtype=np.int64)
+    return (out, rows) if henries is None else (out, rows[:ncap], rows[ncap:])
+
+
+def dc_table(table, la, lb):
+    """The table in which every inductor is a short: one zero-volt `E` row per inductor appended, each with a branch
+    unknown of its own (ComponentTable.with_branch_rows_appended): K + B + L unknowns, the first K + B the circuit's.
+    The branch unknown of an `E` row is the current that enters lead a from the element, so the inductor's current from
+    a to b is its negative."""
+    count = len(la)
+    return table.with_branch_rows_appended(np.full(count, c.TYPE_CODE["E"], dtype=np.uint8), np.zeros(count), la, lb)
 
 
 class TransientEnvelope:
@@ -96,10 +181,12 @@ class Transient:
     [steps // keep_every, K+B] or None and solution_steps, the steps they belong to; envelope (TransientEnvelope) or None;
     info [steps]: 0 solved, > 0 singular (sparse path: NaN); scaled_residual [steps], computed on the device; iterations
     [steps].  timings: nodal_last_timings of the call, [0] the ms of the matrix work done once (0.0: it was kept from an
-    earlier call), [2] the whole call on the device."""
+    earlier call), [2] the whole call on the device.  currents [steps + 1, Q]: the currents of the inductors named in
+    current_probes, from lead a to lead b, row 0 the start's; final_currents [L]: every inductor's after the last step
+    (NaN when a step was singular), what `initial_currents` of a continuing call takes."""
 
     def __init__(self, t, waveforms, probes, info, scaled_residual, iterations, solutions=None, solution_steps=None,
-                 envelope=None, timings=None):
+                 envelope=None, timings=None, currents=None, current_probes=(), final_currents=None):
         self.t = t
         self.waveforms = waveforms
         self.probes = list(probes)
@@ -110,6 +197,9 @@ class Transient:
         self.solution_steps = solution_steps if solution_steps is not None else np.zeros(0, dtype=np.int64)
         self.envelope = envelope
         self.timings = timings
+        self.currents = currents if currents is not None else np.zeros((len(t), 0), dtype=np.float64)
+        self.current_probes = list(current_probes)
+        self.final_currents = final_currents if final_currents is not None else np.zeros(0, dtype=np.float64)
 
     def __len__(self):
         return len(self.info)
