@@ -16,6 +16,7 @@ against the reference's attributes keeps working without paying a device->host
 copy on the hot path.
 """
 
+import contextlib
 import logging
 import os
 import warnings
@@ -32,6 +33,13 @@ try:  # same warning class the reference's spsolve call emits
 except Exception:  # pragma: no cover - scipy is optional at run time
     class MatrixRankWarning(UserWarning):
         pass
+
+
+def _warn_singular(singular):
+    """The reference's warning for a sparse system that is singular, attributed to the caller of the Circuit method
+    that calls this (hence the stack level: this frame, the method, its caller)."""
+    if singular:
+        warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=3)
 
 
 def default_device():
@@ -184,6 +192,30 @@ class Circuit:
             self._A = self._handle.export_csr()[3]
         return self._A
 
+    # -- the library's errors as the reference's exceptions --------------------------
+    def _singular(self, look_at_connectivity=True):
+        """The exception the reference raises for a singular dense system (reference nodal/nodal.py:313-336)."""
+        if look_at_connectivity and not is_connected(self.netlist):
+            logging.error("Model error: unconnected circuit")
+            return UnconnectedCircuitError()
+        logging.error("Model error: matrix is singular")
+        return np.linalg.LinAlgError("Singular matrix")
+
+    @contextlib.contextmanager
+    def _reference_errors(self, missing=None, message="no solution: call solve() first"):
+        """Around a call into the library: a NodalHipError becomes what the reference would have raised.  `missing`:
+        the text by which an E_INVALID says that what the call reads is not on the device ("" for any E_INVALID; None:
+        the call reads nothing of the kind) -- ValueError(message).  E_SINGULAR on the dense path: _singular().
+        Everything else, and E_SINGULAR on the sparse path, is raised again as it is."""
+        try:
+            yield
+        except _ffi.NodalHipError as exc:
+            if missing is not None and exc.status == _ffi.E_INVALID and missing in str(exc):
+                raise ValueError(message) from None
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            raise self._singular()
+
     # -- solve ---------------------------------------------------------------
     def solve(self):
         """Solve G e = A on the device (reference nodal/nodal.py:313-336).
@@ -199,16 +231,11 @@ class Circuit:
         h = self._handle
         if self.sparse:
             e, info, self.iterations, self.relative_residual = h.solve_sparse()
-            if info > 0:
-                warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+            _warn_singular(info > 0)
         else:
             e, info = h.solve_dense()
             if info > 0:
-                if not is_connected(self.netlist):
-                    logging.error("Model error: unconnected circuit")
-                    raise UnconnectedCircuitError
-                logging.error("Model error: matrix is singular")
-                raise np.linalg.LinAlgError("Singular matrix")
+                raise self._singular()
         return Solution(e, self.netlist, self.currents)
 
     def branches(self):
@@ -217,12 +244,8 @@ class Circuit:
         `netlist.component_keys`.  Raises ValueError when there is no solution on the device: before the
         first solve(), or after a solve_sources() (a sweep does not keep the single solve's solution)."""
         from .branches import Branches
-        try:
+        with self._reference_errors(missing=""):
             v, i, p, dissipated, absorbed = self._handle.branches()
-        except _ffi.NodalHipError as exc:
-            if exc.status != _ffi.E_INVALID:
-                raise
-            raise ValueError("no solution: call solve() first") from None
         return Branches(self.netlist, v, i, p, dissipated, absorbed, table=self.table)
 
     def solve_sources(self, sources, branches=False, keep_solutions=True):
@@ -252,22 +275,13 @@ class Circuit:
                                self.netlist, self.currents,
                                envelope=Envelope.empty(self.netlist, self.table.ncomp) if branches else None)
         env = None
-        try:
+        with self._reference_errors():
             if branches:
                 x, info, resid, env = h.solve_sources_branches(rows, values, dense=not self.sparse,
                                                                keep_solutions=keep_solutions)
             else:
                 x, info, resid = h.solve_sources(rows, values, dense=not self.sparse)
-        except _ffi.NodalHipError as exc:
-            if exc.status != _ffi.E_SINGULAR or self.sparse:
-                raise
-            if not is_connected(self.netlist):
-                logging.error("Model error: unconnected circuit")
-                raise UnconnectedCircuitError
-            logging.error("Model error: matrix is singular")
-            raise np.linalg.LinAlgError("Singular matrix")
-        if (info > 0).any():
-            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        _warn_singular((info > 0).any())
         if env is not None:
             from .branches import Envelope
             env = Envelope(self.netlist, env["current_absmax"], env["current_member"], env["potential_min"],
@@ -291,20 +305,9 @@ class Circuit:
         outputs = list(outputs)
         kind, p, q2 = resolve_outputs(self.netlist, outputs)
         h = self._handle
-        try:
+        with self._reference_errors(missing="no solution"):
             values, y, lam, resid, info = h.sensitivities(kind, p, q2, dense=not self.sparse, adjoints=adjoints)
-        except _ffi.NodalHipError as exc:
-            if exc.status == _ffi.E_INVALID and "no solution" in str(exc):
-                raise ValueError("no solution: call solve() first") from None
-            if exc.status != _ffi.E_SINGULAR or self.sparse:
-                raise
-            if not is_connected(self.netlist):
-                logging.error("Model error: unconnected circuit")
-                raise UnconnectedCircuitError
-            logging.error("Model error: matrix is singular")
-            raise np.linalg.LinAlgError("Singular matrix")
-        if (info > 0).any():
-            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        _warn_singular((info > 0).any())
         return Sensitivities(self.netlist, outputs, values, y, info, resid, adjoints=lam, table=self.table)
 
     def gradient(self, cotangents, sources=None, solutions=None, adjoints=False):
@@ -324,21 +327,10 @@ class Circuit:
         from .gradient import Gradient, check_gradient_arguments
         h = self._handle
         cot, rows, x, columns = check_gradient_arguments(self.netlist, h.n, cotangents, sources, solutions)
-        try:
+        with self._reference_errors(missing="no solution"):
             values, gsrc, lam, resid, info = h.gradient(cot, dense=not self.sparse, rows=rows, solutions=x,
                                                         adjoints=adjoints)
-        except _ffi.NodalHipError as exc:
-            if exc.status == _ffi.E_INVALID and "no solution" in str(exc):
-                raise ValueError("no solution: call solve() first") from None
-            if exc.status != _ffi.E_SINGULAR or self.sparse:
-                raise
-            if not is_connected(self.netlist):
-                logging.error("Model error: unconnected circuit")
-                raise UnconnectedCircuitError
-            logging.error("Model error: matrix is singular")
-            raise np.linalg.LinAlgError("Singular matrix")
-        if (info > 0).any():
-            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        _warn_singular((info > 0).any())
         by_name = {name: gsrc[:, cols].sum(axis=1) for name, cols in columns.items()}
         return Gradient(self.netlist, values, by_name, info, resid, adjoints=lam, table=self.table)
 
@@ -402,20 +394,9 @@ class Circuit:
         from .ports import PortEquivalent, _as_pair, resolve_ports
         ports = [_as_pair(self.netlist, port) for port in ports]
         ia, ib = resolve_ports(self.netlist, ports)
-        try:
+        with self._reference_errors(missing="no solution"):
             z, v_oc, info, resid = self._handle.port_matrix(ia, ib, dense=not self.sparse, voc=bool(sources))
-        except _ffi.NodalHipError as exc:
-            if exc.status == _ffi.E_INVALID and "no solution" in str(exc):
-                raise ValueError("no solution: call solve() first") from None
-            if exc.status != _ffi.E_SINGULAR or self.sparse:
-                raise
-            if not is_connected(self.netlist):
-                logging.error("Model error: unconnected circuit")
-                raise UnconnectedCircuitError
-            logging.error("Model error: matrix is singular")
-            raise np.linalg.LinAlgError("Singular matrix")
-        if (info > 0).any():
-            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        _warn_singular((info > 0).any())
         return PortEquivalent(self.netlist, ports, z, v_oc, info, resid)
 
     def transient(self, capacitors, dt, steps, sources=None, probes=(), method="euler", initial=None, keep_every=0,
@@ -480,12 +461,8 @@ class Circuit:
         if x0 is None and len(lnames):
             x0, i0, dc_singular = self._transient_dc_start(la, lb)
         elif x0 is None:
-            try:
+            with self._reference_errors(missing=""):
                 x0 = h.download_x()
-            except _ffi.NodalHipError as exc:
-                if exc.status != _ffi.E_INVALID:
-                    raise
-                raise ValueError("no solution: call solve() first") from None
         key = (farads.tobytes(), ca.tobytes(), cb.tobytes(), dt, code)
         if len(lnames):
             key += (henries.tobytes(), la.tobytes(), lb.tobytes())
@@ -500,39 +477,32 @@ class Circuit:
         ch = child._handle
         cur = final = None
         try:
-            if record:
-                ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 1)
-            if dc_singular:  # (sparse: the start is NaN, and with it every step)
-                wave = np.full((steps + 1, len(pa)), np.nan)
-                x = np.full((steps // keep_every, h.n), np.nan) if keep_every > 0 else None
-                env = None
-                if envelope:
-                    K = self.table.K
-                    env = {"potential_min": np.full(K, np.nan), "potential_min_step": np.full(K, -1, dtype=np.int32),
-                           "potential_max": np.full(K, np.nan), "potential_max_step": np.full(K, -1, dtype=np.int32)}
-                resid, info, iters = np.full(steps, np.nan), np.ones(steps, dtype=np.int32), np.zeros(steps, dtype=np.int32)
-                cur, final = np.full((steps + 1, len(cur_index)), np.nan), np.full(len(lnames), np.nan)
-            elif len(lnames):
-                wave, x, env, resid, info, iters, cur, final = ch.transient_rlc(
-                    cap_rows, ind_rows, rows, values, x0, i0, pa, pb, cur_index, dense=not self.sparse, method=code,
-                    keep_every=keep_every, envelope=envelope)
-            else:
-                wave, x, env, resid, info, iters = ch.transient(cap_rows, rows, values, x0, pa, pb, dense=not self.sparse,
-                                                                method=code, keep_every=keep_every, envelope=envelope)
-        except _ffi.NodalHipError as exc:
-            if exc.status != _ffi.E_SINGULAR or self.sparse:
-                raise
-            if not is_connected(self.netlist):
-                logging.error("Model error: unconnected circuit")
-                raise UnconnectedCircuitError
-            logging.error("Model error: matrix is singular")
-            raise np.linalg.LinAlgError("Singular matrix")
+            with self._reference_errors():
+                if record:
+                    ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 1)
+                if dc_singular:  # (sparse: the start is NaN, and with it every step)
+                    wave = np.full((steps + 1, len(pa)), np.nan)
+                    x = np.full((steps // keep_every, h.n), np.nan) if keep_every > 0 else None
+                    env = None
+                    if envelope:
+                        K = self.table.K
+                        env = {"potential_min": np.full(K, np.nan), "potential_min_step": np.full(K, -1, dtype=np.int32),
+                               "potential_max": np.full(K, np.nan), "potential_max_step": np.full(K, -1, dtype=np.int32)}
+                    resid, info, iters = np.full(steps, np.nan), np.ones(steps, dtype=np.int32), np.zeros(steps, dtype=np.int32)
+                    cur, final = np.full((steps + 1, len(cur_index)), np.nan), np.full(len(lnames), np.nan)
+                elif len(lnames):
+                    wave, x, env, resid, info, iters, cur, final = ch.transient_rlc(
+                        cap_rows, ind_rows, rows, values, x0, i0, pa, pb, cur_index, dense=not self.sparse, method=code,
+                        keep_every=keep_every, envelope=envelope)
+                else:
+                    wave, x, env, resid, info, iters = ch.transient(cap_rows, rows, values, x0, pa, pb, dense=not self.sparse,
+                                                                    method=code, keep_every=keep_every, envelope=envelope)
         finally:
             if record:
                 ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 0)  # (the handle goes back to a pool some day)
-        if (info > 0).any() or dc_singular:
-            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
-        elif record:
+        singular = (info > 0).any() or dc_singular
+        _warn_singular(singular)
+        if record and not singular:
             from .sweep import _row_map
             from .transient_gradient import TransientRecord
             row_map, columns, at = _row_map(self.netlist), {}, 0
@@ -565,8 +535,7 @@ class Circuit:
             else:
                 e, info = dh.solve_dense()
                 if info > 0:
-                    logging.error("Model error: matrix is singular")
-                    raise np.linalg.LinAlgError("Singular matrix")
+                    raise self._singular(look_at_connectivity=False)
             self._transient_dc = (key, clone, np.array(e, dtype=np.float64), info > 0)
         _, _, e, singular = self._transient_dc
         n = self.table.n
@@ -587,30 +556,18 @@ class Circuit:
         another shape or that are not finite.  Singular networks behave as in gradient().  A second call with other
         cotangents repeats no matrix work; the circuit, the record and the next transient() are left as they were."""
         from .ports import _as_pair, resolve_ports
-        from .transient_gradient import TransientGradient, check_transient_gradient_arguments
+        from .transient_gradient import NO_RECORD, TransientGradient, check_transient_gradient_arguments
         rec = self._transient_record
         pa, pb = ((), ()) if rec is None else (rec.pa, rec.pb)
         if rec is not None and probes is not None:
             pa, pb = resolve_ports(self.netlist, [_as_pair(self.netlist, port) for port in probes])
         cot = check_transient_gradient_arguments(rec, wave_cotangents, len(pa))  # (raises without a record)
         ch = rec.child._handle
-        try:
+        with self._reference_errors(missing="no recorded transient", message=NO_RECORD):
             grad, gsrc, gx0, lam, resid, info = ch.transient_gradient(rec.steps, rec.nsrc, pa, pb, cot,
                                                                       dense=not self.sparse, adjoints=adjoints)
-        except _ffi.NodalHipError as exc:
-            if exc.status == _ffi.E_INVALID and "no recorded transient" in str(exc):
-                from .transient_gradient import NO_RECORD
-                raise ValueError(NO_RECORD) from None
-            if exc.status != _ffi.E_SINGULAR or self.sparse:
-                raise
-            if not is_connected(self.netlist):
-                logging.error("Model error: unconnected circuit")
-                raise UnconnectedCircuitError
-            logging.error("Model error: matrix is singular")
-            raise np.linalg.LinAlgError("Singular matrix")
         timings = ch.timings()
-        if (info > 0).any():
-            warnings.warn("Matrix is exactly singular", MatrixRankWarning, stacklevel=2)
+        _warn_singular((info > 0).any())
         ncomp = self.table.ncomp
         values = grad[:ncomp].copy()
         capacitors = -(rec.dt / rec.farads ** 2) * grad[rec.cap_rows]  # (the companion value is dt / C)

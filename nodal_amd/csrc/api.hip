@@ -734,32 +734,39 @@ int nodal_solve_pairs(nodal_handle h, int32_t dense, int32_t npairs, const int32
 
 }  // extern "C"
 
+int sweep_check_rows(nodal_ctx *h, const char *prefix, const char *row, int32_t nsrc, const int64_t *rows,
+                     int32_t *rows_dev, int32_t *slot_dev, int32_t *bad_dev) {
+    const std::string the = std::string(prefix) + row, a = std::string(prefix) + "a " + row;
+    std::vector<int32_t> r32((size_t)nsrc + 1);
+    for (int32_t j = 0; j < nsrc; ++j) {
+        if (rows[j] < 0 || rows[j] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, (the + " out of range").c_str());
+        r32[j] = (int32_t)rows[j];
+    }
+    if (nsrc > 0)
+        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nsrc * 4, hipMemcpyHostToDevice, h->stream));
+    NODAL_TRY(stamp_sweep_slots(h, rows_dev, nsrc, slot_dev, bad_dev));
+    int32_t bad = 0;
+    NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the host copies before it are done too)
+    if (bad & 1)
+        return nodal_fail(h, NODAL_E_INVALID, (a + " that is not an independent source (A or E)").c_str());
+    if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, (a + " named twice").c_str());
+    return NODAL_OK;
+}
+
 namespace {
-// Arguments of a source sweep: rows in range, values uploaded, the slot map built -- and the rows checked on the device
-// to be independent sources, each named once (one read-back)
+// Arguments of a source sweep: values uploaded, and the rows through sweep_check_rows into sw_rows and sw_slot
 int sweep_prepare(nodal_ctx *h, int32_t count, int32_t nsrc, const int64_t *rows, const double *values) {
     if (count < 0 || nsrc < 0 || (nsrc > 0 && !rows) || (count > 0 && nsrc > 0 && !values))
         return nodal_fail(h, NODAL_E_INVALID, "source sweep: bad count, rows or values");
     if (!h->have_numeric || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "assemble_numeric not called");
-    std::vector<int32_t> r32((size_t)nsrc + 1);
-    for (int32_t j = 0; j < nsrc; ++j) {
-        if (rows[j] < 0 || rows[j] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "source sweep: row out of range");
-        r32[j] = (int32_t)rows[j];
-    }
     NODAL_HIP_TRY(h, h->sw_rows.reserve((size_t)(nsrc + 16) * 4));
     NODAL_HIP_TRY(h, h->sw_slot.reserve((size_t)h->ncomp * 4 + 64));
     NODAL_HIP_TRY(h, h->sw_vals.reserve((size_t)count * nsrc * 8 + 64));
-    int32_t *rows_dev = h->sw_rows.as<int32_t>(), *bad_dev = rows_dev + ((nsrc + 15) & ~15);
-    if (nsrc > 0)
-        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nsrc * 4, hipMemcpyHostToDevice, h->stream));
     if ((int64_t)count * nsrc > 0)
         NODAL_HIP_TRY(h, hipMemcpyAsync(h->sw_vals.p, values, (size_t)count * nsrc * 8, hipMemcpyHostToDevice, h->stream));
-    NODAL_TRY(stamp_sweep_slots(h, rows_dev, nsrc, h->sw_slot.as<int32_t>(), bad_dev));
-    int32_t bad = 0;
-    NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the host copies above are done too)
-    if (bad & 1) return nodal_fail(h, NODAL_E_INVALID, "source sweep: a row that is not an independent source (A or E)");
-    if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, "source sweep: a row named twice");
-    return NODAL_OK;
+    int32_t *rows_dev = h->sw_rows.as<int32_t>();
+    return sweep_check_rows(h, "source sweep: ", "row", nsrc, rows, rows_dev, h->sw_slot.as<int32_t>(),
+                            rows_dev + ((nsrc + 15) & ~15));
 }
 
 // multi_rhs_solve's client for a source sweep: the columns are the members' folded sources, a finished block feeds the

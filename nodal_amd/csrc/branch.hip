@@ -18,7 +18,7 @@
 // Envelopes: one thread owns one table row (one node) for the whole sweep and the blocks of a sweep follow each other on
 // the handle's stream, so the running maximum is a plain read-modify-write.  It starts as NaN / -1 and is replaced on
 // !(m <= best): the first member that counts always wins, and among exact ties the lowest index stays.
-#include "ctx.h"
+#include "table_rows.h"
 
 namespace {
 
@@ -38,8 +38,6 @@ struct RowEntry {
     double value;
     int32_t a, b, k;
 };
-
-__device__ __forceinline__ double lead(const double *__restrict__ x, int32_t node) { return node < 0 ? 0.0 : x[node]; }
 
 __device__ __forceinline__ double row_current(const RowEntry &r, double v, double source_value,
                                               const double *__restrict__ x, int32_t K) {
@@ -204,13 +202,6 @@ __global__ __launch_bounds__(BTB) void k_power_totals(int64_t groups, int stride
     }
 }
 
-// the value column the last numeric assembly used (stamp_numeric's choice)
-const double *assembled_values(nodal_ctx *h) {
-    return h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
-}
-
-int64_t row_groups(int64_t ncomp) { return (ncomp + BTB - 1) / BTB; }
-
 }  // namespace
 
 // voltage / current / power [ncomp] and totals2 = {dissipated, absorbed_by_sources} of the solution in h->x, to the
@@ -220,7 +211,7 @@ int branch_single(nodal_ctx *h, double *voltage, double *current, double *power,
     if (totals2) totals2[0] = totals2[1] = 0.0;
     if (ncomp == 0) return NODAL_OK;
     hipStream_t st = h->stream;
-    const int64_t groups = row_groups(ncomp);
+    const int64_t groups = groups_of(ncomp, BTB);
     double *out[3] = {voltage, current, power};
     int wanted = 0;
     for (double *p : out) wanted += p ? 1 : 0;
@@ -246,7 +237,7 @@ int branch_single(nodal_ctx *h, double *voltage, double *current, double *power,
 
 int branch_sweep_begin(nodal_ctx *h, BranchSweep *env, int32_t count) {
     const int64_t ncomp = h->ncomp, K = h->K;
-    const int64_t groups = row_groups(ncomp);
+    const int64_t groups = groups_of(ncomp, BTB);
     // doubles first (absmax [ncomp], min [K], max [K]), then their members as int32
     const size_t doubles = (size_t)(ncomp + 2 * K), bytes = doubles * 8 + doubles * 4;
     NODAL_HIP_TRY(h, h->br_env.reserve(bytes + 64));
@@ -270,7 +261,7 @@ int branch_sweep_begin(nodal_ctx *h, BranchSweep *env, int32_t count) {
 int branch_sweep_block(nodal_ctx *h, const BranchSweep *env, int32_t m0, int cols, const double *rows,
                        const int32_t *info, const double *swept_dev, const int32_t *slot_dev, int32_t nsrc) {
     const int64_t ncomp = h->ncomp, n = h->n;
-    const int64_t groups = row_groups(ncomp);
+    const int64_t groups = groups_of(ncomp, BTB);
     hipStream_t st = h->stream;
     for (int g0 = 0; g0 < cols; g0 += BCOLS) {
         const int c = cols - g0 < BCOLS ? cols - g0 : BCOLS;

@@ -398,6 +398,11 @@ int stamp_to_dense(nodal_ctx *h, double *G_dev, int64_t ld, bool col_major);
 int stamp_sweep_slots(nodal_ctx *h, const int32_t *rows_dev, int32_t nsrc, int32_t *slot_dev, int32_t *bad_dev);
 int stamp_rhs_multi(nodal_ctx *h, const int32_t *slot_dev, const double *swept_dev, int32_t nsrc, int32_t cols,
                     double *out, int64_t rs, int64_t cs);
+// The swept rows of a call (api.hip): in range, narrowed and uploaded to rows_dev, stamp_sweep_slots, and the verdict read
+// back (one wait) -- E_INVALID for a row out of range, one that is no A / E source, one named twice.  The texts are
+// `prefix` + ["a "] + `row` + what is wrong: ("source sweep: ", "row"), ("gradient: ", "swept row").
+int sweep_check_rows(nodal_ctx *h, const char *prefix, const char *row, int32_t nsrc, const int64_t *rows,
+                     int32_t *rows_dev, int32_t *slot_dev, int32_t *bad_dev);
 // ---- same G, many right-hand sides (multi_rhs_solve in sparse.hip) ----
 // What a front end tells the one driver of source sweeps, port matrices and adjoint sensitivities.  Columns are
 // addressed as element (row, y) at [row * rs + y * cs] throughout.
@@ -499,10 +504,14 @@ int sens_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, const d
 int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const int32_t *p, const int32_t *q2,
              double *sens_out, double *value_out, double *adjoint_out, double *resid_out, int32_t *info_out);
 void sens_free_child(nodal_ctx *h);
-// what the gradient (gradient.hip) shares with the call above: the CCVS / CCCS rows grouped by their driving resistor
-// (sn_cross, sn_ndrivers, sn_ncross; kept per table_epoch) and the child context that holds G^T (h->adjoint)
+// what the gradients (gradient.hip, transient_gradient.hip) share with the call above: the CCVS / CCCS rows grouped by
+// their driving resistor (sn_cross, sn_ndrivers, sn_ncross; kept per table_epoch) and the child context that holds G^T
+// (h->adjoint)
 int sens_cross_list(nodal_ctx *h);
 int sens_transposed_child(nodal_ctx *h);
+// *s: the context the transposed solves run on -- h itself when G is symmetric (B == 0 and passive), otherwise the
+// child, brought up to date
+int adjoint_context(nodal_ctx *h, nodal_ctx **s);
 
 // ---- loss gradients (gradient.hip; the transposed solves: multi_rhs_solve in sparse.hip) ----
 // one adjoint solve per member with the caller's dense cotangent, the per-row formulas summed over the members on the
@@ -558,7 +567,11 @@ int transient_solver_begin(nodal_ctx *h, TransientSolver &ts, bool dense, int32_
 // device.  *inf > 0: singular, nothing was judged.
 int transient_solver_step(nodal_ctx *h, TransientSolver &ts, const double *bvec, double *xk, int32_t *inf, int32_t *it,
                           double *resid_host, bool *judged, double *ms_matrix);
-// rhs += S (g o S^T x_prev), the capacitors' history currents (k_transient_history with `method`, then k_transient_rhs
+// out[node[e]] += the signed sum of src over entry e's contributions (a group.h node list: item << 3 | slot, slot 0 adds,
+// any other subtracts), in list order, one lane per entry and no atomics; nent == 0 launches nothing
+int signed_list_add(nodal_ctx *h, int64_t nent, const int32_t *node, const int32_t *cptr, const uint32_t *contrib,
+                    const double *src, double *out);
+// rhs += S (g o S^T x_prev), the capacitors' history currents (k_transient_history with `method`, then signed_list_add
 // over the node list of the last transient_run: tr_node, tr_ptr, tr_con); hist [ncap] is scratch.  A run with inductors
 // passes hist [ncap + nind] whose last nind words it formed itself (transient.hip); ncap == 0 skips the first kernel.
 int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t *rows_dev, int64_t nent, const double *x_prev,

@@ -19,7 +19,7 @@
 // brought up sixteen rows at a time and written in whatever layout the route asks for -- for the interleaved block that
 // is a [16][n] -> [n][16] transposition, k_gradient_interleave -- and a finished block meets its members' solutions in the
 // same layout.
-#include "ctx.h"
+#include "table_rows.h"
 
 #include <algorithm>
 
@@ -27,18 +27,6 @@ namespace {
 
 constexpr int STB = 256;
 constexpr int SCOLS = 16;  // members per launch of the table kernels (SLU_MULTI)
-
-int64_t groups_of(int64_t items) { return (items + STB - 1) / STB; }
-
-// the value column the last numeric assembly used (stamp_numeric's choice)
-const double *assembled_values(nodal_ctx *h) {
-    return h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
-}
-
-// element (j, y) of a block, +0.0 for the ground lead
-__device__ __forceinline__ double lead(const double *__restrict__ v, int32_t node, int64_t rs, int64_t at) {
-    return node < 0 ? 0.0 : v[(int64_t)node * rs + at];
-}
 
 // ---- rows -> the layout a route asks for -------------------------------------------------------------------------
 // out[i * rs + y * cs] = src[y * n + i], y < cols: the dense panel's columns, [cols][n] rows, a column alone.  One
@@ -72,9 +60,9 @@ __global__ __launch_bounds__(64) void k_gradient_interleave(int64_t n, int cols,
 }
 
 // ---- the table kernels ---------------------------------------------------------------------------------------------
-// One thread per table row for the whole block of members: the row's record is loaded once, then per member y the term
-// D_y * w_y with D = L(j1) - L(j2) and w = 1 (A, E), u / v^2 (R), u (VCVS), -u / Rd (CCVS, CCCS), u = X(p1) - X(p2) --
-// added one after the other, in member order, onto grad[i].
+// One thread per table row for the whole block of members: the row's record is decoded once (row_term, table_rows.h),
+// then per member y the term D_y * w_y with D = L(j1) - L(j2) and w = u / den, u = X(p1) - X(p2), or 1 for a row that
+// does not read x -- added one after the other, in member order, onto grad[i].
 // IL: lam and x are interleaved by row, element (j, y) at [j * 16 + y] -- the sixteen L (or X) of a lead are one
 // 128-byte line, fetched as eight 16-byte loads; otherwise element (j, y) at lam[j * rs + y * cs] / x[j * xrs + y * xcs].
 template <bool IL>
@@ -89,33 +77,11 @@ __global__ __launch_bounds__(STB) void k_gradient_block(int64_t ncomp, int32_t K
                                                         double *__restrict__ grad) {
     const int64_t i = (int64_t)blockIdx.x * STB + threadIdx.x;
     if (i >= ncomp) return;
-    const int t = type[i];
-    int32_t j1 = -1, j2 = -1, p1 = -1, p2 = -1;
-    bool reads_x = false;
-    double den = 1.0;  // w = u / den
-    if (t == NODAL_T_R) {
-        j1 = p1 = a[i];
-        j2 = p2 = b[i];
-        const double v = value[i];
-        den = v * v;
-        reads_x = true;
-    } else if (t == NODAL_T_A) {
-        j1 = a[i];
-        j2 = b[i];
-    } else if (t <= NODAL_T_CCCS && k[i] >= 0) {
-        j1 = K + k[i];
-        if (t != NODAL_T_E) {
-            p1 = c[i];
-            p2 = d[i];
-            reads_x = true;
-            if (t != NODAL_T_VCVS) {
-                const int32_t dr = drv[i];
-                den = -(dr >= 0 ? value[dr] : 1.0);
-            }
-        }
-    } else {
-        return;  // (a row without a term: its sum stays the zero it started from)
-    }
+    const RowTerm r = row_term(i, K, type, value, a, b, c, d, drv, k);
+    if (r.none) return;  // (its sum stays the zero it started from)
+    const int32_t j1 = r.j1, j2 = r.j2, p1 = r.p1, p2 = r.p2;
+    const bool reads_x = r.reads_x;
+    const double den = r.den;  // w = u / den
     double acc = grad[i];
     if constexpr (IL) {
         const double2 *l1 = reinterpret_cast<const double2 *>(lam + (int64_t)(j1 < 0 ? 0 : j1) * SCOLS);
@@ -169,10 +135,8 @@ __global__ __launch_bounds__(STB) void k_gradient_cross(int64_t ndrivers, int32_
     double acc = grad[i];
     for (int y = 0; y < cols; ++y)
         for (int32_t q = gptr[g]; q < gptr[g + 1]; ++q) {
-            const int32_t j = rows[q];
-            const double u = lead(x, c[j], xrs, (int64_t)y * xcs) - lead(x, d[j], xrs, (int64_t)y * xcs);
-            const double lm = lam[((int64_t)K + k[j]) * rs + (int64_t)y * cs];
-            const double term = lm * value[j] * u / (v * v);
+            const double term =
+                cross_term(rows[q], K, v, value, c, d, k, lam, rs, (int64_t)y * cs, x, xrs, (int64_t)y * xcs);
             acc += term;
         }
     grad[i] = acc;
@@ -213,7 +177,7 @@ struct GradientClient final : MultiRhsClient {
             k_gradient_interleave<<<(unsigned)((n + 63) / 64), 64, 0, h->stream>>>(n, cols, src, stride, out);
         } else {
             if (stride != n) return nodal_fail(h, NODAL_E_INVALID, "gradient: rows of another stride");
-            k_gradient_spread<<<(unsigned)groups_of(n * cols), STB, 0, h->stream>>>(n, cols, src, out, rs, cs);
+            k_gradient_spread<<<groups_of(n * cols, STB), STB, 0, h->stream>>>(n, cols, src, out, rs, cs);
         }
         NODAL_HIP_TRY(h, hipGetLastError());
         return NODAL_OK;
@@ -285,14 +249,14 @@ int grad_launch_table(nodal_ctx *h, int cols, const double *lam, int64_t rs, int
     const bool il = rs == SCOLS && cs == 1;
     const double *value = assembled_values(h);
     auto launch = il ? k_gradient_block<true> : k_gradient_block<false>;
-    launch<<<(unsigned)groups_of(ncomp), STB, 0, st>>>(ncomp, h->K, cols, h->type.as<uint8_t>(), value, h->a.as<int32_t>(),
-                                                      h->b.as<int32_t>(), h->c.as<int32_t>(), h->d.as<int32_t>(),
-                                                      h->drv.as<int32_t>(), h->k.as<int32_t>(), lam, rs, cs, x, xrs, xcs,
-                                                      grad_dev);
+    launch<<<groups_of(ncomp, STB), STB, 0, st>>>(ncomp, h->K, cols, h->type.as<uint8_t>(), value, h->a.as<int32_t>(),
+                                                  h->b.as<int32_t>(), h->c.as<int32_t>(), h->d.as<int32_t>(),
+                                                  h->drv.as<int32_t>(), h->k.as<int32_t>(), lam, rs, cs, x, xrs, xcs,
+                                                  grad_dev);
     if (h->sn_ncross > 0) {
         const int32_t *drivers = h->sn_cross.as<int32_t>(), *gptr = drivers + h->sn_ndrivers,
                       *grows = gptr + h->sn_ndrivers + 1;
-        k_gradient_cross<<<(unsigned)groups_of(h->sn_ndrivers), STB, 0, st>>>(
+        k_gradient_cross<<<groups_of(h->sn_ndrivers, STB), STB, 0, st>>>(
             h->sn_ndrivers, h->K, cols, drivers, gptr, grows, h->type.as<uint8_t>(), value, h->c.as<int32_t>(),
             h->d.as<int32_t>(), h->k.as<int32_t>(), lam, rs, cs, x, xrs, xcs, grad_dev);
     }
@@ -302,7 +266,7 @@ int grad_launch_table(nodal_ctx *h, int cols, const double *lam, int64_t rs, int
 
 int grad_launch_sources(nodal_ctx *h, int cols, int32_t nsrc, const int32_t *swept_dev, const double *lam, int64_t rs,
                         int64_t cs, double *out) {
-    k_gradient_sources<<<(unsigned)groups_of((int64_t)cols * nsrc), STB, 0, h->stream>>>(
+    k_gradient_sources<<<groups_of((int64_t)cols * nsrc, STB), STB, 0, h->stream>>>(
         cols, nsrc, h->K, swept_dev, h->type.as<uint8_t>(), h->a.as<int32_t>(), h->b.as<int32_t>(), h->k.as<int32_t>(), lam,
         rs, cs, out);
     NODAL_HIP_TRY(h, hipGetLastError());
@@ -318,20 +282,9 @@ int grad_run(nodal_ctx *h, bool dense, int32_t count, const double *x, const dou
     const int32_t pad = (nsrc + 15) & ~15;
     NODAL_HIP_TRY(h, h->gr_spec.reserve((size_t)(pad + 16 + ncomp) * 4 + 64));
     int32_t *swept_dev = h->gr_spec.as<int32_t>();
-    if (nsrc > 0) {
-        std::vector<int32_t> r32((size_t)nsrc);
-        for (int32_t j = 0; j < nsrc; ++j) {
-            if (rows[j] < 0 || rows[j] >= ncomp) return nodal_fail(h, NODAL_E_INVALID, "gradient: swept row out of range");
-            r32[j] = (int32_t)rows[j];
-        }
-        int32_t *bad_dev = swept_dev + pad, *slot_dev = bad_dev + 16;
-        NODAL_HIP_TRY(h, hipMemcpyAsync(swept_dev, r32.data(), (size_t)nsrc * 4, hipMemcpyHostToDevice, st));
-        NODAL_TRY(stamp_sweep_slots(h, swept_dev, nsrc, slot_dev, bad_dev));
-        int32_t bad = 0;
-        NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copy above is done too)
-        if (bad & 1) return nodal_fail(h, NODAL_E_INVALID, "gradient: a swept row that is not an independent source (A or E)");
-        if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, "gradient: a swept row named twice");
-    }
+    if (nsrc > 0)
+        NODAL_TRY(sweep_check_rows(h, "gradient: ", "swept row", nsrc, rows, swept_dev, swept_dev + pad + 16,
+                                   swept_dev + pad));
     for (int64_t i = 0; i < ncomp; ++i) grad_out[i] = 0.0;
     if (count == 0) return NODAL_OK;
     if (n == 0) {  // (every lead is ground: nothing depends on anything)
@@ -366,12 +319,8 @@ int grad_run(nodal_ctx *h, bool dense, int32_t count, const double *x, const dou
     client.gsrc_out = grad_sources_out;
     client.adjoint_out = adjoint_out;
 
-    const bool passive = h->B == 0 && h->passive_network;
-    nodal_ctx *s = h;
-    if (!passive) {
-        NODAL_TRY(sens_transposed_child(h));
-        s = h->adjoint;
-    }
+    nodal_ctx *s = nullptr;
+    NODAL_TRY(adjoint_context(h, &s));
     int status = keep.restore(h, multi_rhs_solve(h, s, dense, count, resid_out, info_out, client), "gradient");
     if (status == NODAL_OK) {
         // the sum is not defined with a member missing

@@ -15,7 +15,7 @@
 // block of right-hand sides where a sweep folds its members' sources, and k_port_gather reads a finished block at the
 // port nodes into Z on the device where a sweep's rows would go down to the host.
 // Z comes down once, P x P numbers instead of P x n.  No floating-point atomics: a repeated call returns the same bits.
-#include "ctx.h"
+#include "table_rows.h"
 
 namespace {
 
@@ -60,8 +60,6 @@ __global__ __launch_bounds__(PTB) void k_port_gather(int32_t nports, int cols, i
     out[p * ld + m0 + y] = v;
 }
 
-unsigned groups_of(int64_t items) { return (unsigned)((items + PTB - 1) / PTB); }
-
 }  // namespace
 
 int port_rhs_block(nodal_ctx *h, const PortCall *call, int32_t m0, int cols, double *out, int64_t rs, int64_t cs) {
@@ -80,8 +78,8 @@ int port_gather_block(nodal_ctx *h, const PortCall *call, int32_t m0, int cols, 
     for (int y = 0; y < cols; ++y)
         if (info[m0 + y] > 0) bad.word[y >> 5] |= 1u << (y & 31);
     const int64_t P = call->nports;
-    k_port_gather<<<groups_of(P * cols), PTB, 0, h->stream>>>(call->nports, cols, m0, call->ia, call->ib, rows, 1, h->n, bad,
-                                                             call->z, P);
+    k_port_gather<<<groups_of(P * cols, PTB), PTB, 0, h->stream>>>(call->nports, cols, m0, call->ia, call->ib, rows, 1, h->n, bad,
+                                                                  call->z, P);
     NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }
@@ -135,8 +133,8 @@ int port_run(nodal_ctx *h, bool dense, int32_t nports, const int32_t *ia, const 
     HandleKeeper keep;
     NODAL_TRY(keep.save(h, h->have_x));
     if (voc_out) {
-        k_port_gather<<<groups_of(P), PTB, 0, st>>>(nports, 1, 0, ia_dev, ib_dev, h->sn_x.as<double>(), 1, n, PortFlags{},
-                                                   voc_dev, 1);
+        k_port_gather<<<groups_of(P, PTB), PTB, 0, st>>>(nports, 1, 0, ia_dev, ib_dev, h->sn_x.as<double>(), 1, n, PortFlags{},
+                                                        voc_dev, 1);
         NODAL_HIP_TRY(h, hipGetLastError());
         NODAL_HIP_TRY(h, hipMemcpyAsync(voc_out, voc_dev, (size_t)P * 8, hipMemcpyDeviceToHost, st));
     }

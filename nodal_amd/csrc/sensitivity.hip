@@ -24,7 +24,7 @@
 // over the columns (rows come out with sorted columns, and the same input gives the same pattern), once per
 // struct_epoch of the parent, and its values are gathered from the parent's `data` through the kept permutation on
 // every call.
-#include "ctx.h"
+#include "table_rows.h"
 
 #include <algorithm>
 
@@ -32,10 +32,6 @@ namespace {
 
 constexpr int STB = 256;
 constexpr int SCOLS = 16;  // outputs per launch of the table kernels (SLU_MULTI)
-
-__device__ __forceinline__ double lead(const double *__restrict__ x, int32_t node) { return node < 0 ? 0.0 : x[node]; }
-
-int64_t groups_of(int64_t items) { return (items + STB - 1) / STB; }
 
 // ---- the outputs: check, value, right-hand side ----------------------------------------------------------------
 // One thread per output q: value[q] = c^T x; *bad |= 1 for the current of a row that has none of its own to
@@ -111,37 +107,19 @@ __global__ __launch_bounds__(STB) void k_sensitivity_block(int64_t ncomp, int32_
                                                            double *__restrict__ sens) {
     const int64_t i = (int64_t)blockIdx.x * STB + threadIdx.x;
     if (i >= ncomp) return;
-    const int t = type[i];
-    const double v = value[i];
-    // D = L(j1) - L(j2) with j2 = -1 for the rows that read their branch unknown alone; w: the row's own factor
-    int32_t j1 = -1, j2 = -1;
-    double w = 0.0, expl = 0.0;
-    if (t == NODAL_T_R) {
-        j1 = a[i];
-        j2 = b[i];
-        const double u = lead(x, j1) - lead(x, j2);
-        w = u / (v * v);
-        expl = -(u / v) / v;
-    } else if (t == NODAL_T_A) {
-        j1 = a[i];
-        j2 = b[i];
-        w = 1.0;
-    } else if (t <= NODAL_T_CCCS && k[i] >= 0) {
-        j1 = K + k[i];
-        if (t == NODAL_T_E) {
-            w = 1.0;
-        } else {
-            const double u = lead(x, c[i]) - lead(x, d[i]);
-            if (t == NODAL_T_VCVS) {
-                w = u;
-            } else {
-                const int32_t dr = drv[i];
-                const double Rd = dr >= 0 ? value[dr] : 1.0;
-                w = -u / Rd;
-            }
+    // D = L(j1) - L(j2); w: the row's own factor, 0 for a row without a term; expl: a resistor's explicit term
+    const RowTerm r = row_term(i, K, type, value, a, b, c, d, drv, k);
+    const int32_t j1 = r.j1, j2 = r.j2;
+    const bool mine = type[i] == NODAL_T_R;
+    double w = r.none ? 0.0 : 1.0, expl = 0.0;
+    if (r.reads_x) {
+        const double u = lead(x, r.p1) - lead(x, r.p2);
+        w = u / r.den;
+        if (mine) {
+            const double v = value[i];
+            expl = -(u / v) / v;
         }
     }
-    const bool mine = t == NODAL_T_R;
     if constexpr (IL) {
         double D[SCOLS];
         const double2 *l1 = reinterpret_cast<const double2 *>(lam + (int64_t)(j1 < 0 ? 0 : j1) * SCOLS);
@@ -195,10 +173,7 @@ __global__ __launch_bounds__(STB) void k_sensitivity_cross(int64_t ndrivers, int
     const double v = value[i];
     double acc = sens[(int64_t)y * ncomp + i];
     for (int32_t q = gptr[g]; q < gptr[g + 1]; ++q) {
-        const int32_t j = rows[q];
-        const double u = lead(x, c[j]) - lead(x, d[j]);
-        const double lm = lam[((int64_t)K + k[j]) * rs + (int64_t)y * cs];
-        const double term = lm * value[j] * u / (v * v);
+        const double term = cross_term(rows[q], K, v, value, c, d, k, lam, rs, (int64_t)y * cs, x, 1, 0);
         acc += term;
     }
     sens[(int64_t)y * ncomp + i] = acc;
@@ -211,14 +186,11 @@ __global__ __launch_bounds__(STB) void k_gather_values(int64_t nnz, const int32_
     if (q < nnz) out[q] = data[perm[q]];
 }
 
-// the value column the last numeric assembly used (stamp_numeric's choice)
-const double *assembled_values(nodal_ctx *h) {
-    return h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
-}
+}  // namespace
 
 // The CCVS / CCCS rows grouped by their driver, in table order inside a group, groups by driver row: kept on the
 // device per table_epoch as [drivers (nd) | gptr (nd + 1) | rows (nc)].
-int ensure_cross_list(nodal_ctx *h) {
+int sens_cross_list(nodal_ctx *h) {
     if (h->sn_cross_epoch == h->table_epoch) return NODAL_OK;
     h->sn_ndrivers = h->sn_ncross = 0;
     const int64_t ncomp = h->ncomp;
@@ -283,7 +255,7 @@ int ensure_cross_list(nodal_ctx *h) {
 }
 
 // The child context with G^T: made once, its pattern rebuilt when the parent's moves, its values gathered every call.
-int ensure_transposed_child(nodal_ctx *h) {
+int sens_transposed_child(nodal_ctx *h) {
     const int64_t n = h->n, nnz = h->nnz;
     hipStream_t st = h->stream;
     if (!h->adjoint) {
@@ -364,18 +336,21 @@ int ensure_transposed_child(nodal_ctx *h) {
         h->adjoint_epoch = h->struct_epoch;
     }
     if (nnz > 0) {
-        k_gather_values<<<(unsigned)groups_of(nnz), STB, 0, st>>>(nnz, h->sn_perm.as<int32_t>(), h->data.as<double>(),
-                                                                 c->data.as<double>());
+        k_gather_values<<<groups_of(nnz, STB), STB, 0, st>>>(nnz, h->sn_perm.as<int32_t>(), h->data.as<double>(),
+                                                             c->data.as<double>());
         NODAL_HIP_TRY(h, hipGetLastError());
     }
     c->have_numeric = true;
     return NODAL_OK;
 }
 
-}  // namespace
-
-int sens_cross_list(nodal_ctx *h) { return ensure_cross_list(h); }
-int sens_transposed_child(nodal_ctx *h) { return ensure_transposed_child(h); }
+int adjoint_context(nodal_ctx *h, nodal_ctx **s) {
+    *s = h;
+    if (h->B == 0 && h->passive_network) return NODAL_OK;
+    NODAL_TRY(sens_transposed_child(h));
+    *s = h->adjoint;
+    return NODAL_OK;
+}
 
 void sens_free_child(nodal_ctx *h) {
     if (!h->adjoint) return;
@@ -406,14 +381,14 @@ int sens_block(nodal_ctx *h, const SensCall *call, int32_t m0, int cols, const d
         const double *value = assembled_values(h);
         const bool il = rs == SCOLS && cs == 1;
         auto launch = il ? k_sensitivity_block<true> : k_sensitivity_block<false>;
-        launch<<<(unsigned)groups_of(ncomp), STB, 0, st>>>(ncomp, h->K, cols, h->type.as<uint8_t>(), value,
-                                                          h->a.as<int32_t>(), h->b.as<int32_t>(), h->c.as<int32_t>(),
-                                                          h->d.as<int32_t>(), h->drv.as<int32_t>(), h->k.as<int32_t>(),
-                                                          call->x, lam, rs, cs, ex, sens);
+        launch<<<groups_of(ncomp, STB), STB, 0, st>>>(ncomp, h->K, cols, h->type.as<uint8_t>(), value,
+                                                      h->a.as<int32_t>(), h->b.as<int32_t>(), h->c.as<int32_t>(),
+                                                      h->d.as<int32_t>(), h->drv.as<int32_t>(), h->k.as<int32_t>(),
+                                                      call->x, lam, rs, cs, ex, sens);
         if (h->sn_ncross > 0) {
             const int32_t *drivers = h->sn_cross.as<int32_t>(), *gptr = drivers + h->sn_ndrivers,
                           *rows = gptr + h->sn_ndrivers + 1;
-            k_sensitivity_cross<<<(unsigned)groups_of(h->sn_ndrivers * SCOLS), STB, 0, st>>>(
+            k_sensitivity_cross<<<groups_of(h->sn_ndrivers * SCOLS, STB), STB, 0, st>>>(
                 h->sn_ndrivers, ncomp, h->K, cols, drivers, gptr, rows, h->type.as<uint8_t>(), value, h->c.as<int32_t>(),
                 h->d.as<int32_t>(), h->k.as<int32_t>(), call->x, lam, rs, cs, sens);
         }
@@ -481,15 +456,15 @@ int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const
     // multigrid route writes h->x
     HandleKeeper keep;
     NODAL_TRY(keep.save(h, true));
-    k_sens_values<<<(unsigned)groups_of(count), STB, 0, st>>>(count, h->K, kind_dev, p_dev, q2_dev, h->type.as<uint8_t>(),
-                                                             assembled_values(h), h->a.as<int32_t>(), h->b.as<int32_t>(),
-                                                             h->k.as<int32_t>(), h->sn_x.as<double>(), value_dev, bad_dev);
+    k_sens_values<<<groups_of(count, STB), STB, 0, st>>>(count, h->K, kind_dev, p_dev, q2_dev, h->type.as<uint8_t>(),
+                                                         assembled_values(h), h->a.as<int32_t>(), h->b.as<int32_t>(),
+                                                         h->k.as<int32_t>(), h->sn_x.as<double>(), value_dev, bad_dev);
     NODAL_HIP_TRY(h, hipGetLastError());
     if (value_out) NODAL_HIP_TRY(h, hipMemcpyAsync(value_out, value_dev, (size_t)count * 8, hipMemcpyDeviceToHost, st));
     int32_t bad = 0;
     NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the host copies above are done too)
     if (bad) return nodal_fail(h, NODAL_E_INVALID, "sensitivities: the current of a current source is its value, not an output");
-    NODAL_TRY(ensure_cross_list(h));
+    NODAL_TRY(sens_cross_list(h));
 
     SensCall call;
     call.kind = kind_dev;
@@ -508,12 +483,8 @@ int sens_run(nodal_ctx *h, bool dense, int32_t count, const int32_t *kind, const
         }
         return NODAL_OK;
     }
-    const bool passive = h->B == 0 && h->passive_network;
-    nodal_ctx *s = h;
-    if (!passive) {
-        NODAL_TRY(ensure_transposed_child(h));
-        s = h->adjoint;
-    }
+    nodal_ctx *s = nullptr;
+    NODAL_TRY(adjoint_context(h, &s));
     AdjointClient client(h, &call);
     int status = keep.restore(h, multi_rhs_solve(h, s, dense, count, resid_out, info_out, client), "sensitivities");
     const int w = nodal_wait_stream(h, st, NODAL_SITE);

@@ -12,7 +12,7 @@
 // with v = x(a) - x(b) of the previous solution.  A step is, on the handle's stream,
 //     k_transient_history   one lane per capacitor: J_k from x_{k-1}, one state word per capacitor
 //     stamp_rhs_multi       the sources of step k into a zeroed vector (one column)
-//     k_transient_rhs       one lane per node with capacitors: +-J of its capacitors in list order, no atomics
+//     k_signed_list_add       one lane per node with capacitors: +-J of its capacitors in list order, no atomics
 //     the solve             multigrid (the hierarchy of step 1), sparse LU (factored once) or the dense panel (n <= 64)
 //     the judgement         the block judge of multi_rhs_solve on one column
 //     k_transient_probe     row k of the waveforms
@@ -27,13 +27,14 @@
 // writes x_k into row k of tr_tape instead of the two alternating vectors and leaves the tape for that sweep.
 //
 // Inductors (nodal_transient_rlc) are companion R rows too, g = h / L (Euler) or h / (2 L) (trapezoidal), behind the
-// capacitors' in the row list, the history array and the node lists, so k_transient_rhs serves both.  What differs is
+// capacitors' in the row list, the history array and the node lists, so k_signed_list_add serves both.  What differs is
 // the state: the inductor's current i (positive from lead a to lead b through the element),
 //     Euler:        i_k = i_{k-1} + g v_k,              J_k = -i_{k-1}
 //     trapezoidal:  i_k = i_{k-1} + g (v_k + v_{k-1}),  J_k = -(i_{k-1} + g v_{k-1})
 // so that i_k = -J_k + g v_k in both: the lane finishes i_k and forms J_{k+1} from x_k alone, AFTER the solve, where a
 // capacitor's lane forms J_k from x_{k-1} before it.
 #include "group.h"
+#include "table_rows.h"
 
 #include <chrono>
 
@@ -41,15 +42,6 @@ namespace {
 
 constexpr int TTB = 256;
 constexpr int RING = 8;  // kept solutions staged on the device before they go down in one copy
-
-unsigned groups_of(int64_t items) { return (unsigned)((items + TTB - 1) / TTB); }
-
-// the value column the last numeric assembly used (stamp_numeric's choice)
-const double *assembled_values(nodal_ctx *h) {
-    return h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
-}
-
-__device__ __forceinline__ double lead(const double *__restrict__ x, int32_t node) { return node < 0 ? 0.0 : x[node]; }
 
 // grouping enumerator (group.h): capacitor i touches node a (slot 0: +J) and node b (slot 1: -J); one column, so a
 // node's capacitors form ONE entry whose run lists capacitor << 3 | slot in ascending (capacitor, slot) order
@@ -124,21 +116,22 @@ __global__ __launch_bounds__(TTB) void k_transient_current_probe(int32_t ncur, c
     if (q < ncur) out[q] = cur[index[q]];
 }
 
-// One lane per entry of the node list: rhs[node] += the +-J of the node's capacitors, then of its inductors, in list
-// order.  The lane is the only writer of its node's row.
-__global__ __launch_bounds__(TTB) void k_transient_rhs(int64_t nent, const int32_t *__restrict__ node,
-                                                       const int32_t *__restrict__ cptr, const uint32_t *__restrict__ contrib,
-                                                       const double *__restrict__ hist, double *__restrict__ rhs) {
+// One lane per entry of a group.h node list: out[node] += the signed values of the node's contributions, src[item] for
+// slot 0 and -src[item] for any other, in list order -- the +-J of a node's capacitors and then of its inductors, the
+// +-w of a node's probes.  The lane is the only writer of its node's row.
+__global__ __launch_bounds__(TTB) void k_signed_list_add(int64_t nent, const int32_t *__restrict__ node,
+                                                         const int32_t *__restrict__ cptr, const uint32_t *__restrict__ contrib,
+                                                         const double *__restrict__ src, double *__restrict__ out) {
     const int64_t e = (int64_t)blockIdx.x * TTB + threadIdx.x;
     if (e >= nent) return;
     const int32_t row = node[e];
-    double acc = rhs[row];
+    double acc = out[row];
     for (int32_t p = cptr[e]; p < cptr[e + 1]; ++p) {
         const uint32_t u = contrib[p];
-        const double j = hist[u >> 3];
-        acc += (u & 7u) ? -j : j;
+        const double v = src[u >> 3];
+        acc += (u & 7u) ? -v : v;
     }
-    rhs[row] = acc;
+    out[row] = acc;
 }
 
 // out[p] = x(a_p) - x(b_p); a probe between a node and itself reads +0.0 whatever x holds
@@ -190,17 +183,20 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
+int signed_list_add(nodal_ctx *h, int64_t nent, const int32_t *node, const int32_t *cptr, const uint32_t *contrib,
+                    const double *src, double *out) {
+    if (nent > 0) k_signed_list_add<<<groups_of(nent, TTB), TTB, 0, h->stream>>>(nent, node, cptr, contrib, src, out);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
 int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t *rows_dev, int64_t nent, const double *x_prev,
                           double *hist, double *rhs) {
     hipStream_t st = h->stream;
     if (ncap > 0)  // (0: inductors alone, whose words of hist are formed after each solve)
-        k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, method, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(),
-                                                            assembled_values(h), x_prev, hist);
-    if (nent > 0)
-        k_transient_rhs<<<groups_of(nent), TTB, 0, st>>>(nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(),
-                                                        h->tr_con.as<uint32_t>(), hist, rhs);
-    NODAL_HIP_TRY(h, hipGetLastError());
-    return NODAL_OK;
+        k_transient_history<<<groups_of(ncap, TTB), TTB, 0, st>>>(ncap, method, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(),
+                                                                 assembled_values(h), x_prev, hist);
+    return signed_list_add(h, nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(), h->tr_con.as<uint32_t>(), hist, rhs);
 }
 
 int transient_solver_begin(nodal_ctx *h, TransientSolver &ts, bool dense, int32_t steps, bool *dead, double *ms_matrix) {
@@ -273,11 +269,11 @@ int transient_solver_step(nodal_ctx *h, TransientSolver &ts, const double *bvec,
         bool redo = ts.all_direct;
         if (!ts.all_direct) {
             NODAL_TRY(nodal_lift_error(h, s, slu_apply(s, bvec, xk)));
-            k_transient_defect<<<groups_of(n), TTB, 0, st>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(),
-                                                            s->data.as<double>(), xk, bvec, ts.rvec);
+            k_transient_defect<<<groups_of(n, TTB), TTB, 0, st>>>(n, s->indptr.as<int32_t>(), s->indices.as<int32_t>(),
+                                                                 s->data.as<double>(), xk, bvec, ts.rvec);
             NODAL_HIP_TRY(h, hipGetLastError());
             NODAL_TRY(nodal_lift_error(h, s, slu_apply(s, ts.rvec, ts.dvec)));
-            k_transient_correct<<<groups_of(n), TTB, 0, st>>>(n, ts.dvec, xk);
+            k_transient_correct<<<groups_of(n, TTB), TTB, 0, st>>>(n, ts.dvec, xk);
             NODAL_HIP_TRY(h, hipGetLastError());
             NODAL_TRY(nodal_lift_error(h, s, csr_judge_block(s, xk, bvec, 1, 0, 1, ts.norms)));
             NODAL_TRY(nodal_read_words(h, resid_host, ts.norms + 4 * SLU_MULTI, 8));
@@ -374,20 +370,18 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         for (int64_t i = 0; i < ncap; ++i) r32[(size_t)i] = (int32_t)cap_rows[i];
         for (int64_t j = 0; j < nind; ++j) r32[(size_t)(ncap + j)] = (int32_t)ind.rows[j];
         NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nitems * 4, hipMemcpyHostToDevice, st));
-        int32_t bad = 0;
-        if (ncap > 0) {
+        const struct { int64_t at, count; const char *message; } kinds[2] = {
+            {0, ncap, "transient: a capacitor row that is not a resistor (R)"},
+            {ncap, nind, "transient: an inductor row that is not a resistor (R)"}};
+        for (const auto &kind : kinds) {
+            if (kind.count == 0) continue;
+            int32_t bad = 0;
             NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
-            k_transient_check<<<groups_of(ncap), TTB, 0, st>>>(ncap, rows_dev, h->type.as<uint8_t>(), bad_dev);
+            k_transient_check<<<groups_of(kind.count, TTB), TTB, 0, st>>>(kind.count, rows_dev + kind.at, h->type.as<uint8_t>(),
+                                                                       bad_dev);
             NODAL_HIP_TRY(h, hipGetLastError());
             NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copy above is done too)
-            if (bad) return nodal_fail(h, NODAL_E_INVALID, "transient: a capacitor row that is not a resistor (R)");
-        }
-        if (nind > 0) {
-            NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
-            k_transient_check<<<groups_of(nind), TTB, 0, st>>>(nind, rows_dev + ncap, h->type.as<uint8_t>(), bad_dev);
-            NODAL_HIP_TRY(h, hipGetLastError());
-            NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));
-            if (bad) return nodal_fail(h, NODAL_E_INVALID, "transient: an inductor row that is not a resistor (R)");
+            if (bad) return nodal_fail(h, NODAL_E_INVALID, kind.message);
         }
         NODAL_TRY(grp::build_lists(h, CapLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), nitems}, (int64_t)K, &nent,
                                    &ncon, h->tr_none, h->tr_node, h->tr_ptr, h->tr_con, nullptr, nullptr));
@@ -439,19 +433,19 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     }
     NODAL_HIP_TRY(h, hipMemcpyAsync(state(0), x0, (size_t)n * 8, hipMemcpyHostToDevice, st));
     if (nprobe > 0) {
-        k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, state(0), wave_dev);
+        k_transient_probe<<<groups_of(nprobe, TTB), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, state(0), wave_dev);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
     const double *value = assembled_values(h);
     if (ncap > 0 && method == 1) {  // J_0 = g v_0
-        k_transient_history<<<groups_of(ncap), TTB, 0, st>>>(ncap, 0, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), value,
-                                                            state(0), hist);
+        k_transient_history<<<groups_of(ncap, TTB), TTB, 0, st>>>(ncap, 0, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), value,
+                                                                 state(0), hist);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
     if (nind > 0) {  // i_0 and J_1, row 0 of the currents
-        k_transient_inductor_start<<<groups_of(nind), TTB, 0, st>>>(nind, method, rows_dev + ncap, h->a.as<int32_t>(),
-                                                                   h->b.as<int32_t>(), value, state(0), i0_dev, icur, hist + ncap);
-        if (ncur > 0) k_transient_current_probe<<<groups_of(ncur), TTB, 0, st>>>(ncur, cidx_dev, icur, cur_dev);
+        k_transient_inductor_start<<<groups_of(nind, TTB), TTB, 0, st>>>(nind, method, rows_dev + ncap, h->a.as<int32_t>(),
+                                                                        h->b.as<int32_t>(), value, state(0), i0_dev, icur, hist + ncap);
+        if (ncur > 0) k_transient_current_probe<<<groups_of(ncur, TTB), TTB, 0, st>>>(ncur, cidx_dev, icur, cur_dev);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
     NODAL_WAIT_STREAM(h, st);  // (x0, i0 and the probes are the caller's, r32 ends here)
@@ -504,16 +498,16 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         if (!judged)
             NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + (k - 1), norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
         if (nind > 0) {  // i_k and J_{k+1}
-            k_transient_inductor<<<groups_of(nind), TTB, 0, st>>>(nind, method, rows_dev + ncap, h->a.as<int32_t>(),
-                                                                 h->b.as<int32_t>(), value, xk, icur, hist + ncap);
+            k_transient_inductor<<<groups_of(nind, TTB), TTB, 0, st>>>(nind, method, rows_dev + ncap, h->a.as<int32_t>(),
+                                                                      h->b.as<int32_t>(), value, xk, icur, hist + ncap);
             if (ncur > 0)
-                k_transient_current_probe<<<groups_of(ncur), TTB, 0, st>>>(ncur, cidx_dev, icur, cur_dev + (size_t)k * ncur);
+                k_transient_current_probe<<<groups_of(ncur, TTB), TTB, 0, st>>>(ncur, cidx_dev, icur, cur_dev + (size_t)k * ncur);
         }
         // what the caller asked for of x_k
-        if (nprobe > 0) k_transient_probe<<<groups_of(nprobe), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, xk, wave_dev + (size_t)k * nprobe);
+        if (nprobe > 0) k_transient_probe<<<groups_of(nprobe, TTB), TTB, 0, st>>>(nprobe, pa_dev, pb_dev, xk, wave_dev + (size_t)k * nprobe);
         if (want_env && K > 0) {
-            k_transient_envelope<<<groups_of(K), TTB, 0, st>>>(K, k, env_first ? 1 : 0, xk, pmin_dev, pmin_step_dev, pmax_dev,
-                                                              pmax_step_dev);
+            k_transient_envelope<<<groups_of(K, TTB), TTB, 0, st>>>(K, k, env_first ? 1 : 0, xk, pmin_dev, pmin_step_dev, pmax_dev,
+                                                                   pmax_step_dev);
             env_first = false;
         }
         NODAL_HIP_TRY(h, hipGetLastError());

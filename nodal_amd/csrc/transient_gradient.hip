@@ -9,7 +9,7 @@
 // The loss reads the probe waveforms; the caller hands over w[k][p] = dL / d wave[k][p], k = 0 .. steps, which makes
 // c_k = sum_p w[k][p] (e(a_p) - e(b_p)).  Backward, with lambda_{steps+1} = 0:
 //     M^T lambda_k = c_k + S (g o S^T lambda_{k+1}),   k = steps .. 1
-// -- the forward step with lambda in the role of x, so k_transient_history (method 0) and k_transient_rhs serve
+// -- the forward step with lambda in the role of x, so k_transient_history (method 0) and k_signed_list_add serve
 // unchanged, and the solve is the forward run's (transient_solver_step) on h itself when M is symmetric (B == 0 and
 // passive: the kept hierarchy or factors serve as they are) and on the child that holds M^T otherwise (factored once,
 // kept under tg_lu_epoch).  The results:
@@ -17,10 +17,11 @@
 //     grad[cap row i]      = sum_k (lambda_k(a) - lambda_k(b)) ((x_k(a) - x_k(b)) - (x_{k-1}(a) - x_{k-1}(b))) / r_i^2
 //     grad_sources[k-1][j] = s_{rows[j]}(lambda_k)
 //     grad_x0              = c_0 + S (g o S^T lambda_1)
-// s_i the per-row formula of gradient.hip.  A step is, on the handle's stream,
-//     k_tgrad_seed          one lane per node with probes: +-w of its probes in list order into the zeroed vector
+// s_i the per-row formula of table_rows.h (row_term), which the companion rows' history term shares (resistor_term).
+// A step is, on the handle's stream,
+//     k_signed_list_add     one lane per node with probes: +-w of its probes in list order into the zeroed vector
 //     k_transient_history   from lambda_{k+1} (skipped at k == steps: it is zero)
-//     k_transient_rhs
+//     k_signed_list_add     the history currents (transient_add_history)
 //     the solve, the judgement
 // and the finished lambda_k of up to sixteen consecutive steps stay in a [16][n] block, row k - k_lo.  Once per block:
 //     k_gradient_block      members y = 0 .. cols - 1 are the steps k_hi - y: lam walks the block backwards (cs = -n), x
@@ -30,20 +31,12 @@
 // so the sum over the steps is one fixed sequence: descending k, block by block, per block the sixteen table terms and
 // then the sixteen history terms.  No floating-point atomics, every row has one writer.
 #include "group.h"
+#include "table_rows.h"
 
 namespace {
 
 constexpr int GTB = 256;
 constexpr int GCOLS = 16;  // steps to a block (SLU_MULTI: the width of the table kernels)
-
-unsigned groups_of(int64_t items) { return (unsigned)((items + GTB - 1) / GTB); }
-
-// the value column the last numeric assembly used (stamp_numeric's choice)
-const double *assembled_values(nodal_ctx *h) {
-    return h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
-}
-
-__device__ __forceinline__ double lead(const double *__restrict__ x, int32_t node) { return node < 0 ? 0.0 : x[node]; }
 
 // grouping enumerator (group.h): probe p touches node a (slot 0: +w) and node b (slot 1: -w); a probe between a node
 // and itself touches nothing.  One column, so a node's probes form ONE entry whose run lists probe << 3 | slot in
@@ -61,23 +54,6 @@ struct ProbeLeads {
     }
 };
 
-// One lane per entry of the probes' node list: rhs[node] += the +-w of the node's probes, in list order; w is row k of
-// the cotangents.  The lane is the only writer of its node's row.
-__global__ __launch_bounds__(GTB) void k_tgrad_seed(int64_t nent, const int32_t *__restrict__ node,
-                                                    const int32_t *__restrict__ cptr, const uint32_t *__restrict__ contrib,
-                                                    const double *__restrict__ w, double *__restrict__ rhs) {
-    const int64_t e = (int64_t)blockIdx.x * GTB + threadIdx.x;
-    if (e >= nent) return;
-    const int32_t row = node[e];
-    double acc = rhs[row];
-    for (int32_t p = cptr[e]; p < cptr[e + 1]; ++p) {
-        const uint32_t u = contrib[p];
-        const double v = w[u >> 3];
-        acc += (u & 7u) ? -v : v;
-    }
-    rhs[row] = acc;
-}
-
 // One lane per capacitor: the companion row's record is loaded once, then for the steps k = k_hi - y, y = 0 .. cols - 1,
 // -(lambda_k(a) - lambda_k(b)) (x_{k-1}(a) - x_{k-1}(b)) / r^2 is added onto grad[row].  lam_hi: lambda_{k_hi}, the
 // earlier steps n doubles below each; x_hi: x_{k_hi - 1}, likewise.  The lane is the row's only writer.
@@ -87,13 +63,13 @@ __global__ __launch_bounds__(GTB) void k_tgrad_caps(int64_t ncap, int cols, int6
                                                     const double *__restrict__ x_hi, double *__restrict__ grad) {
     const int64_t i = (int64_t)blockIdx.x * GTB + threadIdx.x;
     if (i >= ncap) return;
-    const int32_t r = rows[i], ia = a[r], ib = b[r];
-    const double v = value[r], den = v * v;
+    const int32_t r = rows[i];
+    const RowTerm t = resistor_term(r, value, a, b);
     double acc = grad[r];
     for (int y = 0; y < cols; ++y) {
         const double *lam = lam_hi - (int64_t)y * n, *x = x_hi - (int64_t)y * n;
-        const double D = lead(lam, ia) - lead(lam, ib);
-        const double w = (lead(x, ia) - lead(x, ib)) / den;
+        const double D = lead(lam, t.j1) - lead(lam, t.j2);
+        const double w = (lead(x, t.p1) - lead(x, t.p2)) / t.den;
         acc -= D * w;
     }
     grad[r] = acc;
@@ -138,24 +114,17 @@ int run(nodal_ctx *h, bool dense, int32_t nprobe, const int32_t *probe_a, const 
     // c_k into the zeroed vector, then the history of `next` (null: none)
     auto right_hand_side = [&](int32_t k, const double *next, double *out) -> int {
         NODAL_HIP_TRY(h, hipMemsetAsync(out, 0, (size_t)n * 8, st));
-        if (pent > 0) {
-            k_tgrad_seed<<<groups_of(pent), GTB, 0, st>>>(pent, h->tg_node.as<int32_t>(), h->tg_ptr.as<int32_t>(),
-                                                         h->tg_con.as<uint32_t>(), cot_dev + (size_t)k * nprobe, out);
-            NODAL_HIP_TRY(h, hipGetLastError());
-        }
+        // (+-w of a node's probes in list order, w row k of the cotangents)
+        NODAL_TRY(signed_list_add(h, pent, h->tg_node.as<int32_t>(), h->tg_ptr.as<int32_t>(), h->tg_con.as<uint32_t>(),
+                                  cot_dev + (size_t)k * nprobe, out));
         if (next && ncap > 0) NODAL_TRY(transient_add_history(h, ncap, 0, rows_dev, nent, next, hist, out));
         return NODAL_OK;
     };
 
     // ---- the matrix: h's own where it is symmetric, the transposed child otherwise ----
     TransientSolver ts;
-    ts.s = h;
-    ts.lu_epoch = &h->tr_lu_epoch;
-    if (!(h->B == 0 && h->passive_network)) {
-        NODAL_TRY(sens_transposed_child(h));
-        ts.s = h->adjoint;
-        ts.lu_epoch = &h->tg_lu_epoch;
-    }
+    NODAL_TRY(adjoint_context(h, &ts.s));
+    ts.lu_epoch = ts.s == h ? &h->tr_lu_epoch : &h->tg_lu_epoch;
     ts.rvec = rvec;
     ts.dvec = dvec;
     ts.norms = norms;
@@ -207,8 +176,8 @@ int run(nodal_ctx *h, bool dense, int32_t nprobe, const int32_t *probe_a, const 
             const double *lam_hi = blk + (size_t)(cols - 1) * n;
             NODAL_TRY(grad_launch_table(h, cols, lam_hi, 1, -n, tape + (size_t)k_hi * n, 1, -n, grad_dev));
             if (ncap > 0) {
-                k_tgrad_caps<<<groups_of(ncap), GTB, 0, st>>>(ncap, cols, n, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(),
-                                                             value, lam_hi, tape + (size_t)(k_hi - 1) * n, grad_dev);
+                k_tgrad_caps<<<groups_of(ncap, GTB), GTB, 0, st>>>(ncap, cols, n, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(),
+                                                                  value, lam_hi, tape + (size_t)(k_hi - 1) * n, grad_dev);
                 NODAL_HIP_TRY(h, hipGetLastError());
             }
         }

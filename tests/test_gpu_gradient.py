@@ -54,6 +54,28 @@ def test_single_solve_parity(k, sparse):
     assert np.array_equal(kept.values, grad.values)
 
 
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
+@pytest.mark.parametrize("k", range(len(INPUTS)), ids=[i[0] for i in INPUTS])
+def test_a_unit_cotangent_gives_the_sensitivity_row(k, sparse):
+    """One output c^T x as a loss: the gradient with cotangent c and the sensitivity of that output share the row
+    formulas (csrc/table_rows.h), the right-hand side and the route, so they agree bit for bit.  A voltage output: the
+    explicit term of a current output belongs to the sensitivity alone.  One column: with more the gradient is a fused
+    chain over the members and the sensitivity is not."""
+    name, rows = INPUTS[k]
+    nl = n.Netlist.from_rows(rows)
+    c = n.Circuit(nl, sparse=sparse)
+    c.solve()
+    table = ref.table_of(nl)
+    # (the sample's voltage between two nodes, or -- where it drew one node twice -- its node potential)
+    found = [(s, ref.output_vector(nl, table, s)) for s in ref.sample_outputs(nl, table, 3, 700 + k) if s[0] != "i"]
+    spec, (cvec, row) = max(found, key=lambda f: np.count_nonzero(f[1][0]))
+    assert row is None and cvec.any()
+    sens = c.sensitivities([spec], adjoints=True)
+    grad = c.gradient(cvec, adjoints=True)
+    assert np.array_equal(np.asarray(grad.adjoints)[0], np.asarray(sens.adjoints)[0]), (name, sparse, spec)
+    assert np.array_equal(np.asarray(grad.values), np.asarray(sens.values)[0]), (name, sparse, spec)
+
+
 # ---- every route of the driver, at its smallest shape ---------------------------------------------------------------
 class Case:
     """a network, its reference, one sweep of M members and what the device made of it"""

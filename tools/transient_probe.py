@@ -41,7 +41,7 @@ from nodal_amd import constants as c  # noqa: E402
 from nodal_amd import generators as gen  # noqa: E402
 from tools.sweep_probe import with_loads  # noqa: E402
 
-KERNELS = ("k_transient_history", "k_transient_rhs", "k_transient_probe", "k_transient_envelope")
+KERNELS = ("k_transient_history", "k_signed_list_add", "k_transient_probe", "k_transient_envelope")
 DT = 1.0  # (of the order of a node's own RC: unit resistors, capacitors of 0.5 .. 2)
 
 

@@ -36,7 +36,7 @@ from nodal_amd import constants as c  # noqa: E402
 from nodal_amd.transient import dc_table  # noqa: E402
 from tools.transient_probe import DT, assembled, network, timed  # noqa: E402
 
-KERNELS = ("k_transient_history", "k_transient_rhs", "k_transient_probe", "k_transient_inductor_start",
+KERNELS = ("k_transient_history", "k_signed_list_add", "k_transient_probe", "k_transient_inductor_start",
            "k_transient_inductor", "k_transient_current_probe")
 INDUCTORS = 64
 
