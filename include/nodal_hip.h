@@ -337,6 +337,53 @@ int nodal_transient_gradient(nodal_handle h, int32_t dense, int32_t nprobe, cons
                              double *adjoint_out /* [steps][n], may be NULL */,
                              double *resid_out /* [steps], may be NULL */, int32_t *info_out /* [steps] */);
 
+/* ---- AC analysis: frequency sweeps of RLC networks (replaces a transient run per frequency, long enough to settle, with
+ *      an amplitude fit afterwards; on the host: G exported, G + j B formed and solved anew per frequency) ----
+ * The steady state at each angular frequency omega [nfreq] (rad/s).  G (n x n, n = K + B) is that of the last
+ * nodal_assemble_numeric.  The reactive elements are arguments, not table rows: kind [nreact] (0 a capacitor, 1 an
+ * inductor), value (farads or henries), lead_a, lead_b (node indices, -1 ground).  A capacitor has the susceptance
+ * b = omega C, an inductor b = -1 / (omega L); B(omega) stamps every element like a conductance of value b (+b at (a, a)
+ * and (b, b), -b at (a, b) and (b, a), ground leads dropped), and the phasors solve
+ *   (G + j B) (x_r + j x_i) = s_r + j s_i
+ * as the real system of 2n unknowns interleaved by unknown (real part of unknown i at 2i, imaginary part at 2i + 1; entry
+ * (i, j) the block [[g, -b], [b, g]]), on a child context kept on the handle.  The excitation is small-signal: every
+ * independent source (A, E) is OFF except src_rows [nsrc] (each named once), which carry the complex amplitudes
+ * src_re + j src_im [nsrc], constant over the sweep; s_r (s_i) is the right-hand side of the table with every A / E
+ * value replaced by the real (imaginary) part of its amplitude.  Dependent sources stay in G.
+ *   wave_out [nfreq][nprobe][2]    x(probe_a[p]) - x(probe_b[p]) as (re, im); probe_a == probe_b reads exactly +0.0
+ *   cur_out [nfreq][ncur][2]       j b_q (x(a) - x(b)), the current from lead a to lead b through element
+ *                                  q = cur_index[t] (an index into the reactive list)
+ *   x_out [nfreq / keep_every][n][2]  the solution of every keep_every-th frequency (keep_every 0: none)
+ *   peak_out [K]                   per node the largest |x| over the solved frequencies, peak_freq_out [K] the frequency
+ *                                  index that attains it (among exact ties the lowest); NaN and -1 when none was solved
+ *   resid_out [nfreq]              the scaled residual of the real system, as nodal_solve_sources defines it
+ *   info_out [nfreq]               > 0: singular at that frequency (NaN in its rows only, later frequencies are solved,
+ *                                  status OK) -- except with dense != 0, where it returns NODAL_E_SINGULAR
+ * Each output may be NULL.  Routes: 2n <= 64 the dense panel; dense != 0 the dense LU at any size; everything else the
+ * sparse LU, factored anew per frequency on the kept analysis, two substitutions, one refinement step and the judgement
+ * (a frequency above the bar is redone by the sparse direct solve).  The child's pattern (the union of G's and the
+ * elements' node pairs) and the symbolic analysis are kept per structure and set of (kind, lead_a, lead_b): a later
+ * call with other values, frequencies, sources or probes repeats neither.  An entry's susceptances are added in list
+ * order (capacitors ascending, then inductors ascending) by one lane, no atomics: a repeated call gives the same bits.
+ * nodal_last_timings afterwards: [0] host ms of the pattern and the symbolic analysis this call did, exactly 0.0 when
+ * both were kept; [1] the ms of the numeric factorisations, summed; [2] the whole call.
+ * NODAL_E_INVALID: no nodal_assemble_numeric before the call, nfreq < 0, an omega that is not finite and > 0, a kind other
+ * than 0 / 1, a value that is not finite and > 0, a lead outside [-1, K), both leads of an element on one node, the
+ * source-row errors of nodal_solve_sources, a probe node outside [-1, K), a cur_index outside [0, nreact).  nfreq == 0
+ * does nothing; n == 0 gives zeros.
+ * Phasors, currents, peaks and residuals come down once, after the last frequency.  Leaves the handle as it found it:
+ * the solution if any, the table, G, A, what the last solve reported, the transient tape, the kept hierarchy and
+ * factors. */
+int nodal_ac_sweep(nodal_handle h, int32_t dense, int32_t nfreq, const double *omega /* [nfreq], rad/s, > 0 */,
+                   int64_t nreact, const uint8_t *kind /* 0 capacitor, 1 inductor */, const double *value /* F or H */,
+                   const int32_t *lead_a, const int32_t *lead_b /* node indices, -1 ground */,
+                   int32_t nsrc, const int64_t *src_rows, const double *src_re, const double *src_im,
+                   int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b, double *wave_out /* [nfreq][nprobe][2] */,
+                   int32_t ncur, const int32_t *cur_index /* into the reactive list */, double *cur_out /* [nfreq][ncur][2] */,
+                   int32_t keep_every, double *x_out /* [nfreq / keep_every][n][2] */,
+                   double *peak_out /* [K] */, int32_t *peak_freq_out /* [K] */,
+                   double *resid_out /* [nfreq] */, int32_t *info_out /* [nfreq] */);
+
 /* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
  *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
  *      reference has no equivalent of an active network and no coupling between ports) ----

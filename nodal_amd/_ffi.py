@@ -64,6 +64,9 @@ SIGNATURES = {
                                       _f64p, _i32p, _i32p, C.c_int64, _i64p, _f64p, C.c_int32, _i32p, _f64p, _f64p]),
     "nodal_transient_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
                                            _f64p, _i32p]),
+    "nodal_ac_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
+                                 _i64p, _f64p, _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _i32p, _f64p, C.c_int32,
+                                 _f64p, _f64p, _i32p, _f64p, _i32p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
@@ -487,6 +490,49 @@ class Handle:
             _ptr(gx0, C.c_double), _ptr(lam, C.c_double) if adjoints and steps else None, _ptr(resid, C.c_double),
             _ptr(info, C.c_int32)))
         return grad, gsrc, gx0, lam, resid, info
+
+    def ac_sweep(self, omega, kind, value, lead_a, lead_b, rows, amplitudes, ia, ib, cur_index, dense, keep_every=0,
+                 peaks=False):
+        """Frequency sweep on the circuit's own handle (nodal_ac_sweep): omega [F] in rad/s, the reactive elements as
+        kind [E] (0 capacitor, 1 inductor), value [E], lead_a / lead_b [E] node indices, rows [R] the driven A / E rows
+        with their complex amplitudes [R] (every other source is off), (ia, ib) the probes' node indices, cur_index [Q]
+        the elements whose currents are wanted.  Returns (phasors complex128 [F, P], currents complex128 [F, Q],
+        solutions complex128 [F // keep_every, n] or None, (peak magnitude [K], peak frequency index [K]) or None,
+        scaled residual [F], info [F]); NodalHipError(E_INVALID) as the header lists, with dense a singular frequency
+        raises NodalHipError(E_SINGULAR)."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        value = np.ascontiguousarray(value, dtype=np.float64)
+        lead_a, lead_b = (np.ascontiguousarray(v, dtype=np.int32) for v in (lead_a, lead_b))
+        assert omega.ndim == 1 and kind.ndim == 1 and value.shape == kind.shape == lead_a.shape == lead_b.shape
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        amplitudes = np.asarray(amplitudes, dtype=np.complex128)
+        assert rows.ndim == 1 and amplitudes.shape == rows.shape
+        src_re, src_im = np.ascontiguousarray(amplitudes.real), np.ascontiguousarray(amplitudes.imag)
+        ia, ib = (np.ascontiguousarray(v, dtype=np.int32) for v in (ia, ib))
+        assert ia.ndim == 1 and ib.shape == ia.shape
+        cur_index = np.ascontiguousarray(cur_index, dtype=np.int32)
+        assert cur_index.ndim == 1
+        nfreq, K = len(omega), self._K
+        wave = np.zeros((nfreq, len(ia)), dtype=np.complex128)
+        cur = np.zeros((nfreq, len(cur_index)), dtype=np.complex128)
+        kept = nfreq // keep_every if keep_every > 0 else 0
+        x = np.zeros((kept, self.n), dtype=np.complex128) if keep_every > 0 else None
+        peak = (np.empty(K), np.empty(K, dtype=np.int32)) if peaks else None
+        resid = np.zeros(nfreq, dtype=np.float64)
+        info = np.zeros(nfreq, dtype=np.int32)
+
+        def opt(arr, ctype):  # (an empty array goes as NULL)
+            return _ptr(arr, ctype) if arr is not None and arr.size else None
+
+        self._check(self.lib.nodal_ac_sweep(
+            self._h, int(dense), nfreq, opt(omega, C.c_double), len(kind), opt(kind, C.c_uint8), opt(value, C.c_double),
+            opt(lead_a, C.c_int32), opt(lead_b, C.c_int32), len(rows), opt(rows, C.c_int64), opt(src_re, C.c_double),
+            opt(src_im, C.c_double), len(ia), opt(ia, C.c_int32), opt(ib, C.c_int32), opt(wave, C.c_double), len(cur_index),
+            opt(cur_index, C.c_int32), opt(cur, C.c_double), int(keep_every), opt(x, C.c_double),
+            opt(peak[0], C.c_double) if peaks else None, opt(peak[1], C.c_int32) if peaks else None,
+            _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
+        return wave, cur, x, peak, resid, info
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

@@ -579,6 +579,57 @@ class Circuit:
         return TransientGradient(values, capacitors, by_name, gx0, info, resid, adjoints=lam, timings=timings,
                                  start_values=start)
 
+    def ac(self, frequencies, capacitors=(), inductors=(), sources=None, probes=(), current_probes=(), keep_every=0,
+           peaks=False):
+        """The steady state of the circuit with capacitors and inductors at each of `frequencies` (Hz), on the device
+        (nodal_ac_sweep): the phasors x of (G + j B(w)) x = s, w = 2 pi f, one solve of the real system of twice the
+        size per frequency.
+
+        `capacitors` and `inductors` are sequences of (name, farads or henries, node_a, node_b) on nodes of the netlist,
+        as transient() takes them; loops of inductors are legal here.  The excitation is small-signal: `sources` maps
+        names of A / E components to complex amplitudes that stay constant over the sweep, and every independent source
+        that is not named is off (None: all of them, and every result is zero); dependent sources stay in place.
+        TypeError / KeyError / ValueError for bad names as solve_sources gives them.  `probes` are (node_plus,
+        node_minus) pairs or single labels against ground (thevenin's ports); `current_probes` names capacitors or
+        inductors whose currents are wanted, positive from node_a to node_b through the element.  keep_every=s > 0
+        brings the full solution of every s-th frequency down, peaks=True adds per node the largest |potential| over the
+        frequencies and a frequency index that attains it.  Returns an ACSweep (ac.py): `frequencies`, `omega`,
+        `phasors` [F, P], `currents` [F, Q], `solutions`, `solution_indices`, `peaks`, `info`, `scaled_residual`,
+        `timings`, magnitude_db(), phase_deg().
+
+        The doubled system lives on a child of the circuit's own device context; its pattern and symbolic analysis are
+        kept under the elements' kinds and leads: a second call with other values, frequencies, amplitudes or probes
+        repeats neither (`timings[0] == 0.0`).  Singular networks behave as in solve_sources(): the dense path raises
+        LinAlgError / UnconnectedCircuitError, the sparse path returns NaN rows with info > 0 for the singular
+        frequencies and warns once.  The circuit itself -- its solution if any, table, G, A, a recorded transient -- is
+        left as it was; solve() is neither needed nor touched."""
+        from .ac import ACPeaks, ACSweep, check_ac_arguments, resolve_amplitudes, resolve_reactive
+        from .ports import _as_pair, resolve_ports
+        omega = check_ac_arguments(frequencies)
+        keep_every = int(keep_every)
+        if keep_every < 0:
+            raise ValueError(f"keep_every must not be negative, not {keep_every}")
+        names, kind, value, ea, eb = resolve_reactive(self.netlist, capacitors, inductors)
+        rows, amplitudes = resolve_amplitudes(self.netlist, sources)
+        probes = [_as_pair(self.netlist, port) for port in probes]
+        pa, pb = resolve_ports(self.netlist, probes)
+        index = {name: q for q, name in enumerate(names)}
+        current_probes = list(current_probes)
+        for name in current_probes:
+            if name not in index:
+                raise KeyError(f"current probe {name!r} is not the name of a capacitor or an inductor")
+        cur_index = np.asarray([index[name] for name in current_probes], dtype=np.int32).reshape(len(current_probes))
+        h = self._handle
+        with self._reference_errors():
+            wave, cur, x, peak, resid, info = h.ac_sweep(omega, kind, value, ea, eb, rows, amplitudes, pa, pb, cur_index,
+                                                         dense=not self.sparse, keep_every=keep_every, peaks=peaks)
+        timings = h.timings()
+        _warn_singular((info > 0).any())
+        kept = np.arange(1, len(omega) // keep_every + 1, dtype=np.int64) * keep_every - 1 if keep_every > 0 else None
+        return ACSweep(np.array(frequencies, dtype=np.float64), omega, wave, probes, info, resid, currents=cur,
+                       current_probes=current_probes, solutions=x, solution_indices=kept,
+                       peaks=ACPeaks(peak[0], peak[1]) if peaks else None, timings=timings)
+
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last
         solution, computed on the device."""

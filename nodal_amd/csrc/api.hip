@@ -246,6 +246,7 @@ void nodal_free_buffers(nodal_ctx *h) {
     presolve_free_plan(h);
     nodal_free_block_child(h);
     sens_free_child(h);
+    ac_free_child(h);
     if (h->reduced) {
         nodal_free_buffers(h->reduced);
         delete h->reduced;
@@ -270,6 +271,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->tr_ind,
                       &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
                       &h->tg_con,
+                      &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
                       &h->dbg_resid, &h->dbg_apply};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
@@ -290,6 +292,7 @@ void nodal_poison_scratch(nodal_ctx *h) {
     nodal_poison_scratch(h->lowdeg);
     nodal_poison_scratch(h->blocksys);
     nodal_poison_scratch(h->adjoint);
+    nodal_poison_scratch(h->ac);
 }
 
 void nodal_nan_probe(nodal_ctx *h, const double *dev, int64_t n, const char *tag) {
@@ -951,6 +954,34 @@ int nodal_transient_gradient(nodal_handle h, int32_t dense, int32_t nprobe, cons
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_matrix;
     h->ms[1] = 0.0;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
+int nodal_ac_sweep(nodal_handle h, int32_t dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+                   const double *value, const int32_t *lead_a, const int32_t *lead_b, int32_t nsrc, const int64_t *src_rows,
+                   const double *src_re, const double *src_im, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
+                   double *wave_out, int32_t ncur, const int32_t *cur_index, double *cur_out, int32_t keep_every, double *x_out,
+                   double *peak_out, int32_t *peak_freq_out, double *resid_out, int32_t *info_out) {
+    if (!h || nreact < 0 || (nreact > 0 && (!kind || !value || !lead_a || !lead_b)) || nsrc < 0 ||
+        (nsrc > 0 && (!src_rows || !src_re || !src_im)) || nprobe < 0 || (nprobe > 0 && (!probe_a || !probe_b)) || ncur < 0 ||
+        (ncur > 0 && !cur_index) || keep_every < 0)
+        return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: assemble_numeric not called");
+    if (nfreq < 0 || (nfreq > 0 && !omega)) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: a negative number of frequencies");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_analysis = 0.0, ms_factor = 0.0;
+    const int s = ac_run(h, dense != 0, nfreq, omega, nreact, kind, value, lead_a, lead_b, nsrc, src_rows, src_re, src_im, nprobe,
+                         probe_a, probe_b, wave_out, ncur, cur_index, cur_out, keep_every, x_out, peak_out, peak_freq_out,
+                         resid_out, info_out, &ms_analysis, &ms_factor);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = ms_analysis;
+    h->ms[1] = ms_factor;
     h->ms[2] = elapsed(h, 0, 1);
     return s;
 }

@@ -233,6 +233,15 @@ struct nodal_ctx {
     // the node -> incident-probe lists (as tr_none .. tr_con)
     DevBuf tg_vec, tg_out, tg_spec, tg_none, tg_node, tg_ptr, tg_con;
     uint64_t tg_lu_epoch = 0;     // numeric_epoch the sparse LU factors of the transposed child belong to (0: none)
+    // AC analysis (ac.hip): the child context that holds the interleaved real form of G + j B(omega), 2n unknowns, as CSR
+    // (kept per struct_epoch and reactive leads: ac_epoch, ac_key = kinds | leads a | leads b); per stored entry of the
+    // child the place of G's value in `data` (-1: none), the entries' runs of reactive elements and the runs themselves
+    // (element << 1 | subtract); the call's elements, probes and probed elements; right-hand side, solution, refinement
+    // vectors and norms; phasors, currents, residuals and peaks until they go down; the staging ring of kept solutions
+    nodal_ctx *ac = nullptr;
+    uint64_t ac_epoch = 0;
+    std::vector<int32_t> ac_key;
+    DevBuf ac_gsrc, ac_ptr, ac_con, ac_spec, ac_vec, ac_out, ac_ring;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
@@ -509,6 +518,9 @@ void sens_free_child(nodal_ctx *h);
 // (h->adjoint)
 int sens_cross_list(nodal_ctx *h);
 int sens_transposed_child(nodal_ctx *h);
+// a csr_only child context of h in *slot, made on first use on h's streams, its solver options brought up to h's: what
+// holds a matrix no netlist stamped (h->adjoint, h->ac); the caller sets K, B, n, nnz and the CSR arrays
+nodal_ctx *csr_child(nodal_ctx *h, nodal_ctx **slot);
 // *s: the context the transposed solves run on -- h itself when G is symmetric (B == 0 and passive), otherwise the
 // child, brought up to date
 int adjoint_context(nodal_ctx *h, nodal_ctx **s);
@@ -557,6 +569,7 @@ struct TransientSolver {
     bool direct = false;      // multigrid route: the iteration gave up, this step and every later one by the direct solve
     bool all_direct = false;  // sparse LU route: pivots were replaced, every step by the direct solve (which judges its own)
     bool mg_setup = false, first = true;
+    bool force_dense = false;  // the dense panel at any size (ac.hip with `dense`); set before transient_solver_begin
     double bar = 0.0;
 };
 // the route and its matrix work (the dense panel's room, the factorisation unless kept, whether the hierarchy is to be
@@ -582,6 +595,17 @@ int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t 
 int tgrad_run(nodal_ctx *h, bool dense, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
               const double *wave_cot, double *grad_out, double *grad_sources_out, double *grad_x0_out, double *adjoint_out,
               double *resid_out, int32_t *info_out, double *ms_matrix);
+
+// ---- AC analysis (ac.hip): one solve of the interleaved real form of G + j B(omega) per frequency, on the child h->ac ----
+// the arguments are those of nodal_ac_sweep; ms_analysis: host milliseconds of the child's pattern and of the sparse LU's
+// symbolic analysis done by this call (0.0 when both were kept), ms_factor: of the numeric factorisations, summed
+int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+           const double *value, const int32_t *lead_a, const int32_t *lead_b, int32_t nsrc, const int64_t *src_rows,
+           const double *src_re, const double *src_im, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
+           double *wave_out, int32_t ncur, const int32_t *cur_index, double *cur_out, int32_t keep_every, double *x_out,
+           double *peak_out, int32_t *peak_freq_out, double *resid_out, int32_t *info_out, double *ms_analysis,
+           double *ms_factor);
+void ac_free_child(nodal_ctx *h);
 
 // ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])
@@ -719,6 +743,7 @@ int64_t slu_perturbed(nodal_ctx *h);  // pivots the last slu_factor replaced
 constexpr int SLU_MULTI = 16;         // right-hand sides of slu_apply_multi (interleaved by row: element (i, c) at [i * 16 + c])
 int slu_apply_multi(nodal_ctx *h, const double *r, double *z);
 bool slu_analysis_kept(nodal_ctx *h); // an analysis for the context's present pattern is at hand (no host work to factor)
+double slu_analysis_ms(nodal_ctx *h); // host milliseconds the last slu_factor spent on its analysis, 0.0 when it was kept
 void slu_destroy(nodal_ctx *h);
 void slu_poison(nodal_ctx *h);
 int sparse_direct_solve(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_t *iters, double *resid);

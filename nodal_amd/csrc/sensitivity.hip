@@ -254,11 +254,10 @@ int sens_cross_list(nodal_ctx *h) {
     return NODAL_OK;
 }
 
-// The child context with G^T: made once, its pattern rebuilt when the parent's moves, its values gathered every call.
-int sens_transposed_child(nodal_ctx *h) {
-    const int64_t n = h->n, nnz = h->nnz;
-    hipStream_t st = h->stream;
-    if (!h->adjoint) {
+// A csr_only child context of h in *slot -- a matrix that no netlist stamped: G^T here, the AC analysis' doubled system in
+// ac.hip -- made on first use, on h's streams, its solver options brought up to h's on every call.
+nodal_ctx *csr_child(nodal_ctx *h, nodal_ctx **slot) {
+    if (!*slot) {
         nodal_ctx *c = new nodal_ctx();
         c->device = h->device;
         c->stream = h->stream;  // shared: one ordered timeline
@@ -272,10 +271,9 @@ int sens_transposed_child(nodal_ctx *h) {
         c->keep_host_table = false;
         c->csr_only = true;
         c->use_presolve = false;
-        h->adjoint = c;
-        h->adjoint_epoch = 0;
+        *slot = c;
     }
-    nodal_ctx *c = h->adjoint;
+    nodal_ctx *c = *slot;
     // (not passive, never optimistic: the dense LU of the child pivots)
     c->passive_network = false;
     c->optimistic_nopivot = false;
@@ -285,9 +283,18 @@ int sens_transposed_child(nodal_ctx *h) {
     c->force_pivoting = h->force_pivoting;
     c->use_graphs = h->use_graphs;
     c->amg_min_n = h->amg_min_n;
+    c->have_x = false;
+    return c;
+}
+
+// The child context with G^T: made once, its pattern rebuilt when the parent's moves, its values gathered every call.
+int sens_transposed_child(nodal_ctx *h) {
+    const int64_t n = h->n, nnz = h->nnz;
+    hipStream_t st = h->stream;
+    if (!h->adjoint) h->adjoint_epoch = 0;
+    nodal_ctx *c = csr_child(h, &h->adjoint);
     c->K = h->K;
     c->B = h->B;
-    c->have_x = false;
     if (h->adjoint_epoch != h->struct_epoch || c->n != n || c->nnz != nnz) {
         c->have_numeric = false;
         std::vector<int32_t> indptr((size_t)n + 1), indices((size_t)nnz);

@@ -85,6 +85,7 @@ struct SluState {
     int vec_nr = 0;                // right-hand sides `vec` and `xb` are sized for
     int64_t perturbed = 0;
     bool analysis_kept = false;  // the last slu_factor reused an analysis (row matching!) made for EARLIER values
+    double analysis_ms = 0.0;    // host milliseconds the last slu_factor spent on its analysis (0.0: kept)
 };
 
 SluState *state_of(nodal_ctx *h) { return static_cast<SluState *>(h->slu); }
@@ -1625,6 +1626,7 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
         h->slu = S;
     }
     S->perturbed = 0;
+    S->analysis_ms = 0.0;
     const auto t0 = std::chrono::steady_clock::now();
     auto ms_since = [&](auto t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
     S->analysis_kept = S->have_symbolic && S->epoch == h->struct_epoch && S->n == n && S->nnz == nnz;
@@ -1738,6 +1740,7 @@ int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor, double tiny_thre
         S->have_symbolic = true;
     }
     const double t_sym = ms_since(t0);
+    S->analysis_ms = S->analysis_kept ? 0.0 : t_sym;
     // ---- numeric ----
     NODAL_HIP_TRY(h, S->fronts.reserve((size_t)S->front_doubles * 8 + 64));
     if (S->vec_nr < 1) S->vec_nr = 1;
@@ -2085,6 +2088,11 @@ int slu_apply_multi(nodal_ctx *h, const double *r, double *z) {
 bool slu_analysis_kept(nodal_ctx *h) {
     SluState *S = state_of(h);
     return S && S->have_symbolic && S->epoch == h->struct_epoch && S->n == h->n && S->nnz == h->nnz;
+}
+
+double slu_analysis_ms(nodal_ctx *h) {
+    SluState *S = state_of(h);
+    return S ? S->analysis_ms : 0.0;
 }
 
 int64_t slu_perturbed(nodal_ctx *h) {

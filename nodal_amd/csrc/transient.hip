@@ -205,7 +205,7 @@ int transient_solver_begin(nodal_ctx *h, TransientSolver &ts, bool dense, int32_
     hipStream_t st = h->stream;  // (s shares it: one ordered timeline)
     const bool passive = s == h && h->B == 0 && h->passive_network;  // (a child holds G^T of a network that is not)
     const int64_t multigrid_min = 4096;  // multi_rhs_solve's bound for passive systems
-    ts.route = n <= 64 ? TR_ROUTE_DENSE : (passive && n > multigrid_min) ? TR_ROUTE_MG : TR_ROUTE_LU;
+    ts.route = (n <= 64 || ts.force_dense) ? TR_ROUTE_DENSE : (passive && n > multigrid_min) ? TR_ROUTE_MG : TR_ROUTE_LU;
     ts.direct = ts.all_direct = ts.mg_setup = false;
     ts.first = true;
     ts.bar = knob::MULTI_BAR.now();
