@@ -516,6 +516,34 @@ int nodal_debug_residual(nodal_handle h, int32_t transposed, int32_t cols, int32
  * matrix in question ARE created or refreshed (as any direct solve would leave them). */
 int nodal_debug_direct_apply(nodal_handle h, int32_t transposed, int32_t cols, const double *r, double *z,
                              int64_t *perturbed_out, int32_t *info_out);
+/* The smoothed-aggregation hierarchy (csrc/sagg.hip) as the last setup or values-only refresh left it, raw: what the
+ * tests compare level by level with an fp64 host reference of the setup's algebra (tests/hierarchy_reference.py).
+ * The hierarchy is the handle's own or, when that holds none, the one of its presolved (branch-free) system.
+ * Both calls are stream waits and device-to-host copies only: nothing is launched, nothing on the device is written,
+ * the handle is left as found.  NODAL_E_INVALID when the handle holds no ready hierarchy.
+ * nodal_debug_hierarchy_info: *nlev levels (<= 12); ints[l * 16 + k] per level l:
+ *   0 n, 1 ld, 2 nc (rows of the next level; 0 on the last), 3 width (slots allocated for A), 4 maxlen (longest row),
+ *   5 wfix (> 0: rows zero-padded to this many slots), 6 nnz, 7 rld, 8 rcap (row cap of R), 9 wslots, 10 fold_want (the
+ *   setup wrote W), 11 fold (the cycle uses W), 12 d16 (adcol exists), 13 in_tail (the level runs inside the tail
+ *   kernel), and -- the same on every level -- 14 refreshed (the last setup was a values-only refresh), 15
+ *   dense_coarsest (coarse_inv exists).  reals[l * 2] = the prolongator's smoothing weight of level l, reals[l * 2 + 1]
+ *   = the smoother's weight (the one in W).
+ * nodal_debug_hierarchy_array: one device buffer of one level as raw bytes in the layout the kernels use: A, P and W
+ *   column-major ELL (slot s of row i at [s * ld + i]), R in blocks of eight (entry t of coarse row I at
+ *   [((t >> 3) * rld + I) * 8 + (t & 7)]), adcol int16 column - row.  *bytes_out = the extent the setup addresses:
+ *   width*ld items for acol / aval / avalf / adcol, 4*ld for pcol / pval / pvalf, rcap*rld for rcol / rval / rvalf,
+ *   wslots*ld for wcol / wval, n for alen / dinv / agg / wlen, nc for rlen; slots the setup does not write (past a row's
+ *   padding, rows n .. ld) hold whatever the buffer held.  A buffer the level does not have (no next level, no W, no
+ *   adcol) gives 0.  level == -1: coarse_inv, n_last x n_last row-major (`which` is ignored).  dst == NULL: the size
+ *   only; otherwise capacity_bytes must cover it. */
+enum {
+    NODAL_HA_ACOL = 0, NODAL_HA_AVAL = 1, NODAL_HA_AVALF = 2, NODAL_HA_ALEN = 3, NODAL_HA_DINV = 4, NODAL_HA_ADCOL = 5,
+    NODAL_HA_AGG = 6, NODAL_HA_PCOL = 7, NODAL_HA_PVAL = 8, NODAL_HA_PVALF = 9, NODAL_HA_RCOL = 10, NODAL_HA_RVAL = 11,
+    NODAL_HA_RVALF = 12, NODAL_HA_RLEN = 13, NODAL_HA_WCOL = 14, NODAL_HA_WVAL = 15, NODAL_HA_WLEN = 16
+};
+int nodal_debug_hierarchy_info(nodal_handle h, int32_t *nlev, int64_t *ints /* [12][16] */, double *reals /* [12][2] */);
+int nodal_debug_hierarchy_array(nodal_handle h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes,
+                                int64_t *bytes_out);
 
 #ifdef __cplusplus
 }

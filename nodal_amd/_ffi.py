@@ -82,7 +82,19 @@ SIGNATURES = {
     "nodal_debug_sources_rhs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i64p, _f64p, _f64p]),
     "nodal_debug_residual": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p]),
     "nodal_debug_direct_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p, _i64p, _i32p]),
+    "nodal_debug_hierarchy_info": (C.c_int, [C.c_void_p, _i32p, _i64p, _f64p]),
+    "nodal_debug_hierarchy_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
 }
+
+# nodal_debug_hierarchy_array: `which` in the header's order (NODAL_HA_*) with the item type of each buffer, and the
+# names of the sixteen info words of a level (nodal_debug_hierarchy_info)
+HIERARCHY_ARRAYS = (("acol", np.int32), ("aval", np.float64), ("avalf", np.float32), ("alen", np.int32),
+                    ("dinv", np.float64), ("adcol", np.int16), ("agg", np.int32), ("pcol", np.int32),
+                    ("pval", np.float64), ("pvalf", np.float32), ("rcol", np.int32), ("rval", np.float64),
+                    ("rvalf", np.float32), ("rlen", np.int32), ("wcol", np.int32), ("wval", np.float32),
+                    ("wlen", np.int32))
+HIERARCHY_INFO = ("n", "ld", "nc", "width", "maxlen", "wfix", "nnz", "rld", "rcap", "wslots", "fold_want", "fold", "d16",
+                  "in_tail", "refreshed", "dense_coarsest")
 
 _lib = None
 _live = weakref.WeakSet()  # handles still open; closed before the HIP runtime unloads
@@ -575,6 +587,38 @@ class Handle:
         self._check(self.lib.nodal_debug_direct_apply(self._h, int(bool(transposed)), cols, _ptr(r, C.c_double),
                                                       _ptr(z, C.c_double), C.byref(perturbed), C.byref(info)))
         return z, perturbed.value, info.value
+
+    def debug_hierarchy(self):
+        """The multigrid hierarchy of the last sparse solve as the setup left it (testing hook): a list with one dict
+        per level -- the info words (HIERARCHY_INFO, ints), "omega_p" and "omega", and every device buffer of
+        HIERARCHY_ARRAYS as a flat numpy array in the kernels' own layout, padding included (empty where the level
+        has none); the last level's dict also holds "coarse_inv" (flat, n x n row-major; empty without a dense
+        coarsest level).  Nothing is decoded here."""
+        nlev = C.c_int32(0)
+        ints = np.zeros((12, 16), dtype=np.int64)
+        reals = np.zeros((12, 2), dtype=np.float64)
+        self._check(self.lib.nodal_debug_hierarchy_info(self._h, C.byref(nlev), _ptr(ints, C.c_int64),
+                                                        _ptr(reals, C.c_double)))
+
+        def fetch(level, which, dtype):
+            size = C.c_int64(0)
+            self._check(self.lib.nodal_debug_hierarchy_array(self._h, level, which, None, 0, C.byref(size)))
+            out = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+            if size.value:
+                self._check(self.lib.nodal_debug_hierarchy_array(self._h, level, which, C.c_void_p(out.ctypes.data),
+                                                                 out.nbytes, C.byref(size)))
+                assert size.value == out.nbytes
+            return out
+
+        levels = []
+        for l in range(nlev.value):
+            lv = {name: int(ints[l, k]) for k, name in enumerate(HIERARCHY_INFO)}
+            lv["omega_p"], lv["omega"] = float(reals[l, 0]), float(reals[l, 1])
+            for which, (name, dtype) in enumerate(HIERARCHY_ARRAYS):
+                lv[name] = fetch(l, which, dtype)
+            levels.append(lv)
+        levels[-1]["coarse_inv"] = fetch(-1, 0, np.float64)
+        return levels
 
     def download_x(self):
         x = host_empty(self.n, np.float64)

@@ -1024,6 +1024,21 @@ int nodal_debug_direct_apply(nodal_handle h, int32_t transposed, int32_t cols, c
     return sparse_debug_direct_apply(h, transposed != 0, cols, r, z, perturbed_out, info_out);
 }
 
+int nodal_debug_hierarchy_info(nodal_handle h, int32_t *nlev, int64_t *ints, double *reals) {
+    if (!h || !nlev || !ints || !reals) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return sagg_debug_info(h, nlev, ints, reals);
+}
+
+int nodal_debug_hierarchy_array(nodal_handle h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes,
+                                int64_t *bytes_out) {
+    if (!h || !bytes_out) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return sagg_debug_array(h, level, which, dst, capacity_bytes, bytes_out);
+}
+
 int nodal_residual(nodal_handle h, double *scaled_residual) {
     if (!h || !scaled_residual) return NODAL_E_INVALID;
     DeviceGuard g(h);

@@ -697,6 +697,9 @@ int sagg_apply(nodal_ctx *h, const double *r, double *z, bool x0_ready = false, 
 // i < n0.  false: no hierarchy.
 bool sagg_x0_slot(nodal_ctx *h, const double **dinv, nodal_cyc_t **x0, int64_t *n0, double *omega);
 int sagg_levels(nodal_ctx *h);
+// testing hooks (nodal_debug_hierarchy_info / nodal_debug_hierarchy_array): the hierarchy's sizes and raw device buffers
+int sagg_debug_info(nodal_ctx *h, int32_t *nlev, int64_t *ints, double *reals);
+int sagg_debug_array(nodal_ctx *h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
 int sagg_spmv(nodal_ctx *h, const double *x, double *y, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);  // y = A x on the hierarchy's own (level-0, ELL) matrix
 int amg_has_floating_component(nodal_ctx *h, const uint8_t *grounded0, int32_t *floating);
 int csr_has_floating_component(nodal_ctx *h, const uint8_t *grounded, int32_t *floating);

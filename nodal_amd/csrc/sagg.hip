@@ -2434,6 +2434,93 @@ void sagg_invalidate(nodal_ctx *h) {
     if (h->sagg) static_cast<SHierarchy *>(h->sagg)->ready = false;
 }
 int sagg_levels(nodal_ctx *h) { return h->sagg ? static_cast<SHierarchy *>(h->sagg)->nlev : 0; }
+
+// ---- testing hooks (nodal_debug_hierarchy_info / _array): the hierarchy as the setup left it, raw ----
+// Stream waits and device-to-host copies only: nothing is launched, nothing on the device is written.  The hierarchy is
+// the context's own or, when that holds none, the one of its presolved system (presolve.hip solves the reduced network
+// on h->reduced, which shares the context's stream): *owner is the context it belongs to.
+static SHierarchy *debug_hierarchy(nodal_ctx *h, nodal_ctx **owner) {
+    for (nodal_ctx *c : {h, h->reduced}) {
+        SHierarchy *H = c ? static_cast<SHierarchy *>(c->sagg) : nullptr;
+        if (H && H->ready && H->nlev >= 1 && H->nlev <= MAX_LEVELS && (int)H->pool.size() >= H->nlev) {
+            *owner = c;
+            return H;
+        }
+    }
+    return nullptr;
+}
+
+int sagg_debug_info(nodal_ctx *h, int32_t *nlev, int64_t *ints, double *reals) {
+    nodal_ctx *c = nullptr;
+    SHierarchy *H = debug_hierarchy(h, &c);
+    if (!H) return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: the handle holds no ready hierarchy");
+    *nlev = H->nlev;
+    memset(ints, 0, sizeof(int64_t) * MAX_LEVELS * 16);
+    memset(reals, 0, sizeof(double) * MAX_LEVELS * 2);
+    for (int l = 0; l < H->nlev; ++l) {
+        const SLevel *L = H->pool[l];
+        const bool next = l + 1 < H->nlev;
+        int64_t *w = ints + (size_t)l * 16;
+        w[0] = L->n; w[1] = L->ld; w[2] = next ? L->nc : 0; w[3] = L->width; w[4] = L->maxlen; w[5] = L->wfix;
+        w[6] = L->nnz; w[7] = next ? L->rld : 0; w[8] = next ? rcap_for(L->nc) : 0; w[9] = next ? L->wslots : 0;
+        w[10] = next && L->fold_want; w[11] = next && L->fold; w[12] = L->d16; w[13] = H->tail >= 0 && l >= H->tail;
+        w[14] = H->refreshed; w[15] = H->dense_coarsest;
+        reals[(size_t)l * 2] = omega_p(l);
+        reals[(size_t)l * 2 + 1] = OMEGA;
+    }
+    return NODAL_OK;
+}
+
+int sagg_debug_array(nodal_ctx *h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out) {
+    nodal_ctx *c = nullptr;
+    SHierarchy *H = debug_hierarchy(h, &c);
+    if (!H) return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: the handle holds no ready hierarchy");
+    const DevBuf *buf = nullptr;
+    int64_t bytes = 0;
+    if (level == -1) {
+        const int64_t nl = H->pool[H->nlev - 1]->n;
+        buf = &H->coarse_inv;
+        bytes = H->dense_coarsest ? nl * nl * 8 : 0;
+    } else {
+        if (level < 0 || level >= H->nlev) return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: no such level");
+        const SLevel *L = H->pool[level];
+        const bool next = level + 1 < H->nlev;
+        const int64_t slots = (int64_t)L->width * L->ld, pslots = next ? (int64_t)PW * L->ld : 0;
+        const int64_t rslots = next ? (int64_t)rcap_for(L->nc) * L->rld : 0;
+        const int64_t wslots = next && L->fold_want ? (int64_t)L->wslots * L->ld : 0;
+        switch (which) {
+        case NODAL_HA_ACOL: buf = &L->acol; bytes = slots * 4; break;
+        case NODAL_HA_AVAL: buf = &L->aval; bytes = slots * 8; break;
+        case NODAL_HA_AVALF: buf = &L->avalf; bytes = slots * 4; break;
+        case NODAL_HA_ALEN: buf = &L->alen; bytes = L->n * 4; break;
+        case NODAL_HA_DINV: buf = &L->dinv; bytes = L->n * 8; break;
+        case NODAL_HA_ADCOL: buf = &L->adcol; bytes = L->d16 ? slots * 2 : 0; break;
+        case NODAL_HA_AGG: buf = &L->agg; bytes = next ? L->n * 4 : 0; break;
+        case NODAL_HA_PCOL: buf = &L->pcol; bytes = pslots * 4; break;
+        case NODAL_HA_PVAL: buf = &L->pval; bytes = pslots * 8; break;
+        case NODAL_HA_PVALF: buf = &L->pvalf; bytes = pslots * 4; break;
+        case NODAL_HA_RCOL: buf = &L->rcol; bytes = rslots * 4; break;
+        case NODAL_HA_RVAL: buf = &L->rval; bytes = rslots * 8; break;
+        case NODAL_HA_RVALF: buf = &L->rvalf; bytes = rslots * 4; break;
+        case NODAL_HA_RLEN: buf = &L->rlen; bytes = next ? L->nc * 4 : 0; break;
+        case NODAL_HA_WCOL: buf = &L->wcol; bytes = wslots * 4; break;
+        case NODAL_HA_WVAL: buf = &L->wval; bytes = wslots * 4; break;
+        case NODAL_HA_WLEN: buf = &L->wlen; bytes = wslots ? L->n * 4 : 0; break;
+        default: return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: no such array");
+        }
+    }
+    if (bytes < 0 || (bytes > 0 && (!buf->p || (size_t)bytes > buf->cap)))
+        return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: the level's buffer is smaller than its extent");
+    *bytes_out = bytes;
+    if (!dst || bytes == 0) return NODAL_OK;
+    if (capacity_bytes < bytes) return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: destination too small");
+    NODAL_WAIT_STREAM(h, c->stream);
+    if (H->aux) NODAL_WAIT_STREAM(h, H->aux);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dst, buf->p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    NODAL_WAIT_STREAM(h, c->stream);
+    return NODAL_OK;
+}
+
 bool sagg_x0_slot(nodal_ctx *h, const double **dinv, nodal_cyc_t **x0, int64_t *n0, double *omega) {
     SHierarchy *H = static_cast<SHierarchy *>(h->sagg);
     if (!H || !H->ready) return false;
