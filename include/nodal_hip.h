@@ -384,6 +384,54 @@ int nodal_ac_sweep(nodal_handle h, int32_t dense, int32_t nfreq, const double *o
                    double *peak_out /* [K] */, int32_t *peak_freq_out /* [K] */,
                    double *resid_out /* [nfreq] */, int32_t *info_out /* [nfreq] */);
 
+/* ---- noise analysis: thermal-noise spectra of RLC networks (replaces one nodal_ac_sweep per resistor with a unit current
+ *      through it, read at the output: as many solves per frequency as the network has resistors; the reference has no
+ *      equivalent) ----
+ * A(omega) = G + j B(omega) exactly as nodal_ac_sweep defines it, with the same reactive-element arguments.  Output p is
+ * the node pair (out_a[p], out_b[p]), -1 the ground node, and y_p solves
+ *   A(omega)^T y_p = e(out_a[p]) - e(out_b[p])        (the plain transpose, not the conjugate transpose).
+ * Every table row k of type R with assembled value R_k > 0 and leads (a, b) contributes
+ *   c_k(f, p) = 4 k_B T / R_k |y_p(a) - y_p(b)|^2     V^2 / Hz, k_B = 1.380649e-23 J / K, T = temperature (kelvin, one for
+ *                                                     the whole network), a ground lead reads +0.0;
+ * a row with both leads on one node, every other row type and a resistor with R_k <= 0 are noiseless: exactly +0.0.
+ *   density_out [nfreq][nout]      S_out(f, p) = sum_k c_k(f, p)
+ *   gain_out [nfreq][nout][2]      H(f, p) = y_p^T s as (re, im), nothing conjugated: s is the right-hand side of the table
+ *                                  with source input_row (an A or E row) at amplitude 1 and every other independent source
+ *                                  off, the source stamp of nodal_ac_sweep.  The input-referred density is S_out / |H|^2.
+ *   contrib_out [nout][ncomp]      C_k(p) = sum_f weight[f] c_k(f, p), accumulated on the device in frequency order (the
+ *                                  caller's weights: the trapezoid rule over its frequencies in Hz); the
+ *                                  [nfreq][nout][ncomp] array never exists.  NaN throughout when any frequency is singular.
+ *   resid_out [nfreq][nout]        the scaled residual of every output's real system, as nodal_solve_sources defines it
+ *   info_out [nfreq]               > 0: singular at that frequency (NaN in its rows only, later frequencies are solved,
+ *                                  status OK) -- except with dense != 0, where it returns NODAL_E_SINGULAR
+ * Each output array may be NULL.  No forward solution is needed or made.  The transposed system lives on a child context:
+ * when G is symmetric (no branch rows, every R > 0) A^T = A and it is the child of nodal_ac_sweep itself, pattern and
+ * symbolic analysis shared with it in both directions; otherwise a second child built from the G^T that
+ * nodal_sensitivities keeps, kept under the same key (structure, kinds, leads).  Per frequency ONE numeric factorisation
+ * whatever nout is.  Routes: 2n <= 64 the dense panel and dense != 0 the dense LU at any size, the outputs as columns of
+ * one multi-right-hand-side solve; everything else the sparse LU, factored anew per frequency on the kept analysis, per
+ * output two substitutions, one refinement step and the judgement (an output above the bar is redone by the sparse direct
+ * solve).  Then one pass over the component table per block of sixteen outputs: a lane per row, the sums over the rows by
+ * a fixed-order reduction (wave shuffles, LDS, a fold over the workgroups' partials).  No floating-point atomics: a
+ * repeated call gives the same bits.
+ * nodal_last_timings afterwards: [0] host ms of the pattern and the symbolic analysis this call did, exactly 0.0 when
+ * both were kept; [1] the ms of the numeric factorisations, summed; [2] the whole call.
+ * NODAL_E_INVALID: every argument error of nodal_ac_sweep (frequencies, elements), a temperature that is not finite and
+ * > 0, an output node outside [-1, K), an input_row that is neither -1 nor an A / E row, gain_out without an input_row,
+ * contrib_out without weight.  nfreq == 0 and nout == 0 do nothing; n == 0 gives zeros.
+ * Densities, gains and residuals come down once, after the last frequency, the contributions once.  Leaves the handle as
+ * it found it: the solution if any, the table, G, A, what the last solve reported, the transient tape, the kept
+ * hierarchy and factors, the kept work of nodal_ac_sweep. */
+int nodal_ac_noise(nodal_handle h, int32_t dense, int32_t nfreq, const double *omega /* [nfreq], rad/s, > 0 */,
+                   int64_t nreact, const uint8_t *kind /* 0 capacitor, 1 inductor */, const double *value /* F or H */,
+                   const int32_t *lead_a, const int32_t *lead_b /* node indices, -1 ground */,
+                   double temperature /* K, finite, > 0 */,
+                   int32_t nout, const int32_t *out_a, const int32_t *out_b /* node indices, -1 ground */,
+                   int64_t input_row /* -1: none */, const double *weight /* [nfreq] or NULL */,
+                   double *density_out /* [nfreq][nout] */, double *gain_out /* [nfreq][nout][2] */,
+                   double *contrib_out /* [nout][ncomp] */, double *resid_out /* [nfreq][nout] */,
+                   int32_t *info_out /* [nfreq] */);
+
 /* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
  *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
  *      reference has no equivalent of an active network and no coupling between ports) ----

@@ -67,6 +67,8 @@ SIGNATURES = {
     "nodal_ac_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
                                  _i64p, _f64p, _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _i32p, _f64p, C.c_int32,
                                  _f64p, _f64p, _i32p, _f64p, _i32p]),
+    "nodal_ac_noise": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_double,
+                                 C.c_int32, _i32p, _i32p, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
@@ -545,6 +547,41 @@ class Handle:
             opt(peak[0], C.c_double) if peaks else None, opt(peak[1], C.c_int32) if peaks else None,
             _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
         return wave, cur, x, peak, resid, info
+
+    def ac_noise(self, omega, kind, value, lead_a, lead_b, temperature, oa, ob, dense, input_row=-1, weight=None):
+        """Thermal-noise spectra on the circuit's own handle (nodal_ac_noise): omega [F] in rad/s and the reactive
+        elements as ac_sweep takes them, the temperature in kelvin, (oa, ob) the outputs' node indices [P], input_row
+        the A / E row the gain is taken from (-1: none), weight [F] the quadrature weights of the integrated
+        contributions (None: none are made).  Returns (density [F, P], gain complex128 [F, P] or None, contributions
+        [P, ncomp] or None, scaled residual [F, P], info [F]); NodalHipError(E_INVALID) as the header lists, with dense
+        a singular frequency raises NodalHipError(E_SINGULAR)."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        value = np.ascontiguousarray(value, dtype=np.float64)
+        lead_a, lead_b = (np.ascontiguousarray(v, dtype=np.int32) for v in (lead_a, lead_b))
+        assert omega.ndim == 1 and kind.ndim == 1 and value.shape == kind.shape == lead_a.shape == lead_b.shape
+        oa, ob = (np.ascontiguousarray(v, dtype=np.int32) for v in (oa, ob))
+        assert oa.ndim == 1 and ob.shape == oa.shape
+        nfreq, nout = len(omega), len(oa)
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, dtype=np.float64)
+            assert weight.shape == omega.shape
+        density = np.zeros((nfreq, nout), dtype=np.float64)
+        gain = np.zeros((nfreq, nout), dtype=np.complex128) if input_row >= 0 else None
+        contrib = np.zeros((nout, self._ncomp), dtype=np.float64) if weight is not None else None
+        resid = np.zeros((nfreq, nout), dtype=np.float64)
+        info = np.zeros(nfreq, dtype=np.int32)
+
+        def opt(arr, ctype):  # (an empty array goes as NULL)
+            return _ptr(arr, ctype) if arr is not None and arr.size else None
+
+        self._check(self.lib.nodal_ac_noise(
+            self._h, int(dense), nfreq, opt(omega, C.c_double), len(kind), opt(kind, C.c_uint8), opt(value, C.c_double),
+            opt(lead_a, C.c_int32), opt(lead_b, C.c_int32), float(temperature), nout, opt(oa, C.c_int32), opt(ob, C.c_int32),
+            int(input_row), _ptr(weight, C.c_double) if weight is not None else None, opt(density, C.c_double),
+            _ptr(gain, C.c_double) if gain is not None else None,
+            _ptr(contrib, C.c_double) if contrib is not None else None, _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
+        return density, gain, contrib, resid, info
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

@@ -630,6 +630,68 @@ class Circuit:
                        current_probes=current_probes, solutions=x, solution_indices=kept,
                        peaks=ACPeaks(peak[0], peak[1]) if peaks else None, timings=timings)
 
+    def noise(self, frequencies, capacitors=(), inductors=(), outputs=(), input=None, temperature=300.0,
+              contributions=False):
+        """The thermal noise of the circuit's resistors at each of `frequencies` (Hz), on the device (nodal_ac_noise):
+        per output the density S_out(f) in V^2/Hz, summed over every resistor, from ONE adjoint solve per output and
+        frequency, (G + j B(w))^T y = e(out+) - e(out-), instead of one solve per resistor.
+
+        `capacitors` and `inductors` are sequences of (name, farads or henries, node_a, node_b) as ac() takes them, and
+        G + j B(w) is the matrix of ac().  `outputs` are (node_plus, node_minus) pairs or single labels against ground,
+        resolved as ac() resolves `probes`.  A table row of type R with a value > 0 and leads (a, b) adds
+        4 k_B T / R |y(a) - y(b)|^2 to an output, `temperature` in kelvin for the whole network; sources, dependent
+        elements, capacitors, inductors, resistors with a value <= 0 and resistors with both leads on one node are
+        noiseless and add exactly 0.0.  `input` names one A or E component: the result then carries the gain
+        H(f) = y^T s from that source (amplitude 1, every other independent source off, as in ac()) to each output and
+        the input-referred density S_out / |H|^2.  TypeError / KeyError / ValueError for bad names and values as ac()
+        gives them; ValueError for a temperature that is not finite and > 0 and for an `input` that names more than
+        one row.  contributions=True adds every component's share integrated over the frequencies by the trapezoid
+        rule, [P, ncomp] in the order of `netlist.component_keys` (the frequencies must then be strictly increasing);
+        the sum is accumulated on the device, so the [F, P, ncomp] array never exists.  Returns a NoiseSweep
+        (noise.py): `frequencies`, `omega`, `outputs`, `density` [F, P], `gain`, `input_density`, `contributions`,
+        `info`, `scaled_residual` [F, P], `timings`, amplitude_density(), integrated(), rms(), top(p, count).
+
+        No forward solution is needed or made, and a frequency costs one numeric factorisation whatever the number of
+        outputs.  The transposed system lives on a child of the circuit's own device context, kept like ac()'s under the
+        elements' kinds and leads: a second call with other values, frequencies, outputs or temperature repeats neither
+        its pattern nor its symbolic analysis (`timings[0] == 0.0`), and a passive circuit without branch rows, whose
+        matrix is symmetric, shares both with ac() in either order.  No floating-point atomics: a repeated call gives
+        the same bits.  Singular networks behave as in ac(): the dense path raises LinAlgError /
+        UnconnectedCircuitError, the sparse path returns NaN rows with info > 0 for the singular frequencies, NaN in
+        every integrated quantity, and warns once.  The circuit itself -- its solution if any, table, G, A, a recorded
+        transient, what ac() keeps -- is left as it was; solve() is neither needed nor touched."""
+        from .ac import check_ac_arguments, resolve_amplitudes, resolve_reactive
+        from .noise import NoiseSweep, check_noise_arguments, trapezoid_weights
+        from .ports import _as_pair, resolve_ports
+        omega = check_ac_arguments(frequencies)
+        temperature = check_noise_arguments(temperature, contributions, frequencies)
+        _, kind, value, ea, eb = resolve_reactive(self.netlist, capacitors, inductors)
+        outputs = [_as_pair(self.netlist, port) for port in outputs]
+        oa, ob = resolve_ports(self.netlist, outputs)
+        input_row = -1
+        if input is not None:
+            if not isinstance(input, str):
+                raise TypeError("input must be the name of one A or E component")
+            rows, _ = resolve_amplitudes(self.netlist, {input: 1.0})
+            if len(rows) != 1:
+                raise ValueError(f"input {input!r} names {len(rows)} rows of the table, not one")
+            input_row = int(rows[0])
+        freqs = np.array(frequencies, dtype=np.float64)
+        weight = trapezoid_weights(freqs) if contributions else None
+        h = self._handle
+        with self._reference_errors():
+            density, gain, contrib, resid, info = h.ac_noise(omega, kind, value, ea, eb, temperature, oa, ob,
+                                                             dense=not self.sparse, input_row=input_row, weight=weight)
+        timings = h.timings()
+        _warn_singular((info > 0).any())
+        referred = None
+        if gain is not None:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                referred = density / (gain.real * gain.real + gain.imag * gain.imag)
+        return NoiseSweep(freqs, omega, outputs, density, info, resid, gain=gain, input_density=referred,
+                          contributions=contrib, names=list(self.netlist.component_keys) if contributions else None,
+                          timings=timings)
+
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last
         solution, computed on the device."""

@@ -28,6 +28,12 @@
 // and every keep_every-th frequency one device-to-device copy into a staging ring.  Phasors, currents, peaks and residuals
 // come down once, after the last frequency.  The handle itself -- solution, table, G, A, tape, hierarchy, factors -- is
 // only read.
+//
+// The noise analysis (noise.hip) solves with the transpose of the same matrix.  What it shares is exported from here:
+// ac_child takes which child it builds -- h->ac from the handle's own pattern and values, or h->ac_t from those of
+// h->adjoint, which holds G^T (B is symmetric, the stamps are the same) --, ac_child_values launches k_ac_values for
+// either, and ac_check_arguments / ac_sources_check / ac_sources_stamp are the argument checks and the small-signal
+// right-hand side.
 #include "table_rows.h"
 
 #include <chrono>
@@ -119,15 +125,42 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// Where a child keeps itself on the handle: h->ac, from h's own pattern and values, or h->ac_t, from those of h->adjoint.
+struct AcSlot {
+    nodal_ctx **child, *src;
+    uint64_t *epoch;
+    std::vector<int32_t> *key;
+    DevBuf *gsrc, *ptr, *con;
+};
+AcSlot ac_slot(nodal_ctx *h, bool transposed) {
+    if (transposed) return {&h->ac_t, h->adjoint, &h->ac_t_epoch, &h->ac_t_key, &h->ac_t_gsrc, &h->ac_t_ptr, &h->ac_t_con};
+    return {&h->ac, h, &h->ac_epoch, &h->ac_key, &h->ac_gsrc, &h->ac_ptr, &h->ac_con};
+}
+
+void free_slot(nodal_ctx *h, bool transposed) {
+    const AcSlot a = ac_slot(h, transposed);
+    if (!*a.child) return;
+    nodal_free_buffers(*a.child);
+    delete *a.child;
+    *a.child = nullptr;
+    *a.epoch = 0;
+    a.key->clear();
+}
+
+}  // namespace
+
 // The child context with the interleaved real form: made once, its pattern and maps rebuilt when the parent's structure
 // or the reactive leads move.  order: the reactive elements, capacitors ascending, then inductors ascending.
-int ac_child(nodal_ctx *h, int64_t nreact, const uint8_t *kind, const int32_t *lead_a, const int32_t *lead_b,
-             double *ms_pattern) {
+int ac_child(nodal_ctx *h, bool transposed, int64_t nreact, const uint8_t *kind, const int32_t *lead_a, const int32_t *lead_b,
+             double *ms_pattern, nodal_ctx **child) {
+    const AcSlot a = ac_slot(h, transposed);
     const int64_t n = h->n, nnz = h->nnz, n2 = 2 * n;
     hipStream_t st = h->stream;
     if (n2 >= (1ll << 31) - 2) return nodal_fail(h, NODAL_E_UNSUPPORTED, "ac sweep: more than 2^30 unknowns");
-    if (!h->ac) h->ac_epoch = 0;
-    nodal_ctx *c = csr_child(h, &h->ac);
+    if (!a.src || a.src->n != n || a.src->nnz != nnz) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: no transposed matrix on the handle");
+    if (!*a.child) *a.epoch = 0;
+    nodal_ctx *c = csr_child(h, a.child);
+    *child = c;
     c->K = (int32_t)n2;
     c->B = 0;
     std::vector<int32_t> key((size_t)3 * nreact);
@@ -136,14 +169,14 @@ int ac_child(nodal_ctx *h, int64_t nreact, const uint8_t *kind, const int32_t *l
         key[(size_t)(nreact + q)] = lead_a[q];
         key[(size_t)(2 * nreact + q)] = lead_b[q];
     }
-    if (h->ac_epoch == h->struct_epoch && c->n == n2 && key == h->ac_key) return NODAL_OK;
+    if (*a.epoch == h->struct_epoch && c->n == n2 && key == *a.key) return NODAL_OK;
 
     const auto t0 = std::chrono::steady_clock::now();
     c->have_numeric = false;
-    h->ac_epoch = 0;
+    *a.epoch = 0;
     std::vector<int32_t> indptr((size_t)n + 1), indices((size_t)nnz);
-    NODAL_HIP_TRY(h, hipMemcpyAsync(indptr.data(), h->indptr.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, st));
-    if (nnz > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(indices.data(), h->indices.p, (size_t)nnz * 4, hipMemcpyDeviceToHost, st));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(indptr.data(), a.src->indptr.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (nnz > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(indices.data(), a.src->indices.p, (size_t)nnz * 4, hipMemcpyDeviceToHost, st));
     NODAL_WAIT_STREAM(h, st);
     // the reactive stamps as (row, column, place in the list order, element, subtract), sorted
     struct Stamp {
@@ -238,38 +271,92 @@ int ac_child(nodal_ctx *h, int64_t nreact, const uint8_t *kind, const int32_t *l
     NODAL_HIP_TRY(h, c->data.reserve((size_t)nnz2 * 8 + 16));
     NODAL_HIP_TRY(h, c->rhs.reserve((size_t)n2 * 8 + 16));
     NODAL_HIP_TRY(h, c->x.reserve((size_t)n2 * 8 + 16));
-    NODAL_HIP_TRY(h, h->ac_gsrc.reserve((size_t)nnz2 * 4 + 16));
-    NODAL_HIP_TRY(h, h->ac_ptr.reserve((size_t)(nnz2 + 1) * 4 + 16));
-    NODAL_HIP_TRY(h, h->ac_con.reserve(con.size() * 4 + 16));
+    NODAL_HIP_TRY(h, a.gsrc->reserve((size_t)nnz2 * 4 + 16));
+    NODAL_HIP_TRY(h, a.ptr->reserve((size_t)(nnz2 + 1) * 4 + 16));
+    NODAL_HIP_TRY(h, a.con->reserve(con.size() * 4 + 16));
     NODAL_HIP_TRY(h, hipMemcpyAsync(c->indptr.p, cindptr.data(), (size_t)(n2 + 1) * 4, hipMemcpyHostToDevice, st));
     NODAL_HIP_TRY(h, hipMemcpyAsync(c->diag_pos.p, diag.data(), (size_t)n2 * 4, hipMemcpyHostToDevice, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(h->ac_ptr.p, cptr.data(), (size_t)(nnz2 + 1) * 4, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(a.ptr->p, cptr.data(), (size_t)(nnz2 + 1) * 4, hipMemcpyHostToDevice, st));
     if (nnz2 > 0) {
         NODAL_HIP_TRY(h, hipMemcpyAsync(c->indices.p, cind.data(), (size_t)nnz2 * 4, hipMemcpyHostToDevice, st));
         NODAL_HIP_TRY(h, hipMemcpyAsync(c->rowidx.p, crow.data(), (size_t)nnz2 * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(h->ac_gsrc.p, gsrc.data(), (size_t)nnz2 * 4, hipMemcpyHostToDevice, st));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(a.gsrc->p, gsrc.data(), (size_t)nnz2 * 4, hipMemcpyHostToDevice, st));
     }
-    if (!con.empty()) NODAL_HIP_TRY(h, hipMemcpyAsync(h->ac_con.p, con.data(), con.size() * 4, hipMemcpyHostToDevice, st));
+    if (!con.empty()) NODAL_HIP_TRY(h, hipMemcpyAsync(a.con->p, con.data(), con.size() * 4, hipMemcpyHostToDevice, st));
     NODAL_HIP_TRY(h, hipMemsetAsync(c->rhs.p, 0, (size_t)n2 * 8, st));
     NODAL_WAIT_STREAM(h, st);  // (the copies read vectors that end here)
     c->n = n2;
     c->nnz = nnz2;
     ++c->struct_epoch;  // whatever the child had cached about its own matrix is void
-    h->ac_epoch = h->struct_epoch;
-    h->ac_key.swap(key);
+    *a.epoch = h->struct_epoch;
+    a.key->swap(key);
     *ms_pattern = ms_since(t0);
     return NODAL_OK;
 }
 
-}  // namespace
-
 void ac_free_child(nodal_ctx *h) {
-    if (!h->ac) return;
-    nodal_free_buffers(h->ac);
-    delete h->ac;
-    h->ac = nullptr;
-    h->ac_epoch = 0;
-    h->ac_key.clear();
+    free_slot(h, false);
+    free_slot(h, true);
+}
+
+int ac_child_values(nodal_ctx *h, bool transposed, double omega, const uint8_t *kind_dev, const double *value_dev) {
+    const AcSlot a = ac_slot(h, transposed);
+    nodal_ctx *c = *a.child;
+    if (c->nnz > 0) {
+        k_ac_values<<<groups_of(c->nnz, ATB), ATB, 0, h->stream>>>(c->nnz, omega, a.gsrc->as<int32_t>(), a.ptr->as<int32_t>(),
+                                                                  a.con->as<uint32_t>(), kind_dev, value_dev,
+                                                                  a.src->data.as<double>(), c->data.as<double>());
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    ++c->numeric_epoch;
+    c->have_numeric = true;
+    return NODAL_OK;
+}
+
+int ac_check_arguments(nodal_ctx *h, const char *what, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+                       const double *value, const int32_t *lead_a, const int32_t *lead_b) {
+    const int32_t K = h->K;
+    auto finite_positive = [](double v) { return v > 0.0 && v - v == 0.0; };
+    auto fail = [&](const char *text) { return nodal_fail(h, NODAL_E_INVALID, (std::string(what) + text).c_str()); };
+    for (int32_t f = 0; f < nfreq; ++f)
+        if (!finite_positive(omega[f])) return fail("an angular frequency that is not finite and positive");
+    for (int64_t q = 0; q < nreact; ++q) {
+        if (kind[q] > 1) return fail("a reactive element's kind is neither 0 (capacitor) nor 1 (inductor)");
+        if (!finite_positive(value[q])) return fail("a reactive element's value is not finite and positive");
+        if (lead_a[q] < -1 || lead_a[q] >= K || lead_b[q] < -1 || lead_b[q] >= K) return fail("a reactive element's lead out of range");
+        if (lead_a[q] == lead_b[q]) return fail("both leads of a reactive element on one node");
+    }
+    return NODAL_OK;
+}
+
+// the swept rows: the named sources' real parts, a zero, their imaginary parts, a zero -- two members of nsrc + 1 values,
+// the extra one for every source that is not named (k_ac_sources_off)
+int ac_sources_check(nodal_ctx *h, const char *what, const char *row, int32_t nsrc, const int64_t *src_rows, const double *src_re,
+                     const double *src_im) {
+    hipStream_t st = h->stream;
+    NODAL_HIP_TRY(h, h->sw_rows.reserve((size_t)(nsrc + 16) * 4));
+    NODAL_HIP_TRY(h, h->sw_slot.reserve((size_t)h->ncomp * 4 + 64));
+    NODAL_HIP_TRY(h, h->sw_vals.reserve((size_t)2 * (nsrc + 1) * 8 + 64));
+    std::vector<double> amplitudes((size_t)2 * (nsrc + 1), 0.0);
+    for (int32_t j = 0; j < nsrc; ++j) {
+        amplitudes[(size_t)j] = src_re[j];
+        amplitudes[(size_t)(nsrc + 1 + j)] = src_im[j];
+    }
+    NODAL_HIP_TRY(h, hipMemcpyAsync(h->sw_vals.p, amplitudes.data(), amplitudes.size() * 8, hipMemcpyHostToDevice, st));
+    int32_t *rows_dev = h->sw_rows.as<int32_t>(), *slot_dev = h->sw_slot.as<int32_t>();
+    return sweep_check_rows(h, what, row, nsrc, src_rows, rows_dev, slot_dev, rows_dev + ((nsrc + 15) & ~15));  // (waits)
+}
+
+// the right-hand side does not depend on omega: members (re, im) of the source stamp, element (row, y) at [2 row + y]
+int ac_sources_stamp(nodal_ctx *h, int32_t nsrc, double *bvec) {
+    hipStream_t st = h->stream;
+    int32_t *slot_dev = h->sw_slot.as<int32_t>();
+    if (h->ncomp > 0) {
+        k_ac_sources_off<<<groups_of(h->ncomp, ATB), ATB, 0, st>>>(h->ncomp, h->type.as<uint8_t>(), nsrc, slot_dev);
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)2 * h->n * 8, st));
+    return stamp_rhs_multi(h, slot_dev, h->sw_vals.as<double>(), nsrc + 1, 2, bvec, 2, 1);
 }
 
 int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
@@ -283,37 +370,16 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     hipStream_t st = h->stream;
     const double nan = __builtin_nan("");
     *ms_analysis = *ms_factor = 0.0;
-    auto finite_positive = [](double v) { return v > 0.0 && v - v == 0.0; };
 
     // ---- the arguments ----
-    for (int32_t f = 0; f < nfreq; ++f)
-        if (!finite_positive(omega[f])) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: an angular frequency that is not finite and positive");
-    for (int64_t q = 0; q < nreact; ++q) {
-        if (kind[q] > 1) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: a reactive element's kind is neither 0 (capacitor) nor 1 (inductor)");
-        if (!finite_positive(value[q])) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: a reactive element's value is not finite and positive");
-        if (lead_a[q] < -1 || lead_a[q] >= K || lead_b[q] < -1 || lead_b[q] >= K)
-            return nodal_fail(h, NODAL_E_INVALID, "ac sweep: a reactive element's lead out of range");
-        if (lead_a[q] == lead_b[q]) return nodal_fail(h, NODAL_E_INVALID, "ac sweep: both leads of a reactive element on one node");
-    }
+    NODAL_TRY(ac_check_arguments(h, "ac sweep: ", nfreq, omega, nreact, kind, value, lead_a, lead_b));
     for (int32_t p = 0; p < nprobe; ++p)
         if (probe_a[p] < -1 || probe_a[p] >= K || probe_b[p] < -1 || probe_b[p] >= K)
             return nodal_fail(h, NODAL_E_INVALID, "ac sweep: probe node out of range");
     for (int32_t t = 0; t < ncur; ++t)
         if (cur_index[t] < 0 || cur_index[t] >= nreact)
             return nodal_fail(h, NODAL_E_INVALID, "ac sweep: current probe outside the reactive elements");
-    // the swept rows: the named sources' real parts, a zero, their imaginary parts, a zero -- two members of nsrc + 1
-    // values, the extra one for every source that is not named (k_ac_sources_off)
-    NODAL_HIP_TRY(h, h->sw_rows.reserve((size_t)(nsrc + 16) * 4));
-    NODAL_HIP_TRY(h, h->sw_slot.reserve((size_t)h->ncomp * 4 + 64));
-    NODAL_HIP_TRY(h, h->sw_vals.reserve((size_t)2 * (nsrc + 1) * 8 + 64));
-    std::vector<double> amplitudes((size_t)2 * (nsrc + 1), 0.0);
-    for (int32_t j = 0; j < nsrc; ++j) {
-        amplitudes[(size_t)j] = src_re[j];
-        amplitudes[(size_t)(nsrc + 1 + j)] = src_im[j];
-    }
-    NODAL_HIP_TRY(h, hipMemcpyAsync(h->sw_vals.p, amplitudes.data(), amplitudes.size() * 8, hipMemcpyHostToDevice, st));
-    int32_t *rows_dev = h->sw_rows.as<int32_t>(), *slot_dev = h->sw_slot.as<int32_t>();
-    NODAL_TRY(sweep_check_rows(h, "ac sweep: ", "source row", nsrc, src_rows, rows_dev, slot_dev, rows_dev + ((nsrc + 15) & ~15)));  // (waits)
+    NODAL_TRY(ac_sources_check(h, "ac sweep: ", "source row", nsrc, src_rows, src_re, src_im));
     if (nfreq == 0) return NODAL_OK;
 
     const int32_t nkeep = (keep_every > 0 && x_out) ? nfreq / keep_every : 0;
@@ -334,9 +400,8 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     const bool want_peak = (peak_out || peak_freq_out) && K > 0;
 
     // ---- once per call: the child's pattern, the elements and probes up, the right-hand side, the buffers ----
-    NODAL_TRY(ac_child(h, nreact, kind, lead_a, lead_b, ms_analysis));
-    nodal_ctx *c = h->ac;
-    const int64_t nnz2 = c->nnz;
+    nodal_ctx *c = nullptr;
+    NODAL_TRY(ac_child(h, false, nreact, kind, lead_a, lead_b, ms_analysis, &c));
     // ac_spec: values [nreact] doubles | leads a | leads b | probed elements | probe a | probe b | kinds (bytes)
     const size_t rw = ((size_t)nreact + 15) & ~(size_t)15, cw = ((size_t)ncur + 15) & ~(size_t)15, pw = ((size_t)nprobe + 15) & ~(size_t)15;
     NODAL_HIP_TRY(h, h->ac_spec.reserve(rw * 8 + (2 * rw + cw + 2 * pw) * 4 + rw + 64));
@@ -370,13 +435,7 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
         NODAL_HIP_TRY(h, h->ac_ring.reserve((size_t)std::min<int32_t>(RING, nkeep) * n2 * 8 + 64));
         ring = h->ac_ring.as<double>();
     }
-    // the right-hand side does not depend on omega: members (re, im) of the source stamp, element (row, y) at [2 row + y]
-    if (h->ncomp > 0) {
-        k_ac_sources_off<<<groups_of(h->ncomp, ATB), ATB, 0, st>>>(h->ncomp, h->type.as<uint8_t>(), nsrc, slot_dev);
-        NODAL_HIP_TRY(h, hipGetLastError());
-    }
-    NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)n2 * 8, st));
-    NODAL_TRY(stamp_rhs_multi(h, slot_dev, h->sw_vals.as<double>(), nsrc + 1, 2, bvec, 2, 1));
+    NODAL_TRY(ac_sources_stamp(h, nsrc, bvec));
     NODAL_WAIT_STREAM(h, st);  // (the elements and probes are the caller's)
 
     // ---- the frequencies ----
@@ -394,14 +453,7 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     };
     for (int32_t f = 0; f < nfreq; ++f) {
         const double w = omega[f];
-        if (nnz2 > 0) {
-            k_ac_values<<<groups_of(nnz2, ATB), ATB, 0, st>>>(nnz2, w, h->ac_gsrc.as<int32_t>(), h->ac_ptr.as<int32_t>(),
-                                                             h->ac_con.as<uint32_t>(), kind_dev, val_dev, h->data.as<double>(),
-                                                             c->data.as<double>());
-            NODAL_HIP_TRY(h, hipGetLastError());
-        }
-        ++c->numeric_epoch;
-        c->have_numeric = true;
+        NODAL_TRY(ac_child_values(h, false, w, kind_dev, val_dev));
         // the solve, on the child as both handle and solve context: every size read is 2n
         TransientSolver ts;
         ts.s = c;

@@ -272,6 +272,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
                       &h->tg_con,
                       &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
+                      &h->ac_t_gsrc, &h->ac_t_ptr, &h->ac_t_con, &h->nz_spec, &h->nz_vec, &h->nz_part, &h->nz_out,
                       &h->dbg_resid, &h->dbg_apply};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
@@ -293,6 +294,7 @@ void nodal_poison_scratch(nodal_ctx *h) {
     nodal_poison_scratch(h->blocksys);
     nodal_poison_scratch(h->adjoint);
     nodal_poison_scratch(h->ac);
+    nodal_poison_scratch(h->ac_t);
 }
 
 void nodal_nan_probe(nodal_ctx *h, const double *dev, int64_t n, const char *tag) {
@@ -978,6 +980,31 @@ int nodal_ac_sweep(nodal_handle h, int32_t dense, int32_t nfreq, const double *o
     const int s = ac_run(h, dense != 0, nfreq, omega, nreact, kind, value, lead_a, lead_b, nsrc, src_rows, src_re, src_im, nprobe,
                          probe_a, probe_b, wave_out, ncur, cur_index, cur_out, keep_every, x_out, peak_out, peak_freq_out,
                          resid_out, info_out, &ms_analysis, &ms_factor);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = ms_analysis;
+    h->ms[1] = ms_factor;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
+int nodal_ac_noise(nodal_handle h, int32_t dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+                   const double *value, const int32_t *lead_a, const int32_t *lead_b, double temperature, int32_t nout,
+                   const int32_t *out_a, const int32_t *out_b, int64_t input_row, const double *weight, double *density_out,
+                   double *gain_out, double *contrib_out, double *resid_out, int32_t *info_out) {
+    if (!h || nreact < 0 || (nreact > 0 && (!kind || !value || !lead_a || !lead_b)) || nout < 0 ||
+        (nout > 0 && (!out_a || !out_b)))
+        return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "noise: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "noise: assemble_numeric not called");
+    if (nfreq < 0 || (nfreq > 0 && !omega)) return nodal_fail(h, NODAL_E_INVALID, "noise: a negative number of frequencies");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_analysis = 0.0, ms_factor = 0.0;
+    const int s = noise_run(h, dense != 0, nfreq, omega, nreact, kind, value, lead_a, lead_b, temperature, nout, out_a, out_b,
+                            input_row, weight, density_out, gain_out, contrib_out, resid_out, info_out, &ms_analysis, &ms_factor);
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_analysis;

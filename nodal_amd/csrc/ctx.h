@@ -242,6 +242,15 @@ struct nodal_ctx {
     uint64_t ac_epoch = 0;
     std::vector<int32_t> ac_key;
     DevBuf ac_gsrc, ac_ptr, ac_con, ac_spec, ac_vec, ac_out, ac_ring;
+    // noise analysis (noise.hip): the child with the interleaved real form of (G + j B)^T for networks whose G is not
+    // symmetric, built from the pattern and values of h->adjoint (G^T) and kept like h->ac with maps of its own (a
+    // symmetric G shares h->ac); the call's elements and outputs; right-hand sides, adjoint phasors, the input's
+    // right-hand side, refinement vectors and norms; the workgroups' partial sums; densities, gains, residuals and the
+    // integrated contributions until they go down
+    nodal_ctx *ac_t = nullptr;
+    uint64_t ac_t_epoch = 0;
+    std::vector<int32_t> ac_t_key;
+    DevBuf ac_t_gsrc, ac_t_ptr, ac_t_con, nz_spec, nz_vec, nz_part, nz_out;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
@@ -606,6 +615,31 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
            double *peak_out, int32_t *peak_freq_out, double *resid_out, int32_t *info_out, double *ms_analysis,
            double *ms_factor);
 void ac_free_child(nodal_ctx *h);
+// What the noise analysis shares with the sweep above.  `transposed` picks the child: false h->ac, built from h's own
+// pattern and values (G), true h->ac_t, built from h->adjoint's (G^T; the caller has brought it up to date) -- B is
+// symmetric, so the stamps are the same.
+// the arguments that name frequencies and reactive elements; `what` begins the error texts ("ac sweep: ")
+int ac_check_arguments(nodal_ctx *h, const char *what, int32_t nfreq, const double *omega, int64_t nreact,
+                       const uint8_t *kind, const double *value, const int32_t *lead_a, const int32_t *lead_b);
+// the child, its pattern and maps rebuilt when the parent's structure or the reactive leads move; *ms_pattern is written
+// only then
+int ac_child(nodal_ctx *h, bool transposed, int64_t nreact, const uint8_t *kind, const int32_t *lead_a,
+             const int32_t *lead_b, double *ms_pattern, nodal_ctx **child);
+// the child's values at omega (k_ac_values) from the device copies of the elements' kinds and values
+int ac_child_values(nodal_ctx *h, bool transposed, double omega, const uint8_t *kind_dev, const double *value_dev);
+// the small-signal right-hand side: the named rows checked and uploaded (waits), then -- every other independent source
+// off -- the members (re, im) of the source stamp written interleaved into the zeroed bvec [2n]
+int ac_sources_check(nodal_ctx *h, const char *what, const char *row, int32_t nsrc, const int64_t *src_rows, const double *src_re,
+                     const double *src_im);
+int ac_sources_stamp(nodal_ctx *h, int32_t nsrc, double *bvec);
+
+// ---- noise analysis (noise.hip): thermal-noise spectra by the adjoint of the AC system, one factorisation per frequency ----
+// the arguments are those of nodal_ac_noise; ms_analysis, ms_factor as ac_run's
+int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+              const double *value, const int32_t *lead_a, const int32_t *lead_b, double temperature, int32_t nout,
+              const int32_t *out_a, const int32_t *out_b, int64_t input_row, const double *weight, double *density_out,
+              double *gain_out, double *contrib_out, double *resid_out, int32_t *info_out, double *ms_analysis,
+              double *ms_factor);
 
 // ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])
