@@ -432,6 +432,58 @@ int nodal_ac_noise(nodal_handle h, int32_t dense, int32_t nfreq, const double *o
                    double *contrib_out /* [nout][ncomp] */, double *resid_out /* [nfreq][nout] */,
                    int32_t *info_out /* [nfreq] */);
 
+/* ---- AC port analysis: the multiport impedance matrix Z(j omega) of an RLC network over a list of frequencies (replaces
+ *      one nodal_ac_sweep per port with an A source across it -- a numeric factorisation per port and frequency, and the
+ *      source has to be in the netlist already -- and nodal_port_matrix, which sees G alone, at DC; the reference has no
+ *      equivalent) ----
+ * A(omega) = G + j B(omega) exactly as nodal_ac_sweep defines it, with the same reactive-element arguments.  Port q is the
+ * ordered node pair (ia[q], ib[q]), -1 the ground node (potential +0.0); s_q = e(ia[q]) - e(ib[q]), real, zeros in the
+ * branch rows.  There is no other excitation: every independent source is off, the dependent ones stay in G.  x_q solves
+ *   A(omega) x_q = s_q                                  (A itself, not its transpose)
+ * and
+ *   z_out [nfreq][nports][nports][2]   z[f][p][q] = x_q[ia[p]] - x_q[ib[p]] as (re, im): volts at port p per ampere
+ *                                      entering ia[q] and leaving ib[q], the sign convention of nodal_port_matrix.  A port
+ *                                      with ia == ib has a row and a column of exactly +0.0 in both parts; two identical
+ *                                      ports are legal
+ *   node_peak_out [K]                  per node i the largest |x_q(i)| over all ports and all solved frequencies -- the
+ *                                      worst transfer impedance magnitude from any port to that node --,
+ *   node_peak_port_out [K],            the port and the frequency index that attain it (among exact ties the lowest
+ *   node_peak_freq_out [K]             frequency, then the lowest port); NaN / -1 / -1 when no frequency was solved.  |x|^2
+ *                                      is compared and the root taken once at the end.  Made when any of the three is given
+ *   resid_out [nfreq][nports]          the scaled residual of every column's real system, as nodal_solve_sources defines it
+ *   info_out [nfreq]                   > 0: singular at that frequency (NaN in its rows only, later frequencies are solved,
+ *                                      status OK) -- except with dense != 0, where it returns NODAL_E_SINGULAR
+ *   work_out [3]                       counts made on the host: [0] numeric factorisations (the dense routes: one per chunk
+ *                                      of 512 ports and frequency), [1] applications of the sparse factors to a block of up
+ *                                      to sixteen columns, [2] columns redone alone
+ * Each output array may be NULL.  The matrix is the one nodal_ac_sweep keeps on the handle: pattern and symbolic analysis
+ * are shared with it in both directions, and with nodal_ac_noise wherever that shares with nodal_ac_sweep.  Routes:
+ * 2n <= 64 the dense panel and dense != 0 the dense LU at any size, the ports as columns of one multi-right-hand-side
+ * solve, up to 512 at a time, every group of sixteen judged; everything else the sparse LU, factored ONCE per frequency
+ * whatever nports is, then per block of up to sixteen ports one substitution with sixteen interleaved right-hand sides,
+ * the block's residual, a second substitution, the correction and the block judgement.  A column above the bar (the
+ * NODAL_MULTI_BAR knob) -- every column when the factorisation replaced pivots -- is redone alone by the sparse direct
+ * solve, and the factors are made anew afterwards.  The finished blocks are read at the port nodes on the device
+ * (csrc/ac_ports.hip): nfreq x nports^2 complex numbers come down, once, after the last frequency, with the peaks and the
+ * dense routes' residuals (the sparse route reads a block's residuals when it judges it).  No floating-point atomics: a
+ * repeated call gives the same bits.
+ * nodal_last_timings afterwards: as after nodal_ac_sweep -- [0] host ms of the pattern and the symbolic analysis this call
+ * did, exactly 0.0 when both were kept; [1] the ms of the numeric factorisations, summed; [2] the whole call.
+ * NODAL_E_INVALID: every argument error of nodal_ac_sweep (no nodal_assemble_numeric before the call, nfreq < 0,
+ * frequencies, elements), nports < 0, a port node outside [-1, K).  nfreq == 0 and nports == 0 do nothing; n == 0 gives
+ * zeros.
+ * Leaves the handle as it found it: the solution if any, the table, G, A, what the last solve reported, the transient
+ * tape, the kept hierarchy and factors, the kept work of nodal_ac_sweep and nodal_ac_noise. */
+int nodal_ac_ports(nodal_handle h, int32_t dense, int32_t nfreq, const double *omega /* [nfreq], rad/s, > 0 */,
+                   int64_t nreact, const uint8_t *kind /* 0 capacitor, 1 inductor */, const double *value /* F or H */,
+                   const int32_t *lead_a, const int32_t *lead_b /* node indices, -1 ground */,
+                   int32_t nports, const int32_t *ia, const int32_t *ib /* node indices, -1 ground */,
+                   double *z_out /* [nfreq][nports][nports][2] */,
+                   double *node_peak_out /* [K] or NULL */, int32_t *node_peak_port_out /* [K] or NULL */,
+                   int32_t *node_peak_freq_out /* [K] or NULL */,
+                   double *resid_out /* [nfreq][nports] or NULL */, int32_t *info_out /* [nfreq] or NULL */,
+                   int64_t *work_out /* [3] or NULL */);
+
 /* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
  *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
  *      reference has no equivalent of an active network and no coupling between ports) ----

@@ -15,4 +15,5 @@ from .gradient import Gradient, check_gradient_arguments  # noqa: E402,F401
 from .transient import Transient, TransientEnvelope, resolve_capacitors  # noqa: E402,F401
 from .ac import ACPeaks, ACSweep, resolve_reactive  # noqa: E402,F401
 from .noise import NoiseSweep, trapezoid_weights  # noqa: E402,F401
+from .ac_ports import ACPortPeaks, ACPortSweep, check_ac_port_arguments  # noqa: E402,F401
 from .ports import PortEquivalent, resolve_ports  # noqa: E402,F401

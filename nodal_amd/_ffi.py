@@ -69,6 +69,8 @@ SIGNATURES = {
                                  _f64p, _f64p, _i32p, _f64p, _i32p]),
     "nodal_ac_noise": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_double,
                                  C.c_int32, _i32p, _i32p, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
+    "nodal_ac_ports": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
+                                 _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _f64p, _i32p, _i64p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
@@ -582,6 +584,40 @@ class Handle:
             _ptr(gain, C.c_double) if gain is not None else None,
             _ptr(contrib, C.c_double) if contrib is not None else None, _ptr(resid, C.c_double), _ptr(info, C.c_int32)))
         return density, gain, contrib, resid, info
+
+    def ac_ports(self, omega, kind, value, lead_a, lead_b, ia, ib, dense, peaks=False):
+        """The multiport impedance matrix over a frequency sweep on the circuit's own handle (nodal_ac_ports): omega [F]
+        in rad/s and the reactive elements as ac_sweep takes them, (ia, ib) the ports' node indices [P].  Returns (z
+        complex128 [F, P, P], (peak magnitude [K], peak port int32 [K], peak frequency index int32 [K]) or None, scaled
+        residual [F, P], info [F], work int64 [3]: numeric factorisations, block applications of the sparse factors,
+        columns redone alone); NodalHipError(E_INVALID) as the header lists, with dense a singular frequency raises
+        NodalHipError(E_SINGULAR)."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        value = np.ascontiguousarray(value, dtype=np.float64)
+        lead_a, lead_b = (np.ascontiguousarray(v, dtype=np.int32) for v in (lead_a, lead_b))
+        assert omega.ndim == 1 and kind.ndim == 1 and value.shape == kind.shape == lead_a.shape == lead_b.shape
+        ia, ib = (np.ascontiguousarray(v, dtype=np.int32) for v in (ia, ib))
+        assert ia.ndim == 1 and ib.shape == ia.shape
+        nfreq, nports, K = len(omega), len(ia), self._K
+        z = np.zeros((nfreq, nports, nports), dtype=np.complex128)
+        peak = None
+        if peaks:  # (what the library leaves when no frequency is solved, for the calls that do nothing as well)
+            peak = (np.full(K, np.nan), np.full(K, -1, dtype=np.int32), np.full(K, -1, dtype=np.int32))
+        resid = np.zeros((nfreq, nports), dtype=np.float64)
+        info = np.zeros(nfreq, dtype=np.int32)
+        work = np.zeros(3, dtype=np.int64)
+
+        def opt(arr, ctype):  # (an empty array goes as NULL)
+            return _ptr(arr, ctype) if arr is not None and arr.size else None
+
+        self._check(self.lib.nodal_ac_ports(
+            self._h, int(dense), nfreq, opt(omega, C.c_double), len(kind), opt(kind, C.c_uint8), opt(value, C.c_double),
+            opt(lead_a, C.c_int32), opt(lead_b, C.c_int32), nports, opt(ia, C.c_int32), opt(ib, C.c_int32),
+            opt(z, C.c_double), opt(peak[0], C.c_double) if peaks else None, opt(peak[1], C.c_int32) if peaks else None,
+            opt(peak[2], C.c_int32) if peaks else None, opt(resid, C.c_double), opt(info, C.c_int32),
+            _ptr(work, C.c_int64)))
+        return z, peak, resid, info, work
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

@@ -630,6 +630,41 @@ class Circuit:
                        current_probes=current_probes, solutions=x, solution_indices=kept,
                        peaks=ACPeaks(peak[0], peak[1]) if peaks else None, timings=timings)
 
+    def ac_ports(self, frequencies, ports, capacitors=(), inductors=(), peaks=False):
+        """The impedance matrix Z(jw) of the circuit with capacitors and inductors seen from `ports`, at each of
+        `frequencies` (Hz), on the device (nodal_ac_ports): Z[f][p][q] is the voltage of port p per ampere entering
+        node_plus of port q and leaving its node_minus, with every independent source off and the dependent ones in
+        place -- thevenin()'s `z` at a frequency, ac()'s matrix G + j B(w).
+
+        `ports` are (node_plus, node_minus) pairs or single labels against ground, resolved as thevenin() resolves
+        them; `capacitors` and `inductors` are sequences of (name, farads or henries, node_a, node_b) as ac() takes
+        them.  KeyError / ValueError for bad labels, ports, values and frequencies as those two give them.  A port
+        between a node and itself has a row and a column of exactly 0; two identical ports are legal.  peaks=True adds
+        per node the largest |potential| per ampere over all ports and solved frequencies, with the port and the
+        frequency index that attain it.  Returns an ACPortSweep (ac_ports.py): `frequencies`, `omega`, `ports`, `z`
+        [F, P, P], `info` [F], `scaled_residual` [F, P], `peaks`, `work`, `timings`, driving_point(), reciprocity(),
+        y(), s(z0), peak_impedance().
+
+        A frequency costs ONE numeric factorisation whatever the number of ports; the ports go through the factors
+        sixteen at a time and only F x P x P numbers come to the host.  The doubled system is the one ac() keeps on the
+        circuit's device context: pattern and symbolic analysis are shared with ac() in either order, and with noise()
+        wherever that shares with ac() (`timings[0] == 0.0`).  No floating-point atomics: a repeated call gives the
+        same bits.  Singular networks behave as in ac(): the dense path raises LinAlgError / UnconnectedCircuitError,
+        the sparse path returns NaN for the singular frequencies with info > 0 and warns once.  The circuit itself --
+        its solution if any, table, G, A, a recorded transient, what ac() and noise() keep -- is left as it was;
+        solve() is neither needed nor touched."""
+        from .ac import resolve_reactive
+        from .ac_ports import ACPortPeaks, ACPortSweep, check_ac_port_arguments
+        omega, pairs, ia, ib = check_ac_port_arguments(self.netlist, frequencies, ports)
+        _, kind, value, ea, eb = resolve_reactive(self.netlist, capacitors, inductors)
+        h = self._handle
+        with self._reference_errors():
+            z, peak, resid, info, work = h.ac_ports(omega, kind, value, ea, eb, ia, ib, dense=not self.sparse, peaks=peaks)
+        timings = h.timings()
+        _warn_singular((info > 0).any())
+        return ACPortSweep(np.array(frequencies, dtype=np.float64), omega, pairs, z, info, resid,
+                           peaks=ACPortPeaks(*peak) if peaks else None, work=work, timings=timings)
+
     def noise(self, frequencies, capacitors=(), inductors=(), outputs=(), input=None, temperature=300.0,
               contributions=False):
         """The thermal noise of the circuit's resistors at each of `frequencies` (Hz), on the device (nodal_ac_noise):

@@ -251,6 +251,11 @@ struct nodal_ctx {
     uint64_t ac_t_epoch = 0;
     std::vector<int32_t> ac_t_key;
     DevBuf ac_t_gsrc, ac_t_ptr, ac_t_con, nz_spec, nz_vec, nz_part, nz_out;
+    // AC port analysis (ac_ports.hip), on h->ac: the call's elements and ports; the four interleaved blocks (right-hand
+    // sides, solutions, defect, correction) or the dense route's right-hand sides and solutions, one vector and the
+    // judge's norms; the [16][2n] rows of a block with a column redone alone (reserved when the first one is); Z,
+    // residuals and peaks until they go down
+    DevBuf ap_spec, ap_vec, ap_rows, ap_out;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
@@ -640,6 +645,24 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
               const int32_t *out_a, const int32_t *out_b, int64_t input_row, const double *weight, double *density_out,
               double *gain_out, double *contrib_out, double *resid_out, int32_t *info_out, double *ms_analysis,
               double *ms_factor);
+
+// ---- AC port analysis (ac_ports.hip): the multiport Z(j omega) of an RLC network, one factorisation per frequency ----
+// Every column of one frequency on the child c (2n unknowns) whose values ac_child_values has just written: the per-
+// frequency block loop.  client.build adds the right-hand sides of columns m0 .. m0 + cols - 1 (cols <= 16) into a zeroed
+// block, client.hand_over takes the finished ones (never as rows: wants_rows is not looked at; nothing waits), both with
+// element (row, y) at [row * rs + y * cs] -- the interleaved block (16, 1), or the rows of the dense and redo routes
+// (1, 2n).  resid_host [count]: the sparse route leaves every column's scaled residual there (on_host[q] = 1); the dense
+// route leaves it at resid_dev [count] on the device.  *dead: singular at this frequency, whatever was handed over is
+// void.  work [3]: numeric factorisations, applications of the sparse factors to a block, columns redone alone -- added
+// to.  ms_analysis, ms_factor: added to, as ac_run's.  Buffers: h->ap_vec, h->ap_rows.
+int ac_block_frequency(nodal_ctx *h, nodal_ctx *c, bool dense, int32_t count, MultiRhsClient &client, double *resid_host,
+                       uint8_t *on_host, double *resid_dev, bool *dead, int64_t *work, double *ms_analysis, double *ms_factor);
+// the arguments are those of nodal_ac_ports; ms_analysis, ms_factor as ac_run's
+int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+                 const double *value, const int32_t *lead_a, const int32_t *lead_b, int32_t nports, const int32_t *ia,
+                 const int32_t *ib, double *z_out, double *node_peak_out, int32_t *node_peak_port_out,
+                 int32_t *node_peak_freq_out, double *resid_out, int32_t *info_out, int64_t *work_out, double *ms_analysis,
+                 double *ms_factor);
 
 // ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])
