@@ -96,7 +96,8 @@ HIERARCHY_ARRAYS = (("acol", np.int32), ("aval", np.float64), ("avalf", np.float
                     ("dinv", np.float64), ("adcol", np.int16), ("agg", np.int32), ("pcol", np.int32),
                     ("pval", np.float64), ("pvalf", np.float32), ("rcol", np.int32), ("rval", np.float64),
                     ("rvalf", np.float32), ("rlen", np.int32), ("wcol", np.int32), ("wval", np.float32),
-                    ("wlen", np.int32))
+                    ("wlen", np.int32), ("p2col", np.int32), ("p2val", np.float32), ("p2len", np.int32),
+                    ("d2", np.float32))
 HIERARCHY_INFO = ("n", "ld", "nc", "width", "maxlen", "wfix", "nnz", "rld", "rcap", "wslots", "fold_want", "fold", "d16",
                   "in_tail", "refreshed", "dense_coarsest")
 

@@ -138,6 +138,9 @@ inline constexpr OnUnless0 SA_FUSE_DIR{"NODAL_SA_FUSE_DIR"};  // process: 0 dire
 inline constexpr OffUnlessNon0 SA_GRAPH{"NODAL_SA_GRAPH"};  // process: 1 hipGraph replay of iteration pairs on a kept hierarchy
 inline constexpr Text SA_FOLD_POST{"NODAL_SA_FOLD_POST"};  // process: levels that fold their first post-smoothing sweep into the prolongation: unset or "" levels of at most 524288 rows, "0" none, "1" all outside the tail, "l0,l2" those named
 inline constexpr OffUnlessNon0 SA_FOLD_CHECK{"NODAL_SA_FOLD_CHECK"};  // process: 1 with NODAL_TRACE: the setup prints the scaled difference of the folded launch and the two it replaces
+inline constexpr OnUnless0 SA_FOLD_VISIT{"NODAL_SA_FOLD_VISIT"};  // process: 0 the level directly above the dense tail keeps its six launches per visit instead of three
+inline constexpr Int64 SA_VISIT_CAP{"NODAL_SA_VISIT_CAP", 16777216};  // process: bytes of the dense P2^T above which that level keeps its six launches
+inline constexpr OffUnlessNon0 SA_VISIT_CHECK{"NODAL_SA_VISIT_CHECK"};  // process: 1 with NODAL_TRACE: the setup prints the scaled difference of the three-launch visit and the six launches it replaces
 inline constexpr OnUnless0 SA_TAIL_DENSE{"NODAL_SA_TAIL_DENSE"};  // process: 0 the tail walked by k_tail on every visit instead of applied as a dense operator
 inline constexpr OffUnlessNon0 SA_TAIL_CHECK{"NODAL_SA_TAIL_CHECK"};  // process: 1 with NODAL_TRACE: the setup prints the scaled difference of both forms of the tail
 inline constexpr Int SA_TAIL_NU{"NODAL_SA_TAIL_NU", 3};  // create: sweeps inside the LDS tail (at least 1)

@@ -114,7 +114,8 @@ enum { ST_MAXLEN = 0, ST_GRADED = 1, ST_BADDIAG = 2, ST_OVERFLOW = 3, ST_NNZ = 4
        ST_MAXR = 6, ST_NC = 7 /* aggregates of the level (the scan's total) */,
        ST_FARCOL = 8 /* level 0: some column lies further than 32767 from its row */,
        ST_FOLDMISS = 9 /* a column of P's row is missing from the row of A P (a row without a stored diagonal): no W */,
-       ST_COUNT = 10 };
+       ST_VISITMISS = 10 /* a row of P2 = G W has more than P2CAP columns: the level keeps its six launches */,
+       ST_COUNT = 11 };
 
 struct SLevel {
     int64_t n = 0, ld = 0, nc = 0;
@@ -136,6 +137,11 @@ struct SLevel {
     DevBuf wcol, wval, wlen;
     int32_t wslots = 0;
     bool fold_want = false, fold = false;
+    // The level directly above the dense tail in three launches (k_visit_first / _second / _last, sagg_cycle.h):
+    // P2 = W - w D^-1 (A W) = G^2 P, column-major ELL like W, P2CAP slots, f32 values (build_visit), and d2 = P2^T dense,
+    // n_t x ld row-major f32.  visit_want: the setup wrote them; visit: the cycle uses them (decide_folds).
+    DevBuf p2col, p2val, p2len, d2;
+    bool visit_want = false, visit = false;
     Ell A() const {
         Ell e;
         e.n = n; e.ld = ld; e.width = width;
@@ -262,7 +268,7 @@ struct SHierarchy {
         for (SLevel *l : pool) {
             DevBuf *b[] = {&l->acol, &l->aval, &l->alen, &l->dinv, &l->agg, &l->pcol, &l->pval, &l->rcol,
                            &l->rval, &l->rlen, &l->vec, &l->part, &l->gflag, &l->avalf, &l->pvalf, &l->rvalf, &l->adcol,
-                           &l->wcol, &l->wval, &l->wlen};
+                           &l->wcol, &l->wval, &l->wlen, &l->p2col, &l->p2val, &l->p2len, &l->d2};
             for (DevBuf *x : b) x->release();
             delete l;
         }
@@ -1440,6 +1446,12 @@ void decide_folds(SHierarchy *H, const unsigned long long *hs, bool trace) {
             fprintf(stderr, "[sagg] level %d (%lld rows): first post-smoothing sweep %s\n", k, (long long)L->n,
                     miss ? "NOT folded: a row of A P lacks a column of its P row (no stored diagonal)"
                          : "folded into the prolongation");
+        // (the three-launch visit ends with P2 = G W in the place of W: no W, no P2)
+        const bool wide = hs[(size_t)k * ST_COUNT + ST_VISITMISS] != 0;
+        L->visit = L->visit_want && L->fold && !wide;
+        if (trace && L->visit_want)
+            fprintf(stderr, "[sagg] level %d (%lld rows): visit %s\n", k, (long long)L->n,
+                    L->visit ? "in three launches" : "NOT in three launches: W missing, or a row of P2 beyond its slots");
     }
 }
 
@@ -1758,6 +1770,163 @@ int form_tail_op(nodal_ctx *h, SHierarchy *H) {
     return NODAL_OK;
 }
 
+// ---- the level directly above the dense tail in three launches: its operators (cycle kernels: sagg_cycle.h) ----
+// P2 = W - w D^-1 (A W), one WAVEFRONT per row, from the f32 W the A P kernel wrote and the level's f64 A and dinv, in
+// f64.  Lane u takes source u of the row -- source 0 the row's own W row (coefficient 1), source s the W row its A entry
+// s - 1 names (coefficient -w dinv_i a_ik) -- and stages its products in an LDS list at the offset a wave scan of the W
+// rows' lengths gives it: the list is in (source, slot) order.  The row's columns (< n_t <= 1024) are marked in a
+// 1024-bit mask and numbered in ascending order; lane q then sums the products of column q in list order: one order of
+// summation, slots sorted by column.  (One lane per row with ap_rows_lds's per-lane table took 115 us at 8.9 k rows: some
+// 500 dependent LDS probes per row on 139 wavefronts.)  More than P2CAP columns, or more than P2LIST products:
+// ST_VISITMISS (the level keeps its six launches).
+constexpr int P2LIST = 1024;
+__global__ __launch_bounds__(64) void p2_rows_wave(Ell A, const double *__restrict__ dinv, const int32_t *__restrict__ wcol,
+                                                   const float *__restrict__ wval, const int32_t *__restrict__ wlen,
+                                                   int32_t *__restrict__ p2col, float *__restrict__ p2val,
+                                                   int32_t *__restrict__ p2len, unsigned long long *__restrict__ stats) {
+    __shared__ int32_t lJ[P2LIST];
+    __shared__ double lV[P2LIST];
+    __shared__ uint32_t mask[TAIL_MAX_N / 32];
+    __shared__ int32_t cols[P2CAP];
+    static_assert(TAIL_MAX_N / 32 <= 64, "one lane per word of the column mask");
+    const int lane = threadIdx.x;
+    bool overflow = false;
+    for (int64_t i = blockIdx.x; i < A.n; i += gridDim.x) {
+        if (lane < TAIL_MAX_N / 32) mask[lane] = 0u;
+        const int32_t total = A.len[i] + 1;
+        const double wd = -OMEGA * dinv[i];
+        int np = 0;
+        bool fits = true;
+        for (int32_t g0 = 0; g0 < total; g0 += 64) {  // (one round unless the row has 64 entries)
+            const int32_t src = g0 + lane;
+            const bool has = src < total;
+            const int32_t su = has && src >= 1 ? src - 1 : 0;  // (unconditional loads: a slot of the row)
+            const int32_t ka = A.col[(int64_t)su * A.ld + i];
+            const double a = A.val[(int64_t)su * A.ld + i];
+            const int32_t k = src == 0 ? (int32_t)i : ka;
+            const double cf = src == 0 ? 1.0 : wd * a;
+            const int32_t lk = wlen[k];
+            const int32_t len = has ? lk : 0;
+            int tot = 0;
+            int o = np + wave_excl_scan(len, &tot);
+            if (np + tot > P2LIST) {  // (uniform)
+                fits = false;
+                break;
+            }
+            constexpr int SQ = 8;
+            for (int32_t s0 = 0; s0 < len; s0 += SQ) {
+                int32_t cj[SQ];
+                float cv[SQ];
+#pragma unroll
+                for (int q = 0; q < SQ; ++q) {
+                    const int32_t s = s0 + q < len ? s0 + q : s0;
+                    cj[q] = wcol[(int64_t)s * A.ld + k];
+                    cv[q] = wval[(int64_t)s * A.ld + k];
+                }
+#pragma unroll
+                for (int q = 0; q < SQ; ++q)
+                    if (s0 + q < len) {
+                        lJ[o] = cj[q];
+                        lV[o] = cf * (double)cv[q];
+                        ++o;
+                    }
+            }
+            np += tot;
+        }
+        __syncthreads();
+        if (fits)
+            for (int p = lane; p < np; p += 64) atomicOr(&mask[lJ[p] >> 5], 1u << (lJ[p] & 31));  // (a set: any order)
+        __syncthreads();
+        uint32_t m = lane < TAIL_MAX_N / 32 ? mask[lane] : 0u;
+        int distinct = 0;
+        int at = wave_excl_scan(__popc(m), &distinct);
+        if (!fits || distinct > P2CAP) {  // (uniform)
+            overflow = true;
+            if (lane == 0) p2len[i] = 0;
+            __syncthreads();
+            continue;
+        }
+        while (m) {  // the lane's columns in ascending order
+            cols[at++] = lane * 32 + (__ffs(m) - 1);
+            m &= m - 1u;
+        }
+        __syncthreads();
+        if (lane < distinct) {
+            const int32_t c = cols[lane];
+            double acc = 0.0;
+#pragma unroll 8
+            for (int p = 0; p < np; ++p) {
+                const int32_t j = lJ[p];
+                const double v = lV[p];
+                if (j == c) acc += v;
+            }
+            p2col[(int64_t)lane * A.ld + i] = c;
+            p2val[(int64_t)lane * A.ld + i] = (float)acc;
+        }
+        if (lane == 0) p2len[i] = distinct;
+        __syncthreads();  // (the next row reuses the list)
+    }
+    if (overflow) stats[ST_VISITMISS] = 1ull;  // (every writer stores the same word)
+}
+
+// d2 = 0 in 16-byte stores over the whole device (the runtime's fill took 27 us for 13.5 MB on 140 workgroups)
+__global__ __launch_bounds__(TB) void d2_zero(float4 *__restrict__ d, int64_t pieces) {
+    for (int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x; e < pieces; e += (int64_t)gridDim.x * TB)
+        d[e] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// d2[J * ld + i] = P2[i, J] (d2 zero-filled in front of this launch): one thread per slot of the P2 arrays
+__global__ __launch_bounds__(TB) void d2_scatter(int64_t n, int64_t ld, const int32_t *__restrict__ p2col,
+                                                 const float *__restrict__ p2val, const int32_t *__restrict__ p2len,
+                                                 float *__restrict__ d2) {
+    for (int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x; e < (int64_t)P2CAP * ld; e += (int64_t)gridDim.x * TB) {
+        const int64_t s = e / ld, i = e - s * ld;
+        if (i >= n || s >= p2len[i]) continue;
+        d2[(int64_t)p2col[e] * ld + i] = p2val[e];
+    }
+}
+
+// The sweep counts as NODAL_SA_NU names them (read per call: the solvers, and the setup's decision below)
+void apply_nu_knob(SHierarchy *H) {
+    if (const char *e = knob::SA_NU.now()) {  // e.g. "212": sweeps at level 0, level 1, deeper levels
+        for (int k = 0; k < 3 && e[k] >= '1' && e[k] <= '3'; ++k) H->nu[k] = e[k] - '0';
+    }
+}
+
+// Which level visits in three launches, and its operators (fresh setup and values-only refresh, behind the tail's
+// operator): the level directly above the dense tail, on the symmetric route (rc = P2^T b needs A = A^T and R = P^T),
+// with two sweeps per side, W written, outside level 0 (whose last sweep carries the outer iteration's dot products),
+// and a dense P2^T of at most NODAL_SA_VISIT_CAP bytes.  Nothing is built for any other level.
+// NODAL_SA_FOLD_VISIT=0: none.
+int build_visit(nodal_ctx *h, SHierarchy *H, bool general) {
+    static const bool on = knob::SA_FOLD_VISIT.now();
+    static const int64_t cap = knob::SA_VISIT_CAP.now();
+    for (int k = 0; k < H->nlev; ++k) H->pool[k]->visit_want = H->pool[k]->visit = false;
+    if (!on || general || H->tail < 2 || !H->tail_dense) return NODAL_OK;
+    const int l = H->tail - 1;
+    SLevel *L = H->pool[l];
+    apply_nu_knob(H);
+    const int64_t nt = H->pool[H->tail]->n;
+    if (H->nu[l < 2 ? l : 2] != 2 || !L->fold_want || nt > TAIL_MAX_N || nt * L->ld * 4 > cap) return NODAL_OK;
+    hipStream_t st = h->stream;
+    NODAL_HIP_TRY(h, L->p2col.reserve((size_t)P2CAP * L->ld * 4 + 64));
+    NODAL_HIP_TRY(h, L->p2val.reserve((size_t)P2CAP * L->ld * 4 + 64));
+    NODAL_HIP_TRY(h, L->p2len.reserve((size_t)L->ld * 4 + 64));
+    NODAL_HIP_TRY(h, L->d2.reserve((size_t)nt * L->ld * 4 + 64));
+    Ell A = L->A();
+    const unsigned gl = (unsigned)(L->n < 8192 ? L->n : 8192);
+    p2_rows_wave<<<gl, 64, 0, st>>>(A, L->dinv.as<double>(), L->wcol.as<int32_t>(), L->wval.as<float>(), L->wlen.as<int32_t>(),
+                                  L->p2col.as<int32_t>(), L->p2val.as<float>(), L->p2len.as<int32_t>(),
+                                  H->stats.as<unsigned long long>() + (size_t)l * ST_COUNT);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    d2_zero<<<grid_for(nt * L->ld / 4), TB, 0, st>>>(L->d2.as<float4>(), nt * L->ld / 4);  // (ld is a multiple of 64)
+    d2_scatter<<<grid_for((int64_t)P2CAP * L->ld), TB, 0, st>>>(L->n, L->ld, L->p2col.as<int32_t>(), L->p2val.as<float>(),
+                                                                 L->p2len.as<int32_t>(), L->d2.as<float>());
+    NODAL_HIP_TRY(h, hipGetLastError());
+    L->visit_want = true;
+    return NODAL_OK;
+}
+
 // NODAL_TRACE with NODAL_SA_FOLD_CHECK=1: per folded level both forms of the end of a visit -- k_prolong + k_post
 // against k_prolong_post -- on fixed vectors of both signs (x, b and the coarse correction uniform in (-1, 1), the
 // residual by k_smooth_residual as in the cycle).  Prints the level, its rows and
@@ -1825,6 +1994,7 @@ int fold_check_level(nodal_ctx *h, SHierarchy *H, int l, bool two) {
                     "(worst row against its own bound: %.3e)\n", l, (long long)n, (int)L->wslots, (int)L->maxlen, dm, qm);
     return NODAL_OK;
 }
+int visit_self_check(nodal_ctx *h, SHierarchy *H);  // (behind cycle(), which it runs)
 int fold_self_check(nodal_ctx *h, SHierarchy *H) {
     static const bool check = knob::TRACE.now() && knob::SA_FOLD_CHECK.now();
     if (!check) return NODAL_OK;
@@ -1977,6 +2147,7 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
     if (H->tail >= 0) k_tail_pack<<<1, 1024, 0, st>>>(H->td, H->tail_image.as<char>());
     NODAL_HIP_TRY(h, hipGetLastError());
     NODAL_TRY(form_tail_op(h, H));
+    NODAL_TRY(build_visit(h, H, general));
     NODAL_HIP_TRY(h, hipMemcpyAsync(hs, dstats, (size_t)MAX_LEVELS * ST_COUNT * 8, hipMemcpyDeviceToHost, st));
     NODAL_WAIT_STREAM(h, st);
     const int64_t bar = n0 / 100 < 32 ? (n0 / 100 > 0 ? n0 / 100 : 1) : 32;
@@ -1985,6 +2156,7 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
         if (hs[(size_t)k * ST_COUNT + ST_BADDIAG] || hs[(size_t)k * ST_COUNT + ST_OVERFLOW]) return NODAL_OK;
     decide_folds(H, hs, false);
     NODAL_TRY(fold_self_check(h, H));
+    NODAL_TRY(visit_self_check(h, H));
     *ok = true;
     return NODAL_OK;
 }
@@ -2195,6 +2367,7 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
         NODAL_HIP_TRY(h, L->part.reserve(5 * DOT_BLOCKS * 8 + 512));  // (+ s1, s2, the frozen triple, a ring of samples)
     }
     NODAL_TRY(build_tail(h, H, hs));
+    NODAL_TRY(build_visit(h, H, general));
 
     // structural singularity: OR the "touches ground" flags up, look at the last level
     if (!check_floating) {
@@ -2230,6 +2403,7 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
     }
     decide_folds(H, hs, trace);
     NODAL_TRY(fold_self_check(h, H));
+    NODAL_TRY(visit_self_check(h, H));
     H->ready = true;
     *accepted = true;
     H->sym_valid = true;
@@ -2284,6 +2458,26 @@ void kcycle_schedule(SHierarchy *H, int it) {
     }
 }
 
+// The visit of the level directly above the dense tail in three launches (kernels and algebra: sagg_cycle.h).  x1, x2 in
+// the slots the six-launch form uses for them; rc, c in the tail level's.
+int visit_three(nodal_ctx *h, SHierarchy *H, int l, const cyc_t *b, const cyc_t *x0, cyc_t *out) {
+    hipStream_t st = h->stream;
+    SLevel *L = H->pool[l], *C = H->pool[l + 1];
+    const Ell A = L->A();
+    const double *dinv = L->dinv.as<double>();
+    cyc_t *x1 = L->v<cyc_t>(V_X1), *x2 = L->v<cyc_t>(V_T);
+    double *rc = C->v<double>(V_RC), *c1 = C->v<double>(V_C1);
+    const int nt = (int)C->n;
+    const unsigned g = grid_for(L->n);
+    SAGG_DISPATCH_W(L->wfix, (k_visit_first<W><<<g + (unsigned)nt, TB, 0, st>>>(A, dinv, b, x0, x1, g, L->d2.as<float>(), rc)));
+    SAGG_DISPATCH_W(L->wfix, (k_visit_second<W><<<g + (unsigned)((nt + 3) / 4), TB, 0, st>>>(A, dinv, b, x1, x2, g, nt,
+                                                                                             H->tail_op.as<double>(), rc, c1)));
+    SAGG_DISPATCH_W(L->wfix, (k_visit_last<W><<<grid_for(L->n * VL), TB, 0, st>>>(A, dinv, b, x2, out, L->p2col.as<int32_t>(), L->p2val.as<float>(),
+                                                                L->p2len.as<int32_t>(), c1)));
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
 // One cycle of level l (never a last level: the hierarchy has two levels at least and the tail starts at level 1
 // or below).  TBV: type of the right-hand side (f64 from the outer iteration at level 0, cyc_t inside); TOUT: of the
 // result (cyc_t; f64 when the general path's FGMRES takes it as a Krylov vector).
@@ -2305,7 +2499,11 @@ int cycle(nodal_ctx *h, SHierarchy *H, int l, const TBV *b, const cyc_t *x0, TOU
     // is the residual k_smooth_residual leaves below.  One sweep with the outer iteration's dot products (reachable
     // through NODAL_SA_NU only) keeps the two launches: k_post<W, true> forms the dots.
     const bool fold = L->fold && !(sb && nu == 1);
-    auto hand_up = [&](const auto *c1, const auto *c2, const double *cf) {  // the coarse correction goes up into xp
+    if constexpr (std::is_same_v<TBV, cyc_t> && std::is_same_v<TOUT, cyc_t>) {
+        // the level directly above the dense tail: both chains of the visit side by side, three launches (SLevel::visit)
+        if (L->visit && !sb && nu == 2 && l + 1 == H->tail && H->tail_dense) return visit_three(h, H, l, b, x0, out);
+    }
+    auto hand_up =[&](const auto *c1, const auto *c2, const double *cf) {  // the coarse correction goes up into xp
         using TC = std::remove_cv_t<std::remove_pointer_t<decltype(c1)>>;
         if (!fold)
             k_prolong<TC><<<grid_for(n), TB, 0, st>>>(n, L->ld, L->pcol.as<int32_t>(), L->pvalf.as<float>(), x, c1, c2, cf, xp);
@@ -2417,6 +2615,159 @@ __global__ void f_set_scalars(double *__restrict__ sc, double tol2) {
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// NODAL_TRACE with NODAL_SA_VISIT_CHECK=1: the level that visits in three launches runs both forms of the visit on one
+// fixed right-hand side of both signs (b uniform in (-1, 1), x0 = w D^-1 b as its producer leaves it) and prints
+//   d = max_i |out_3 - out_6|_i / den_i,
+// den_i = the row-wise sum of the absolute terms that carry one f32 rounding each, formed on the host in fp64 from the
+// exported operators.  With e = 2^-24, |.| entrywise, |G| v = v + w D^-1 |A| v, and the exact operators (A, P in f64,
+// W = G P, P2 = G W) as the reference, the two forms leave it by (first order)
+//   six launches:  e_r = |r| + |A||x1|            (r rounded; the sweep reads the f32 copy of A)
+//                  e_c = |T| |P|^T (|r| + e_r)     (R = the f32 copy of P^T; T and its product are fp64)
+//                  e_xp = |xp| + w D^-1 e_r + |W||c| + |W| e_c
+//                  dev_6 = |out| + |G| e_xp + w D^-1 |A||xp|
+//   three:         e_x2 = |x2| + w D^-1 |A||x1|
+//                  E v = |P2| v + |G||W| v         (an entry of the stored P2: its own rounding and that of the W under it)
+//                  e_c' = |T| E^T |b|              (d2 holds P2's entries)
+//                  dev_3 = |out| + |G| e_x2 + w D^-1 |A||x2| + E |c| + |P2| e_c'
+// times e each (x1 is the same launch on the same operands in both forms: the same bits), so den = dev_6 + dev_3 and
+// d <= 2^-24 up to second-order terms and the fp64 sums (each over fewer than n + n_t terms, 2^-53 apiece: below 2^-36
+// of their absolute terms at 1e5 rows).  The per-row bound is therefore 2 x 2^-24 = 2^-23 whatever the slot counts: the
+// slots enter through den, every sum is fp64 and no rounding is per slot.  q = the largest d_i over 2^-23.
+int visit_check_level(nodal_ctx *h, SHierarchy *H, int l) {
+    hipStream_t st = h->stream;
+    SLevel *L = H->pool[l], *C = H->pool[l + 1];
+    const int64_t n = L->n, ld = L->ld, nt = C->n;
+    uint64_t seed = 0x9e3779b97f4a7c15ull + 977ull * (uint64_t)l;
+    auto unit = [&]() {  // (splitmix64: uniform in (-1, 1))
+        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        return (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
+    };
+    std::vector<double> dinv((size_t)n), T((size_t)nt * nt), c6((size_t)nt), c3((size_t)nt);
+    std::vector<cyc_t> hb((size_t)n), hx0((size_t)n), x1((size_t)n), x2((size_t)n), r((size_t)n), xp((size_t)n),
+        o6((size_t)n), o3((size_t)n);
+    std::vector<int32_t> acol((size_t)L->width * ld), alen((size_t)n), pcol((size_t)PW * ld), wcol((size_t)L->wslots * ld),
+        wlen((size_t)n), p2col((size_t)P2CAP * ld), p2len((size_t)n);
+    std::vector<float> aval((size_t)L->width * ld), pval((size_t)PW * ld), wval((size_t)L->wslots * ld),
+        p2val((size_t)P2CAP * ld);
+    auto down = [&](void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = down(dinv.data(), L->dinv.p, (size_t)n * 8);
+    for (int64_t i = 0; i < n; ++i) {
+        hb[i] = (cyc_t)unit();
+        hx0[i] = (cyc_t)(OMEGA * dinv[i] * (double)hb[i]);
+    }
+    const size_t vb = align256((size_t)n * sizeof(cyc_t));
+    DevBuf buf;
+    if (e == hipSuccess) e = buf.reserve(4 * vb);
+    char *p = buf.as<char>();
+    cyc_t *b = reinterpret_cast<cyc_t *>(p), *x0 = reinterpret_cast<cyc_t *>(p + vb), *out6 = reinterpret_cast<cyc_t *>(p + 2 * vb),
+          *out3 = reinterpret_cast<cyc_t *>(p + 3 * vb);
+    if (e == hipSuccess) e = hipMemcpyAsync(b, hb.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(x0, hx0.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
+    int rc = NODAL_OK;
+    if (e == hipSuccess) {
+        L->visit = false;
+        rc = cycle<cyc_t, cyc_t>(h, H, l, b, x0, out6, nullptr);
+        L->visit = true;
+    }
+    if (e == hipSuccess && rc == NODAL_OK) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = down(r.data(), L->v<cyc_t>(V_R), (size_t)n * sizeof(cyc_t));
+    if (e == hipSuccess) e = down(xp.data(), L->v<cyc_t>(V_XP), (size_t)n * sizeof(cyc_t));
+    if (e == hipSuccess) e = down(c6.data(), C->v<double>(V_C1), (size_t)nt * 8);
+    if (e == hipSuccess && rc == NODAL_OK) rc = cycle<cyc_t, cyc_t>(h, H, l, b, x0, out3, nullptr);
+    if (e == hipSuccess && rc == NODAL_OK) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = down(x1.data(), L->v<cyc_t>(V_X1), (size_t)n * sizeof(cyc_t));
+    if (e == hipSuccess) e = down(x2.data(), L->v<cyc_t>(V_T), (size_t)n * sizeof(cyc_t));
+    if (e == hipSuccess) e = down(c3.data(), C->v<double>(V_C1), (size_t)nt * 8);
+    if (e == hipSuccess) e = down(o6.data(), out6, (size_t)n * sizeof(cyc_t));
+    if (e == hipSuccess) e = down(o3.data(), out3, (size_t)n * sizeof(cyc_t));
+    if (e == hipSuccess) e = down(acol.data(), L->acol.p, acol.size() * 4);
+    if (e == hipSuccess) e = down(aval.data(), L->avalf.p, aval.size() * 4);
+    if (e == hipSuccess) e = down(alen.data(), L->alen.p, (size_t)n * 4);
+    if (e == hipSuccess) e = down(pcol.data(), L->pcol.p, pcol.size() * 4);
+    if (e == hipSuccess) e = down(pval.data(), L->pvalf.p, pval.size() * 4);
+    if (e == hipSuccess) e = down(wcol.data(), L->wcol.p, wcol.size() * 4);
+    if (e == hipSuccess) e = down(wval.data(), L->wval.p, wval.size() * 4);
+    if (e == hipSuccess) e = down(wlen.data(), L->wlen.p, (size_t)n * 4);
+    if (e == hipSuccess) e = down(p2col.data(), L->p2col.p, p2col.size() * 4);
+    if (e == hipSuccess) e = down(p2val.data(), L->p2val.p, p2val.size() * 4);
+    if (e == hipSuccess) e = down(p2len.data(), L->p2len.p, (size_t)n * 4);
+    if (e == hipSuccess) e = down(T.data(), H->tail_op.p, (size_t)nt * nt * 8);
+    buf.release();
+    if (rc != NODAL_OK) return rc;
+    NODAL_HIP_TRY(h, e);
+    using Vec = std::vector<double>;
+    auto absv = [](const auto &v) { Vec y(v.size()); for (size_t i = 0; i < v.size(); ++i) y[i] = fabs((double)v[i]); return y; };
+    auto add = [](Vec a, const Vec &b2) { for (size_t i = 0; i < a.size(); ++i) a[i] += b2[i]; return a; };
+    auto wd = [&](Vec v) { for (int64_t i = 0; i < n; ++i) v[i] *= OMEGA * dinv[i]; return v; };
+    auto absA = [&](const Vec &v) {
+        Vec y((size_t)n, 0.0);
+        for (int64_t i = 0; i < n; ++i)
+            for (int32_t s = 0; s < alen[i]; ++s) y[i] += fabs((double)aval[(size_t)s * ld + i]) * v[acol[(size_t)s * ld + i]];
+        return y;
+    };
+    auto absG = [&](const Vec &v) { return add(v, wd(absA(v))); };
+    auto absGT = [&](const Vec &v) { return add(v, absA(wd(v))); };  // (|a_ij| = |a_ji|)
+    // a column-major ELL operator n x n_t (slots, cols, vals, per-row length or -1 entries): |M| v and |M|^T v
+    auto ell = [&](int slots, const std::vector<int32_t> &col, const std::vector<float> &val, const std::vector<int32_t> *len,
+                   const Vec &v, bool transposed) {
+        Vec y((size_t)(transposed ? nt : n), 0.0);
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t m = len ? (*len)[i] : slots;
+            for (int32_t s = 0; s < m; ++s) {
+                const int32_t J = col[(size_t)s * ld + i];
+                if (J < 0) continue;
+                const double a = fabs((double)val[(size_t)s * ld + i]);
+                if (transposed) y[J] += a * v[i];
+                else y[i] += a * v[J];
+            }
+        }
+        return y;
+    };
+    auto absT = [&](const Vec &v) {
+        Vec y((size_t)nt, 0.0);
+        for (int64_t i = 0; i < nt; ++i)
+            for (int64_t j = 0; j < nt; ++j) y[i] += fabs(T[(size_t)i * nt + j]) * v[j];
+        return y;
+    };
+    auto Pt = [&](const Vec &v) { return ell(PW, pcol, pval, nullptr, v, true); };
+    auto Wm = [&](const Vec &v) { return ell(L->wslots, wcol, wval, &wlen, v, false); };
+    auto Wt = [&](const Vec &v) { return ell(L->wslots, wcol, wval, &wlen, v, true); };
+    auto P2m = [&](const Vec &v) { return ell(P2CAP, p2col, p2val, &p2len, v, false); };
+    auto P2t = [&](const Vec &v) { return ell(P2CAP, p2col, p2val, &p2len, v, true); };
+    const Vec ax1 = absA(absv(x1));
+    const Vec e_r = add(absv(r), ax1);
+    const Vec e_c6 = absT(Pt(add(absv(r), e_r)));
+    const Vec e_xp = add(add(absv(xp), wd(e_r)), add(Wm(absv(c6)), Wm(e_c6)));
+    const Vec dev6 = add(add(absv(o6), absG(e_xp)), wd(absA(absv(xp))));
+    const Vec e_x2 = add(absv(x2), wd(ax1));
+    const Vec e_c3 = absT(add(P2t(absv(hb)), Wt(absGT(absv(hb)))));
+    const Vec ac3 = absv(c3);
+    const Vec dev3 = add(add(add(absv(o3), absG(e_x2)), wd(absA(absv(x2)))), add(add(P2m(ac3), absG(Wm(ac3))), P2m(e_c3)));
+    double dm = 0.0;
+    int maxp2 = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const double di = fabs((double)o3[i] - (double)o6[i]) / (dev6[i] + dev3[i]);  // (0 / 0: a NaN, which the maximum keeps)
+        dm = !(di <= dm) ? di : dm;
+        maxp2 = p2len[i] > maxp2 ? p2len[i] : maxp2;
+    }
+    fprintf(stderr, "[sagg] visit check: level %d, rows %lld, n_t %lld, longest P2 row %d, three launches against the six "
+                    "d = %.3e (against the bound 2^-23: %.3e)\n", l, (long long)n, (long long)nt, maxp2, dm, dm / 0x1p-23);
+    return NODAL_OK;
+}
+int visit_self_check(nodal_ctx *h, SHierarchy *H) {
+    static const bool check = knob::TRACE.now() && knob::SA_VISIT_CHECK.now();
+    if (!check) return NODAL_OK;
+    for (int l = 1; l + 1 < H->nlev; ++l) {
+        const SLevel *L = H->pool[l];
+        if (L->visit && l + 1 == H->tail && H->tail_dense && H->nu[l < 2 ? l : 2] == 2) NODAL_TRY(visit_check_level(h, H, l));
+    }
+    return NODAL_OK;
+}
+
 }  // namespace
 
 // z ~= A^-1 r with one cycle of the hierarchy built by sagg_setup_csr (the preconditioner of the
@@ -2506,6 +2857,10 @@ int sagg_debug_array(nodal_ctx *h, int32_t level, int32_t which, void *dst, int6
         case NODAL_HA_WCOL: buf = &L->wcol; bytes = wslots * 4; break;
         case NODAL_HA_WVAL: buf = &L->wval; bytes = wslots * 4; break;
         case NODAL_HA_WLEN: buf = &L->wlen; bytes = wslots ? L->n * 4 : 0; break;
+        case NODAL_HA_P2COL: buf = &L->p2col; bytes = next && L->visit_want ? (int64_t)P2CAP * L->ld * 4 : 0; break;
+        case NODAL_HA_P2VAL: buf = &L->p2val; bytes = next && L->visit_want ? (int64_t)P2CAP * L->ld * 4 : 0; break;
+        case NODAL_HA_P2LEN: buf = &L->p2len; bytes = next && L->visit_want ? L->n * 4 : 0; break;
+        case NODAL_HA_D2: buf = &L->d2; bytes = next && L->visit_want ? L->nc * L->ld * 4 : 0; break;
         default: return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: no such array");
         }
     }
@@ -2590,9 +2945,7 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
     static const int kc = knob::SA_KCYCLE.now();
     H->kcycle = kc != 0;
     H->klevels = knob::SA_KLEVELS.now();
-    if (const char *e = knob::SA_NU.now()) {  // e.g. "212": sweeps at level 0, level 1, deeper levels
-        for (int k = 0; k < 3 && e[k] >= '1' && e[k] <= '3'; ++k) H->nu[k] = e[k] - '0';
-    }
+    apply_nu_knob(H);
 
     const size_t vec = align_up((size_t)n * 8);
     NODAL_HIP_TRY(h, h->solver.reserve(6 * vec + 4 * MAX_PARTIALS * 8 + F_COUNT * 8 + 256));
@@ -2707,6 +3060,11 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
             for (const void *q : ps) mix((uint64_t)(uintptr_t)q);
             mix((uint64_t)(L->fold ? 1 + L->wslots : 0));
             if (L->fold) { mix((uint64_t)(uintptr_t)L->wcol.p); mix((uint64_t)(uintptr_t)L->wval.p); mix((uint64_t)(uintptr_t)L->wlen.p); }
+            mix((uint64_t)L->visit);
+            if (L->visit) {
+                mix((uint64_t)(uintptr_t)L->p2col.p); mix((uint64_t)(uintptr_t)L->p2val.p);
+                mix((uint64_t)(uintptr_t)L->p2len.p); mix((uint64_t)(uintptr_t)L->d2.p);
+            }
             mix((uint64_t)L->n); mix((uint64_t)L->ld); mix((uint64_t)L->wfix); mix((uint64_t)L->rld);
         }
         if (H->it_exec && H->it_key != key) H->drop_graph();

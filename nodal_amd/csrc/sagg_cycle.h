@@ -803,35 +803,49 @@ __global__ __launch_bounds__(1024) void k_tail_pack_op(TailDesc d, const char *_
 // wave_sum: one order of summation.  NV > 1: a block of NV interleaved right-hand sides (vectors strided by NV,
 // sagg_multi.h); the row's loads serve all of them.  A zero of T takes nothing from rc (a block-diagonal T keeps a
 // NaN inside its block, as the cycle does).
+// row i of out = T rc for one right-hand side, by one wavefront (k_tail_apply<CH, 1> and the second launch of the
+// three-launch visit, k_visit_second: a chunk past the row's end adds nothing, so every CH >= n / 64 gives the same bits)
+template <int CH>
+__device__ __forceinline__ void tail_apply_row(int n, const double *__restrict__ T, const double *__restrict__ rc,
+                                               double *__restrict__ out, int i, int lane) {
+    const double *row = T + (int64_t)i * n;
+    double t[CH], r[CH];
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+        const int j = lane + 64 * u;
+        t[u] = row[j < n ? j : 0];
+    }
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+        const int j = lane + 64 * u;
+        r[u] = rc[j < n ? j : 0];
+    }
+    double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+    for (int u = 0; u < CH; u += 2) {
+        if (lane + 64 * u < n && t[u] != 0.0) s0 = fma(t[u], r[u], s0);
+        if (lane + 64 * (u + 1) < n && t[u + 1] != 0.0) s1 = fma(t[u + 1], r[u + 1], s1);
+    }
+    const double s = wave_sum(s0 + s1);
+    if (lane == 0) out[i] = s;
+}
+
 template <int CH, int NV>
 __global__ __launch_bounds__(256) void k_tail_apply(int n, const double *__restrict__ T,
                                                     const double *__restrict__ rc, double *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int i = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
-    const double *row = T + (int64_t)i * n;
-    double t[CH];
-#pragma unroll
-    for (int u = 0; u < CH; ++u) {
-        const int j = lane + 64 * u;
-        t[u] = row[j < n ? j : 0];
-    }
     if constexpr (NV == 1) {
-        double r[CH];
+        tail_apply_row<CH>(n, T, rc, out, i, lane);
+    } else {
+        const double *row = T + (int64_t)i * n;
+        double t[CH];
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
             const int j = lane + 64 * u;
-            r[u] = rc[j < n ? j : 0];
+            t[u] = row[j < n ? j : 0];
         }
-        double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-        for (int u = 0; u < CH; u += 2) {
-            if (lane + 64 * u < n && t[u] != 0.0) s0 = fma(t[u], r[u], s0);
-            if (lane + 64 * (u + 1) < n && t[u + 1] != 0.0) s1 = fma(t[u + 1], r[u + 1], s1);
-        }
-        const double s = wave_sum(s0 + s1);
-        if (lane == 0) out[i] = s;
-    } else {
         double s[NV];
 #pragma unroll
         for (int c = 0; c < NV; ++c) s[c] = 0.0;
@@ -851,6 +865,172 @@ __global__ __launch_bounds__(256) void k_tail_apply(int n, const double *__restr
             const double v = wave_sum(s[c]);
             if (lane == 0) out[(int64_t)i * NV + c] = v;
         }
+    }
+}
+
+// ---- the level directly above the dense tail in three launches (SLevel::visit) ----
+// With G = I - w D^-1 A, sweep(x) = G x + w D^-1 b, x0 = w D^-1 b, W = G P, P2 = G W, R = P^T and A = A^T, the six
+// launches  x1 = sweep(x0); r = b - A x1; rc = R r; c = T rc; xp = x1 + w D^-1 r + W c; out = sweep(xp)  are
+//     rc = P2^T b,   out = sweep(sweep(x1)) + P2 c:
+// the smoothing chain x0 -> x1 -> x2 -> out and the coarse chain b -> rc -> c share no intermediate result and meet in
+// the last launch.  Launch 1 and 2 run one link of each chain side by side: the leading `grows` workgroups sweep the
+// level's rows, the others form rc (one workgroup per coarse row of the dense P2^T) resp. c (k_tail_apply's rows).  No
+// workgroup reads what another workgroup of the same launch writes.
+static_assert(LPR_RAGGED == 1 && TB == 256, "the visit's launches mix row blocks and dense-row blocks of 256 threads");
+
+// xcd_block() for a part of a launch: the part's blocks [first, first + count) numbered from 0
+__device__ __forceinline__ unsigned xcd_block_sub(unsigned first, unsigned count) {
+    const unsigned b = blockIdx.x - first;
+    return (count & 7u) ? b : (b & 7u) * (count >> 3) + (b >> 3);
+}
+
+// xout = xin + w D^-1 (b - A xin) on the rows of the sub-grid's block `vb` (k_post's row body)
+template <int W>
+__device__ __forceinline__ void visit_sweep_rows(const Ell &A, const double *__restrict__ dinv, const cyc_t *__restrict__ b,
+                                                 const cyc_t *__restrict__ xin, cyc_t *__restrict__ xout, unsigned vb,
+                                                 unsigned count) {
+    for (int64_t i = (int64_t)vb * TB + threadIdx.x; i < A.n; i += (int64_t)count * TB) {
+        const double s = ell_row_w<W>(A, A.valf, i, 0, [&](int32_t j) { return (double)xin[j]; });
+        xout[i] = (cyc_t)fma(OMEGA * dinv[i], (double)b[i] - s, (double)xin[i]);
+    }
+}
+
+// launch 1: { x1 = sweep(x0) } || { rc = P2^T b }.  D2 = P2^T dense, nt x ld row-major f32 (zeros outside P2's pattern
+// and in the columns n .. ld).  One workgroup per coarse row: thread t takes the 16-byte pieces t, t + 256, ... of the
+// row and of b, ten of each in flight; per-thread sums in piece order, wave_sum, the four waves' sums in wave order:
+// one order of summation, no atomics.  A zero of D2 takes nothing from b (as in k_tail_apply).
+template <int W>
+__global__ __launch_bounds__(TB) void k_visit_first(Ell A, const double *__restrict__ dinv, const cyc_t *__restrict__ b,
+                                                    const cyc_t *__restrict__ x0, cyc_t *__restrict__ x1, unsigned grows,
+                                                    const float *__restrict__ D2, double *__restrict__ rc) {
+    if (blockIdx.x < grows) {
+        visit_sweep_rows<W>(A, dinv, b, x0, x1, xcd_block_sub(0, grows), grows);
+        return;
+    }
+    __shared__ double ws[TB / 64];
+    const int64_t I = (int64_t)(blockIdx.x - grows);
+    const float4 *row = reinterpret_cast<const float4 *>(D2 + I * A.ld);
+    const float4 *bv = reinterpret_cast<const float4 *>(b);
+    const int pieces = (int)(A.ld >> 2);  // (ld is a multiple of 64)
+    constexpr int U = 10;  // (10 x 256 pieces of four columns: a row of up to 10 240 columns in one round trip)
+    double s0 = 0.0, s1 = 0.0;
+    for (int p0 = threadIdx.x; p0 < pieces; p0 += TB * U) {
+        float4 d[U], v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int p = p0 + TB * u;
+            d[u] = row[p < pieces ? p : p0];
+            v[u] = bv[p < pieces ? p : p0];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int p = p0 + TB * u;
+            if (p >= pieces) continue;
+            const int64_t j = (int64_t)p * 4;
+            if (j + 0 < A.n && d[u].x != 0.0f) s0 = fma((double)d[u].x, (double)v[u].x, s0);
+            if (j + 1 < A.n && d[u].y != 0.0f) s1 = fma((double)d[u].y, (double)v[u].y, s1);
+            if (j + 2 < A.n && d[u].z != 0.0f) s0 = fma((double)d[u].z, (double)v[u].z, s0);
+            if (j + 3 < A.n && d[u].w != 0.0f) s1 = fma((double)d[u].w, (double)v[u].w, s1);
+        }
+    }
+    const double s = wave_sum(s0 + s1);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < TB / 64; ++w) t += ws[w];
+        rc[I] = t;
+    }
+}
+
+// launch 2: { x2 = sweep(x1) } || { c = T rc } (k_tail_apply's rows: four per workgroup, one wavefront each)
+template <int W>
+__global__ __launch_bounds__(TB) void k_visit_second(Ell A, const double *__restrict__ dinv, const cyc_t *__restrict__ b,
+                                                     const cyc_t *__restrict__ x1, cyc_t *__restrict__ x2, unsigned grows,
+                                                     int nt, const double *__restrict__ T, const double *__restrict__ rc,
+                                                     double *__restrict__ c) {
+    if (blockIdx.x < grows) {
+        visit_sweep_rows<W>(A, dinv, b, x1, x2, xcd_block_sub(0, grows), grows);
+        return;
+    }
+    const int i = (int)(blockIdx.x - grows) * 4 + (int)(threadIdx.x >> 6);
+    if (i >= nt) return;
+    tail_apply_row<TAIL_MAX_N / 64>(nt, T, rc, c, i, (int)(threadIdx.x & 63));
+}
+
+// launch 3: out = sweep(x2) + P2 c.  VL adjacent lanes share a row: lane `sub` takes the slots sub, sub + VL, ... of the
+// row of A and of the P2 row (column-major like W, f32, at most P2CAP slots: every slot number below the cap is
+// addressable, so its P2CAP / VL loads do not wait for the row's length), all requested before the first gather: two
+// dependent round trips whatever the rows' lengths (one thread walking a 30-slot P2 row in batches of 16 behind a
+// 32-slot row of A took 7.7 us at 8.9 k rows).  The lanes' partial sums are added by shuffles in one fixed order.
+constexpr int P2CAP = 64;
+constexpr int VL = 4;
+template <int W>
+__global__ __launch_bounds__(TB) void k_visit_last(Ell A, const double *__restrict__ dinv, const cyc_t *__restrict__ b,
+                                                   const cyc_t *__restrict__ x2, cyc_t *__restrict__ out,
+                                                   const int32_t *__restrict__ p2col, const float *__restrict__ p2val,
+                                                   const int32_t *__restrict__ p2len, const double *__restrict__ c) {
+    constexpr int PQ = P2CAP / VL, AQ = W > 0 ? (W + VL - 1) / VL : 8, ROWS = TB / VL;
+    static_assert(P2CAP % VL == 0 && TB % VL == 0 && 64 % VL == 0, "whole rows per wavefront");
+    const int sub = threadIdx.x & (VL - 1);
+    for (int64_t i = (int64_t)xcd_block() * ROWS + threadIdx.x / VL; i < A.n; i += (int64_t)gridDim.x * ROWS) {
+        const int32_t len = p2len[i];
+        int32_t J[PQ];
+        float w[PQ];
+#pragma unroll
+        for (int j = 0; j < PQ; ++j) {
+            J[j] = p2col[(int64_t)(sub + VL * j) * A.ld + i];
+            w[j] = p2val[(int64_t)(sub + VL * j) * A.ld + i];
+        }
+        double s = 0.0;
+        if constexpr (W > 0) {
+            int32_t ca[AQ];
+            float va[AQ];
+#pragma unroll
+            for (int j = 0; j < AQ; ++j) {
+                const int q = sub + VL * j;
+                const int64_t at = (int64_t)(q < W ? q : 0) * A.ld + i;
+                ca[j] = A.col[at];
+                va[j] = A.valf[at];
+            }
+#pragma unroll
+            for (int j = 0; j < AQ; ++j) {
+                const double xv = (double)x2[ca[j]];
+                if (sub + VL * j < W) s = fma((double)va[j], xv, s);
+            }
+        } else {
+            const int32_t la = A.len[i];
+            for (int32_t s0 = sub; s0 < la; s0 += VL * AQ) {
+                int32_t ca[AQ];
+                float va[AQ];
+#pragma unroll
+                for (int j = 0; j < AQ; ++j) {
+                    const int32_t q = s0 + VL * j;
+                    const int64_t at = (int64_t)(q < la ? q : s0) * A.ld + i;
+                    ca[j] = A.col[at];
+                    va[j] = A.valf[at];
+                }
+#pragma unroll
+                for (int j = 0; j < AQ; ++j) {
+                    const double xv = (double)x2[ca[j]];
+                    if (s0 + VL * j < la) s = fma((double)va[j], xv, s);
+                }
+            }
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < PQ; ++j) {
+            const bool ok = sub + VL * j < len;  // (a slot past the end holds whatever the buffer held: neither gathered nor used)
+            const double cv = c[ok ? J[j] : 0];
+            if (ok) acc = fma((double)w[j], cv, acc);
+        }
+#pragma unroll
+        for (int off = VL >> 1; off > 0; off >>= 1) {
+            s += __shfl_xor(s, off, 64);
+            acc += __shfl_xor(acc, off, 64);
+        }
+        if (sub == 0) out[i] = (cyc_t)(fma(OMEGA * dinv[i], (double)b[i] - s, (double)x2[i]) + acc);
     }
 }
 
