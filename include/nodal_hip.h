@@ -484,6 +484,60 @@ int nodal_ac_ports(nodal_handle h, int32_t dense, int32_t nfreq, const double *o
                    double *resid_out /* [nfreq][nports] or NULL */, int32_t *info_out /* [nfreq] or NULL */,
                    int64_t *work_out /* [3] or NULL */);
 
+/* ---- gradients through frequency: the adjoint of the AC analysis (replaces central differences of nodal_ac_sweep, two
+ *      sweeps per component, capacitor, inductor and amplitude; the reference has no equivalent) ----
+ * A(omega) = G + j B(omega) exactly as nodal_ac_sweep defines it, with the same frequency, reactive-element, source and
+ * probe arguments.  The forward system is A x_f = s, s from the driven rows src_rows with amplitudes alpha_j, every other
+ * independent source off; probe p reads W[f][p] = x_f(a_p) - x_f(b_p).  For a real scalar loss L of the probe phasors the
+ * caller passes the cotangent
+ *   wave_cot [nfreq][nprobe][2]        g[f][p] = dL/dRe W[f][p] + j dL/dIm W[f][p] as (re, im), so dL = Re(sum conj(g) dW)
+ * and nothing else is conjugated anywhere.  The adjoint system is
+ *   c_f = sum_p conj(g[f][p]) (e(a_p) - e(b_p))         (added in probe order; probes may share nodes; a_p == b_p adds nothing)
+ *   A(omega_f)^T y_f = c_f                              (the plain transpose, as nodal_ac_noise has it)
+ * and dL = sum_f Re(y_f^T (ds - dA x_f)).  With X, L the complex x_f, y_f (+0.0 at a ground lead), D the difference of L
+ * and U that of X over the leads the static adjoint (nodal_sensitivities) names for the row, m = K + k the branch unknown:
+ *   table row R, value v               Re(D U) / v^2, plus for every CCVS / CCCS row j it drives
+ *                                      Re(L(m_j) v_j (X(c_j) - X(d_j))) / v^2, in table order
+ *   VCVS (VCCS) row                    Re(L(m) U)
+ *   CCVS, CCCS row                     -Re(L(m) U) / Rd
+ *   A, E row, a row without a term     exactly +0.0 (the small-signal excitation never reads the table value)
+ *   capacitor C on (a, b)              omega Im(D U)
+ *   inductor L on (a, b)               Im(D U) / (omega L^2)
+ *   amplitude of driven row j          conj(D_j), D_j = L(a) - L(b) for an A row and L(m) for an E row, in g's convention
+ * Outputs, each may be NULL:
+ *   wave_out [nfreq][nprobe][2]        the forward phasors, as nodal_ac_sweep gives them
+ *   grad_out [ncomp]                   dL/d(table value), summed over the frequencies on the device in ascending index
+ *   grad_react_out [nreact]            dL/dC, dL/dL with respect to the values as passed, summed likewise
+ *   grad_sources_out [nfreq][nsrc][2]  the term of each frequency (the amplitudes are constant over the sweep: the caller sums)
+ *   adjoint_out [nfreq / keep_every][n][2]   y of every keep_every-th frequency (keep_every == 0: none)
+ *   resid_out [nfreq][2]               the scaled residual of the forward and of the adjoint system
+ *   info_out [nfreq]                   > 0: singular at that frequency -- NaN in its rows and in the whole of grad_out and
+ *                                      grad_react_out, status OK -- except with dense != 0, where it returns NODAL_E_SINGULAR
+ *   work_out [3]                       as nodal_ac_ports counts it: numeric factorisations, block applications, columns
+ *                                      redone alone
+ * Routes: a symmetric G (no branch rows, every R > 0) has A^T = A, and s and c_f are two columns of ONE factorisation per
+ * frequency on the matrix nodal_ac_sweep keeps; every other network solves one column there and one on the transposed
+ * matrix nodal_ac_noise keeps, two factorisations per frequency.  Pattern and symbolic analysis are shared with
+ * nodal_ac_sweep, nodal_ac_noise and nodal_ac_ports in both directions.  2n <= 64 the dense panel, dense != 0 the dense LU,
+ * everything else the sparse LU with nodal_ac_ports' refinement, judgement and redo of a column above the bar.  The table
+ * pass runs on the device (csrc/ac_gradient.hip), one lane per row, no floating-point atomics: a repeated call gives the
+ * same bits.  Phasors, source terms and residuals come down once after the last frequency, the gradients once.
+ * nodal_last_timings afterwards: as after nodal_ac_sweep.
+ * NODAL_E_INVALID: every argument error of nodal_ac_sweep, a probe node outside [-1, K), wave_cot == NULL with nfreq > 0
+ * and nprobe > 0, a cotangent that is not finite.  nfreq == 0, nprobe == 0 and n == 0 give zeros in the gradients.
+ * Leaves the handle as it found it, the kept work of nodal_ac_sweep, nodal_ac_noise and nodal_ac_ports included. */
+int nodal_ac_gradient(nodal_handle h, int32_t dense, int32_t nfreq, const double *omega /* [nfreq], rad/s, > 0 */,
+                      int64_t nreact, const uint8_t *kind /* 0 capacitor, 1 inductor */, const double *value /* F or H */,
+                      const int32_t *lead_a, const int32_t *lead_b /* node indices, -1 ground */,
+                      int32_t nsrc, const int64_t *src_rows, const double *src_re, const double *src_im,
+                      int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b /* node indices, -1 ground */,
+                      const double *wave_cot /* [nfreq][nprobe][2] */, double *wave_out /* [nfreq][nprobe][2] or NULL */,
+                      double *grad_out /* [ncomp] or NULL */, double *grad_react_out /* [nreact] or NULL */,
+                      double *grad_sources_out /* [nfreq][nsrc][2] or NULL */, int32_t keep_every,
+                      double *adjoint_out /* [nfreq / keep_every][n][2] or NULL */,
+                      double *resid_out /* [nfreq][2] or NULL */, int32_t *info_out /* [nfreq] or NULL */,
+                      int64_t *work_out /* [3] or NULL */);
+
 /* ---- multiport Thevenin / Norton equivalents (replaces a loop of equivalent_resistance over node pairs, reference
  *      nodal/equiv.py:31-61: one rebuild and solve per pair, resistive networks only, the number R(a, b) alone; the
  *      reference has no equivalent of an active network and no coupling between ports) ----

@@ -16,4 +16,5 @@ from .transient import Transient, TransientEnvelope, resolve_capacitors  # noqa:
 from .ac import ACPeaks, ACSweep, resolve_reactive  # noqa: E402,F401
 from .noise import NoiseSweep, trapezoid_weights  # noqa: E402,F401
 from .ac_ports import ACPortPeaks, ACPortSweep, check_ac_port_arguments  # noqa: E402,F401
+from .ac_gradient import ACGradient, check_ac_gradient_arguments  # noqa: E402,F401
 from .ports import PortEquivalent, resolve_ports  # noqa: E402,F401

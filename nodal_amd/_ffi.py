@@ -71,6 +71,9 @@ SIGNATURES = {
                                  C.c_int32, _i32p, _i32p, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_ac_ports": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
                                  _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _f64p, _i32p, _i64p]),
+    "nodal_ac_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
+                                    _i64p, _f64p, _f64p, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
+                                    C.c_int32, _f64p, _f64p, _i32p, _i64p]),
     "nodal_port_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_residual": (C.c_int, [C.c_void_p, _f64p]),
     "nodal_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _i32p]),
@@ -619,6 +622,48 @@ class Handle:
             opt(peak[2], C.c_int32) if peaks else None, opt(resid, C.c_double), opt(info, C.c_int32),
             _ptr(work, C.c_int64)))
         return z, peak, resid, info, work
+
+    def ac_gradient(self, omega, kind, value, lead_a, lead_b, rows, amplitudes, ia, ib, cotangents, dense, adjoints=False):
+        """The adjoint of the frequency sweep on the circuit's own handle (nodal_ac_gradient): omega [F] in rad/s, the
+        reactive elements, the driven rows with their complex amplitudes and the probes as ac_sweep takes them,
+        cotangents complex128 [F, P] = dL/dRe W + j dL/dIm W of the probe phasors W.  Returns (phasors complex128
+        [F, P], grad [ncomp], grad_reactive [E], source terms complex128 [F, R], adjoints complex128 [F, n] or None,
+        scaled residual [F, 2] of the forward and the adjoint system, info [F], work int64 [3] as ac_ports counts it);
+        NodalHipError(E_INVALID) as the header lists, with dense a singular frequency raises
+        NodalHipError(E_SINGULAR)."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        value = np.ascontiguousarray(value, dtype=np.float64)
+        lead_a, lead_b = (np.ascontiguousarray(v, dtype=np.int32) for v in (lead_a, lead_b))
+        assert omega.ndim == 1 and kind.ndim == 1 and value.shape == kind.shape == lead_a.shape == lead_b.shape
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        amplitudes = np.asarray(amplitudes, dtype=np.complex128)
+        assert rows.ndim == 1 and amplitudes.shape == rows.shape
+        src_re, src_im = np.ascontiguousarray(amplitudes.real), np.ascontiguousarray(amplitudes.imag)
+        ia, ib = (np.ascontiguousarray(v, dtype=np.int32) for v in (ia, ib))
+        assert ia.ndim == 1 and ib.shape == ia.shape
+        nfreq, nprobe = len(omega), len(ia)
+        cot = np.ascontiguousarray(cotangents, dtype=np.complex128)
+        assert cot.shape == (nfreq, nprobe)
+        wave = np.zeros((nfreq, nprobe), dtype=np.complex128)
+        grad = np.zeros(self._ncomp, dtype=np.float64)
+        greact = np.zeros(len(kind), dtype=np.float64)
+        gsrc = np.zeros((nfreq, len(rows)), dtype=np.complex128)
+        lam = np.zeros((nfreq, self.n), dtype=np.complex128) if adjoints else None
+        resid = np.zeros((nfreq, 2), dtype=np.float64)
+        info = np.zeros(nfreq, dtype=np.int32)
+        work = np.zeros(3, dtype=np.int64)
+
+        def opt(arr, ctype):  # (an empty array goes as NULL)
+            return _ptr(arr, ctype) if arr is not None and arr.size else None
+
+        self._check(self.lib.nodal_ac_gradient(
+            self._h, int(dense), nfreq, opt(omega, C.c_double), len(kind), opt(kind, C.c_uint8), opt(value, C.c_double),
+            opt(lead_a, C.c_int32), opt(lead_b, C.c_int32), len(rows), opt(rows, C.c_int64), opt(src_re, C.c_double),
+            opt(src_im, C.c_double), nprobe, opt(ia, C.c_int32), opt(ib, C.c_int32), opt(cot, C.c_double),
+            opt(wave, C.c_double), opt(grad, C.c_double), opt(greact, C.c_double), opt(gsrc, C.c_double),
+            1 if adjoints else 0, opt(lam, C.c_double), opt(resid, C.c_double), opt(info, C.c_int32), _ptr(work, C.c_int64)))
+        return wave, grad, greact, gsrc, lam, resid, info, work
 
     def debug_sources_rhs(self, rows, values):
         """The right-hand sides solve_sources builds, [M, n] (testing hook)."""

@@ -3,6 +3,7 @@
     x = autograd.solve(circuit, values)                                   # [K+B]
     X = autograd.solve_sources(circuit, values, names, source_values)     # [M, K+B]
     W = autograd.transient(circuit, values, capacitors, dt, steps, ...)   # [steps+1, P]
+    W = autograd.ac(circuit, values, capacitors, inductors, frequencies, ...)  # [F, P] complex
 
 `values` is a float64 CPU tensor [ncomp] in the order of `netlist.component_keys` (what `Circuit.values` holds),
 `source_values` a float64 CPU tensor [M, len(names)] with the members' values of the swept A / E components
@@ -14,6 +15,9 @@ their table value is not used by any member -- and the swept values get theirs t
 `Circuit.transient_gradient` (the time stepping run backwards) and hands gradients to `values`, the capacitances and
 `source_values` [steps, len(names)]; at a swept row `values` gets what the DC start owes to the table value, zero when
 the run starts from `initial`.
+`ac` returns the probe phasors of `Circuit.ac`, complex128 [F, P]; its backward is one `Circuit.ac_gradient` call with the
+incoming cotangent (torch's dL/dRe + j dL/dIm for a complex tensor is the convention of that call) and hands gradients to
+`values`, the farads, the henries and the complex amplitudes.
 
 This module imports torch; `import nodal_amd` does not import it.
 """
@@ -126,6 +130,43 @@ class _Transient(torch.autograd.Function):
                 torch.from_numpy(np.ascontiguousarray(swept)) if ctx.names else None, None, None, None, None, None, None)
 
 
+class _AC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, circuit, values, farads, henries, amplitudes, cap_leads, ind_leads, frequencies, names, probes):
+        held, caps, inds = _values_of(values), _values_of(farads), _values_of(henries)
+        names = list(names)
+        if amplitudes.dtype != torch.complex128 or amplitudes.device.type != "cpu":
+            raise TypeError("the amplitudes must be a complex128 CPU tensor")
+        amps = np.array(amplitudes.detach().numpy(), dtype=np.complex128)
+        if amps.shape != (len(names),):
+            raise ValueError(f"the amplitudes must have shape ({len(names)},), not {tuple(amps.shape)}")
+        if caps.shape != (len(cap_leads),) or inds.shape != (len(ind_leads),):
+            raise ValueError("one value per capacitor and per inductor")
+        ctx.circuit, ctx.held, ctx.names = circuit, held, names
+        ctx.call = dict(frequencies=np.array(frequencies, dtype=np.float64),
+                        capacitors=[(name, float(f), a, b) for (name, a, b), f in zip(cap_leads, caps)],
+                        inductors=[(name, float(f), a, b) for (name, a, b), f in zip(ind_leads, inds)],
+                        sources={name: complex(v) for name, v in zip(names, amps)} if names else None,
+                        probes=list(probes))
+        circuit.set_values(held)
+        sweep = circuit.ac(**ctx.call)
+        return torch.from_numpy(np.array(sweep.phasors, dtype=np.complex128))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, cotangent):
+        circuit = ctx.circuit
+        _put_back(circuit, ctx.held)
+        if cotangent.dtype != torch.complex128 or cotangent.device.type != "cpu":
+            raise TypeError("nodal_amd.autograd.ac works on complex128 CPU phasors")
+        grad = circuit.ac_gradient(cotangents=np.array(cotangent.detach().numpy(), dtype=np.complex128), **ctx.call)
+        amps = np.array([grad.sources[name] for name in ctx.names], dtype=np.complex128).reshape(len(ctx.names))
+        return (None, torch.from_numpy(np.array(grad.values, dtype=np.float64)),
+                torch.from_numpy(np.array(grad.capacitors, dtype=np.float64)),
+                torch.from_numpy(np.array(grad.inductors, dtype=np.float64)), torch.from_numpy(amps),
+                None, None, None, None, None)
+
+
 def solve(circuit, values):
     """The solution [K+B] of `circuit` with the component values `values` [ncomp], differentiable in `values`."""
     return _Solve.apply(circuit, values)
@@ -151,3 +192,22 @@ def transient(circuit, values, capacitors, dt, steps, source_names=(), source_va
         source_values = torch.zeros((steps, 0), dtype=torch.float64)
     return _Transient.apply(circuit, values, farads, source_values, leads, dt, steps, tuple(source_names), tuple(probes),
                             initial)
+
+
+def ac(circuit, values, capacitors, inductors, frequencies, source_names=(), amplitudes=None, probes=()):
+    """The probe phasors complex128 [F, P] of `Circuit.ac` at `frequencies` (Hz) with the component values `values`
+    [ncomp], the capacitors and inductors -- (name, farads or henries, node_a, node_b) with each value a float64 CPU
+    scalar tensor, e.g. an element of one tensor -- and the complex amplitudes `amplitudes` complex128 [len(source_names)]
+    of the independent sources `source_names`, every other one off; differentiable in values, farads, henries and
+    amplitudes.  The table value of an A / E row is never read: its gradient is exactly zero."""
+    def split(elements):
+        elements = list(elements)
+        held = torch.stack([torch.as_tensor(e[1], dtype=torch.float64) for e in elements]) if elements else \
+            torch.zeros(0, dtype=torch.float64)
+        return held, [(e[0], e[2], e[3]) for e in elements]
+    farads, cap_leads = split(capacitors)
+    henries, ind_leads = split(inductors)
+    if amplitudes is None:
+        amplitudes = torch.zeros(0, dtype=torch.complex128)
+    return _AC.apply(circuit, values, farads, henries, amplitudes, cap_leads, ind_leads, tuple(frequencies), tuple(source_names),
+                     tuple(probes))

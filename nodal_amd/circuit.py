@@ -727,6 +727,52 @@ class Circuit:
                           contributions=contrib, names=list(self.netlist.component_keys) if contributions else None,
                           timings=timings)
 
+    def ac_gradient(self, frequencies, cotangents, capacitors=(), inductors=(), sources=None, probes=(), adjoints=False):
+        """The derivative of a real scalar loss L of ac()'s probe phasors with respect to every component value, every
+        capacitance and inductance and every driven amplitude, on the device (nodal_ac_gradient): one forward and one
+        adjoint solve per frequency, (G + j B(w))^T y = sum_p conj(g_p) (e(a_p) - e(b_p)), instead of two sweeps per
+        parameter by central differences.
+
+        `frequencies`, `capacitors`, `inductors`, `sources` and `probes` are those of ac(), with its errors.
+        `cotangents` is complex [F, P]: g[f][p] = dL/dRe W[f][p] + j dL/dIm W[f][p] of the phasors W = ac(...).phasors --
+        what torch's backward hands over for a complex tensor; for L = sum w |W - t|^2 it is 2 w (W - t).  TypeError
+        for cotangents that are not complex, ValueError for another shape and for entries that are not finite.
+        Returns an ACGradient (ac_gradient.py): `values` [ncomp] in the order of `netlist.component_keys` (exactly 0.0
+        at A / E rows: the small-signal excitation never reads their table value), `capacitors`, `inductors` (and
+        `capacitors_by_name`, `inductors_by_name`) with respect to the farads and henries as passed, `sources` name ->
+        complex in the cotangents' convention, summed over the frequencies and the rows that carry the name,
+        `source_terms` [F, R], `phasors` [F, P], `info`, `scaled_residual` [F, 2] (forward, adjoint), `adjoints`
+        [F, K+B] with adjoints=True, `work`, `timings`.
+
+        A circuit whose matrix is symmetric (passive, no branch rows) spends ONE numeric factorisation per frequency on
+        both solves; any other spends two, the second on the transposed system noise() keeps.  Patterns and symbolic
+        analyses are shared with ac(), noise() and ac_ports() in either order (`timings[0] == 0.0`).  The sums over the
+        frequencies are formed on the device in ascending order without floating-point atomics: a repeated call gives
+        the same bits.  Singular networks behave as in noise(): the dense path raises LinAlgError /
+        UnconnectedCircuitError, the sparse path returns NaN rows with info > 0 for the singular frequencies, NaN in
+        every summed gradient, and warns once.  The circuit itself -- its solution if any, table, G, A, a recorded
+        transient, what ac(), noise() and ac_ports() keep -- is left as it was; solve() is neither needed nor
+        touched."""
+        from .ac import check_ac_arguments, resolve_amplitudes, resolve_reactive
+        from .ac_gradient import ACGradient, check_ac_gradient_arguments, sources_by_name
+        from .ports import _as_pair, resolve_ports
+        omega = check_ac_arguments(frequencies)
+        names, kind, value, ea, eb = resolve_reactive(self.netlist, capacitors, inductors)
+        rows, amplitudes = resolve_amplitudes(self.netlist, sources)
+        probes = [_as_pair(self.netlist, port) for port in probes]
+        pa, pb = resolve_ports(self.netlist, probes)
+        cot = check_ac_gradient_arguments(cotangents, len(omega), len(probes))
+        h = self._handle
+        with self._reference_errors():
+            wave, grad, greact, gsrc, lam, resid, info, work = h.ac_gradient(
+                omega, kind, value, ea, eb, rows, amplitudes, pa, pb, cot, dense=not self.sparse, adjoints=adjoints)
+        timings = h.timings()
+        _warn_singular((info > 0).any())
+        ncap = int((kind == 0).sum())
+        return ACGradient(grad, greact[:ncap], greact[ncap:], sources_by_name(list(self.netlist.component_keys), rows, gsrc),
+                          gsrc, wave, info, resid, capacitor_names=names[:ncap], inductor_names=names[ncap:],
+                          source_rows=rows, adjoints=lam, work=work, timings=timings)
+
     def scaled_residual(self):
         """||G x - A||_inf / (||G||_inf ||x||_inf + ||A||_inf) of the last
         solution, computed on the device."""

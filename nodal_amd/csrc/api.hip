@@ -273,7 +273,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->tg_con,
                       &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
                       &h->ac_t_gsrc, &h->ac_t_ptr, &h->ac_t_con, &h->nz_spec, &h->nz_vec, &h->nz_part, &h->nz_out,
-                      &h->ap_spec, &h->ap_vec, &h->ap_rows, &h->ap_out,
+                      &h->ap_spec, &h->ap_vec, &h->ap_rows, &h->ap_out, &h->ag_spec, &h->ag_vec, &h->ag_out,
                       &h->dbg_resid, &h->dbg_apply};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
@@ -1031,6 +1031,36 @@ int nodal_ac_ports(nodal_handle h, int32_t dense, int32_t nfreq, const double *o
     const int s = ac_ports_run(h, dense != 0, nfreq, omega, nreact, kind, value, lead_a, lead_b, nports, ia, ib, z_out,
                                node_peak_out, node_peak_port_out, node_peak_freq_out, resid_out, info_out, work_out,
                                &ms_analysis, &ms_factor);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = ms_analysis;
+    h->ms[1] = ms_factor;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
+int nodal_ac_gradient(nodal_handle h, int32_t dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+                      const double *value, const int32_t *lead_a, const int32_t *lead_b, int32_t nsrc, const int64_t *src_rows,
+                      const double *src_re, const double *src_im, int32_t nprobe, const int32_t *probe_a,
+                      const int32_t *probe_b, const double *wave_cot, double *wave_out, double *grad_out,
+                      double *grad_react_out, double *grad_sources_out, int32_t keep_every, double *adjoint_out,
+                      double *resid_out, int32_t *info_out, int64_t *work_out) {
+    if (!h || nreact < 0 || (nreact > 0 && (!kind || !value || !lead_a || !lead_b)) || nsrc < 0 ||
+        (nsrc > 0 && (!src_rows || !src_re || !src_im)) || nprobe < 0 || (nprobe > 0 && (!probe_a || !probe_b)) || keep_every < 0)
+        return NODAL_E_INVALID;
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "ac gradient: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "ac gradient: assemble_numeric not called");
+    if (nfreq < 0 || (nfreq > 0 && !omega)) return nodal_fail(h, NODAL_E_INVALID, "ac gradient: a negative number of frequencies");
+    if (nfreq > 0 && nprobe > 0 && !wave_cot) return nodal_fail(h, NODAL_E_INVALID, "ac gradient: no cotangents");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_analysis = 0.0, ms_factor = 0.0;
+    const int s = ac_gradient_run(h, dense != 0, nfreq, omega, nreact, kind, value, lead_a, lead_b, nsrc, src_rows, src_re,
+                                  src_im, nprobe, probe_a, probe_b, wave_cot, wave_out, grad_out, grad_react_out,
+                                  grad_sources_out, keep_every, adjoint_out, resid_out, info_out, work_out, &ms_analysis,
+                                  &ms_factor);
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_analysis;

@@ -256,6 +256,10 @@ struct nodal_ctx {
     // judge's norms; the [16][2n] rows of a block with a column redone alone (reserved when the first one is); Z,
     // residuals and peaks until they go down
     DevBuf ap_spec, ap_vec, ap_rows, ap_out;
+    // AC gradient (ac_gradient.hip), on h->ac and, when G is not symmetric, h->ac_t: the call's elements, probes and
+    // cotangents; the forward right-hand side, x_f and y_f (2n each); phasors, source terms, residuals and the two
+    // gradient sums until they go down
+    DevBuf ag_spec, ag_vec, ag_out;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
@@ -663,6 +667,15 @@ int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, i
                  const int32_t *ib, double *z_out, double *node_peak_out, int32_t *node_peak_port_out,
                  int32_t *node_peak_freq_out, double *resid_out, int32_t *info_out, int64_t *work_out, double *ms_analysis,
                  double *ms_factor);
+
+// ---- AC gradient (ac_gradient.hip): the adjoint of the AC analysis, dL/d(every value) of a loss of the probe phasors ----
+// the arguments are those of nodal_ac_gradient; ms_analysis, ms_factor as ac_run's
+int ac_gradient_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
+                    const double *value, const int32_t *lead_a, const int32_t *lead_b, int32_t nsrc, const int64_t *src_rows,
+                    const double *src_re, const double *src_im, int32_t nprobe, const int32_t *probe_a,
+                    const int32_t *probe_b, const double *wave_cot, double *wave_out, double *grad_out,
+                    double *grad_react_out, double *grad_sources_out, int32_t keep_every, double *adjoint_out,
+                    double *resid_out, int32_t *info_out, int64_t *work_out, double *ms_analysis, double *ms_factor);
 
 // ---- multiport Thevenin / Norton equivalents (ports.hip; the solves: multi_rhs_solve in sparse.hip) ----
 // one call of nodal_port_matrix: the ports' nodes (device, [nports] each, -1 ground) and Z (device, [nports][nports])

@@ -81,3 +81,40 @@ __device__ __forceinline__ double cross_term(int32_t j, int32_t K, double v, con
     const double lm = lam[((int64_t)K + k[j]) * rs + lat];
     return lm * value[j] * u / (v * v);
 }
+
+// ---- the complex evaluation of the same formulas (ac_gradient.hip) ----
+// x and lam are phasors interleaved by unknown: the real part of unknown i at [2i], the imaginary part at [2i + 1].
+struct Phasor {
+    double re, im;
+};
+// v(j1) - v(j2), +0.0 for a ground (or absent) lead
+__device__ __forceinline__ Phasor phasor_diff(const double *__restrict__ v, int32_t j1, int32_t j2) {
+    return {lead(v, j1, 2, 0) - lead(v, j2, 2, 0), lead(v, j1, 2, 1) - lead(v, j2, 2, 1)};
+}
+// Re(d u) and Im(d u): every product and the sum a statement of its own (-ffp-contract=on would fuse one of the products
+// into the sum, and the two parts of a term would round differently)
+__device__ __forceinline__ double re_product(Phasor d, Phasor u) {
+    const double p = d.re * u.re;
+    const double q = d.im * u.im;
+    return p - q;
+}
+__device__ __forceinline__ double im_product(Phasor d, Phasor u) {
+    const double p = d.re * u.im;
+    const double q = d.im * u.re;
+    return p + q;
+}
+// the term of row_term's row at one frequency: Re(D U) / den; exactly +0.0 for an A or E row -- the small-signal
+// excitation never reads the table value -- and for a row without a term
+__device__ __forceinline__ double row_term_complex(const RowTerm &r, const double *__restrict__ x, const double *__restrict__ lam) {
+    if (r.none || !r.reads_x) return 0.0;
+    const double re = re_product(phasor_diff(lam, r.j1, r.j2), phasor_diff(x, r.p1, r.p2));
+    return re / r.den;
+}
+// cross_term with complex L(m_j) and X: Re(L(m_j) (X(c_j) - X(d_j))) v_j / v^2
+__device__ __forceinline__ double cross_term_complex(int32_t j, int32_t K, double v, const double *__restrict__ value,
+                                                     const int32_t *__restrict__ c, const int32_t *__restrict__ d,
+                                                     const int32_t *__restrict__ k, const double *__restrict__ lam,
+                                                     const double *__restrict__ x) {
+    const double re = re_product(phasor_diff(lam, K + k[j], -1), phasor_diff(x, c[j], d[j]));
+    return re * value[j] / (v * v);
+}
