@@ -690,13 +690,17 @@ int nodal_debug_direct_apply(nodal_handle h, int32_t transposed, int32_t cols, c
  *   padding, rows n .. ld) hold whatever the buffer held.  A buffer the level does not have (no next level, no W, no
  *   adcol) gives 0.  The one level that visits in three launches (directly above the dense tail) also has P2 = W -
  *   w D^-1 (A W): p2col / p2val (f32) 64*ld items laid out like W, p2len n, and d2 = P2^T dense, nc x ld row-major f32
- *   (zeros outside P2's pattern); 0 on every other level.  level == -1: coarse_inv, n_last x n_last row-major (`which` is ignored).  dst == NULL: the size
+ *   (zeros outside P2's pattern); 0 on every other level.  A level whose visit forms rc = W^T b also has W^T by coarse
+ *   row: wtstart nc + 1 row starts (u32), and wtcol (fine row, ascending within a row) / wtval (f32, the bits of W's
+ *   entry) / wtsrc (that entry's position slot * ld + row in wval), each 16*n items of which the first wtstart[nc] are
+ *   written; 0 on every other level.  level == -1: coarse_inv, n_last x n_last row-major (`which` is ignored).  dst == NULL: the size
  *   only; otherwise capacity_bytes must cover it. */
 enum {
     NODAL_HA_ACOL = 0, NODAL_HA_AVAL = 1, NODAL_HA_AVALF = 2, NODAL_HA_ALEN = 3, NODAL_HA_DINV = 4, NODAL_HA_ADCOL = 5,
     NODAL_HA_AGG = 6, NODAL_HA_PCOL = 7, NODAL_HA_PVAL = 8, NODAL_HA_PVALF = 9, NODAL_HA_RCOL = 10, NODAL_HA_RVAL = 11,
     NODAL_HA_RVALF = 12, NODAL_HA_RLEN = 13, NODAL_HA_WCOL = 14, NODAL_HA_WVAL = 15, NODAL_HA_WLEN = 16,
-    NODAL_HA_P2COL = 17, NODAL_HA_P2VAL = 18, NODAL_HA_P2LEN = 19, NODAL_HA_D2 = 20
+    NODAL_HA_P2COL = 17, NODAL_HA_P2VAL = 18, NODAL_HA_P2LEN = 19, NODAL_HA_D2 = 20,
+    NODAL_HA_WTSTART = 21, NODAL_HA_WTCOL = 22, NODAL_HA_WTVAL = 23, NODAL_HA_WTSRC = 24
 };
 int nodal_debug_hierarchy_info(nodal_handle h, int32_t *nlev, int64_t *ints /* [12][16] */, double *reals /* [12][2] */);
 int nodal_debug_hierarchy_array(nodal_handle h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes,

@@ -100,7 +100,8 @@ HIERARCHY_ARRAYS = (("acol", np.int32), ("aval", np.float64), ("avalf", np.float
                     ("pval", np.float64), ("pvalf", np.float32), ("rcol", np.int32), ("rval", np.float64),
                     ("rvalf", np.float32), ("rlen", np.int32), ("wcol", np.int32), ("wval", np.float32),
                     ("wlen", np.int32), ("p2col", np.int32), ("p2val", np.float32), ("p2len", np.int32),
-                    ("d2", np.float32))
+                    ("d2", np.float32), ("wtstart", np.uint32), ("wtcol", np.int32), ("wtval", np.float32),
+                    ("wtsrc", np.int32))
 HIERARCHY_INFO = ("n", "ld", "nc", "width", "maxlen", "wfix", "nnz", "rld", "rcap", "wslots", "fold_want", "fold", "d16",
                   "in_tail", "refreshed", "dense_coarsest")
 

@@ -141,6 +141,8 @@ inline constexpr OffUnlessNon0 SA_FOLD_CHECK{"NODAL_SA_FOLD_CHECK"};  // process
 inline constexpr OnUnless0 SA_FOLD_VISIT{"NODAL_SA_FOLD_VISIT"};  // process: 0 the level directly above the dense tail keeps its six launches per visit instead of three
 inline constexpr Int64 SA_VISIT_CAP{"NODAL_SA_VISIT_CAP", 16777216};  // process: bytes of the dense P2^T above which that level keeps its six launches
 inline constexpr OffUnlessNon0 SA_VISIT_CHECK{"NODAL_SA_VISIT_CHECK"};  // process: 1 with NODAL_TRACE: the setup prints the scaled difference of the three-launch visit and the six launches it replaces
+inline constexpr OnUnless0 SA_RESTRICT_B{"NODAL_SA_RESTRICT_B"};  // process: 0 a level with one sweep per side keeps its residual and restriction launches instead of forming rc = W^T b beside the residual in one
+inline constexpr OffUnlessNon0 SA_RESTRICT_CHECK{"NODAL_SA_RESTRICT_CHECK"};  // process: 1 with NODAL_TRACE: the setup prints the scaled difference of rc formed from b and by the two launches it replaces
 inline constexpr OnUnless0 SA_TAIL_DENSE{"NODAL_SA_TAIL_DENSE"};  // process: 0 the tail walked by k_tail on every visit instead of applied as a dense operator
 inline constexpr OffUnlessNon0 SA_TAIL_CHECK{"NODAL_SA_TAIL_CHECK"};  // process: 1 with NODAL_TRACE: the setup prints the scaled difference of both forms of the tail
 inline constexpr Int SA_TAIL_NU{"NODAL_SA_TAIL_NU", 3};  // create: sweeps inside the LDS tail (at least 1)

@@ -115,7 +115,9 @@ enum { ST_MAXLEN = 0, ST_GRADED = 1, ST_BADDIAG = 2, ST_OVERFLOW = 3, ST_NNZ = 4
        ST_FARCOL = 8 /* level 0: some column lies further than 32767 from its row */,
        ST_FOLDMISS = 9 /* a column of P's row is missing from the row of A P (a row without a stored diagonal): no W */,
        ST_VISITMISS = 10 /* a row of P2 = G W has more than P2CAP columns: the level keeps its six launches */,
-       ST_COUNT = 11 };
+       ST_RESTRICTMISS = 11 /* W^T: a coarse row beyond the per-row sort (1) or more entries than its arrays hold (2): the
+                               level keeps its residual and restriction launches */,
+       ST_COUNT = 12 };
 
 struct SLevel {
     int64_t n = 0, ld = 0, nc = 0;
@@ -142,6 +144,14 @@ struct SLevel {
     // n_t x ld row-major f32.  visit_want: the setup wrote them; visit: the cycle uses them (decide_folds).
     DevBuf p2col, p2val, p2len, d2;
     bool visit_want = false, visit = false;
+    // The restricted residual from the right-hand side, rc = W^T b, beside the residual in one launch
+    // (k_residual_restrict, sagg_cycle.h): W^T by coarse row -- entries wtstart[I] .. wtstart[I + 1] of wtcol (fine row,
+    // ascending) / wtval (the bits of W's entry) / wtsrc (its position slot * ld + row in wval, for the values-only
+    // refresh), at most wtcap of them (build_wt).  restrict_want: the setup enqueued the build; restrict_b: the cycle
+    // uses it (decide_folds).
+    DevBuf wtstart, wtcol, wtval, wtsrc;
+    int64_t wtcap = 0;
+    bool restrict_want = false, restrict_b = false;
     Ell A() const {
         Ell e;
         e.n = n; e.ld = ld; e.width = width;
@@ -219,6 +229,13 @@ struct SHierarchy {
     // aggregates only): flags_levels = how many levels' flags_up have been enqueued there in this setup
     bool want_flags = false;
     int flags_levels = 0;
+    // W^T of a level (build_wt) goes there as well, behind ev_w (recorded on the main stream after the A P launch that
+    // writes W), with scratch of its own: the next level's R build re-reserves rstart / keys on the main stream while
+    // that chain may still run.  ev_wt: behind the last such chain; wt_pending: the main stream has not waited for it yet.
+    hipEvent_t ev_w = nullptr, ev_wt = nullptr;
+    bool wt_pending = false;
+    bool general = false;  // the setup's route: no symmetry to use (sagg_setup_csr)
+    DevBuf wt_scratch, wt_keys;
     DevBuf stats, coarse_inv, mis_t, mis_m, mis_flag, mis_id, agg1, keys, rstart, cursor, lists;
     TailDesc td;
     uint64_t *host_stats = nullptr;  // pinned
@@ -264,11 +281,14 @@ struct SHierarchy {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_flags) (void)hipEventDestroy(ev_flags);
+        if (ev_w) (void)hipEventDestroy(ev_w);
+        if (ev_wt) (void)hipEventDestroy(ev_wt);
         if (aux) (void)hipStreamDestroy(aux);
         for (SLevel *l : pool) {
             DevBuf *b[] = {&l->acol, &l->aval, &l->alen, &l->dinv, &l->agg, &l->pcol, &l->pval, &l->rcol,
                            &l->rval, &l->rlen, &l->vec, &l->part, &l->gflag, &l->avalf, &l->pvalf, &l->rvalf, &l->adcol,
-                           &l->wcol, &l->wval, &l->wlen, &l->p2col, &l->p2val, &l->p2len, &l->d2};
+                           &l->wcol, &l->wval, &l->wlen, &l->p2col, &l->p2val, &l->p2len, &l->d2,
+                           &l->wtstart, &l->wtcol, &l->wtval, &l->wtsrc};
             for (DevBuf *x : b) x->release();
             delete l;
         }
@@ -280,7 +300,8 @@ struct SHierarchy {
         apcol.release();
         apval.release();
         aplen.release();
-        DevBuf *b[] = {&stats, &coarse_inv, &mis_t, &mis_m, &mis_flag, &mis_id, &agg1, &keys, &rstart, &cursor, &lists};
+        DevBuf *b[] = {&stats, &coarse_inv, &mis_t, &mis_m, &mis_flag, &mis_id, &agg1, &keys, &rstart, &cursor, &lists,
+                       &wt_scratch, &wt_keys};
         for (DevBuf *x : b) x->release();
         if (host_stats) (void)hipHostFree(host_stats);
     }
@@ -646,24 +667,48 @@ __global__ __launch_bounds__(TB) void build_P(Ell A, const double *__restrict__ 
 // ---- R = P^T by coarse row: count, scan, fill, sort each row's (node << 2 | slot) keys ----
 // (the counting atomic's return value is the entry's place inside its row -- any order will do, the rows
 // are sorted afterwards --: kept per (slot, fine row), so that the fill needs no atomics of its own)
+// LEN: the operator has a per-row length (W: `len[i]` slots of up to 64, keys node << 6 | slot) instead of PW slots with
+// column -1 in the empty ones (P); the same steps transpose either (W^T: build_wt below).
+template <bool LEN>
+struct TKey { static constexpr int SHIFT = LEN ? 6 : 2; };
+template <bool LEN = false>
 __global__ __launch_bounds__(TB) void r_count(int64_t n, int64_t ld, const int32_t *__restrict__ pcol,
-                                              uint32_t *__restrict__ cnt, uint32_t *__restrict__ place) {
+                                              uint32_t *__restrict__ cnt, uint32_t *__restrict__ place,
+                                              const int32_t *__restrict__ len = nullptr) {
     for (int64_t i = (int64_t)xcd_block() * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+        if constexpr (LEN) {
+            const int32_t m = len[i];
+            for (int32_t k = 0; k < m; ++k)
+                place[(int64_t)k * ld + i] = atomicAdd(&cnt[pcol[(int64_t)k * ld + i]], 1u);
+        } else {
 #pragma unroll
-        for (int k = 0; k < PW; ++k) {
-            const int32_t J = pcol[(int64_t)k * ld + i];
-            if (J >= 0) place[(int64_t)k * ld + i] = atomicAdd(&cnt[J], 1u);
+            for (int k = 0; k < PW; ++k) {
+                const int32_t J = pcol[(int64_t)k * ld + i];
+                if (J >= 0) place[(int64_t)k * ld + i] = atomicAdd(&cnt[J], 1u);
+            }
         }
     }
 }
+template <bool LEN = false>
 __global__ __launch_bounds__(TB) void r_fill(int64_t n, int64_t ld, const int32_t *__restrict__ pcol,
                                              const uint32_t *__restrict__ rstart, const uint32_t *__restrict__ place,
-                                             uint64_t *__restrict__ keys) {
+                                             uint64_t *__restrict__ keys, const int32_t *__restrict__ len = nullptr,
+                                             uint32_t keycap = 0, int64_t nc = 0) {
+    if constexpr (LEN) {
+        if (rstart[nc] > keycap) return;  // (more entries than the key buffer holds: wt_pack records it, nothing is built)
+    }
     for (int64_t i = (int64_t)xcd_block() * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+        if constexpr (LEN) {
+            const int32_t m = len[i];
+            for (int32_t k = 0; k < m; ++k)
+                keys[rstart[pcol[(int64_t)k * ld + i]] + place[(int64_t)k * ld + i]] =
+                    ((uint64_t)i << TKey<true>::SHIFT) | (uint64_t)k;
+        } else {
 #pragma unroll
-        for (int k = 0; k < PW; ++k) {
-            const int32_t J = pcol[(int64_t)k * ld + i];
-            if (J >= 0) keys[rstart[J] + place[(int64_t)k * ld + i]] = ((uint64_t)i << 2) | (uint64_t)k;
+            for (int k = 0; k < PW; ++k) {
+                const int32_t J = pcol[(int64_t)k * ld + i];
+                if (J >= 0) keys[rstart[J] + place[(int64_t)k * ld + i]] = ((uint64_t)i << 2) | (uint64_t)k;
+            }
         }
     }
 }
@@ -750,8 +795,10 @@ __global__ __launch_bounds__(TB) void r_refresh(int64_t nc, int64_t rld, const i
 // per-row sort of the (node << 2 | slot) keys.  Up to 32 keys: one lane per row with a sorting
 // network in registers (grp::sort_rows_short stops at 16, the rows of R average 17, and its
 // workgroup-per-row LDS sort for the rest cost 80 us per 1e5 rows).
+// (keycap: W^T only -- more keys than the buffer holds were never written, see r_fill)
 __global__ __launch_bounds__(TB) void r_sort_short(const uint32_t *__restrict__ rstart, uint64_t *__restrict__ keys,
-                                                   int64_t nc) {
+                                                   int64_t nc, uint32_t keycap = 0xffffffffu) {
+    if (rstart[nc] > keycap) return;
     for (int64_t I = (int64_t)xcd_block() * TB + threadIdx.x; I < nc; I += (int64_t)gridDim.x * TB) {
         const uint32_t s0 = rstart[I];
         const int len = (int)(rstart[I + 1] - s0);
@@ -766,9 +813,10 @@ __global__ __launch_bounds__(TB) void r_sort_short(const uint32_t *__restrict__ 
 // beyond every cap: left as they are, the setup declines.  (No work lists: ten thousand rows appending
 // themselves to one list through one counter cost 100 us.)
 __global__ __launch_bounds__(64) void r_sort_medium(const uint32_t *__restrict__ rstart, uint64_t *__restrict__ keys,
-                                                    int64_t nc) {
+                                                    int64_t nc, uint32_t keycap = 0xffffffffu) {
     __shared__ uint64_t buf[RCAP_SMALL];
     const int lane = threadIdx.x;
+    if (rstart[nc] > keycap) return;
     for (int64_t I = blockIdx.x; I < nc; I += gridDim.x) {
         const uint32_t s0 = rstart[I];
         const int len = (int)(rstart[I + 1] - s0);
@@ -791,6 +839,42 @@ __global__ __launch_bounds__(64) void r_sort_medium(const uint32_t *__restrict__
         for (int e = lane; e < len; e += 64) keys[s0 + e] = buf[e];
         __syncthreads();
     }
+}
+
+// ---- W^T by coarse row (SLevel::wtstart; k_residual_restrict, sagg_cycle.h) ----
+// The sorted keys of coarse row I, entries wtstart[I] .. wtstart[I + 1], become (fine row, value, source position): the
+// value is a copy of W's, read through src = slot * ld + fine row, which the values-only refresh reads again
+// (wt_refresh).  One wavefront per coarse row: contiguous stores.  A row beyond the per-row sort (RCAP_SMALL) or more
+// entries than the arrays hold: ST_RESTRICTMISS, the level keeps k_smooth_residual + k_restrict.
+__global__ __launch_bounds__(TB) void wt_pack(int64_t nc, const uint32_t *__restrict__ wtstart,
+                                              const uint64_t *__restrict__ keys, int64_t ld,
+                                              const float *__restrict__ wval, uint32_t cap, int32_t *__restrict__ wtcol,
+                                              float *__restrict__ wtval, int32_t *__restrict__ wtsrc,
+                                              unsigned long long *__restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const bool over = wtstart[nc] > cap;
+    if (over && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&stats[ST_RESTRICTMISS], 2ull);
+    if (over) return;
+    for (int64_t I = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6); I < nc; I += (int64_t)gridDim.x * (TB / 64)) {
+        const uint32_t s0 = wtstart[I], l = wtstart[I + 1] - s0;
+        if (l > (uint32_t)RCAP_SMALL && lane == 0) atomicOr(&stats[ST_RESTRICTMISS], 1ull);  // (rare; its keys are unsorted)
+        for (uint32_t t = lane; t < l; t += 64) {
+            const uint64_t key = keys[s0 + t];
+            const int64_t i = (int64_t)(key >> TKey<true>::SHIFT);
+            const int64_t src = (int64_t)(key & ((1u << TKey<true>::SHIFT) - 1)) * ld + i;
+            wtcol[s0 + t] = (int32_t)i;
+            wtval[s0 + t] = wval[src];
+            wtsrc[s0 + t] = (int32_t)src;
+        }
+    }
+}
+// the values again behind a values-only refresh of W (same pattern, same positions): one streaming pass
+__global__ __launch_bounds__(TB) void wt_refresh(int64_t nc, const uint32_t *__restrict__ wtstart,
+                                                 const int32_t *__restrict__ wtsrc, const float *__restrict__ wval,
+                                                 float *__restrict__ wtval) {
+    const int64_t total = wtstart[nc];
+    for (int64_t e = (int64_t)blockIdx.x * TB + threadIdx.x; e < total; e += (int64_t)gridDim.x * TB)
+        wtval[e] = wval[wtsrc[e]];
 }
 
 // ---------------------------------------------------------------------------------
@@ -1452,7 +1536,67 @@ void decide_folds(SHierarchy *H, const unsigned long long *hs, bool trace) {
         if (trace && L->visit_want)
             fprintf(stderr, "[sagg] level %d (%lld rows): visit %s\n", k, (long long)L->n,
                     L->visit ? "in three launches" : "NOT in three launches: W missing, or a row of P2 beyond its slots");
+        // rc = W^T b beside the residual: W in use, W^T complete, and not the level that visits in three launches
+        // (the pattern's verdict: a values-only refresh does not build W^T again, the symbolic setup's word stands)
+        const unsigned long long over = hs[(size_t)k * ST_COUNT + ST_RESTRICTMISS] |
+                                        (H->sym_valid ? H->sym_stats[(size_t)k * ST_COUNT + ST_RESTRICTMISS] : 0ull);
+        L->restrict_b = L->restrict_want && L->fold && !L->visit && !over;
+        if (trace && L->restrict_want && runs_cycle)
+            fprintf(stderr, "[sagg] level %d (%lld rows): restriction %s\n", k, (long long)L->n,
+                    L->restrict_b ? "from b beside the residual launch"
+                                  : over ? "NOT from b: a row of W^T beyond the per-row sort, or more entries than its arrays hold"
+                                         : "NOT from b: W missing, or the level visits in three launches");
     }
+}
+
+// ---- W^T of a level whose visit restricts from its right-hand side (SLevel::wtstart) ----
+// Wanted where the setup can tell: NODAL_SA_RESTRICT_B not 0, level >= 1, the symmetric route (rc = W^T b needs A = A^T
+// and R = P^T), W written, one sweep per side as NODAL_SA_NU stands now (cycle() looks again per call), and source
+// positions that fit 32 bits.  The arrays hold WT_AVG entries per fine row (grids: 9-13); more is a cap miss.
+void apply_nu_knob(SHierarchy *H);
+constexpr int WT_AVG = 16;
+bool restrict_wanted(SHierarchy *H, int l, const SLevel *L) {
+    static const bool on = knob::SA_RESTRICT_B.now();
+    if (!on || l < 1 || H->general || !L->fold_want || (int64_t)L->wslots * L->ld >= (1ll << 31)) return false;
+    apply_nu_knob(H);
+    return H->nu[l < 2 ? l : 2] == 1;
+}
+// (before the fork, like every buffer a forked section writes: build_level)
+int reserve_wt(nodal_ctx *h, SHierarchy *H, SLevel *L, int64_t nc) {
+    const int64_t cap = (int64_t)(L->wslots < WT_AVG ? L->wslots : WT_AVG) * L->n;
+    L->wtcap = cap;
+    NODAL_HIP_TRY(h, L->wtstart.reserve(align256((size_t)(nc + 1) * 4) + 256));
+    NODAL_HIP_TRY(h, L->wtcol.reserve((size_t)cap * 4 + 64));
+    NODAL_HIP_TRY(h, L->wtval.reserve((size_t)cap * 4 + 64));
+    NODAL_HIP_TRY(h, L->wtsrc.reserve((size_t)cap * 4 + 64));
+    NODAL_HIP_TRY(h, H->wt_keys.reserve((size_t)cap * 8 + 64));
+    NODAL_HIP_TRY(h, H->wt_scratch.reserve(align256(scan_tmp_bytes(nc + 1)) + (size_t)L->wslots * L->ld * 4 + 64));
+    return NODAL_OK;
+}
+// count with placing atomics, scan, fill keys, per-row sort, pack: the steps of R = P^T on W's slots.  Every launch,
+// the scan's included, goes where h->stream points.
+int build_wt(nodal_ctx *h, SHierarchy *H, int l) {
+    hipStream_t st = h->stream;
+    SLevel *L = H->pool[l];
+    const int64_t n = L->n, ld = L->ld, nc = L->nc;
+    const uint32_t cap = (uint32_t)L->wtcap;
+    uint32_t *wtstart = L->wtstart.as<uint32_t>();
+    char *sc = H->wt_scratch.as<char>();
+    uint32_t *place = reinterpret_cast<uint32_t *>(sc + align256(scan_tmp_bytes(nc + 1)));
+    uint64_t *keys = H->wt_keys.as<uint64_t>();
+    const int32_t *wcol = L->wcol.as<int32_t>(), *wlen = L->wlen.as<int32_t>();
+    NODAL_HIP_TRY(h, hipMemsetAsync(wtstart, 0, align256((size_t)(nc + 1) * 4) + 256, st));
+    r_count<true><<<grid_for(n), TB, 0, st>>>(n, ld, wcol, wtstart, place, wlen);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    NODAL_TRY(scan_exclusive_u32(h, wtstart, wtstart, nc + 1, nullptr, sc));
+    r_fill<true><<<grid_for(n), TB, 0, st>>>(n, ld, wcol, wtstart, place, keys, wlen, cap, nc);
+    r_sort_short<<<grid_for(nc), TB, 0, st>>>(wtstart, keys, nc, cap);
+    r_sort_medium<<<(unsigned)(nc < 8192 ? nc : 8192), 64, 0, st>>>(wtstart, keys, nc, cap);
+    wt_pack<<<grid_for(nc * 64), TB, 0, st>>>(nc, wtstart, keys, ld, L->wval.as<float>(), cap, L->wtcol.as<int32_t>(),
+                                             L->wtval.as<float>(), L->wtsrc.as<int32_t>(),
+                                             H->stats.as<unsigned long long>() + (size_t)l * ST_COUNT);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
 }
 
 int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool *declined, bool *stop) {
@@ -1558,7 +1702,9 @@ int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool
         if (hipStreamCreateWithFlags(&H->aux, hipStreamNonBlocking) != hipSuccess) H->aux = nullptr;
         if (H->aux && ((!H->ev_fork && hipEventCreateWithFlags(&H->ev_fork, hipEventDisableTiming) != hipSuccess) ||
                        (!H->ev_join && hipEventCreateWithFlags(&H->ev_join, hipEventDisableTiming) != hipSuccess) ||
-                       (!H->ev_flags && hipEventCreateWithFlags(&H->ev_flags, hipEventDisableTiming) != hipSuccess))) {
+                       (!H->ev_flags && hipEventCreateWithFlags(&H->ev_flags, hipEventDisableTiming) != hipSuccess) ||
+                       (!H->ev_w && hipEventCreateWithFlags(&H->ev_w, hipEventDisableTiming) != hipSuccess) ||
+                       (!H->ev_wt && hipEventCreateWithFlags(&H->ev_wt, hipEventDisableTiming) != hipSuccess))) {
             (void)hipStreamDestroy(H->aux);
             H->aux = nullptr;
         }
@@ -1605,6 +1751,9 @@ int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool
             NODAL_HIP_TRY(h, L->wval.reserve((size_t)apw * ld * 4 + 64));
             NODAL_HIP_TRY(h, L->wlen.reserve((size_t)ld * 4 + 64));
         }
+        L->restrict_b = false;
+        L->restrict_want = restrict_wanted(H, l, L);
+        if (L->restrict_want) NODAL_TRY(reserve_wt(h, H, L, nc));
     }
     hipStream_t main_st = h->stream;
     struct StreamGuard {  // (whatever way this function is left, the context gets its stream back)
@@ -1617,6 +1766,7 @@ int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool
         NODAL_HIP_TRY(h, hipStreamWaitEvent(H->aux, H->ev_fork, 0));
         H->aux_pending = true;
         NODAL_TRY(galerkin_product<false>(h, H, l, nullptr, 1));  // A P first: the long launch of the pair
+        if (L->restrict_want) NODAL_HIP_TRY(h, hipEventRecord(H->ev_w, main_st));  // (W is written)
         h->stream = H->aux;
         st = H->aux;
     }
@@ -1656,8 +1806,22 @@ int build_level(nodal_ctx *h, SHierarchy *H, int l, unsigned long long *hs, bool
         st = main_st;
     }
     NODAL_TRY(galerkin_product<false>(h, H, l, forked ? H->ev_join : nullptr, forked ? 2 : 0));
-    // (the main stream now waits for R; flags that went up behind R are joined by sagg_setup_csr, through ev_flags)
-    if (forked && H->flags_levels != l + 1) H->aux_pending = false;
+    // W^T off the critical path: on the other stream behind R and the flags, and enqueued behind the Galerkin sums (its
+    // nine launches in front of them kept the main stream waiting for the host); nobody waits for it before the first
+    // cycle
+    if (L->restrict_want && forked) {
+        NODAL_HIP_TRY(h, hipStreamWaitEvent(H->aux, H->ev_w, 0));
+        h->stream = H->aux;
+        NODAL_TRY(build_wt(h, H, l));
+        h->stream = main_st;
+        NODAL_HIP_TRY(h, hipEventRecord(H->ev_wt, H->aux));
+        H->wt_pending = true;
+    } else if (L->restrict_want) {
+        NODAL_TRY(build_wt(h, H, l));
+    }
+    // (the main stream now waits for R; flags that went up behind R and W^T are joined by sagg_setup_csr, through
+    // ev_flags and ev_wt)
+    if (forked && H->flags_levels != l + 1 && !H->wt_pending) H->aux_pending = false;
     return NODAL_OK;
 }
 
@@ -1995,6 +2159,7 @@ int fold_check_level(nodal_ctx *h, SHierarchy *H, int l, bool two) {
     return NODAL_OK;
 }
 int visit_self_check(nodal_ctx *h, SHierarchy *H);  // (behind cycle(), which it runs)
+int restrict_self_check(nodal_ctx *h, SHierarchy *H);  // (behind the cycle kernels it runs)
 int fold_self_check(nodal_ctx *h, SHierarchy *H) {
     static const bool check = knob::TRACE.now() && knob::SA_FOLD_CHECK.now();
     if (!check) return NODAL_OK;
@@ -2126,11 +2291,13 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
         const bool forked = H->aux != nullptr && nodal_extra_streams_ok(h) &&
                             knob::SA_FORK.now();
         hipStream_t rst = st;
+        const bool wt = L->restrict_want && H->sym_stats[(size_t)l * ST_COUNT + ST_RESTRICTMISS] == 0;  // (W^T is complete)
         if (forked) {
             NODAL_HIP_TRY(h, hipEventRecord(H->ev_fork, st));
             NODAL_HIP_TRY(h, hipStreamWaitEvent(H->aux, H->ev_fork, 0));
             H->aux_pending = true;
             NODAL_TRY(galerkin_product<true>(h, H, l, nullptr, 1));
+            if (wt) NODAL_HIP_TRY(h, hipEventRecord(H->ev_w, st));  // (W is rewritten)
             rst = H->aux;
         }
         r_refresh<<<grid_for(C->n * 8), TB, 0, rst>>>(C->n, L->rld, L->rlen.as<int32_t>(), L->rcol.as<int32_t>(), L->ld,
@@ -2138,8 +2305,23 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
                                                      L->rvalf.as<float>());
         NODAL_HIP_TRY(h, hipGetLastError());
         if (forked) NODAL_HIP_TRY(h, hipEventRecord(H->ev_join, H->aux));
+        if (forked && wt) NODAL_HIP_TRY(h, hipStreamWaitEvent(H->aux, H->ev_w, 0));
         NODAL_TRY(galerkin_product<true>(h, H, l, forked ? H->ev_join : nullptr, forked ? 2 : 0));
-        if (forked) H->aux_pending = false;
+        if (wt) {  // W^T's values through the kept source positions, behind the A P launch that rewrote W
+            wt_refresh<<<grid_for(L->wtcap), TB, 0, rst>>>(C->n, L->wtstart.as<uint32_t>(), L->wtsrc.as<int32_t>(),
+                                                          L->wval.as<float>(), L->wtval.as<float>());
+            NODAL_HIP_TRY(h, hipGetLastError());
+            if (forked) {
+                NODAL_HIP_TRY(h, hipEventRecord(H->ev_wt, H->aux));
+                H->wt_pending = true;
+            }
+        }
+        if (forked && !H->wt_pending) H->aux_pending = false;
+    }
+    if (H->wt_pending) {
+        NODAL_HIP_TRY(h, hipStreamWaitEvent(st, H->ev_wt, 0));
+        H->wt_pending = false;
+        H->aux_pending = false;
     }
     const int last = H->nlev - 1;
     if (H->dense_coarsest)
@@ -2157,6 +2339,7 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
     decide_folds(H, hs, false);
     NODAL_TRY(fold_self_check(h, H));
     NODAL_TRY(visit_self_check(h, H));
+    NODAL_TRY(restrict_self_check(h, H));
     *ok = true;
     return NODAL_OK;
 }
@@ -2227,6 +2410,8 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
     H->sym_valid = false;
     H->refreshed = false;
     H->want_flags = check_floating;
+    H->general = general;
+    H->wt_pending = false;
     H->flags_levels = 0;
     H->last_iters = 0;
     H->drop_graph();
@@ -2319,6 +2504,11 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
     NODAL_HIP_TRY(h, hipMemcpyAsync(hs, dstats, (size_t)MAX_LEVELS * ST_COUNT * 8, hipMemcpyDeviceToHost, st));
     if (!H->ev_copy) NODAL_HIP_TRY(h, hipEventCreateWithFlags(&H->ev_copy, hipEventDisableTiming));
     NODAL_HIP_TRY(h, hipEventRecord(H->ev_copy, st));
+    if (H->wt_pending) {  // W^T of the levels that restrict from b: before the first cycle, and before the last read-back
+        NODAL_HIP_TRY(h, hipStreamWaitEvent(st, H->ev_wt, 0));
+        H->wt_pending = false;
+        if (!(check_floating && H->flags_levels != 0)) H->aux_pending = false;
+    }
     if (check_floating) {
         // (round 4) the "touches ground" flags go up the aggregate maps while the host waits for that copy: they
         // need the aggregates of every level, which are all there, and nothing the copy brings
@@ -2404,6 +2594,7 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
     decide_folds(H, hs, trace);
     NODAL_TRY(fold_self_check(h, H));
     NODAL_TRY(visit_self_check(h, H));
+    NODAL_TRY(restrict_self_check(h, H));
     H->ready = true;
     *accepted = true;
     H->sym_valid = true;
@@ -2524,20 +2715,43 @@ int cycle(nodal_ctx *h, SHierarchy *H, int l, const TBV *b, const cyc_t *x0, TOU
         SAGG_DISPATCH_W(L->wfix, (k_post<W, false, TBV, cyc_t><<<g, tb, 0, st>>>(A, dinv, b, x, x2, nullptr, nullptr, nullptr)));
         x = x2;
     }
-    SAGG_DISPATCH_W(L->wfix, (k_smooth_residual<W, TBV><<<g, tb, 0, st>>>(A, b, x, r)));
     const bool last = l + 1 == H->tail || l + 1 == H->nlev - 1;
+    // One sweep per side: r and rc = W^T b in one launch (SLevel::restrict_b; k_residual_restrict); r waits for
+    // k_prolong_post, which `fold` says is there.
+    bool from_b = false;
+    if constexpr (std::is_same_v<TBV, cyc_t>) {
+        from_b = L->restrict_b && fold && nu == 1 && !sb;
+        if (from_b) {
+            const unsigned rblocks = restrict_blocks(nc);
+            const unsigned gw = rblocks + grid_for(n);
+            const uint32_t *ws = L->wtstart.as<uint32_t>();
+            const int32_t *wc = L->wtcol.as<int32_t>();
+            const float *wv = L->wtval.as<float>();
+            if (last) {
+                SAGG_DISPATCH_W(L->wfix, (k_residual_restrict<W, double><<<gw, TB, 0, st>>>(
+                                             A, b, x, r, rblocks, nc, ws, wc, wv, C->v<double>(V_RC), C->dinv.as<double>(), nullptr)));
+            } else {
+                SAGG_DISPATCH_W(L->wfix, (k_residual_restrict<W, cyc_t><<<gw, TB, 0, st>>>(
+                                             A, b, x, r, rblocks, nc, ws, wc, wv, C->v<cyc_t>(V_RC), C->dinv.as<double>(),
+                                             C->v<cyc_t>(V_X))));
+            }
+        }
+    }
+    if (!from_b) SAGG_DISPATCH_W(L->wfix, (k_smooth_residual<W, TBV><<<g, tb, 0, st>>>(A, b, x, r)));
     const double *coef = nullptr;
     if (last) {
         double *rc = C->v<double>(V_RC), *c1 = C->v<double>(V_C1);
-        k_restrict<double><<<grid_for(nc * RL), TB, 0, st>>>(nc, L->rld, L->rcol.as<int32_t>(), L->rvalf.as<float>(),
-                                                            L->rlen.as<int32_t>(), r, rc, C->dinv.as<double>(), nullptr);
+        if (!from_b)
+            k_restrict<double><<<grid_for(nc * RL), TB, 0, st>>>(nc, L->rld, L->rcol.as<int32_t>(), L->rvalf.as<float>(),
+                                                                L->rlen.as<int32_t>(), r, rc, C->dinv.as<double>(), nullptr);
         NODAL_HIP_TRY(h, hipGetLastError());
         NODAL_TRY(last_level(h, H, l + 1, rc, c1));
         hand_up((const double *)c1, (const double *)nullptr, nullptr);
     } else {
         cyc_t *rc = C->v<cyc_t>(V_RC), *c1 = C->v<cyc_t>(V_C1), *c2 = C->v<cyc_t>(V_C2), *x0c = C->v<cyc_t>(V_X);
-        k_restrict<cyc_t><<<grid_for(nc * RL), TB, 0, st>>>(nc, L->rld, L->rcol.as<int32_t>(), L->rvalf.as<float>(),
-                                                           L->rlen.as<int32_t>(), r, rc, C->dinv.as<double>(), x0c);
+        if (!from_b)
+            k_restrict<cyc_t><<<grid_for(nc * RL), TB, 0, st>>>(nc, L->rld, L->rcol.as<int32_t>(), L->rvalf.as<float>(),
+                                                               L->rlen.as<int32_t>(), r, rc, C->dinv.as<double>(), x0c);
         NODAL_HIP_TRY(h, hipGetLastError());
         int nparts = 0;
         // K-cycle (two flexible-CG steps on the coarse problem) at the first coarse level only, when
@@ -2758,6 +2972,111 @@ int visit_check_level(nodal_ctx *h, SHierarchy *H, int l) {
                     "d = %.3e (against the bound 2^-23: %.3e)\n", l, (long long)n, (long long)nt, maxp2, dm, dm / 0x1p-23);
     return NODAL_OK;
 }
+// NODAL_TRACE with NODAL_SA_RESTRICT_CHECK=1: every level that restricts from b forms rc both ways on one fixed
+// right-hand side of both signs (b uniform in (-1, 1), x0 = w D^-1 b as its producer leaves it) and prints
+//   d = max_I |rc_new - rc_old|_I / den_I,   den_I = sum_i |R_Ii| (|b_i| + sum_j |a_ij| |x0_j|) + sum_i |W_iI| |b_i|,
+// den formed on the host in fp64 from the operators as stored.  Against the exact rc (A, P in f64, W = G P) the two
+// launches carry the f32 roundings of x0, of the copies of A and of R and of r as stored -- each at most 2^-24 of a
+// term of the first sum --, the one launch that of the stored W, 2^-24 of a term of the second; every sum is fp64.  The
+// roundings are of either sign and do not add up in practice: the bar is 2^-23 as for the visit check above (measured:
+// tests/test_gpu_restrict_from_b.py).
+template <typename TO>
+int restrict_check_level(nodal_ctx *h, SHierarchy *H, int l) {
+    hipStream_t st = h->stream;
+    SLevel *L = H->pool[l], *C = H->pool[l + 1];
+    const int64_t n = L->n, ld = L->ld, nc = C->n, rld = L->rld;
+    uint64_t seed = 0x9e3779b97f4a7c15ull + 1297ull * (uint64_t)l;
+    auto unit = [&]() {  // (splitmix64: uniform in (-1, 1))
+        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        return (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
+    };
+    const int64_t rslots = (int64_t)rcap_for(nc) * rld;
+    std::vector<double> dinv((size_t)n);
+    std::vector<cyc_t> hb((size_t)n), hx0((size_t)n);
+    std::vector<TO> rc_old((size_t)nc), rc_new((size_t)nc);
+    std::vector<int32_t> acol((size_t)L->width * ld), alen((size_t)n), rcol((size_t)rslots), rlen((size_t)nc),
+        wcol((size_t)L->wslots * ld), wlen((size_t)n);
+    std::vector<float> aval((size_t)L->width * ld), rval((size_t)rslots), wval((size_t)L->wslots * ld);
+    auto down = [&](void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = down(dinv.data(), L->dinv.p, (size_t)n * 8);
+    for (int64_t i = 0; i < n; ++i) {
+        hb[i] = (cyc_t)unit();
+        hx0[i] = (cyc_t)(OMEGA * dinv[i] * (double)hb[i]);
+    }
+    const size_t vb = align256((size_t)n * sizeof(cyc_t)), cb = align256((size_t)nc * sizeof(TO));
+    DevBuf buf;
+    if (e == hipSuccess) e = buf.reserve(3 * vb + 2 * cb);
+    char *p = buf.as<char>();
+    cyc_t *b = reinterpret_cast<cyc_t *>(p), *x0 = reinterpret_cast<cyc_t *>(p + vb), *r = reinterpret_cast<cyc_t *>(p + 2 * vb);
+    TO *ro = reinterpret_cast<TO *>(p + 3 * vb), *rn = reinterpret_cast<TO *>(p + 3 * vb + cb);
+    if (e == hipSuccess) e = hipMemcpyAsync(b, hb.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(x0, hx0.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        const Ell A = L->A();
+        const unsigned g = grid_for(n);
+        const unsigned rblocks = restrict_blocks(nc);
+        SAGG_DISPATCH_W(L->wfix, (k_smooth_residual<W, cyc_t><<<g, TB, 0, st>>>(A, b, x0, r)));
+        k_restrict<TO><<<grid_for(nc * RL), TB, 0, st>>>(nc, rld, L->rcol.as<int32_t>(), L->rvalf.as<float>(),
+                                                        L->rlen.as<int32_t>(), r, ro, C->dinv.as<double>(), nullptr);
+        SAGG_DISPATCH_W(L->wfix, (k_residual_restrict<W, TO><<<rblocks + g, TB, 0, st>>>(
+                                     A, b, x0, r, rblocks, nc, L->wtstart.as<uint32_t>(), L->wtcol.as<int32_t>(),
+                                     L->wtval.as<float>(), rn, C->dinv.as<double>(), nullptr)));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = down(rc_old.data(), ro, (size_t)nc * sizeof(TO));
+    if (e == hipSuccess) e = down(rc_new.data(), rn, (size_t)nc * sizeof(TO));
+    if (e == hipSuccess) e = down(acol.data(), L->acol.p, acol.size() * 4);
+    if (e == hipSuccess) e = down(aval.data(), L->avalf.p, aval.size() * 4);
+    if (e == hipSuccess) e = down(alen.data(), L->alen.p, (size_t)n * 4);
+    if (e == hipSuccess) e = down(rcol.data(), L->rcol.p, rcol.size() * 4);
+    if (e == hipSuccess) e = down(rval.data(), L->rvalf.p, rval.size() * 4);
+    if (e == hipSuccess) e = down(rlen.data(), L->rlen.p, (size_t)nc * 4);
+    if (e == hipSuccess) e = down(wcol.data(), L->wcol.p, wcol.size() * 4);
+    if (e == hipSuccess) e = down(wval.data(), L->wval.p, wval.size() * 4);
+    if (e == hipSuccess) e = down(wlen.data(), L->wlen.p, (size_t)n * 4);
+    buf.release();
+    NODAL_HIP_TRY(h, e);
+    std::vector<double> t((size_t)n), den((size_t)nc, 0.0);
+    for (int64_t i = 0; i < n; ++i) {  // |b_i| + sum_j |a_ij| |x0_j|
+        double s = fabs((double)hb[i]);
+        for (int32_t q = 0; q < alen[i]; ++q)
+            s += fabs((double)aval[(size_t)q * ld + i]) * fabs((double)hx0[acol[(size_t)q * ld + i]]);
+        t[i] = s;
+    }
+    for (int64_t I = 0; I < nc; ++I)
+        for (int32_t q = 0; q < rlen[I]; ++q) {
+            const size_t at = ((size_t)(q >> 3) * rld + I) * 8 + (q & 7);
+            den[I] += fabs((double)rval[at]) * t[rcol[at]];
+        }
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t q = 0; q < wlen[i]; ++q)
+            den[wcol[(size_t)q * ld + i]] += fabs((double)wval[(size_t)q * ld + i]) * fabs((double)hb[i]);
+    double dm = 0.0;
+    for (int64_t I = 0; I < nc; ++I) {
+        const double di = fabs((double)rc_new[I] - (double)rc_old[I]) / den[I];  // (0 / 0: a NaN, which the maximum keeps)
+        dm = !(di <= dm) ? di : dm;
+    }
+    fprintf(stderr, "[sagg] restrict check: level %d, rows %lld, coarse rows %lld, rc from b against the two launches "
+                    "d = %.3e (against the bound 2^-23: %.3e)\n", l, (long long)n, (long long)nc, dm, dm / 0x1p-23);
+    return NODAL_OK;
+}
+int restrict_self_check(nodal_ctx *h, SHierarchy *H) {
+    static const bool check = knob::TRACE.now() && knob::SA_RESTRICT_CHECK.now();
+    if (!check) return NODAL_OK;
+    for (int l = 1; l + 1 < H->nlev; ++l) {
+        if (!H->pool[l]->restrict_b) continue;
+        const bool last = l + 1 == H->tail || l + 1 == H->nlev - 1;  // (as cycle() tells the two forms apart)
+        if (last) NODAL_TRY(restrict_check_level<double>(h, H, l));
+        else NODAL_TRY(restrict_check_level<cyc_t>(h, H, l));
+    }
+    return NODAL_OK;
+}
+
 int visit_self_check(nodal_ctx *h, SHierarchy *H) {
     static const bool check = knob::TRACE.now() && knob::SA_VISIT_CHECK.now();
     if (!check) return NODAL_OK;
@@ -2861,6 +3180,10 @@ int sagg_debug_array(nodal_ctx *h, int32_t level, int32_t which, void *dst, int6
         case NODAL_HA_P2VAL: buf = &L->p2val; bytes = next && L->visit_want ? (int64_t)P2CAP * L->ld * 4 : 0; break;
         case NODAL_HA_P2LEN: buf = &L->p2len; bytes = next && L->visit_want ? L->n * 4 : 0; break;
         case NODAL_HA_D2: buf = &L->d2; bytes = next && L->visit_want ? L->nc * L->ld * 4 : 0; break;
+        case NODAL_HA_WTSTART: buf = &L->wtstart; bytes = next && L->restrict_b ? (L->nc + 1) * 4 : 0; break;
+        case NODAL_HA_WTCOL: buf = &L->wtcol; bytes = next && L->restrict_b ? L->wtcap * 4 : 0; break;
+        case NODAL_HA_WTVAL: buf = &L->wtval; bytes = next && L->restrict_b ? L->wtcap * 4 : 0; break;
+        case NODAL_HA_WTSRC: buf = &L->wtsrc; bytes = next && L->restrict_b ? L->wtcap * 4 : 0; break;
         default: return nodal_fail(h, NODAL_E_INVALID, "debug hierarchy: no such array");
         }
     }

@@ -1034,6 +1034,68 @@ __global__ __launch_bounds__(TB) void k_visit_last(Ell A, const double *__restri
     }
 }
 
+// ---- a level with one sweep per side: residual and restricted residual in one launch (SLevel::restrict_b) ----
+// From x0 = w D^-1 b the visit forms r = b - A x0 and rc = R r.  With G = I - w D^-1 A, W = G P (k_prolong_post's
+// operator), A = A^T and R = P^T:  rc = P^T (I - w A D^-1) b = (G P)^T b = W^T b  -- rc needs b only, and r is not read
+// before k_prolong_post.  The leading `rblocks` workgroups form rc (they feed the next launch), the others r
+// (k_smooth_residual's rows, the same bits); no workgroup reads what another one of the launch writes.
+// Restriction: WT_LANES adjacent lanes per coarse row of W^T (entries wtstart[I] .. wtstart[I + 1]: fine row, f32
+// value), lane u of them takes the entries u, u + WT_LANES, ...; WT_U rounds (128 entries: the rows of the 143 k-row
+// level of grid(1000) average 85, the longest seen has 130) are requested before the first gather, unconditionally (an
+// entry past the end re-reads the lane's first one): three dependent round trips for such a row.  Per-lane sums in entry
+// order, then the lanes' sums by shuffles in one fixed order: no atomics.  Sixteen lanes, not a wavefront, per row: a
+// wavefront per row made 8.9 k wavefronts at that level, more than the device holds at once (8192), and the residual
+// part queued behind them -- 10.6 us for the launch where its two parts take 6.5 and 5.0 us alone.  With 16 rows per
+// workgroup both parts (560 + 560 workgroups) are resident from the start and run their round trips side by side.
+constexpr int WT_LANES = 16, WT_U = 8;
+static_assert(64 % WT_LANES == 0 && TB % WT_LANES == 0, "whole rows per wavefront");
+inline unsigned restrict_blocks(int64_t nc) {  // workgroups of the restriction part: whole groups of eight, so that the
+    const int64_t g = (nc + TB / WT_LANES - 1) / (TB / WT_LANES);  // residual part keeps its rows' XCDs (xcd_block_sub)
+    return (unsigned)((g + 7) & ~(int64_t)7);
+}
+template <int W, typename TO>
+__global__ __launch_bounds__(TB) void k_residual_restrict(Ell A, const cyc_t *__restrict__ b, const cyc_t *__restrict__ x0,
+                                                          cyc_t *__restrict__ r, unsigned rblocks, int64_t nc,
+                                                          const uint32_t *__restrict__ wtstart,
+                                                          const int32_t *__restrict__ wtcol, const float *__restrict__ wtval,
+                                                          TO *__restrict__ rc, const double *__restrict__ cdinv,
+                                                          cyc_t *__restrict__ x0c) {
+    if (blockIdx.x >= rblocks) {
+        const unsigned count = gridDim.x - rblocks;
+        for (int64_t i = (int64_t)xcd_block_sub(rblocks, count) * TB + threadIdx.x; i < A.n; i += (int64_t)count * TB) {
+            const double s = ell_row_w<W>(A, A.valf, i, 0, [&](int32_t j) { return (double)x0[j]; });
+            r[i] = (cyc_t)((double)b[i] - s);
+        }
+        return;
+    }
+    const uint32_t sub = threadIdx.x & (WT_LANES - 1);
+    const int64_t I = (int64_t)xcd_block_sub(0, rblocks) * (TB / WT_LANES) + threadIdx.x / WT_LANES;
+    const bool live = I < nc;  // (a row's lanes together; nobody leaves before the shuffles)
+    const uint32_t s0 = live ? wtstart[I] : 0u, len = live ? wtstart[I + 1] - s0 : 0u;
+    double s = 0.0;
+    for (uint32_t t0 = sub; t0 < len; t0 += WT_LANES * WT_U) {
+        int32_t c[WT_U];
+        double v[WT_U];
+#pragma unroll
+        for (int u = 0; u < WT_U; ++u) {
+            const bool ok = t0 + WT_LANES * u < len;
+            const uint32_t at = s0 + (ok ? t0 + WT_LANES * u : t0);
+            c[u] = wtcol[at];
+            const float loaded = wtval[at];  // (unconditional: `at` is always an entry of the row)
+            v[u] = ok ? (double)loaded : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < WT_U; ++u) s = fma(v[u], (double)b[c[u]], s);
+    }
+#pragma unroll
+    for (int off = WT_LANES >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (live && sub == 0) {
+        const TO stored = (TO)s;
+        rc[I] = stored;
+        if (x0c) x0c[I] = (cyc_t)(OMEGA * cdinv[I] * (double)stored);  // pre-smoothed iterate of the coarse visit
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // flexible CG (Polak-Ribiere beta: the K-cycle is a mildly non-linear operator)
 // ---------------------------------------------------------------------------------

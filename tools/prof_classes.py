@@ -32,7 +32,7 @@ LEVEL0_BYTES = {
 }
 SETUP_NAMES = ("mis_", "assign_", "build_P", "r_count", "r_fill", "r_sort", "r_to_ell", "r_refresh", "ap_rows",
                "galerkin", "coarsest_inverse", "flags_up", "last_level", "any_unflagged", "k_tail_pack", "row_stats",
-               "csr_to_ell", "reduce_bstat", "scan_", "grounded_flags", "select_nodes")
+               "csr_to_ell", "reduce_bstat", "scan_", "grounded_flags", "select_nodes", "wt_")
 # ("k_tail_pack" also takes k_tail_pack_op, the launch that forms the tail's dense operator once per setup; the
 # per-visit k_tail_apply falls under coarse_levels like the k_tail it replaces)
 STAMP_NAMES = ("grp::", "fold_matrix", "fold_rhs", "set_tail")
