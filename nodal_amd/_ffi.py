@@ -105,6 +105,14 @@ HIERARCHY_ARRAYS = (("acol", np.int32), ("aval", np.float64), ("avalf", np.float
 HIERARCHY_INFO = ("n", "ld", "nc", "width", "maxlen", "wfix", "nnz", "rld", "rcap", "wslots", "fold_want", "fold", "d16",
                   "in_tail", "refreshed", "dense_coarsest")
 
+# csrc/galerkin_groups.h: what a coarse row may have to share a wavefront with three others in the Galerkin sums
+# (tests/test_galerkin_groups_host.py holds these against the header)
+GALERKIN_SUB_ROWS = 4
+GALERKIN_SUB_ENTRIES = 32
+GALERKIN_SUB_PRODUCTS = 128
+GALERKIN_SUB_COLUMNS = 16
+GALERKIN_DYN_PRODUCTS = 1024  # (knobs.h: the default of NODAL_SA_GLIST, the product list of a 64-slot level)
+
 _lib = None
 _live = weakref.WeakSet()  # handles still open; closed before the HIP runtime unloads
 

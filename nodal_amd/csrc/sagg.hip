@@ -32,6 +32,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "galerkin_groups.h"
 #include "group.h"
 
 int grounded_flags(nodal_ctx *h, uint8_t *flags_dev);  // lowdeg.hip
@@ -1280,6 +1281,393 @@ __global__ __launch_bounds__(64) void galerkin(int64_t ld, const int32_t *__rest
     if (my_flags & 4u) atomicOr(&stats[ST_BADDIAG], 1ull);
 }
 
+// ---- The same sums with groups cut at run time (NODAL_SA_GDYN) and four small coarse rows per wavefront
+// (NODAL_SA_GROWS).  galerkin_groups.h holds the rule and the capacities; the kernel above is what runs with both off.
+struct GalerkinArgs {
+    int64_t ld;
+    const int32_t *apcol;
+    const double *apval;
+    const int32_t *aplen;
+    int64_t nc, rld;
+    const int32_t *rcol;
+    const double *rval;
+    const int32_t *rlen;
+    int64_t cld;
+    int32_t *ccol;
+    double *cval;
+    float *cvalf;
+    int32_t *clen;
+    double *cdinv;
+};
+
+// lane exchanges within a row of 16 lanes (DPP: no LDS crossbar); lanes shifted in from outside the row read 0
+template <int CTRL>
+__device__ __forceinline__ int dpp_row(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+}
+__device__ __forceinline__ int row16_incl_scan(int v) {
+    v += dpp_row<0x111>(v);  // row_shr:1
+    v += dpp_row<0x112>(v);
+    v += dpp_row<0x114>(v);
+    v += dpp_row<0x118>(v);
+    return v;
+}
+// how many of the row's other 15 lanes hold a smaller value (row_ror:1..15)
+template <int K = 1>
+__device__ __forceinline__ int row16_rank(int32_t v) {
+    int r = dpp_row<0x120 + K>(v) < v ? 1 : 0;
+    if constexpr (K < 15) r += row16_rank<K + 1>(v);
+    return r;
+}
+
+// One group of row I of R from entry t0 on, cut by galerkin_groups.h: the products of the entries it keeps go to the
+// list as galerkin_products writes them.  *take: the entries kept (at least one).
+__device__ __forceinline__ int galerkin_products_dyn(const GalerkinArgs &a, int64_t I, int t0, int remaining,
+                                                     const GalerkinCaps &caps, int32_t *lJ, double *lV, int *take) {
+    const int lane = threadIdx.x;
+    const int cand = galerkin_group_candidates(remaining, caps);
+    int32_t i = 0, len = 0;
+    double w = 0.0;
+    if (lane < cand) {
+        const int t = t0 + lane;
+        const int64_t rat = ((int64_t)(t >> 3) * a.rld + I) * 8 + (t & 7);
+        i = a.rcol[rat];
+        w = a.rval[rat];
+        len = a.aplen[i];
+        len = len < 0 ? 0 : (len > caps.products ? caps.products : len);  // (no input overflows the list)
+    }
+    int all = 0;
+    int o = wave_excl_scan(len, &all);
+    const int tk = __popcll(__ballot(galerkin_group_keeps(lane, cand, o + len, caps)));
+    if (lane >= tk) len = 0;
+    const int np = __shfl(o + len, tk - 1, 64);
+    constexpr int INFL = 8;
+    for (int32_t s0 = 0; s0 < len; s0 += INFL) {
+        int32_t cj[INFL];
+        double cv[INFL];
+#pragma unroll
+        for (int q = 0; q < INFL; ++q) {
+            const int32_t s = s0 + q < len ? s0 + q : s0;
+            cj[q] = a.apcol[(int64_t)s * a.ld + i];
+            cv[q] = a.apval[(int64_t)s * a.ld + i];
+        }
+#pragma unroll
+        for (int q = 0; q < INFL; ++q)
+            if (s0 + q < len) {
+                lJ[o] = cj[q];
+                lV[o] = w * cv[q];
+                ++o;
+            }
+    }
+    for (int p = lane + np; p < np + 72; p += 64) lJ[p] = -1;
+    __syncthreads();
+    *take = tk;
+    return np;
+}
+
+// one coarse row by the whole wavefront: the kernel above with its groups cut by `caps`
+template <bool NUMERIC>
+__device__ __forceinline__ void galerkin_row_wave(const GalerkinArgs &a, int64_t I, const GalerkinCaps &caps, int maxseg,
+                                                  int32_t *set, int32_t *lJ, double *lV, uint32_t &my_max,
+                                                  uint32_t &my_nnz, uint32_t &my_flags) {
+    const int lane = threadIdx.x;
+    const int rl = a.rlen[I];
+    int np = 0, take = 0, ngroups = 0;
+    int total = 0;
+    int32_t myJ = 0x7fffffff;
+    if constexpr (NUMERIC) {
+        total = a.clen[I];
+        if (lane < total) myJ = a.ccol[(int64_t)lane * a.cld + I];
+    } else {
+        for (int k = lane; k < 256; k += 64) set[k] = -1;
+        __syncthreads();
+        for (int t0 = 0; t0 < rl; t0 += take, ++ngroups) {
+            np = galerkin_products_dyn(a, I, t0, rl - t0, caps, lJ, lV, &take);
+            for (int p = lane; p < np; p += 64) {
+                const int32_t J = lJ[p];
+                uint32_t hsh = ((uint32_t)J * 2654435761u) >> 24;
+                for (int probe = 0; probe < 256; ++probe) {
+                    const int32_t old = atomicCAS(&set[hsh], -1, J);
+                    if (old == -1 || old == J) break;
+                    hsh = (hsh + 1) & 255u;
+                    if (probe == 255) my_flags |= 1u;
+                }
+            }
+            __syncthreads();
+        }
+        int32_t mine[4];
+        int cnt = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            mine[q] = set[lane * 4 + q];
+            cnt += mine[q] >= 0 ? 1 : 0;
+        }
+        int off = wave_excl_scan(cnt, &total);
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (mine[q] >= 0) set[off++] = mine[q];
+        __syncthreads();
+        if (total > ACAP) {
+            my_flags |= 1u;
+            total = ACAP;
+        }
+        myJ = lane < total ? set[lane] : 0x7fffffff;
+        __syncthreads();
+#pragma unroll
+        for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                const int32_t other = __shfl_xor(myJ, j, 64);
+                const bool up = (lane & k) == 0, lower = (lane & j) == 0;
+                const int32_t lo = myJ < other ? myJ : other, hi = myJ < other ? other : myJ;
+                myJ = (lower == up) ? lo : hi;
+            }
+        }
+    }
+    const bool kept = !NUMERIC && ngroups == 1;  // the row's only group is still in the list
+    const int nseg = min(maxseg, total <= 16 ? 4 : (total <= 32 ? 2 : 1)), segw = 64 / nseg;
+    const int seg = lane / segw;
+    const int32_t segJ = __shfl(myJ, lane % segw, 64);
+    double acc = 0.0;
+    for (int t0 = 0; t0 < rl; t0 += take) {
+        if (kept) take = rl;
+        else np = galerkin_products_dyn(a, I, t0, rl - t0, caps, lJ, lV, &take);
+        int chunk = (((np + nseg - 1) / nseg) + 7) & ~7;
+        if (nseg > 1 && ((chunk >> 3) & 1) == 0) chunk += 8;
+        for (int p = seg * chunk; p < (seg + 1) * chunk; p += 8) {
+            int32_t j8[8];
+            double v8[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                j8[u] = lJ[p + u];
+                v8[u] = lV[p + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += j8[u] == segJ ? v8[u] : 0.0;
+        }
+        __syncthreads();
+    }
+    if (nseg == 4) {
+        const double a1 = __shfl(acc, lane + 16, 64), a2 = __shfl(acc, lane + 32, 64), a3 = __shfl(acc, lane + 48, 64);
+        acc = (acc + a1) + (a2 + a3);
+    } else if (nseg == 2) {
+        acc += __shfl(acc, lane + 32, 64);
+    }
+    if (lane >= total && lane < APAD) {
+        a.ccol[(int64_t)lane * a.cld + I] = (int32_t)I;
+        a.cval[(int64_t)lane * a.cld + I] = 0.0;
+        a.cvalf[(int64_t)lane * a.cld + I] = 0.0f;
+    }
+    if (lane < total) {
+        a.ccol[(int64_t)lane * a.cld + I] = myJ;
+        a.cval[(int64_t)lane * a.cld + I] = acc;
+        a.cvalf[(int64_t)lane * a.cld + I] = (float)acc;
+        if (myJ == (int32_t)I) {
+            if (!(acc > 0.0)) my_flags |= 4u;
+            a.cdinv[I] = acc > 0.0 ? 1.0 / acc : 1.0;
+        }
+    }
+    if (lane == 0) {
+        a.clen[I] = total;
+        my_max = (uint32_t)total > my_max ? (uint32_t)total : my_max;
+        my_nnz += (uint32_t)total;
+    }
+    __syncthreads();
+}
+
+// SHARED: a sub-group of 16 lanes per coarse row, four consecutive rows per wavefront and step of the row loop: the four
+// rows' chains of dependent loads (R entry -> A P row length -> A P slots) run side by side.  A row takes the shared path
+// when its R entries, its products and its columns fit the sub-group (galerkin_groups.h); lane 2k and 2k + 1 of the R row
+// go to lane k, the products to the sub-group's quarter of the list in (R entry, A P slot) order, the columns to a hash
+// table of 16 slots -- slot s is lane s's column, a full table is a row of more than 16 columns -- and every lane sums
+// the products of its column, segment by segment as the whole wavefront would (the same bits on either path).  The
+// lane's rank among the row's columns is the slot of A_c it writes: no sort.  Rows that do not fit are then taken one by one by the whole wavefront.  Which path a row takes depends on the
+// row alone, so neither the grid size nor a values-only refresh (NUMERIC: the same test with the kept column count)
+// changes a sum's order.
+template <bool NUMERIC, bool SHARED>
+__global__ __launch_bounds__(64) void galerkin_rows(GalerkinArgs a, unsigned long long *__restrict__ stats,
+                                                    uint32_t *__restrict__ bstat, GalerkinCaps caps, int pcap, int maxseg) {
+    extern __shared__ __attribute__((aligned(16))) char gsm[];
+    int32_t *set = reinterpret_cast<int32_t *>(gsm);       // [256]
+    double *lV = reinterpret_cast<double *>(gsm + 1024);   // [pcap]
+    int32_t *lJ = reinterpret_cast<int32_t *>(lV + pcap);  // [pcap]
+    const int lane = threadIdx.x;
+    uint32_t my_max = 0, my_nnz = 0, my_flags = 0;
+    if constexpr (!SHARED) {
+        for (int64_t I = blockIdx.x; I < a.nc; I += gridDim.x)
+            galerkin_row_wave<NUMERIC>(a, I, caps, maxseg, set, lJ, lV, my_max, my_nnz, my_flags);
+    } else {
+        constexpr int32_t NONE = 0x7fffffff;
+        const int sub = lane >> 4, sl = lane & 15;
+        const int ecap = galerkin_sub_entries(caps.entries);
+        int32_t *sJ = lJ + sub * GALERKIN_SUB_STRIDE;  // (pcap >= 4 strides: galerkin_product)
+        double *sV = lV + sub * GALERKIN_SUB_STRIDE;
+        int32_t *tbl = set + sub * GALERKIN_SUB_LANES;
+        const int64_t nq = (a.nc + GALERKIN_SUB_ROWS - 1) / GALERKIN_SUB_ROWS;
+        for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+            const int64_t I = q * GALERKIN_SUB_ROWS + sub;
+            const bool valid = I < a.nc;
+            const int rl = valid ? a.rlen[I] : 0;
+            bool fits = valid && rl <= ecap;
+            int total = 0;
+            int32_t myJ = NONE;
+            if constexpr (NUMERIC) {
+                total = valid ? a.clen[I] : 0;
+                fits = fits && total <= GALERKIN_SUB_COLUMNS;
+                if (fits && sl < total) myJ = a.ccol[(int64_t)sl * a.cld + I];
+            } else {
+                tbl[sl] = -1;
+            }
+            const int t = 2 * sl;
+            int32_t i0 = 0, i1 = 0, len0 = 0, len1 = 0;
+            double w0 = 0.0, w1 = 0.0;
+            if (fits && t < rl) {
+                const int64_t rat = ((int64_t)(t >> 3) * a.rld + I) * 8 + (t & 7);  // (t is even: t + 1 is in the same block of eight)
+                i0 = a.rcol[rat];
+                w0 = a.rval[rat];
+                if (t + 1 < rl) {
+                    i1 = a.rcol[rat + 1];
+                    w1 = a.rval[rat + 1];
+                }
+                len0 = a.aplen[i0];
+                if (t + 1 < rl) len1 = a.aplen[i1];
+                len0 = len0 < 0 ? 0 : (len0 > GALERKIN_SUB_STRIDE ? GALERKIN_SUB_STRIDE : len0);  // (bounds the sum below)
+                len1 = len1 < 0 ? 0 : (len1 > GALERKIN_SUB_STRIDE ? GALERKIN_SUB_STRIDE : len1);
+            }
+            const int cnt = len0 + len1, incl = row16_incl_scan(cnt);
+            const int np = __shfl(incl, lane | 15, 64);
+            fits = fits && np <= GALERKIN_SUB_PRODUCTS;
+            if (!fits) len0 = len1 = 0;
+            const int o0 = incl - cnt, o1 = o0 + len0;
+            constexpr int INFL = 6;  // slots in flight per R entry
+            const int lmax = len0 > len1 ? len0 : len1;
+            for (int32_t s0 = 0; s0 < lmax; s0 += INFL) {
+                int32_t cj0[INFL], cj1[INFL];
+                double cv0[INFL], cv1[INFL];
+#pragma unroll
+                for (int u = 0; u < INFL; ++u) {
+                    const int32_t sa = s0 + u < len0 ? s0 + u : 0, sb = s0 + u < len1 ? s0 + u : 0;
+                    cj0[u] = a.apcol[(int64_t)sa * a.ld + i0];
+                    cv0[u] = a.apval[(int64_t)sa * a.ld + i0];
+                    cj1[u] = a.apcol[(int64_t)sb * a.ld + i1];
+                    cv1[u] = a.apval[(int64_t)sb * a.ld + i1];
+                }
+#pragma unroll
+                for (int u = 0; u < INFL; ++u) {
+                    if (s0 + u < len0) {
+                        sJ[o0 + s0 + u] = cj0[u];
+                        sV[o0 + s0 + u] = w0 * cv0[u];
+                    }
+                    if (s0 + u < len1) {
+                        sJ[o1 + s0 + u] = cj1[u];
+                        sV[o1 + s0 + u] = w1 * cv1[u];
+                    }
+                }
+            }
+            const int npf = fits ? np : 0;
+            if (fits && sl < 8) sJ[np + sl] = -1;  // empty products up to the next multiple of eight
+            __syncthreads();
+            if constexpr (!NUMERIC) {
+                bool full = false;
+                for (int p = sl; p < npf; p += GALERKIN_SUB_LANES) {
+                    const int32_t J = sJ[p];
+                    uint32_t hsh = ((uint32_t)J * 2654435761u) >> 28;
+                    for (int probe = 0; probe < GALERKIN_SUB_LANES; ++probe) {
+                        const int32_t old = atomicCAS(&tbl[hsh], -1, J);
+                        if (old == -1 || old == J) break;
+                        hsh = (hsh + 1) & (GALERKIN_SUB_LANES - 1);
+                        if (probe == GALERKIN_SUB_LANES - 1) full = true;
+                    }
+                }
+                __syncthreads();
+                if ((__ballot(full) >> (sub * GALERKIN_SUB_LANES)) & 0xffffull) fits = false;  // more than 16 columns
+                const int32_t c = tbl[sl];
+                myJ = fits && c >= 0 ? c : NONE;
+                total = __popcll((__ballot(myJ != NONE) >> (sub * GALERKIN_SUB_LANES)) & 0xffffull);
+            }
+            const int rank = NUMERIC ? sl : row16_rank(myJ);
+            // The sums in the order of the whole-wavefront path, whose one group such a row is (its R entries are within
+            // `caps.entries`): the list cut into the same nseg segments of `chunk` products, each summed in list order,
+            // the partial sums combined as there -- here by one lane, there by four.  The same bits, so that which
+            // path a row takes shows nowhere downstream (the aggregation of the next level breaks ties on them).
+            const int nseg = min(maxseg, 4);
+            int chunk = (((np + nseg - 1) / nseg) + 7) & ~7;
+            if (nseg > 1 && ((chunk >> 3) & 1) == 0) chunk += 8;
+            const int np8 = fits ? (np + 7) & ~7 : 0;
+            double p0 = 0.0, p1 = 0.0, p2 = 0.0, sum = 0.0;  // the segments done, the one under way
+            int sg = 0, next = chunk;
+            for (int p = 0; p < np8; p += 8) {
+                int32_t j8[8];
+                double v8[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    j8[u] = sJ[p + u];
+                    v8[u] = sV[p + u];
+                }
+                const bool cut = p == next;  // (chunk is a multiple of eight: a step lies in one segment)
+                p0 = cut && sg == 0 ? sum : p0;
+                p1 = cut && sg == 1 ? sum : p1;
+                p2 = cut && sg == 2 ? sum : p2;
+                sum = cut ? 0.0 : sum;
+                sg += cut ? 1 : 0;
+                next += cut ? chunk : 0;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) sum += j8[u] == myJ ? v8[u] : 0.0;
+            }
+            p0 = sg == 0 ? sum : p0;
+            p1 = sg == 1 ? sum : p1;
+            p2 = sg == 2 ? sum : p2;
+            const double acc = (p0 + p1) + (p2 + (sg == 3 ? sum : 0.0));  // (segments the list does not reach: + 0.0)
+            if (fits) {
+                if (myJ != NONE) {
+                    a.ccol[(int64_t)rank * a.cld + I] = myJ;
+                    a.cval[(int64_t)rank * a.cld + I] = acc;
+                    a.cvalf[(int64_t)rank * a.cld + I] = (float)acc;
+                    if (myJ == (int32_t)I) {
+                        if (!(acc > 0.0)) my_flags |= 4u;
+                        a.cdinv[I] = acc > 0.0 ? 1.0 / acc : 1.0;
+                    }
+                }
+                // zero padding up to APAD = 32 slots: slot 16 + sl, and slot sl where no column went
+                static_assert(APAD == 2 * GALERKIN_SUB_LANES && GALERKIN_SUB_COLUMNS <= GALERKIN_SUB_LANES, "padding by lane");
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int slot = sl + k * GALERKIN_SUB_LANES;
+                    if (slot >= total) {
+                        a.ccol[(int64_t)slot * a.cld + I] = (int32_t)I;
+                        a.cval[(int64_t)slot * a.cld + I] = 0.0;
+                        a.cvalf[(int64_t)slot * a.cld + I] = 0.0f;
+                    }
+                }
+                if (sl == 0) {
+                    a.clen[I] = total;
+                    my_max = (uint32_t)total > my_max ? (uint32_t)total : my_max;
+                    my_nnz += (uint32_t)total;
+                }
+            }
+            const unsigned long long done = __ballot(fits);
+            __syncthreads();
+            for (int s = 0; s < GALERKIN_SUB_ROWS; ++s) {  // the rows that did not fit, by the whole wavefront
+                const int64_t Is = q * GALERKIN_SUB_ROWS + s;
+                if (Is < a.nc && !((done >> (s * GALERKIN_SUB_LANES)) & 1ull))
+                    galerkin_row_wave<NUMERIC>(a, Is, caps, maxseg, set, lJ, lV, my_max, my_nnz, my_flags);
+            }
+        }
+        // (the sub-groups' first lanes counted their rows, lane 0 the whole-wavefront rows as well)
+        const uint32_t m1 = __shfl(my_max, 16, 64), m2 = __shfl(my_max, 32, 64), m3 = __shfl(my_max, 48, 64);
+        const uint32_t n1 = __shfl(my_nnz, 16, 64), n2 = __shfl(my_nnz, 32, 64), n3 = __shfl(my_nnz, 48, 64);
+        my_max = max(max(my_max, m1), max(m2, m3));
+        my_nnz += n1 + n2 + n3;
+    }
+    if (lane == 0) {
+        bstat[blockIdx.x] = my_max;
+        bstat[BSTAT_MAX + blockIdx.x] = my_nnz;
+    }
+    if (my_flags & 1u) atomicOr(&stats[ST_OVERFLOW], 1ull);  // (rare)
+    if (my_flags & 4u) atomicOr(&stats[ST_BADDIAG], 1ull);
+}
+
 // dense inverse of the coarsest matrix (n <= COARSEST) by Gauss-Jordan in LDS; SPD, no pivoting
 __global__ __launch_bounds__(256) void coarsest_inverse(Ell A, double *__restrict__ inv,
                                                         unsigned long long *__restrict__ stats) {
@@ -1453,6 +1841,30 @@ int galerkin_product(nodal_ctx *h, SHierarchy *H, int l, hipEvent_t r_ready = nu
     static const int maxseg = knob::SA_GSEG.now();
     const unsigned gg = (unsigned)(nc < gcap ? nc : (gcap < BSTAT_MAX ? gcap : BSTAT_MAX));
     if (r_ready) NODAL_HIP_TRY(h, hipStreamWaitEvent(st, r_ready, 0));  // (R was built on the hierarchy's other stream)
+    // NODAL_SA_GROWS: 16-slot levels take four small coarse rows per wavefront; NODAL_SA_GDYN: 64-slot levels cut their
+    // groups by the products that fit a list of NODAL_SA_GLIST slots (at a 16-slot level G entries never fill the list:
+    // the groups stay).  Neither: the kernel and the groups of before.
+    static const bool grows = knob::SA_GROWS.now() != 0, gdyn = knob::SA_GDYN.now();
+    static const int glist = knob::SA_GLIST.now();
+    const bool shared = grows && apw == 16, dyn = gdyn && apw == 64;
+    if (shared || dyn) {
+        GalerkinCaps caps{G, 64, G * apw};
+        if (dyn) caps = GalerkinCaps{64, 64, (glist < apw ? apw : (glist > 1024 ? 1024 : glist)) & ~7};
+        int pc2 = caps.products + 72;
+        if (shared && pc2 < GALERKIN_SUB_ROWS * GALERKIN_SUB_STRIDE) pc2 = GALERKIN_SUB_ROWS * GALERKIN_SUB_STRIDE;
+        const size_t lds2 = 1024 + (size_t)pc2 * 12;
+        const int64_t units = shared ? (nc + GALERKIN_SUB_ROWS - 1) / GALERKIN_SUB_ROWS : nc;  // (a workgroup walks rows, or fours of rows)
+        const unsigned g2 = (unsigned)(units < (int64_t)gg ? units : (int64_t)gg);
+        const GalerkinArgs ga{ld, apcol, apval, aplen, nc, L->rld, L->rcol.as<int32_t>(), L->rval.as<double>(),
+                              L->rlen.as<int32_t>(), C->ld, C->acol.as<int32_t>(), C->aval.as<double>(),
+                              C->avalf.as<float>(), C->alen.as<int32_t>(), C->dinv.as<double>()};
+        unsigned long long *cst = dstats + (size_t)(l + 1) * ST_COUNT;
+        if (shared) galerkin_rows<NUMERIC, true><<<g2, 64, lds2, st>>>(ga, cst, H->bstat.as<uint32_t>(), caps, pc2, maxseg);
+        else galerkin_rows<NUMERIC, false><<<g2, 64, lds2, st>>>(ga, cst, H->bstat.as<uint32_t>(), caps, pc2, maxseg);
+        if (!NUMERIC) reduce_bstat<<<1, 1024, 0, st>>>((int)g2, H->bstat.as<uint32_t>(), cst, ST_MAXLEN, ST_NNZ);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return NODAL_OK;
+    }
     galerkin<NUMERIC><<<gg, 64, lds, st>>>(
         ld, apcol, apval, aplen, nc, L->rld, L->rcol.as<int32_t>(), L->rval.as<double>(), L->rlen.as<int32_t>(),
         C->ld, C->acol.as<int32_t>(), C->aval.as<double>(), C->avalf.as<float>(), C->alen.as<int32_t>(),
