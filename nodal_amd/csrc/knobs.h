@@ -129,8 +129,8 @@ inline constexpr Double SA_PADSLACK{"NODAL_SA_PADSLACK", 1.3};  // process: padd
 inline constexpr OnUnless0 SA_D16{"NODAL_SA_D16"};  // process: 0 32-bit instead of 16-bit column deltas at level 0
 inline constexpr Int SA_GG{"NODAL_SA_GG", 40};  // process: R entries per Galerkin group at level 0
 inline constexpr Int64 SA_GCAP{"NODAL_SA_GCAP", 16384};  // process: most workgroups of the Galerkin product (each walks several rows)
-inline constexpr Int SA_GROWS{"NODAL_SA_GROWS", 4};  // process: coarse rows per wavefront of the Galerkin sums at 16-slot levels: 0 one (the kernel of before), else four
-inline constexpr OnUnless0 SA_GDYN{"NODAL_SA_GDYN"};  // process: 0 the Galerkin groups of 64-slot levels are 16 R entries as before instead of what fits the list
+inline constexpr Int SA_GROWS{"NODAL_SA_GROWS", 4};  // process: coarse rows per wavefront of the Galerkin sums at 16-slot levels: 0 one coarse row per wavefront, else four small ones
+inline constexpr OnUnless0 SA_GDYN{"NODAL_SA_GDYN"};  // process: 0 the Galerkin groups of 64-slot levels are 16 R entries each instead of what fits the list
 inline constexpr Int SA_GLIST{"NODAL_SA_GLIST", 1024};  // process: slots of the Galerkin product list at 64-slot levels under NODAL_SA_GDYN, clamped to 64..1024
 inline constexpr Int SA_GSEG{"NODAL_SA_GSEG", 4};  // process: 1, 2 or 4 lane segments of the Galerkin accumulation
 inline constexpr Text SA_NU{"NODAL_SA_NU"};  // call: e.g. "212" Jacobi sweeps per side at level 0 / 1 / deeper (1-3 each)

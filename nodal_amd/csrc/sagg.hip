@@ -22,10 +22,12 @@
 //      aggregates, the nodes at distance 2 join the aggregate of their strongest assigned
 //      neighbour;
 //   2. P rows in registers; R by integer counting + per-row sort of (node, slot) keys;
-//   3. Galerkin product A_c = R A P: one wavefront per coarse row -- pass 1 collects the
-//      row's column set in an LDS hash set and sorts it with wave shuffles, pass 2
-//      regenerates the products in (R entry, A slot, P slot) order, stages them in LDS and
-//      every lane sums the products of "its" column in that fixed order.
+//   3. Galerkin product A_c = R (A P): A P by fine row, then one kernel (galerkin_rows) sums the
+//      coarse rows -- a wavefront per row, or a quarter of one for each of four small rows.  The
+//      row's R entries are taken in groups whose products fit an LDS list (galerkin_groups.h);
+//      pass 1 collects the row's column set in an LDS hash set and orders it, pass 2 stages the
+//      products in (R entry, A P slot) order and every lane sums the products of "its" column
+//      in that fixed order.
 // One host round trip per level (the number of aggregates sizes the next level).
 #include <hip/hip_ext.h>
 
@@ -1091,29 +1093,73 @@ __global__ __launch_bounds__(64) void ap_rows_lds(Ell A, const int32_t *__restri
     if (miss) stats[ST_FOLDMISS] = 1ull;  // (every writer stores the same word)
 }
 
-// Step 2: A_c = R (AP), one wavefront (= one 64-thread workgroup) per coarse row.  The products
-// w_t * AP[i_t, :] of a group of G entries of the R row go to an LDS list in (R entry, AP slot)
-// order; pass 1 collects the row's column set in an LDS hash set, which is sorted with wave
-// shuffles (lane l owns column l); pass 2 walks the list and every lane sums the products of
-// its column in list order.  A row of one group (the usual case) keeps its products in LDS
-// between the passes.  Three dependent round trips per group: R entry -> AP row length / slots.
-__device__ __forceinline__ int galerkin_products(int64_t ld, const int32_t *__restrict__ apcol,
-                                                 const double *__restrict__ apval, const int32_t *__restrict__ aplen,
-                                                 int64_t rld, const int32_t *__restrict__ rcol,
-                                                 const double *__restrict__ rval, int64_t I, int t0, int tn,
-                                                 int32_t *lJ, double *lV) {
+// ---- Step 2: A_c = R (AP), one kernel (galerkin_rows).  A coarse row is summed by a whole wavefront (galerkin_row_wave),
+// or, at 16-slot levels, four small rows side by side by a quarter of a wavefront each (NODAL_SA_GROWS).  The entries of a
+// row of R are taken in groups whose products fit the LDS list: at most GalerkinCaps::entries of them, and at 64-slot
+// levels cut at run time by the products they make (NODAL_SA_GDYN).  galerkin_groups.h holds the rule and the capacities;
+// with both knobs off the caps are {G, 64, G * apw}: one row per wavefront, fixed groups of G entries.
+struct GalerkinArgs {
+    int64_t ld;
+    const int32_t *apcol;
+    const double *apval;
+    const int32_t *aplen;
+    int64_t nc, rld;
+    const int32_t *rcol;
+    const double *rval;
+    const int32_t *rlen;
+    int64_t cld;
+    int32_t *ccol;
+    double *cval;
+    float *cvalf;
+    int32_t *clen;
+    double *cdinv;
+};
+
+// lane exchanges within a row of 16 lanes (DPP: no LDS crossbar); lanes shifted in from outside the row read 0
+template <int CTRL>
+__device__ __forceinline__ int dpp_row(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+}
+__device__ __forceinline__ int row16_incl_scan(int v) {
+    v += dpp_row<0x111>(v);  // row_shr:1
+    v += dpp_row<0x112>(v);
+    v += dpp_row<0x114>(v);
+    v += dpp_row<0x118>(v);
+    return v;
+}
+// how many of the row's other 15 lanes hold a smaller value (row_ror:1..15)
+template <int K = 1>
+__device__ __forceinline__ int row16_rank(int32_t v) {
+    int r = dpp_row<0x120 + K>(v) < v ? 1 : 0;
+    if constexpr (K < 15) r += row16_rank<K + 1>(v);
+    return r;
+}
+
+// One wavefront (= one 64-thread workgroup) per coarse row.  The products w_t * AP[i_t, :] of a group of entries of
+// the R row go to an LDS list in (R entry, AP slot) order; pass 1 collects the row's column set in an LDS hash set,
+// which is sorted with wave shuffles (lane l owns column l); pass 2 walks the list and every lane sums the products of
+// its column in list order.  A row of one group (the usual case) keeps its products in LDS between the passes.  Three
+// dependent round trips per group: R entry -> AP row length / slots.
+// This is one group of row I of R from entry t0 on, cut by galerkin_groups.h.  *take: the entries kept (at least one).
+__device__ __forceinline__ int galerkin_products(const GalerkinArgs &a, int64_t I, int t0, int remaining,
+                                                 const GalerkinCaps &caps, int32_t *lJ, double *lV, int *take) {
     const int lane = threadIdx.x;
+    const int cand = galerkin_group_candidates(remaining, caps);
     int32_t i = 0, len = 0;
     double w = 0.0;
-    if (lane < tn) {
+    if (lane < cand) {
         const int t = t0 + lane;
-        const int64_t rat = ((int64_t)(t >> 3) * rld + I) * 8 + (t & 7);
-        i = rcol[rat];
-        w = rval[rat];
-        len = aplen[i];
+        const int64_t rat = ((int64_t)(t >> 3) * a.rld + I) * 8 + (t & 7);
+        i = a.rcol[rat];
+        w = a.rval[rat];
+        len = a.aplen[i];
+        len = len < 0 ? 0 : (len > caps.products ? caps.products : len);  // (no input overflows the list)
     }
-    int np = 0;
-    int o = wave_excl_scan(len, &np);
+    int all = 0;
+    int o = wave_excl_scan(len, &all);
+    const int tk = __popcll(__ballot(galerkin_group_keeps(lane, cand, o + len, caps)));
+    if (lane >= tk) len = 0;
+    const int np = __shfl(o + len, tk - 1, 64);
     constexpr int INFL = 8;  // slots in flight (a row of A P has 9-13 entries on a grid: two dependent rounds instead of four)
     for (int32_t s0 = 0; s0 < len; s0 += INFL) {
         int32_t cj[INFL];
@@ -1121,8 +1167,8 @@ __device__ __forceinline__ int galerkin_products(int64_t ld, const int32_t *__re
 #pragma unroll
         for (int q = 0; q < INFL; ++q) {
             const int32_t s = s0 + q < len ? s0 + q : s0;
-            cj[q] = apcol[(int64_t)s * ld + i];
-            cv[q] = apval[(int64_t)s * ld + i];
+            cj[q] = a.apcol[(int64_t)s * a.ld + i];
+            cv[q] = a.apval[(int64_t)s * a.ld + i];
         }
 #pragma unroll
         for (int q = 0; q < INFL; ++q)
@@ -1135,43 +1181,31 @@ __device__ __forceinline__ int galerkin_products(int64_t ld, const int32_t *__re
     for (int p = lane + np; p < np + 72; p += 64) lJ[p] = -1;  // empty products behind the list (the accumulation
                                                               // loop reads whole segments of multiples of 8)
     __syncthreads();
+    *take = tk;
     return np;
 }
 
-// G: R entries per group (G * APW products fit in the LDS list)
+// one coarse row by the whole wavefront, its groups cut by `caps`
 // NUMERIC: the row's sorted column set is already in ccol / clen (same pattern as at the symbolic
 // setup): no hash set, no sort -- every lane takes its column and sums its products.
 template <bool NUMERIC>
-__global__ __launch_bounds__(64) void galerkin(int64_t ld, const int32_t *__restrict__ apcol,
-                                               const double *__restrict__ apval, const int32_t *__restrict__ aplen,
-                                               int64_t nc, int64_t rld, const int32_t *__restrict__ rcol,
-                                               const double *__restrict__ rval, const int32_t *__restrict__ rlen,
-                                               int64_t cld, int32_t *__restrict__ ccol, double *__restrict__ cval,
-                                               float *__restrict__ cvalf,
-                                               int32_t *__restrict__ clen, double *__restrict__ cdinv,
-                                               unsigned long long *__restrict__ stats, uint32_t *__restrict__ bstat,
-                                               int G, int pcap, int maxseg) {
-    extern __shared__ __attribute__((aligned(16))) char gsm[];
-    int32_t *set = reinterpret_cast<int32_t *>(gsm);         // [256]
-    double *lV = reinterpret_cast<double *>(gsm + 1024);     // [pcap]
-    int32_t *lJ = reinterpret_cast<int32_t *>(lV + pcap);    // [pcap]
+__device__ __forceinline__ void galerkin_row_wave(const GalerkinArgs &a, int64_t I, const GalerkinCaps &caps, int maxseg,
+                                                  int32_t *set, int32_t *lJ, double *lV, uint32_t &my_max,
+                                                  uint32_t &my_nnz, uint32_t &my_flags) {
     const int lane = threadIdx.x;
-    uint32_t my_max = 0, my_nnz = 0, my_flags = 0;
-    for (int64_t I = blockIdx.x; I < nc; I += gridDim.x) {
-        const int rl = rlen[I];
-        const int ngroups = (rl + G - 1) / G;
-        int np = 0;
-        int total = 0;
-        int32_t myJ = 0x7fffffff;
-        if constexpr (NUMERIC) {
-            total = clen[I];
-            if (lane < total) myJ = ccol[(int64_t)lane * cld + I];
-        } else {
+    const int rl = a.rlen[I];
+    int np = 0, take = 0, ngroups = 0;
+    int total = 0;
+    int32_t myJ = 0x7fffffff;
+    if constexpr (NUMERIC) {
+        total = a.clen[I];
+        if (lane < total) myJ = a.ccol[(int64_t)lane * a.cld + I];
+    } else {
         for (int k = lane; k < 256; k += 64) set[k] = -1;
         __syncthreads();
         // pass 1: the set of columns
-        for (int g = 0; g < ngroups; ++g) {
-            np = galerkin_products(ld, apcol, apval, aplen, rld, rcol, rval, I, g * G, min(G, rl - g * G), lJ, lV);
+        for (int t0 = 0; t0 < rl; t0 += take, ++ngroups) {
+            np = galerkin_products(a, I, t0, rl - t0, caps, lJ, lV, &take);
             for (int p = lane; p < np; p += 64) {
                 const int32_t J = lJ[p];
                 uint32_t hsh = ((uint32_t)J * 2654435761u) >> 24;
@@ -1215,226 +1249,25 @@ __global__ __launch_bounds__(64) void galerkin(int64_t ld, const int32_t *__rest
                 myJ = (lower == up) ? lo : hi;
             }
         }
-        }  // !NUMERIC
-        // pass 2: eight products per step, loaded unconditionally (a compare-then-load loop pays the
-        // LDS latency twice per product); + 0.0 for the others leaves the sum, and its order, unchanged.
-        // Every lane reading every product made the kernel LDS-bandwidth-bound (a wave-wide 8-byte read takes
-        // 4 cycles whether it is a broadcast or not: 1500 cycles per coarse row of 250 products, 336 us at 1e6
-        // nodes).  A row of at most 16 (32) columns is therefore summed by 4 (2) SEGMENTS of lanes: lane
-        // (seg, c) sums the products of column c in segment seg of the list -- a quarter (half) of the reads,
-        // four (two) addresses per read instruction -- and the partial sums are combined in a fixed order.
-        const int nseg = min(maxseg, total <= 16 ? 4 : (total <= 32 ? 2 : 1)), segw = 64 / nseg;
-        const int seg = lane / segw;
-        const int32_t segJ = __shfl(myJ, lane % segw, 64);  // (lane c < total holds column c)
-        double acc = 0.0;
-        for (int g = 0; g < ngroups; ++g) {
-            if (ngroups > 1 || NUMERIC)
-                np = galerkin_products(ld, apcol, apval, aplen, rld, rcol, rval, I, g * G, min(G, rl - g * G), lJ, lV);
-            int chunk = (((np + nseg - 1) / nseg) + 7) & ~7;
-            if (nseg > 1 && ((chunk >> 3) & 1) == 0) chunk += 8;  // an odd number of 64-byte lines between the segments' reads: fewer bank conflicts
-            // (nseg * chunk <= np + 64: behind the list there are empty products)
-            for (int p = seg * chunk; p < (seg + 1) * chunk; p += 8) {
-                int32_t j8[8];
-                double v8[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    j8[u] = lJ[p + u];
-                    v8[u] = lV[p + u];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc += j8[u] == segJ ? v8[u] : 0.0;
-            }
-            __syncthreads();
-        }
-        if (nseg == 4) {
-            const double a1 = __shfl(acc, lane + 16, 64), a2 = __shfl(acc, lane + 32, 64), a3 = __shfl(acc, lane + 48, 64);
-            acc = (acc + a1) + (a2 + a3);
-        } else if (nseg == 2) {
-            acc += __shfl(acc, lane + 32, 64);
-        }
-        if (lane >= total && lane < APAD) {  // zero padding: fixed-trip-count row loops (tail, unrolled kernels)
-            ccol[(int64_t)lane * cld + I] = (int32_t)I;
-            cval[(int64_t)lane * cld + I] = 0.0;
-            cvalf[(int64_t)lane * cld + I] = 0.0f;
-        }
-        if (lane < total) {
-            ccol[(int64_t)lane * cld + I] = myJ;
-            cval[(int64_t)lane * cld + I] = acc;
-            cvalf[(int64_t)lane * cld + I] = (float)acc;
-            if (myJ == (int32_t)I) {
-                if (!(acc > 0.0)) my_flags |= 4u;
-                cdinv[I] = acc > 0.0 ? 1.0 / acc : 1.0;
-            }
-        }
-        if (lane == 0) {
-            clen[I] = total;
-            my_max = (uint32_t)total > my_max ? (uint32_t)total : my_max;
-            my_nnz += (uint32_t)total;
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        bstat[blockIdx.x] = my_max;
-        bstat[BSTAT_MAX + blockIdx.x] = my_nnz;
-    }
-    if (my_flags & 1u) atomicOr(&stats[ST_OVERFLOW], 1ull);  // (rare)
-    if (my_flags & 4u) atomicOr(&stats[ST_BADDIAG], 1ull);
-}
-
-// ---- The same sums with groups cut at run time (NODAL_SA_GDYN) and four small coarse rows per wavefront
-// (NODAL_SA_GROWS).  galerkin_groups.h holds the rule and the capacities; the kernel above is what runs with both off.
-struct GalerkinArgs {
-    int64_t ld;
-    const int32_t *apcol;
-    const double *apval;
-    const int32_t *aplen;
-    int64_t nc, rld;
-    const int32_t *rcol;
-    const double *rval;
-    const int32_t *rlen;
-    int64_t cld;
-    int32_t *ccol;
-    double *cval;
-    float *cvalf;
-    int32_t *clen;
-    double *cdinv;
-};
-
-// lane exchanges within a row of 16 lanes (DPP: no LDS crossbar); lanes shifted in from outside the row read 0
-template <int CTRL>
-__device__ __forceinline__ int dpp_row(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-}
-__device__ __forceinline__ int row16_incl_scan(int v) {
-    v += dpp_row<0x111>(v);  // row_shr:1
-    v += dpp_row<0x112>(v);
-    v += dpp_row<0x114>(v);
-    v += dpp_row<0x118>(v);
-    return v;
-}
-// how many of the row's other 15 lanes hold a smaller value (row_ror:1..15)
-template <int K = 1>
-__device__ __forceinline__ int row16_rank(int32_t v) {
-    int r = dpp_row<0x120 + K>(v) < v ? 1 : 0;
-    if constexpr (K < 15) r += row16_rank<K + 1>(v);
-    return r;
-}
-
-// One group of row I of R from entry t0 on, cut by galerkin_groups.h: the products of the entries it keeps go to the
-// list as galerkin_products writes them.  *take: the entries kept (at least one).
-__device__ __forceinline__ int galerkin_products_dyn(const GalerkinArgs &a, int64_t I, int t0, int remaining,
-                                                     const GalerkinCaps &caps, int32_t *lJ, double *lV, int *take) {
-    const int lane = threadIdx.x;
-    const int cand = galerkin_group_candidates(remaining, caps);
-    int32_t i = 0, len = 0;
-    double w = 0.0;
-    if (lane < cand) {
-        const int t = t0 + lane;
-        const int64_t rat = ((int64_t)(t >> 3) * a.rld + I) * 8 + (t & 7);
-        i = a.rcol[rat];
-        w = a.rval[rat];
-        len = a.aplen[i];
-        len = len < 0 ? 0 : (len > caps.products ? caps.products : len);  // (no input overflows the list)
-    }
-    int all = 0;
-    int o = wave_excl_scan(len, &all);
-    const int tk = __popcll(__ballot(galerkin_group_keeps(lane, cand, o + len, caps)));
-    if (lane >= tk) len = 0;
-    const int np = __shfl(o + len, tk - 1, 64);
-    constexpr int INFL = 8;
-    for (int32_t s0 = 0; s0 < len; s0 += INFL) {
-        int32_t cj[INFL];
-        double cv[INFL];
-#pragma unroll
-        for (int q = 0; q < INFL; ++q) {
-            const int32_t s = s0 + q < len ? s0 + q : s0;
-            cj[q] = a.apcol[(int64_t)s * a.ld + i];
-            cv[q] = a.apval[(int64_t)s * a.ld + i];
-        }
-#pragma unroll
-        for (int q = 0; q < INFL; ++q)
-            if (s0 + q < len) {
-                lJ[o] = cj[q];
-                lV[o] = w * cv[q];
-                ++o;
-            }
-    }
-    for (int p = lane + np; p < np + 72; p += 64) lJ[p] = -1;
-    __syncthreads();
-    *take = tk;
-    return np;
-}
-
-// one coarse row by the whole wavefront: the kernel above with its groups cut by `caps`
-template <bool NUMERIC>
-__device__ __forceinline__ void galerkin_row_wave(const GalerkinArgs &a, int64_t I, const GalerkinCaps &caps, int maxseg,
-                                                  int32_t *set, int32_t *lJ, double *lV, uint32_t &my_max,
-                                                  uint32_t &my_nnz, uint32_t &my_flags) {
-    const int lane = threadIdx.x;
-    const int rl = a.rlen[I];
-    int np = 0, take = 0, ngroups = 0;
-    int total = 0;
-    int32_t myJ = 0x7fffffff;
-    if constexpr (NUMERIC) {
-        total = a.clen[I];
-        if (lane < total) myJ = a.ccol[(int64_t)lane * a.cld + I];
-    } else {
-        for (int k = lane; k < 256; k += 64) set[k] = -1;
-        __syncthreads();
-        for (int t0 = 0; t0 < rl; t0 += take, ++ngroups) {
-            np = galerkin_products_dyn(a, I, t0, rl - t0, caps, lJ, lV, &take);
-            for (int p = lane; p < np; p += 64) {
-                const int32_t J = lJ[p];
-                uint32_t hsh = ((uint32_t)J * 2654435761u) >> 24;
-                for (int probe = 0; probe < 256; ++probe) {
-                    const int32_t old = atomicCAS(&set[hsh], -1, J);
-                    if (old == -1 || old == J) break;
-                    hsh = (hsh + 1) & 255u;
-                    if (probe == 255) my_flags |= 1u;
-                }
-            }
-            __syncthreads();
-        }
-        int32_t mine[4];
-        int cnt = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            mine[q] = set[lane * 4 + q];
-            cnt += mine[q] >= 0 ? 1 : 0;
-        }
-        int off = wave_excl_scan(cnt, &total);
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (mine[q] >= 0) set[off++] = mine[q];
-        __syncthreads();
-        if (total > ACAP) {
-            my_flags |= 1u;
-            total = ACAP;
-        }
-        myJ = lane < total ? set[lane] : 0x7fffffff;
-        __syncthreads();
-#pragma unroll
-        for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const int32_t other = __shfl_xor(myJ, j, 64);
-                const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-                const int32_t lo = myJ < other ? myJ : other, hi = myJ < other ? other : myJ;
-                myJ = (lower == up) ? lo : hi;
-            }
-        }
     }
     const bool kept = !NUMERIC && ngroups == 1;  // the row's only group is still in the list
+    // pass 2: eight products per step, loaded unconditionally (a compare-then-load loop pays the
+    // LDS latency twice per product); + 0.0 for the others leaves the sum, and its order, unchanged.
+    // Every lane reading every product made the kernel LDS-bandwidth-bound (a wave-wide 8-byte read takes
+    // 4 cycles whether it is a broadcast or not: 1500 cycles per coarse row of 250 products, 336 us at 1e6
+    // nodes).  A row of at most 16 (32) columns is therefore summed by 4 (2) SEGMENTS of lanes: lane
+    // (seg, c) sums the products of column c in segment seg of the list -- a quarter (half) of the reads,
+    // four (two) addresses per read instruction -- and the partial sums are combined in a fixed order.
     const int nseg = min(maxseg, total <= 16 ? 4 : (total <= 32 ? 2 : 1)), segw = 64 / nseg;
     const int seg = lane / segw;
-    const int32_t segJ = __shfl(myJ, lane % segw, 64);
+    const int32_t segJ = __shfl(myJ, lane % segw, 64);  // (lane c < total holds column c)
     double acc = 0.0;
     for (int t0 = 0; t0 < rl; t0 += take) {
         if (kept) take = rl;
-        else np = galerkin_products_dyn(a, I, t0, rl - t0, caps, lJ, lV, &take);
+        else np = galerkin_products(a, I, t0, rl - t0, caps, lJ, lV, &take);
         int chunk = (((np + nseg - 1) / nseg) + 7) & ~7;
-        if (nseg > 1 && ((chunk >> 3) & 1) == 0) chunk += 8;
+        if (nseg > 1 && ((chunk >> 3) & 1) == 0) chunk += 8;  // an odd number of 64-byte lines between the segments' reads: fewer bank conflicts
+        // (nseg * chunk <= np + 64: behind the list there are empty products)
         for (int p = seg * chunk; p < (seg + 1) * chunk; p += 8) {
             int32_t j8[8];
             double v8[8];
@@ -1454,7 +1287,7 @@ __device__ __forceinline__ void galerkin_row_wave(const GalerkinArgs &a, int64_t
     } else if (nseg == 2) {
         acc += __shfl(acc, lane + 32, 64);
     }
-    if (lane >= total && lane < APAD) {
+    if (lane >= total && lane < APAD) {  // zero padding: fixed-trip-count row loops (tail, unrolled kernels)
         a.ccol[(int64_t)lane * a.cld + I] = (int32_t)I;
         a.cval[(int64_t)lane * a.cld + I] = 0.0;
         a.cvalf[(int64_t)lane * a.cld + I] = 0.0f;
@@ -1833,8 +1666,6 @@ int galerkin_product(nodal_ctx *h, SHierarchy *H, int l, hipEvent_t r_ready = nu
     // 8.80 -> 8.66 ms per fresh solve of the 1e6-node grid, 7.45 -> 7.22 ms with the patterns kept)
     static const int g_env = knob::SA_GG.now();
     if (g_env >= 8 && g_env <= 64 && apw == 16) G = g_env & ~7;
-    const int pcap = G * apw + 72;  // (the list is padded with empty products up to the segments' common length)
-    const size_t lds = 1024 + (size_t)pcap * 12;
     // (at most 16384 workgroups, each walking several rows: the one-workgroup fold of their statistics
     // reads 2 x 16384 words instead of 2 x 65536 -- 3 instead of 10 us)
     static const int64_t gcap = knob::SA_GCAP.now();
@@ -1843,35 +1674,24 @@ int galerkin_product(nodal_ctx *h, SHierarchy *H, int l, hipEvent_t r_ready = nu
     if (r_ready) NODAL_HIP_TRY(h, hipStreamWaitEvent(st, r_ready, 0));  // (R was built on the hierarchy's other stream)
     // NODAL_SA_GROWS: 16-slot levels take four small coarse rows per wavefront; NODAL_SA_GDYN: 64-slot levels cut their
     // groups by the products that fit a list of NODAL_SA_GLIST slots (at a 16-slot level G entries never fill the list:
-    // the groups stay).  Neither: the kernel and the groups of before.
+    // the groups stay).  Neither: one coarse row per wavefront, groups of G entries.
     static const bool grows = knob::SA_GROWS.now() != 0, gdyn = knob::SA_GDYN.now();
     static const int glist = knob::SA_GLIST.now();
     const bool shared = grows && apw == 16, dyn = gdyn && apw == 64;
-    if (shared || dyn) {
-        GalerkinCaps caps{G, 64, G * apw};
-        if (dyn) caps = GalerkinCaps{64, 64, (glist < apw ? apw : (glist > 1024 ? 1024 : glist)) & ~7};
-        int pc2 = caps.products + 72;
-        if (shared && pc2 < GALERKIN_SUB_ROWS * GALERKIN_SUB_STRIDE) pc2 = GALERKIN_SUB_ROWS * GALERKIN_SUB_STRIDE;
-        const size_t lds2 = 1024 + (size_t)pc2 * 12;
-        const int64_t units = shared ? (nc + GALERKIN_SUB_ROWS - 1) / GALERKIN_SUB_ROWS : nc;  // (a workgroup walks rows, or fours of rows)
-        const unsigned g2 = (unsigned)(units < (int64_t)gg ? units : (int64_t)gg);
-        const GalerkinArgs ga{ld, apcol, apval, aplen, nc, L->rld, L->rcol.as<int32_t>(), L->rval.as<double>(),
-                              L->rlen.as<int32_t>(), C->ld, C->acol.as<int32_t>(), C->aval.as<double>(),
-                              C->avalf.as<float>(), C->alen.as<int32_t>(), C->dinv.as<double>()};
-        unsigned long long *cst = dstats + (size_t)(l + 1) * ST_COUNT;
-        if (shared) galerkin_rows<NUMERIC, true><<<g2, 64, lds2, st>>>(ga, cst, H->bstat.as<uint32_t>(), caps, pc2, maxseg);
-        else galerkin_rows<NUMERIC, false><<<g2, 64, lds2, st>>>(ga, cst, H->bstat.as<uint32_t>(), caps, pc2, maxseg);
-        if (!NUMERIC) reduce_bstat<<<1, 1024, 0, st>>>((int)g2, H->bstat.as<uint32_t>(), cst, ST_MAXLEN, ST_NNZ);
-        NODAL_HIP_TRY(h, hipGetLastError());
-        return NODAL_OK;
-    }
-    galerkin<NUMERIC><<<gg, 64, lds, st>>>(
-        ld, apcol, apval, aplen, nc, L->rld, L->rcol.as<int32_t>(), L->rval.as<double>(), L->rlen.as<int32_t>(),
-        C->ld, C->acol.as<int32_t>(), C->aval.as<double>(), C->avalf.as<float>(), C->alen.as<int32_t>(),
-        C->dinv.as<double>(), dstats + (size_t)(l + 1) * ST_COUNT, H->bstat.as<uint32_t>(), G, pcap, maxseg);
-    if (!NUMERIC)
-        reduce_bstat<<<1, 1024, 0, st>>>((int)gg, H->bstat.as<uint32_t>(), dstats + (size_t)(l + 1) * ST_COUNT,
-                                         ST_MAXLEN, ST_NNZ);
+    GalerkinCaps caps{G, 64, G * apw};
+    if (dyn) caps = GalerkinCaps{64, 64, (glist < apw ? apw : (glist > 1024 ? 1024 : glist)) & ~7};
+    int pcap = caps.products + 72;  // (the list is padded with empty products up to the segments' common length)
+    if (shared && pcap < GALERKIN_SUB_ROWS * GALERKIN_SUB_STRIDE) pcap = GALERKIN_SUB_ROWS * GALERKIN_SUB_STRIDE;
+    const size_t lds = 1024 + (size_t)pcap * 12;
+    const int64_t units = shared ? (nc + GALERKIN_SUB_ROWS - 1) / GALERKIN_SUB_ROWS : nc;  // (a workgroup walks rows, or fours of rows)
+    const unsigned grid = (unsigned)(units < (int64_t)gg ? units : (int64_t)gg);
+    const GalerkinArgs ga{ld, apcol, apval, aplen, nc, L->rld, L->rcol.as<int32_t>(), L->rval.as<double>(),
+                          L->rlen.as<int32_t>(), C->ld, C->acol.as<int32_t>(), C->aval.as<double>(),
+                          C->avalf.as<float>(), C->alen.as<int32_t>(), C->dinv.as<double>()};
+    unsigned long long *cst = dstats + (size_t)(l + 1) * ST_COUNT;
+    if (shared) galerkin_rows<NUMERIC, true><<<grid, 64, lds, st>>>(ga, cst, H->bstat.as<uint32_t>(), caps, pcap, maxseg);
+    else galerkin_rows<NUMERIC, false><<<grid, 64, lds, st>>>(ga, cst, H->bstat.as<uint32_t>(), caps, pcap, maxseg);
+    if (!NUMERIC) reduce_bstat<<<1, 1024, 0, st>>>((int)grid, H->bstat.as<uint32_t>(), cst, ST_MAXLEN, ST_NNZ);
     NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }
@@ -2274,48 +2094,9 @@ int tail_apply(nodal_ctx *h, SHierarchy *H, const double *b, double *out) {
     return NODAL_OK;
 }
 
-// NODAL_TRACE with NODAL_SA_TAIL_CHECK=1: both forms of the tail applied to one fixed vector of both signs,
-// d = max_i |y_dense - y_cycle|_i / sum_j |T_ij| |b_j|; the dense product alone against the same product in long double
-int tail_self_check(nodal_ctx *h, SHierarchy *H) {
-    const int n = H->td.lv[0].n;
-    std::vector<double> b((size_t)n), yc((size_t)n), yd((size_t)n), T((size_t)n * n);
-    uint64_t seed = 0x9e3779b97f4a7c15ull;
-    for (int i = 0; i < n; ++i) {  // (splitmix64: uniform in (-1, 1))
-        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        z ^= z >> 31;
-        b[i] = (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
-    }
-    DevBuf v;
-    hipError_t e = v.reserve((size_t)3 * n * 8);
-    double *db = v.as<double>(), *dc = db + n, *dd = dc + n;
-    int rc = NODAL_OK;
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) rc = tail_walk(h, H, db, dc, 1);
-    if (e == hipSuccess && rc == NODAL_OK) rc = tail_apply<1>(h, H, db, dd);
-    if (e == hipSuccess && rc == NODAL_OK) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(yc.data(), dc, (size_t)n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(yd.data(), dd, (size_t)n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(T.data(), H->tail_op.p, (size_t)n * n * 8, hipMemcpyDeviceToHost);
-    v.release();
-    if (rc != NODAL_OK) return rc;
-    NODAL_HIP_TRY(h, e);
-    double d = 0.0, dp = 0.0;
-    for (int i = 0; i < n; ++i) {
-        long double y = 0.0L, a = 0.0L;
-        for (int j = 0; j < n; ++j) {
-            y += (long double)T[(size_t)i * n + j] * b[j];
-            a += fabsl((long double)T[(size_t)i * n + j] * b[j]);
-        }
-        const double den = (double)a;
-        const double q = fabs(yd[i] - yc[i]) / den, qp = (double)(fabsl((long double)yd[i] - y) / a);
-        d = !(q <= d) ? q : d;  // (a NaN stays)
-        dp = !(qp <= dp) ? qp : dp;
-    }
-    fprintf(stderr, "[sagg] tail check: n_t %d, dense operator against the cycle d = %.3e (product alone %.3e)\n", n, d, dp);
-    return NODAL_OK;
-}
+// (the self-checks stand in sagg_checks.h, behind the cycle they run)
+int tail_self_check(nodal_ctx *h, SHierarchy *H);
+int setup_self_checks(nodal_ctx *h, SHierarchy *H);
 
 // T behind the image (fresh setup and values-only refresh)
 int form_tail_op(nodal_ctx *h, SHierarchy *H) {
@@ -2503,87 +2284,6 @@ int build_visit(nodal_ctx *h, SHierarchy *H, bool general) {
     return NODAL_OK;
 }
 
-// NODAL_TRACE with NODAL_SA_FOLD_CHECK=1: per folded level both forms of the end of a visit -- k_prolong + k_post
-// against k_prolong_post -- on fixed vectors of both signs (x, b and the coarse correction uniform in (-1, 1), the
-// residual by k_smooth_residual as in the cycle).  Prints the level, its rows and
-//   d = max_i |m_fused - m_two|_i / (|x_i| + w dinv_i (|b_i| + sum_j |a_ij| |xp_j|) + sum_s |w_is| |e|),
-// and q = the largest d_i over the row's own bound (slots + width + 8) 2^-23 (operands stored f32, sums in f64).
-template <typename TC>
-int fold_check_level(nodal_ctx *h, SHierarchy *H, int l, bool two) {
-    hipStream_t st = h->stream;
-    const SLevel *L = H->pool[l];
-    const int64_t n = L->n, nc = H->pool[l + 1]->n;
-    const Ell A = L->A();
-    uint64_t seed = 0x9e3779b97f4a7c15ull + (uint64_t)l;
-    auto unit = [&]() {  // (splitmix64: uniform in (-1, 1))
-        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        z ^= z >> 31;
-        return (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
-    };
-    std::vector<cyc_t> hx((size_t)n), hb((size_t)n);
-    std::vector<TC> he((size_t)2 * nc);
-    for (auto &v : hx) v = (cyc_t)unit();
-    for (auto &v : hb) v = (cyc_t)unit();
-    for (auto &v : he) v = (TC)unit();
-    const double hcoef[2] = {0.9, 0.4};
-    const size_t vb = align256((size_t)n * sizeof(cyc_t)), eb = align256((size_t)nc * sizeof(TC)), db = align256((size_t)n * 8);
-    DevBuf buf;
-    hipError_t e = buf.reserve(6 * vb + 2 * eb + 2 * db + 256);
-    char *p = buf.as<char>();
-    cyc_t *x = reinterpret_cast<cyc_t *>(p), *b = reinterpret_cast<cyc_t *>(p + vb), *r = reinterpret_cast<cyc_t *>(p + 2 * vb),
-          *xp = reinterpret_cast<cyc_t *>(p + 3 * vb), *mt = reinterpret_cast<cyc_t *>(p + 4 * vb),
-          *mf = reinterpret_cast<cyc_t *>(p + 5 * vb);
-    TC *c1 = reinterpret_cast<TC *>(p + 6 * vb), *c2 = reinterpret_cast<TC *>(p + 6 * vb + eb);
-    double *d = reinterpret_cast<double *>(p + 6 * vb + 2 * eb), *q = reinterpret_cast<double *>(p + 6 * vb + 2 * eb + db);
-    double *coef = reinterpret_cast<double *>(p + 6 * vb + 2 * eb + 2 * db);
-    std::vector<double> hd((size_t)n), hq((size_t)n);
-    if (e == hipSuccess) e = hipMemcpyAsync(x, hx.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b, hb.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c1, he.data(), (size_t)nc * sizeof(TC), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(c2, he.data() + nc, (size_t)nc * sizeof(TC), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(coef, hcoef, sizeof hcoef, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        const unsigned g = grid_for(n), tb = L->wfix ? TB : TB * LPR_RAGGED;
-        const double *dinv = L->dinv.as<double>(), *cf = two ? coef : nullptr;
-        const int32_t *wcol = L->wcol.as<int32_t>(), *wlen = L->wlen.as<int32_t>();
-        const float *wval = L->wval.as<float>();
-        SAGG_DISPATCH_W(L->wfix, (k_smooth_residual<W, cyc_t><<<g, tb, 0, st>>>(A, b, x, r)));
-        k_prolong<TC><<<g, TB, 0, st>>>(n, L->ld, L->pcol.as<int32_t>(), L->pvalf.as<float>(), x, c1, two ? c2 : nullptr, cf, xp);
-        SAGG_DISPATCH_W(L->wfix, (k_post<W, false, cyc_t, cyc_t><<<g, tb, 0, st>>>(A, dinv, b, xp, mt, nullptr, nullptr, nullptr)));
-        k_prolong_post<TC, cyc_t><<<g, TB, 0, st>>>(n, L->ld, wcol, wval, wlen, x, r, dinv, c1, two ? c2 : nullptr, cf, mf);
-        k_fold_check<TC><<<g, TB, 0, st>>>(A, dinv, b, x, xp, wcol, wval, wlen, c1, two ? c2 : nullptr, cf, mt, mf, d, q);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(hd.data(), d, (size_t)n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hq.data(), q, (size_t)n * 8, hipMemcpyDeviceToHost);
-    buf.release();
-    NODAL_HIP_TRY(h, e);
-    double dm = 0.0, qm = 0.0;
-    for (int64_t i = 0; i < n; ++i) {
-        dm = !(hd[i] <= dm) ? hd[i] : dm;  // (a NaN stays)
-        qm = !(hq[i] <= qm) ? hq[i] : qm;
-    }
-    fprintf(stderr, "[sagg] fold check: level %d, rows %lld, slots %d, width %d, fused launch against the two d = %.3e "
-                    "(worst row against its own bound: %.3e)\n", l, (long long)n, (int)L->wslots, (int)L->maxlen, dm, qm);
-    return NODAL_OK;
-}
-int visit_self_check(nodal_ctx *h, SHierarchy *H);  // (behind cycle(), which it runs)
-int restrict_self_check(nodal_ctx *h, SHierarchy *H);  // (behind the cycle kernels it runs)
-int fold_self_check(nodal_ctx *h, SHierarchy *H) {
-    static const bool check = knob::TRACE.now() && knob::SA_FOLD_CHECK.now();
-    if (!check) return NODAL_OK;
-    for (int l = 0; l + 1 < H->nlev; ++l) {
-        if (!H->pool[l]->fold) continue;
-        const bool last = l + 1 == H->tail || l + 1 == H->nlev - 1;  // (as cycle() tells the two hand-overs apart)
-        if (last) NODAL_TRY(fold_check_level<double>(h, H, l, false));
-        else NODAL_TRY(fold_check_level<cyc_t>(h, H, l, true));
-    }
-    return NODAL_OK;
-}
-
 int build_tail(nodal_ctx *h, SHierarchy *H, const unsigned long long *hs) {
     H->tail = -1;
     H->tail_dense = false;
@@ -2749,9 +2449,7 @@ int sagg_refresh(nodal_ctx *h, SHierarchy *H, const int32_t *indptr0, const int3
     for (int k = 1; k < H->nlev; ++k)
         if (hs[(size_t)k * ST_COUNT + ST_BADDIAG] || hs[(size_t)k * ST_COUNT + ST_OVERFLOW]) return NODAL_OK;
     decide_folds(H, hs, false);
-    NODAL_TRY(fold_self_check(h, H));
-    NODAL_TRY(visit_self_check(h, H));
-    NODAL_TRY(restrict_self_check(h, H));
+    NODAL_TRY(setup_self_checks(h, H));
     *ok = true;
     return NODAL_OK;
 }
@@ -3004,9 +2702,7 @@ static int sagg_setup_csr_body(nodal_ctx *h, int64_t n0, int64_t nnz0, const int
                 H->dense_coarsest ? "dense" : "diagonal");
     }
     decide_folds(H, hs, trace);
-    NODAL_TRY(fold_self_check(h, H));
-    NODAL_TRY(visit_self_check(h, H));
-    NODAL_TRY(restrict_self_check(h, H));
+    NODAL_TRY(setup_self_checks(h, H));
     H->ready = true;
     *accepted = true;
     H->sym_valid = true;
@@ -3239,267 +2935,9 @@ __global__ void f_set_scalars(double *__restrict__ sc, double tol2) {
     sc[F_TOL2] = tol2;
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// NODAL_TRACE with NODAL_SA_VISIT_CHECK=1: the level that visits in three launches runs both forms of the visit on one
-// fixed right-hand side of both signs (b uniform in (-1, 1), x0 = w D^-1 b as its producer leaves it) and prints
-//   d = max_i |out_3 - out_6|_i / den_i,
-// den_i = the row-wise sum of the absolute terms that carry one f32 rounding each, formed on the host in fp64 from the
-// exported operators.  With e = 2^-24, |.| entrywise, |G| v = v + w D^-1 |A| v, and the exact operators (A, P in f64,
-// W = G P, P2 = G W) as the reference, the two forms leave it by (first order)
-//   six launches:  e_r = |r| + |A||x1|            (r rounded; the sweep reads the f32 copy of A)
-//                  e_c = |T| |P|^T (|r| + e_r)     (R = the f32 copy of P^T; T and its product are fp64)
-//                  e_xp = |xp| + w D^-1 e_r + |W||c| + |W| e_c
-//                  dev_6 = |out| + |G| e_xp + w D^-1 |A||xp|
-//   three:         e_x2 = |x2| + w D^-1 |A||x1|
-//                  E v = |P2| v + |G||W| v         (an entry of the stored P2: its own rounding and that of the W under it)
-//                  e_c' = |T| E^T |b|              (d2 holds P2's entries)
-//                  dev_3 = |out| + |G| e_x2 + w D^-1 |A||x2| + E |c| + |P2| e_c'
-// times e each (x1 is the same launch on the same operands in both forms: the same bits), so den = dev_6 + dev_3 and
-// d <= 2^-24 up to second-order terms and the fp64 sums (each over fewer than n + n_t terms, 2^-53 apiece: below 2^-36
-// of their absolute terms at 1e5 rows).  The per-row bound is therefore 2 x 2^-24 = 2^-23 whatever the slot counts: the
-// slots enter through den, every sum is fp64 and no rounding is per slot.  q = the largest d_i over 2^-23.
-int visit_check_level(nodal_ctx *h, SHierarchy *H, int l) {
-    hipStream_t st = h->stream;
-    SLevel *L = H->pool[l], *C = H->pool[l + 1];
-    const int64_t n = L->n, ld = L->ld, nt = C->n;
-    uint64_t seed = 0x9e3779b97f4a7c15ull + 977ull * (uint64_t)l;
-    auto unit = [&]() {  // (splitmix64: uniform in (-1, 1))
-        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        z ^= z >> 31;
-        return (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
-    };
-    std::vector<double> dinv((size_t)n), T((size_t)nt * nt), c6((size_t)nt), c3((size_t)nt);
-    std::vector<cyc_t> hb((size_t)n), hx0((size_t)n), x1((size_t)n), x2((size_t)n), r((size_t)n), xp((size_t)n),
-        o6((size_t)n), o3((size_t)n);
-    std::vector<int32_t> acol((size_t)L->width * ld), alen((size_t)n), pcol((size_t)PW * ld), wcol((size_t)L->wslots * ld),
-        wlen((size_t)n), p2col((size_t)P2CAP * ld), p2len((size_t)n);
-    std::vector<float> aval((size_t)L->width * ld), pval((size_t)PW * ld), wval((size_t)L->wslots * ld),
-        p2val((size_t)P2CAP * ld);
-    auto down = [&](void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
-    hipError_t e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = down(dinv.data(), L->dinv.p, (size_t)n * 8);
-    for (int64_t i = 0; i < n; ++i) {
-        hb[i] = (cyc_t)unit();
-        hx0[i] = (cyc_t)(OMEGA * dinv[i] * (double)hb[i]);
-    }
-    const size_t vb = align256((size_t)n * sizeof(cyc_t));
-    DevBuf buf;
-    if (e == hipSuccess) e = buf.reserve(4 * vb);
-    char *p = buf.as<char>();
-    cyc_t *b = reinterpret_cast<cyc_t *>(p), *x0 = reinterpret_cast<cyc_t *>(p + vb), *out6 = reinterpret_cast<cyc_t *>(p + 2 * vb),
-          *out3 = reinterpret_cast<cyc_t *>(p + 3 * vb);
-    if (e == hipSuccess) e = hipMemcpyAsync(b, hb.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(x0, hx0.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
-    int rc = NODAL_OK;
-    if (e == hipSuccess) {
-        L->visit = false;
-        rc = cycle<cyc_t, cyc_t>(h, H, l, b, x0, out6, nullptr);
-        L->visit = true;
-    }
-    if (e == hipSuccess && rc == NODAL_OK) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = down(r.data(), L->v<cyc_t>(V_R), (size_t)n * sizeof(cyc_t));
-    if (e == hipSuccess) e = down(xp.data(), L->v<cyc_t>(V_XP), (size_t)n * sizeof(cyc_t));
-    if (e == hipSuccess) e = down(c6.data(), C->v<double>(V_C1), (size_t)nt * 8);
-    if (e == hipSuccess && rc == NODAL_OK) rc = cycle<cyc_t, cyc_t>(h, H, l, b, x0, out3, nullptr);
-    if (e == hipSuccess && rc == NODAL_OK) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = down(x1.data(), L->v<cyc_t>(V_X1), (size_t)n * sizeof(cyc_t));
-    if (e == hipSuccess) e = down(x2.data(), L->v<cyc_t>(V_T), (size_t)n * sizeof(cyc_t));
-    if (e == hipSuccess) e = down(c3.data(), C->v<double>(V_C1), (size_t)nt * 8);
-    if (e == hipSuccess) e = down(o6.data(), out6, (size_t)n * sizeof(cyc_t));
-    if (e == hipSuccess) e = down(o3.data(), out3, (size_t)n * sizeof(cyc_t));
-    if (e == hipSuccess) e = down(acol.data(), L->acol.p, acol.size() * 4);
-    if (e == hipSuccess) e = down(aval.data(), L->avalf.p, aval.size() * 4);
-    if (e == hipSuccess) e = down(alen.data(), L->alen.p, (size_t)n * 4);
-    if (e == hipSuccess) e = down(pcol.data(), L->pcol.p, pcol.size() * 4);
-    if (e == hipSuccess) e = down(pval.data(), L->pvalf.p, pval.size() * 4);
-    if (e == hipSuccess) e = down(wcol.data(), L->wcol.p, wcol.size() * 4);
-    if (e == hipSuccess) e = down(wval.data(), L->wval.p, wval.size() * 4);
-    if (e == hipSuccess) e = down(wlen.data(), L->wlen.p, (size_t)n * 4);
-    if (e == hipSuccess) e = down(p2col.data(), L->p2col.p, p2col.size() * 4);
-    if (e == hipSuccess) e = down(p2val.data(), L->p2val.p, p2val.size() * 4);
-    if (e == hipSuccess) e = down(p2len.data(), L->p2len.p, (size_t)n * 4);
-    if (e == hipSuccess) e = down(T.data(), H->tail_op.p, (size_t)nt * nt * 8);
-    buf.release();
-    if (rc != NODAL_OK) return rc;
-    NODAL_HIP_TRY(h, e);
-    using Vec = std::vector<double>;
-    auto absv = [](const auto &v) { Vec y(v.size()); for (size_t i = 0; i < v.size(); ++i) y[i] = fabs((double)v[i]); return y; };
-    auto add = [](Vec a, const Vec &b2) { for (size_t i = 0; i < a.size(); ++i) a[i] += b2[i]; return a; };
-    auto wd = [&](Vec v) { for (int64_t i = 0; i < n; ++i) v[i] *= OMEGA * dinv[i]; return v; };
-    auto absA = [&](const Vec &v) {
-        Vec y((size_t)n, 0.0);
-        for (int64_t i = 0; i < n; ++i)
-            for (int32_t s = 0; s < alen[i]; ++s) y[i] += fabs((double)aval[(size_t)s * ld + i]) * v[acol[(size_t)s * ld + i]];
-        return y;
-    };
-    auto absG = [&](const Vec &v) { return add(v, wd(absA(v))); };
-    auto absGT = [&](const Vec &v) { return add(v, absA(wd(v))); };  // (|a_ij| = |a_ji|)
-    // a column-major ELL operator n x n_t (slots, cols, vals, per-row length or -1 entries): |M| v and |M|^T v
-    auto ell = [&](int slots, const std::vector<int32_t> &col, const std::vector<float> &val, const std::vector<int32_t> *len,
-                   const Vec &v, bool transposed) {
-        Vec y((size_t)(transposed ? nt : n), 0.0);
-        for (int64_t i = 0; i < n; ++i) {
-            const int32_t m = len ? (*len)[i] : slots;
-            for (int32_t s = 0; s < m; ++s) {
-                const int32_t J = col[(size_t)s * ld + i];
-                if (J < 0) continue;
-                const double a = fabs((double)val[(size_t)s * ld + i]);
-                if (transposed) y[J] += a * v[i];
-                else y[i] += a * v[J];
-            }
-        }
-        return y;
-    };
-    auto absT = [&](const Vec &v) {
-        Vec y((size_t)nt, 0.0);
-        for (int64_t i = 0; i < nt; ++i)
-            for (int64_t j = 0; j < nt; ++j) y[i] += fabs(T[(size_t)i * nt + j]) * v[j];
-        return y;
-    };
-    auto Pt = [&](const Vec &v) { return ell(PW, pcol, pval, nullptr, v, true); };
-    auto Wm = [&](const Vec &v) { return ell(L->wslots, wcol, wval, &wlen, v, false); };
-    auto Wt = [&](const Vec &v) { return ell(L->wslots, wcol, wval, &wlen, v, true); };
-    auto P2m = [&](const Vec &v) { return ell(P2CAP, p2col, p2val, &p2len, v, false); };
-    auto P2t = [&](const Vec &v) { return ell(P2CAP, p2col, p2val, &p2len, v, true); };
-    const Vec ax1 = absA(absv(x1));
-    const Vec e_r = add(absv(r), ax1);
-    const Vec e_c6 = absT(Pt(add(absv(r), e_r)));
-    const Vec e_xp = add(add(absv(xp), wd(e_r)), add(Wm(absv(c6)), Wm(e_c6)));
-    const Vec dev6 = add(add(absv(o6), absG(e_xp)), wd(absA(absv(xp))));
-    const Vec e_x2 = add(absv(x2), wd(ax1));
-    const Vec e_c3 = absT(add(P2t(absv(hb)), Wt(absGT(absv(hb)))));
-    const Vec ac3 = absv(c3);
-    const Vec dev3 = add(add(add(absv(o3), absG(e_x2)), wd(absA(absv(x2)))), add(add(P2m(ac3), absG(Wm(ac3))), P2m(e_c3)));
-    double dm = 0.0;
-    int maxp2 = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const double di = fabs((double)o3[i] - (double)o6[i]) / (dev6[i] + dev3[i]);  // (0 / 0: a NaN, which the maximum keeps)
-        dm = !(di <= dm) ? di : dm;
-        maxp2 = p2len[i] > maxp2 ? p2len[i] : maxp2;
-    }
-    fprintf(stderr, "[sagg] visit check: level %d, rows %lld, n_t %lld, longest P2 row %d, three launches against the six "
-                    "d = %.3e (against the bound 2^-23: %.3e)\n", l, (long long)n, (long long)nt, maxp2, dm, dm / 0x1p-23);
-    return NODAL_OK;
-}
-// NODAL_TRACE with NODAL_SA_RESTRICT_CHECK=1: every level that restricts from b forms rc both ways on one fixed
-// right-hand side of both signs (b uniform in (-1, 1), x0 = w D^-1 b as its producer leaves it) and prints
-//   d = max_I |rc_new - rc_old|_I / den_I,   den_I = sum_i |R_Ii| (|b_i| + sum_j |a_ij| |x0_j|) + sum_i |W_iI| |b_i|,
-// den formed on the host in fp64 from the operators as stored.  Against the exact rc (A, P in f64, W = G P) the two
-// launches carry the f32 roundings of x0, of the copies of A and of R and of r as stored -- each at most 2^-24 of a
-// term of the first sum --, the one launch that of the stored W, 2^-24 of a term of the second; every sum is fp64.  The
-// roundings are of either sign and do not add up in practice: the bar is 2^-23 as for the visit check above (measured:
-// tests/test_gpu_restrict_from_b.py).
-template <typename TO>
-int restrict_check_level(nodal_ctx *h, SHierarchy *H, int l) {
-    hipStream_t st = h->stream;
-    SLevel *L = H->pool[l], *C = H->pool[l + 1];
-    const int64_t n = L->n, ld = L->ld, nc = C->n, rld = L->rld;
-    uint64_t seed = 0x9e3779b97f4a7c15ull + 1297ull * (uint64_t)l;
-    auto unit = [&]() {  // (splitmix64: uniform in (-1, 1))
-        uint64_t z = (seed += 0x9e3779b97f4a7c15ull);
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        z ^= z >> 31;
-        return (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
-    };
-    const int64_t rslots = (int64_t)rcap_for(nc) * rld;
-    std::vector<double> dinv((size_t)n);
-    std::vector<cyc_t> hb((size_t)n), hx0((size_t)n);
-    std::vector<TO> rc_old((size_t)nc), rc_new((size_t)nc);
-    std::vector<int32_t> acol((size_t)L->width * ld), alen((size_t)n), rcol((size_t)rslots), rlen((size_t)nc),
-        wcol((size_t)L->wslots * ld), wlen((size_t)n);
-    std::vector<float> aval((size_t)L->width * ld), rval((size_t)rslots), wval((size_t)L->wslots * ld);
-    auto down = [&](void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); };
-    hipError_t e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = down(dinv.data(), L->dinv.p, (size_t)n * 8);
-    for (int64_t i = 0; i < n; ++i) {
-        hb[i] = (cyc_t)unit();
-        hx0[i] = (cyc_t)(OMEGA * dinv[i] * (double)hb[i]);
-    }
-    const size_t vb = align256((size_t)n * sizeof(cyc_t)), cb = align256((size_t)nc * sizeof(TO));
-    DevBuf buf;
-    if (e == hipSuccess) e = buf.reserve(3 * vb + 2 * cb);
-    char *p = buf.as<char>();
-    cyc_t *b = reinterpret_cast<cyc_t *>(p), *x0 = reinterpret_cast<cyc_t *>(p + vb), *r = reinterpret_cast<cyc_t *>(p + 2 * vb);
-    TO *ro = reinterpret_cast<TO *>(p + 3 * vb), *rn = reinterpret_cast<TO *>(p + 3 * vb + cb);
-    if (e == hipSuccess) e = hipMemcpyAsync(b, hb.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(x0, hx0.data(), (size_t)n * sizeof(cyc_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        const Ell A = L->A();
-        const unsigned g = grid_for(n);
-        const unsigned rblocks = restrict_blocks(nc);
-        SAGG_DISPATCH_W(L->wfix, (k_smooth_residual<W, cyc_t><<<g, TB, 0, st>>>(A, b, x0, r)));
-        k_restrict<TO><<<grid_for(nc * RL), TB, 0, st>>>(nc, rld, L->rcol.as<int32_t>(), L->rvalf.as<float>(),
-                                                        L->rlen.as<int32_t>(), r, ro, C->dinv.as<double>(), nullptr);
-        SAGG_DISPATCH_W(L->wfix, (k_residual_restrict<W, TO><<<rblocks + g, TB, 0, st>>>(
-                                     A, b, x0, r, rblocks, nc, L->wtstart.as<uint32_t>(), L->wtcol.as<int32_t>(),
-                                     L->wtval.as<float>(), rn, C->dinv.as<double>(), nullptr)));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = down(rc_old.data(), ro, (size_t)nc * sizeof(TO));
-    if (e == hipSuccess) e = down(rc_new.data(), rn, (size_t)nc * sizeof(TO));
-    if (e == hipSuccess) e = down(acol.data(), L->acol.p, acol.size() * 4);
-    if (e == hipSuccess) e = down(aval.data(), L->avalf.p, aval.size() * 4);
-    if (e == hipSuccess) e = down(alen.data(), L->alen.p, (size_t)n * 4);
-    if (e == hipSuccess) e = down(rcol.data(), L->rcol.p, rcol.size() * 4);
-    if (e == hipSuccess) e = down(rval.data(), L->rvalf.p, rval.size() * 4);
-    if (e == hipSuccess) e = down(rlen.data(), L->rlen.p, (size_t)nc * 4);
-    if (e == hipSuccess) e = down(wcol.data(), L->wcol.p, wcol.size() * 4);
-    if (e == hipSuccess) e = down(wval.data(), L->wval.p, wval.size() * 4);
-    if (e == hipSuccess) e = down(wlen.data(), L->wlen.p, (size_t)n * 4);
-    buf.release();
-    NODAL_HIP_TRY(h, e);
-    std::vector<double> t((size_t)n), den((size_t)nc, 0.0);
-    for (int64_t i = 0; i < n; ++i) {  // |b_i| + sum_j |a_ij| |x0_j|
-        double s = fabs((double)hb[i]);
-        for (int32_t q = 0; q < alen[i]; ++q)
-            s += fabs((double)aval[(size_t)q * ld + i]) * fabs((double)hx0[acol[(size_t)q * ld + i]]);
-        t[i] = s;
-    }
-    for (int64_t I = 0; I < nc; ++I)
-        for (int32_t q = 0; q < rlen[I]; ++q) {
-            const size_t at = ((size_t)(q >> 3) * rld + I) * 8 + (q & 7);
-            den[I] += fabs((double)rval[at]) * t[rcol[at]];
-        }
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t q = 0; q < wlen[i]; ++q)
-            den[wcol[(size_t)q * ld + i]] += fabs((double)wval[(size_t)q * ld + i]) * fabs((double)hb[i]);
-    double dm = 0.0;
-    for (int64_t I = 0; I < nc; ++I) {
-        const double di = fabs((double)rc_new[I] - (double)rc_old[I]) / den[I];  // (0 / 0: a NaN, which the maximum keeps)
-        dm = !(di <= dm) ? di : dm;
-    }
-    fprintf(stderr, "[sagg] restrict check: level %d, rows %lld, coarse rows %lld, rc from b against the two launches "
-                    "d = %.3e (against the bound 2^-23: %.3e)\n", l, (long long)n, (long long)nc, dm, dm / 0x1p-23);
-    return NODAL_OK;
-}
-int restrict_self_check(nodal_ctx *h, SHierarchy *H) {
-    static const bool check = knob::TRACE.now() && knob::SA_RESTRICT_CHECK.now();
-    if (!check) return NODAL_OK;
-    for (int l = 1; l + 1 < H->nlev; ++l) {
-        if (!H->pool[l]->restrict_b) continue;
-        const bool last = l + 1 == H->tail || l + 1 == H->nlev - 1;  // (as cycle() tells the two forms apart)
-        if (last) NODAL_TRY(restrict_check_level<double>(h, H, l));
-        else NODAL_TRY(restrict_check_level<cyc_t>(h, H, l));
-    }
-    return NODAL_OK;
-}
-
-int visit_self_check(nodal_ctx *h, SHierarchy *H) {
-    static const bool check = knob::TRACE.now() && knob::SA_VISIT_CHECK.now();
-    if (!check) return NODAL_OK;
-    for (int l = 1; l + 1 < H->nlev; ++l) {
-        const SLevel *L = H->pool[l];
-        if (L->visit && l + 1 == H->tail && H->tail_dense && H->nu[l < 2 ? l : 2] == 2) NODAL_TRY(visit_check_level(h, H, l));
-    }
-    return NODAL_OK;
-}
-
 }  // namespace
+
+#include "sagg_checks.h"
 
 // z ~= A^-1 r with one cycle of the hierarchy built by sagg_setup_csr (the preconditioner of the
 // general path's FGMRES, sparse_general.hip)
@@ -3682,7 +3120,7 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
     H->klevels = knob::SA_KLEVELS.now();
     apply_nu_knob(H);
 
-    const size_t vec = align_up((size_t)n * 8);
+    const size_t vec = align256((size_t)n * 8);
     NODAL_HIP_TRY(h, h->solver.reserve(6 * vec + 4 * MAX_PARTIALS * 8 + F_COUNT * 8 + 256));
     char *base = h->solver.as<char>();
     SolveBufs sb;

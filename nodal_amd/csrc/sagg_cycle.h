@@ -417,36 +417,6 @@ __global__ __launch_bounds__(TB) void k_prolong_post(int64_t n, int64_t ld, cons
     }
 }
 
-// NODAL_SA_FOLD_CHECK (sagg.hip, fold_self_check): per row the difference of the two forms over the sum of the
-// magnitudes that enter either of them, d[i], and the same over the row's own bound (slots + width + 8) 2^-23, q[i]
-template <typename TC>
-__global__ __launch_bounds__(TB) void k_fold_check(Ell A, const double *__restrict__ dinv, const cyc_t *__restrict__ b,
-                                                   const cyc_t *__restrict__ x, const cyc_t *__restrict__ xp,
-                                                   const int32_t *__restrict__ wcol, const float *__restrict__ wval,
-                                                   const int32_t *__restrict__ wlen, const TC *__restrict__ c1,
-                                                   const TC *__restrict__ c2, const double *__restrict__ coef,
-                                                   const cyc_t *__restrict__ m_two, const cyc_t *__restrict__ m_fused,
-                                                   double *__restrict__ d, double *__restrict__ q) {
-    const bool two = coef != nullptr;
-    const double s1 = two ? coef[0] : 1.0, s2 = two ? coef[1] : 0.0;
-    for (int64_t i = (int64_t)xcd_block() * TB + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * TB) {
-        double ax = 0.0, we = 0.0;
-        const int32_t la = A.len[i], lw = wlen[i];
-        for (int32_t s = 0; s < la; ++s)
-            ax += fabs((double)A.valf[(int64_t)s * A.ld + i]) * fabs((double)xp[A.col[(int64_t)s * A.ld + i]]);
-        for (int32_t s = 0; s < lw; ++s) {
-            const int32_t j = wcol[(int64_t)s * A.ld + i];
-            const double e = two ? s1 * (double)c1[j] + s2 * (double)c2[j] : (double)c1[j];
-            we += fabs((double)wval[(int64_t)s * A.ld + i]) * fabs(e);
-        }
-        const double den = fabs((double)x[i]) + OMEGA * dinv[i] * (fabs((double)b[i]) + ax) + we;
-        const double diff = fabs((double)m_fused[i] - (double)m_two[i]);
-        const double di = diff / den;  // (0 / 0: a NaN, which the host's maximum keeps)
-        d[i] = di;
-        q[i] = di / ((double)(lw + la + 8) * 0x1p-23);
-    }
-}
-
 // v = A c and the partial dot products c.v, c.u1 (and c.u2 when given)
 template <int W>
 __global__ __launch_bounds__(TB * RowLanes<W>::value) void k_spmv_dots(Ell A, const cyc_t *__restrict__ c, cyc_t *__restrict__ v,

@@ -160,7 +160,7 @@ def test_exported_p2_and_its_dense_transpose(runs, shape):
 @pytest.mark.parametrize("shape", FOLDING)
 def test_self_check_is_under_its_bound(runs, shape):
     """NODAL_TRACE with NODAL_SA_VISIT_CHECK=1: d = max_i |out_3 - out_6|_i over the row's sum of the absolute terms
-    that carry one f32 rounding each; the derivation next to visit_check_level (csrc/sagg.hip) gives d <= 2^-24 to first
+    that carry one f32 rounding each; the derivation next to visit_check_level (csrc/sagg_checks.h) gives d <= 2^-24 to first
     order and 2^-23 as the bound, whatever the slot counts (every sum is fp64)."""
     checks = [m for m in map(CHECK.search, runs["fold"][shape][3]) if m]
     assert checks, runs["fold"][shape][3][-6:]

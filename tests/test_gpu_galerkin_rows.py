@@ -145,8 +145,8 @@ def run_child(args, env):
 @pytest.mark.parametrize("setting", list(SETTINGS))
 def test_knob_settings_in_child_processes(exported, setting, tmp_path):
     """Every setting passes the reference (the child runs check_hierarchy itself).  NODAL_SA_GCAP=64: another grid, every
-    byte the same.  Both knobs at 0: the parent's kernels -- the same patterns, and values within twice the reference's
-    Galerkin bound of the default's (each is within the bound of the exact product)."""
+    byte the same.  Both knobs at 0: one coarse row per wavefront, fixed groups -- the same patterns, and values within
+    twice the reference's Galerkin bound of the default's (each is within the bound of the exact product)."""
     out = str(tmp_path / "export.npz")
     report = run_child([out, *CHILD_SHAPES], SETTINGS[setting])
     print(setting, {s: (r["sizes"], {k: f"{v:.3g}" for k, v in r["stats"].items()}) for s, r in report.items()})

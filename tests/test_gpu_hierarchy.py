@@ -105,8 +105,8 @@ def test_values_only_refresh():
     (refreshed = 1) that leave every pattern as it was; the second passes the reference for the second member's values
     (no stale value anywhere), and the third agrees with the FRESH setup of the same values, the first export --
     patterns, pval and rval bit for bit (same kernels, same inputs; r_refresh against r_to_ell), and the coarse
-    matrices with their dinv bit for bit as well: galerkin<true> sums a row's products in the list order of
-    galerkin<false>, and on MI355X the two gave the same bits on every level, which is therefore what is asserted
+    matrices with their dinv bit for bit as well: galerkin_rows<true, .> sums a row's products in the list order of
+    galerkin_rows<false, .>, and on MI355X the two gave the same bits on every level, which is therefore what is asserted
     (the Galerkin bound against the reference holds for both through check_hierarchy).
 
     The refresh is not compared level by level with a fresh handle set up on the second member's values alone: the

@@ -188,7 +188,7 @@ def test_values_only_refresh(runs):
 @pytest.mark.parametrize("shape", CHOSEN_SHAPES + ["refresh100"])
 def test_self_check_is_under_its_bound(runs, setting, shape):
     """NODAL_TRACE with NODAL_SA_RESTRICT_CHECK=1: d = max_I |rc_new - rc_old|_I over the coarse row's sum of absolute
-    terms (derivation beside restrict_check_level, csrc/sagg.hip); one line per setup or refresh."""
+    terms (derivation beside restrict_check_level, csrc/sagg_checks.h); one line per setup or refresh."""
     run = runs[setting][shape]
     checks = [m for m in map(CHECK.search, run["trace"]) if m]
     assert len(checks) == len(run["its"]), run["trace"][-8:]
