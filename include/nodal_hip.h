@@ -705,6 +705,33 @@ enum {
 int nodal_debug_hierarchy_info(nodal_handle h, int32_t *nlev, int64_t *ints /* [12][16] */, double *reals /* [12][2] */);
 int nodal_debug_hierarchy_array(nodal_handle h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes,
                                 int64_t *bytes_out);
+/* ONE application of the multigrid cycle (csrc/sagg.hip cycle(), csrc/sagg_multi.h m_cycle()) to the caller's vector,
+ * with no Krylov step behind it: what tests/cycle_reference.py states in numpy and tests/test_gpu_cycle.py compares.
+ * The hierarchy is the one nodal_debug_hierarchy_info finds, as the last solve left it (sweep counts and K-cycle
+ * switches included: no knob is read here); vectors have level 0's n entries (ints[0] of that call).
+ * mode 0: the general route's call -- the start iterate w D^-1 r, then the cycle from f64 r to f64 z.
+ * mode 1: the flexible CG's call -- the same cycle with f32 z (returned widened), whose last sweep also leaves the
+ *   partial sums of z.r and z.u; dots_out[2] = those arrays summed in the order the iteration sums them.  A level 0
+ *   with one sweep per side keeps its unfolded launches in this mode.
+ * mode 2: the block iteration's call on sixteen columns interleaved by row, element (i, y) of r, u and z at
+ *   [i * 16 + y]; dots_out[2][16] = the block's totals of z.r and z.u per column.  The block cycle runs at most two
+ *   sweeps per side (a count of three from NODAL_SA_NU gives two) and folds nothing.
+ * u: required in modes 1 and 2 (it stands where the iteration keeps A p), ignored in mode 0.
+ * frozen == NULL: an adaptive K-cycle that leaves no sample.  Otherwise the caller's (s1, s2, t) -- three doubles,
+ *   [16][3] in mode 2 -- are written where the frozen launches read them and the cycle runs frozen: r2 = rc - t A_c c1,
+ *   correction P (s1 c1 + s2 c2); that cycle is linear in r.  Ignored where level 0 does not hand over through the
+ *   K-cycle (params_out[10] says whether it was used).
+ * params_out[16]: what the call ran with -- 0..2 sweeps at level 0 / 1 / deeper, 3 the tail's sweeps, 4 kcycle,
+ *   5 klevels, 6 tail (first level inside the tail, -1 none), 7 tail_dense, 8 nlev, 9 level 0 took the folded
+ *   prolongation in this mode, 10 frozen coefficients used, 11 the block's columns (16), 12 / 13 / 14 bit l: level l
+ *   folds its first post-smoothing sweep / restricts from its right-hand side / visits in three launches, 15 the
+ *   hierarchy was set up by the general route.
+ * NODAL_E_INVALID: no ready hierarchy, an unknown mode, a missing u, or a hierarchy without a level outside the tail
+ *   (where the block driver declines as well).  Host vectors; scratch of its own or the cycle's; launches no kernel a
+ *   solve does not launch.  Leaves solution, right-hand side, table, hierarchy arrays, factorisations and the K-cycle's
+ *   calibration state as it found them: a solve after it returns the bits of the same solve without it. */
+int nodal_debug_cycle_apply(nodal_handle h, int32_t mode, const double *r, const double *u, const double *frozen,
+                            double *z, double *dots_out /* [2] or [2][16] */, int32_t *params_out /* [16] */);
 
 #ifdef __cplusplus
 }

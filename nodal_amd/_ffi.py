@@ -91,6 +91,7 @@ SIGNATURES = {
     "nodal_debug_direct_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p, _i64p, _i32p]),
     "nodal_debug_hierarchy_info": (C.c_int, [C.c_void_p, _i32p, _i64p, _f64p]),
     "nodal_debug_hierarchy_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
+    "nodal_debug_cycle_apply": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
 }
 
 # nodal_debug_hierarchy_array: `which` in the header's order (NODAL_HA_*) with the item type of each buffer, and the
@@ -104,6 +105,10 @@ HIERARCHY_ARRAYS = (("acol", np.int32), ("aval", np.float64), ("avalf", np.float
                     ("wtsrc", np.int32))
 HIERARCHY_INFO = ("n", "ld", "nc", "width", "maxlen", "wfix", "nnz", "rld", "rcap", "wslots", "fold_want", "fold", "d16",
                   "in_tail", "refreshed", "dense_coarsest")
+
+# nodal_debug_cycle_apply: the sixteen words of params_out
+CYCLE_PARAMS = ("nu0", "nu1", "nu2", "tail_nu", "kcycle", "klevels", "tail", "tail_dense", "nlev", "fold0", "frozen",
+                "columns", "fold_mask", "restrict_mask", "visit_mask", "general")
 
 # csrc/galerkin_groups.h: what a coarse row may have to share a wavefront with three others in the Galerkin sums
 # (tests/test_galerkin_groups_host.py holds these against the header)
@@ -747,6 +752,31 @@ class Handle:
             levels.append(lv)
         levels[-1]["coarse_inv"] = fetch(-1, 0, np.float64)
         return levels
+
+    def debug_cycle_apply(self, r, mode=0, u=None, frozen=None):
+        """z = ONE application of the multigrid cycle to r, nothing behind it (testing hook; nodal_hip.h).  mode 0: the
+        general route's call; 1: the flexible CG's (z stored in f32); 2: the block cycle, r [n0, 16].  u (modes 1, 2;
+        zeros when not given) stands where the iteration keeps A p.  frozen: (s1, s2, t), [16, 3] in mode 2, for a
+        frozen K-cycle; None: adaptive.  Returns (z, dots, params): dots None / [2] / [2, 16] = z.r and z.u as the
+        device summed them, params a dict of CYCLE_PARAMS."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.ndim == (2 if mode == 2 else 1) and (mode != 2 or r.shape[1] == 16), (r.shape, mode)
+        if u is None and mode != 0:
+            u = np.zeros_like(r)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            assert u.shape == r.shape, (u.shape, r.shape)
+        if frozen is not None:
+            frozen = np.ascontiguousarray(frozen, dtype=np.float64)
+            assert frozen.shape == ((16, 3) if mode == 2 else (3,)), frozen.shape
+        z = np.full(r.shape, np.nan, dtype=np.float64)
+        dots = np.full((2, 16) if mode == 2 else 2, np.nan, dtype=np.float64)
+        params = np.zeros(16, dtype=np.int32)
+        self._check(self.lib.nodal_debug_cycle_apply(self._h, mode, _ptr(r, C.c_double),
+                                                     _ptr(u, C.c_double) if u is not None else None,
+                                                     _ptr(frozen, C.c_double) if frozen is not None else None,
+                                                     _ptr(z, C.c_double), _ptr(dots, C.c_double), _ptr(params, C.c_int32)))
+        return z, (None if mode == 0 else dots), {name: int(params[k]) for k, name in enumerate(CYCLE_PARAMS)}
 
     def download_x(self):
         x = host_empty(self.n, np.float64)

@@ -1122,6 +1122,14 @@ int nodal_debug_hierarchy_array(nodal_handle h, int32_t level, int32_t which, vo
     return sagg_debug_array(h, level, which, dst, capacity_bytes, bytes_out);
 }
 
+int nodal_debug_cycle_apply(nodal_handle h, int32_t mode, const double *r, const double *u, const double *frozen,
+                            double *z, double *dots_out, int32_t *params_out) {
+    if (!h || !r || !z) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return sagg_debug_cycle_apply(h, mode, r, u, frozen, z, dots_out, params_out);
+}
+
 int nodal_residual(nodal_handle h, double *scaled_residual) {
     if (!h || !scaled_residual) return NODAL_E_INVALID;
     DeviceGuard g(h);

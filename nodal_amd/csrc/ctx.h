@@ -261,7 +261,8 @@ struct nodal_ctx {
     // gradient sums until they go down
     DevBuf ag_spec, ag_vec, ag_out;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
-    DevBuf dbg_apply;  // testing hook nodal_debug_direct_apply: the caller's r | z, nothing else lives here
+    DevBuf dbg_apply;  // testing hooks nodal_debug_direct_apply / nodal_debug_cycle_apply: the caller's vectors during
+                       // the call, nothing else lives here
     // exact elimination of nodes with <= 2 neighbours (lowdeg.hip): the reduced network is a
     // matrix-only context (no component table) that inherits the grounded-node flags
     nodal_ctx *lowdeg = nullptr;
@@ -770,6 +771,9 @@ int sagg_levels(nodal_ctx *h);
 // testing hooks (nodal_debug_hierarchy_info / nodal_debug_hierarchy_array): the hierarchy's sizes and raw device buffers
 int sagg_debug_info(nodal_ctx *h, int32_t *nlev, int64_t *ints, double *reals);
 int sagg_debug_array(nodal_ctx *h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
+// testing hook (nodal_debug_cycle_apply): one application of the hierarchy's cycle to host vectors, nothing behind it
+int sagg_debug_cycle_apply(nodal_ctx *h, int32_t mode, const double *r, const double *u, const double *frozen, double *z,
+                           double *dots_out, int32_t *params_out);
 int sagg_spmv(nodal_ctx *h, const double *x, double *y, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);  // y = A x on the hierarchy's own (level-0, ELL) matrix
 int amg_has_floating_component(nodal_ctx *h, const uint8_t *grounded0, int32_t *floating);
 int csr_has_floating_component(nodal_ctx *h, const uint8_t *grounded, int32_t *floating);

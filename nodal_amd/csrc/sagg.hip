@@ -3059,17 +3059,21 @@ bool sagg_x0_slot(nodal_ctx *h, const double **dinv, nodal_cyc_t **x0, int64_t *
     *omega = OMEGA;
     return true;
 }
+// (the launches of sagg_apply under the K-cycle schedule the caller has set: sagg_apply, sagg_debug_cycle_apply)
+static int apply_scheduled(nodal_ctx *h, SHierarchy *H, const double *r, double *z, bool x0_ready) {
+    SLevel *L0 = H->pool[0];
+    cyc_t *x0 = L0->v<cyc_t>(V_X);
+    if (!x0_ready) k_x0<<<grid_for(L0->n), TB, 0, h->stream>>>(L0->n, L0->dinv.as<double>(), r, x0);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return cycle<double, double>(h, H, 0, r, x0, z, nullptr);
+}
 // it >= 0: the cycle is the preconditioner of iteration `it` of a FLEXIBLE method (FGMRES: sparse_general.hip), which
 // may calibrate and freeze the K-cycle's coefficients like sagg_fcg_solve does (kcycle_schedule)
 int sagg_apply(nodal_ctx *h, const double *r, double *z, bool x0_ready, int it) {
     SHierarchy *H = static_cast<SHierarchy *>(h->sagg);
     if (!H || !H->ready) return nodal_fail(h, NODAL_E_INVALID, "sagg_setup_csr not called");
-    SLevel *L0 = H->pool[0];
-    cyc_t *x0 = L0->v<cyc_t>(V_X);
-    if (!x0_ready) k_x0<<<grid_for(L0->n), TB, 0, h->stream>>>(L0->n, L0->dinv.as<double>(), r, x0);
-    NODAL_HIP_TRY(h, hipGetLastError());
     kcycle_schedule(H, it);
-    const int rc = cycle<double, double>(h, H, 0, r, x0, z, nullptr);
+    const int rc = apply_scheduled(h, H, r, z, x0_ready);
     H->kfrozen = false;
     H->kslot = -1;
     return rc;
@@ -3091,6 +3095,29 @@ int sagg_spmv(nodal_ctx *h, const double *x, double *y, hipEvent_t start, hipEve
     }
     NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
+}
+
+// The flexible CG's vectors, partial sums and scalars in one buffer of solve_bufs_bytes(n) bytes (sagg_fcg_solve on
+// the context's solver buffer; the testing hook sagg_debug_cycle_apply on scratch of its own)
+static size_t solve_bufs_bytes(int64_t n) {
+    return 6 * align256((size_t)n * 8) + 4 * MAX_PARTIALS * 8 + F_COUNT * 8 + 256;
+}
+static SolveBufs solve_bufs(char *base, int64_t n) {
+    const size_t vec = align256((size_t)n * 8);
+    SolveBufs sb;
+    sb.r = reinterpret_cast<double *>(base);
+    sb.z = reinterpret_cast<cyc_t *>(base + vec);
+    sb.p = reinterpret_cast<double *>(base + 2 * vec);
+    sb.Ap = reinterpret_cast<double *>(base + 3 * vec);
+    sb.x0 = reinterpret_cast<cyc_t *>(base + 4 * vec);
+    sb.p2 = reinterpret_cast<double *>(base + 5 * vec);  // the direction of the odd iterations (fused f_dir_spmv)
+    sb.part_rz = reinterpret_cast<double *>(base + 6 * vec);
+    sb.part_zap = sb.part_rz + MAX_PARTIALS;
+    sb.part_rr = sb.part_zap + MAX_PARTIALS;
+    sb.part_pap = sb.part_rr + MAX_PARTIALS;
+    sb.sc = sb.part_pap + MAX_PARTIALS;
+    sb.g0 = (int)grid_for(n, MAX_PARTIALS);
+    return sb;
 }
 
 // Flexible CG preconditioned by the hierarchy.  Return: NODAL_OK (converged, *info = 0); -2 the
@@ -3120,22 +3147,9 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
     H->klevels = knob::SA_KLEVELS.now();
     apply_nu_knob(H);
 
-    const size_t vec = align256((size_t)n * 8);
-    NODAL_HIP_TRY(h, h->solver.reserve(6 * vec + 4 * MAX_PARTIALS * 8 + F_COUNT * 8 + 256));
+    NODAL_HIP_TRY(h, h->solver.reserve(solve_bufs_bytes(n)));
     char *base = h->solver.as<char>();
-    SolveBufs sb;
-    sb.r = reinterpret_cast<double *>(base);
-    sb.z = reinterpret_cast<cyc_t *>(base + vec);
-    sb.p = reinterpret_cast<double *>(base + 2 * vec);
-    sb.Ap = reinterpret_cast<double *>(base + 3 * vec);
-    sb.x0 = reinterpret_cast<cyc_t *>(base + 4 * vec);
-    sb.p2 = reinterpret_cast<double *>(base + 5 * vec);  // the direction of the odd iterations (fused f_dir_spmv)
-    sb.part_rz = reinterpret_cast<double *>(base + 6 * vec);
-    sb.part_zap = sb.part_rz + MAX_PARTIALS;
-    sb.part_rr = sb.part_zap + MAX_PARTIALS;
-    sb.part_pap = sb.part_rr + MAX_PARTIALS;
-    sb.sc = sb.part_pap + MAX_PARTIALS;
-    sb.g0 = (int)grid_for(n, MAX_PARTIALS);
+    const SolveBufs sb = solve_bufs(base, n);
     double *x = h->x.as<double>();
     const Ell A0 = H->pool[0]->A();
 
@@ -3367,3 +3381,160 @@ int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, 
 }
 
 #include "sagg_multi.h"
+
+// ---- testing hook (nodal_debug_cycle_apply): ONE application of the cycle to the caller's vector, no Krylov step ----
+// The hierarchy debug_hierarchy() finds, on its owner's stream, as the last solve left it (sweep counts, K-cycle
+// switches: no knob is read here).  mode 0: sagg_apply's launches (k_x0, cycle<double, double>); mode 1: the flexible
+// CG's call (cycle<double, cyc_t> with a SolveBufs laid out by solve_bufs, `u` in the place of Ap, x0 by k_x0: the
+// expression f_init / f_update use); mode 2: the block's call (m_init_b, m_cycle<double>(outer), m_reduce_kernel).
+// With NODAL_SA_NU's third sweep m_cycle runs two per side (it has no third).  frozen: the caller's (s1, s2, t) in
+// the slots the frozen launches read, the cycle under kfrozen; NULL: kcycle_schedule(H, -1).  Vectors of the single
+// modes live in the context's dbg_apply, the block's in the hierarchy's block buffer (m_layout); the K-cycle words,
+// kfrozen, kslot, kcount and ksamples come back as they were.
+namespace {
+
+// a partial array summed the way reduce_partials3 sums it for f_direction / f_dir_spmv: thread t of TB takes the
+// entries t, t + TB, ..., a wavefront folds by halves (wave_sum), the wavefronts' sums are added in order
+double sum_like_reduce_partials(const double *part, int count) {
+    double lane[TB];
+    for (int t = 0; t < TB; ++t) {
+        double s = 0.0;
+        for (int i = t; i < count; i += TB) s += part[i];
+        lane[t] = s;
+    }
+    double total = 0.0;
+    for (int w = 0; w < TB / 64; ++w) {
+        double *v = lane + 64 * w;
+        for (int off = 32; off > 0; off >>= 1)
+            for (int l = 0; l < off; ++l) v[l] += v[l + off];
+        total += v[0];
+    }
+    return total;
+}
+
+struct KState {  // (whatever way the hook is left)
+    SHierarchy *H;
+    bool kfrozen;
+    int kslot, kcount, ksamples;
+    explicit KState(SHierarchy *h_) : H(h_), kfrozen(h_->kfrozen), kslot(h_->kslot), kcount(h_->kcount), ksamples(h_->ksamples) {}
+    ~KState() { H->kfrozen = kfrozen; H->kslot = kslot; H->kcount = kcount; H->ksamples = ksamples; }
+};
+
+}  // namespace
+
+int sagg_debug_cycle_apply(nodal_ctx *h, int32_t mode, const double *r, const double *u, const double *frozen, double *z,
+                           double *dots_out, int32_t *params_out) {
+    nodal_ctx *c = nullptr;
+    SHierarchy *H = debug_hierarchy(h, &c);
+    if (!H) return nodal_fail(h, NODAL_E_INVALID, "debug cycle: the handle holds no ready hierarchy");
+    if (mode < 0 || mode > 2) return nodal_fail(h, NODAL_E_INVALID, "debug cycle: no such mode");
+    if (H->nlev < 2 || H->tail == 0) return nodal_fail(h, NODAL_E_INVALID, "debug cycle: no level outside the tail");
+    if (mode != 0 && !u) return nodal_fail(h, NODAL_E_INVALID, "debug cycle: this mode needs u");
+    SLevel *L0 = H->pool[0];
+    const int64_t n = L0->n;
+    if (mode == 2 && c->n != n) return nodal_fail(h, NODAL_E_INVALID, "debug cycle: the block driver declines");
+    hipStream_t st = c->stream;
+    NODAL_WAIT_STREAM(h, st);
+    if (H->aux) NODAL_WAIT_STREAM(h, H->aux);
+    const int nu0 = H->nu[0];
+    const bool last0 = 1 == H->tail || 1 == H->nlev - 1;
+    const bool kc0 = !last0 && 0 < H->klevels && H->kcycle;  // level 0 hands over through the K-cycle's launches
+    const bool use_frozen = frozen != nullptr && kc0;
+    if (params_out) {
+        int32_t *p = params_out;
+        for (int k = 0; k < 16; ++k) p[k] = 0;
+        p[0] = H->nu[0]; p[1] = H->nu[1]; p[2] = H->nu[2]; p[3] = H->tail >= 0 ? H->td.nu : 0;
+        p[4] = H->kcycle; p[5] = H->klevels; p[6] = H->tail; p[7] = H->tail_dense; p[8] = H->nlev;
+        p[9] = mode == 0 ? L0->fold : (mode == 1 ? (L0->fold && nu0 != 1) : 0);
+        p[10] = use_frozen; p[11] = MK;
+        for (int l = 0; l < H->nlev; ++l) {
+            p[12] |= (int32_t)H->pool[l]->fold << l;
+            p[13] |= (int32_t)H->pool[l]->restrict_b << l;
+            p[14] |= (int32_t)H->pool[l]->visit << l;
+        }
+        p[15] = H->general;
+    }
+    KState keep(H);
+    kcycle_schedule(H, -1);
+    if (use_frozen) H->kfrozen = true;
+
+    if (mode == 2) {
+        MBufs M;
+        NODAL_TRY(m_layout(c, H, M));
+        const size_t vb = (size_t)n * MK * 8;
+        // r through m_init_b (x0 as the block iteration forms it; it also clears M.x and M.Ap), then u in the place of Ap
+        double *stage = M.p;  // (the direction's buffer: not read by the cycle)
+        NODAL_HIP_TRY(h, hipMemcpyAsync(stage, r, vb, hipMemcpyHostToDevice, st));
+        double *part_rr = M.part + (int64_t)2 * MPARTS * MK;
+        m_init_b<<<M.g0, TB, 0, st>>>(n, stage, M.x, M.r, M.Ap, L0->dinv.as<double>(), M.x0, part_rr, MPARTS);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        NODAL_HIP_TRY(h, hipMemcpyAsync(M.Ap, u, vb, hipMemcpyHostToDevice, st));
+        if (use_frozen) {
+            double *cf = M.lv[1].tot + 6 * MK, *fs = cf + 2 * MK, *ft = fs + 2 * MK;
+            double hfs[2 * MK], hft[MK];
+            for (int y = 0; y < MK; ++y) {
+                hfs[2 * y] = frozen[3 * y];
+                hfs[2 * y + 1] = frozen[3 * y + 1];
+                hft[y] = frozen[3 * y + 2];
+            }
+            NODAL_HIP_TRY(h, hipMemcpyAsync(fs, hfs, sizeof hfs, hipMemcpyHostToDevice, st));
+            NODAL_HIP_TRY(h, hipMemcpyAsync(ft, hft, sizeof hft, hipMemcpyHostToDevice, st));
+            NODAL_WAIT_STREAM(h, st);
+        }
+        NODAL_TRY(m_cycle<double>(c, H, M, 0, M.r, M.x0, M.z, true));
+        m_reduce_kernel<<<4, MR, 0, st>>>(M.part, MPARTS, M.g0, M.tot);  // [0] z.r [1] z.u, as m_iterate reduces them
+        NODAL_HIP_TRY(h, hipGetLastError());
+        std::vector<cyc_t> zs((size_t)n * MK);
+        NODAL_HIP_TRY(h, hipMemcpyAsync(zs.data(), M.z, zs.size() * sizeof(cyc_t), hipMemcpyDeviceToHost, st));
+        if (dots_out) NODAL_HIP_TRY(h, hipMemcpyAsync(dots_out, M.tot, (size_t)2 * MK * 8, hipMemcpyDeviceToHost, st));
+        NODAL_WAIT_STREAM(h, st);
+        for (size_t k = 0; k < zs.size(); ++k) z[k] = (double)zs[k];
+        return NODAL_OK;
+    }
+
+    // the frozen words of the single cycle: (s1, s2, t) at cf + 3 of the first coarse level (k_kcoef); put back below
+    double *cf = use_frozen ? H->pool[1]->part.as<double>() + 5 * DOT_BLOCKS : nullptr;
+    double saved[3] = {0.0, 0.0, 0.0};
+    if (use_frozen) {
+        NODAL_HIP_TRY(h, hipMemcpyAsync(saved, cf + 3, sizeof saved, hipMemcpyDeviceToHost, st));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(cf + 3, frozen, sizeof saved, hipMemcpyHostToDevice, st));
+        NODAL_WAIT_STREAM(h, st);
+    }
+    int rc = NODAL_OK;
+    const size_t vec = align256((size_t)n * 8);
+    if (mode == 0) {
+        NODAL_HIP_TRY(h, c->dbg_apply.reserve(2 * vec + 256));
+        double *dr = c->dbg_apply.as<double>(), *dz = dr + vec / 8;
+        NODAL_HIP_TRY(h, hipMemcpyAsync(dr, r, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        rc = apply_scheduled(c, H, dr, dz, false);
+        if (rc == NODAL_OK) {
+            NODAL_HIP_TRY(h, hipMemcpyAsync(z, dz, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            NODAL_WAIT_STREAM(h, st);
+        }
+    } else {
+        NODAL_HIP_TRY(h, c->dbg_apply.reserve(solve_bufs_bytes(n)));
+        const SolveBufs sb = solve_bufs(c->dbg_apply.as<char>(), n);
+        NODAL_HIP_TRY(h, hipMemcpyAsync(sb.r, r, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(sb.Ap, u, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        k_x0<<<grid_for(n), TB, 0, st>>>(n, L0->dinv.as<double>(), sb.r, sb.x0);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        rc = cycle<double, cyc_t>(c, H, 0, sb.r, sb.x0, sb.z, &sb);
+        if (rc == NODAL_OK) {
+            std::vector<cyc_t> zs((size_t)n);
+            std::vector<double> parts((size_t)2 * MAX_PARTIALS);
+            NODAL_HIP_TRY(h, hipMemcpyAsync(zs.data(), sb.z, zs.size() * sizeof(cyc_t), hipMemcpyDeviceToHost, st));
+            NODAL_HIP_TRY(h, hipMemcpyAsync(parts.data(), sb.part_rz, parts.size() * 8, hipMemcpyDeviceToHost, st));
+            NODAL_WAIT_STREAM(h, st);
+            for (size_t k = 0; k < zs.size(); ++k) z[k] = (double)zs[k];
+            if (dots_out) {
+                dots_out[0] = sum_like_reduce_partials(parts.data(), sb.g0);
+                dots_out[1] = sum_like_reduce_partials(parts.data() + MAX_PARTIALS, sb.g0);
+            }
+        }
+    }
+    if (use_frozen) {
+        NODAL_HIP_TRY(h, hipMemcpyAsync(cf + 3, saved, sizeof saved, hipMemcpyHostToDevice, st));
+        NODAL_WAIT_STREAM(h, st);
+    }
+    return rc;
+}
