@@ -297,6 +297,62 @@ int nodal_transient_rlc(nodal_handle h, int32_t dense, int32_t steps, int32_t me
                         int32_t *info_out, int32_t *iters_out, int64_t nind, const int64_t *ind_rows, const double *i0,
                         int32_t ncur, const int32_t *cur_index, double *cur_out, double *i_final_out);
 
+/* ---- nonlinear DC analysis: networks with diodes, by Newton's method (replaces a host loop that downloads x, evaluates
+ *      the junctions in numpy, uploads a value column, re-assembles and solves per iteration; with the reference a new
+ *      netlist, a new Circuit and a .solve() per iteration, reference nodal/nodal.py:306-336) ----
+ * The handle holds the circuit WITH one extra R row per diode, diode_rows [ndiode] (table rows of type R, checked on the
+ * device as cap_rows are; their table values are overwritten).  Diode d, anode = lead a and cathode = lead b of its row,
+ * carries i(v) = i_sat[d] (exp(v / n_vt[d]) - 1) + gmin v from a to b at v = x(a) - x(b) (ground: +0.0); n_vt in volts
+ * (emission coefficient times thermal voltage).  One word vh per diode is the limited junction voltage; vh_0 = v of x0
+ * (x0 [n], NULL: zeros; only its potentials are read).  Iteration k = 0 .. linearises at vh_k,
+ *   e = exp(vh / n_vt),  g = i_sat e / n_vt + gmin,  i = i_sat (e - 1) + gmin vh,  J = g vh - i
+ * writes 1 / g into the diode's row of the value column on the device, assembles G anew (symbolic phase kept) and solves
+ * G x_{k+1} = A + the J, injected into lead a and drawn from lead b (the capacitors' convention in nodal_transient); A has
+ * the sources src_rows [nsrc] at src_values [nsrc] (nodal_solve_sources' row rules, one setting).  Then per diode, with
+ * the raw v = x_{k+1}(a) - x_{k+1}(b) and v_crit = n_vt ln(n_vt / (sqrt(2) i_sat)), SPICE's junction limiting
+ *   limited:  v > v_crit and |v - vh| > 2 n_vt
+ *     vh > 0:   a = 1 + (v - vh) / n_vt,  vh' = a > 0 ? vh + n_vt ln a : v_crit
+ *     vh <= 0:  vh' = n_vt ln(v / n_vt)
+ *   otherwise vh' = v
+ * and the diode's convergence test, with ihat = i + g (v - vh):
+ *   |v - vh| <= reltol max(|v|, |vh|) + vntol  and  |i(v) - ihat| <= reltol max(|i(v)|, |ihat|) + abstol
+ * The loop ends when no diode fails its test (*converged = 1), after max_iter iterations, on a singular iteration, or on
+ * an iterate that is not finite or a g that overflows (*converged = 0; the loop never hangs).  ndiode == 0 is one linear
+ * solve, converged after one iteration.
+ *   x_out [n]                     the last iterate
+ *   v_out, i_out, g_out [ndiode]  v, i(v), g(v) = i_sat exp(v / n_vt) / n_vt + gmin at the last iterate
+ *   iterates_out [max_iter][n]    x_1 .. (rows past *iterations are left as they were)
+ *   vh_out [max_iter + 1][ndiode] vh_0, vh_1 .. ; NaN past the last one formed
+ *   record_out [max_iter][4]      per iteration: diodes that failed the test, diodes that were limited, max |v - vh|,
+ *                                 the scaled residual of the solve as nodal_solve_sources defines it; zeros past
+ *                                 *iterations
+ *   info_out [max_iter]           > 0: the iteration was singular: NaN in its record, in x_out, v_out, i_out, g_out
+ *                                 (status OK) -- except with dense != 0, where a singular G returns NODAL_E_SINGULAR
+ *   iters_out [max_iter]          iterations of the solve (multigrid), 1 (sparse LU + refinement), 0 (dense panel)
+ *   route_out [max_iter]          0 dense panel, 1 sparse LU, 2 multigrid, 3 the sparse direct solve took the step
+ *                                 over (nodal_transient's fall-backs); -1 past *iterations
+ * Each of them may be NULL; iterations and converged may not.  Routes as nodal_transient's, chosen anew every iteration,
+ * and the matrix work is redone every iteration because the matrix moved: n <= 64 the dense panel; B == 0, all R > 0 and
+ * n > 4096 the multigrid iteration, the hierarchy's values refreshed on its kept symbolic setup; everything else the
+ * sparse LU, factored anew on its kept analysis.  nodal_last_timings afterwards: [0] host ms of the matrix work
+ * (assembly, factorisation, hierarchy setup) summed over the iterations; [1] the part of [0] that was symbolic (an LU
+ * analysis, a full hierarchy setup), exactly 0.0 when all of it was kept; [2] the whole call.
+ * NODAL_E_INVALID: max_iter < 1, gmin or a tolerance negative or not finite, an i_sat or n_vt that is not > 0 and finite,
+ * a diode_rows entry out of range or not of type R, diodes on a network without nodes, the source-row errors of
+ * nodal_solve_sources, no nodal_assemble_numeric before the call.
+ * Host waits per iteration: the assembly's status words, what the solver looks at, and ONE read of the record (with the
+ * scaled residual where the solver left it on the device).  The counts are integer atomics and the maximum an integer
+ * maximum over the bits of |v - vh|: no floating-point atomics, a repeated call gives the same bits.  Afterwards the
+ * handle's value column holds 1 / g of the last linearisation in the diode rows (1.0 after an overflow), G is assembled
+ * from it, factors or hierarchy belong to it; the solution is dropped, a recorded transient is void.  The host copy of
+ * the values that the presolve of networks with branch rows keeps is NOT updated in the diode rows: no route of this call
+ * or of nodal_transient reads them there; nodal_upload_values / nodal_upload_components before any other solve. */
+int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                    const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                    const double *x0, int32_t max_iter, double reltol, double vntol, double abstol, double *x_out,
+                    double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out, double *record_out,
+                    int32_t *info_out, int32_t *iters_out, int32_t *route_out, int32_t *iterations, int32_t *converged);
+
 /* ---- gradients through time (replaces finite differences over whole transient runs: two nodal_transient calls per
  *      component; with the reference each of them a host loop of rebuild and solve, reference nodal/nodal.py:306-336) ----
  * The adjoint of the backward-Euler run the handle has RECORDED: with NODAL_OPT_TRANSIENT_TAPE set, a nodal_transient call

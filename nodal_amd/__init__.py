@@ -13,6 +13,7 @@ from .branches import Branches, Envelope  # noqa: E402,F401
 from .sensitivity import Sensitivities, resolve_outputs  # noqa: E402,F401
 from .gradient import Gradient, check_gradient_arguments  # noqa: E402,F401
 from .transient import Transient, TransientEnvelope, resolve_capacitors  # noqa: E402,F401
+from .operating_point import NewtonHistory, OperatingPoint, resolve_diodes  # noqa: E402,F401
 from .ac import ACPeaks, ACSweep, resolve_reactive  # noqa: E402,F401
 from .noise import NoiseSweep, trapezoid_weights  # noqa: E402,F401
 from .ac_ports import ACPortPeaks, ACPortSweep, check_ac_port_arguments  # noqa: E402,F401

@@ -62,6 +62,9 @@ SIGNATURES = {
     "nodal_transient_rlc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
                                       _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p, _i32p,
                                       _f64p, _i32p, _i32p, C.c_int64, _i64p, _f64p, C.c_int32, _i32p, _f64p, _f64p]),
+    "nodal_newton_dc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, _i64p, _f64p,
+                                  _f64p, C.c_int32, C.c_double, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p,
+                                  _f64p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "nodal_transient_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
                                            _f64p, _i32p]),
     "nodal_ac_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
@@ -501,6 +504,45 @@ class Handle:
             _ptr(i0, C.c_double) if len(i0) else None, len(cur_index), _ptr(cur_index, C.c_int32) if len(cur_index) else None,
             _ptr(cur, C.c_double) if cur.size else None, _ptr(final, C.c_double) if len(final) else None))
         return wave, x, env, resid, info, iters, cur, final
+
+    def newton_dc(self, diode_rows, i_sat, n_vt, gmin, rows, values, x0, dense, max_iter, reltol, vntol, abstol,
+                  keep_iterates=False):
+        """Newton's method on a handle that holds the circuit with one companion resistor per diode (nodal_newton_dc):
+        diode_rows their table rows, i_sat, n_vt [D], values [len(rows)] the one setting of the swept sources, x0 [n] or
+        None.  Returns a dict: x [n], v, i, g [D], iterations, converged, record [iterations, 4], info, iters, route
+        [iterations], and with keep_iterates iterates [iterations, n] and vh [iterations + 1, D] (None otherwise);
+        NodalHipError(E_INVALID) as the header lists, with dense a singular G raises NodalHipError(E_SINGULAR)."""
+        diode_rows = np.ascontiguousarray(diode_rows, dtype=np.int64)
+        i_sat, n_vt = (np.ascontiguousarray(v, dtype=np.float64) for v in (i_sat, n_vt))
+        D = len(diode_rows)
+        assert diode_rows.ndim == 1 and i_sat.shape == (D,) and n_vt.shape == (D,)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.shape == (len(rows),)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            assert x0.shape == (self.n,)
+        max_iter = int(max_iter)
+        x = np.zeros(self.n, dtype=np.float64)
+        v, i, g = (np.zeros(D, dtype=np.float64) for _ in range(3))
+        iterates = np.zeros((max_iter, self.n), dtype=np.float64) if keep_iterates else None
+        vh = np.zeros((max_iter + 1, D), dtype=np.float64) if keep_iterates else None
+        record = np.zeros((max_iter, 4), dtype=np.float64)
+        info, iters, route = (np.zeros(max_iter, dtype=np.int32) for _ in range(3))
+        iterations, converged = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.nodal_newton_dc(
+            self._h, int(dense), D, _ptr(diode_rows, C.c_int64) if D else None, _ptr(i_sat, C.c_double) if D else None,
+            _ptr(n_vt, C.c_double) if D else None, float(gmin), len(rows), _ptr(rows, C.c_int64) if len(rows) else None,
+            _ptr(values, C.c_double) if len(rows) else None, _ptr(x0, C.c_double) if x0 is not None else None, max_iter,
+            float(reltol), float(vntol), float(abstol), _ptr(x, C.c_double) if self.n else None,
+            _ptr(v, C.c_double) if D else None, _ptr(i, C.c_double) if D else None, _ptr(g, C.c_double) if D else None,
+            _ptr(iterates, C.c_double) if keep_iterates and self.n else None, _ptr(vh, C.c_double) if keep_iterates and D else None,
+            _ptr(record, C.c_double), _ptr(info, C.c_int32), _ptr(iters, C.c_int32), _ptr(route, C.c_int32),
+            C.byref(iterations), C.byref(converged)))
+        r = iterations.value
+        return {"x": x, "v": v, "i": i, "g": g, "iterations": r, "converged": bool(converged.value), "record": record[:r],
+                "info": info[:r], "iters": iters[:r], "route": route[:r],
+                "iterates": iterates[:r] if keep_iterates else None, "vh": vh[:r + 1] if keep_iterates else None}
 
     def transient_gradient(self, steps, nsrc, ia, ib, cotangents, dense, adjoints=False):
         """The adjoint of the transient run this handle recorded (nodal_transient_gradient; OPT_TRANSIENT_TAPE): steps

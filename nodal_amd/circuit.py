@@ -97,6 +97,7 @@ class Circuit:
         self._transient_child = None
         self._transient_dc = None
         self._transient_record = None
+        self._newton_child = None
         self.currents = self.build_model()
 
     @classmethod
@@ -111,6 +112,7 @@ class Circuit:
         self._transient_child = None
         self._transient_dc = None
         self._transient_record = None
+        self._newton_child = None
         self.table = other.table if table is None else table
         self.currents = other.currents
         self._assemble(self.table)
@@ -374,6 +376,7 @@ class Circuit:
         self._transient_child = None  # (its matrix carried the old values)
         self._transient_dc = None
         self._transient_record = None
+        self._newton_child = None
         self.table = table.with_values(new)
 
     def thevenin(self, ports, sources=True):
@@ -518,6 +521,67 @@ class Circuit:
         return Transient(dt * np.arange(steps + 1, dtype=np.float64), wave, probes, info, resid, iters, solutions=x,
                          solution_steps=kept, envelope=env, timings=ch.timings(), currents=cur,
                          current_probes=current_probes, final_currents=final)
+
+    def operating_point(self, diodes, sources=None, initial=None, max_iter=100, reltol=1e-3, vntol=1e-6, abstol=1e-12,
+                        gmin=1e-12, keep_iterates=False):
+        """The DC operating point of the circuit with diodes, by Newton's method on the device (nodal_newton_dc).
+
+        `diodes` is a sequence of (name, i_sat, n_vt, anode, cathode) on nodes of the netlist: diode d carries
+        i(v) = i_sat (exp(v / n_vt) - 1) + gmin v from anode to cathode at v = x(anode) - x(cathode), n_vt in volts
+        (emission coefficient times thermal voltage).  `sources` maps names of A / E components to ONE value each, in
+        force for this call (solve_sources' names and errors; a source that is not named keeps its netlist value);
+        `initial` is a float64 [K+B] vector of which the potentials are read (None: zeros) -- `initial=previous.x`
+        together with `sources` gives DC transfer curves and continuation in the caller's hands.  An iteration
+        linearises every diode at its limited junction voltage, assembles and solves; SPICE's junction limiting
+        (pnjlim) keeps the exponentials finite; it has converged when every diode has
+        |v - vh| <= reltol max(|v|, |vh|) + vntol and |i(v) - ihat| <= reltol max(|i(v)|, |ihat|) + abstol, ihat the
+        current its linearisation predicted.  Returns an OperatingPoint (operating_point.py): `x`, `voltages`,
+        `currents`, `conductances` [D], `converged`, `iterations`, `history`, `scaled_residual`, `timings`,
+        linearised() -- the small-signal circuit at this point for ac(), noise(), thevenin(sources=False) -- and with
+        keep_iterates=True `iterates` and `limited_voltages`.
+
+        The matrix is that of the netlist with one companion resistor per diode, assembled on a second device context
+        that is kept on the circuit, keyed by the diodes' leads, until set_values(): a second call with other sources,
+        diode parameters, tolerances or `initial` repeats no symbolic work (`timings[1] == 0.0`).  A run that does not
+        converge in max_iter iterations returns converged=False and warns once (RuntimeWarning).  Singular iterations
+        behave as in solve_sources(): the dense path raises LinAlgError / UnconnectedCircuitError, the sparse path
+        returns NaN with info > 0 in the history and warns once.  ValueError for unknown nodes, duplicate names or
+        names of components, non-positive i_sat / n_vt, negative gmin / tolerances, max_iter < 1, and an `initial`
+        that is not finite or of another shape.  No floating-point atomics: a repeated call gives the same bits.  The
+        circuit itself -- its solution if any, table, G, A, what transient() and ac() keep -- is left as it was;
+        solve() is neither needed nor touched."""
+        from .operating_point import (NewtonHistory, OperatingPoint, check_operating_point_arguments, companion_table,
+                                      resolve_diodes)
+        from .sweep import resolve_sources
+        h = self._handle
+        max_iter, reltol, vntol, abstol, gmin, x0 = check_operating_point_arguments(max_iter, reltol, vntol, abstol, gmin,
+                                                                                    initial, h.n)
+        names, i_sat, n_vt, ia, ib = resolve_diodes(self.netlist, diodes)
+        setting = {}
+        if sources is not None:
+            if not hasattr(sources, "items"):
+                raise TypeError("sources must map component names to values")
+            setting = {name: [value] for name, value in sources.items()}
+        rows, values = resolve_sources(self.netlist, setting)
+        values = values[0] if len(rows) else np.zeros(0, dtype=np.float64)
+        key = (ia.tobytes(), ib.tobytes())
+        if self._newton_child is None or self._newton_child[0] != key:
+            self._newton_child = None  # (its device context goes back to the pool first)
+            table, diode_rows = companion_table(self.table, i_sat, n_vt, ia, ib, gmin)
+            self._newton_child = (key, Circuit._clone_of(self, table), diode_rows)
+        _, child, diode_rows = self._newton_child
+        ch = child._handle
+        with self._reference_errors():
+            r = ch.newton_dc(diode_rows, i_sat, n_vt, gmin, rows, values, x0, dense=not self.sparse, max_iter=max_iter,
+                             reltol=reltol, vntol=vntol, abstol=abstol, keep_iterates=keep_iterates)
+        singular = (r["info"] > 0).any()
+        _warn_singular(singular)
+        if not r["converged"] and not singular:
+            warnings.warn(f"operating_point did not converge in {r['iterations']} iterations", RuntimeWarning, stacklevel=2)
+        history = NewtonHistory(r["record"], r["info"], r["iters"], r["route"])
+        return OperatingPoint(r["x"], names, r["v"], r["i"], r["g"], r["converged"], r["iterations"], history,
+                              timings=ch.timings(), iterates=r["iterates"], limited_voltages=r["vh"], circuit=self,
+                              leads=(ia, ib))
 
     def _transient_dc_start(self, la, lb):
         """The DC operating point with every inductor a short, of the netlist's own source values: (x_0 [K+B], i_0 [L],

@@ -5,6 +5,7 @@
 #include "ctx.h"
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <vector>
 
 int dense_prepare(nodal_ctx *h);  // sparse.hip
@@ -933,6 +934,50 @@ int nodal_transient_rlc(nodal_handle h, int32_t dense, int32_t steps, int32_t me
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_matrix;
     h->ms[1] = 0.0;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
+int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                    const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                    const double *x0, int32_t max_iter, double reltol, double vntol, double abstol, double *x_out,
+                    double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out, double *record_out,
+                    int32_t *info_out, int32_t *iters_out, int32_t *route_out, int32_t *iterations, int32_t *converged) {
+    if (!h || ndiode < 0 || (ndiode > 0 && (!diode_rows || !i_sat || !n_vt)) || max_iter < 1 || !iterations || !converged)
+        return NODAL_E_INVALID;
+    if (!(gmin >= 0.0 && reltol >= 0.0 && vntol >= 0.0 && abstol >= 0.0) || std::isinf(gmin) || std::isinf(reltol) ||
+        std::isinf(vntol) || std::isinf(abstol))
+        return nodal_fail(h, NODAL_E_INVALID, "newton: gmin and the tolerances must be finite and not negative");
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "newton: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "newton: assemble_numeric not called");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    h->tape_valid = false;  // (the node lists and the state buffers of a recorded transient are written over)
+    NODAL_TRY(sweep_prepare(h, 1, nsrc, src_rows, src_values));
+    h->amg_levels = 0;
+    h->last_batch_block = false;
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_matrix = 0.0, ms_symbolic = 0.0;
+    NewtonOutputs out;
+    out.x = x_out;
+    out.v = v_out;
+    out.i = i_out;
+    out.g = g_out;
+    out.iterates = iterates_out;
+    out.vh = vh_out;
+    out.record = record_out;
+    out.info = info_out;
+    out.iters = iters_out;
+    out.route = route_out;
+    out.iterations = iterations;
+    out.converged = converged;
+    const int s = newton_run(h, dense != 0, ndiode, diode_rows, i_sat, n_vt, gmin, nsrc, x0, max_iter, reltol, vntol, abstol,
+                             out, &ms_matrix, &ms_symbolic);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = ms_matrix;
+    h->ms[1] = ms_symbolic;
     h->ms[2] = elapsed(h, 0, 1);
     return s;
 }

@@ -609,6 +609,22 @@ int signed_list_add(nodal_ctx *h, int64_t nent, const int32_t *node, const int32
 int transient_add_history(nodal_ctx *h, int64_t ncap, int method, const int32_t *rows_dev, int64_t nent, const double *x_prev,
                           double *hist, double *rhs);
 
+// ---- nonlinear DC analysis (newton.hip): diodes as companion R rows, Newton's method with the lane work on the device ----
+struct NewtonOutputs {           // host arrays, each may be null except iterations and converged
+    double *x = nullptr;         // [n] the last iterate
+    double *v = nullptr, *i = nullptr, *g = nullptr;  // [nd] of the last iterate
+    double *iterates = nullptr;  // [max_iter][n]
+    double *vh = nullptr;        // [max_iter + 1][nd]
+    double *record = nullptr;    // [max_iter][4]: not converged, limited, max |v - vh|, scaled residual
+    int32_t *info = nullptr, *iters = nullptr, *route = nullptr;  // [max_iter]
+    int32_t *iterations = nullptr, *converged = nullptr;
+};
+// the swept sources are those of the last sweep_prepare (one setting); *ms_matrix: host ms of assembly, factorisation and
+// hierarchy setup summed over the iterations, *ms_symbolic: the part of it that was an analysis or a full hierarchy setup
+int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, const double *isat, const double *nvt,
+               double gmin, int32_t nsrc, const double *x0, int32_t max_iter, double reltol, double vntol, double abstol,
+               const NewtonOutputs &out, double *ms_matrix, double *ms_symbolic);
+
 // ---- gradients through time (transient_gradient.hip): the adjoint of the recorded backward-Euler run ----
 // the arguments are those of nodal_transient_gradient; ms_matrix as transient_run's
 int tgrad_run(nodal_ctx *h, bool dense, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
@@ -747,6 +763,7 @@ void sagg_destroy(nodal_ctx *h);
 // -3 declined (not this hierarchy's kind of network: use amg.hip)
 int sagg_fcg_solve(nodal_ctx *h, const double *b, bool do_setup, int32_t *info, int32_t *iters, double *resid);
 bool sagg_ready(nodal_ctx *h, int64_t n);  // a hierarchy for n unknowns is set up
+bool sagg_refreshed(nodal_ctx *h);         // ... and its last setup kept the symbolic part: the values alone were refreshed
 // up to 16 probe pairs per iteration on that hierarchy (sagg_multi.h); -1: breakdown / no convergence
 int sagg_pairs_block_width();  // pairs the block iteration takes per call (sagg_multi.h: MK)
 // up to 16 general right-hand sides B (interleaved by row, unused columns zero) on that hierarchy; each column stops on

@@ -1,0 +1,365 @@
+// Nonlinear DC analysis: networks with diodes, solved by Newton's method with the loop's lane work on the device.
+//
+// Replaces a host loop of download x, evaluate the junctions in numpy, upload a value column, re-assemble and solve per
+// iteration (with the reference: a new netlist, a new `Circuit` and a `.solve()` per iteration, reference
+// nodal/nodal.py:306-336, plus a host pass over the diodes).
+//
+// The handle holds the circuit with one extra R row per diode, as nodal_transient holds one per capacitor.  A diode
+// carries i(v) = i_sat (exp(v / n_vt) - 1) + gmin v from its anode (lead a) to its cathode (lead b) at v = x(a) - x(b).
+// One state word vh per diode is the limited junction voltage the next linearisation is taken at.  Iteration k is, on
+// the handle's stream,
+//     k_newton_linearise    one lane per diode: e = exp(vh / n_vt), g = i_sat e / n_vt + gmin, i = i_sat (e - 1) + gmin vh;
+//                           1 / g into the diode's row of the value column the assembly reads, J = g vh - i into the
+//                           history array (injected into lead a, drawn from lead b: the capacitors' convention)
+//     stamp_numeric         G from the value column, the symbolic phase kept
+//     stamp_rhs_multi       the sources (one setting) into a zeroed vector
+//     k_signed_list_add     one lane per node with diodes: +-J of its diodes in list order, no atomics
+//     the solve             transient_solver_begin / transient_solver_step: the dense panel (n <= 64), the sparse LU
+//                           factored anew on its kept analysis, or the multigrid iteration on a hierarchy whose values
+//                           are refreshed on its kept symbolic setup (a step it gives up on: the sparse direct solve)
+//     the judgement         the block judge of multi_rhs_solve on one column
+//     k_newton_update       one lane per diode: raw v from the new x, SPICE's junction limiting vh' = pnjlim(v, vh), this
+//                           diode's convergence test, and into the iteration's record two integer counts (atomicAdd) and
+//                           the largest |v - vh| (atomicMax on the bits of a non-negative double, NaN above everything):
+//                           no floating-point sums, a repeated call gives the same bits
+// and then ONE read of the record's four words, the scaled residual among them.  The loop ends when no diode failed its
+// test, on max_iter, on info > 0 or on a record that is not finite; k_newton_outputs then forms v, i(v), g(v) from x.
+#include "group.h"
+#include "table_rows.h"
+
+#include <chrono>
+#include <cmath>
+
+namespace {
+
+constexpr int TTB = 256;
+
+// grouping enumerator (group.h): diode i touches its anode (slot 0: +J) and its cathode (slot 1: -J); one column
+struct DiodeLeads {
+    static constexpr int SLOTS = 2;
+    const int32_t *rows, *a, *b;
+    int64_t nitems;
+    template <class F>
+    __device__ void for_each(int64_t i, F f) const {
+        const int32_t r = rows[i];
+        const int ia = a[r], ib = b[r];
+        if (ia >= 0) f(0, ia, 0);
+        if (ib >= 0) f(1, ib, 0);
+    }
+};
+
+// bad[0] |= 1 for a diode row that is not a resistor, |= 2 for a saturation current or an n_vt that is not > 0 and finite
+__global__ __launch_bounds__(TTB) void k_newton_check(int64_t nd, const int32_t *__restrict__ rows,
+                                                      const uint8_t *__restrict__ type, const double *__restrict__ isat,
+                                                      const double *__restrict__ nvt, int32_t *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (i >= nd) return;
+    if (type[rows[i]] != NODAL_T_R) atomicOr(bad, 1);
+    if (!(isat[i] > 0.0 && isat[i] < INFINITY && nvt[i] > 0.0 && nvt[i] < INFINITY)) atomicOr(bad, 2);
+}
+
+// vh_0 = x0(a) - x0(b)
+__global__ __launch_bounds__(TTB) void k_newton_start(int64_t nd, const int32_t *__restrict__ rows,
+                                                      const int32_t *__restrict__ a, const int32_t *__restrict__ b,
+                                                      const double *__restrict__ x, double *__restrict__ vh) {
+    const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (i >= nd) return;
+    const int32_t r = rows[i];
+    vh[i] = lead(x, a[r]) - lead(x, b[r]);
+}
+
+// One lane per diode: the companion model at vh.  Every product is a statement of its own (the library is built with
+// -ffp-contract=on), so that g, i and J are the roundings the formulas name.
+__global__ __launch_bounds__(TTB) void k_newton_linearise(int64_t nd, const int32_t *__restrict__ rows,
+                                                          const double *__restrict__ isat, const double *__restrict__ nvt,
+                                                          double gmin, const double *__restrict__ vh,
+                                                          double *__restrict__ value, double *__restrict__ hist,
+                                                          double *__restrict__ gk, double *__restrict__ ik) {
+    const int64_t d = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (d >= nd) return;
+    const double v = vh[d], is = isat[d], nv = nvt[d];
+    const double e = exp(v / nv);
+    const double ge = is * e;
+    const double gl = gmin * v;
+    const double g = ge / nv + gmin;
+    const double ie = is * (e - 1.0);
+    const double i = ie + gl;
+    const double gv = g * v;
+    value[rows[d]] = 1.0 / g;
+    hist[d] = gv - i;
+    gk[d] = g;
+    ik[d] = i;
+}
+
+// the bits of a non-negative double order as the values do, every NaN above +inf
+__device__ __forceinline__ unsigned long long magnitude_bits(double m) {
+    return (unsigned long long)__double_as_longlong(fabs(m));
+}
+
+// One lane per diode after the solve: the limited voltage of the next linearisation, the convergence test against the
+// linearisation (gk, ik at vh) this x was solved with, and the record: rec[0] diodes that failed, rec[1] diodes that
+// were limited, rec[2] the bits of max |v - vh|.
+__global__ __launch_bounds__(TTB) void k_newton_update(int64_t nd, const int32_t *__restrict__ rows,
+                                                       const int32_t *__restrict__ a, const int32_t *__restrict__ b,
+                                                       const double *__restrict__ isat, const double *__restrict__ nvt,
+                                                       double gmin, double reltol, double vntol, double abstol,
+                                                       const double *__restrict__ x, const double *__restrict__ vh,
+                                                       const double *__restrict__ gk, const double *__restrict__ ik,
+                                                       double *__restrict__ vh_next, unsigned long long *__restrict__ rec) {
+    const int64_t d = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (d >= nd) return;
+    const int32_t r = rows[d];
+    const double v = lead(x, a[r]) - lead(x, b[r]);
+    const double old = vh[d], is = isat[d], nv = nvt[d];
+    const double dv = v - old;
+    const double vcrit = nv * log(nv / (1.4142135623730951 * is));
+    const bool limited = v > vcrit && fabs(dv) > 2.0 * nv;
+    double next = v;
+    if (limited) {
+        if (old > 0.0) {
+            const double arg = 1.0 + dv / nv;
+            const double step = nv * log(arg);
+            next = arg > 0.0 ? old + step : vcrit;
+        } else {
+            next = nv * log(v / nv);
+        }
+    }
+    vh_next[d] = next;
+    // the current the junction carries at v against the current its linearisation predicted there
+    const double ee = is * (exp(v / nv) - 1.0);
+    const double gl = gmin * v;
+    const double iv = ee + gl;
+    const double slope = gk[d] * dv;
+    const double ihat = ik[d] + slope;
+    const double vbar = reltol * fmax(fabs(v), fabs(old)) + vntol;
+    const double ibar = reltol * fmax(fabs(iv), fabs(ihat)) + abstol;
+    const bool ok = fabs(dv) <= vbar && fabs(iv - ihat) <= ibar;  // (false with a NaN anywhere)
+    if (!ok) atomicAdd(rec, 1ull);
+    if (limited) atomicAdd(rec + 1, 1ull);
+    atomicMax(rec + 2, magnitude_bits(dv));
+}
+
+// One lane per diode, once the loop has ended: v, i(v) and g(v) of the final x
+__global__ __launch_bounds__(TTB) void k_newton_outputs(int64_t nd, const int32_t *__restrict__ rows,
+                                                        const int32_t *__restrict__ a, const int32_t *__restrict__ b,
+                                                        const double *__restrict__ isat, const double *__restrict__ nvt,
+                                                        double gmin, const double *__restrict__ x, double *__restrict__ vout,
+                                                        double *__restrict__ iout, double *__restrict__ gout) {
+    const int64_t d = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (d >= nd) return;
+    const int32_t r = rows[d];
+    const double v = lead(x, a[r]) - lead(x, b[r]);
+    const double is = isat[d], nv = nvt[d];
+    const double e = exp(v / nv);
+    const double ge = is * e;
+    const double ie = is * (e - 1.0);
+    const double gl = gmin * v;
+    vout[d] = v;
+    iout[d] = ie + gl;
+    gout[d] = ge / nv + gmin;
+}
+
+// value[rows[d]] = fill: what the companion rows hold after a linearisation that overflowed
+__global__ __launch_bounds__(TTB) void k_newton_fill(int64_t nd, const int32_t *__restrict__ rows, double fill,
+                                                     double *__restrict__ value) {
+    const int64_t d = (int64_t)blockIdx.x * TTB + threadIdx.x;
+    if (d < nd) value[rows[d]] = fill;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, const double *isat, const double *nvt,
+               double gmin, int32_t nsrc, const double *x0, int32_t max_iter, double reltol, double vntol, double abstol,
+               const NewtonOutputs &out, double *ms_matrix, double *ms_symbolic) {
+    const int64_t n = h->n;
+    const int32_t K = h->K;
+    hipStream_t st = h->stream;
+    const double nan = __builtin_nan("");
+    *ms_matrix = *ms_symbolic = 0.0;
+    *out.iterations = 0;
+    *out.converged = 0;
+    h->have_x = false;
+    h->last_iterations = 0;
+    for (int32_t k = 0; k < max_iter; ++k) {
+        if (out.info) out.info[k] = 0;
+        if (out.iters) out.iters[k] = 0;
+        if (out.route) out.route[k] = -1;
+        if (out.record)
+            for (int q = 0; q < 4; ++q) out.record[4 * (size_t)k + q] = 0.0;
+    }
+    for (int64_t i = 0; i < nd; ++i)
+        if (diode_rows[i] < 0 || diode_rows[i] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "newton: diode row out of range");
+    if (nd > 0 && K == 0) return nodal_fail(h, NODAL_E_INVALID, "newton: diodes on a network without nodes");
+    if (n == 0) {  // (nothing to solve: one iteration that moves nothing)
+        *out.iterations = 1;
+        *out.converged = 1;
+        return NODAL_OK;
+    }
+
+    // ---- once per call: rows and parameters up, the node lists, the buffers ----
+    const bool keep_vh = out.vh != nullptr;
+    const size_t row_words = ((size_t)nd + 15) & ~(size_t)15;
+    const size_t vh_slots = keep_vh ? (size_t)max_iter + 1 : 2;
+    // tr_spec: diode rows | bad flag (16 words) | i_sat, n_vt, J, g_k, i_k [nd] each | v, i, g of the answer [nd] each |
+    // the limited voltages [vh_slots][nd] | the records [max_iter][4]
+    NODAL_HIP_TRY(h, h->tr_spec.reserve((row_words + 16) * 4 + ((size_t)nd * (8 + vh_slots) + 4 * (size_t)max_iter) * 8 + 64));
+    int32_t *rows_dev = h->tr_spec.as<int32_t>(), *bad_dev = rows_dev + row_words;
+    double *isat_dev = reinterpret_cast<double *>(bad_dev + 16), *nvt_dev = isat_dev + nd, *hist = nvt_dev + nd,
+           *gk = hist + nd, *ik = gk + nd, *ans = ik + nd, *vh_dev = ans + 3 * nd;
+    unsigned long long *rec_dev = reinterpret_cast<unsigned long long *>(vh_dev + vh_slots * (size_t)nd);
+    auto vh_at = [&](int32_t k) { return vh_dev + (keep_vh ? (size_t)k : (size_t)(k & 1)) * (size_t)nd; };
+    // tr_vec: the iterate | right-hand side | defect | correction | the judge's norms
+    NODAL_HIP_TRY(h, h->tr_vec.reserve((size_t)4 * n * 8 + 5 * SLU_MULTI * 8 + 256));
+    double *xk = h->tr_vec.as<double>(), *bvec = xk + n, *rvec = bvec + n, *dvec = rvec + n, *norms = dvec + n;
+    if (x0) NODAL_HIP_TRY(h, hipMemcpyAsync(xk, x0, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    else NODAL_HIP_TRY(h, hipMemsetAsync(xk, 0, (size_t)n * 8, st));
+    NODAL_HIP_TRY(h, hipMemsetAsync(rec_dev, 0, 4 * (size_t)max_iter * 8, st));
+    int64_t nent = 0, ncon = 0;
+    if (nd > 0) {
+        std::vector<int32_t> r32((size_t)nd);
+        for (int64_t i = 0; i < nd; ++i) r32[(size_t)i] = (int32_t)diode_rows[i];
+        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(isat_dev, isat, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(nvt_dev, nvt, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+        int32_t bad = 0;
+        NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
+        k_newton_check<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->type.as<uint8_t>(), isat_dev, nvt_dev, bad_dev);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copies above are done too)
+        if (bad & 1) return nodal_fail(h, NODAL_E_INVALID, "newton: a diode row that is not a resistor (R)");
+        if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, "newton: i_sat and n_vt must be positive and finite");
+        NODAL_TRY(grp::build_lists(h, DiodeLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), nd}, (int64_t)K, &nent,
+                                   &ncon, h->tr_none, h->tr_node, h->tr_ptr, h->tr_con, nullptr, nullptr));
+        k_newton_start<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), xk, vh_at(0));
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    NODAL_WAIT_STREAM(h, st);  // (x0 is the caller's, r32 ends here)
+    double *value = const_cast<double *>(assembled_values(h));
+
+    // ---- the iterations ----
+    bool dead = false, overflow = false;
+    int32_t done = 0;
+    for (int32_t k = 0; k < max_iter; ++k) {
+        double ms_stamp = 0.0, ms_begin = 0.0, ms_step = 0.0;
+        if (nd > 0) {  // (without diodes the matrix does not move: what the handle kept of it serves)
+            k_newton_linearise<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, isat_dev, nvt_dev, gmin, vh_at(k), value, hist,
+                                                                  gk, ik);
+            NODAL_HIP_TRY(h, hipGetLastError());
+            const auto t0 = std::chrono::steady_clock::now();
+            const int sn = stamp_numeric(h, h->member, nullptr);
+            ms_stamp = ms_since(t0);
+            if (sn == NODAL_E_ZERO_RESISTANCE) {  // (g overflowed: 1 / g == 0)
+                overflow = true;
+                done = k + 1;
+                break;
+            }
+            NODAL_TRY(sn);
+        }
+        NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)n * 8, st));
+        NODAL_TRY(stamp_rhs_multi(h, h->sw_slot.as<int32_t>(), h->sw_vals.as<double>(), nsrc, 1, bvec, 1, 0));
+        NODAL_TRY(signed_list_add(h, nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(), h->tr_con.as<uint32_t>(), hist, bvec));
+        // the route and its matrix work, anew: the matrix moved
+        TransientSolver ts;
+        ts.s = h;
+        ts.lu_epoch = &h->tr_lu_epoch;
+        ts.rvec = rvec;
+        ts.dvec = dvec;
+        ts.norms = norms;
+        NODAL_TRY(transient_solver_begin(h, ts, dense, 1, &dead, &ms_begin));
+        if (ts.route == TR_ROUTE_LU && ms_begin > 0.0) *ms_symbolic += slu_analysis_ms(h);
+        done = k + 1;
+        if (dead) {
+            *ms_matrix += ms_stamp + ms_begin;
+            break;
+        }
+        int32_t inf = 0, it = 0;
+        double resid = 0.0;
+        bool judged = false;  // resid is on the host already
+        NODAL_TRY(transient_solver_step(h, ts, bvec, xk, &inf, &it, &resid, &judged, &ms_step));
+        *ms_matrix += ms_stamp + ms_begin + ms_step;
+        if (ts.route == TR_ROUTE_MG && ts.mg_setup && !ts.direct && !sagg_refreshed(h)) *ms_symbolic += ms_step;
+        if (inf > 0) {
+            if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+            dead = true;
+            break;
+        }
+        if (out.iters) out.iters[k] = it;
+        h->last_iterations = it;
+        if (out.route)  // (a multigrid step handed on, or a sparse LU step redone: the sparse direct solve)
+            out.route[k] = ts.route == TR_ROUTE_DENSE ? 0 : (ts.direct || (ts.route == TR_ROUTE_LU && !judged)) ? 3
+                           : ts.route == TR_ROUTE_LU ? 1 : 2;
+        unsigned long long *rec = rec_dev + 4 * (size_t)k;
+        if (!judged) NODAL_HIP_TRY(h, hipMemcpyAsync(rec + 3, norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
+        if (nd > 0) {
+            k_newton_update<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), isat_dev,
+                                                               nvt_dev, gmin, reltol, vntol, abstol, xk, vh_at(k), gk, ik,
+                                                               vh_at(k + 1), rec);
+            NODAL_HIP_TRY(h, hipGetLastError());
+        }
+        if (out.iterates) NODAL_HIP_TRY(h, hipMemcpyAsync(out.iterates + (size_t)k * n, xk, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        unsigned long long words[4];
+        NODAL_TRY(nodal_read_words(h, words, rec, 32));  // (the iteration's one look at the device besides the solver's)
+        double dvmax, scaled;
+        memcpy(&dvmax, &words[2], 8);
+        memcpy(&scaled, &words[3], 8);
+        if (judged) scaled = resid;
+        if (out.record) {
+            double *row = out.record + 4 * (size_t)k;
+            row[0] = (double)words[0];
+            row[1] = (double)words[1];
+            row[2] = dvmax;
+            row[3] = scaled;
+        }
+        if (!(std::isfinite(dvmax) && std::isfinite(scaled))) break;  // (an iterate that overflowed: not converged)
+        if (words[0] == 0) {
+            *out.converged = 1;
+            break;
+        }
+    }
+    *out.iterations = done;
+
+    // ---- after the last iteration ----
+    if (overflow) {
+        // the value column holds a zero: 1.0 in every companion row and one more assembly, so that the handle stays usable
+        k_newton_fill<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, 1.0, value);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        NODAL_TRY(stamp_numeric(h, h->member, nullptr));
+    }
+    const bool lost = dead || overflow;  // no state to report
+    if (lost && done >= 1) {
+        if (out.info) out.info[done - 1] = dead ? 1 : 0;
+        if (out.record)
+            for (int q = 0; q < 4; ++q) out.record[4 * (size_t)(done - 1) + q] = nan;
+        if (out.iterates)
+            for (int64_t i = 0; i < n; ++i) out.iterates[(size_t)(done - 1) * n + i] = nan;
+    }
+    if (nd > 0 && !lost && (out.v || out.i || out.g)) {
+        k_newton_outputs<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), isat_dev,
+                                                            nvt_dev, gmin, xk, ans, ans + nd, ans + 2 * nd);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        if (out.v) NODAL_HIP_TRY(h, hipMemcpyAsync(out.v, ans, (size_t)nd * 8, hipMemcpyDeviceToHost, st));
+        if (out.i) NODAL_HIP_TRY(h, hipMemcpyAsync(out.i, ans + nd, (size_t)nd * 8, hipMemcpyDeviceToHost, st));
+        if (out.g) NODAL_HIP_TRY(h, hipMemcpyAsync(out.g, ans + 2 * nd, (size_t)nd * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (out.x && !lost) NODAL_HIP_TRY(h, hipMemcpyAsync(out.x, xk, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    // vh_0 .. vh_r, r the iterations whose update ran (a dead or overflowed iteration formed none)
+    const int32_t vh_rows = lost ? (done > 0 ? done : 1) : done + 1;
+    if (keep_vh && nd > 0) {
+        NODAL_HIP_TRY(h, hipMemcpyAsync(out.vh, vh_dev, (size_t)vh_rows * nd * 8, hipMemcpyDeviceToHost, st));
+    }
+    NODAL_WAIT_STREAM(h, st);
+    if (keep_vh)
+        for (size_t t = (size_t)vh_rows * nd; t < ((size_t)max_iter + 1) * nd; ++t) out.vh[t] = nan;
+    if (lost) {
+        if (out.x)
+            for (int64_t i = 0; i < n; ++i) out.x[i] = nan;
+        for (double *p : {out.v, out.i, out.g})
+            if (p)
+                for (int64_t d = 0; d < nd; ++d) p[d] = nan;
+    }
+    return NODAL_OK;
+}

@@ -2950,6 +2950,10 @@ bool sagg_ready(nodal_ctx *h, int64_t n) {
     SHierarchy *H = static_cast<SHierarchy *>(h->sagg);
     return H && H->ready && H->pool[0]->n == n;
 }
+bool sagg_refreshed(nodal_ctx *h) {
+    SHierarchy *H = static_cast<SHierarchy *>(h->sagg);
+    return H && H->ready && H->refreshed;
+}
 void sagg_invalidate(nodal_ctx *h) {
     if (h->sagg) static_cast<SHierarchy *>(h->sagg)->ready = false;
 }
