@@ -788,6 +788,50 @@ int nodal_debug_hierarchy_array(nodal_handle h, int32_t level, int32_t which, vo
  *   calibration state as it found them: a solve after it returns the bits of the same solve without it. */
 int nodal_debug_cycle_apply(nodal_handle h, int32_t mode, const double *r, const double *u, const double *frozen,
                             double *z, double *dots_out /* [2] or [2][16] */, int32_t *params_out /* [16] */);
+/* The plain-aggregation hierarchy (csrc/amg.hip: pairwise matching, aggregate-block smoother, K-cycle, LDS-resident
+ * tail) -- the one that takes what the smoothed hierarchy declines -- as the last setup left it, raw, and ONE application
+ * of its cycle: what tests/amg_reference.py states in numpy / scipy and tests/test_gpu_amg.py compares.  The hierarchy is
+ * the handle's own or, where the handle holds none, the one on the context of its reduced system (presolve or low-degree
+ * elimination, round after round).  NODAL_E_INVALID when the last sparse solve did not precondition with it (a dense or
+ * direct solve, one the smoothed hierarchy took, a matrix assembled anew since): level 0 aliases the context's CSR
+ * arrays, so a hierarchy is exported only while it is the live one.
+ * nodal_debug_amg_info: *nlev levels (<= 16); ints[l * 8 + k] per level l: 0 n, 1 nnz, 2 nc (rows of the next level; 0
+ *   on the last), 3 block (the level smooths with the aggregates' block inverses), 4 in_tail (the level runs inside the
+ *   tail kernel).  words[16]: 0 tail (first level inside the tail kernel, -1 none), 1 kmax, 2 coarse_direct (coarse_inv
+ *   exists), 3 block_smoother, 4 sweeps0, and the constants 5 BLOCK_MAX, 6 COARSEST_MAX, 7 K_MIN_ROWS,
+ *   8 SPLIT_PROLONG_MIN, 9 DOT_BLOCKS, 10 the tail's LDS budget in bytes, 11 STREAM_CAP, 12 LONG_PART, 13 the most
+ *   levels a tail holds.  reals[2]: theta (matching threshold), OMEGA (smoother weight).  tail[128], all zero without a
+ *   tail: 0 nlev, 1 o_inv, 2 o_C1, 3 o_V1, 4 image_bytes, 5 total_bytes, and per tail level k at [8 + 14 k]: n, nnz, nc,
+ *   o_data, o_dinv, o_indptr, o_memptr, o_indices, o_agg, o_mem, o_B, o_X, o_E, o_R (byte offsets into the tail's LDS;
+ *   the image is its first image_bytes).
+ * nodal_debug_amg_array: one device buffer of one level as raw bytes: the CSR matrix indptr (i32, n + 1) / indices (i32)
+ *   / data (f64), dinv (f64, n), agg (i32, n: node -> aggregate), memptr (i32, nc + 1) / mem (i32, n: aggregate ->
+ *   members), boff (u32, nc + 1: where each aggregate's block starts in binv, in doubles) and binv (the inverses of the
+ *   aggregates' diagonal blocks, m x m in member order, TRANSPOSED; an aggregate above BLOCK_MAX members holds its m
+ *   diagonal reciprocals).  A buffer the level does not have (agg / memptr / mem on the last level, boff / binv without
+ *   the block smoother) gives 0.  level == NODAL_AMG_LEVEL_COARSE_INV: coarse_inv, n_last x n_last row-major;
+ *   NODAL_AMG_LEVEL_TAIL_IMAGE: the packed image the tail kernel copies into LDS (`which` is ignored for both).
+ *   dst == NULL: the size only; otherwise capacity_bytes must cover it.  Both calls are stream waits and device-to-host
+ *   copies only: nothing is launched, nothing on the device is written.
+ * nodal_debug_amg_apply: exactly one cycle(level) from r to z -- host vectors of that level's n entries -- for a level
+ *   outside the tail; level 0 is the preconditioner's own call (one level only: z = dinv r).  params_out[16]: 0 nlev,
+ *   1 tail, 2 kmax, 3 coarse_direct, 4 block_smoother, 5 sweeps0, 6 level, 7 the level smooths by blocks, 8 its coarse
+ *   solve (0: none, the last level -- dense inverse or Jacobi; 1: the tail kernel; 2: direct / plain V hand-over; 3:
+ *   two-step K-cycle), 9 the partial sums per dot product behind the correction's coefficients (0: s1 = 1, s2 = 0),
+ *   10 prolongation in a launch of its own, 11 two Jacobi sweeps per side.  NODAL_E_INVALID also for an unknown level or
+ *   one inside the tail.  Scratch of its own or the cycle's, no kernel a solve does not launch; solution, right-hand
+ *   side, hierarchy arrays and factorisations stay as found: a solve after it returns the bits of the same solve
+ *   without it. */
+enum {
+    NODAL_AA_INDPTR = 0, NODAL_AA_INDICES = 1, NODAL_AA_DATA = 2, NODAL_AA_DINV = 3, NODAL_AA_AGG = 4,
+    NODAL_AA_MEMPTR = 5, NODAL_AA_MEM = 6, NODAL_AA_BOFF = 7, NODAL_AA_BINV = 8
+};
+enum { NODAL_AMG_LEVEL_COARSE_INV = -1, NODAL_AMG_LEVEL_TAIL_IMAGE = -2 };
+int nodal_debug_amg_info(nodal_handle h, int32_t *nlev, int64_t *ints /* [16][8] */, int64_t *words /* [16] */,
+                         double *reals /* [2] */, int64_t *tail /* [128] */);
+int nodal_debug_amg_array(nodal_handle h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes,
+                          int64_t *bytes_out);
+int nodal_debug_amg_apply(nodal_handle h, int32_t level, const double *r, double *z, int32_t *params_out /* [16] */);
 
 #ifdef __cplusplus
 }

@@ -95,7 +95,25 @@ SIGNATURES = {
     "nodal_debug_hierarchy_info": (C.c_int, [C.c_void_p, _i32p, _i64p, _f64p]),
     "nodal_debug_hierarchy_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
     "nodal_debug_cycle_apply": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
+    "nodal_debug_amg_info": (C.c_int, [C.c_void_p, _i32p, _i64p, _i64p, _f64p, _i64p]),
+    "nodal_debug_amg_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
+    "nodal_debug_amg_apply": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f64p, _i32p]),
 }
+
+# nodal_debug_amg_array: `which` in the header's order (NODAL_AA_*) with the item type of each buffer, the two special
+# level numbers, and the names of the words nodal_debug_amg_info / nodal_debug_amg_apply return
+AMG_ARRAYS = (("indptr", np.int32), ("indices", np.int32), ("data", np.float64), ("dinv", np.float64),
+              ("agg", np.int32), ("memptr", np.int32), ("mem", np.int32), ("boff", np.uint32), ("binv", np.float64))
+AMG_LEVEL_COARSE_INV = -1
+AMG_LEVEL_TAIL_IMAGE = -2
+AMG_LEVEL_INFO = ("n", "nnz", "nc", "block", "in_tail")
+AMG_WORDS = ("tail", "kmax", "coarse_direct", "block_smoother", "sweeps0", "BLOCK_MAX", "COARSEST_MAX", "K_MIN_ROWS",
+             "SPLIT_PROLONG_MIN", "DOT_BLOCKS", "TAIL_LDS_BUDGET", "STREAM_CAP", "LONG_PART", "TAIL_MAX_LEVELS")
+AMG_TAIL_WORDS = ("nlev", "o_inv", "o_C1", "o_V1", "image_bytes", "total_bytes")
+AMG_TAIL_LEVEL = ("n", "nnz", "nc", "o_data", "o_dinv", "o_indptr", "o_memptr", "o_indices", "o_agg", "o_mem",
+                  "o_B", "o_X", "o_E", "o_R")
+AMG_APPLY_PARAMS = ("nlev", "tail", "kmax", "coarse_direct", "block_smoother", "sweeps0", "level", "block", "handover",
+                    "nparts", "split_prolong", "two_sweeps")
 
 # nodal_debug_hierarchy_array: `which` in the header's order (NODAL_HA_*) with the item type of each buffer, and the
 # names of the sixteen info words of a level (nodal_debug_hierarchy_info)
@@ -819,6 +837,66 @@ class Handle:
                                                      _ptr(frozen, C.c_double) if frozen is not None else None,
                                                      _ptr(z, C.c_double), _ptr(dots, C.c_double), _ptr(params, C.c_int32)))
         return z, (None if mode == 0 else dots), {name: int(params[k]) for k, name in enumerate(CYCLE_PARAMS)}
+
+    def debug_amg(self):
+        """The plain-aggregation hierarchy (csrc/amg.hip) the last sparse solve preconditioned with, raw (testing
+        hook): (levels, info).  levels: one dict per level with the words of AMG_LEVEL_INFO and every buffer of
+        AMG_ARRAYS as a flat numpy array (empty where the level has none).  info: the words of AMG_WORDS, "theta",
+        "OMEGA", "coarse_inv" (flat, row-major; empty without one), "tail_image" (uint8; empty without a tail) and
+        "tdesc": None or the words of AMG_TAIL_WORDS plus "lv", a list of dicts of AMG_TAIL_LEVEL.  Nothing is
+        decoded here.  NodalHipError (NODAL_E_INVALID) when that solve used another preconditioner or none."""
+        nlev = C.c_int32(0)
+        ints = np.zeros((16, 8), dtype=np.int64)
+        words = np.zeros(16, dtype=np.int64)
+        reals = np.zeros(2, dtype=np.float64)
+        tail = np.zeros(128, dtype=np.int64)
+        self._check(self.lib.nodal_debug_amg_info(self._h, C.byref(nlev), _ptr(ints, C.c_int64), _ptr(words, C.c_int64),
+                                                  _ptr(reals, C.c_double), _ptr(tail, C.c_int64)))
+
+        def fetch(level, which, dtype):
+            size = C.c_int64(0)
+            self._check(self.lib.nodal_debug_amg_array(self._h, level, which, None, 0, C.byref(size)))
+            out = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+            if size.value:
+                self._check(self.lib.nodal_debug_amg_array(self._h, level, which, C.c_void_p(out.ctypes.data),
+                                                           out.nbytes, C.byref(size)))
+                assert size.value == out.nbytes
+            return out
+
+        levels = []
+        for l in range(nlev.value):
+            lv = {name: int(ints[l, k]) for k, name in enumerate(AMG_LEVEL_INFO)}
+            for which, (name, dtype) in enumerate(AMG_ARRAYS):
+                lv[name] = fetch(l, which, dtype)
+            levels.append(lv)
+        info = {name: int(words[k]) for k, name in enumerate(AMG_WORDS)}
+        info["theta"], info["OMEGA"] = float(reals[0]), float(reals[1])
+        info["coarse_inv"] = fetch(AMG_LEVEL_COARSE_INV, 0, np.float64)
+        info["tail_image"] = fetch(AMG_LEVEL_TAIL_IMAGE, 0, np.uint8)
+        info["tdesc"] = None
+        if info["tail"] >= 0:
+            td = {name: int(tail[k]) for k, name in enumerate(AMG_TAIL_WORDS)}
+            td["lv"] = [{name: int(tail[8 + 14 * k + j]) for j, name in enumerate(AMG_TAIL_LEVEL)}
+                        for k in range(td["nlev"])]
+            info["tdesc"] = td
+        return levels, info
+
+    def debug_amg_apply(self, r, level=0):
+        """z = ONE cycle of the plain-aggregation hierarchy at `level` (outside the tail) applied to r, nothing behind
+        it (testing hook; nodal_hip.h).  Returns (z, params): params a dict of AMG_APPLY_PARAMS."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.ndim == 1, r.shape
+        nlev, ints = C.c_int32(0), np.zeros((16, 8), dtype=np.int64)
+        words, reals, tail = np.zeros(16, dtype=np.int64), np.zeros(2), np.zeros(128, dtype=np.int64)
+        self._check(self.lib.nodal_debug_amg_info(self._h, C.byref(nlev), _ptr(ints, C.c_int64), _ptr(words, C.c_int64),
+                                                  _ptr(reals, C.c_double), _ptr(tail, C.c_int64)))
+        if 0 <= level < nlev.value:  # (the library reads the level's n entries; it answers for any other level itself)
+            assert r.shape[0] == ints[level, 0], (r.shape, int(ints[level, 0]))
+        z = np.full(r.shape, np.nan, dtype=np.float64)
+        params = np.zeros(16, dtype=np.int32)
+        self._check(self.lib.nodal_debug_amg_apply(self._h, level, _ptr(r, C.c_double), _ptr(z, C.c_double),
+                                                   _ptr(params, C.c_int32)))
+        return z, {name: int(params[k]) for k, name in enumerate(AMG_APPLY_PARAMS)}
 
     def download_x(self):
         x = host_empty(self.n, np.float64)

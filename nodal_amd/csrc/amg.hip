@@ -111,6 +111,8 @@ struct Hierarchy {
     bool block_smoother = false;  // aggregate-block Jacobi on the levels above the LDS tail (chosen at setup)
     double theta = 0.0;           // matching: a free node proposes only over links >= theta x its strongest
     int sweeps0 = 2;    // Jacobi sweeps before / after the coarse correction at level 0 (NODAL_AMG_SWEEPS0=1: one)
+    bool ready = false;  // the last setup ran to its end and no other solver has taken the context's matrix since
+                         // (amg_invalidate): what the testing hooks at the bottom of this file export
     TailDesc tdesc;
     DevBuf tail_image;
     // Level objects and scratch buffers outlive a setup: a solve rebuilds the hierarchy for new
@@ -133,6 +135,7 @@ struct Hierarchy {
     }
     void begin_setup() {
         levels.clear();
+        ready = false;
         tail = -1;
         coarse_direct = false;
     }
@@ -150,6 +153,7 @@ struct Hierarchy {
         coarse_inv.release();
         tail_image.release();
         tail = -1;
+        ready = false;
     }
 };
 
@@ -1351,6 +1355,7 @@ int amg_setup_csr(nodal_ctx *h, int64_t n0, int64_t nnz0, const int32_t *indptr,
         for (const Level *l : H->levels) fprintf(stderr, " %lld/%lld", (long long)l->A.n, (long long)l->A.nnz);
         fprintf(stderr, "  kmax %d tail %d\n", H->kmax, H->tail);
     }
+    H->ready = true;
     return NODAL_OK;
 }
 
@@ -1460,9 +1465,14 @@ int cycle(nodal_ctx *h, Hierarchy *H, int l, const double *b, double *out) {
             post_smooth<<<stream::grid_for_rows(n), TB, 0, st>>>(L->A, dinv, b, xp, out);
         }
     } else {
+        // (two sweeps: the fused launch's result is the first of them, as above.  Until the cycle was held to a host
+        // reference this branch ran ONE post-smoothing sweep after two pre-smoothing ones -- every point-mode level 0
+        // below SPLIT_PROLONG_MIN rows)
+        double *first = two_sweeps ? L->v(V_R2) : out;
         prolong_smooth<<<stream::grid_for_rows(n), TB, 0, st>>>(L->A, dinv, b, x, L->agg.as<int32_t>(),
                                                                c1, c2, C->part.as<double>(), nparts,
-                                                               out);
+                                                               first);
+        if (two_sweeps) post_smooth<<<stream::grid_for_rows(n), TB, 0, st>>>(L->A, dinv, b, first, out);
     }
     NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
@@ -1574,6 +1584,170 @@ int csr_has_floating_component(nodal_ctx *h, const uint8_t *grounded, int32_t *f
     cc_verdict<<<grid_for(n), TB, 0, st>>>(n, label, root_ok, flags + 1);
     NODAL_HIP_TRY(h, hipGetLastError());
     NODAL_HIP_TRY(h, hipMemcpyAsync(floating, flags + 1, 4, hipMemcpyDeviceToHost, st));
+    NODAL_WAIT_STREAM(h, st);
+    return NODAL_OK;
+}
+
+// ---- testing hooks (nodal_debug_amg_info / _array / _apply): the hierarchy as the setup left it, raw ----
+// Level 0 aliases the owner's CSR arrays and another solver may have taken a later solve, so the hierarchy counts only
+// while `ready` holds: amg_setup_csr sets it at its end, amg_invalidate clears it -- at the start of every sparse solve
+// (for the context and the contexts of its reduced systems), where the smoothed hierarchy or the structural check takes
+// the solve, and when the matrix is assembled anew.
+void amg_invalidate(nodal_ctx *h) {
+    for (int depth = 0; h && depth < 256; ++depth) {  // (the chain of low-degree rounds: 48 at the most)
+        if (h->amg) static_cast<Hierarchy *>(h->amg)->ready = false;
+        if (h->reduced) amg_invalidate(h->reduced);
+        h = h->lowdeg;
+    }
+}
+
+namespace {
+
+// the context's own hierarchy or, where it holds none, the one of its reduced system (presolve.hip: h->reduced,
+// lowdeg.hip: h->lowdeg, round after round); all of them share the handle's stream.  *owner: the context it belongs to
+Hierarchy *debug_amg(nodal_ctx *h, nodal_ctx **owner) {
+    for (int depth = 0; h && depth < 256; ++depth) {
+        Hierarchy *H = static_cast<Hierarchy *>(h->amg);
+        if (H && H->ready && !H->levels.empty() && (int)H->levels.size() <= MAX_LEVELS) {
+            *owner = h;
+            return H;
+        }
+        if (h->reduced)
+            if (Hierarchy *R = debug_amg(h->reduced, owner)) return R;
+        h = h->lowdeg;
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+int amg_debug_info(nodal_ctx *h, int32_t *nlev, int64_t *ints, int64_t *words, double *reals, int64_t *tail) {
+    nodal_ctx *c = nullptr;
+    Hierarchy *H = debug_amg(h, &c);
+    if (!H) return nodal_fail(h, NODAL_E_INVALID, "debug amg: the last sparse solve did not use the plain-aggregation hierarchy");
+    const int nl = (int)H->levels.size();
+    *nlev = nl;
+    memset(ints, 0, sizeof(int64_t) * MAX_LEVELS * 8);
+    memset(words, 0, sizeof(int64_t) * 16);
+    memset(tail, 0, sizeof(int64_t) * 128);
+    for (int l = 0; l < nl; ++l) {
+        const Level *L = H->levels[l];
+        int64_t *w = ints + (size_t)l * 8;
+        w[0] = L->A.n; w[1] = L->A.nnz; w[2] = l + 1 < nl ? L->nc : 0; w[3] = L->block;
+        w[4] = H->tail >= 0 && l >= H->tail;
+    }
+    words[0] = H->tail; words[1] = H->kmax; words[2] = H->coarse_direct; words[3] = H->block_smoother;
+    words[4] = H->sweeps0; words[5] = BLOCK_MAX; words[6] = COARSEST_MAX; words[7] = K_MIN_ROWS;
+    words[8] = SPLIT_PROLONG_MIN; words[9] = DOT_BLOCKS; words[10] = TAIL_LDS_BUDGET; words[11] = stream::STREAM_CAP;
+    words[12] = stream::LONG_PART; words[13] = TAIL_MAX_LEVELS;
+    reals[0] = H->theta;
+    reals[1] = OMEGA;
+    if (H->tail >= 0) {
+        const TailDesc &d = H->tdesc;
+        tail[0] = d.nlev; tail[1] = d.o_inv; tail[2] = d.o_C1; tail[3] = d.o_V1; tail[4] = d.image_bytes;
+        tail[5] = d.total_bytes;
+        for (int k = 0; k < d.nlev && k < TAIL_MAX_LEVELS; ++k) {
+            const TailLevel &t = d.lv[k];
+            const int v[14] = {t.n, t.nnz, t.nc, t.o_data, t.o_dinv, t.o_indptr, t.o_memptr, t.o_indices, t.o_agg, t.o_mem,
+                               t.o_B, t.o_X, t.o_E, t.o_R};
+            for (int j = 0; j < 14; ++j) tail[8 + k * 14 + j] = v[j];
+        }
+    }
+    return NODAL_OK;
+}
+
+int amg_debug_array(nodal_ctx *h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out) {
+    nodal_ctx *c = nullptr;
+    Hierarchy *H = debug_amg(h, &c);
+    if (!H) return nodal_fail(h, NODAL_E_INVALID, "debug amg: the last sparse solve did not use the plain-aggregation hierarchy");
+    hipStream_t st = c->stream;
+    const int nl = (int)H->levels.size();
+    const void *src = nullptr;
+    int64_t bytes = 0;
+    size_t cap = 0;  // what the owning buffer holds (0: not one of the hierarchy's own, level 0's matrix)
+    auto owned = [&](const DevBuf &b, int64_t nbytes) { src = b.p; cap = b.cap; bytes = nbytes; };
+    if (level == NODAL_AMG_LEVEL_COARSE_INV) {
+        const int64_t n = H->levels.back()->A.n;
+        owned(H->coarse_inv, H->coarse_direct ? n * n * 8 : 0);
+    } else if (level == NODAL_AMG_LEVEL_TAIL_IMAGE) {
+        owned(H->tail_image, H->tail >= 0 ? H->tdesc.image_bytes : 0);
+    } else {
+        if (level < 0 || level >= nl) return nodal_fail(h, NODAL_E_INVALID, "debug amg: no such level");
+        const Level *L = H->levels[level];
+        const bool next = level + 1 < nl;
+        const int64_t n = L->A.n, nnz = L->A.nnz, nc = next ? L->nc : 0;
+        switch (which) {
+        case NODAL_AA_INDPTR: src = L->A.indptr; bytes = (n + 1) * 4; break;
+        case NODAL_AA_INDICES: src = L->A.indices; bytes = nnz * 4; break;
+        case NODAL_AA_DATA: src = L->A.data; bytes = nnz * 8; break;
+        case NODAL_AA_DINV: owned(L->dinv, n * 8); break;
+        case NODAL_AA_AGG: owned(L->agg, next ? n * 4 : 0); break;
+        case NODAL_AA_MEMPTR: owned(L->memptr, next ? (nc + 1) * 4 : 0); break;
+        case NODAL_AA_MEM: owned(L->mem, next ? n * 4 : 0); break;
+        case NODAL_AA_BOFF: owned(L->boff, L->block ? (nc + 1) * 4 : 0); break;
+        case NODAL_AA_BINV: {
+            uint32_t total = 0;  // the scan's last word: the doubles the blocks of this level take
+            if (L->block) {
+                if (!L->boff.p || (size_t)(nc + 1) * 4 > L->boff.cap)
+                    return nodal_fail(h, NODAL_E_INVALID, "debug amg: the level's buffer is smaller than its extent");
+                NODAL_WAIT_STREAM(h, st);
+                NODAL_HIP_TRY(h, hipMemcpyAsync(&total, L->boff.as<uint32_t>() + nc, 4, hipMemcpyDeviceToHost, st));
+                NODAL_WAIT_STREAM(h, st);
+            }
+            owned(L->binv, (int64_t)total * 8);
+            break;
+        }
+        default: return nodal_fail(h, NODAL_E_INVALID, "debug amg: no such array");
+        }
+    }
+    if (bytes < 0 || (bytes > 0 && (!src || (cap && (size_t)bytes > cap))))
+        return nodal_fail(h, NODAL_E_INVALID, "debug amg: the level's buffer is smaller than its extent");
+    *bytes_out = bytes;
+    if (!dst || bytes == 0) return NODAL_OK;
+    if (capacity_bytes < bytes) return nodal_fail(h, NODAL_E_INVALID, "debug amg: destination too small");
+    NODAL_WAIT_STREAM(h, st);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, st));
+    NODAL_WAIT_STREAM(h, st);
+    return NODAL_OK;
+}
+
+// ONE cycle(h, H, level, r, z) on the caller's host vector (level 0: amg_apply, the one-level Jacobi case included).  The
+// vectors live in the owner's dbg_apply; the cycle's own scratch (every level's `vec` and `part`) is written before it is
+// read in every visit, so a solve after the call computes what it would have computed without it.
+int amg_debug_apply(nodal_ctx *h, int32_t level, const double *r, double *z, int32_t *params_out) {
+    nodal_ctx *c = nullptr;
+    Hierarchy *H = debug_amg(h, &c);
+    if (!H) return nodal_fail(h, NODAL_E_INVALID, "debug amg: the last sparse solve did not use the plain-aggregation hierarchy");
+    const int nl = (int)H->levels.size();
+    if (level < 0 || level >= nl) return nodal_fail(h, NODAL_E_INVALID, "debug amg: no such level");
+    if (H->tail >= 0 && level >= H->tail)
+        return nodal_fail(h, NODAL_E_INVALID, "debug amg: the level runs inside the tail kernel");
+    const Level *L = H->levels[level];
+    const int64_t n = L->A.n;
+    if (params_out) {
+        int32_t *p = params_out;
+        for (int k = 0; k < 16; ++k) p[k] = 0;
+        const bool last = level == nl - 1;
+        const bool coarse_is_last = level + 1 == nl - 1;
+        p[0] = nl; p[1] = H->tail; p[2] = H->kmax; p[3] = H->coarse_direct; p[4] = H->block_smoother; p[5] = H->sweeps0;
+        p[6] = level; p[7] = !last && L->block;
+        p[8] = last ? 0 : level + 1 == H->tail ? 1 : (coarse_is_last || level + 1 > H->kmax) ? 2 : 3;
+        p[9] = p[8] == 1 ? 1 : p[8] == 3 ? (int32_t)dot_grid(H->levels[level + 1]->A.n) : 0;
+        p[10] = !last && n >= SPLIT_PROLONG_MIN;
+        p[11] = !last && !L->block && level == 0 && H->sweeps0 == 2;
+    }
+    hipStream_t st = c->stream;
+    NODAL_WAIT_STREAM(h, st);
+    const size_t vec = ((size_t)n * 8 + 255) & ~(size_t)255;
+    NODAL_HIP_TRY(h, c->dbg_apply.reserve(2 * vec + 256));
+    double *dr = c->dbg_apply.as<double>(), *dz = dr + vec / 8;
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dr, r, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    const int rc = level == 0 ? amg_apply(c, dr, dz) : cycle(c, H, level, dr, dz);
+    if (rc != NODAL_OK) {
+        if (c != h) h->err = c->err;
+        return rc;
+    }
+    NODAL_HIP_TRY(h, hipMemcpyAsync(z, dz, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     NODAL_WAIT_STREAM(h, st);
     return NODAL_OK;
 }

@@ -1175,6 +1175,28 @@ int nodal_debug_cycle_apply(nodal_handle h, int32_t mode, const double *r, const
     return sagg_debug_cycle_apply(h, mode, r, u, frozen, z, dots_out, params_out);
 }
 
+int nodal_debug_amg_info(nodal_handle h, int32_t *nlev, int64_t *ints, int64_t *words, double *reals, int64_t *tail) {
+    if (!h || !nlev || !ints || !words || !reals || !tail) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return amg_debug_info(h, nlev, ints, words, reals, tail);
+}
+
+int nodal_debug_amg_array(nodal_handle h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes,
+                          int64_t *bytes_out) {
+    if (!h || !bytes_out) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return amg_debug_array(h, level, which, dst, capacity_bytes, bytes_out);
+}
+
+int nodal_debug_amg_apply(nodal_handle h, int32_t level, const double *r, double *z, int32_t *params_out) {
+    if (!h || !r || !z) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return amg_debug_apply(h, level, r, z, params_out);
+}
+
 int nodal_residual(nodal_handle h, double *scaled_residual) {
     if (!h || !scaled_residual) return NODAL_E_INVALID;
     DeviceGuard g(h);

@@ -758,6 +758,14 @@ int amg_apply(nodal_ctx *h, const double *r, double *z);
 int amg_num_levels(nodal_ctx *h);
 int64_t amg_level_size(nodal_ctx *h, int level);
 void amg_destroy(nodal_ctx *h);
+// another solver takes the matrix (or the matrix changes): the hierarchies of h and of its reduced systems are no longer
+// what the last solve preconditioned with.  Only the testing hooks below look at this.
+void amg_invalidate(nodal_ctx *h);
+// testing hooks (nodal_debug_amg_info / nodal_debug_amg_array / nodal_debug_amg_apply): sizes, raw device buffers and
+// one application of cycle() at a level outside the tail
+int amg_debug_info(nodal_ctx *h, int32_t *nlev, int64_t *ints, int64_t *words, double *reals, int64_t *tail);
+int amg_debug_array(nodal_ctx *h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
+int amg_debug_apply(nodal_ctx *h, int32_t level, const double *r, double *z, int32_t *params_out);
 void sagg_destroy(nodal_ctx *h);
 // smoothed-aggregation FCG (sagg.hip): NODAL_OK, -1 breakdown, -2 structurally singular,
 // -3 declined (not this hierarchy's kind of network: use amg.hip)

@@ -483,6 +483,7 @@ int amg_fcg_solve_ex(nodal_ctx *h, const double *b, bool do_setup, int32_t *info
             sagg_invalidate(h);
             do_setup = true;
         } else if (s != -3) {
+            amg_invalidate(h);  // (the smoothed hierarchy took the matrix)
             return s;
         }
     }
@@ -525,6 +526,7 @@ int amg_fcg_solve_ex(nodal_ctx *h, const double *b, bool do_setup, int32_t *info
         int32_t floating = 0;
         NODAL_TRY(amg_has_floating_component(h, h->work3.as<uint8_t>(), &floating));
         if (floating) {
+            amg_invalidate(h);  // (set up, but nothing is preconditioned with it)
             *info = 1;
             *iters = 0;
             *resid = 0.0;
@@ -1330,6 +1332,7 @@ int sparse_solve(nodal_ctx *h, int32_t method, int32_t *info, int32_t *iters, do
     *iters = 0;
     *resid = 0.0;
     h->have_x = false;
+    amg_invalidate(h);  // (whichever solver takes this solve: only amg_setup_csr makes a hierarchy the live one again)
     if (n == 0) {
         h->have_x = true;
         return NODAL_OK;

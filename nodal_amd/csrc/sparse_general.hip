@@ -554,6 +554,7 @@ int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_
     // diagonal had to be added): its ELL copy serves the Krylov SpMV too (13 instead of 22 us at 1e6 rows)
     ell_spmv = use_sa && K == (int)n && gn_nnz == (uint32_t)h->nnz;
     if (use_sa) {
+        amg_invalidate(h);
         h->amg_levels = sagg_levels(h);
     } else {
         NODAL_TRY(amg_setup_csr(h, K, gn_nnz, h->gn_indptr.as<int32_t>(), h->gn_indices.as<int32_t>(),

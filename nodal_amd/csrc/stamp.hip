@@ -370,6 +370,7 @@ Table table_of(nodal_ctx *h) {
 int stamp_symbolic(nodal_ctx *h) {
     if (!h->have_table) return nodal_fail(h, NODAL_E_INVALID, "no component table uploaded");
     h->have_symbolic = h->have_numeric = h->have_x = false;
+    amg_invalidate(h);
     ++h->struct_epoch;
     const int64_t n = h->n;
     const Table tb = table_of(h);
@@ -418,6 +419,7 @@ int stamp_numeric(nodal_ctx *h, int32_t member, int64_t *bad_component) {
         return nodal_fail(h, NODAL_E_INVALID, "batch member out of range");
     hipStream_t st = h->stream;
     ++h->numeric_epoch;  // (what a transient call kept of G's values -- hierarchy, factors -- is void)
+    amg_invalidate(h);   // (level 0 of the plain-aggregation hierarchy aliases the arrays written below)
     const Table tb = table_of(h);
     const double *value =
         h->batch > 0 ? h->values_batch.as<double>() + (int64_t)member * h->ncomp : tb.value;

@@ -665,24 +665,36 @@ def test_multigrid_block_smoother_on_high_contrast_grid(decades, monkeypatch, ca
     h.close()
 
 
-def test_multigrid_block_smoother_forced_on_uniform_and_general_networks(monkeypatch):
+def test_multigrid_block_smoother_forced_on_uniform_and_general_networks(tmp_path):
     """NODAL_AMG_BLOCK=1: the block smoother on networks that would not select it -- a uniform
     grid (multigrid CG) and config 5 in miniature (presolve + FGMRES preconditioned by the
-    multigrid on the node block)."""
+    multigrid on the node block).
+
+    The smoothed hierarchy (csrc/sagg.hip) takes both networks first and does not read NODAL_AMG_BLOCK: with NODAL_TRACE
+    this test was seen to build `[sagg] levels` twice and not one block.  NODAL_SAGG is read once per process, so the two
+    solves run in a child process (tests/amg_child.py) with NODAL_SAGG=0, and the trace pins the route."""
+    import os
+    import subprocess
+    import sys
     from nodal_amd import generators as gen
     from oracle import nodal_oracle as oracle
-    monkeypatch.setenv("NODAL_AMG_BLOCK", "1")
-    for table in (gen.grid_table(80), gen.cfg5_table(90)):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, NODAL_SAGG="0", NODAL_TRACE="1")
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "amg_child.py"), str(tmp_path), "--forced-block"],
+                       env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "amg child ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    traces = r.stderr.split("[child] ")[1:]
+    assert [t.split()[0] for t in traces] == ["grid80", "cfg5_90"]
+    for t in traces:
+        assert "[amg] blocks:" in t and "[sagg] levels" not in t, t[-2000:]
+    with np.load(tmp_path / "forced_block.npz") as f:
+        data = {k: f[k] for k in f.files}
+    for name, table in (("grid80", gen.grid_table(80)), ("cfg5_90", gen.cfg5_table(90))):
         G, A = oracle.assemble_fast(table)
         xo, _ = oracle.solve(G.tocsr(), A, True)
-        h = _ffi.Handle(0)
-        h.upload(table)
-        h.assemble_symbolic()
-        assert h.assemble_numeric()[0] == _ffi.OK
-        x, info, iters, _ = h.solve_sparse()
-        assert info == 0 and iters > 0 and h.residual() <= 1e-12
+        x, info, iters, residual = (data[f"{name}.{k}"] for k in ("x", "info", "iters", "residual"))
+        assert info == 0 and iters > 0 and residual <= 1e-12
         assert np.abs(x - xo).max() <= 1e-9 * np.abs(xo).max()
-        h.close()
 
 
 def test_multigrid_contrast_mode_with_a_hub(monkeypatch, capfd):
@@ -757,8 +769,10 @@ def test_expander_like_network_keeps_the_jacobi_preconditioner(monkeypatch, capf
 def test_hub_node_with_thousands_of_neighbours():
     """A node tied to 4000 nodes of a grid: its row block exceeds what the CSR-stream kernels
     stage at once (chunked walk, the hub's row summed by the whole workgroup), its aggregate
-    has thousands of members (restriction through the same pattern), and its coarse images
-    keep their levels out of the LDS tail."""
+    has hundreds of members (797 seen through the hierarchy export: most spokes pair up among
+    themselves before the leftovers join the hub; restriction through the same pattern), and its
+    coarse images keep level 1 out of the LDS tail (rows of 1312 entries: plain-aggregation
+    hierarchy, point mode, levels 14401 / 1344 / 124 / 54, tail 2)."""
     from nodal_amd import generators as gen
     from oracle import nodal_oracle as oracle
     side = 120
