@@ -695,6 +695,37 @@ int nodal_set_option(nodal_handle h, int32_t option, int32_t value);
  * kernel; host buffers, column-major, leading dimensions M, K, M. */
 int nodal_debug_gemm(nodal_handle h, int32_t M, int32_t N, int32_t K, const double *A,
                      const double *B, double *C);
+/* The dense path's pieces on host arrays of the caller's choosing (column-major): copied into the handle's scratch WITH
+ * their padding rows, handed to the production function, copied back.  No arithmetic and no environment knob of their own.
+ *
+ * nodal_debug_gemm_ex: every entry point of gemm_f64.hip with the caller's leading dimensions.
+ *   kind 0: gemm_f64 -- C (op)= A B, A: lda x K, B: ldb x N, C: ldc x N; mode 0 C -= A B, 1 C = A B, 2 C = -A B.
+ *   kind 1: gemm_sub_tn_upper_f64 -- C -= At^T B for the upper block triangle of C, the diagonal blocks of `band` rows
+ *           (a multiple of 128) whole; A is the K x M panel At (lda >= K, M columns); mode must be 0.
+ *   kind 2: gemm_pair_f64 -- the first problem and (M2 .. ldc2) a second one in one launch, both in `mode`.
+ *   C (and C2) come back whole, padding rows included.  band is read by kind 1 only, the second problem by kind 2 only. */
+int nodal_debug_gemm_ex(nodal_handle h, int32_t kind, int32_t mode, int32_t band, int32_t M, int32_t N, int32_t K,
+                        const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int32_t M2,
+                        int32_t N2, int32_t K2, const double *A2, int64_t lda2, const double *B2, int64_t ldb2, double *C2,
+                        int64_t ldc2);
+/* nodal_debug_block_inverse: the block elimination's inverse of a diagonal block (block_elim.hip: one Gauss-Jordan
+ *   workgroup up to w = 128, the 2 x 2 Schur formula above, 1 <= w <= 512) on A (lda x w).  Q (ldq x w) goes up as the
+ *   caller filled it and comes back with the inverse in its leading w rows; *dinfo_out is 0 or `base` + the 1-based column
+ *   of the first zero (or NaN) pivot.  variant: 0 rank-16 steps with DPP lane exchanges (the default form), 1 rank-16
+ *   steps with bpermute exchanges (NODAL_GJ_DPP=0), 2 rank-4 steps (NODAL_GJ_SCALAR=2), 3 scalar steps (NODAL_GJ_SCALAR=1).
+ *   The handle's own choice is put back afterwards. */
+int nodal_debug_block_inverse(nodal_handle h, int32_t w, const double *A, int64_t lda, int32_t base, int32_t variant,
+                              double *Q, int64_t ldq, int32_t *dinfo_out);
+/* nodal_debug_dense_solve: dense_factor_solve_multi on A (n x n, leading dimension n) and B (n x nrhs) without any
+ *   stamping, in the library's padded panel (padding rows filled with NaN).  route: the flags the dispatcher reads, set for
+ *   this call and put back afterwards -- bit 0 passive (symmetric positive definite: no pivoting; above 256 unknowns the
+ *   symmetric block elimination), bit 1 optimistic (no pivoting, the full block elimination), bit 2 force pivoting.
+ *   X (n x nrhs), *info_out as dgesv.  ipiv_out[n]: the caller passes the identity 0 .. n-1; it comes back as the
+ *   0-based LAPACK interchange list (row c was swapped with row ipiv[c]) of the pivoting routes and untouched otherwise.
+ *   Overwrites the handle's dense panel and pivots (scratch of every dense solve); the table, the assembled system and
+ *   the solution stay. */
+int nodal_debug_dense_solve(nodal_handle h, int32_t n, int32_t nrhs, int32_t route, const double *A, const double *B,
+                            double *X, int32_t *info_out, int32_t *ipiv_out);
 /* the rhs columns nodal_solve_sources builds for the same arguments, [count][n] row-major */
 int nodal_debug_sources_rhs(nodal_handle h, int32_t count, int32_t nsrc, const int64_t *rows,
                             const double *values, double *rhs_out);

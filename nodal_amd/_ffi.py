@@ -89,6 +89,12 @@ SIGNATURES = {
     "nodal_synchronize": (C.c_int, [C.c_void_p]),
     "nodal_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "nodal_debug_gemm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p]),
+    "nodal_debug_gemm_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, _f64p, C.c_int64, _f64p, C.c_int64, _f64p, C.c_int64,
+                                      C.c_int32, C.c_int32, C.c_int32, _f64p, C.c_int64, _f64p, C.c_int64, _f64p, C.c_int64]),
+    "nodal_debug_block_inverse": (C.c_int, [C.c_void_p, C.c_int32, _f64p, C.c_int64, C.c_int32, C.c_int32, _f64p, C.c_int64,
+                                            _i32p]),
+    "nodal_debug_dense_solve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _i32p, _i32p]),
     "nodal_debug_sources_rhs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i64p, _f64p, _f64p]),
     "nodal_debug_residual": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p]),
     "nodal_debug_direct_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p, _i64p, _i32p]),
@@ -955,6 +961,64 @@ class Handle:
                                               _ptr(A, C.c_double), _ptr(B, C.c_double),
                                               _ptr(out, C.c_double)))
         return out
+
+    # nodal_debug_gemm_ex: kind and mode in the header's order
+    GEMM_KINDS = ("plain", "tn_upper", "pair")
+    GEMM_MODES = ("sub", "set", "setneg")
+    # nodal_debug_block_inverse: variant in the header's order
+    INVERSE_VARIANTS = ("rank16_dpp", "rank16_bpermute", "rank4", "scalar")
+
+    def debug_gemm_ex(self, kind, mode, sizes, A, B, Cm, band=128, second=None):
+        """An entry point of gemm_f64.hip on arrays whose row counts ARE the leading dimensions (testing hook): sizes =
+        (M, N, K), A [lda, K] (kind "tn_upper": the K x M panel, [lda, M]), B [ldb, N], Cm [ldc, N].  kind "pair":
+        second = (sizes2, A2, B2, C2).  Returns the whole C image(s), padding rows included."""
+        def prep(sizes, A_, B_, C_):
+            A_, B_ = (np.asfortranarray(x, dtype=np.float64) for x in (A_, B_))
+            out = np.array(C_, dtype=np.float64, order="F", copy=True)
+            M, N, K = sizes
+            assert B_.shape[1] == N and out.shape[1] == N and A_.shape[1] == (M if kind == "tn_upper" else K)
+            return [M, N, K, _ptr(A_, C.c_double), A_.shape[0], _ptr(B_, C.c_double), B_.shape[0],
+                    _ptr(out, C.c_double), out.shape[0]], (A_, B_, out)
+        a0, keep0 = prep(sizes, A, B, Cm)
+        if second is not None:
+            a1, keep1 = prep(*second)
+        else:
+            a1, keep1 = [0, 0, 0, None, 0, None, 0, None, 0], (None, None, None)
+        self._check(self.lib.nodal_debug_gemm_ex(self._h, self.GEMM_KINDS.index(kind), self.GEMM_MODES.index(mode), band,
+                                                 *a0, *a1))
+        return keep0[2] if second is None else (keep0[2], keep1[2])
+
+    def debug_block_inverse(self, A, w, variant, base=0, Q=None):
+        """invert_diag of block_elim.hip on the leading w x w block of the Fortran-ordered A [lda, w] (testing hook).  Q
+        [ldq, w] goes up as given (default: NaN) and comes back with the inverse; returns (Q, dinfo)."""
+        A = np.asfortranarray(A, dtype=np.float64)
+        out = np.full((w, w), np.nan, order="F") if Q is None else np.array(Q, dtype=np.float64, order="F", copy=True)
+        assert A.shape[1] == w and out.shape[1] == w
+        dinfo = C.c_int32(0)
+        self._check(self.lib.nodal_debug_block_inverse(self._h, w, _ptr(A, C.c_double), A.shape[0], base,
+                                                       self.INVERSE_VARIANTS.index(variant), _ptr(out, C.c_double),
+                                                       out.shape[0], C.byref(dinfo)))
+        return out, dinfo.value
+
+    def debug_dense_solve(self, A, B, passive=False, optimistic=False, force_pivoting=False):
+        """dense_factor_solve_multi on A [n, n] and B [n, nrhs] with the dispatcher's route flags (testing hook).
+        Returns (X [n, nrhs], info, rows): rows[i] = the original row that stands at position i after the interchanges
+        the route applied (the identity for the routes that do not pivot)."""
+        A = np.asfortranarray(A, dtype=np.float64)
+        B = np.asfortranarray(B, dtype=np.float64)
+        n, nrhs = B.shape
+        assert A.shape == (n, n)
+        X = np.full((n, nrhs), np.nan, order="F")
+        ipiv = np.arange(n, dtype=np.int32)
+        info = C.c_int32(0)
+        route = int(bool(passive)) | int(bool(optimistic)) << 1 | int(bool(force_pivoting)) << 2
+        self._check(self.lib.nodal_debug_dense_solve(self._h, n, nrhs, route, _ptr(A, C.c_double), _ptr(B, C.c_double),
+                                                     _ptr(X, C.c_double), C.byref(info), _ptr(ipiv, C.c_int32)))
+        rows = np.arange(n)
+        for c, p in enumerate(ipiv):
+            if p != c:
+                rows[c], rows[p] = rows[p], rows[c]
+        return X, info.value, rows
 
     def solve_info(self):
         """(iterations, multigrid levels, relative residual) of the last sparse solve."""

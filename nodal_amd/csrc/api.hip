@@ -1300,6 +1300,142 @@ int nodal_debug_gemm(nodal_handle h, int32_t M, int32_t N, int32_t K, const doub
     return NODAL_OK;
 }
 
+}  // extern "C"
+
+// ---- testing hooks of the dense path's pieces (gemm_f64.hip, block_elim.hip, dense_lu.hip): host arrays into scratch,
+// the production function, the results back.  No arithmetic here. ----
+namespace {
+
+inline size_t dbg_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+struct DebugGemmOperands {
+    const double *A, *B;
+    double *C;
+    int64_t lda, ldb, ldc, acols;  // acols: columns of the host image of A (K, or M for the transposed panel)
+    int32_t M, N, K;
+    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    size_t bytes() const { return dbg_pad((size_t)lda * acols * 8) + dbg_pad((size_t)ldb * N * 8) + dbg_pad((size_t)ldc * N * 8); }
+    int up(nodal_ctx *h, char *&w) {
+        dA = reinterpret_cast<double *>(w);
+        w += dbg_pad((size_t)lda * acols * 8);
+        dB = reinterpret_cast<double *>(w);
+        w += dbg_pad((size_t)ldb * N * 8);
+        dC = reinterpret_cast<double *>(w);
+        w += dbg_pad((size_t)ldc * N * 8);
+        NODAL_HIP_TRY(h, hipMemcpyAsync(dA, A, (size_t)lda * acols * 8, hipMemcpyHostToDevice, h->stream));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(dB, B, (size_t)ldb * N * 8, hipMemcpyHostToDevice, h->stream));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(dC, C, (size_t)ldc * N * 8, hipMemcpyHostToDevice, h->stream));
+        return NODAL_OK;
+    }
+    int down(nodal_ctx *h) {
+        NODAL_HIP_TRY(h, hipMemcpyAsync(C, dC, (size_t)ldc * N * 8, hipMemcpyDeviceToHost, h->stream));
+        return NODAL_OK;
+    }
+};
+
+}  // namespace
+
+size_t dense_debug_inverse_scratch();  // block_elim.hip
+int dense_debug_block_inverse(nodal_ctx *h, double *D, int64_t lda, int w, double *Q, int64_t ldq, double *scratch,
+                              int32_t *dinfo, int base, int variant);
+
+extern "C" {
+
+int nodal_debug_gemm_ex(nodal_handle h, int32_t kind, int32_t mode, int32_t band, int32_t M, int32_t N, int32_t K,
+                        const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int32_t M2,
+                        int32_t N2, int32_t K2, const double *A2, int64_t lda2, const double *B2, int64_t ldb2, double *C2,
+                        int64_t ldc2) {
+    if (!h) return NODAL_E_INVALID;
+    if (kind < 0 || kind > 2 || mode < GEMM_SUB || mode > GEMM_SETNEG || M < 1 || N < 1 || K < 1 || !A || !B || !C ||
+        lda < (kind == 1 ? K : M) || ldb < K || ldc < M || (kind == 1 && mode != GEMM_SUB))
+        return nodal_fail(h, NODAL_E_INVALID, "debug_gemm_ex: kind, mode, sizes or leading dimensions");
+    if (kind == 2 && (M2 < 1 || N2 < 1 || K2 < 1 || !A2 || !B2 || !C2 || lda2 < M2 || ldb2 < K2 || ldc2 < M2))
+        return nodal_fail(h, NODAL_E_INVALID, "debug_gemm_ex: the second problem's sizes or leading dimensions");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    DebugGemmOperands p{A, B, C, lda, ldb, ldc, kind == 1 ? M : K, M, N, K};
+    DebugGemmOperands q{A2, B2, C2, lda2, ldb2, ldc2, K2, M2, N2, K2};
+    NODAL_HIP_TRY(h, h->work.reserve(p.bytes() + (kind == 2 ? q.bytes() : 0) + 256));
+    char *w = h->work.as<char>();
+    NODAL_TRY(p.up(h, w));
+    if (kind == 2) NODAL_TRY(q.up(h, w));
+    if (kind == 0) NODAL_TRY(gemm_f64(h, h->stream, mode, p.dC, ldc, p.dA, lda, p.dB, ldb, M, N, K));
+    else if (kind == 1) NODAL_TRY(gemm_sub_tn_upper_f64(h, h->stream, p.dC, ldc, p.dA, lda, p.dB, ldb, M, N, K, band));
+    else
+        NODAL_TRY(gemm_pair_f64(h, h->stream, mode, GemmProblem{p.dC, ldc, p.dA, lda, p.dB, ldb, M, N, K},
+                                GemmProblem{q.dC, ldc2, q.dA, lda2, q.dB, ldb2, M2, N2, K2}));
+    NODAL_TRY(p.down(h));
+    if (kind == 2) NODAL_TRY(q.down(h));
+    NODAL_WAIT_STREAM(h, h->stream);
+    return NODAL_OK;
+}
+
+int nodal_debug_block_inverse(nodal_handle h, int32_t w, const double *A, int64_t lda, int32_t base, int32_t variant,
+                              double *Q, int64_t ldq, int32_t *dinfo_out) {
+    if (!h || !A || !Q || !dinfo_out || w < 1 || lda < w || ldq < w) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    const size_t sa = dbg_pad((size_t)lda * w * 8), sq = dbg_pad((size_t)ldq * w * 8);
+    const size_t st = dbg_pad(dense_debug_inverse_scratch() * 8);
+    NODAL_HIP_TRY(h, h->work.reserve(sa + sq + st + 512));
+    char *wk = h->work.as<char>();
+    double *dA = reinterpret_cast<double *>(wk), *dQ = reinterpret_cast<double *>(wk + sa);
+    double *dT = reinterpret_cast<double *>(wk + sa + sq);
+    int32_t *dinfo = reinterpret_cast<int32_t *>(wk + sa + sq + st);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dA, A, (size_t)lda * w * 8, hipMemcpyHostToDevice, h->stream));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dQ, Q, (size_t)ldq * w * 8, hipMemcpyHostToDevice, h->stream));
+    NODAL_HIP_TRY(h, hipMemsetAsync(dinfo, 0, 4, h->stream));
+    NODAL_TRY(dense_debug_block_inverse(h, dA, lda, w, dQ, ldq, dT, dinfo, base, variant));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(Q, dQ, (size_t)ldq * w * 8, hipMemcpyDeviceToHost, h->stream));
+    return nodal_read_words(h, dinfo_out, dinfo, 4);
+}
+
+int nodal_debug_dense_solve(nodal_handle h, int32_t n, int32_t nrhs, int32_t route, const double *A, const double *B,
+                            double *X, int32_t *info_out, int32_t *ipiv_out) {
+    if (!h || n < 1 || nrhs < 1 || route < 0 || route > 7 || !A || !B || !X || !info_out || !ipiv_out) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    // the dispatcher reads the system's size and route from the context: set for this call, put back on every way out
+    struct Restore {
+        nodal_ctx *h;
+        int64_t n;
+        bool passive, optimistic, pivoting;
+        ~Restore() {
+            h->n = n;
+            h->passive_network = passive;
+            h->optimistic_nopivot = optimistic;
+            h->force_pivoting = pivoting;
+        }
+    } restore{h, h->n, h->passive_network, h->optimistic_nopivot, h->force_pivoting};
+    h->n = n;
+    h->passive_network = (route & 1) != 0;
+    h->optimistic_nopivot = (route & 2) != 0;
+    h->force_pivoting = (route & 4) != 0;
+    const int64_t lda = dense_lda(n);
+    const size_t panel = (size_t)lda * (size_t)(n + nrhs) * 8;
+    NODAL_HIP_TRY(h, h->dense.reserve(panel + 64));
+    NODAL_HIP_TRY(h, h->piv.reserve((size_t)n * 4 + 64));  // (as the dispatcher reserves it: the pointer stays)
+    NODAL_HIP_TRY(h, h->dbg_apply.reserve((size_t)n * nrhs * 8 + 64));
+    double *dA = h->dense.as<double>(), *dX = h->dbg_apply.as<double>();
+    hipStream_t st = h->stream;
+    NODAL_HIP_TRY(h, hipMemsetAsync(dA, 0xff, panel, st));  // the padding rows hold NaN: nothing may read them into a result
+    NODAL_HIP_TRY(h, hipMemcpy2DAsync(dA, (size_t)lda * 8, A, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemcpy2DAsync(dA + (int64_t)n * lda, (size_t)lda * 8, B, (size_t)n * 8, (size_t)n * 8, (size_t)nrhs,
+                                      hipMemcpyHostToDevice, st));
+    // routes without row interchanges never write the list: it starts as the identity (the caller's ipiv_out)
+    NODAL_HIP_TRY(h, hipMemcpyAsync(h->piv.as<int32_t>(), ipiv_out, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    *info_out = 0;
+    NODAL_TRY(dense_factor_solve_multi(h, nrhs, dX, n, info_out));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(X, dX, (size_t)n * nrhs * 8, hipMemcpyDeviceToHost, st));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(ipiv_out, h->piv.as<int32_t>(), (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    NODAL_WAIT_STREAM(h, st);
+    return NODAL_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
 int nodal_last_solve_info(nodal_handle h, int32_t *iterations, int32_t *amg_levels,
                           double *relative_residual) {
     if (!h) return NODAL_E_INVALID;

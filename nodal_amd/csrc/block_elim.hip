@@ -488,9 +488,10 @@ __global__ __launch_bounds__(256) void bs_block(const double *__restrict__ A, in
 // Q (ld ldq) = inverse of the w x w block at D (ld lda), w <= BI_MAX; D itself is overwritten.
 // w <= 128: one Gauss-Jordan workgroup; otherwise the 2 x 2 Schur-complement formula with the
 // leading m1 = 128 (w <= 256) or 256 columns, recursively.  `scratch` holds 2 * m1 * m2 doubles
-// per recursion level (T1, T2).
+// per recursion level (T1, T2).  dpp: -1 the rank-16 kernel's exchange form as NODAL_GJ_DPP latched it (every production
+// call), 0 / 1 the bpermute / DPP form for this call (the testing hook at the end of the file).
 int invert_diag(nodal_ctx *h, hipStream_t sp, double *D, int64_t lda, int w, double *Q, int64_t ldq,
-                double *scratch, int32_t *dinfo, int base) {
+                double *scratch, int32_t *dinfo, int base, int dpp = -1) {
     if (w <= GJ) {
         if (h->gj_scalar == 1) {
             gj128<<<1, 1024, 0, sp>>>(D, lda, w, Q, ldq, dinfo, base);
@@ -507,7 +508,7 @@ int invert_diag(nodal_ctx *h, hipStream_t sp, double *D, int64_t lda, int w, dou
                 lds_allowed[dev].store(true, std::memory_order_release);
             }
             static const bool gj_dpp = knob::GJ_DPP.now();
-            if (gj_dpp) gj128_mfma16<true><<<1, 1024, GJ16_LDS, sp>>>(D, lda, w, Q, ldq, dinfo, base);
+            if (dpp < 0 ? gj_dpp : dpp != 0) gj128_mfma16<true><<<1, 1024, GJ16_LDS, sp>>>(D, lda, w, Q, ldq, dinfo, base);
             else gj128_mfma16<false><<<1, 1024, GJ16_LDS, sp>>>(D, lda, w, Q, ldq, dinfo, base);
         }
         NODAL_HIP_TRY(h, hipGetLastError());
@@ -517,11 +518,11 @@ int invert_diag(nodal_ctx *h, hipStream_t sp, double *D, int64_t lda, int w, dou
     double *T1 = scratch, *T2 = scratch + (size_t)m1 * m2, *deeper = T2 + (size_t)m1 * m2;
     double *Bq = D + (int64_t)m1 * lda, *Cq = D + m1, *Dq = D + (int64_t)m1 * lda + m1;
     double *Q11 = Q, *Q12 = Q + (int64_t)m1 * ldq, *Q21 = Q + m1, *Q22 = Q + (int64_t)m1 * ldq + m1;
-    NODAL_TRY(invert_diag(h, sp, D, lda, m1, Q11, ldq, deeper, dinfo, base));
+    NODAL_TRY(invert_diag(h, sp, D, lda, m1, Q11, ldq, deeper, dinfo, base, dpp));
     NODAL_TRY(gemm_pair_f64(h, sp, GEMM_SET, GemmProblem{T1, m1, Q11, ldq, Bq, lda, m1, m2, m1},    // T1 = A^-1 B
                             GemmProblem{T2, m2, Cq, lda, Q11, ldq, m2, m1, m1}));                  // T2 = C A^-1
     NODAL_TRY(gemm_f64(h, sp, GEMM_SUB, Dq, lda, Cq, lda, T1, m1, m2, m2, m1));                    // S = D - C T1
-    NODAL_TRY(invert_diag(h, sp, Dq, lda, m2, Q22, ldq, deeper, dinfo, base + m1));                // S^-1
+    NODAL_TRY(invert_diag(h, sp, Dq, lda, m2, Q22, ldq, deeper, dinfo, base + m1, dpp));           // S^-1
     NODAL_TRY(gemm_pair_f64(h, sp, GEMM_SETNEG, GemmProblem{Q12, ldq, T1, m1, Q22, ldq, m1, m2, m2},  // -T1 S^-1
                             GemmProblem{Q21, ldq, Q22, ldq, T2, m2, m2, m1, m2}));                    // -S^-1 T2
     NODAL_TRY(gemm_f64(h, sp, GEMM_SUB, Q11, ldq, Q12, ldq, T2, m2, m1, m1, m2));                  // + T1 S^-1 T2
@@ -706,6 +707,21 @@ int factor_blockinv(nodal_ctx *h, double *A, int64_t n, int64_t lda, int64_t nco
 }
 
 }  // namespace
+
+// testing hook (nodal_debug_block_inverse): invert_diag on the caller's block, nothing else.  D (w x w, lda) and Q (ldq)
+// are device pointers, `scratch` holds dense_debug_inverse_scratch() doubles, *dinfo is zero on entry.
+// variant: 0 rank-16 steps with DPP exchanges, 1 rank-16 with bpermute exchanges, 2 rank-4 steps, 3 scalar steps.
+size_t dense_debug_inverse_scratch() { return 2 * (size_t)(2 * GJ) * (2 * GJ) + 2 * (size_t)GJ * GJ; }
+int dense_debug_block_inverse(nodal_ctx *h, double *D, int64_t lda, int w, double *Q, int64_t ldq, double *scratch,
+                              int32_t *dinfo, int base, int variant) {
+    if (w < 1 || w > BI_MAX || lda < w || ldq < w || variant < 0 || variant > 3)
+        return nodal_fail(h, NODAL_E_INVALID, "debug_block_inverse: 1 <= w <= 512, lda, ldq >= w, variant 0 .. 3");
+    const int saved = h->gj_scalar;
+    h->gj_scalar = variant == 3 ? 1 : (variant == 2 ? 2 : 0);
+    const int s = invert_diag(h, h->stream, D, lda, w, Q, ldq, scratch, dinfo, base, variant == 0 ? 1 : 0);
+    h->gj_scalar = saved;
+    return s;
+}
 
 // Factor-and-solve by block elimination: A is the column-major augmented matrix (n + nrhs
 // columns, leading dimension lda); the solutions go to xout (column c at xout + c * ldx).
