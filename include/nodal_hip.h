@@ -863,6 +863,64 @@ int nodal_debug_amg_info(nodal_handle h, int32_t *nlev, int64_t *ints /* [16][8]
 int nodal_debug_amg_array(nodal_handle h, int32_t level, int32_t which, void *dst, int64_t capacity_bytes,
                           int64_t *bytes_out);
 int nodal_debug_amg_apply(nodal_handle h, int32_t level, const double *r, double *z, int32_t *params_out /* [16] */);
+/* The general route's restarted flexible GMRES and its block preconditioner (csrc/sparse_general.hip) with nothing
+ * behind them: what tests/fgmres_reference.py states in numpy and tests/test_gpu_fgmres.py compares.
+ * nodal_debug_fgmres_cycle: the production setup, then exactly ONE restart cycle of the production function -- no outer
+ *   loop, no verdict, no presolve, no rescue by another solver.  No knob is read: the cycle runs with the arguments.
+ *   system 0: the handle's assembled G, branch rows included.  1: the presolved, branch-free system the last sparse solve
+ *     left on the reduced context (the rule of nodal_debug_hierarchy_info); NODAL_E_INVALID when there is none.
+ *   precond 0: the block preconditioner (node block + multigrid + Schur diagonal), set up by the production setup.
+ *     1: the sparse direct factors -- slu_factor, then slu_apply per column, as the refinement behind every sparse direct
+ *     solve does; only with system 0.
+ *   window 2 .. 41: column j is orthogonalised against v_s0 .. v_j, s0 = max(0, j + 1 - window).  max_cols 1 .. 40.
+ *   rel_tol >= 0: the cycle stops once the estimate is <= rel_tol |b|; 0 never stops on the estimate.
+ *   n: the system's unknowns as the caller sized its vectors (NODAL_E_INVALID when the system has another count).
+ *   b: a host vector of n entries, or NULL for that system's own right-hand side.
+ *   Returns x [n]; V [(count + 1)][n] and Z [count][n] without the device's row padding (capacity: (max_cols + 1) n
+ *   and max_cols n; after a stop on the estimate row `count` of V holds what the buffer held: the kernel that scales
+ *   v_count returns once the flag is up);
+ *   gst [NODAL_FG_WORDS], the small least-squares problem as the device holds it (enum below: H row-major [41][40] with
+ *   R = Q^T H-bar on and above the diagonal, the rotations, g, and the scalars); y [41], zero from `count` on;
+ *   norms_out[2] = |b - A x| at the cycle's end and |b|, as the device summed them; params_out[16]: 0 n, 1 K (rows of
+ *   the node block; n under precond 1), 2 ld (the device's row stride of V and Z), 3 count (columns run), 4 the window
+ *   used, 5 use_sa (the smoothed hierarchy took the node block; else plain aggregation), 6 ell_spmv (the Krylov SpMV
+ *   ran on the hierarchy's ELL copy), 7 the hierarchy's levels, 8 gd (workgroups of the dot-product kernels), 9 the
+ *   cycle's breakdown flag (x is not updated then).  A zero b returns x = 0 and count 0 with nothing launched after
+ *   the norm of b; V and Z are not written.
+ *   NODAL_E_INVALID: arguments out of range, no such system, a matrix the setup finds singular.  Host vectors; the
+ *   iterate and b live in scratch of the hook's own.  Solution, right-hand side and table stay as found; the
+ *   preconditioner (node block, Schur diagonal, hierarchy or sparse LU factors), the Krylov storage and the K-cycle's
+ *   calibration are left as the first cycle of a solve of that system leaves them: a solve after it returns the bits of
+ *   the same solve without it.
+ * nodal_debug_general_array: a stream wait and a device-to-host copy of one buffer, as the last precond-0 setup of
+ *   nodal_debug_fgmres_cycle left it: the node block as CSR -- gn_indptr (i32, K + 1), gn_indices / gn_rowidx (i32, nnz
+ *   of the block), gn_data (f64), gn_diag (i32, K: position of each row's diagonal) -- schur (f64, n - K: 1 / S~ per
+ *   branch row), and the system that cycle ran on: indptr (i32, n + 1) / indices (i32) / data (f64) and its own
+ *   right-hand side (f64, n); the reduced system has no other export.  dst == NULL: the size only; otherwise
+ *   capacity_bytes must cover it.  NODAL_E_INVALID when no such setup stands (none yet, or the system was assembled
+ *   anew since).  Nothing is launched, nothing on the device is written. */
+enum {
+    NODAL_FG_RESTART = 40, NODAL_FG_MAXV = NODAL_FG_RESTART + 1,
+    NODAL_FG_H = 0,                                               /* [41][40] row-major: column j at [i * 40 + j] */
+    NODAL_FG_CS = NODAL_FG_H + NODAL_FG_MAXV * NODAL_FG_RESTART,  /* [40] cosines of the rotations */
+    NODAL_FG_SN = NODAL_FG_CS + NODAL_FG_RESTART,                 /* [40] sines */
+    NODAL_FG_G = NODAL_FG_SN + NODAL_FG_RESTART,                  /* [41] the rotated right-hand side */
+    NODAL_FG_INV_H = NODAL_FG_G + NODAL_FG_MAXV,                  /* 1 / h_{j+1,j} of the last column */
+    NODAL_FG_EST = NODAL_FG_INV_H + 1,                            /* the residual estimate |g_{count}| */
+    NODAL_FG_DONE = NODAL_FG_INV_H + 2, NODAL_FG_COUNT = NODAL_FG_INV_H + 3, NODAL_FG_INFO = NODAL_FG_INV_H + 4,
+    NODAL_FG_TOLB = NODAL_FG_INV_H + 5,
+    NODAL_FG_LOG = NODAL_FG_INV_H + 6,                            /* [40] |w after the projections|^2 / |w|^2 */
+    NODAL_FG_WORDS = NODAL_FG_LOG + NODAL_FG_RESTART
+};
+enum {
+    NODAL_GA_GN_INDPTR = 0, NODAL_GA_GN_INDICES = 1, NODAL_GA_GN_ROWIDX = 2, NODAL_GA_GN_DATA = 3, NODAL_GA_GN_DIAG = 4,
+    NODAL_GA_SCHUR = 5, NODAL_GA_INDPTR = 6, NODAL_GA_INDICES = 7, NODAL_GA_DATA = 8, NODAL_GA_RHS = 9
+};
+int nodal_debug_fgmres_cycle(nodal_handle h, int32_t system, int32_t precond, int32_t window, int32_t max_cols,
+                             double rel_tol, int64_t n, const double *b, double *x_out, double *V_out, double *Z_out,
+                             double *gst_out /* [NODAL_FG_WORDS] */, double *y_out /* [41] */, double *norms_out /* [2] */,
+                             int64_t *params_out /* [16] */);
+int nodal_debug_general_array(nodal_handle h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
 
 #ifdef __cplusplus
 }

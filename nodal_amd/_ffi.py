@@ -104,7 +104,27 @@ SIGNATURES = {
     "nodal_debug_amg_info": (C.c_int, [C.c_void_p, _i32p, _i64p, _i64p, _f64p, _i64p]),
     "nodal_debug_amg_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
     "nodal_debug_amg_apply": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f64p, _i32p]),
+    "nodal_debug_fgmres_cycle": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64,
+                                           _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64p]),
+    "nodal_debug_general_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
 }
+
+# nodal_debug_fgmres_cycle: the small least-squares problem's block of doubles in the header's layout (NODAL_FG_*), and
+# the names of the words of params_out
+FG_RESTART = 40
+FG_MAXV = FG_RESTART + 1
+FG_H = 0                              # [41][40] row-major
+FG_CS = FG_H + FG_MAXV * FG_RESTART   # [40]
+FG_SN = FG_CS + FG_RESTART            # [40]
+FG_G = FG_SN + FG_RESTART             # [41]
+FG_INV_H = FG_G + FG_MAXV
+FG_EST, FG_DONE, FG_COUNT, FG_INFO, FG_TOLB, FG_LOG = (FG_INV_H + k for k in range(1, 7))
+FG_WORDS = FG_LOG + FG_RESTART
+FGMRES_PARAMS = ("n", "K", "ld", "count", "window", "use_sa", "ell_spmv", "levels", "gd", "breakdown")
+# nodal_debug_general_array: `which` in the header's order (NODAL_GA_*) with the item type of each buffer
+GENERAL_ARRAYS = (("gn_indptr", np.int32), ("gn_indices", np.int32), ("gn_rowidx", np.int32), ("gn_data", np.float64),
+                  ("gn_diag", np.int32), ("schur", np.float64), ("indptr", np.int32), ("indices", np.int32),
+                  ("data", np.float64), ("rhs", np.float64))
 
 # nodal_debug_amg_array: `which` in the header's order (NODAL_AA_*) with the item type of each buffer, the two special
 # level numbers, and the names of the words nodal_debug_amg_info / nodal_debug_amg_apply return
@@ -903,6 +923,58 @@ class Handle:
         self._check(self.lib.nodal_debug_amg_apply(self._h, level, _ptr(r, C.c_double), _ptr(z, C.c_double),
                                                    _ptr(params, C.c_int32)))
         return z, {name: int(params[k]) for k, name in enumerate(AMG_APPLY_PARAMS)}
+
+    def debug_fgmres_cycle(self, system=0, precond=0, window=FG_MAXV, max_cols=FG_RESTART, rel_tol=0.0, b=None, n=None):
+        """ONE restart cycle of the general route's flexible GMRES, nothing behind it (testing hook; nodal_hip.h).
+        system 0: the handle's G; 1: the presolved system of the last sparse solve (pass its n, or leave it to a first
+        sizing call).  precond 0: the block preconditioner; 1: the sparse direct factors.  Returns a dict: x [n],
+        V [count + 1, n], Z [count, n], H [41, 40], cs [40], sn [40], g [41], y [41], gst (the whole block), rnorm,
+        bnorm, inv_h, est, done, tolb and the words of FGMRES_PARAMS."""
+        if n is None and system == 0:
+            n = self.n
+        elif n is None:  # (a presolved system that reached the iteration has a hierarchy: level 0 is the system)
+            nlev, ints, reals = C.c_int32(0), np.zeros((12, 16), dtype=np.int64), np.zeros((12, 2))
+            self._check(self.lib.nodal_debug_hierarchy_info(self._h, C.byref(nlev), _ptr(ints, C.c_int64),
+                                                            _ptr(reals, C.c_double)))
+            n = int(ints[0, 0])
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float64)
+            assert b.shape == (n,), (b.shape, n)
+        x = np.full(n, np.nan)
+        V = np.full((max_cols + 1, n), np.nan)
+        Z = np.full((max_cols, n), np.nan)
+        gst = np.full(FG_WORDS, np.nan)
+        y = np.full(FG_MAXV, np.nan)
+        norms = np.full(2, np.nan)
+        params = np.zeros(16, dtype=np.int64)
+        self._check(self.lib.nodal_debug_fgmres_cycle(self._h, system, precond, window, max_cols, float(rel_tol), n,
+                                                      _ptr(b, C.c_double) if b is not None else None, _ptr(x, C.c_double),
+                                                      _ptr(V, C.c_double), _ptr(Z, C.c_double), _ptr(gst, C.c_double),
+                                                      _ptr(y, C.c_double), _ptr(norms, C.c_double), _ptr(params, C.c_int64)))
+        out = {name: int(params[k]) for k, name in enumerate(FGMRES_PARAMS)}
+        count = out["count"]
+        assert out["n"] == n and 0 <= count <= max_cols, (out, n)
+        out.update(x=x, V=V[:count + 1] if count else V[:0], Z=Z[:count], gst=gst, y=y,
+                   H=gst[FG_H:FG_CS].reshape(FG_MAXV, FG_RESTART), cs=gst[FG_CS:FG_SN], sn=gst[FG_SN:FG_G],
+                   g=gst[FG_G:FG_INV_H], inv_h=float(gst[FG_INV_H]), est=float(gst[FG_EST]), done=float(gst[FG_DONE]),
+                   gcount=float(gst[FG_COUNT]), tolb=float(gst[FG_TOLB]), rnorm=float(norms[0]), bnorm=float(norms[1]))
+        return out
+
+    def debug_general_arrays(self):
+        """What the last precond-0 setup of debug_fgmres_cycle left, raw (testing hook): a dict of GENERAL_ARRAYS --
+        the node block as CSR with gn_rowidx and gn_diag, schur = 1 / S~ per branch row, and the CSR arrays and
+        right-hand side of the system that cycle ran on."""
+        return {name: self._general_array(which, dtype) for which, (name, dtype) in enumerate(GENERAL_ARRAYS)}
+
+    def _general_array(self, which, dtype):
+        size = C.c_int64(0)
+        self._check(self.lib.nodal_debug_general_array(self._h, which, None, 0, C.byref(size)))
+        out = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+        if size.value:
+            self._check(self.lib.nodal_debug_general_array(self._h, which, C.c_void_p(out.ctypes.data), out.nbytes,
+                                                           C.byref(size)))
+            assert size.value == out.nbytes
+        return out
 
     def download_x(self):
         x = host_empty(self.n, np.float64)

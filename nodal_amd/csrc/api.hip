@@ -1197,6 +1197,23 @@ int nodal_debug_amg_apply(nodal_handle h, int32_t level, const double *r, double
     return amg_debug_apply(h, level, r, z, params_out);
 }
 
+int nodal_debug_fgmres_cycle(nodal_handle h, int32_t system, int32_t precond, int32_t window, int32_t max_cols,
+                             double rel_tol, int64_t n, const double *b, double *x_out, double *V_out, double *Z_out, double *gst_out,
+                             double *y_out, double *norms_out, int64_t *params_out) {
+    if (!h) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return general_debug_cycle(h, system, precond, window, max_cols, rel_tol, n, b, x_out, V_out, Z_out, gst_out, y_out,
+                               norms_out, params_out);
+}
+
+int nodal_debug_general_array(nodal_handle h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out) {
+    if (!h || !bytes_out) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return general_debug_array(h, which, dst, capacity_bytes, bytes_out);
+}
+
 int nodal_residual(nodal_handle h, double *scaled_residual) {
     if (!h || !scaled_residual) return NODAL_E_INVALID;
     DeviceGuard g(h);

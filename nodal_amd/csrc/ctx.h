@@ -321,6 +321,11 @@ struct nodal_ctx {
     DevBuf krylov;          // FGMRES bases (sparse_general.hip)
     DevBuf gn_indptr, gn_indices, gn_rowidx, gn_data, gn_diag;  // node block of G
     DevBuf schur;           // diagonal Schur-complement approximation of the branch block
+    int64_t gn_nnz = 0;     // entries of the node block the last general setup extracted
+    // testing hooks nodal_debug_fgmres_cycle / nodal_debug_general_array: the `system` whose block preconditioner the
+    // former set up last (-1: none) and that context's numeric_epoch then
+    int32_t dbg_general_system = -1;
+    uint64_t dbg_general_epoch = 0;
 
     // ---- timing ----
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -832,6 +837,12 @@ int sparse_debug_residual(nodal_ctx *h, bool transposed, int32_t cols, int32_t l
 // testing hook (nodal_debug_direct_apply): slu_factor + one slu_apply (cols 1) or slu_apply_multi (cols 16) on host vectors
 int sparse_debug_direct_apply(nodal_ctx *h, bool transposed, int32_t cols, const double *r, double *z,
                               int64_t *perturbed_out, int32_t *info_out);
+// testing hook (nodal_debug_fgmres_cycle): the general route's setup and ONE restart cycle on host vectors, nothing behind
+// it; (nodal_debug_general_array): what that setup left, raw (sparse_general.hip)
+int general_debug_cycle(nodal_ctx *h, int32_t system, int32_t precond, int32_t window, int32_t max_cols, double rel_tol,
+                        int64_t n_caller, const double *b_host, double *x_out, double *V_out, double *Z_out, double *gst_out, double *y_out,
+                        double *norms_out, int64_t *params_out);
+int general_debug_array(nodal_ctx *h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
 // dense_child: solve the reduced system by the dense block elimination (only if it is passive)
 void presolve_plan_ahead(nodal_ctx *h);  // host-only; called by stamp_numeric while its kernels run
 void presolve_free_plan(nodal_ctx *h);

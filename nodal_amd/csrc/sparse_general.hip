@@ -23,13 +23,17 @@
 namespace {
 
 constexpr int TB = 256;
-constexpr int RESTART = 40;
+constexpr int RESTART = NODAL_FG_RESTART;
 constexpr int MAXV = RESTART + 1;
 constexpr int DOT_GRID = 1024;
-// the small least-squares problem's state on the device (see gs_finish)
-enum { G_H = 0, G_CS = G_H + MAXV * RESTART, G_SN = G_CS + RESTART, G_G = G_SN + RESTART,
-       G_INV_H = G_G + MAXV, G_EST, G_DONE, G_COUNT, G_INFO, G_TOLB,
-       G_LOG /* per column: |w after the projections|^2 / |w|^2 (NODAL_TRACE) */, G_WORDS = G_LOG + RESTART };
+// the small least-squares problem's state on the device (see gs_finish); the layout is stated in nodal_hip.h, where the
+// testing hook nodal_debug_fgmres_cycle returns the block
+enum { G_H = NODAL_FG_H, G_CS = NODAL_FG_CS, G_SN = NODAL_FG_SN, G_G = NODAL_FG_G,
+       G_INV_H = NODAL_FG_INV_H, G_EST = NODAL_FG_EST, G_DONE = NODAL_FG_DONE, G_COUNT = NODAL_FG_COUNT,
+       G_INFO = NODAL_FG_INFO, G_TOLB = NODAL_FG_TOLB,
+       G_LOG = NODAL_FG_LOG /* per column: |w after the projections|^2 / |w|^2 (NODAL_TRACE) */, G_WORDS = NODAL_FG_WORDS };
+static_assert(G_CS == G_H + MAXV * RESTART && G_SN == G_CS + RESTART && G_G == G_SN + RESTART && G_INV_H == G_G + MAXV &&
+              G_TOLB == G_INV_H + 5 && G_LOG == G_TOLB + 1 && G_WORDS == G_LOG + RESTART, "the block is contiguous");
 
 inline unsigned grid_for(int64_t n, unsigned cap = 4096) {
     int64_t g = (n + TB - 1) / TB;
@@ -452,16 +456,251 @@ __global__ __launch_bounds__(TB) void find_zero_row(const int32_t *__restrict__ 
 
 namespace {
 
+// What the three parts of a solve -- the preconditioner setup, a restart cycle, the outer loop -- hand to each other.
 // `direct`: the preconditioner is the multifrontal LU of sparse_direct.hip (factorised by the caller) --
 // the iteration is then iterative refinement with a true-residual test: no presolve, no structural
 // verdicts (the caller has been through them), no multigrid; any right-hand side / solution vectors.
-int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_t *iters, double *resid,
-                 bool direct) {
+struct GeneralState {
+    bool direct = false;
+    int K = 0;              // rows of the node block (n behind the direct factors)
+    bool use_sa = false;    // node block: the smoothed hierarchy of sagg.hip (else the plain aggregation of amg.hip)
+    bool ell_spmv = false;  // the Krylov SpMV runs on the hierarchy's level-0 ELL copy of the system
+    // Krylov storage: V (m+1), Z (m), w, r; the dot products' partial sums; the two coefficient columns; y; the small
+    // least-squares problem
+    double *V = nullptr, *Z = nullptr, *w = nullptr, *r = nullptr, *partial = nullptr, *partial2 = nullptr;
+    double *hdev = nullptr, *hdev2 = nullptr, *ydev = nullptr, *gst = nullptr;
+    int64_t ld = 0;
+    unsigned gd = 0, gv = 0;
+};
+
+// ---- preconditioner setup: node block + multigrid + Schur diagonal ----
+// *info = 1: the hierarchy found a floating island (singular: NaNs + warning, as the reference's spsolve, quirk 3)
+int general_setup(nodal_ctx *h, GeneralState &S, int32_t *info) {
     const int64_t n = h->n;
-    const int K = direct ? (int)n : h->K;
+    const int K = S.K;
     hipStream_t st = h->stream;
     const int32_t *indptr = h->indptr.as<int32_t>();
     const int32_t *indices = h->indices.as<int32_t>();
+    const double *data = h->data.as<double>();
+    bool use_sa = false;
+    NODAL_HIP_TRY(h, h->work.reserve(align_up((size_t)(K + 1) * 4) + scan_tmp_bytes(K + 1) + 512));
+    uint32_t *cnt = h->work.as<uint32_t>();
+    void *scan_tmp = h->work.as<char>() + align_up((size_t)(K + 1) * 4);
+    NODAL_HIP_TRY(h, hipMemsetAsync(cnt, 0, (size_t)(K + 1) * 4, st));
+    gn_count<<<grid_for(K), TB, 0, st>>>(indptr, indices, K, cnt);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    NODAL_TRY(scan_exclusive_u32(h, cnt, cnt, (int64_t)K + 1, nullptr, scan_tmp));
+    uint32_t gn_nnz = 0;
+    NODAL_TRY(nodal_read_words(h, &gn_nnz, cnt + K, 4));
+    h->gn_nnz = gn_nnz;
+    NODAL_HIP_TRY(h, h->gn_indptr.reserve((size_t)(K + 1) * 4));
+    NODAL_HIP_TRY(h, h->gn_indices.reserve((size_t)gn_nnz * 4 + 4));
+    NODAL_HIP_TRY(h, h->gn_rowidx.reserve((size_t)gn_nnz * 4 + 4));
+    NODAL_HIP_TRY(h, h->gn_data.reserve((size_t)gn_nnz * 8 + 8));
+    NODAL_HIP_TRY(h, h->gn_diag.reserve((size_t)K * 4 + 4));
+    gn_fill<<<grid_for(K + 1), TB, 0, st>>>(indptr, indices, data, K, cnt, h->gn_indptr.as<int32_t>(),
+                                           h->gn_indices.as<int32_t>(), h->gn_rowidx.as<int32_t>(),
+                                           h->gn_data.as<double>(), h->gn_diag.as<int32_t>());
+    NODAL_HIP_TRY(h, hipGetLastError());
+    NODAL_HIP_TRY(h, h->schur.reserve((size_t)(n - K) * 8 + 64));
+    double *flag = h->schur.as<double>() + (n - K);  // spare word: multigrid's SPD flag (unused here)
+    NODAL_HIP_TRY(h, hipMemsetAsync(flag, 0, 8, st));
+    // node block: smoothed aggregation where it takes the matrix (sagg.hip), else plain aggregation
+    {
+        // a presolved system (no branch unknowns left, resistors / current sources / transconductances):
+        // its table says which nodes touch ground, so the hierarchy can tell a floating island
+        const bool check_floating = h->B == 0 && h->have_table && !h->csr_only && K == (int)n;
+        int32_t floating = 0;
+        NODAL_TRY(sagg_setup_csr(h, K, gn_nnz, h->gn_indptr.as<int32_t>(), h->gn_indices.as<int32_t>(),
+                                 h->gn_data.as<double>(), true, check_floating, &use_sa, &floating));
+        if (!use_sa && check_floating) {  // the hierarchy declined the matrix: the same verdict on the CSR pattern
+            NODAL_HIP_TRY(h, h->work3.reserve((size_t)n + 256));
+            NODAL_TRY(grounded_flags(h, h->work3.as<uint8_t>()));
+            NODAL_TRY(csr_has_floating_component(h, h->work3.as<uint8_t>(), &floating));
+        }
+        if (floating) {  // singular: NaNs + warning, as the reference's spsolve (quirk 3)
+            *info = 1;
+            return NODAL_OK;
+        }
+    }
+    // the hierarchy's level-0 matrix is the system itself (a presolved network: no branch rows, no
+    // diagonal had to be added): its ELL copy serves the Krylov SpMV too (13 instead of 22 us at 1e6 rows)
+    S.use_sa = use_sa;
+    S.ell_spmv = use_sa && K == (int)n && gn_nnz == (uint32_t)h->nnz;
+    if (use_sa) {
+        amg_invalidate(h);
+        h->amg_levels = sagg_levels(h);
+    } else {
+        NODAL_TRY(amg_setup_csr(h, K, gn_nnz, h->gn_indptr.as<int32_t>(), h->gn_indices.as<int32_t>(),
+                                h->gn_rowidx.as<int32_t>(), h->gn_data.as<double>(),
+                                h->gn_diag.as<int32_t>(), flag));
+        h->amg_levels = amg_num_levels(h);
+    }
+    if (n > K) {
+        schur_diag<<<grid_for(n - K), TB, 0, st>>>(indptr, indices, data, K, (int)n,
+                                                  h->gn_data.as<double>(), h->gn_diag.as<int32_t>(),
+                                                  h->schur.as<double>());
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    return NODAL_OK;
+}
+
+// ---- Krylov storage: V (m+1), Z (m), w, r ----
+int general_storage(nodal_ctx *h, GeneralState &S) {
+    const int64_t n = h->n;
+    const int64_t ld = (int64_t)(align_up((size_t)n * 8) / 8);
+    const size_t vecs = (size_t)(2 * RESTART + 3) * ld * 8;
+    const size_t scal = ((size_t)DOT_GRID * MAXV + DOT_GRID + 2 * (MAXV + 1) + MAXV + G_WORDS) * 8;
+    NODAL_HIP_TRY(h, h->krylov.reserve(vecs + scal + 1024));
+    S.ld = ld;
+    S.V = h->krylov.as<double>();
+    S.Z = S.V + (int64_t)(RESTART + 1) * ld;
+    S.w = S.Z + (int64_t)RESTART * ld;
+    S.r = S.w + ld;
+    S.partial = S.r + ld;
+    S.partial2 = S.partial + (int64_t)DOT_GRID * MAXV;
+    S.hdev = S.partial2 + DOT_GRID;        // MAXV + 1
+    S.hdev2 = S.hdev + (MAXV + 1);         // MAXV + 1
+    S.ydev = S.hdev2 + (MAXV + 1);         // MAXV
+    S.gst = S.ydev + MAXV;                 // G_WORDS: the small least-squares problem
+    S.gd = grid_for(n, DOT_GRID);
+    S.gv = grid_for(n);
+    return NODAL_OK;
+}
+
+int device_norm(nodal_ctx *h, const GeneralState &S, double *out) {  // sqrt(sum partial2) -> host
+    gs_reduce<<<1, TB, 0, h->stream>>>(S.partial, 0, 0, S.hdev, S.partial2, (int)S.gd);
+    double v = 0.0;
+    NODAL_TRY(nodal_read_words(h, &v, S.hdev + MAXV, 8));
+    *out = std::sqrt(v);
+    return NODAL_OK;
+}
+
+// ---- one restart cycle ----
+// From r = b - A x (in S.r, |r| = rnorm) to the updated x and its true residual (S.r again, *rnorm_out): at most max_cols
+// columns, each orthogonalised against the last `window` basis vectors, stopping early once the estimate is <= tolb.
+// `first`: the first cycle of a solve (the K-cycle of the smoothed hierarchy calibrates on its iteration numbers).
+// *count: the columns the cycle ran.  *info = 1 (breakdown: singular operator) leaves x alone.
+int general_cycle(nodal_ctx *h, const GeneralState &S, const double *b, double *x, bool first, int window, int max_cols,
+                  double tolb, double rnorm, int *count, double *rnorm_out, int32_t *info) {
+    const int64_t n = h->n, ld = S.ld;
+    const int K = S.K;
+    const bool direct = S.direct, use_sa = S.use_sa, ell_spmv = S.ell_spmv;
+    hipStream_t st = h->stream;
+    const int32_t *indptr = h->indptr.as<int32_t>();
+    const int32_t *indices = h->indices.as<int32_t>();
+    const double *data = h->data.as<double>();
+    double *V = S.V, *Z = S.Z, *w = S.w, *r = S.r, *partial = S.partial, *partial2 = S.partial2;
+    double *hdev = S.hdev, *hdev2 = S.hdev2, *ydev = S.ydev, *gst = S.gst;
+    const unsigned gd = S.gd, gv = S.gv;
+    hipEvent_t e0 = h->ev[2], e1 = h->ev[3];
+    double hst[6];  // G_INV_H .. G_TOLB, as polled
+
+    scale_to<<<gv, TB, 0, st>>>(r, 1.0 / rnorm, V, n);
+    gst_begin<<<1, 64, 0, st>>>(gst, rnorm, tolb);
+    // the kernel that normalises v_{j+1} also leaves the start iterate of the cycle that preconditions it
+    const double *x0_dinv = nullptr;
+    nodal_cyc_t *x0_slot = nullptr;
+    int64_t x0_n = 0;
+    double x0_omega = 0.0;
+    if (use_sa && !direct && !sagg_x0_slot(h, &x0_dinv, &x0_slot, &x0_n, &x0_omega)) x0_slot = nullptr;
+    // Iterations are enqueued in batches; between batches the host reads the estimate and
+    // sizes the next batch from the convergence rate seen so far (three quarters of what is
+    // still missing, at least two).  A batch that overshoots costs idle launches only: every
+    // kernel that touches the small problem returns once G_DONE is up.
+    // (behind the direct factorisation an iteration is a 10-ms pair of triangular sweeps and one or two of them
+    // converge: the host looks after every one -- a batch of six ran four sweeps for nothing)
+    int enq = 0, batch = direct ? 1 : 6;
+    double est_prev = rnorm;
+    int at_prev = 0;
+    bool done = false;
+    while (!done && enq < max_cols) {
+        if (batch > max_cols - enq) batch = max_cols - enq;
+        for (int c = 0; c < batch; ++c, ++enq) {
+            const int j = enq;
+            double *vj = V + (int64_t)j * ld, *zj = Z + (int64_t)j * ld;
+            // z_j = M^-1 v_j
+            if (j == 0) nodal_nan_probe(h, vj, n, "fgmres v0");
+            if (direct) NODAL_TRY(slu_apply(h, vj, zj));
+            else if (use_sa) NODAL_TRY(sagg_apply(h, vj, zj, j > 0 && x0_slot != nullptr, first ? j : -1));
+            else NODAL_TRY(amg_apply(h, vj, zj));
+            if (j == 0) nodal_nan_probe(h, zj, K, "fgmres z0 (node block)");
+            if (n > K) {
+                branch_solve<<<grid_for(n - K), TB, 0, st>>>(indptr, indices, data, K, (int)n,
+                                                            h->schur.as<double>(), vj, zj);
+                NODAL_HIP_TRY(h, hipGetLastError());
+            }
+            // w = A z_j   (one launch per batch is timed)
+            if (ell_spmv) {
+                NODAL_TRY(sagg_spmv(h, zj, w, c == 0 ? e0 : nullptr, c == 0 ? e1 : nullptr));
+            } else {
+                if (c == 0) NODAL_HIP_TRY(h, hipEventRecord(e0, st));
+                NODAL_TRY(csr_spmv(h, zj, w));
+                if (c == 0) NODAL_HIP_TRY(h, hipEventRecord(e1, st));
+            }
+            if (j == 0) {
+                nodal_nan_probe(h, zj, n, "fgmres z0");
+                nodal_nan_probe(h, w, n, "fgmres w0 = A z0");
+            }
+            // classical Gram-Schmidt, twice, against the last `window` basis vectors (see window_first in general_impl)
+            const int nv_all = j + 1;
+            const int s0 = nv_all > window ? nv_all - window : 0, nv = nv_all - s0;
+            const double *Vw = V + (int64_t)s0 * ld;
+            DISPATCH_NV(nv, (gs_dots<NV><<<gd, TB, 0, st>>>(Vw, ld, nv, w, n, partial)));
+            gs_reduce<<<nv, TB, 0, st>>>(partial, (int)gd, nv, hdev + s0, nullptr, 0);
+            DISPATCH_NV(nv, (gs_update_dots<NV><<<gd, TB, 0, st>>>(Vw, ld, nv, hdev + s0, w, n, partial)));
+            gs_reduce<<<nv, TB, 0, st>>>(partial, (int)gd, nv, hdev2 + s0, nullptr, 0);
+            DISPATCH_NV(nv, (gs_update<NV><<<gd, TB, 0, st>>>(Vw, ld, nv, hdev2 + s0, w, n, partial2)));
+            gs_finish<<<1, TB, 0, st>>>(hdev, hdev2, partial2, (int)gd, j, s0, gst);
+            scale_by_device<<<gv, TB, 0, st>>>(w, gst, V + (int64_t)(j + 1) * ld, n, x0_dinv, x0_slot, x0_n, x0_omega);
+            NODAL_HIP_TRY(h, hipGetLastError());
+        }
+        NODAL_TRY(nodal_read_words(h, hst, gst + G_INV_H, sizeof hst));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) { h->kern_ms += ms; h->kern_launches += 1; }
+        const double est = hst[G_EST - G_INV_H];
+        done = hst[G_DONE - G_INV_H] != 0.0;
+        if (hst[G_INFO - G_INV_H] != 0.0) *info = 1;
+        if (done) break;
+        // contraction per iteration since the last poll -> iterations still missing
+        // (tolb == 0, the testing hook's "never stop on the estimate": all of them)
+        double need = RESTART;
+        if (est > 0.0 && est < est_prev && enq > at_prev && tolb > 0.0) {
+            const double rate = std::log(est / est_prev) / (double)(enq - at_prev);
+            need = std::log(tolb / est) / rate;
+        }
+        batch = (int)std::floor(0.75 * need);
+        if (batch < 2) batch = 2;
+        if (batch > enq) batch = enq;  // (at most doubling)
+        if (direct) batch = 1;
+        est_prev = est;
+        at_prev = enq;
+    }
+    *count = (int)hst[G_COUNT - G_INV_H];
+    if (knob::TRACE.now()) {
+        double lg[RESTART];
+        NODAL_TRY(nodal_read_words(h, lg, gst + G_LOG, sizeof lg));
+        fprintf(stderr, "[fgmres] |w after Gram-Schmidt|^2 / |w|^2 per column:");
+        for (int i = 0; i < *count && i < RESTART; ++i) fprintf(stderr, " %.2g", lg[i]);
+        fprintf(stderr, "\n");
+    }
+    if (*info) return NODAL_OK;
+    // y = H^-1 g ; x += Z y
+    gst_solve<<<1, 64, 0, st>>>(gst, ydev);
+    add_combination<<<gv, TB, 0, st>>>(Z, ld, RESTART, ydev, x, gst, n);
+    // true residual
+    NODAL_TRY(ell_spmv ? sagg_spmv(h, x, w) : csr_spmv(h, x, w));
+    residual_of<<<gd, TB, 0, st>>>(b, w, r, n, partial2);
+    NODAL_TRY(device_norm(h, S, rnorm_out));
+    return NODAL_OK;
+}
+
+// ---- the outer loop and its verdicts ----
+int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_t *iters, double *resid,
+                 bool direct) {
+    const int64_t n = h->n;
+    hipStream_t st = h->stream;
+    const int32_t *indptr = h->indptr.as<int32_t>();
     const double *data = h->data.as<double>();
     *info = 0;
 
@@ -507,102 +746,20 @@ int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_
             return nodal_fail(h, NODAL_E_UNSUPPORTED, "the presolve declined this pattern of sources");
     }
 
-    bool use_sa = false;
-    bool ell_spmv = false;
+    GeneralState S;
+    S.direct = direct;
+    S.K = direct ? (int)n : h->K;
+    const int K = S.K;
     if (!direct) {
-    // ---- preconditioner setup: node block + multigrid + Schur diagonal ----
-    NODAL_HIP_TRY(h, h->work.reserve(align_up((size_t)(K + 1) * 4) + scan_tmp_bytes(K + 1) + 512));
-    uint32_t *cnt = h->work.as<uint32_t>();
-    void *scan_tmp = h->work.as<char>() + align_up((size_t)(K + 1) * 4);
-    NODAL_HIP_TRY(h, hipMemsetAsync(cnt, 0, (size_t)(K + 1) * 4, st));
-    gn_count<<<grid_for(K), TB, 0, st>>>(indptr, indices, K, cnt);
-    NODAL_HIP_TRY(h, hipGetLastError());
-    NODAL_TRY(scan_exclusive_u32(h, cnt, cnt, (int64_t)K + 1, nullptr, scan_tmp));
-    uint32_t gn_nnz = 0;
-    NODAL_TRY(nodal_read_words(h, &gn_nnz, cnt + K, 4));
-    NODAL_HIP_TRY(h, h->gn_indptr.reserve((size_t)(K + 1) * 4));
-    NODAL_HIP_TRY(h, h->gn_indices.reserve((size_t)gn_nnz * 4 + 4));
-    NODAL_HIP_TRY(h, h->gn_rowidx.reserve((size_t)gn_nnz * 4 + 4));
-    NODAL_HIP_TRY(h, h->gn_data.reserve((size_t)gn_nnz * 8 + 8));
-    NODAL_HIP_TRY(h, h->gn_diag.reserve((size_t)K * 4 + 4));
-    gn_fill<<<grid_for(K + 1), TB, 0, st>>>(indptr, indices, data, K, cnt, h->gn_indptr.as<int32_t>(),
-                                           h->gn_indices.as<int32_t>(), h->gn_rowidx.as<int32_t>(),
-                                           h->gn_data.as<double>(), h->gn_diag.as<int32_t>());
-    NODAL_HIP_TRY(h, hipGetLastError());
-    NODAL_HIP_TRY(h, h->schur.reserve((size_t)(n - K) * 8 + 64));
-    double *flag = h->schur.as<double>() + (n - K);  // spare word: multigrid's SPD flag (unused here)
-    NODAL_HIP_TRY(h, hipMemsetAsync(flag, 0, 8, st));
-    // node block: smoothed aggregation where it takes the matrix (sagg.hip), else plain aggregation
-    {
-        // a presolved system (no branch unknowns left, resistors / current sources / transconductances):
-        // its table says which nodes touch ground, so the hierarchy can tell a floating island
-        const bool check_floating = h->B == 0 && h->have_table && !h->csr_only && K == (int)n;
-        int32_t floating = 0;
-        NODAL_TRY(sagg_setup_csr(h, K, gn_nnz, h->gn_indptr.as<int32_t>(), h->gn_indices.as<int32_t>(),
-                                 h->gn_data.as<double>(), true, check_floating, &use_sa, &floating));
-        if (!use_sa && check_floating) {  // the hierarchy declined the matrix: the same verdict on the CSR pattern
-            NODAL_HIP_TRY(h, h->work3.reserve((size_t)n + 256));
-            NODAL_TRY(grounded_flags(h, h->work3.as<uint8_t>()));
-            NODAL_TRY(csr_has_floating_component(h, h->work3.as<uint8_t>(), &floating));
-        }
-        if (floating) {  // singular: NaNs + warning, as the reference's spsolve (quirk 3)
-            *info = 1;
-            return NODAL_OK;
-        }
+        NODAL_TRY(general_setup(h, S, info));
+        if (*info) return NODAL_OK;
     }
-    // the hierarchy's level-0 matrix is the system itself (a presolved network: no branch rows, no
-    // diagonal had to be added): its ELL copy serves the Krylov SpMV too (13 instead of 22 us at 1e6 rows)
-    ell_spmv = use_sa && K == (int)n && gn_nnz == (uint32_t)h->nnz;
-    if (use_sa) {
-        amg_invalidate(h);
-        h->amg_levels = sagg_levels(h);
-    } else {
-        NODAL_TRY(amg_setup_csr(h, K, gn_nnz, h->gn_indptr.as<int32_t>(), h->gn_indices.as<int32_t>(),
-                                h->gn_rowidx.as<int32_t>(), h->gn_data.as<double>(),
-                                h->gn_diag.as<int32_t>(), flag));
-        h->amg_levels = amg_num_levels(h);
-    }
-    if (n > K) {
-        schur_diag<<<grid_for(n - K), TB, 0, st>>>(indptr, indices, data, K, (int)n,
-                                                  h->gn_data.as<double>(), h->gn_diag.as<int32_t>(),
-                                                  h->schur.as<double>());
-        NODAL_HIP_TRY(h, hipGetLastError());
-    }
-    }  // (!direct)
-    auto system_spmv = [&](const double *in, double *out) -> int {
-        return ell_spmv ? sagg_spmv(h, in, out) : csr_spmv(h, in, out);
-    };
-
-    // ---- Krylov storage: V (m+1), Z (m), w, r ----
-    const int64_t ld = (int64_t)(align_up((size_t)n * 8) / 8);
-    const size_t vecs = (size_t)(2 * RESTART + 3) * ld * 8;
-    const size_t scal = ((size_t)DOT_GRID * MAXV + DOT_GRID + 2 * (MAXV + 1) + MAXV + G_WORDS) * 8;
-    NODAL_HIP_TRY(h, h->krylov.reserve(vecs + scal + 1024));
-    double *V = h->krylov.as<double>();
-    double *Z = V + (int64_t)(RESTART + 1) * ld;
-    double *w = Z + (int64_t)RESTART * ld;
-    double *r = w + ld;
-    double *partial = r + ld;
-    double *partial2 = partial + (int64_t)DOT_GRID * MAXV;
-    double *hdev = partial2 + DOT_GRID;        // MAXV + 1
-    double *hdev2 = hdev + (MAXV + 1);         // MAXV + 1
-    double *ydev = hdev2 + (MAXV + 1);         // MAXV
-    double *gst = ydev + MAXV;                 // G_WORDS: the small least-squares problem
-
-    const unsigned gd = grid_for(n, DOT_GRID), gv = grid_for(n);
+    NODAL_TRY(general_storage(h, S));
     NODAL_HIP_TRY(h, hipMemsetAsync(x, 0, (size_t)n * 8, st));
 
-    auto device_norm = [&](double *out) -> int {  // sqrt(sum partial2) -> host
-        gs_reduce<<<1, TB, 0, st>>>(partial, 0, 0, hdev, partial2, (int)gd);
-        double v = 0.0;
-        NODAL_TRY(nodal_read_words(h, &v, hdev + MAXV, 8));
-        *out = std::sqrt(v);
-        return NODAL_OK;
-    };
-
-    residual_of<<<gd, TB, 0, st>>>(b, nullptr, r, n, partial2);
+    residual_of<<<S.gd, TB, 0, st>>>(b, nullptr, S.r, n, S.partial2);
     double bnorm = 0.0;
-    NODAL_TRY(device_norm(&bnorm));
+    NODAL_TRY(device_norm(h, S, &bnorm));
     *iters = 0;
     *resid = 0.0;
     if (bnorm == 0.0) return NODAL_OK;  // x = 0
@@ -626,106 +783,13 @@ int general_impl(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_
     bool converged = false;
     h->kern_ms = 0;
     h->kern_launches = 0;
-    hipEvent_t e0 = h->ev[2], e1 = h->ev[3];
-    double hst[6];  // G_INV_H .. G_TOLB, as polled
 
     for (int cyc = 0; cyc < max_cycles && !converged; ++cyc) {
         const int window = (cyc == 0 || window_env) ? window_first : RESTART + 1;
-        scale_to<<<gv, TB, 0, st>>>(r, 1.0 / rnorm, V, n);
-        gst_begin<<<1, 64, 0, st>>>(gst, rnorm, tol * bnorm);
-        // the kernel that normalises v_{j+1} also leaves the start iterate of the cycle that preconditions it
-        const double *x0_dinv = nullptr;
-        nodal_cyc_t *x0_slot = nullptr;
-        int64_t x0_n = 0;
-        double x0_omega = 0.0;
-        if (use_sa && !direct && !sagg_x0_slot(h, &x0_dinv, &x0_slot, &x0_n, &x0_omega)) x0_slot = nullptr;
-        // Iterations are enqueued in batches; between batches the host reads the estimate and
-        // sizes the next batch from the convergence rate seen so far (three quarters of what is
-        // still missing, at least two).  A batch that overshoots costs idle launches only: every
-        // kernel that touches the small problem returns once G_DONE is up.
-        // (behind the direct factorisation an iteration is a 10-ms pair of triangular sweeps and one or two of them
-        // converge: the host looks after every one -- a batch of six ran four sweeps for nothing)
-        int enq = 0, batch = direct ? 1 : 6;
-        double est_prev = rnorm;
-        int at_prev = 0;
-        bool done = false;
-        while (!done && enq < RESTART) {
-            if (batch > RESTART - enq) batch = RESTART - enq;
-            for (int c = 0; c < batch; ++c, ++enq) {
-                const int j = enq;
-                double *vj = V + (int64_t)j * ld, *zj = Z + (int64_t)j * ld;
-                // z_j = M^-1 v_j
-                if (j == 0) nodal_nan_probe(h, vj, n, "fgmres v0");
-                if (direct) NODAL_TRY(slu_apply(h, vj, zj));
-                else if (use_sa) NODAL_TRY(sagg_apply(h, vj, zj, j > 0 && x0_slot != nullptr, cyc == 0 ? j : -1));
-                else NODAL_TRY(amg_apply(h, vj, zj));
-                if (j == 0) nodal_nan_probe(h, zj, K, "fgmres z0 (node block)");
-                if (n > K) {
-                    branch_solve<<<grid_for(n - K), TB, 0, st>>>(indptr, indices, data, K, (int)n,
-                                                                h->schur.as<double>(), vj, zj);
-                    NODAL_HIP_TRY(h, hipGetLastError());
-                }
-                // w = A z_j   (one launch per batch is timed)
-                if (ell_spmv) {
-                    NODAL_TRY(sagg_spmv(h, zj, w, c == 0 ? e0 : nullptr, c == 0 ? e1 : nullptr));
-                } else {
-                    if (c == 0) NODAL_HIP_TRY(h, hipEventRecord(e0, st));
-                    NODAL_TRY(csr_spmv(h, zj, w));
-                    if (c == 0) NODAL_HIP_TRY(h, hipEventRecord(e1, st));
-                }
-                if (j == 0) {
-                    nodal_nan_probe(h, zj, n, "fgmres z0");
-                    nodal_nan_probe(h, w, n, "fgmres w0 = A z0");
-                }
-                // classical Gram-Schmidt, twice, against the last `window` basis vectors (see window_first above)
-                const int nv_all = j + 1;
-                const int s0 = nv_all > window ? nv_all - window : 0, nv = nv_all - s0;
-                const double *Vw = V + (int64_t)s0 * ld;
-                DISPATCH_NV(nv, (gs_dots<NV><<<gd, TB, 0, st>>>(Vw, ld, nv, w, n, partial)));
-                gs_reduce<<<nv, TB, 0, st>>>(partial, (int)gd, nv, hdev + s0, nullptr, 0);
-                DISPATCH_NV(nv, (gs_update_dots<NV><<<gd, TB, 0, st>>>(Vw, ld, nv, hdev + s0, w, n, partial)));
-                gs_reduce<<<nv, TB, 0, st>>>(partial, (int)gd, nv, hdev2 + s0, nullptr, 0);
-                DISPATCH_NV(nv, (gs_update<NV><<<gd, TB, 0, st>>>(Vw, ld, nv, hdev2 + s0, w, n, partial2)));
-                gs_finish<<<1, TB, 0, st>>>(hdev, hdev2, partial2, (int)gd, j, s0, gst);
-                scale_by_device<<<gv, TB, 0, st>>>(w, gst, V + (int64_t)(j + 1) * ld, n, x0_dinv, x0_slot, x0_n, x0_omega);
-                NODAL_HIP_TRY(h, hipGetLastError());
-            }
-            NODAL_TRY(nodal_read_words(h, hst, gst + G_INV_H, sizeof hst));
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) { h->kern_ms += ms; h->kern_launches += 1; }
-            const double est = hst[G_EST - G_INV_H];
-            done = hst[G_DONE - G_INV_H] != 0.0;
-            if (hst[G_INFO - G_INV_H] != 0.0) *info = 1;
-            if (done) break;
-            // contraction per iteration since the last poll -> iterations still missing
-            double need = RESTART;
-            if (est > 0.0 && est < est_prev && enq > at_prev) {
-                const double rate = std::log(est / est_prev) / (double)(enq - at_prev);
-                need = std::log(tol * bnorm / est) / rate;
-            }
-            batch = (int)std::floor(0.75 * need);
-            if (batch < 2) batch = 2;
-            if (batch > enq) batch = enq;  // (at most doubling)
-            if (direct) batch = 1;
-            est_prev = est;
-            at_prev = enq;
-        }
-        total += (int)hst[G_COUNT - G_INV_H];
-        if (knob::TRACE.now()) {
-            double lg[RESTART];
-            NODAL_TRY(nodal_read_words(h, lg, gst + G_LOG, sizeof lg));
-            fprintf(stderr, "[fgmres] |w after Gram-Schmidt|^2 / |w|^2 per column:");
-            for (int i = 0; i < (int)hst[G_COUNT - G_INV_H] && i < RESTART; ++i) fprintf(stderr, " %.2g", lg[i]);
-            fprintf(stderr, "\n");
-        }
+        int count = 0;
+        NODAL_TRY(general_cycle(h, S, b, x, cyc == 0, window, RESTART, tol * bnorm, rnorm, &count, &rnorm, info));
+        total += count;
         if (*info) break;
-        // y = H^-1 g ; x += Z y
-        gst_solve<<<1, 64, 0, st>>>(gst, ydev);
-        add_combination<<<gv, TB, 0, st>>>(Z, ld, RESTART, ydev, x, gst, n);
-        // true residual
-        NODAL_TRY(system_spmv(x, w));
-        residual_of<<<gd, TB, 0, st>>>(b, w, r, n, partial2);
-        NODAL_TRY(device_norm(&rnorm));
         if (!(rnorm == rnorm)) { *info = 1; break; }
         if (rnorm <= 10.0 * tol * bnorm) converged = true;
         if (!converged && direct && h->slu_strict) {
@@ -789,3 +853,123 @@ int sparse_general_solve(nodal_ctx *h, int32_t *info, int32_t *iters, double *re
 int general_krylov_direct(nodal_ctx *h, const double *b, double *x, int32_t *info, int32_t *iters, double *resid) {
     return general_impl(h, b, x, info, iters, resid, true);
 }
+
+// ---- testing hooks (nodal_debug_fgmres_cycle / nodal_debug_general_array) ----
+// The context a hook's `system` names: 0 the handle's own assembled G; 1 the presolved, branch-free system the last
+// sparse solve left on h->reduced (which shares the handle's stream).  nullptr: there is none.
+static nodal_ctx *debug_general_system(nodal_ctx *h, int32_t system) {
+    if (system == 0) return h->have_numeric && !h->csr_only ? h : nullptr;
+    nodal_ctx *r = system == 1 ? h->reduced : nullptr;
+    return r && r->have_numeric && r->B == 0 && r->K == (int)r->n && r->n > 0 ? r : nullptr;
+}
+
+// general_setup (precond 0) or slu_factor (precond 1), the start of a solve (x = 0, |b|), then exactly ONE
+// general_cycle with the caller's window, column cap and tolerance: no outer loop, no verdict, no rescue.  The caller's
+// b and the iterate live in the context's dbg_apply; x, rhs and the solution flag of the context stay.  The
+// preconditioner, the Krylov storage and the K-cycle's calibration are left as a solve's first cycle leaves them.
+int general_debug_cycle(nodal_ctx *h, int32_t system, int32_t precond, int32_t window, int32_t max_cols, double rel_tol,
+                        int64_t n_caller, const double *b_host, double *x_out, double *V_out, double *Z_out, double *gst_out, double *y_out,
+                        double *norms_out, int64_t *params_out) {
+    if ((system != 0 && system != 1) || (precond != 0 && precond != 1) || (precond == 1 && system != 0))
+        return nodal_fail(h, NODAL_E_INVALID, "debug fgmres cycle: no such system / preconditioner");
+    if (window < 2 || window > MAXV || max_cols < 1 || max_cols > RESTART || !(rel_tol >= 0.0))
+        return nodal_fail(h, NODAL_E_INVALID, "debug fgmres cycle: window 2..41, max_cols 1..40, rel_tol >= 0");
+    if (!x_out || !V_out || !Z_out || !gst_out || !y_out || !norms_out || !params_out)
+        return nodal_fail(h, NODAL_E_INVALID, "debug fgmres cycle: an output is missing");
+    nodal_ctx *c = debug_general_system(h, system);
+    if (!c) return nodal_fail(h, NODAL_E_INVALID, "debug fgmres cycle: the handle holds no such system");
+    const int64_t n = c->n;
+    if (n != n_caller) return nodal_fail(h, NODAL_E_INVALID, "debug fgmres cycle: the system has another number of unknowns");
+    hipStream_t st = c->stream;
+    for (int k = 0; k < 16; ++k) params_out[k] = 0;
+    norms_out[0] = norms_out[1] = 0.0;
+    if (n == 0) return NODAL_OK;
+
+    GeneralState S;
+    S.direct = precond == 1;
+    S.K = S.direct ? (int)n : c->K;
+    int32_t info = 0;
+    if (S.direct) {  // (the node block and the Schur diagonal of an earlier precond-0 call stay: nothing here writes them)
+        NODAL_TRY(nodal_lift_error(h, c, slu_factor(c, &info)));
+        if (info > 0) return nodal_fail(h, NODAL_E_INVALID, "debug fgmres cycle: the sparse LU found the matrix singular");
+    } else {
+        h->dbg_general_system = -1;
+        NODAL_TRY(nodal_lift_error(h, c, general_setup(c, S, &info)));
+        if (info) return nodal_fail(h, NODAL_E_INVALID, "debug fgmres cycle: a floating island");
+        h->dbg_general_system = system;
+        h->dbg_general_epoch = c->numeric_epoch;
+    }
+    NODAL_TRY(nodal_lift_error(h, c, general_storage(c, S)));
+    const size_t vec = align_up((size_t)n * 8);
+    NODAL_HIP_TRY(h, c->dbg_apply.reserve(2 * vec + 256));
+    double *x = c->dbg_apply.as<double>(), *bdev = x + vec / 8;
+    const double *b = c->rhs.as<double>();
+    if (b_host) {
+        NODAL_HIP_TRY(h, hipMemcpyAsync(bdev, b_host, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        b = bdev;
+    }
+    NODAL_HIP_TRY(h, hipMemsetAsync(x, 0, (size_t)n * 8, st));
+    residual_of<<<S.gd, TB, 0, st>>>(b, nullptr, S.r, n, S.partial2);
+    double bnorm = 0.0, rnorm = 0.0;
+    int st_ = nodal_lift_error(h, c, device_norm(c, S, &bnorm));  // (waits: the copy of b_host is done)
+    if (st_ != NODAL_OK) {
+        (void)nodal_wait_stream(h, st, NODAL_SITE);
+        return st_;
+    }
+    int count = 0;
+    for (int k = 0; k < G_WORDS; ++k) gst_out[k] = 0.0;
+    for (int k = 0; k < MAXV; ++k) y_out[k] = 0.0;
+    if (bnorm > 0.0) {
+        c->kern_ms = 0;
+        c->kern_launches = 0;
+        NODAL_TRY(nodal_lift_error(h, c, general_cycle(c, S, b, x, true, window, max_cols, rel_tol * bnorm, bnorm, &count,
+                                                       &rnorm, &info)));
+        NODAL_HIP_TRY(h, hipMemcpyAsync(gst_out, S.gst, (size_t)G_WORDS * 8, hipMemcpyDeviceToHost, st));
+        if (!info) NODAL_HIP_TRY(h, hipMemcpyAsync(y_out, S.ydev, (size_t)MAXV * 8, hipMemcpyDeviceToHost, st));
+        NODAL_HIP_TRY(h, hipMemcpy2DAsync(V_out, (size_t)n * 8, S.V, (size_t)S.ld * 8, (size_t)n * 8, (size_t)count + 1,
+                                          hipMemcpyDeviceToHost, st));
+        if (count > 0)
+            NODAL_HIP_TRY(h, hipMemcpy2DAsync(Z_out, (size_t)n * 8, S.Z, (size_t)S.ld * 8, (size_t)n * 8, (size_t)count,
+                                              hipMemcpyDeviceToHost, st));
+    }
+    NODAL_HIP_TRY(h, hipMemcpyAsync(x_out, x, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    NODAL_WAIT_STREAM(h, st);
+    norms_out[0] = rnorm;
+    norms_out[1] = bnorm;
+    params_out[0] = n; params_out[1] = S.K; params_out[2] = S.ld; params_out[3] = count; params_out[4] = window;
+    params_out[5] = S.use_sa; params_out[6] = S.ell_spmv; params_out[7] = S.direct ? 0 : c->amg_levels;
+    params_out[8] = S.gd; params_out[9] = info;
+    return NODAL_OK;
+}
+
+// Stream wait and one device-to-host copy: what the last precond-0 setup of general_debug_cycle left, and the system it
+// ran on.  Nothing is launched, nothing on the device is written.
+int general_debug_array(nodal_ctx *h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out) {
+    nodal_ctx *c = h->dbg_general_system >= 0 ? debug_general_system(h, h->dbg_general_system) : nullptr;
+    if (!c || c->numeric_epoch != h->dbg_general_epoch)
+        return nodal_fail(h, NODAL_E_INVALID, "debug general array: no block preconditioner set up by nodal_debug_fgmres_cycle");
+    const int64_t n = c->n, K = c->K, gnz = c->gn_nnz;
+    const DevBuf *buf = nullptr;
+    int64_t bytes = 0;
+    switch (which) {
+    case NODAL_GA_GN_INDPTR: buf = &c->gn_indptr; bytes = (K + 1) * 4; break;
+    case NODAL_GA_GN_INDICES: buf = &c->gn_indices; bytes = gnz * 4; break;
+    case NODAL_GA_GN_ROWIDX: buf = &c->gn_rowidx; bytes = gnz * 4; break;
+    case NODAL_GA_GN_DATA: buf = &c->gn_data; bytes = gnz * 8; break;
+    case NODAL_GA_GN_DIAG: buf = &c->gn_diag; bytes = K * 4; break;
+    case NODAL_GA_SCHUR: buf = &c->schur; bytes = (n - K) * 8; break;
+    case NODAL_GA_INDPTR: buf = &c->indptr; bytes = (n + 1) * 4; break;
+    case NODAL_GA_INDICES: buf = &c->indices; bytes = c->nnz * 4; break;
+    case NODAL_GA_DATA: buf = &c->data; bytes = c->nnz * 8; break;
+    case NODAL_GA_RHS: buf = &c->rhs; bytes = n * 8; break;
+    default: return nodal_fail(h, NODAL_E_INVALID, "debug general array: no such buffer");
+    }
+    *bytes_out = bytes;
+    if (!dst || bytes == 0) return NODAL_OK;
+    if (capacity_bytes < bytes) return nodal_fail(h, NODAL_E_INVALID, "debug general array: the destination is too small");
+    NODAL_WAIT_STREAM(h, c->stream);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dst, buf->p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    NODAL_WAIT_STREAM(h, c->stream);
+    return NODAL_OK;
+}
+
