@@ -921,6 +921,47 @@ int nodal_debug_fgmres_cycle(nodal_handle h, int32_t system, int32_t precond, in
                              double *gst_out /* [NODAL_FG_WORDS] */, double *y_out /* [41] */, double *norms_out /* [2] */,
                              int64_t *params_out /* [16] */);
 int nodal_debug_general_array(nodal_handle h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
+/* The presolve's plan, rewrite and recovery (csrc/presolve.hip) and the scan under its renumbering (csrc/scan.hip) with
+ * no solve and no acceptance test behind them: what tests/presolve_reference.py states as linear algebra on the
+ * original G x = b and tests/test_gpu_presolve.py compares.  The hooks have no arithmetic and no knob of their own and
+ * launch no kernel a solve does not launch.
+ * nodal_debug_presolve_build: for the handle's assembled member, whatever its size (the n > 512 and sparse-switch
+ *   thresholds belong to the callers), the plan -- the one made ahead during the assembly when it stands, as a solve
+ *   takes it -- then the rewrite into the reduced context and that context's symbolic (unless kept) and numeric
+ *   assembly, exactly as a sparse solve's presolve does them.  info[16]: 0 the plan is ok (0: declined, nothing below
+ *   but 4 .. 6, 11 .. 13 is set), 1 the rewrite succeeded (0: a row it cannot express, nothing assembled), 2 Kr,
+ *   3 max_level, 4 pivots, 5 branches kept, 6 components of the reduced table, 7 its unknowns, 8 entries of its matrix,
+ *   9 its passive_network, 10 same_topology: the reduced context's symbolic assembly was reused, 11 the plan was the
+ *   one made ahead, 12 K, 13 B.  A declined plan or a failed rewrite is a result, not an error.  NODAL_E_INVALID: no
+ *   assembled system with branch equations and a host copy of its table; a stamping error of the reduced table comes
+ *   back as the reduced assembly's status.  The handle's solution, right-hand side and matrix stay as found; the
+ *   reduced context is left as the presolve of a solve leaves it before its solver runs.
+ * nodal_debug_presolve_array: one array of what the last nodal_debug_presolve_build left (enum below), host structs
+ *   flattened or one device-to-host copy behind a stream wait.  The plan: pivots (i32, sorted), the expressions in plan
+ *   order -- p, q, c, d (i32), cst, g (f64) -- the kept branches in branch order -- kk, type, a, b, c, d (i32), value
+ *   (f64) -- row_of, level_of (i32, B).  The device's newidx (i32, K).  The reduced component table: type (u8), value
+ *   (f64), a, b, c, d, k (i32).  The reduced context's CSR (indptr i32 n' + 1, indices i32, data f64) and right-hand
+ *   side (f64 n').  dst == NULL: the size only.  NODAL_E_INVALID when no such build stands (none yet, the system
+ *   assembled or the table uploaded anew since, or the array belongs to a stage the build did not reach).
+ * nodal_debug_presolve_recover: presolve_recover of that build on the caller's y (host, ny = Kr + kept entries; it
+ *   need not solve anything): the handle's x is filled with NaN, then the recovery kernels run as in a solve; x_out
+ *   [n].  Whatever solution the handle held is put back and its flag stays: a solve after the hooks returns the bits of
+ *   the same solve without them.
+ * nodal_debug_scan_u32: scan_exclusive_u32 of in [n] (host) in scratch of the hook's own sized by scan_tmp_bytes; in_place
+ *   != 0 scans the device copy onto itself; total_out != NULL asks for the device total.  out [n]. */
+enum {
+    NODAL_PS_PIVOTS = 0, NODAL_PS_EXPR_P = 1, NODAL_PS_EXPR_Q = 2, NODAL_PS_EXPR_C = 3, NODAL_PS_EXPR_D = 4,
+    NODAL_PS_EXPR_CST = 5, NODAL_PS_EXPR_G = 6, NODAL_PS_KEPT_KK = 7, NODAL_PS_KEPT_TYPE = 8, NODAL_PS_KEPT_A = 9,
+    NODAL_PS_KEPT_B = 10, NODAL_PS_KEPT_C = 11, NODAL_PS_KEPT_D = 12, NODAL_PS_KEPT_VALUE = 13, NODAL_PS_ROW_OF = 14,
+    NODAL_PS_LEVEL_OF = 15, NODAL_PS_NEWIDX = 16, NODAL_PS_R_TYPE = 17, NODAL_PS_R_VALUE = 18, NODAL_PS_R_A = 19,
+    NODAL_PS_R_B = 20, NODAL_PS_R_C = 21, NODAL_PS_R_D = 22, NODAL_PS_R_K = 23, NODAL_PS_R_INDPTR = 24,
+    NODAL_PS_R_INDICES = 25, NODAL_PS_R_DATA = 26, NODAL_PS_R_RHS = 27
+};
+int nodal_debug_presolve_build(nodal_handle h, int64_t *info /* [16] */);
+int nodal_debug_presolve_array(nodal_handle h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
+int nodal_debug_presolve_recover(nodal_handle h, int64_t ny, const double *y, double *x_out);
+int nodal_debug_scan_u32(nodal_handle h, int64_t n, const uint32_t *in, uint32_t *out, int32_t in_place,
+                         uint32_t *total_out);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@ OPT_TRANSIENT_TAPE = 5
 
 _p = C.POINTER
 _i32p, _i64p, _f64p, _u8p = _p(C.c_int32), _p(C.c_int64), _p(C.c_double), _p(C.c_uint8)
+_u32p = _p(C.c_uint32)
 
 # name -> (restype, argtypes); every symbol include/nodal_hip.h declares
 SIGNATURES = {
@@ -107,7 +108,25 @@ SIGNATURES = {
     "nodal_debug_fgmres_cycle": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64,
                                            _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i64p]),
     "nodal_debug_general_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
+    "nodal_debug_presolve_build": (C.c_int, [C.c_void_p, _i64p]),
+    "nodal_debug_presolve_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
+    "nodal_debug_presolve_recover": (C.c_int, [C.c_void_p, C.c_int64, _f64p, _f64p]),
+    "nodal_debug_scan_u32": (C.c_int, [C.c_void_p, C.c_int64, _u32p, _u32p, C.c_int32, _u32p]),
 }
+
+# nodal_debug_presolve_build: the words of info; nodal_debug_presolve_array: `which` in the header's order (NODAL_PS_*)
+# with the item type of each array -- the plan (pivots, expressions, kept branches, row_of, level_of), the device's
+# newidx, the reduced component table, the reduced context's CSR and right-hand side
+PRESOLVE_INFO = ("ok", "built", "Kr", "max_level", "npivots", "nkept", "ncomp", "n", "nnz", "passive", "same_topology",
+                 "ahead", "K", "B")
+PRESOLVE_PLAN_ARRAYS = 16  # the first so many arrays belong to the plan: they exist for a declined plan too
+PRESOLVE_ARRAYS = (("pivots", np.int32), ("expr_p", np.int32), ("expr_q", np.int32), ("expr_c", np.int32),
+                   ("expr_d", np.int32), ("expr_cst", np.float64), ("expr_g", np.float64), ("kept_kk", np.int32),
+                   ("kept_type", np.int32), ("kept_a", np.int32), ("kept_b", np.int32), ("kept_c", np.int32),
+                   ("kept_d", np.int32), ("kept_value", np.float64), ("row_of", np.int32), ("level_of", np.int32),
+                   ("newidx", np.int32), ("r_type", np.uint8), ("r_value", np.float64), ("r_a", np.int32),
+                   ("r_b", np.int32), ("r_c", np.int32), ("r_d", np.int32), ("r_k", np.int32), ("r_indptr", np.int32),
+                   ("r_indices", np.int32), ("r_data", np.float64), ("r_rhs", np.float64))
 
 # nodal_debug_fgmres_cycle: the small least-squares problem's block of doubles in the header's layout (NODAL_FG_*), and
 # the names of the words of params_out
@@ -959,6 +978,44 @@ class Handle:
                    g=gst[FG_G:FG_INV_H], inv_h=float(gst[FG_INV_H]), est=float(gst[FG_EST]), done=float(gst[FG_DONE]),
                    gcount=float(gst[FG_COUNT]), tolb=float(gst[FG_TOLB]), rnorm=float(norms[0]), bnorm=float(norms[1]))
         return out
+
+    def debug_presolve_build(self):
+        """Plan, rewrite and reduced assembly of the presolve for the assembled member, as a sparse solve does them and
+        nothing behind them (testing hook; nodal_hip.h).  Returns a dict: the words of PRESOLVE_INFO (ok False: the
+        plan declined; built False: the rewrite met a row it cannot express) and the arrays of PRESOLVE_ARRAYS the
+        build reached -- the plan's always, newidx, the reduced table (r_*), CSR and right-hand side when built."""
+        info = np.zeros(16, dtype=np.int64)
+        self._check(self.lib.nodal_debug_presolve_build(self._h, _ptr(info, C.c_int64)))
+        out = {name: int(info[k]) for k, name in enumerate(PRESOLVE_INFO)}
+        for which, (name, dtype) in enumerate(PRESOLVE_ARRAYS):
+            if which >= PRESOLVE_PLAN_ARRAYS and not out["built"]:
+                break
+            size = C.c_int64(0)
+            self._check(self.lib.nodal_debug_presolve_array(self._h, which, None, 0, C.byref(size)))
+            arr = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+            if size.value:
+                self._check(self.lib.nodal_debug_presolve_array(self._h, which, C.c_void_p(arr.ctypes.data), arr.nbytes,
+                                                                C.byref(size)))
+                assert size.value == arr.nbytes
+            out[name] = arr
+        return out
+
+    def debug_presolve_recover(self, y):
+        """presolve_recover of the last debug_presolve_build on y (Kr + kept entries, need not solve anything): x [n],
+        NaN where no recovery kernel wrote (testing hook).  The handle's solution stays as found."""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        x = np.zeros(self.n)
+        self._check(self.lib.nodal_debug_presolve_recover(self._h, len(y), _ptr(y, C.c_double), _ptr(x, C.c_double)))
+        return x
+
+    def debug_scan_u32(self, values, in_place=False, total=True):
+        """scan_exclusive_u32 of `values` (testing hook): (the exclusive prefix sums, the device total or None)."""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        out = np.empty_like(values)
+        tot = C.c_uint32(0)
+        self._check(self.lib.nodal_debug_scan_u32(self._h, len(values), _ptr(values, C.c_uint32), _ptr(out, C.c_uint32),
+                                                  int(bool(in_place)), C.byref(tot) if total else None))
+        return out, (int(tot.value) if total else None)
 
     def debug_general_arrays(self):
         """What the last precond-0 setup of debug_fgmres_cycle left, raw (testing hook): a dict of GENERAL_ARRAYS --

@@ -1214,6 +1214,35 @@ int nodal_debug_general_array(nodal_handle h, int32_t which, void *dst, int64_t 
     return general_debug_array(h, which, dst, capacity_bytes, bytes_out);
 }
 
+int nodal_debug_presolve_build(nodal_handle h, int64_t *info) {
+    if (!h || !info) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return presolve_debug_build(h, info);
+}
+
+int nodal_debug_presolve_array(nodal_handle h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out) {
+    if (!h || !bytes_out) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return presolve_debug_array(h, which, dst, capacity_bytes, bytes_out);
+}
+
+int nodal_debug_presolve_recover(nodal_handle h, int64_t ny, const double *y, double *x_out) {
+    if (!h || ny < 0 || (ny > 0 && !y) || !x_out) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return presolve_debug_recover(h, ny, y, x_out);
+}
+
+int nodal_debug_scan_u32(nodal_handle h, int64_t n, const uint32_t *in, uint32_t *out, int32_t in_place,
+                         uint32_t *total_out) {
+    if (!h) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return scan_debug_u32(h, n, in, out, in_place != 0, total_out);
+}
+
 int nodal_residual(nodal_handle h, double *scaled_residual) {
     if (!h || !scaled_residual) return NODAL_E_INVALID;
     DeviceGuard g(h);

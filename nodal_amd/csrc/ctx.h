@@ -343,6 +343,7 @@ struct nodal_ctx {
     bool extra_streams = false;  // NODAL_OPT_EXTRA_STREAMS: the handle is used alone and may use streams of its own
     void *slu = nullptr;  // multifrontal LU of the direct route (sparse_direct.hip)
     void *ps_plan = nullptr;  // the presolve's plan, made ahead of the solve (presolve.hip: presolve_plan_ahead)
+    void *ps_debug = nullptr; // testing hooks nodal_debug_presolve_*: the plan of the last build and what it reported
     bool slu_strict = false;  // refinement judged by |r| / |b| alone (the direct route's second opinion)
     int32_t last_iterations = 0;
     double last_relres = 0;
@@ -420,6 +421,8 @@ static inline int nodal_fail(nodal_ctx *h, int code, const char *msg) {
 size_t scan_tmp_bytes(int64_t n);
 int scan_exclusive_u32(nodal_ctx *h, const uint32_t *in, uint32_t *out, int64_t n,
                        uint32_t *total_dev, void *tmp);
+// testing hook (nodal_debug_scan_u32): scan_exclusive_u32 on a host array, nothing else
+int scan_debug_u32(nodal_ctx *h, int64_t n, const uint32_t *in, uint32_t *out, bool in_place, uint32_t *total_out);
 
 // ---- stamping (stamp.hip) ----
 int stamp_symbolic(nodal_ctx *h);
@@ -848,6 +851,11 @@ void presolve_plan_ahead(nodal_ctx *h);  // host-only; called by stamp_numeric w
 void presolve_free_plan(nodal_ctx *h);
 int presolve_solve(nodal_ctx *h, bool *done, int32_t *info, int32_t *iters, double *resid,
                    bool dense_child = false);
+// testing hooks (nodal_debug_presolve_build / _array / _recover): plan, rewrite and reduced assembly as presolve_solve
+// does them, what they left, and presolve_recover on the caller's y -- no solver, no acceptance test
+int presolve_debug_build(nodal_ctx *h, int64_t *info);
+int presolve_debug_array(nodal_ctx *h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
+int presolve_debug_recover(nodal_ctx *h, int64_t ny, const double *y, double *x_out);
 // ---- sparse direct route (sparse_direct.hip): multifrontal LU + FGMRES refinement ----
 // tiny_factor scales (and signs) the value that replaces an unusable pivot
 int slu_factor(nodal_ctx *h, int32_t *info, double tiny_factor = 1.0, double tiny_threshold = 0.0);

@@ -879,32 +879,32 @@ void presolve_plan_ahead(nodal_ctx *h) {
     c->key = key;
     c->valid = true;
 }
+// (testing hooks at the end of the file: the plan of the last nodal_debug_presolve_build and what it belongs to)
+namespace {
+struct PresolveDebug {
+    PresolvePlan plan;
+    bool valid = false, built = false;
+    uint64_t table_epoch = 0, numeric_epoch = 0;
+};
+}  // namespace
 void presolve_free_plan(nodal_ctx *h) {
     delete static_cast<PlanCache *>(h->ps_plan);
     h->ps_plan = nullptr;
+    delete static_cast<PresolveDebug *>(h->ps_debug);
+    h->ps_debug = nullptr;
 }
 
-int presolve_solve(nodal_ctx *h, bool *done, int32_t *info, int32_t *iters, double *resid,
-                   bool dense_child) {
-    *done = false;
-    if (h->B == 0 || h->host.type.empty()) return NODAL_OK;
-    const double *value = h->host.value.data();
-    if (h->batch > 0) {
-        if (h->host.values_batch.empty()) return NODAL_OK;
-        value = h->host.values_batch.data() + (size_t)h->member * h->ncomp;
-    }
-    const bool trace = knob::TRACE.now();
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = now();
-    PresolvePlan local_plan;
+// The steps presolve_solve and the testing hook nodal_debug_presolve_build share.
+// the plan made ahead while the device stamped (presolve_plan_ahead) when its key stands, else planned now into `local`
+static const PresolvePlan &presolve_take_plan(nodal_ctx *h, const double *value, PresolvePlan &local, bool *ahead_out) {
     PlanCache *pc = static_cast<PlanCache *>(h->ps_plan);
     const bool ahead = pc && pc->valid && !h->host.branch_rows.empty() && pc->key == plan_key(h, value);
-    if (!ahead) presolve_plan(h, value, local_plan);
-    const PresolvePlan &plan = ahead ? pc->plan : local_plan;  // (planned while the device stamped: presolve_plan_ahead)
-    if (!plan.ok) return NODAL_OK;
-    const auto t1 = now();
-
+    if (!ahead) presolve_plan(h, value, local);
+    if (ahead_out) *ahead_out = ahead;
+    return ahead ? pc->plan : local;
+}
+// the context of the reduced system, made on first use: it borrows the handle's streams and events
+static nodal_ctx *presolve_reduced_ctx(nodal_ctx *h) {
     if (!h->reduced) {
         h->reduced = new nodal_ctx();
         h->reduced->device = h->device;
@@ -921,16 +921,45 @@ int presolve_solve(nodal_ctx *h, bool *done, int32_t *info, int32_t *iters, doub
         h->reduced->stream_owner = h->stream_owner ? h->stream_owner : h;
         h->reduced->keep_host_table = false;
     }
-    nodal_ctx *r = h->reduced;
-    const double *value_dev =
-        h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
+    return h->reduced;
+}
+static const double *presolve_values_dev(const nodal_ctx *h) {
+    return h->batch > 0 ? h->values_batch.as<double>() + (int64_t)h->member * h->ncomp : h->value.as<double>();
+}
+// the reduced table's assembly: the symbolic part only for a new topology
+static int presolve_assemble_reduced(nodal_ctx *h, nodal_ctx *r) {
+    int s = r->have_symbolic ? NODAL_OK : stamp_symbolic(r);  // (kept: same topology as the last solve's)
+    if (s == NODAL_OK) s = stamp_numeric(r, 0, nullptr);
+    if (s != NODAL_OK) h->err = r->err;
+    return s;
+}
+
+int presolve_solve(nodal_ctx *h, bool *done, int32_t *info, int32_t *iters, double *resid,
+                   bool dense_child) {
+    *done = false;
+    if (h->B == 0 || h->host.type.empty()) return NODAL_OK;
+    const double *value = h->host.value.data();
+    if (h->batch > 0) {
+        if (h->host.values_batch.empty()) return NODAL_OK;
+        value = h->host.values_batch.data() + (size_t)h->member * h->ncomp;
+    }
+    const bool trace = knob::TRACE.now();
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = now();
+    PresolvePlan local_plan;
+    const PresolvePlan &plan = presolve_take_plan(h, value, local_plan, nullptr);
+    if (!plan.ok) return NODAL_OK;
+    const auto t1 = now();
+
+    nodal_ctx *r = presolve_reduced_ctx(h);
+    const double *value_dev = presolve_values_dev(h);
     bool built = false;
     NODAL_TRY(presolve_build_reduced(h, r, value, value_dev, plan, &built));
     if (!built) return NODAL_OK;
     const auto t2 = now();
-    int s = r->have_symbolic ? NODAL_OK : stamp_symbolic(r);  // (kept: same topology as the last solve's)
-    if (s == NODAL_OK) s = stamp_numeric(r, 0, nullptr);
-    if (s != NODAL_OK) { h->err = r->err; return s; }
+    int s = presolve_assemble_reduced(h, r);
+    if (s != NODAL_OK) return s;
     const auto t3 = now();
     int32_t rinfo = 0;
     if (dense_child) {
@@ -985,5 +1014,140 @@ int presolve_solve(nodal_ctx *h, bool *done, int32_t *info, int32_t *iters, doub
     if (!(scaled <= 1e-11)) return NODAL_OK;  // fall back to the full-system solve
     *info = 0;
     *done = true;
+    return NODAL_OK;
+}
+
+// ---- testing hooks (nodal_debug_presolve_build / _array / _recover) ----
+// Plan, rewrite and reduced assembly through the functions presolve_solve calls, in its order, for the handle's current
+// member at any size; then nothing: no solver, no recovery, no acceptance test.  The plan is copied aside for the two
+// hooks below, with the epochs of the table and of the values it belongs to.
+int presolve_debug_build(nodal_ctx *h, int64_t *info) {
+    for (int k = 0; k < 16; ++k) info[k] = 0;
+    PresolveDebug *d = static_cast<PresolveDebug *>(h->ps_debug);
+    if (d) d->valid = d->built = false;
+    const double *value = plan_values(h);
+    if (!h->have_numeric || h->csr_only || h->B == 0 || h->host.type.empty() || !value)
+        return nodal_fail(h, NODAL_E_INVALID, "debug presolve build: no assembled system with branch equations and a host table");
+    if (!d) h->ps_debug = d = new PresolveDebug();
+    bool ahead = false;
+    PresolvePlan local_plan;
+    d->plan = presolve_take_plan(h, value, local_plan, &ahead);
+    const PresolvePlan &plan = d->plan;
+    d->table_epoch = h->table_epoch;
+    d->numeric_epoch = h->numeric_epoch;
+    d->valid = true;
+    info[0] = plan.ok;
+    info[4] = (int64_t)plan.pivots.size();
+    info[5] = (int64_t)plan.kept.size();
+    info[11] = ahead;
+    info[12] = h->K;
+    info[13] = h->B;
+    if (!plan.ok) return NODAL_OK;
+    info[2] = plan.Kr;
+    info[3] = plan.max_level;
+    nodal_ctx *r = presolve_reduced_ctx(h);
+    bool built = false;
+    NODAL_TRY(presolve_build_reduced(h, r, value, presolve_values_dev(h), plan, &built));
+    if (!built) return NODAL_OK;
+    info[10] = r->have_symbolic;  // (presolve_build_reduced leaves it standing for an unchanged topology only)
+    NODAL_TRY(presolve_assemble_reduced(h, r));
+    NODAL_WAIT_STREAM(h, h->stream);
+    d->built = true;
+    info[1] = 1;
+    info[6] = r->ncomp;
+    info[7] = r->n;
+    info[8] = r->nnz;
+    info[9] = r->passive_network;
+    return NODAL_OK;
+}
+
+static PresolveDebug *presolve_debug_state(nodal_ctx *h) {
+    PresolveDebug *d = static_cast<PresolveDebug *>(h->ps_debug);
+    return d && d->valid && d->table_epoch == h->table_epoch && d->numeric_epoch == h->numeric_epoch ? d : nullptr;
+}
+
+int presolve_debug_array(nodal_ctx *h, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out) {
+    const PresolveDebug *d = presolve_debug_state(h);
+    if (!d) return nodal_fail(h, NODAL_E_INVALID, "debug presolve array: no build of nodal_debug_presolve_build stands");
+    const PresolvePlan &plan = d->plan;
+    std::vector<int32_t> ints;
+    std::vector<double> reals;
+    const void *host = nullptr;
+    const DevBuf *dev = nullptr;
+    int64_t bytes = 0;
+    auto from_exprs = [&](auto field) { for (const Expr &e : plan.exprs) ints.push_back(field(e)); };
+    auto from_kept = [&](auto field) { for (const KeptBranch &k : plan.kept) ints.push_back(field(k)); };
+    const nodal_ctx *r = h->reduced;
+    const bool plan_side = which <= NODAL_PS_LEVEL_OF;
+    if (which < 0 || which > NODAL_PS_R_RHS) return nodal_fail(h, NODAL_E_INVALID, "debug presolve array: no such array");
+    if (!plan_side && (!d->built || !r)) return nodal_fail(h, NODAL_E_INVALID, "debug presolve array: the build did not reach the rewrite");
+    switch (which) {
+    case NODAL_PS_PIVOTS: ints = plan.pivots; break;
+    case NODAL_PS_EXPR_P: from_exprs([](const Expr &e) { return e.p; }); break;
+    case NODAL_PS_EXPR_Q: from_exprs([](const Expr &e) { return e.q; }); break;
+    case NODAL_PS_EXPR_C: from_exprs([](const Expr &e) { return e.c; }); break;
+    case NODAL_PS_EXPR_D: from_exprs([](const Expr &e) { return e.d; }); break;
+    case NODAL_PS_EXPR_CST: for (const Expr &e : plan.exprs) reals.push_back(e.cst); break;
+    case NODAL_PS_EXPR_G: for (const Expr &e : plan.exprs) reals.push_back(e.g); break;
+    case NODAL_PS_KEPT_KK: from_kept([](const KeptBranch &k) { return k.kk; }); break;
+    case NODAL_PS_KEPT_TYPE: from_kept([](const KeptBranch &k) { return k.type; }); break;
+    case NODAL_PS_KEPT_A: from_kept([](const KeptBranch &k) { return k.a; }); break;
+    case NODAL_PS_KEPT_B: from_kept([](const KeptBranch &k) { return k.b; }); break;
+    case NODAL_PS_KEPT_C: from_kept([](const KeptBranch &k) { return k.c; }); break;
+    case NODAL_PS_KEPT_D: from_kept([](const KeptBranch &k) { return k.d; }); break;
+    case NODAL_PS_KEPT_VALUE: for (const KeptBranch &k : plan.kept) reals.push_back(k.value); break;
+    case NODAL_PS_ROW_OF: ints = plan.row_of; break;
+    case NODAL_PS_LEVEL_OF: ints = plan.level_of; break;
+    case NODAL_PS_NEWIDX: dev = &h->ps_newidx; bytes = (int64_t)h->K * 4; break;
+    case NODAL_PS_R_TYPE: dev = &r->type; bytes = r->ncomp; break;
+    case NODAL_PS_R_VALUE: dev = &r->value; bytes = r->ncomp * 8; break;
+    case NODAL_PS_R_A: dev = &r->a; bytes = r->ncomp * 4; break;
+    case NODAL_PS_R_B: dev = &r->b; bytes = r->ncomp * 4; break;
+    case NODAL_PS_R_C: dev = &r->c; bytes = r->ncomp * 4; break;
+    case NODAL_PS_R_D: dev = &r->d; bytes = r->ncomp * 4; break;
+    case NODAL_PS_R_K: dev = &r->k; bytes = r->ncomp * 4; break;
+    case NODAL_PS_R_INDPTR: dev = &r->indptr; bytes = (r->n + 1) * 4; break;
+    case NODAL_PS_R_INDICES: dev = &r->indices; bytes = r->nnz * 4; break;
+    case NODAL_PS_R_DATA: dev = &r->data; bytes = r->nnz * 8; break;
+    default: dev = &r->rhs; bytes = r->n * 8; break;  // NODAL_PS_R_RHS
+    }
+    if (!dev) {
+        const bool is_real = which == NODAL_PS_EXPR_CST || which == NODAL_PS_EXPR_G || which == NODAL_PS_KEPT_VALUE;
+        host = is_real ? (const void *)reals.data() : (const void *)ints.data();
+        bytes = is_real ? (int64_t)reals.size() * 8 : (int64_t)ints.size() * 4;
+    }
+    *bytes_out = bytes;
+    if (!dst || bytes == 0) return NODAL_OK;
+    if (capacity_bytes < bytes) return nodal_fail(h, NODAL_E_INVALID, "debug presolve array: the destination is too small");
+    if (!dev) {
+        memcpy(dst, host, (size_t)bytes);
+        return NODAL_OK;
+    }
+    NODAL_WAIT_STREAM(h, h->stream);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dst, dev->p, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
+    NODAL_WAIT_STREAM(h, h->stream);
+    return NODAL_OK;
+}
+
+// presolve_recover of the last build's plan on the caller's y.  y and the solution the handle held live in dbg_apply
+// during the call; x is NaN before the recovery kernels run, and the solution is put back behind them.
+int presolve_debug_recover(nodal_ctx *h, int64_t ny, const double *y, double *x_out) {
+    const PresolveDebug *d = presolve_debug_state(h);
+    if (!d || !d->built) return nodal_fail(h, NODAL_E_INVALID, "debug presolve recover: no build of nodal_debug_presolve_build stands");
+    const PresolvePlan &plan = d->plan;
+    if (ny != (int64_t)plan.Kr + (int64_t)plan.kept.size())
+        return nodal_fail(h, NODAL_E_INVALID, "debug presolve recover: y has another number of entries than Kr + kept");
+    hipStream_t st = h->stream;
+    const int64_t n = h->n;
+    const size_t ay = (((size_t)ny * 8) + 255) & ~(size_t)255;
+    NODAL_HIP_TRY(h, h->dbg_apply.reserve(ay + (size_t)n * 8 + 256));
+    double *ydev = h->dbg_apply.as<double>(), *saved = ydev + ay / 8, *x = h->x.as<double>();
+    if (ny) NODAL_HIP_TRY(h, hipMemcpyAsync(ydev, y, (size_t)ny * 8, hipMemcpyHostToDevice, st));
+    if (h->have_x) NODAL_HIP_TRY(h, hipMemcpyAsync(saved, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    NODAL_TRY(dense_fill_nan(h, x, n));
+    NODAL_TRY(presolve_recover(h, plan, ydev));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(x_out, x, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (h->have_x) NODAL_HIP_TRY(h, hipMemcpyAsync(x, saved, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    NODAL_WAIT_STREAM(h, st);
     return NODAL_OK;
 }

@@ -143,3 +143,22 @@ int scan_exclusive_u32(nodal_ctx *h, const uint32_t *in, uint32_t *out, int64_t 
     NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }
+
+// testing hook (nodal_debug_scan_u32): the caller's array into dbg_apply -- in | out | total | tmp, the last sized by
+// scan_tmp_bytes -- scan_exclusive_u32 out of place or onto the input itself, and the result back.
+int scan_debug_u32(nodal_ctx *h, int64_t n, const uint32_t *in, uint32_t *out, bool in_place, uint32_t *total_out) {
+    if (n < 0 || (n > 0 && (!in || !out))) return nodal_fail(h, NODAL_E_INVALID, "debug scan: no array");
+    hipStream_t st = h->stream;
+    const size_t vec = (((size_t)n * 4) + 255) & ~(size_t)255;
+    NODAL_HIP_TRY(h, h->dbg_apply.reserve(2 * vec + 256 + scan_tmp_bytes(n)));
+    char *w = h->dbg_apply.as<char>();
+    uint32_t *din = reinterpret_cast<uint32_t *>(w), *dout = in_place ? din : reinterpret_cast<uint32_t *>(w + vec);
+    uint32_t *dtotal = reinterpret_cast<uint32_t *>(w + 2 * vec);
+    if (n) NODAL_HIP_TRY(h, hipMemcpyAsync(din, in, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemsetAsync(dtotal, 0xFF, 4, st));
+    NODAL_TRY(scan_exclusive_u32(h, din, dout, n, total_out ? dtotal : nullptr, w + 2 * vec + 256));
+    if (n) NODAL_HIP_TRY(h, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (total_out) NODAL_HIP_TRY(h, hipMemcpyAsync(total_out, dtotal, 4, hipMemcpyDeviceToHost, st));
+    NODAL_WAIT_STREAM(h, st);
+    return NODAL_OK;
+}
