@@ -962,6 +962,37 @@ int nodal_debug_presolve_array(nodal_handle h, int32_t which, void *dst, int64_t
 int nodal_debug_presolve_recover(nodal_handle h, int64_t ny, const double *y, double *x_out);
 int nodal_debug_scan_u32(nodal_handle h, int64_t n, const uint32_t *in, uint32_t *out, int32_t in_place,
                          uint32_t *total_out);
+/* The rounds of the exact low-degree elimination (csrc/lowdeg.hip) as the last solve left them, round by round: what
+ * tests/lowdeg_reference.py restates in exact rational arithmetic on each round's own parent matrix and
+ * tests/test_gpu_lowdeg.py compares.  The hooks have no arithmetic of their own and change nothing a later solve reads:
+ * a solve after them returns the bits of the same solve without them.
+ * nodal_debug_lowdeg_info: walks h -> its reduced context -> ... while a context's cached decision (ld_state 2: child
+ *   built, 3: child built and a floating leftover found) stands for its present matrix.  *rounds (at most
+ *   NODAL_LD_MAX_ROUNDS); ints [48][8] per round: 0 the parent's n, 1 its nnz, 2 the child's n, 3 its nnz, 4 the
+ *   parent's ld_state, 5 the child's ld_rounds, 6 its ld_slow_rounds, 7 its ncontrib.  A round of state 3 is the last.
+ * nodal_debug_lowdeg_array: a stream wait and a device-to-host copy of one array of round `round` (enum below): the
+ *   parent's newidx (i32, n), right-hand side (f64, n: the vector that round read -- the last pair's during a pair
+ *   sweep), grounded flags (u8, n) and solution (f64, n; 0 bytes when none was recovered); the child's indptr (i32,
+ *   n' + 1), indices (i32), diag_pos (i32, n'), data (f64), right-hand side (f64, n'), grounded flags (u8, n'),
+ *   solution (f64, n'; 0 bytes when it was never solved), cptr (i32, nnz' + 1) and contrib (u32, ncontrib).  The LAST
+ *   child's data, right-hand side and flags belong to its own solver by now: for these the hook runs that round's
+ *   production kernels (schur_values, reduce_rhs) again on the kept lists into scratch of its own and copies that.
+ *   dst == NULL: the size only, nothing launched.  NODAL_E_INVALID: no such round or array, a destination too small.
+ * nodal_debug_floating_small: the one-workgroup connected-components verdict (small_floating_check, through
+ *   csr_floating_check_small) on the caller's graph: host CSR (indptr i32 n + 1, indices i32, self-loops allowed),
+ *   grounded (u8, n); *floating = 1 if some component holds no grounded node.  Every index is checked on the host
+ *   first.  NODAL_E_INVALID for a malformed graph and above 4096 nodes (nothing is uploaded or launched then). */
+enum {
+    NODAL_LD_MAX_ROUNDS = 48,
+    NODAL_LD_P_NEWIDX = 0, NODAL_LD_P_RHS = 1, NODAL_LD_P_GROUNDED = 2, NODAL_LD_P_X = 3, NODAL_LD_C_INDPTR = 4,
+    NODAL_LD_C_INDICES = 5, NODAL_LD_C_DIAG_POS = 6, NODAL_LD_C_DATA = 7, NODAL_LD_C_RHS = 8, NODAL_LD_C_GROUNDED = 9,
+    NODAL_LD_C_X = 10, NODAL_LD_C_CPTR = 11, NODAL_LD_C_CONTRIB = 12
+};
+int nodal_debug_lowdeg_info(nodal_handle h, int32_t *rounds, int64_t *ints /* [48][8] */);
+int nodal_debug_lowdeg_array(nodal_handle h, int32_t round, int32_t which, void *dst, int64_t capacity_bytes,
+                             int64_t *bytes_out);
+int nodal_debug_floating_small(nodal_handle h, int64_t n, const int32_t *indptr, const int32_t *indices,
+                               const uint8_t *grounded, int32_t *floating);
 
 #ifdef __cplusplus
 }

@@ -112,7 +112,19 @@ SIGNATURES = {
     "nodal_debug_presolve_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
     "nodal_debug_presolve_recover": (C.c_int, [C.c_void_p, C.c_int64, _f64p, _f64p]),
     "nodal_debug_scan_u32": (C.c_int, [C.c_void_p, C.c_int64, _u32p, _u32p, C.c_int32, _u32p]),
+    "nodal_debug_lowdeg_info": (C.c_int, [C.c_void_p, _i32p, _i64p]),
+    "nodal_debug_lowdeg_array": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _i64p]),
+    "nodal_debug_floating_small": (C.c_int, [C.c_void_p, C.c_int64, _i32p, _i32p, _u8p, _i32p]),
 }
+
+# nodal_debug_lowdeg_info: the eight words of a round; nodal_debug_lowdeg_array: `which` in the header's order
+# (NODAL_LD_*) with the item type of each array -- p_*: the round's parent, the rest its child (the reduced network)
+LOWDEG_MAX_ROUNDS = 48
+LOWDEG_INFO = ("n", "nnz", "child_n", "child_nnz", "ld_state", "ld_rounds", "ld_slow_rounds", "ncontrib")
+LOWDEG_ARRAYS = (("p_newidx", np.int32), ("p_rhs", np.float64), ("p_grounded", np.uint8), ("p_x", np.float64),
+                 ("indptr", np.int32), ("indices", np.int32), ("diag_pos", np.int32), ("data", np.float64),
+                 ("rhs", np.float64), ("grounded", np.uint8), ("x", np.float64), ("cptr", np.int32),
+                 ("contrib", np.uint32))
 
 # nodal_debug_presolve_build: the words of info; nodal_debug_presolve_array: `which` in the header's order (NODAL_PS_*)
 # with the item type of each array -- the plan (pivots, expressions, kept branches, row_of, level_of), the device's
@@ -1016,6 +1028,40 @@ class Handle:
         self._check(self.lib.nodal_debug_scan_u32(self._h, len(values), _ptr(values, C.c_uint32), _ptr(out, C.c_uint32),
                                                   int(bool(in_place)), C.byref(tot) if total else None))
         return out, (int(tot.value) if total else None)
+
+    def debug_lowdeg(self):
+        """The rounds of the low-degree elimination as the last solve left them (testing hook; nodal_hip.h): a list
+        with one dict per round -- the words of LOWDEG_INFO and the arrays of LOWDEG_ARRAYS (p_x / x empty when that
+        context holds no solution).  An empty list: the last solve did not take the route."""
+        nr, ints = C.c_int32(0), np.zeros((LOWDEG_MAX_ROUNDS, 8), dtype=np.int64)
+        self._check(self.lib.nodal_debug_lowdeg_info(self._h, C.byref(nr), _ptr(ints, C.c_int64)))
+        rounds = []
+        for r in range(nr.value):
+            rd = {name: int(ints[r, k]) for k, name in enumerate(LOWDEG_INFO)}
+            for which, (name, dtype) in enumerate(LOWDEG_ARRAYS):
+                size = C.c_int64(0)
+                self._check(self.lib.nodal_debug_lowdeg_array(self._h, r, which, None, 0, C.byref(size)))
+                arr = np.empty(size.value // np.dtype(dtype).itemsize, dtype=dtype)
+                if size.value:
+                    self._check(self.lib.nodal_debug_lowdeg_array(self._h, r, which, C.c_void_p(arr.ctypes.data),
+                                                                  arr.nbytes, C.byref(size)))
+                    assert size.value == arr.nbytes
+                rd[name] = arr
+            rounds.append(rd)
+        return rounds
+
+    def debug_floating_small(self, indptr, indices, grounded):
+        """small_floating_check on a host CSR graph (testing hook): 1 if a component holds no grounded node, else 0.
+        NodalHipError(E_INVALID) above 4096 nodes or for a malformed graph."""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        grounded = np.ascontiguousarray(grounded, dtype=np.uint8)
+        n = len(indptr) - 1
+        assert n >= 0 and len(grounded) == n and len(indices) == indptr[-1]
+        floating = C.c_int32(-1)
+        self._check(self.lib.nodal_debug_floating_small(self._h, n, _ptr(indptr, C.c_int32), _ptr(indices, C.c_int32),
+                                                        _ptr(grounded, C.c_uint8), C.byref(floating)))
+        return int(floating.value)
 
     def debug_general_arrays(self):
         """What the last precond-0 setup of debug_fgmres_cycle left, raw (testing hook): a dict of GENERAL_ARRAYS --

@@ -275,7 +275,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
                       &h->ac_t_gsrc, &h->ac_t_ptr, &h->ac_t_con, &h->nz_spec, &h->nz_vec, &h->nz_part, &h->nz_out,
                       &h->ap_spec, &h->ap_vec, &h->ap_rows, &h->ap_out, &h->ag_spec, &h->ag_vec, &h->ag_out,
-                      &h->dbg_resid, &h->dbg_apply};
+                      &h->dbg_resid, &h->dbg_apply, &h->dbg_lowdeg};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);
     h->evpool.clear();
@@ -1241,6 +1241,29 @@ int nodal_debug_scan_u32(nodal_handle h, int64_t n, const uint32_t *in, uint32_t
     DeviceGuard g(h);
     if (h->hung) return NODAL_E_HIP;
     return scan_debug_u32(h, n, in, out, in_place != 0, total_out);
+}
+
+int nodal_debug_lowdeg_info(nodal_handle h, int32_t *rounds, int64_t *ints) {
+    if (!h || !rounds || !ints) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return lowdeg_debug_info(h, rounds, ints);
+}
+
+int nodal_debug_lowdeg_array(nodal_handle h, int32_t round, int32_t which, void *dst, int64_t capacity_bytes,
+                             int64_t *bytes_out) {
+    if (!h || !bytes_out) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return lowdeg_debug_array(h, round, which, dst, capacity_bytes, bytes_out);
+}
+
+int nodal_debug_floating_small(nodal_handle h, int64_t n, const int32_t *indptr, const int32_t *indices,
+                               const uint8_t *grounded, int32_t *floating) {
+    if (!h || n < 0 || !indptr || !floating || (n > 0 && !grounded)) return NODAL_E_INVALID;
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;
+    return lowdeg_debug_floating_small(h, n, indptr, indices, grounded, floating);
 }
 
 int nodal_residual(nodal_handle h, double *scaled_residual) {

@@ -278,6 +278,8 @@ struct nodal_ctx {
     int ld_state = 0;              // 1 too few candidates, 2 child built, 3 child built and singular (leftover)
     int ld_share = 0;              // the bar (n / share nodes) the decision was taken with
     int64_t ld_n = 0, ld_nnz = 0;
+    const void *ld_rhs = nullptr;  // the right-hand side the last round read (a pair sweep swaps ps_buf in): for the testing hook
+    DevBuf dbg_lowdeg;             // testing hooks nodal_debug_lowdeg_array / nodal_debug_floating_small: nothing else lives here
 
     // ---- symbolic assembly results ----
     bool have_symbolic = false;
@@ -820,6 +822,12 @@ int csr_small_floating_check(nodal_ctx *h, int32_t *floating);
 int csr_floating_check_small(nodal_ctx *h, int64_t n, const int32_t *indptr, const int32_t *indices,
                              const uint8_t *grounded, uint32_t *flag_dev);
 int lowdeg_solve(nodal_ctx *h, int min_share, bool *done, int32_t *info, int32_t *iters, double *resid);
+// testing hooks (nodal_debug_lowdeg_info / _array, nodal_debug_floating_small): the rounds the last solve left, one array
+// of one round, and small_floating_check on a host graph -- no arithmetic of their own
+int lowdeg_debug_info(nodal_ctx *h, int32_t *rounds, int64_t *ints);
+int lowdeg_debug_array(nodal_ctx *h, int32_t round, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out);
+int lowdeg_debug_floating_small(nodal_ctx *h, int64_t n, const int32_t *indptr, const int32_t *indices,
+                                const uint8_t *grounded, int32_t *floating);
 
 // ---- sparse solvers (sparse_*.hip) ----
 // the multigrid FCG of the passive route with the caller's right-hand side (writes h->x): NODAL_OK, -1 the iteration

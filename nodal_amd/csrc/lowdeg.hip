@@ -19,8 +19,12 @@
 //
 // Everything is deterministic: F is chosen by a fixed priority (odd index first, then a hash:
 // a candidate is taken if it beats every candidate neighbour), the kept nodes keep their
-// relative order, and S is grouped by group.h like every other matrix here (contributions
-// summed in a fixed order, S bitwise symmetric).
+// relative order, and S is grouped by group.h like every other matrix here.  Its contributions are
+// summed in a fixed order that is the same in S(i,k) and S(k,i) -- the entry of A first, then the
+// eliminated neighbours by ascending index (schur_values) -- so S is bitwise symmetric; the order of the
+// lists alone (ascending column of the source entry) was not: tests/test_gpu_lowdeg.py found last-bit
+// differences on a direct resistor with two bypasses, and block_elim.hip's symmetric elimination relies on
+// the symmetry for every child context.
 //
 // The reference hands G to SuperLU (scipy spsolve, reference nodal/nodal.py:325; dense:
 // np.linalg.solve, nodal/nodal.py:327), whose column ordering (COLAMD) eliminates exactly
@@ -120,28 +124,35 @@ struct SchurEntries {
     }
 };
 
+// One entry of S per thread.  The order of the sum is the same in S(i,k) and S(k,i), so that S is BITWISE symmetric:
+// the pass-through entry A(i,k) first (slot 0, at most one), then the eliminated common neighbours f in the order row
+// i stores them -- ascending f, as in row k -- and v w commutes (A is bitwise symmetric).  `contrib` order alone does
+// not do: it puts A(i,k) where column k falls among the f, which differs between the two rows (i < f1 < f2 < k gave
+// ((0 - t1) - t2) + p in row i against ((0 + p) - t1) - t2 in row k: one ulp apart in 7 of 50 such entries on the device).
 __global__ __launch_bounds__(TB) void schur_values(View A, const int32_t *__restrict__ cptr,
                                                    const uint32_t *__restrict__ contrib,
                                                    double *__restrict__ out, int64_t nent) {
     for (int64_t o = (int64_t)blockIdx.x * TB + threadIdx.x; o < nent; o += (int64_t)gridDim.x * TB) {
+        const int32_t p0 = cptr[o], p1 = cptr[o + 1];
         double s = 0.0;
-        for (int32_t p = cptr[o]; p < cptr[o + 1]; ++p) {
+        for (int32_t p = p0; p < p1; ++p) {
             const uint32_t c = contrib[p];
-            const int64_t e = c >> 3;
+            if ((c & 7u) == 0) s += A.data[c >> 3];
+        }
+        for (int32_t p = p0; p < p1; ++p) {
+            const uint32_t c = contrib[p];
             const int slot = (int)(c & 7u);
+            if (slot == 0) continue;
+            const int64_t e = c >> 3;
             const double v = A.data[e];
-            if (slot == 0) {
-                s += v;
-            } else {
-                const int f = A.indices[e];
-                int t = slot - 1;
-                double w = 0.0;
-                for (int32_t q = A.indptr[f]; q < A.indptr[f + 1]; ++q) {
-                    if (A.indices[q] == f) continue;
-                    if (t-- == 0) w = A.data[q];
-                }
-                s -= v * w / A.data[A.diag_pos[f]];
+            const int f = A.indices[e];
+            int t = slot - 1;
+            double w = 0.0;
+            for (int32_t q = A.indptr[f]; q < A.indptr[f + 1]; ++q) {
+                if (A.indices[q] == f) continue;
+                if (t-- == 0) w = A.data[q];
             }
+            s -= v * w / A.data[A.diag_pos[f]];
         }
         out[o] = s;
     }
@@ -461,6 +472,7 @@ int lowdeg_solve(nodal_ctx *h, int min_share, bool *done, int32_t *info, int32_t
     }
     uint8_t *flags = h->grounded.as<uint8_t>();
     if (!h->csr_only) NODAL_TRY(stamp_grounded_flags(h, flags));  // a child already holds its own
+    h->ld_rhs = h->rhs.p;  // (a pair sweep has swapped its own vector in: the testing hook reads the one this round read)
     reduce_rhs<<<grid_for(n), TB, 0, st>>>(A, newidx, h->rhs.as<double>(), flags, c->rhs.as<double>(),
                                           c->grounded.as<uint8_t>());
     NODAL_HIP_TRY(h, hipGetLastError());
@@ -504,5 +516,142 @@ int lowdeg_solve(nodal_ctx *h, int min_share, bool *done, int32_t *info, int32_t
     recover_x<<<grid_for(n), TB, 0, st>>>(A, newidx, h->rhs.as<double>(), c->x.as<double>(),
                                          h->x.as<double>());
     NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+// ---- testing hooks (nodal_debug_lowdeg_info / _array, nodal_debug_floating_small) ----
+// The rounds as the last solve left them: h -> h->lowdeg -> ... while a context's cached decision (state 2 or 3) stands
+// for its present matrix.  Nothing here has arithmetic of its own: a buffer that the child's own solver may have used
+// since (the LAST child's values, right-hand side and flags) is produced again by this file's kernels from the parent's
+// surviving arrays and the kept lists, into dbg_lowdeg; nothing a solve reads is written.
+namespace {
+struct Round {
+    nodal_ctx *p, *c;
+};
+constexpr int LD_MAX_ROUNDS = 48;  // (lowdeg_solve builds no round beyond)
+
+int rounds_of(nodal_ctx *h, Round *out) {
+    int r = 0;
+    for (nodal_ctx *p = h; p && r < LD_MAX_ROUNDS; p = p->lowdeg) {
+        const bool stands = (p->ld_state == 2 || p->ld_state == 3) && p->lowdeg && p->have_numeric &&
+                            p->ld_epoch == p->struct_epoch && p->ld_n == p->n && p->ld_nnz == p->nnz;
+        if (!stands) break;
+        out[r].p = p;
+        out[r].c = p->lowdeg;
+        ++r;
+        if (p->ld_state == 3) break;  // the child was never solved
+    }
+    return r;
+}
+}  // namespace
+
+int lowdeg_debug_info(nodal_ctx *h, int32_t *rounds, int64_t *ints) {
+    Round rs[LD_MAX_ROUNDS];
+    const int nr = rounds_of(h, rs);
+    *rounds = nr;
+    for (int k = 0; k < LD_MAX_ROUNDS * 8; ++k) ints[k] = 0;
+    for (int r = 0; r < nr; ++r) {
+        const nodal_ctx *p = rs[r].p, *c = rs[r].c;
+        int64_t *w = ints + 8 * r;
+        w[0] = p->n;
+        w[1] = p->nnz;
+        w[2] = c->n;
+        w[3] = c->nnz;
+        w[4] = p->ld_state;
+        w[5] = c->ld_rounds;
+        w[6] = c->ld_slow_rounds;
+        w[7] = c->ncontrib;
+    }
+    return NODAL_OK;
+}
+
+int lowdeg_debug_array(nodal_ctx *h, int32_t round, int32_t which, void *dst, int64_t capacity_bytes, int64_t *bytes_out) {
+    Round rs[LD_MAX_ROUNDS];
+    const int nr = rounds_of(h, rs);
+    *bytes_out = 0;
+    if (round < 0 || round >= nr) return nodal_fail(h, NODAL_E_INVALID, "debug lowdeg array: the last solve left no such round");
+    if (which < 0 || which > NODAL_LD_C_CONTRIB) return nodal_fail(h, NODAL_E_INVALID, "debug lowdeg array: no such array");
+    nodal_ctx *p = rs[round].p, *c = rs[round].c;
+    const int64_t n = p->n, nk = c->n, nent = c->nnz;
+    // the last child: its own solver (dense, multigrid, direct) owns its buffers now
+    const bool last = round == nr - 1;
+    const void *prhs = p->ld_rhs && (p->ld_rhs == p->rhs.p || p->ld_rhs == p->ps_buf.p) ? p->ld_rhs : nullptr;
+    const bool p_has_x = p->have_x || (p->ld_state == 2 && c->have_x);
+    const void *src = nullptr;
+    int64_t bytes = 0;
+    bool again = false;
+    switch (which) {
+    case NODAL_LD_P_NEWIDX: src = p->ld_newidx.p; bytes = n * 4; break;
+    case NODAL_LD_P_RHS: src = prhs; bytes = n * 8; break;
+    case NODAL_LD_P_GROUNDED: src = p->grounded.p; bytes = n; break;
+    case NODAL_LD_P_X: src = p->x.p; bytes = p_has_x ? n * 8 : 0; break;
+    case NODAL_LD_C_INDPTR: src = c->indptr.p; bytes = (nk + 1) * 4; break;
+    case NODAL_LD_C_INDICES: src = c->indices.p; bytes = nent * 4; break;
+    case NODAL_LD_C_DIAG_POS: src = c->diag_pos.p; bytes = nk * 4; break;
+    case NODAL_LD_C_DATA: src = c->data.p; bytes = nent * 8; again = last; break;
+    case NODAL_LD_C_RHS: src = c->rhs.p; bytes = nk * 8; again = last; break;
+    case NODAL_LD_C_GROUNDED: src = c->grounded.p; bytes = nk; again = last; break;
+    case NODAL_LD_C_X: src = c->x.p; bytes = c->have_x ? nk * 8 : 0; break;
+    case NODAL_LD_C_CPTR: src = c->cptr.p; bytes = (nent + 1) * 4; break;
+    default: src = c->contrib.p; bytes = c->ncontrib * 4; break;  // NODAL_LD_C_CONTRIB
+    }
+    *bytes_out = bytes;
+    if (!dst || bytes == 0) return NODAL_OK;
+    if (capacity_bytes < bytes) return nodal_fail(h, NODAL_E_INVALID, "debug lowdeg array: the destination is too small");
+    hipStream_t st = h->stream;
+    if (again) {
+        const View A = view_of(p);
+        const size_t a_data = grp::align_up((size_t)nent * 8 + 8), a_rhs = grp::align_up((size_t)nk * 8 + 8);
+        NODAL_HIP_TRY(h, h->dbg_lowdeg.reserve(a_data + a_rhs + (size_t)nk + 256));
+        char *w = h->dbg_lowdeg.as<char>();
+        double *data = reinterpret_cast<double *>(w), *bc = reinterpret_cast<double *>(w + a_data);
+        uint8_t *gc = reinterpret_cast<uint8_t *>(w + a_data + a_rhs);
+        if (which == NODAL_LD_C_DATA) {
+            schur_values<<<grid_for(nent), TB, 0, st>>>(A, c->cptr.as<int32_t>(), c->contrib.as<uint32_t>(), data, nent);
+            src = data;
+        } else {
+            if (!prhs) return nodal_fail(h, NODAL_E_INVALID, "debug lowdeg array: the round's right-hand side is gone");
+            reduce_rhs<<<grid_for(n), TB, 0, st>>>(A, p->ld_newidx.as<int32_t>(), static_cast<const double *>(prhs),
+                                                  p->grounded.as<uint8_t>(), bc, gc);
+            src = which == NODAL_LD_C_RHS ? (const void *)bc : (const void *)gc;
+        }
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    if (!src) return nodal_fail(h, NODAL_E_INVALID, "debug lowdeg array: the buffer is gone");
+    NODAL_WAIT_STREAM(h, st);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, st));
+    NODAL_WAIT_STREAM(h, st);
+    return NODAL_OK;
+}
+
+// small_floating_check through csr_floating_check_small on the caller's graph (host CSR; every index is checked here
+// before anything is uploaded: the kernel indexes LDS with them).  Above CC_MAX nodes the answer is that function's own
+// refusal, with nothing uploaded and nothing launched.
+int lowdeg_debug_floating_small(nodal_ctx *h, int64_t n, const int32_t *indptr, const int32_t *indices,
+                                const uint8_t *grounded, int32_t *floating) {
+    *floating = 0;
+    if (n > CC_MAX) return csr_floating_check_small(h, n, nullptr, nullptr, nullptr, nullptr);
+    if (n == 0) return NODAL_OK;
+    const int64_t nnz = indptr[n];
+    bool ok = indptr[0] == 0 && nnz >= 0 && nnz <= (1 << 26) && (nnz == 0 || indices);
+    for (int64_t i = 0; ok && i < n; ++i) ok = indptr[i] <= indptr[i + 1] && indptr[i + 1] <= nnz;
+    for (int64_t e = 0; ok && e < nnz; ++e) ok = indices[e] >= 0 && indices[e] < n;
+    if (!ok) return nodal_fail(h, NODAL_E_INVALID, "debug floating small: not a CSR graph on n nodes");
+    hipStream_t st = h->stream;
+    const size_t a_ptr = grp::align_up((size_t)(n + 1) * 4), a_idx = grp::align_up((size_t)nnz * 4 + 4),
+                 a_gnd = grp::align_up((size_t)n);
+    NODAL_HIP_TRY(h, h->dbg_lowdeg.reserve(a_ptr + a_idx + a_gnd + 256));
+    char *w = h->dbg_lowdeg.as<char>();
+    int32_t *dptr = reinterpret_cast<int32_t *>(w), *didx = reinterpret_cast<int32_t *>(w + a_ptr);
+    uint8_t *dgnd = reinterpret_cast<uint8_t *>(w + a_ptr + a_idx);
+    uint32_t *flag = reinterpret_cast<uint32_t *>(w + a_ptr + a_idx + a_gnd);
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dptr, indptr, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    if (nnz) NODAL_HIP_TRY(h, hipMemcpyAsync(didx, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(dgnd, grounded, (size_t)n, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemsetAsync(flag, 0, 4, st));
+    NODAL_TRY(csr_floating_check_small(h, n, dptr, didx, dgnd, flag));
+    uint32_t f = 0;
+    NODAL_TRY(nodal_read_words(h, &f, flag, 4));
+    *floating = (int32_t)f;
     return NODAL_OK;
 }
