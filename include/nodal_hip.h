@@ -353,6 +353,66 @@ int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t
                     double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out, double *record_out,
                     int32_t *info_out, int32_t *iters_out, int32_t *route_out, int32_t *iterations, int32_t *converged);
 
+/* ---- nonlinear transient analysis: diodes in a network stepped in time, Newton's method inside every step (replaces a
+ *      host loop around nodal_newton_dc that downloads x, rebuilds the history currents, uploads a value column,
+ *      assembles and solves once per Newton iteration per step) ----
+ * nodal_transient_rlc's arguments and rules, plus nodal_newton_dc's diodes: the handle's table holds one companion R row
+ * per capacitor, then per inductor, then per diode, diode_rows [ndiode] (type R, checked on the device; their table
+ * values are overwritten).  Diode d carries i(v) = i_sat[d] (exp(v / n_vt[d]) - 1) + gmin v from lead a (anode) to lead b
+ * (cathode) of its row.  Step k = 1 .. steps, given x_{k-1}, the capacitors' history words, the inductors' currents and
+ * the method:
+ *   1. base_k = A_k + the capacitors' and inductors' history currents, exactly what nodal_transient_rlc builds, formed
+ *      ONCE per step and held fixed over the step's Newton iterations
+ *   2. vh^0 = x_{k-1}(a) - x_{k-1}(b) per diode (ground: +0.0)
+ *   3. Newton iteration j = 0, 1, ..: linearise at vh^j with nodal_newton_dc's formulas and roundings
+ *        e = exp(vh / n_vt),  g = i_sat e / n_vt + gmin,  i = i_sat (e - 1) + gmin vh,  J = g vh - i
+ *      write 1 / g into the diode's row of the value column, assemble G (symbolic phase kept), solve
+ *        G x = base_k + S J       (J injected into lead a, drawn from lead b; a node's J in ascending order of its diodes)
+ *      by the route nodal_newton_dc would choose (n <= 64 the dense panel; B == 0, all R > 0 and n > 4096 multigrid;
+ *      otherwise the sparse LU), then per diode nodal_newton_dc's junction limiting vh^{j+1} = pnjlim(v, vh^j) and its
+ *      convergence test, unchanged.  The step has converged when no diode fails; x_k is that iterate
+ *   4. after convergence what a linear step runs after its solve: the inductor lane (i_k and J_{k+1} from x_k, once per
+ *      step), probes, envelope, the kept solutions
+ * A diode has no memory: method 0 / 1 change the capacitors' and inductors' companions only, and method 1 needs a DC
+ * start as before.
+ *   info_out [steps]              0 solved; 1 singular (nodal_transient's rule, dense != 0: NODAL_E_SINGULAR); 2 the
+ *                                 step's Newton loop did not converge in max_iter iterations, met an iterate that is not
+ *                                 finite, or a g that overflowed (then the diode rows of the value column hold 1.0 and G
+ *                                 is assembled from it).  Info 1 or 2: that step and every later one have no state, NaN
+ *                                 wherever they were to land, status OK.  The loop never hangs
+ *   resid_out [steps]             the LARGEST scaled residual of the step's linear solves, one per Newton iteration
+ *   iters_out [steps]             of the step's last linear solve
+ *   newton_out [steps]            Newton iterations of the step (0: a step without a state that ran none)
+ *   updates_out [steps]           iterations of the step whose matrix work ran (below)
+ *   dv_out, di_out [steps + 1][ndprobe]  v and i(v) of the diodes dprobe_index [ndprobe] (indices into diode_rows) at x_k,
+ *                                 row 0 from x0
+ *   vh_final_out [ndiode]         the limited junction voltages after the last step's last iteration (steps == 0: v of
+ *                                 x0); NaN when a step had no state
+ * Each may be NULL.  Reuse: an iteration skips the assembly and all matrix work behind it when every diode's 1 / g has
+ * exactly the bits of the value G was last assembled from (reverse-biased junctions: i_sat e / n_vt below half an ulp of
+ * gmin); the factors or the hierarchy then stay, as in a linear step.  The lane that limits and tests a diode also
+ * evaluates the next linearisation's 1 / g and counts the diodes whose bits moved into the record the loop reads anyway:
+ * no host wait of its own.  The first iteration of a call always assembles, and so does the one after a converged
+ * iteration in which the limiter changed a diode (vh^0 of the next step is then not that lane's vh').  NODAL_TNL_REUSE=0
+ * (read per call) assembles in every iteration: the same bits.
+ * ndiode == 0: nodal_transient_rlc's launches and bits, newton_out 1 per solved step, updates_out 0.  n == 0, steps == 0:
+ * as nodal_transient_rlc.  No tape is kept (NODAL_OPT_TRANSIENT_TAPE: the adjoint with diodes is not implemented).
+ * nodal_last_timings afterwards as nodal_newton_dc's: [0] host ms of the matrix work summed over all iterations, [1]
+ * the symbolic part of it, exactly 0.0 when all of it was kept, [2] the whole call.
+ * NODAL_E_INVALID: nodal_transient_rlc's and nodal_newton_dc's cases, and a dprobe_index entry outside [0, ndiode).
+ * Host waits per Newton iteration: nodal_newton_dc's -- the assembly's status words (where it ran), what the solver looks
+ * at, ONE read of the record.  Integer atomics only: a repeated call gives the same bits.  Afterwards the handle is as
+ * nodal_newton_dc leaves it. */
+int nodal_transient_nl(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                       int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                       const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                       double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                       int32_t *info_out, int32_t *iters_out, int64_t nind, const int64_t *ind_rows, const double *i0,
+                       int32_t ncur, const int32_t *cur_index, double *cur_out, double *i_final_out, int64_t ndiode,
+                       const int64_t *diode_rows, const double *i_sat, const double *n_vt, double gmin, int32_t max_iter,
+                       double reltol, double vntol, double abstol, int32_t ndprobe, const int32_t *dprobe_index,
+                       int32_t *newton_out, int32_t *updates_out, double *dv_out, double *di_out, double *vh_final_out);
+
 /* ---- gradients through time (replaces finite differences over whole transient runs: two nodal_transient calls per
  *      component; with the reference each of them a host loop of rebuild and solve, reference nodal/nodal.py:306-336) ----
  * The adjoint of the backward-Euler run the handle has RECORDED: with NODAL_OPT_TRANSIENT_TAPE set, a nodal_transient call

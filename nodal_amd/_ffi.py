@@ -66,6 +66,11 @@ SIGNATURES = {
     "nodal_newton_dc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, _i64p, _f64p,
                                   _f64p, C.c_int32, C.c_double, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p,
                                   _f64p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "nodal_transient_nl": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
+                                     _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p, _i32p,
+                                     _f64p, _i32p, _i32p, C.c_int64, _i64p, _f64p, C.c_int32, _i32p, _f64p, _f64p,
+                                     C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, C.c_double, C.c_double,
+                                     C.c_double, C.c_int32, _i32p, _i32p, _i32p, _f64p, _f64p, _f64p]),
     "nodal_transient_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
                                            _f64p, _i32p]),
     "nodal_ac_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
@@ -538,7 +543,17 @@ class Handle:
         return self._transient(cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope,
                                inductors=(ind_rows, i0, cur_index))
 
-    def _transient(self, cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope, inductors=None):
+    def transient_nl(self, cap_rows, ind_rows, diode_rows, i_sat, n_vt, gmin, rows, values, x0, i0, ia, ib, cur_index,
+                     diode_index, dense, max_iter, reltol, vntol, abstol, method=0, keep_every=0, envelope=False):
+        """transient_rlc() with diodes (nodal_transient_nl): diode_rows their companion rows, i_sat, n_vt [D], diode_index
+        [Q] the diodes whose v and i(v) are wanted step by step.  Returns transient_rlc()'s eight and a dict: newton
+        [steps], updates [steps], v, i [steps + 1, Q], vh [D]."""
+        return self._transient(cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope,
+                               inductors=(ind_rows, i0, cur_index),
+                               diodes=(diode_rows, i_sat, n_vt, gmin, max_iter, reltol, vntol, abstol, diode_index))
+
+    def _transient(self, cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope, inductors=None,
+                   diodes=None):
         cap_rows = np.ascontiguousarray(cap_rows, dtype=np.int64)
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         values = np.ascontiguousarray(values, dtype=np.float64)
@@ -574,11 +589,28 @@ class Handle:
         assert ind_rows.ndim == 1 and i0.shape == ind_rows.shape and cur_index.ndim == 1
         cur = np.zeros((steps + 1, len(cur_index)), dtype=np.float64)
         final = np.zeros(len(ind_rows), dtype=np.float64)
-        self._check(self.lib.nodal_transient_rlc(
-            *args, len(ind_rows), _ptr(ind_rows, C.c_int64) if len(ind_rows) else None,
-            _ptr(i0, C.c_double) if len(i0) else None, len(cur_index), _ptr(cur_index, C.c_int32) if len(cur_index) else None,
-            _ptr(cur, C.c_double) if cur.size else None, _ptr(final, C.c_double) if len(final) else None))
-        return wave, x, env, resid, info, iters, cur, final
+        args += [len(ind_rows), _ptr(ind_rows, C.c_int64) if len(ind_rows) else None,
+                 _ptr(i0, C.c_double) if len(i0) else None, len(cur_index), _ptr(cur_index, C.c_int32) if len(cur_index) else None,
+                 _ptr(cur, C.c_double) if cur.size else None, _ptr(final, C.c_double) if len(final) else None]
+        if diodes is None:
+            self._check(self.lib.nodal_transient_rlc(*args))
+            return wave, x, env, resid, info, iters, cur, final
+        diode_rows = np.ascontiguousarray(diodes[0], dtype=np.int64)
+        i_sat, n_vt = (np.ascontiguousarray(v, dtype=np.float64) for v in diodes[1:3])
+        gmin, max_iter, reltol, vntol, abstol = diodes[3:8]
+        index = np.ascontiguousarray(diodes[8], dtype=np.int32)
+        D = len(diode_rows)
+        assert diode_rows.ndim == 1 and i_sat.shape == (D,) and n_vt.shape == (D,) and index.ndim == 1
+        out = {"newton": np.zeros(steps, dtype=np.int32), "updates": np.zeros(steps, dtype=np.int32),
+               "v": np.zeros((steps + 1, len(index)), dtype=np.float64), "i": np.zeros((steps + 1, len(index)), dtype=np.float64),
+               "vh": np.zeros(D, dtype=np.float64)}
+        self._check(self.lib.nodal_transient_nl(
+            *args, D, _ptr(diode_rows, C.c_int64) if D else None, _ptr(i_sat, C.c_double) if D else None,
+            _ptr(n_vt, C.c_double) if D else None, float(gmin), int(max_iter), float(reltol), float(vntol), float(abstol),
+            len(index), _ptr(index, C.c_int32) if len(index) else None, _ptr(out["newton"], C.c_int32),
+            _ptr(out["updates"], C.c_int32), _ptr(out["v"], C.c_double) if out["v"].size else None,
+            _ptr(out["i"], C.c_double) if out["i"].size else None, _ptr(out["vh"], C.c_double) if D else None))
+        return wave, x, env, resid, info, iters, cur, final, out
 
     def newton_dc(self, diode_rows, i_sat, n_vt, gmin, rows, values, x0, dense, max_iter, reltol, vntol, abstol,
                   keep_iterates=False):

@@ -96,6 +96,7 @@ class Circuit:
         self._G = self._A = None
         self._transient_child = None
         self._transient_dc = None
+        self._transient_nl_dc = None
         self._transient_record = None
         self._newton_child = None
         self.currents = self.build_model()
@@ -111,6 +112,7 @@ class Circuit:
         self._G = self._A = None
         self._transient_child = None
         self._transient_dc = None
+        self._transient_nl_dc = None
         self._transient_record = None
         self._newton_child = None
         self.table = other.table if table is None else table
@@ -375,6 +377,7 @@ class Circuit:
         self._G = self._A = None
         self._transient_child = None  # (its matrix carried the old values)
         self._transient_dc = None
+        self._transient_nl_dc = None
         self._transient_record = None
         self._newton_child = None
         self.table = table.with_values(new)
@@ -403,7 +406,8 @@ class Circuit:
         return PortEquivalent(self.netlist, ports, z, v_oc, info, resid)
 
     def transient(self, capacitors, dt, steps, sources=None, probes=(), method="euler", initial=None, keep_every=0,
-                  envelope=False, record=False, inductors=(), initial_currents=None, current_probes=()):
+                  envelope=False, record=False, inductors=(), initial_currents=None, current_probes=(), diodes=(),
+                  diode_probes=(), max_iter=50, reltol=1e-3, vntol=1e-6, abstol=1e-12, gmin=1e-12):
         """Step the circuit with capacitors through `steps` time steps of length `dt` on the device (nodal_transient).
 
         `capacitors` is a sequence of (name, farads, node_a, node_b) on nodes of the netlist; `sources` maps names of
@@ -435,11 +439,28 @@ class Circuit:
         currents are returned as `currents` [steps+1, Q]; `final_currents` [L] is the state after the last step, so
         that a run continues from `solutions[-1]` and `final_currents`.  ValueError for a loop of inductors alone
         (the DC start would be singular) and for record=True with inductors (their adjoint is not implemented); a DC
-        start that is singular together with other components behaves as a singular solve()."""
+        start that is singular together with other components behaves as a singular solve().
+
+        `diodes` is a sequence of (name, i_sat, n_vt, anode, cathode) as operating_point() takes it (nodal_transient_nl):
+        every step is then solved by Newton's method on the device, with operating_point()'s linearisation, junction
+        limiting and convergence test under `max_iter`, `reltol`, `vntol`, `abstol` and `gmin`; a diode has no memory, so
+        the method changes the capacitors' and inductors' companions only.  Without `diodes` nothing changes: the same
+        calls, the same bits.  With diodes initial=None starts from the NONLINEAR DC operating point -- capacitors open,
+        inductors shorts, diodes in -- found by nodal_newton_dc on a further device context kept on the circuit, keyed by
+        the inductors' and diodes' leads, until set_values(); solve() is neither needed nor touched.  A start that does
+        not converge warns once (RuntimeWarning) and gives every step NaN with info 2.  The child's table holds the
+        capacitors', inductors' and diodes' companion rows in that order and is keyed by the diodes' leads as well.
+        `diode_probes` names diodes whose v and i(v) are returned as `diode_voltages` and `diode_currents` [steps+1, Q];
+        `newton_iterations` and `matrix_updates` [steps] count a step's Newton iterations and those of them that
+        assembled and factored (an iteration in which no junction's conductance moved by a bit re-uses the matrix);
+        `final_junctions` [D] are the limited junction voltages after the last step.  A step whose Newton loop does not
+        converge has info 2: it and every later step are NaN, and the run warns once (RuntimeWarning).  ValueError for
+        record=True with diodes (the adjoint is not implemented), and operating_point()'s for the diodes and tolerances."""
         from .ports import _as_pair, resolve_ports
         from .sweep import resolve_sources
-        from .transient import (METHODS, Transient, TransientEnvelope, check_inductor_arguments, check_transient_arguments,
-                                companion_table, resolve_capacitors, resolve_inductors)
+        from .transient import (METHODS, Transient, TransientEnvelope, check_diode_probes, check_inductor_arguments,
+                                check_transient_arguments, companion_table, diode_companion_table, resolve_capacitors,
+                                resolve_inductors)
         h = self._handle
         self._transient_record = None  # (whatever an earlier call recorded: the device drops it as well)
         dt, steps, code, x0 = check_transient_arguments(dt, steps, method, initial, h.n)
@@ -453,6 +474,17 @@ class Circuit:
         i0, cur_index = check_inductor_arguments(lnames, initial, initial_currents, current_probes)
         if record and len(lnames):
             raise ValueError("record=True with inductors: the adjoint of a run with inductors is not implemented")
+        nonlinear = len(diodes) > 0
+        if nonlinear:
+            from . import operating_point as op
+            if record:
+                raise ValueError("record=True with diodes: the adjoint of a run with diodes is not implemented")
+            max_iter, reltol, vntol, abstol, gmin, _ = op.check_operating_point_arguments(max_iter, reltol, vntol, abstol,
+                                                                                          gmin, None, h.n)
+            dnames, i_sat, n_vt, da, db = op.resolve_diodes(self.netlist, diodes)
+            diode_index = check_diode_probes(dnames, diode_probes)
+        else:
+            check_diode_probes((), diode_probes)
         rows, values = resolve_sources(self.netlist, sources if sources is not None else {})
         if len(rows) and values.shape[0] != steps:
             raise ValueError(f"Source waveforms must have {steps} values (one per step), not {values.shape[0]}")
@@ -460,8 +492,11 @@ class Circuit:
             values = np.zeros((steps, 0), dtype=np.float64)
         probes = [_as_pair(self.netlist, port) for port in probes]
         pa, pb = resolve_ports(self.netlist, probes)
-        dc_singular = False
-        if x0 is None and len(lnames):
+        dc_singular = dc_lost = False
+        if x0 is None and nonlinear:
+            x0, i0, dc_singular, dc_lost = self._transient_nl_dc_start(la, lb, i_sat, n_vt, da, db, gmin, max_iter, reltol,
+                                                                       vntol, abstol)
+        elif x0 is None and len(lnames):
             x0, i0, dc_singular = self._transient_dc_start(la, lb)
         elif x0 is None:
             with self._reference_errors(missing=""):
@@ -469,21 +504,27 @@ class Circuit:
         key = (farads.tobytes(), ca.tobytes(), cb.tobytes(), dt, code)
         if len(lnames):
             key += (henries.tobytes(), la.tobytes(), lb.tobytes())
+        if nonlinear:
+            key += ("diodes", da.tobytes(), db.tobytes())
         if self._transient_child is None or self._transient_child[0] != key:
             self._transient_child = None  # (its device context goes back to the pool first)
-            if len(lnames):
+            diode_rows = None
+            if nonlinear:
+                table, cap_rows, ind_rows, diode_rows = diode_companion_table(self.table, farads, ca, cb, dt, code, henries,
+                                                                              la, lb, i_sat, n_vt, da, db, gmin)
+            elif len(lnames):
                 table, cap_rows, ind_rows = companion_table(self.table, farads, ca, cb, dt, code, henries, la, lb)
             else:
                 (table, cap_rows), ind_rows = companion_table(self.table, farads, ca, cb, dt, code), None
-            self._transient_child = (key, Circuit._clone_of(self, table), cap_rows, ind_rows)
-        _, child, cap_rows, ind_rows = self._transient_child
+            self._transient_child = (key, Circuit._clone_of(self, table), cap_rows, ind_rows, diode_rows)
+        _, child, cap_rows, ind_rows, diode_rows = self._transient_child
         ch = child._handle
-        cur = final = None
+        cur = final = junctions = None
         try:
             with self._reference_errors():
                 if record:
                     ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 1)
-                if dc_singular:  # (sparse: the start is NaN, and with it every step)
+                if dc_singular or dc_lost:  # (sparse: the start is NaN, and with it every step)
                     wave = np.full((steps + 1, len(pa)), np.nan)
                     x = np.full((steps // keep_every, h.n), np.nan) if keep_every > 0 else None
                     env = None
@@ -493,6 +534,16 @@ class Circuit:
                                "potential_max": np.full(K, np.nan), "potential_max_step": np.full(K, -1, dtype=np.int32)}
                     resid, info, iters = np.full(steps, np.nan), np.ones(steps, dtype=np.int32), np.zeros(steps, dtype=np.int32)
                     cur, final = np.full((steps + 1, len(cur_index)), np.nan), np.full(len(lnames), np.nan)
+                    if nonlinear:
+                        info *= 1 if dc_singular else 2
+                        junctions = {"newton": np.zeros(steps, dtype=np.int32), "updates": np.zeros(steps, dtype=np.int32),
+                                     "v": np.full((steps + 1, len(diode_index)), np.nan),
+                                     "i": np.full((steps + 1, len(diode_index)), np.nan), "vh": np.full(len(dnames), np.nan)}
+                elif nonlinear:
+                    wave, x, env, resid, info, iters, cur, final, junctions = ch.transient_nl(
+                        cap_rows, ind_rows, diode_rows, i_sat, n_vt, gmin, rows, values, x0, i0, pa, pb, cur_index,
+                        diode_index, dense=not self.sparse, max_iter=max_iter, reltol=reltol, vntol=vntol, abstol=abstol,
+                        method=code, keep_every=keep_every, envelope=envelope)
                 elif len(lnames):
                     wave, x, env, resid, info, iters, cur, final = ch.transient_rlc(
                         cap_rows, ind_rows, rows, values, x0, i0, pa, pb, cur_index, dense=not self.sparse, method=code,
@@ -503,8 +554,13 @@ class Circuit:
         finally:
             if record:
                 ch.set_option(_ffi.OPT_TRANSIENT_TAPE, 0)  # (the handle goes back to a pool some day)
-        singular = (info > 0).any() or dc_singular
+        singular = (info == 1).any() or dc_singular
         _warn_singular(singular)
+        if (info == 2).any():
+            first = int(np.argmax(info == 2)) + 1
+            warnings.warn("transient: the DC start did not converge" if dc_lost else
+                          f"transient: step {first} did not converge in {max_iter} Newton iterations", RuntimeWarning,
+                          stacklevel=2)
         if record and not singular:
             from .sweep import _row_map
             from .transient_gradient import TransientRecord
@@ -520,7 +576,11 @@ class Circuit:
         kept = np.arange(1, steps // keep_every + 1, dtype=np.int64) * keep_every if keep_every > 0 else None
         return Transient(dt * np.arange(steps + 1, dtype=np.float64), wave, probes, info, resid, iters, solutions=x,
                          solution_steps=kept, envelope=env, timings=ch.timings(), currents=cur,
-                         current_probes=current_probes, final_currents=final)
+                         current_probes=current_probes, final_currents=final,
+                         **({} if junctions is None else dict(
+                             newton_iterations=junctions["newton"], matrix_updates=junctions["updates"],
+                             diode_voltages=junctions["v"], diode_currents=junctions["i"], diode_probes=diode_probes,
+                             final_junctions=junctions["vh"])))
 
     def operating_point(self, diodes, sources=None, initial=None, max_iter=100, reltol=1e-3, vntol=1e-6, abstol=1e-12,
                         gmin=1e-12, keep_iterates=False):
@@ -605,6 +665,34 @@ class Circuit:
         n = self.table.n
         # (an E row's branch unknown is the current into lead a out of the element: from a to b it is the negative)
         return e[:n].copy(), -e[n:], singular
+
+    def _transient_nl_dc_start(self, la, lb, i_sat, n_vt, da, db, gmin, max_iter, reltol, vntol, abstol):
+        """The nonlinear DC operating point with capacitors open, every inductor a short and the diodes in, of the
+        netlist's own source values: (x_0 [K+B], i_0 [L], singular, lost).  Newton's method (nodal_newton_dc) on a clone
+        that holds dc_table's zero-volt `E` rows and, behind them, the diodes' companion rows; the clone is kept under
+        the inductors' and diodes' leads, the iteration runs anew for every call (parameters and tolerances may differ;
+        nothing symbolic is repeated).  Dense and singular: LinAlgError; sparse and singular: NaN and singular=True; not
+        converged: lost=True, the caller's warning."""
+        from . import operating_point as op
+        from .transient import dc_table
+        key = (la.tobytes(), lb.tobytes(), da.tobytes(), db.tobytes())
+        if self._transient_nl_dc is None or self._transient_nl_dc[0] != key:
+            self._transient_nl_dc = None  # (its device context goes back to the pool first)
+            table = dc_table(self.table, la, lb) if len(la) else self.table
+            table, diode_rows = op.companion_table(table, i_sat, n_vt, da, db, gmin)
+            self._transient_nl_dc = (key, Circuit._clone_of(self, table), diode_rows)
+        _, clone, diode_rows = self._transient_nl_dc
+        try:
+            r = clone._handle.newton_dc(diode_rows, i_sat, n_vt, gmin, np.zeros(0, dtype=np.int64), np.zeros(0), None,
+                                        dense=not self.sparse, max_iter=max_iter, reltol=reltol, vntol=vntol, abstol=abstol)
+        except _ffi.NodalHipError as exc:
+            if exc.status != _ffi.E_SINGULAR or self.sparse:
+                raise
+            raise self._singular(look_at_connectivity=False) from None
+        n = self.table.n
+        e = np.array(r["x"], dtype=np.float64)
+        singular = bool((r["info"] > 0).any())
+        return e[:n].copy(), -e[n:], singular, not singular and not r["converged"]
 
     def transient_gradient(self, wave_cotangents, probes=None, adjoints=False):
         """The gradient of a scalar loss L of the probe waveforms of the last transient(..., record=True), by the adjoint

@@ -269,7 +269,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->br_env, &h->sn_x, &h->sn_spec, &h->sn_out, &h->sn_cross, &h->sn_perm, &h->pt_buf,
                       &h->gr_cot, &h->gr_x, &h->gr_spec, &h->gr_acc,
                       &h->tr_spec, &h->tr_none, &h->tr_node, &h->tr_ptr, &h->tr_con, &h->tr_vec, &h->tr_out, &h->tr_ring,
-                      &h->tr_ind,
+                      &h->tr_ind, &h->tn_spec, &h->tn_none, &h->tn_node, &h->tn_ptr, &h->tn_con,
                       &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
                       &h->tg_con,
                       &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
@@ -934,6 +934,88 @@ int nodal_transient_rlc(nodal_handle h, int32_t dense, int32_t steps, int32_t me
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_matrix;
     h->ms[1] = 0.0;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
+int nodal_transient_nl(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                       int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                       const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                       double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                       int32_t *info_out, int32_t *iters_out, int64_t nind, const int64_t *ind_rows, const double *i0,
+                       int32_t ncur, const int32_t *cur_index, double *cur_out, double *i_final_out, int64_t ndiode,
+                       const int64_t *diode_rows, const double *i_sat, const double *n_vt, double gmin, int32_t max_iter,
+                       double reltol, double vntol, double abstol, int32_t ndprobe, const int32_t *dprobe_index,
+                       int32_t *newton_out, int32_t *updates_out, double *dv_out, double *di_out, double *vh_final_out) {
+    if (!h || nind < 0 || (nind > 0 && !ind_rows) || ncur < 0 || (ncur > 0 && (!cur_index || nind == 0))) return NODAL_E_INVALID;
+    if (steps < 0 || (method != 0 && method != 1) || ncap < 0 || (ncap > 0 && !cap_rows) || nprobe < 0 ||
+        (nprobe > 0 && (!probe_a || !probe_b)) || keep_every < 0)
+        return NODAL_E_INVALID;
+    if (ndiode < 0 || (ndiode > 0 && (!diode_rows || !i_sat || !n_vt)) || max_iter < 1 || ndprobe < 0 ||
+        (ndprobe > 0 && (!dprobe_index || ndiode == 0)))
+        return NODAL_E_INVALID;
+    if (!(gmin >= 0.0 && reltol >= 0.0 && vntol >= 0.0 && abstol >= 0.0) || std::isinf(gmin) || std::isinf(reltol) ||
+        std::isinf(vntol) || std::isinf(abstol))
+        return nodal_fail(h, NODAL_E_INVALID, "transient: gmin and the tolerances must be finite and not negative");
+    if (!h->have_table || h->csr_only) return nodal_fail(h, NODAL_E_INVALID, "transient: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "transient: assemble_numeric not called");
+    if (h->n > 0 && !x0) return nodal_fail(h, NODAL_E_INVALID, "transient: no initial state");
+    if (ndiode > 0 && h->K == 0) return nodal_fail(h, NODAL_E_INVALID, "transient: diodes on a network without nodes");
+    for (int64_t i = 0; i < ndiode; ++i)
+        if (diode_rows[i] < 0 || diode_rows[i] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "transient: diode row out of range");
+    for (int32_t q = 0; q < ndprobe; ++q)
+        if (dprobe_index[q] < 0 || dprobe_index[q] >= ndiode)
+            return nodal_fail(h, NODAL_E_INVALID, "transient: diode probe outside the diodes");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    h->tape_valid = false;  // (no tape with diodes, and whatever an earlier call recorded is written over)
+    NODAL_TRY(sweep_prepare(h, steps, nsrc, src_rows, src_values));
+    h->amg_levels = 0;
+    h->last_batch_block = false;
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_matrix = 0.0;
+    TransientInductors ind;
+    ind.nind = nind;
+    ind.rows = ind_rows;
+    ind.i0 = i0;
+    ind.ncur = ncur;
+    ind.cur_index = cur_index;
+    ind.cur_out = cur_out;
+    ind.i_final_out = i_final_out;
+    TransientDiodes dio;
+    dio.nd = ndiode;
+    dio.rows = diode_rows;
+    dio.isat = i_sat;
+    dio.nvt = n_vt;
+    dio.gmin = gmin;
+    dio.reltol = reltol;
+    dio.vntol = vntol;
+    dio.abstol = abstol;
+    dio.max_iter = max_iter;
+    dio.ndprobe = ndprobe;
+    dio.dprobe_index = dprobe_index;
+    dio.newton_out = newton_out;
+    dio.updates_out = updates_out;
+    dio.dv_out = dv_out;
+    dio.di_out = di_out;
+    dio.vh_final_out = vh_final_out;
+    const bool nonlinear = ndiode > 0 && h->n > 0;  // (without diodes: nodal_transient_rlc's launches, one iteration a step)
+    std::vector<int32_t> info_own(info_out || !newton_out ? 0 : (size_t)steps);
+    int32_t *info = info_out ? info_out : info_own.data();
+    const int s = transient_run(h, dense != 0, steps, method, ncap, cap_rows, nsrc, x0, nprobe, probe_a, probe_b, wave_out,
+                                keep_every, x_out, pot_min, pot_min_step, pot_max, pot_max_step, resid_out,
+                                nonlinear ? info_out : info, iters_out, &ms_matrix, nind > 0 ? &ind : nullptr,
+                                nonlinear ? &dio : nullptr);
+    if (!nonlinear && s == NODAL_OK)
+        for (int32_t k = 0; k < steps; ++k) {
+            if (newton_out) newton_out[k] = info[k] == 0 ? 1 : 0;
+            if (updates_out) updates_out[k] = 0;
+        }
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = nonlinear ? dio.ms_matrix : ms_matrix;
+    h->ms[1] = nonlinear ? dio.ms_symbolic : 0.0;
     h->ms[2] = elapsed(h, 0, 1);
     return s;
 }

@@ -215,6 +215,10 @@ struct nodal_ctx {
     // ... with inductors (nodal_transient_rlc): their currents, i_0, the probed currents' rows until they go down and the
     // probed inductors' indices
     DevBuf tr_ind;
+    // ... with diodes (nodal_transient_nl, transient_nl.hip): the diode rows, parameters, linearisations, limited voltages,
+    // records, the iteration's right-hand side and the probed diodes' rows until they go down; the node -> incident-diode
+    // lists (as tr_none .. tr_con, which stay the capacitors' and inductors')
+    DevBuf tn_spec, tn_none, tn_node, tn_ptr, tn_con;
     uint64_t numeric_epoch = 1;   // bumped by every numeric assembly (stamp_numeric): the identity of G's values
     uint64_t tr_mg_epoch = 0;     // numeric_epoch the multigrid hierarchy a transient call set up belongs to (0: none)
     uint64_t tr_lu_epoch = 0;     // ... and the sparse LU factors a transient call left
@@ -585,7 +589,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
                   int32_t nsrc, const double *x0, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
                   double *wave_out, int32_t keep_every, double *x_out, double *pot_min, int32_t *pot_min_step,
                   double *pot_max, int32_t *pot_max_step, double *resid_out, int32_t *info_out, int32_t *iters_out,
-                  double *ms_matrix, const TransientInductors *inductors = nullptr);
+                  double *ms_matrix, const TransientInductors *inductors = nullptr, struct TransientDiodes *diodes = nullptr);
 // One step's solve, shared by the forward steps and the backward sweep of transient_gradient.hip.  s: the context whose
 // matrix is solved -- h itself, or the csr_only child that holds G^T (never the multigrid route); lu_epoch: where the
 // numeric_epoch of s's kept LU factors is filed; rvec, dvec [n] and norms ([16][4] + [16]) are the caller's scratch.
@@ -634,6 +638,50 @@ struct NewtonOutputs {           // host arrays, each may be null except iterati
 int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, const double *isat, const double *nvt,
                double gmin, int32_t nsrc, const double *x0, int32_t max_iter, double reltol, double vntol, double abstol,
                const NewtonOutputs &out, double *ms_matrix, double *ms_symbolic);
+
+// the lanes of the loop above for transient_nl.hip: the check of rows and parameters with its verdict (one wait; the two
+// texts of NODAL_E_INVALID are the caller's), vh = v of x, the linearisation at vh, value[rows[d]] = fill
+int newton_check_diodes(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
+                        int32_t *bad_dev, const char *not_r, const char *not_positive);
+int newton_launch_start(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *x, double *vh);
+int newton_launch_linearise(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
+                            double gmin, const double *vh, double *value, double *hist, double *gk, double *ik);
+int newton_launch_fill(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, double fill, double *value);
+
+// ---- nonlinear transient analysis (transient_nl.hip): Newton's method inside every step of transient_run ----
+// nodal_transient_nl's further arguments, and the loop's state.  transient_run with `diodes` leaves the route and the
+// matrix work to step(): prepare() once before the first step (uploads, checks, node lists, row 0 of the diode probes),
+// step() in place of transient_solver_step (base: the step's sources and history currents, held fixed; *inf 0 converged,
+// 1 singular, 2 not converged), after_step() once x_k stands, finish() enqueues what comes down once and finish_host()
+// writes NaN where the steps from first_dead on were to land.
+struct TransientDiodes {
+    int64_t nd = 0;
+    const int64_t *rows = nullptr;            // [nd] table rows of type R, the companion resistors
+    const double *isat = nullptr, *nvt = nullptr;
+    double gmin = 0.0, reltol = 0.0, vntol = 0.0, abstol = 0.0;
+    int32_t max_iter = 1;
+    int32_t ndprobe = 0;
+    const int32_t *dprobe_index = nullptr;    // [ndprobe] indices into the diodes
+    int32_t *newton_out = nullptr, *updates_out = nullptr;  // [steps]
+    double *dv_out = nullptr, *di_out = nullptr;            // [steps + 1][ndprobe]
+    double *vh_final_out = nullptr;                         // [nd]
+    double ms_matrix = 0.0, ms_symbolic = 0.0;  // newton_run's two sums
+    // the loop's state
+    bool reuse = true;        // NODAL_TNL_REUSE
+    bool moved = true;        // the next linearisation's 1 / g differs from what G was assembled from (or is not known to)
+    int64_t nent = 0, rec_at = 0;
+    int32_t slot = 0;         // which of the two vh vectors the next linearisation reads
+    int32_t *rows_dev = nullptr, *bad_dev = nullptr, *pidx_dev = nullptr;
+    double *isat_dev = nullptr, *nvt_dev = nullptr, *hist = nullptr, *gk = nullptr, *ik = nullptr, *vh = nullptr,
+           *rhs = nullptr, *pv_dev = nullptr, *pi_dev = nullptr;
+    unsigned long long *rec_dev = nullptr;
+    int prepare(nodal_ctx *h, int32_t steps, const double *x0_dev);
+    int step(nodal_ctx *h, TransientSolver &ts, bool dense, int32_t k, const double *xp, const double *base, double *xk,
+             int32_t *inf, int32_t *it, double *resid_host, bool *judged);
+    int after_step(nodal_ctx *h, int32_t k, const double *xk);
+    int finish(nodal_ctx *h, int32_t steps);
+    void finish_host(int32_t steps, int32_t first_dead);
+};
 
 // ---- gradients through time (transient_gradient.hip): the adjoint of the recorded backward-Euler run ----
 // the arguments are those of nodal_transient_gradient; ms_matrix as transient_run's

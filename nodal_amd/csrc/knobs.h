@@ -165,6 +165,7 @@ inline constexpr OnUnless0 PAIRS_FUNCTIONAL{"NODAL_PAIRS_FUNCTIONAL"};  // call:
 inline constexpr Int PAIRS_DIRECT{"NODAL_PAIRS_DIRECT", -1};  // call: 1 pair sweeps through the sparse LU, 0 never, -1 by the number of pairs
 inline constexpr Int64 PAIRS_DIRECT_MIN{"NODAL_PAIRS_DIRECT_MIN", 256};  // call: pairs from which a sweep takes the factor-once route
 inline constexpr Double MULTI_BAR{"NODAL_MULTI_BAR", 1e-14};  // call: backward-error bar of the sparse-LU route of the multi-right-hand-side driver; negative: every column redone alone
+inline constexpr OnUnless0 TNL_REUSE{"NODAL_TNL_REUSE"};  // call: 0 nodal_transient_nl assembles G in every Newton iteration, also where no diode's 1 / g moved (the same bits)
 // ---- 3.4 general sparse path
 inline constexpr IntIfSet PRESOLVE{"NODAL_PRESOLVE"};  // create: 0 branch equations stay in the system (full-system FGMRES / pivoted LU)
 inline constexpr OnUnless0 PRESOLVE_KEEP{"NODAL_PRESOLVE_KEEP"};  // process: 0 one source the presolve cannot substitute ends it

@@ -24,6 +24,7 @@
 //                           no floating-point sums, a repeated call gives the same bits
 // and then ONE read of the record's four words, the scaled residual among them.  The loop ends when no diode failed its
 // test, on max_iter, on info > 0 or on a record that is not finite; k_newton_outputs then forms v, i(v), g(v) from x.
+#include "diode_lanes.h"
 #include "group.h"
 #include "table_rows.h"
 
@@ -33,20 +34,6 @@
 namespace {
 
 constexpr int TTB = 256;
-
-// grouping enumerator (group.h): diode i touches its anode (slot 0: +J) and its cathode (slot 1: -J); one column
-struct DiodeLeads {
-    static constexpr int SLOTS = 2;
-    const int32_t *rows, *a, *b;
-    int64_t nitems;
-    template <class F>
-    __device__ void for_each(int64_t i, F f) const {
-        const int32_t r = rows[i];
-        const int ia = a[r], ib = b[r];
-        if (ia >= 0) f(0, ia, 0);
-        if (ib >= 0) f(1, ib, 0);
-    }
-};
 
 // bad[0] |= 1 for a diode row that is not a resistor, |= 2 for a saturation current or an n_vt that is not > 0 and finite
 __global__ __launch_bounds__(TTB) void k_newton_check(int64_t nd, const int32_t *__restrict__ rows,
@@ -77,23 +64,14 @@ __global__ __launch_bounds__(TTB) void k_newton_linearise(int64_t nd, const int3
                                                           double *__restrict__ gk, double *__restrict__ ik) {
     const int64_t d = (int64_t)blockIdx.x * TTB + threadIdx.x;
     if (d >= nd) return;
-    const double v = vh[d], is = isat[d], nv = nvt[d];
-    const double e = exp(v / nv);
-    const double ge = is * e;
-    const double gl = gmin * v;
-    const double g = ge / nv + gmin;
-    const double ie = is * (e - 1.0);
-    const double i = ie + gl;
+    const double v = vh[d];
+    double g, i;
+    diode_model(v, isat[d], nvt[d], gmin, &g, &i);
     const double gv = g * v;
     value[rows[d]] = 1.0 / g;
     hist[d] = gv - i;
     gk[d] = g;
     ik[d] = i;
-}
-
-// the bits of a non-negative double order as the values do, every NaN above +inf
-__device__ __forceinline__ unsigned long long magnitude_bits(double m) {
-    return (unsigned long long)__double_as_longlong(fabs(m));
 }
 
 // One lane per diode after the solve: the limited voltage of the next linearisation, the convergence test against the
@@ -110,30 +88,9 @@ __global__ __launch_bounds__(TTB) void k_newton_update(int64_t nd, const int32_t
     if (d >= nd) return;
     const int32_t r = rows[d];
     const double v = lead(x, a[r]) - lead(x, b[r]);
-    const double old = vh[d], is = isat[d], nv = nvt[d];
-    const double dv = v - old;
-    const double vcrit = nv * log(nv / (1.4142135623730951 * is));
-    const bool limited = v > vcrit && fabs(dv) > 2.0 * nv;
-    double next = v;
-    if (limited) {
-        if (old > 0.0) {
-            const double arg = 1.0 + dv / nv;
-            const double step = nv * log(arg);
-            next = arg > 0.0 ? old + step : vcrit;
-        } else {
-            next = nv * log(v / nv);
-        }
-    }
-    vh_next[d] = next;
-    // the current the junction carries at v against the current its linearisation predicted there
-    const double ee = is * (exp(v / nv) - 1.0);
-    const double gl = gmin * v;
-    const double iv = ee + gl;
-    const double slope = gk[d] * dv;
-    const double ihat = ik[d] + slope;
-    const double vbar = reltol * fmax(fabs(v), fabs(old)) + vntol;
-    const double ibar = reltol * fmax(fabs(iv), fabs(ihat)) + abstol;
-    const bool ok = fabs(dv) <= vbar && fabs(iv - ihat) <= ibar;  // (false with a NaN anywhere)
+    bool limited, ok;
+    double dv;
+    vh_next[d] = diode_limit_and_test(v, vh[d], isat[d], nvt[d], gmin, reltol, vntol, abstol, gk[d], ik[d], &limited, &ok, &dv);
     if (!ok) atomicAdd(rec, 1ull);
     if (limited) atomicAdd(rec + 1, 1ull);
     atomicMax(rec + 2, magnitude_bits(dv));
@@ -149,14 +106,11 @@ __global__ __launch_bounds__(TTB) void k_newton_outputs(int64_t nd, const int32_
     if (d >= nd) return;
     const int32_t r = rows[d];
     const double v = lead(x, a[r]) - lead(x, b[r]);
-    const double is = isat[d], nv = nvt[d];
-    const double e = exp(v / nv);
-    const double ge = is * e;
-    const double ie = is * (e - 1.0);
-    const double gl = gmin * v;
+    double g, i;
+    diode_model(v, isat[d], nvt[d], gmin, &g, &i);
     vout[d] = v;
-    iout[d] = ie + gl;
-    gout[d] = ge / nv + gmin;
+    iout[d] = i;
+    gout[d] = g;
 }
 
 // value[rows[d]] = fill: what the companion rows hold after a linearisation that overflowed
@@ -361,5 +315,37 @@ int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, 
             if (p)
                 for (int64_t d = 0; d < nd; ++d) p[d] = nan;
     }
+    return NODAL_OK;
+}
+
+// ---- the same lanes for nodal_transient_nl (transient_nl.hip), which nests this loop inside every time step ----
+int newton_check_diodes(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
+                        int32_t *bad_dev, const char *not_r, const char *not_positive) {
+    int32_t bad = 0;
+    NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, h->stream));
+    k_newton_check<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, h->type.as<uint8_t>(), isat_dev, nvt_dev, bad_dev);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));
+    if (bad & 1) return nodal_fail(h, NODAL_E_INVALID, not_r);
+    if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, not_positive);
+    return NODAL_OK;
+}
+
+int newton_launch_start(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *x, double *vh) {
+    k_newton_start<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), x, vh);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+int newton_launch_linearise(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
+                            double gmin, const double *vh, double *value, double *hist, double *gk, double *ik) {
+    k_newton_linearise<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, isat_dev, nvt_dev, gmin, vh, value, hist, gk, ik);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+int newton_launch_fill(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, double fill, double *value) {
+    k_newton_fill<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, fill, value);
+    NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }

@@ -33,6 +33,11 @@
 //     trapezoidal:  i_k = i_{k-1} + g (v_k + v_{k-1}),  J_k = -(i_{k-1} + g v_{k-1})
 // so that i_k = -J_k + g v_k in both: the lane finishes i_k and forms J_{k+1} from x_k alone, AFTER the solve, where a
 // capacitor's lane forms J_k from x_{k-1} before it.
+//
+// Diodes (nodal_transient_nl) change none of the above: transient_run with a TransientDiodes forms the same right-hand
+// side once per step, hands the solve to TransientDiodes::step (transient_nl.hip: Newton's method around
+// transient_solver_begin / transient_solver_step) and goes on with the inductor lane, probes, envelope and ring once the
+// step has converged.  Without one (nodal_transient, nodal_transient_rlc) the launches are what they were.
 #include "group.h"
 #include "table_rows.h"
 
@@ -304,7 +309,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
                   int32_t nsrc, const double *x0, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
                   double *wave_out, int32_t keep_every, double *x_out, double *pot_min, int32_t *pot_min_step,
                   double *pot_max, int32_t *pot_max_step, double *resid_out, int32_t *info_out, int32_t *iters_out,
-                  double *ms_matrix, const TransientInductors *inductors) {
+                  double *ms_matrix, const TransientInductors *inductors, TransientDiodes *diodes) {
     const int64_t n = h->n;
     const TransientInductors none;
     const TransientInductors &ind = inductors ? *inductors : none;
@@ -327,7 +332,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     h->have_x = false;
     h->last_iterations = 0;
     // NODAL_OPT_TRANSIENT_TAPE: the states stay on the handle for nodal_transient_gradient (backward Euler only)
-    const bool record = h->transient_tape && method == 0 && nind == 0;  // (no adjoint with inductors: no tape)
+    const bool record = h->transient_tape && method == 0 && nind == 0 && !diodes;  // (no adjoint with inductors or diodes: no tape)
     auto keep_tape = [&](int64_t nent_caps) {
         h->tape_valid = true;
         h->tape_epoch = h->numeric_epoch;
@@ -448,6 +453,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         if (ncur > 0) k_transient_current_probe<<<groups_of(ncur, TTB), TTB, 0, st>>>(ncur, cidx_dev, icur, cur_dev);
         NODAL_HIP_TRY(h, hipGetLastError());
     }
+    if (diodes) NODAL_TRY(diodes->prepare(h, steps, state(0)));
     NODAL_WAIT_STREAM(h, st);  // (x0, i0 and the probes are the caller's, r32 ends here)
 
     // ---- the route and its matrix work ----
@@ -458,10 +464,11 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
     ts.dvec = dvec;
     ts.norms = norms;
     bool dead = steps == 0;   // a singular verdict: no step from there on has a state to start from
-    NODAL_TRY(transient_solver_begin(h, ts, dense, steps, &dead, ms_matrix));
+    if (!diodes) NODAL_TRY(transient_solver_begin(h, ts, dense, steps, &dead, ms_matrix));  // (with diodes: every iteration)
 
     // ---- the steps ----
     int32_t first_dead = dead ? 1 : steps + 1;
+    int32_t dead_info = 1;  // what the steps without a state report: 1 singular, 2 Newton's method did not converge
     std::vector<uint8_t> on_host((size_t)steps, 0);  // the step's residual was read back already (the sparse LU route)
     bool env_first = true;
     int32_t ring_fill = 0, ring_base = 0;  // kept solutions in the ring, and the index of the first of them
@@ -485,11 +492,13 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         // the solve
         int32_t inf = 0, it = 0;
         bool judged = false;  // resid[k - 1] is on the host already
-        NODAL_TRY(transient_solver_step(h, ts, bvec, xk, &inf, &it, &resid[k - 1], &judged, ms_matrix));
+        if (diodes) NODAL_TRY(diodes->step(h, ts, dense, k, xp, bvec, xk, &inf, &it, &resid[k - 1], &judged));
+        else NODAL_TRY(transient_solver_step(h, ts, bvec, xk, &inf, &it, &resid[k - 1], &judged, ms_matrix));
         if (inf > 0) {
-            if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+            if (dense && inf == 1) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
             dead = true;
             first_dead = k;
+            dead_info = inf;
             break;
         }
         iters[k - 1] = it;
@@ -511,6 +520,7 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
             env_first = false;
         }
         NODAL_HIP_TRY(h, hipGetLastError());
+        if (diodes) NODAL_TRY(diodes->after_step(h, k, xk));
         if (nkeep > 0 && k % keep_every == 0) {
             NODAL_HIP_TRY(h, hipMemcpyAsync(ring + (size_t)ring_fill * n, xk, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
             if (++ring_fill == std::min<int32_t>(RING, nkeep)) NODAL_TRY(flush_ring());
@@ -533,12 +543,14 @@ int transient_run(nodal_ctx *h, bool dense, int32_t steps, int32_t method, int64
         if (pot_min_step) NODAL_HIP_TRY(h, hipMemcpyAsync(pot_min_step, pmin_step_dev, (size_t)K * 4, hipMemcpyDeviceToHost, st));
         if (pot_max_step) NODAL_HIP_TRY(h, hipMemcpyAsync(pot_max_step, pmax_step_dev, (size_t)K * 4, hipMemcpyDeviceToHost, st));
     }
+    if (diodes) NODAL_TRY(diodes->finish(h, steps));
     NODAL_WAIT_STREAM(h, st);
+    if (diodes) diodes->finish_host(steps, first_dead);
     for (int32_t k = 1; k < first_dead && k <= steps; ++k)
         if (!on_host[(size_t)k - 1]) resid[k - 1] = resid_dn[(size_t)k - 1];
     // the steps without a state: info 1, NaN wherever they were to land
     for (int32_t k = first_dead; k <= steps; ++k) {
-        info[k - 1] = 1;
+        info[k - 1] = dead_info;
         iters[k - 1] = 0;
         resid[k - 1] = nan;
         if (wave_out)

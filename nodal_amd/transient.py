@@ -15,7 +15,15 @@ element, kept per inductor on the device (`nodal_transient_rlc`).  At DC an indu
 is the solution of the netlist with one zero-volt `E` row per inductor (`dc_table`), whose branch unknown is the current
 INTO lead a out of the element, so i_0 is its negative.
 
-`check_transient_arguments`, `resolve_capacitors`, `resolve_inductors`, `companion_table` and `dc_table` need no device,
+With diodes (`Circuit.transient(diodes=...)`, `nodal_transient_nl`, csrc/transient_nl.hip) every step is a Newton
+iteration on the device: the diodes' companion rows stand behind the inductors' (`diode_companion_table`), the step's
+sources and history currents are formed once and held fixed, and an iteration whose junction conductances did not move
+by a bit re-uses the factorisation or the hierarchy.  Out of scope: adaptive time steps, junction capacitance, devices
+other than the diode, the adjoint of such a run, a presolve route, and a hierarchy kept as a preconditioner while only
+level 0 follows the matrix.
+
+`check_transient_arguments`, `resolve_capacitors`, `resolve_inductors`, `companion_table`, `diode_companion_table`,
+`check_diode_probes` and `dc_table` need no device,
 and `Transient` is a plain container that can be built from arrays.
 """
 
@@ -154,6 +162,27 @@ def companion_table(table, farads, ia, ib, dt, method_code, henries=None, la=Non
     return (out, rows) if henries is None else (out, rows[:ncap], rows[ncap:])
 
 
+def diode_companion_table(table, farads, ia, ib, dt, method_code, henries, la, lb, i_sat, n_vt, da, db, gmin=0.0):
+    """The table of a transient run with diodes: the capacitors' companion rows, then the inductors', then one per
+    diode (operating_point.companion_table: a placeholder value the device overwrites before every assembly, a diode with
+    both leads on one node between ground and ground).  Returns (table, capacitor rows [C], inductor rows [L], diode
+    rows [D]); the original rows keep their indices."""
+    from .operating_point import companion_table as diode_rows_appended
+    table, cap_rows, ind_rows = companion_table(table, farads, ia, ib, dt, method_code, henries, la, lb)
+    table, diode_rows = diode_rows_appended(table, i_sat, n_vt, da, db, gmin)
+    return table, cap_rows, ind_rows, diode_rows
+
+
+def check_diode_probes(names, diode_probes):
+    """`diode_probes` of Circuit.transient as int32 [Q] indices into the diodes `names`; KeyError for a probe that is
+    not the name of a diode (also: any probe when there are no diodes)."""
+    index = {name: j for j, name in enumerate(names)}
+    for name in diode_probes:
+        if name not in index:
+            raise KeyError(f"diode probe {name!r} is not the name of a diode")
+    return np.asarray([index[name] for name in diode_probes], dtype=np.int32).reshape(len(diode_probes))
+
+
 def dc_table(table, la, lb):
     """The table in which every inductor is a short: one zero-volt `E` row per inductor appended, each with a branch
     unknown of its own (ComponentTable.with_branch_rows_appended): K + B + L unknowns, the first K + B the circuit's.
@@ -183,10 +212,19 @@ class Transient:
     [steps].  timings: nodal_last_timings of the call, [0] the ms of the matrix work done once (0.0: it was kept from an
     earlier call), [2] the whole call on the device.  currents [steps + 1, Q]: the currents of the inductors named in
     current_probes, from lead a to lead b, row 0 the start's; final_currents [L]: every inductor's after the last step
-    (NaN when a step was singular), what `initial_currents` of a continuing call takes."""
+    (NaN when a step was singular), what `initial_currents` of a continuing call takes.
+
+    With diodes (nodal_transient_nl): info 2 marks a step whose Newton loop did not converge (it and every later step:
+    NaN); newton_iterations [steps] and matrix_updates [steps]: a step's Newton iterations and those of them whose
+    matrix work ran; diode_voltages, diode_currents [steps + 1, Q]: v and i(v) of the diodes named in diode_probes, row 0
+    the start's; final_junctions [D]: the limited junction voltages after the last step.  scaled_residual is the largest
+    of a step's linear solves (one per Newton iteration), iterations those of its last, timings as OperatingPoint's.  Without diodes: one iteration per solved
+    step, no update, empty arrays."""
 
     def __init__(self, t, waveforms, probes, info, scaled_residual, iterations, solutions=None, solution_steps=None,
-                 envelope=None, timings=None, currents=None, current_probes=(), final_currents=None):
+                 envelope=None, timings=None, currents=None, current_probes=(), final_currents=None,
+                 newton_iterations=None, matrix_updates=None, diode_voltages=None, diode_currents=None, diode_probes=(),
+                 final_junctions=None):
         self.t = t
         self.waveforms = waveforms
         self.probes = list(probes)
@@ -200,6 +238,14 @@ class Transient:
         self.currents = currents if currents is not None else np.zeros((len(t), 0), dtype=np.float64)
         self.current_probes = list(current_probes)
         self.final_currents = final_currents if final_currents is not None else np.zeros(0, dtype=np.float64)
+        solved = (np.asarray(info) == 0).astype(np.int32)
+        self.newton_iterations = newton_iterations if newton_iterations is not None else solved
+        self.matrix_updates = matrix_updates if matrix_updates is not None else np.zeros(len(solved), dtype=np.int32)
+        empty = np.zeros((len(t), 0), dtype=np.float64)
+        self.diode_voltages = diode_voltages if diode_voltages is not None else empty
+        self.diode_currents = diode_currents if diode_currents is not None else empty.copy()
+        self.diode_probes = list(diode_probes)
+        self.final_junctions = final_junctions if final_junctions is not None else np.zeros(0, dtype=np.float64)
 
     def __len__(self):
         return len(self.info)
