@@ -353,6 +353,55 @@ int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t
                     double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out, double *record_out,
                     int32_t *info_out, int32_t *iters_out, int32_t *route_out, int32_t *iterations, int32_t *converged);
 
+/* ---- gradients through the operating point: the adjoint of the Newton solve (replaces finite differences, two whole
+ *      Newton runs per parameter, and the host loop of download x, scipy transpose solve and numpy formulas; with the
+ *      reference every such run is itself a rebuild and a .solve() per iteration, reference nodal/nodal.py:306-336) ----
+ * The handle holds the circuit with one companion R row per diode exactly as nodal_newton_dc requires; diode_rows, i_sat,
+ * n_vt, gmin and src_rows / src_values [nsrc] are those the operating point x [n] was found at (x is the caller's:
+ * nodal_newton_dc drops the handle's solution), cotangent [n] = dL/dx.  At the operating point
+ *   F(x, p) = G(p) x + S i(S^T x) - A(p) = 0,   i(v) = i_sat (exp(v / n_vt) - 1) + gmin v,
+ * S the incidence of the diodes (+1 anode, -1 cathode), so J^T lambda = cotangent with J = G + S diag(g(v)) S^T taken at
+ * v = S^T x ITSELF (not at the last limited voltages of the run, which are one step behind), and dL/dp = -lambda^T dF/dp.
+ * On the handle's stream: v = x(a) - x(b) per diode; the linearisation at v (1 / g(v) into the diode rows of the value
+ * column, J_hist = g v - i(v)); G assembled anew, symbolic phase kept; the right-hand side of a Newton iteration (the
+ * sources at src_values plus the signed list add of J_hist) and the block judge of x against it -- because the
+ * linearisation is at x this is the nonlinear KCL defect G x + S i(v) - A, scaled as nodal_solve_sources defines; the
+ * transposed solve on the handle itself (B == 0 and all R > 0) or on the child that holds G^T, by nodal_newton_dc's routes
+ * and fall-backs (n <= 64 the dense panel; B == 0, all R > 0 and n > 4096 multigrid with the hierarchy's values refreshed
+ * on its kept symbolic setup; otherwise the sparse LU factored anew on its kept analysis; a step above the bar goes to
+ * the sparse direct solve); then the formulas:
+ *   grad_out [ncomp]          s_i(lambda, x) of every table row as nodal_gradient's (cross terms of CCVS / CCCS drivers
+ *                             included); exactly +0.0 in the diode rows, whose table value is the device's own
+ *   grad_isat_out [ndiode]    -D (e - 1),           D = lambda(a) - lambda(b), e = exp(v / n_vt) as the forward pass
+ *   grad_nvt_out [ndiode]     D i_sat e v / n_vt^2
+ *   grad_gmin_out [1]         the sum over the diodes of -D v, reduced in a fixed order (wavefront, workgroup, then one
+ *                             pass over the workgroups' sums)
+ *   grad_sources_out [nsrc]   lambda(a) - lambda(b) of an A row, lambda(K + k) of an E row
+ *   adjoint_out [n]           lambda
+ *   resid_out [1]             the scaled residual of the transposed solve
+ *   op_resid_out [1]          the scaled residual of x as an operating point (above): a caller who hands in an x that is
+ *                             no operating point, or whose values moved since, sees it here
+ *   info_out [1]              0 solved, > 0 J is singular
+ * Each may be NULL except grad_out (with ncomp > 0) and info_out.  A diode with both leads on one node gets three zeros.
+ * A singular J returns NODAL_E_SINGULAR with dense != 0; otherwise NaN in everything lambda feeds, info_out > 0, status
+ * OK, op_resid_out still valid.  A g that overflows (1 / g == 0): every output NaN, op_resid_out too, info_out 0, and the
+ * handle is left as nodal_newton_dc leaves it after an overflow.  n == 0 writes zeros.  ndiode == 0 is nodal_gradient's
+ * single solve on the caller's x, on the matrix the handle holds.
+ * nodal_last_timings afterwards as nodal_newton_dc's: [0] host ms of the matrix work, [1] the part of it that was symbolic
+ * -- exactly 0.0 on a second call on the same structure -- [2] the whole call.
+ * NODAL_E_INVALID: nodal_newton_dc's diode and source-row cases, gmin negative or not finite, x or cotangent NULL with
+ * n > 0, grad_out NULL with ncomp > 0, no nodal_assemble_numeric before the call.
+ * Host waits: the diode check, the assembly's status words, what the solver looks at, one read of three words at the
+ * end.  No floating-point atomics: a repeated call gives the same bits.  Afterwards the handle is as nodal_newton_dc
+ * leaves it: the value column holds 1 / g(v) in the diode rows (1.0 after an overflow), G, factors and hierarchy belong
+ * to it, the solution is dropped, a recorded transient is void; nodal_newton_dc's note on the host copy of the values
+ * holds here too. */
+int nodal_newton_gradient(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                          const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                          const double *x, const double *cotangent, double *grad_out, double *grad_isat_out,
+                          double *grad_nvt_out, double *grad_gmin_out, double *grad_sources_out, double *adjoint_out,
+                          double *resid_out, double *op_resid_out, int32_t *info_out);
+
 /* ---- nonlinear transient analysis: diodes in a network stepped in time, Newton's method inside every step (replaces a
  *      host loop around nodal_newton_dc that downloads x, rebuilds the history currents, uploads a value column,
  *      assembles and solves once per Newton iteration per step) ----

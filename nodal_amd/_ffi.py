@@ -66,6 +66,8 @@ SIGNATURES = {
     "nodal_newton_dc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, _i64p, _f64p,
                                   _f64p, C.c_int32, C.c_double, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p,
                                   _f64p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "nodal_newton_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, _i64p,
+                                        _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_transient_nl": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
                                      _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p, _i32p,
                                      _f64p, _i32p, _i32p, C.c_int64, _i64p, _f64p, C.c_int32, _i32p, _f64p, _f64p,
@@ -650,6 +652,39 @@ class Handle:
         return {"x": x, "v": v, "i": i, "g": g, "iterations": r, "converged": bool(converged.value), "record": record[:r],
                 "info": info[:r], "iters": iters[:r], "route": route[:r],
                 "iterates": iterates[:r] if keep_iterates else None, "vh": vh[:r + 1] if keep_iterates else None}
+
+    def newton_gradient(self, diode_rows, i_sat, n_vt, gmin, rows, values, x, cotangent, dense, adjoints=False):
+        """The adjoint of the Newton solve at the operating point x (nodal_newton_gradient), on a handle that holds the
+        circuit with one companion resistor per diode: diode_rows, i_sat, n_vt [D], gmin and the one setting values
+        [len(rows)] of the swept sources as newton_dc() took them, x [n] its answer, cotangent [n] = dL/dx.  Returns a
+        dict: grad [ncomp] of this handle's table (+0.0 in the companion rows), i_sat, n_vt [D], gmin (float), sources
+        [len(rows)], adjoint [n] or None, resid and op_resid (floats: the scaled residuals of the transposed solve and of
+        x as an operating point), info; NodalHipError(E_INVALID) as the header lists, with dense a singular J raises
+        NodalHipError(E_SINGULAR)."""
+        diode_rows = np.ascontiguousarray(diode_rows, dtype=np.int64)
+        i_sat, n_vt = (np.ascontiguousarray(v, dtype=np.float64) for v in (i_sat, n_vt))
+        D = len(diode_rows)
+        assert diode_rows.ndim == 1 and i_sat.shape == (D,) and n_vt.shape == (D,)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.shape == (len(rows),)
+        x, cot = (np.ascontiguousarray(v, dtype=np.float64) for v in (x, cotangent))
+        assert x.shape == (self.n,) and cot.shape == (self.n,)
+        grad = np.zeros(self._ncomp, dtype=np.float64)
+        gis, gnv = np.zeros(D, dtype=np.float64), np.zeros(D, dtype=np.float64)
+        gsrc = np.zeros(len(rows), dtype=np.float64)
+        lam = np.zeros(self.n, dtype=np.float64) if adjoints else None
+        ggmin, resid, op_resid, info = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+        self._check(self.lib.nodal_newton_gradient(
+            self._h, int(dense), D, _ptr(diode_rows, C.c_int64) if D else None, _ptr(i_sat, C.c_double) if D else None,
+            _ptr(n_vt, C.c_double) if D else None, float(gmin), len(rows), _ptr(rows, C.c_int64) if len(rows) else None,
+            _ptr(values, C.c_double) if len(rows) else None, _ptr(x, C.c_double) if self.n else None,
+            _ptr(cot, C.c_double) if self.n else None, _ptr(grad, C.c_double), _ptr(gis, C.c_double) if D else None,
+            _ptr(gnv, C.c_double) if D else None, C.byref(ggmin), _ptr(gsrc, C.c_double) if len(rows) else None,
+            _ptr(lam, C.c_double) if adjoints and self.n else None, C.byref(resid), C.byref(op_resid),
+            C.byref(info)))
+        return {"grad": grad, "i_sat": gis, "n_vt": gnv, "gmin": ggmin.value, "sources": gsrc, "adjoint": lam,
+                "resid": resid.value, "op_resid": op_resid.value, "info": int(info.value)}
 
     def transient_gradient(self, steps, nsrc, ia, ib, cotangents, dense, adjoints=False):
         """The adjoint of the transient run this handle recorded (nodal_transient_gradient; OPT_TRANSIENT_TAPE): steps

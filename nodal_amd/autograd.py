@@ -4,6 +4,7 @@
     X = autograd.solve_sources(circuit, values, names, source_values)     # [M, K+B]
     W = autograd.transient(circuit, values, capacitors, dt, steps, ...)   # [steps+1, P]
     W = autograd.ac(circuit, values, capacitors, inductors, frequencies, ...)  # [F, P] complex
+    x = autograd.operating_point(circuit, values, diodes, i_sat, n_vt, ...)    # [K+B]
 
 `values` is a float64 CPU tensor [ncomp] in the order of `netlist.component_keys` (what `Circuit.values` holds),
 `source_values` a float64 CPU tensor [M, len(names)] with the members' values of the swept A / E components
@@ -18,6 +19,10 @@ the run starts from `initial`.
 `ac` returns the probe phasors of `Circuit.ac`, complex128 [F, P]; its backward is one `Circuit.ac_gradient` call with the
 incoming cotangent (torch's dL/dRe + j dL/dIm for a complex tensor is the convention of that call) and hands gradients to
 `values`, the farads, the henries and the complex amplitudes.
+`operating_point` returns the x of `Circuit.operating_point`, the nonlinear DC solution with diodes; its backward is one
+`OperatingPoint.gradient` call (nodal_newton_gradient: one adjoint solve with the Newton matrix linearised at x) and
+hands gradients to `values`, the diodes' `i_sat` and `n_vt` and `source_values` [len(names)]; at a named source's row
+`values` gets zero.
 
 This module imports torch; `import nodal_amd` does not import it.
 """
@@ -167,6 +172,39 @@ class _AC(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+class _OperatingPoint(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, circuit, values, i_sat, n_vt, source_values, leads, names, options):
+        held, sat, nvt = _values_of(values), _values_of(i_sat), _values_of(n_vt)
+        names = list(names)
+        swept = _values_of(source_values) if names else np.zeros(0)
+        if swept.shape != (len(names),):
+            raise ValueError(f"source_values must have shape ({len(names)},), not {tuple(swept.shape)}")
+        if sat.shape != (len(leads),) or nvt.shape != (len(leads),):
+            raise ValueError(f"i_sat and n_vt must have shape ({len(leads)},)")
+        ctx.circuit, ctx.held, ctx.names = circuit, held, names
+        ctx.call = dict(diodes=[(name, float(s), float(v), a, b) for (name, a, b), s, v in zip(leads, sat, nvt)],
+                        sources={name: float(swept[j]) for j, name in enumerate(names)} if names else None,
+                        **dict(options))
+        circuit.set_values(held)
+        ctx.op = circuit.operating_point(**ctx.call)
+        return torch.from_numpy(np.array(ctx.op.x, dtype=np.float64))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, cotangent):
+        circuit = ctx.circuit
+        _put_back(circuit, ctx.held)
+        grad = ctx.op.gradient(_values_of(cotangent))
+        values = np.array(grad.values, dtype=np.float64)
+        if ctx.names:
+            values[np.asarray(ctx.op.source_rows)] = 0.0  # (the run does not use the table value of a named source)
+        swept = np.array([grad.source_values[name] for name in ctx.names], dtype=np.float64).reshape(len(ctx.names))
+        return (None, torch.from_numpy(values), torch.from_numpy(np.array(grad.i_sat, dtype=np.float64)),
+                torch.from_numpy(np.array(grad.n_vt, dtype=np.float64)), torch.from_numpy(swept) if ctx.names else None,
+                None, None, None)
+
+
 def solve(circuit, values):
     """The solution [K+B] of `circuit` with the component values `values` [ncomp], differentiable in `values`."""
     return _Solve.apply(circuit, values)
@@ -211,3 +249,17 @@ def ac(circuit, values, capacitors, inductors, frequencies, source_names=(), amp
         amplitudes = torch.zeros(0, dtype=torch.complex128)
     return _AC.apply(circuit, values, farads, henries, amplitudes, cap_leads, ind_leads, tuple(frequencies), tuple(source_names),
                      tuple(probes))
+
+
+def operating_point(circuit, values, diodes, i_sat, n_vt, source_names=(), source_values=None, **newton_options):
+    """The operating point x [K+B] of `Circuit.operating_point` with the component values `values` [ncomp], the diodes
+    `diodes` -- (name, anode, cathode), plain -- with the parameters `i_sat` and `n_vt` [D] and the values
+    `source_values` [len(source_names)] of the independent sources `source_names`; differentiable in values, i_sat, n_vt
+    and source values.  `newton_options` go to Circuit.operating_point (initial, max_iter, reltol, vntol, abstol, gmin).
+    The gradient is that of the exact operating point the iteration approximates: tighten the tolerances where the
+    fourth digit of x matters."""
+    leads = [(d[0], d[1], d[2]) for d in diodes]
+    if source_values is None:
+        source_values = torch.zeros(0, dtype=torch.float64)
+    return _OperatingPoint.apply(circuit, values, i_sat, n_vt, source_values, leads, tuple(source_names),
+                                 tuple(sorted(newton_options.items())))

@@ -597,7 +597,10 @@ class Circuit:
         |v - vh| <= reltol max(|v|, |vh|) + vntol and |i(v) - ihat| <= reltol max(|i(v)|, |ihat|) + abstol, ihat the
         current its linearisation predicted.  Returns an OperatingPoint (operating_point.py): `x`, `voltages`,
         `currents`, `conductances` [D], `converged`, `iterations`, `history`, `scaled_residual`, `timings`,
-        linearised() -- the small-signal circuit at this point for ac(), noise(), thevenin(sources=False) -- and with
+        linearised() -- the small-signal circuit at this point for ac(), noise(), thevenin(sources=False) --
+        gradient(cotangent) -- dL/d(every component value, i_sat, n_vt, gmin, the sources named here) of a loss L(x)
+        through this point by one adjoint solve (nodal_newton_gradient); it is taken at the circuit's values in force
+        when it is called, and its `operating_point_residual` is how a caller sees that they moved since -- and with
         keep_iterates=True `iterates` and `limited_voltages`.
 
         The matrix is that of the netlist with one companion resistor per diode, assembled on a second device context
@@ -610,9 +613,8 @@ class Circuit:
         that is not finite or of another shape.  No floating-point atomics: a repeated call gives the same bits.  The
         circuit itself -- its solution if any, table, G, A, what transient() and ac() keep -- is left as it was;
         solve() is neither needed nor touched."""
-        from .operating_point import (NewtonHistory, OperatingPoint, check_operating_point_arguments, companion_table,
-                                      resolve_diodes)
-        from .sweep import resolve_sources
+        from .operating_point import NewtonHistory, OperatingPoint, check_operating_point_arguments, resolve_diodes
+        from .sweep import _row_map, resolve_sources
         h = self._handle
         max_iter, reltol, vntol, abstol, gmin, x0 = check_operating_point_arguments(max_iter, reltol, vntol, abstol, gmin,
                                                                                     initial, h.n)
@@ -624,12 +626,11 @@ class Circuit:
             setting = {name: [value] for name, value in sources.items()}
         rows, values = resolve_sources(self.netlist, setting)
         values = values[0] if len(rows) else np.zeros(0, dtype=np.float64)
-        key = (ia.tobytes(), ib.tobytes())
-        if self._newton_child is None or self._newton_child[0] != key:
-            self._newton_child = None  # (its device context goes back to the pool first)
-            table, diode_rows = companion_table(self.table, i_sat, n_vt, ia, ib, gmin)
-            self._newton_child = (key, Circuit._clone_of(self, table), diode_rows)
-        _, child, diode_rows = self._newton_child
+        row_map, columns, at = _row_map(self.netlist) if setting else {}, {}, 0
+        for name in setting:  # (the order resolve_sources lays the rows out in)
+            columns[name] = list(range(at, at + len(row_map[name])))
+            at += len(row_map[name])
+        child, diode_rows = self._newton_companion(i_sat, n_vt, ia, ib, gmin)
         ch = child._handle
         with self._reference_errors():
             r = ch.newton_dc(diode_rows, i_sat, n_vt, gmin, rows, values, x0, dense=not self.sparse, max_iter=max_iter,
@@ -641,7 +642,38 @@ class Circuit:
         history = NewtonHistory(r["record"], r["info"], r["iters"], r["route"])
         return OperatingPoint(r["x"], names, r["v"], r["i"], r["g"], r["converged"], r["iterations"], history,
                               timings=ch.timings(), iterates=r["iterates"], limited_voltages=r["vh"], circuit=self,
-                              leads=(ia, ib))
+                              leads=(ia, ib), i_sat=i_sat, n_vt=n_vt, gmin=gmin, source_rows=rows, source_values=values,
+                              source_columns=columns)
+
+    def _newton_companion(self, i_sat, n_vt, ia, ib, gmin):
+        """Find or make the companion child for these leads: (the Circuit that holds this circuit's table with one
+        companion `R` row per diode, those rows' indices).  Kept on the circuit under the diodes' leads until
+        set_values(); other leads re-key it (the earlier child's device context goes back to the pool first)."""
+        from .operating_point import companion_table
+        key = (ia.tobytes(), ib.tobytes())
+        if self._newton_child is None or self._newton_child[0] != key:
+            self._newton_child = None
+            table, diode_rows = companion_table(self.table, i_sat, n_vt, ia, ib, gmin)
+            self._newton_child = (key, Circuit._clone_of(self, table), diode_rows)
+        _, child, diode_rows = self._newton_child
+        return child, diode_rows
+
+    def _operating_point_gradient(self, op, x, cotangent, adjoints):
+        """OperatingPoint.gradient on this circuit: the companion child for the result's leads (the one its run used,
+        unless another operating_point call or set_values() came between: then it is re-keyed or made anew from the
+        values in force), nodal_newton_gradient on it, and the pieces as an OperatingPointGradient."""
+        from .operating_point import OperatingPointGradient
+        ia, ib = op._leads
+        child, diode_rows = self._newton_companion(op.i_sat, op.n_vt, ia, ib, op.gmin)
+        ch = child._handle
+        with self._reference_errors():
+            r = ch.newton_gradient(diode_rows, op.i_sat, op.n_vt, op.gmin, op.source_rows, op.source_values, x, cotangent,
+                                   dense=not self.sparse, adjoints=adjoints)
+        _warn_singular(r["info"] > 0)
+        by_name = {name: r["sources"][cols].sum() for name, cols in (op.source_columns or {}).items()}
+        return OperatingPointGradient(self.netlist, r["grad"], op.diodes, r["i_sat"], r["n_vt"], r["gmin"], by_name,
+                                      r["info"], r["resid"], r["op_resid"], adjoint=r["adjoint"], timings=ch.timings(),
+                                      table=self.table, diode_i_sat=op.i_sat, diode_n_vt=op.n_vt)
 
     def _transient_dc_start(self, la, lb):
         """The DC operating point with every inductor a short, of the netlist's own source values: (x_0 [K+B], i_0 [L],

@@ -1064,6 +1064,49 @@ int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t
     return s;
 }
 
+int nodal_newton_gradient(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                          const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                          const double *x, const double *cotangent, double *grad_out, double *grad_isat_out,
+                          double *grad_nvt_out, double *grad_gmin_out, double *grad_sources_out, double *adjoint_out,
+                          double *resid_out, double *op_resid_out, int32_t *info_out) {
+    if (!h || ndiode < 0 || (ndiode > 0 && (!diode_rows || !i_sat || !n_vt)) || !info_out) return NODAL_E_INVALID;
+    if (!(gmin >= 0.0) || std::isinf(gmin))
+        return nodal_fail(h, NODAL_E_INVALID, "operating-point gradient: gmin must be finite and not negative");
+    if (!h->have_table || h->csr_only)
+        return nodal_fail(h, NODAL_E_INVALID, "operating-point gradient: no component table on the handle");
+    if (!h->have_numeric) return nodal_fail(h, NODAL_E_INVALID, "operating-point gradient: assemble_numeric not called");
+    if (h->ncomp > 0 && !grad_out) return nodal_fail(h, NODAL_E_INVALID, "operating-point gradient: no array for the result");
+    if (h->n > 0 && (!x || !cotangent))
+        return nodal_fail(h, NODAL_E_INVALID, "operating-point gradient: no operating point or no cotangent");
+    DeviceGuard g(h);
+    if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
+    nodal_poison_scratch(h);
+    h->tape_valid = false;  // (the node lists and the state buffers of a recorded transient are written over)
+    NODAL_TRY(sweep_prepare(h, 1, nsrc, src_rows, src_values));
+    h->amg_levels = 0;
+    h->last_batch_block = false;
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
+    double ms_matrix = 0.0, ms_symbolic = 0.0;
+    NewtonGradientOutputs out;
+    out.grad = grad_out;
+    out.grad_isat = grad_isat_out;
+    out.grad_nvt = grad_nvt_out;
+    out.grad_gmin = grad_gmin_out;
+    out.grad_sources = grad_sources_out;
+    out.adjoint = adjoint_out;
+    out.resid = resid_out;
+    out.op_resid = op_resid_out;
+    out.info = info_out;
+    const int s = newton_gradient_run(h, dense != 0, ndiode, diode_rows, i_sat, n_vt, gmin, nsrc, x, cotangent, out, &ms_matrix,
+                                      &ms_symbolic);
+    NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
+    NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
+    h->ms[0] = ms_matrix;
+    h->ms[1] = ms_symbolic;
+    h->ms[2] = elapsed(h, 0, 1);
+    return s;
+}
+
 int nodal_transient_gradient(nodal_handle h, int32_t dense, int32_t nprobe, const int32_t *probe_a, const int32_t *probe_b,
                              const double *wave_cot, double *grad_out, double *grad_sources_out, double *grad_x0_out,
                              double *adjoint_out, double *resid_out, int32_t *info_out) {

@@ -648,6 +648,22 @@ int newton_launch_linearise(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, c
                             double gmin, const double *vh, double *value, double *hist, double *gk, double *ik);
 int newton_launch_fill(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, double fill, double *value);
 
+// ---- gradients through the operating point (newton_gradient.hip): one transposed solve with J at the caller's x ----
+struct NewtonGradientOutputs {   // host arrays, each may be null except grad (with ncomp > 0) and info
+    double *grad = nullptr;                               // [ncomp], +0.0 in the diode rows
+    double *grad_isat = nullptr, *grad_nvt = nullptr;     // [nd]
+    double *grad_gmin = nullptr;                          // [1]
+    double *grad_sources = nullptr;                       // [nsrc]
+    double *adjoint = nullptr;                            // [n]
+    double *resid = nullptr, *op_resid = nullptr;         // [1] each: of the adjoint solve, of x as an operating point
+    int32_t *info = nullptr;                              // [1]
+};
+// the arguments are those of nodal_newton_gradient; the sources are those of the last sweep_prepare (one setting);
+// ms_matrix and ms_symbolic as newton_run's
+int newton_gradient_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, const double *isat, const double *nvt,
+                        double gmin, int32_t nsrc, const double *x, const double *cotangent, const NewtonGradientOutputs &out,
+                        double *ms_matrix, double *ms_symbolic);
+
 // ---- nonlinear transient analysis (transient_nl.hip): Newton's method inside every step of transient_run ----
 // nodal_transient_nl's further arguments, and the loop's state.  transient_run with `diodes` leaves the route and the
 // matrix work to step(): prepare() once before the first step (uploads, checks, node lists, row 0 of the diode probes),

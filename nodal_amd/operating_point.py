@@ -15,8 +15,16 @@ and the assembly's symbolic phase, the sparse LU's analysis and the multigrid hi
 the iterations and over later calls.  With the reference the only way to the same numbers is a host loop that rebuilds
 `Circuit(netlist with companion rows)` and solves it per iteration (reference nodal/nodal.py:306-336).
 
-`resolve_diodes`, `check_operating_point_arguments` and `companion_table` need no device, and `OperatingPoint` is a plain
-container that can be built from arrays.
+Gradients through the operating point.  At the answer F(x, p) = G(p) x + S i(S^T x; theta) - A(p) = 0, so a loss L(x) has
+dL/dp = -lambda^T dF/dp with J^T lambda = dL/dx, J = G + S diag(g(v)) S^T at v = S^T x: ONE linear solve with the matrix a
+Newton iteration assembles, linearised at the answer itself.  `OperatingPoint.gradient` hands the cotangent to
+`nodal_newton_gradient` (csrc/newton_gradient.hip) and returns an `OperatingPointGradient`: a number per component, two
+per diode (i_sat, n_vt), one for gmin and one per source named in the call.  The other routes are finite differences, two
+Newton runs per parameter, and `linearised().gradient(...)`, which answers another question: its x is the last Newton
+step without the history currents, and its companion resistors are constants.
+
+`resolve_diodes`, `check_operating_point_arguments`, `companion_table` and `check_cotangent` need no device, and
+`OperatingPoint` and `OperatingPointGradient` are plain containers that can be built from arrays.
 """
 
 import math
@@ -99,6 +107,16 @@ def companion_table(table, i_sat, n_vt, ia, ib, gmin=0.0):
     return table.with_rows_appended(types, values, ia, ib), np.arange(first, first + len(values), dtype=np.int64)
 
 
+def check_cotangent(cotangent, n):
+    """`cotangent` = dL/dx as float64 [n]; ValueError for another shape or entries that are not finite."""
+    cot = np.ascontiguousarray(cotangent, dtype=np.float64)
+    if cot.shape != (n,):
+        raise ValueError(f"cotangent must have shape ({n},), not {cot.shape}")
+    if not np.isfinite(cot).all():
+        raise ValueError("cotangent has entries that are not finite")
+    return cot
+
+
 ROUTES = {0: "dense", 1: "lu", 2: "multigrid", 3: "direct"}
 
 
@@ -131,10 +149,16 @@ class OperatingPoint:
     every diode there; converged; iterations; history (NewtonHistory); scaled_residual: that of the last iteration's
     linear solve; timings: nodal_last_timings of the call, [0] the host ms of the matrix work summed over the
     iterations, [1] the part of it that was symbolic (0.0: everything symbolic was kept), [2] the whole call.  With
-    keep_iterates: iterates [iterations, K+B], x_1 .. , and limited_voltages [iterations + 1, D], vh_0 .. ."""
+    keep_iterates: iterates [iterations, K+B], x_1 .. , and limited_voltages [iterations + 1, D], vh_0 .. .
+
+    What gradient() needs beside x is remembered when Circuit.operating_point makes the result: i_sat, n_vt [D] and
+    gmin of the diodes, source_rows / source_values (the table rows and the one value each of the sources named in the
+    call) and source_columns (name -> the entries of source_rows that carry it).  A result built from arrays alone
+    has None there and no circuit."""
 
     def __init__(self, x, diodes, voltages, currents, conductances, converged, iterations, history, timings=None,
-                 iterates=None, limited_voltages=None, circuit=None, leads=None):
+                 iterates=None, limited_voltages=None, circuit=None, leads=None, i_sat=None, n_vt=None, gmin=None,
+                 source_rows=None, source_values=None, source_columns=None):
         self.x = x
         self.diodes = list(diodes)
         self.voltages = voltages
@@ -148,10 +172,39 @@ class OperatingPoint:
         self.limited_voltages = limited_voltages
         self._circuit = circuit
         self._leads = leads
+        self.i_sat = i_sat
+        self.n_vt = n_vt
+        self.gmin = gmin
+        self.source_rows = source_rows
+        self.source_values = source_values
+        self.source_columns = source_columns
 
     @property
     def scaled_residual(self):
         return float(self.history.scaled_residual[-1]) if len(self.history) else float("nan")
+
+    def gradient(self, cotangent, adjoints=False):
+        """The gradient of a scalar loss L(x) through this operating point, by the adjoint method on the device
+        (nodal_newton_gradient): `cotangent` [K+B] = dL/dx.  One linear solve with J^T, J = G + S diag(g(v)) S^T the
+        matrix of a Newton iteration linearised at x ITSELF -- the run's last linearisation is at the limited voltages
+        one step behind, which with default tolerances is an error in the fourth digit -- and then a formula per
+        table row, two per diode and one for gmin.  Returns an OperatingPointGradient.
+
+        The gradient is taken at the circuit's values IN FORCE: after set_values() the matrix is the new one while x
+        is this result's, and `operating_point_residual` -- the scaled residual of x in the nonlinear equations, at
+        roundoff for a converged result -- is how a caller sees that they moved (or that the run had not converged).
+        ValueError for a cotangent of another shape or with entries that are not finite, for a result without its
+        circuit and for one whose x is not finite (a lost run).  Singular networks behave as in Circuit.gradient():
+        the dense path raises LinAlgError / UnconnectedCircuitError, the sparse path returns NaN with info > 0 and
+        warns once.  A second call repeats no symbolic work (`timings[1] == 0.0`) and gives the same bits; the circuit
+        itself is left as it was."""
+        if self._circuit is None or self.i_sat is None:
+            raise ValueError("this OperatingPoint was not made by Circuit.operating_point")
+        x = np.ascontiguousarray(self.x, dtype=np.float64)
+        cot = check_cotangent(cotangent, len(x))
+        if not np.isfinite(x).all():
+            raise ValueError("this operating point is not finite (a lost run): there is nothing to differentiate")
+        return self._circuit._operating_point_gradient(self, x, cot, adjoints)
 
     def linearised(self):
         """The small-signal circuit at this operating point: a Circuit on the same netlist whose table has every diode
@@ -171,3 +224,61 @@ class OperatingPoint:
         circuit = self._circuit
         types = np.full(len(g), c.TYPE_CODE["R"], dtype=np.uint8)
         return type(circuit)._clone_of(circuit, circuit.table.with_rows_appended(types, 1.0 / g, ia, ib))
+
+
+class OperatingPointGradient:
+    """Result of OperatingPoint.gradient: the implicit part of dL/dp, what the loss owes to the operating point's
+    dependence on the parameters.
+
+    values [ncomp]: dL / d value of table row i, in the order of `netlist.component_keys` (the array handed in may
+    carry the diodes' companion rows behind them: they are cut off); diodes: the names; i_sat, n_vt [D]: dL/di_sat and
+    dL/dn_vt of every diode; gmin: dL/dgmin (a float); source_values: name -> dL / d value of a source named in the
+    operating_point call (a float); adjoint [K+B] (lambda) or None; scaled_residual of the solve J^T lambda = dL/dx;
+    operating_point_residual: the scaled residual of x in the nonlinear equations at the circuit's values in force;
+    info: 0 solved, > 0 singular (sparse path: NaN); timings: nodal_last_timings of the call."""
+
+    def __init__(self, netlist, values, diodes, i_sat, n_vt, gmin, source_values, info, scaled_residual,
+                 operating_point_residual, adjoint=None, timings=None, table=None, diode_i_sat=None, diode_n_vt=None):
+        self._netlist = netlist
+        self.values = np.asarray(values, dtype=np.float64)[:len(netlist.component_keys)]
+        self.diodes = list(diodes)
+        self.i_sat = np.asarray(i_sat, dtype=np.float64)
+        self.n_vt = np.asarray(n_vt, dtype=np.float64)
+        self.gmin = float(gmin)
+        self.source_values = {name: float(value) for name, value in dict(source_values).items()}
+        self.info = int(info)
+        self.scaled_residual = float(scaled_residual)
+        self.operating_point_residual = float(operating_point_residual)
+        self.adjoint = adjoint
+        self.timings = timings
+        self._table = table
+        self._diode_i_sat, self._diode_n_vt = diode_i_sat, diode_n_vt
+        self._rows = None
+
+    @property
+    def names(self):
+        return list(self._netlist.component_keys)
+
+    def of(self, name):
+        """(dL/di_sat, dL/dn_vt) for a diode's name; dL / d value for a component's name -- one the netlist defines
+        more than once: the sum over its rows, as Gradient.of."""
+        if name in self.diodes:
+            d = self.diodes.index(name)
+            return float(self.i_sat[d]), float(self.n_vt[d])
+        if self._rows is None:
+            from .sweep import _row_map
+            self._rows = _row_map(self._netlist)
+        return float(self.values[self._rows[name]].sum())
+
+    @property
+    def normalized(self):
+        """(values * component value [ncomp], i_sat * dL/di_sat [D], n_vt * dL/dn_vt [D]): the change of the loss per
+        relative change of each parameter.  ValueError when the container was built without the diodes' parameters."""
+        if self._diode_i_sat is None or self._diode_n_vt is None:
+            raise ValueError("this OperatingPointGradient was built without the diodes' i_sat and n_vt")
+        if self._table is None:
+            from .circuit import Circuit
+            self._table = Circuit._lower(self._netlist)
+        value = np.asarray(self._table.value, dtype=np.float64)[:len(self.values)]
+        return (self.values * value, self.i_sat * np.asarray(self._diode_i_sat, dtype=np.float64),
+                self.n_vt * np.asarray(self._diode_n_vt, dtype=np.float64))
