@@ -33,10 +33,9 @@
 // ac_child takes which child it builds -- h->ac from the handle's own pattern and values, or h->ac_t from those of
 // h->adjoint, which holds G^T (B is symmetric, the stamps are the same) --, ac_child_values launches k_ac_values for
 // either, and ac_check_arguments / ac_sources_check / ac_sources_stamp are the argument checks and the small-signal
-// right-hand side.
-#include "table_rows.h"
-
-#include <chrono>
+// right-hand side.  ac_sweep.h declares these and what else the four small-signal analyses share: the upload of a call's
+// reactive elements (ac_upload_spec, below) and the ledger of residuals and singular frequencies (AcLedger).
+#include "ac_sweep.h"
 
 namespace {
 
@@ -119,10 +118,6 @@ __global__ __launch_bounds__(ATB) void k_ac_peak(int32_t K, int32_t freq, int fi
 __global__ __launch_bounds__(ATB) void k_ac_peak_root(int32_t K, double *__restrict__ peak2) {
     const int32_t i = blockIdx.x * ATB + threadIdx.x;
     if (i < K) peak2[i] = sqrt(peak2[i]);
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // Where a child keeps itself on the handle: h->ac, from h's own pattern and values, or h->ac_t, from those of h->adjoint.
@@ -315,7 +310,6 @@ int ac_child_values(nodal_ctx *h, bool transposed, double omega, const uint8_t *
 
 int ac_check_arguments(nodal_ctx *h, const char *what, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
                        const double *value, const int32_t *lead_a, const int32_t *lead_b) {
-    const int32_t K = h->K;
     auto finite_positive = [](double v) { return v > 0.0 && v - v == 0.0; };
     auto fail = [&](const char *text) { return nodal_fail(h, NODAL_E_INVALID, (std::string(what) + text).c_str()); };
     for (int32_t f = 0; f < nfreq; ++f)
@@ -323,9 +317,57 @@ int ac_check_arguments(nodal_ctx *h, const char *what, int32_t nfreq, const doub
     for (int64_t q = 0; q < nreact; ++q) {
         if (kind[q] > 1) return fail("a reactive element's kind is neither 0 (capacitor) nor 1 (inductor)");
         if (!finite_positive(value[q])) return fail("a reactive element's value is not finite and positive");
-        if (lead_a[q] < -1 || lead_a[q] >= K || lead_b[q] < -1 || lead_b[q] >= K) return fail("a reactive element's lead out of range");
+        NODAL_TRY(ac_check_pairs(h, what, "a reactive element's lead", 1, lead_a + q, lead_b + q));
         if (lead_a[q] == lead_b[q]) return fail("both leads of a reactive element on one node");
     }
+    return NODAL_OK;
+}
+
+int ac_check_pairs(nodal_ctx *h, const char *what, const char *noun, int64_t count, const int32_t *a, const int32_t *b) {
+    const int32_t K = h->K;
+    for (int64_t i = 0; i < count; ++i)
+        if (a[i] < -1 || a[i] >= K || b[i] < -1 || b[i] >= K)
+            return nodal_fail(h, NODAL_E_INVALID, (std::string(what) + noun + " out of range").c_str());
+    return NODAL_OK;
+}
+
+int ac_upload_spec(nodal_ctx *h, int64_t nreact, const uint8_t *kind, const double *value, const int32_t *lead_a,
+                   const int32_t *lead_b, std::initializer_list<AcIntList> lists, const double *extra, size_t nextra,
+                   AcSpec *spec) {
+    auto rounded = [](size_t words) { return (words + 15) & ~(size_t)15; };
+    auto up = [&](void *to, const void *from, size_t bytes) {
+        return bytes > 0 ? hipMemcpyAsync(to, from, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
+    };
+    const size_t rw = rounded((size_t)nreact), xw = rounded(nextra);
+    size_t list_words = 0;
+    for (const AcIntList &l : lists) list_words += rounded(l.second);
+    NODAL_HIP_TRY(h, h->ac_spec.reserve((rw + xw) * 8 + ((lead_a ? 2 * rw : 0) + list_words) * 4 + rw + 64));
+    spec->value = h->ac_spec.as<double>();
+    spec->extra = spec->value + rw;
+    int32_t *at = reinterpret_cast<int32_t *>(spec->extra + xw);
+    NODAL_HIP_TRY(h, up(spec->value, value, (size_t)nreact * 8));
+    if (lead_a) {
+        spec->lead_a = at;
+        spec->lead_b = at + rw;
+        at += 2 * rw;
+        NODAL_HIP_TRY(h, up(spec->lead_a, lead_a, (size_t)nreact * 4));
+        NODAL_HIP_TRY(h, up(spec->lead_b, lead_b, (size_t)nreact * 4));
+    }
+    spec->kind = reinterpret_cast<uint8_t *>(at + list_words);
+    NODAL_HIP_TRY(h, up(spec->kind, kind, (size_t)nreact));
+    NODAL_HIP_TRY(h, up(spec->extra, extra, nextra * 8));
+    int k = 0;
+    for (const AcIntList &l : lists) {
+        spec->list[k++] = at;
+        NODAL_HIP_TRY(h, up(at, l.first, l.second * 4));
+        at += rounded(l.second);
+    }
+    return NODAL_OK;
+}
+
+int ac_peak_root(nodal_ctx *h, int32_t K, double *peak2) {
+    k_ac_peak_root<<<groups_of(K, ATB), ATB, 0, h->stream>>>(K, peak2);
+    NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }
 
@@ -373,9 +415,7 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
 
     // ---- the arguments ----
     NODAL_TRY(ac_check_arguments(h, "ac sweep: ", nfreq, omega, nreact, kind, value, lead_a, lead_b));
-    for (int32_t p = 0; p < nprobe; ++p)
-        if (probe_a[p] < -1 || probe_a[p] >= K || probe_b[p] < -1 || probe_b[p] >= K)
-            return nodal_fail(h, NODAL_E_INVALID, "ac sweep: probe node out of range");
+    NODAL_TRY(ac_check_pairs(h, "ac sweep: ", "probe node", nprobe, probe_a, probe_b));
     for (int32_t t = 0; t < ncur; ++t)
         if (cur_index[t] < 0 || cur_index[t] >= nreact)
             return nodal_fail(h, NODAL_E_INVALID, "ac sweep: current probe outside the reactive elements");
@@ -383,14 +423,7 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     if (nfreq == 0) return NODAL_OK;
 
     const int32_t nkeep = (keep_every > 0 && x_out) ? nfreq / keep_every : 0;
-    std::vector<double> resid_own(resid_out ? 0 : (size_t)nfreq);
-    std::vector<int32_t> info_own(info_out ? 0 : (size_t)nfreq);
-    double *resid = resid_out ? resid_out : resid_own.data();
-    int32_t *info = info_out ? info_out : info_own.data();
-    for (int32_t f = 0; f < nfreq; ++f) {
-        info[f] = 0;
-        resid[f] = 0.0;
-    }
+    AcLedger ledger(h, nfreq, 1, resid_out, info_out);
     const size_t wave_words = (size_t)nfreq * nprobe * 2, cur_words = (size_t)nfreq * ncur * 2;
     if (n == 0) {  // (no unknowns: every lead is ground, nothing is driven)
         if (wave_out)
@@ -402,24 +435,9 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     // ---- once per call: the child's pattern, the elements and probes up, the right-hand side, the buffers ----
     nodal_ctx *c = nullptr;
     NODAL_TRY(ac_child(h, false, nreact, kind, lead_a, lead_b, ms_analysis, &c));
-    // ac_spec: values [nreact] doubles | leads a | leads b | probed elements | probe a | probe b | kinds (bytes)
-    const size_t rw = ((size_t)nreact + 15) & ~(size_t)15, cw = ((size_t)ncur + 15) & ~(size_t)15, pw = ((size_t)nprobe + 15) & ~(size_t)15;
-    NODAL_HIP_TRY(h, h->ac_spec.reserve(rw * 8 + (2 * rw + cw + 2 * pw) * 4 + rw + 64));
-    double *val_dev = h->ac_spec.as<double>();
-    int32_t *a_dev = reinterpret_cast<int32_t *>(val_dev + rw), *b_dev = a_dev + rw, *cidx_dev = b_dev + rw, *pa_dev = cidx_dev + cw,
-            *pb_dev = pa_dev + pw;
-    uint8_t *kind_dev = reinterpret_cast<uint8_t *>(pb_dev + pw);
-    if (nreact > 0) {
-        NODAL_HIP_TRY(h, hipMemcpyAsync(val_dev, value, (size_t)nreact * 8, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(a_dev, lead_a, (size_t)nreact * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(b_dev, lead_b, (size_t)nreact * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(kind_dev, kind, (size_t)nreact, hipMemcpyHostToDevice, st));
-    }
-    if (ncur > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(cidx_dev, cur_index, (size_t)ncur * 4, hipMemcpyHostToDevice, st));
-    if (nprobe > 0) {
-        NODAL_HIP_TRY(h, hipMemcpyAsync(pa_dev, probe_a, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(pb_dev, probe_b, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
-    }
+    AcSpec spec;  // the elements with their leads; lists: the probed elements, probe a, probe b
+    NODAL_TRY(ac_upload_spec(h, nreact, kind, value, lead_a, lead_b,
+                             {{cur_index, (size_t)ncur}, {probe_a, (size_t)nprobe}, {probe_b, (size_t)nprobe}}, nullptr, 0, &spec));
     // ac_vec: right-hand side | solution | defect | correction (2n each) | the judge's norms
     NODAL_HIP_TRY(h, h->ac_vec.reserve((size_t)4 * n2 * 8 + 5 * SLU_MULTI * 8 + 256));
     double *bvec = h->ac_vec.as<double>(), *xk = bvec + n2, *rvec = xk + n2, *dvec = rvec + n2, *norms = dvec + n2;
@@ -428,6 +446,7 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     NODAL_HIP_TRY(h, h->ac_out.reserve((wave_words + cur_words + (size_t)nfreq + 2 * peak_words + 2) * 8 + 64));
     double *wave_dev = h->ac_out.as<double>(), *cur_dev = wave_dev + wave_words, *resid_dev = cur_dev + cur_words,
            *peak_dev = resid_dev + nfreq;
+    ledger.resid_dev = resid_dev;
     int32_t *peak_freq_dev = reinterpret_cast<int32_t *>(peak_dev + peak_words);
     if (want_peak) NODAL_HIP_TRY(h, hipMemsetAsync(peak_dev, 0xFF, peak_words * 12, st));  // (NaN and -1 until a frequency is taken in)
     double *ring = nullptr;
@@ -439,7 +458,6 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     NODAL_WAIT_STREAM(h, st);  // (the elements and probes are the caller's)
 
     // ---- the frequencies ----
-    std::vector<uint8_t> on_host((size_t)nfreq, 0);  // the frequency's residual was read back already (the sparse LU route)
     uint64_t lu_epoch = 0;  // (never the child's numeric_epoch: every frequency is factored anew)
     bool peak_first = true;
     int32_t ring_fill = 0, ring_base = 0;  // kept solutions in the ring, and the index of the first of them
@@ -453,7 +471,7 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     };
     for (int32_t f = 0; f < nfreq; ++f) {
         const double w = omega[f];
-        NODAL_TRY(ac_child_values(h, false, w, kind_dev, val_dev));
+        NODAL_TRY(ac_child_values(h, false, w, spec.kind, spec.value));
         // the solve, on the child as both handle and solve context: every size read is 2n
         TransientSolver ts;
         ts.s = c;
@@ -466,33 +484,29 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
         double ms_f = 0.0;
         int32_t inf = 0, it = 0;
         NODAL_TRY(nodal_lift_error(h, c, transient_solver_begin(c, ts, dense, 1, &dead, &ms_f)));
-        if (ts.route == TR_ROUTE_LU) {
-            const double ms_a = slu_analysis_ms(c);
-            *ms_analysis += ms_a;
-            *ms_factor += ms_f > ms_a ? ms_f - ms_a : 0.0;
-        }
+        if (ts.route == TR_ROUTE_LU) ac_add_factor_time(c, ms_f, ms_analysis, ms_factor);
         if (!dead) {
             double ms_none = 0.0;
-            NODAL_TRY(nodal_lift_error(h, c, transient_solver_step(c, ts, bvec, xk, &inf, &it, &resid[f], &judged, &ms_none)));
+            NODAL_TRY(nodal_lift_error(h, c, transient_solver_step(c, ts, bvec, xk, &inf, &it, &ledger.resid[f], &judged, &ms_none)));
             if (inf > 0 && dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
         }
         const bool kept = nkeep > 0 && (f + 1) % keep_every == 0;
-        if (dead || inf > 0) {  // this frequency alone: NaN in its rows, the later ones are solved
-            info[f] = 1;
+        if (dead || inf > 0) {
+            ledger.mark_dead(f);
             if (kept) {
                 NODAL_TRY(nodal_lift_error(h, c, dense_fill_nan(c, ring + (size_t)ring_fill * n2, n2)));
                 if (++ring_fill == std::min<int32_t>(RING, nkeep)) NODAL_TRY(flush_ring());
             }
             continue;
         }
-        on_host[(size_t)f] = judged;
+        ledger.on_host[(size_t)f] = judged;
         if (!judged) NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + f, norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
         // what the caller asked for of x(omega)
         if (nprobe > 0)
-            k_ac_probe<<<groups_of(nprobe, ATB), ATB, 0, st>>>(nprobe, pa_dev, pb_dev, xk,
+            k_ac_probe<<<groups_of(nprobe, ATB), ATB, 0, st>>>(nprobe, spec.list[1], spec.list[2], xk,
                                                               reinterpret_cast<double2 *>(wave_dev) + (size_t)f * nprobe);
         if (ncur > 0)
-            k_ac_current<<<groups_of(ncur, ATB), ATB, 0, st>>>(ncur, w, cidx_dev, kind_dev, val_dev, a_dev, b_dev, xk,
+            k_ac_current<<<groups_of(ncur, ATB), ATB, 0, st>>>(ncur, w, spec.list[0], spec.kind, spec.value, spec.lead_a, spec.lead_b, xk,
                                                               reinterpret_cast<double2 *>(cur_dev) + (size_t)f * ncur);
         if (want_peak) {
             k_ac_peak<<<groups_of(K, ATB), ATB, 0, st>>>(K, f, peak_first ? 1 : 0, xk, peak_dev, peak_freq_dev);
@@ -507,29 +521,15 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
     NODAL_TRY(flush_ring());
 
     // ---- after the last frequency: everything else comes down once ----
-    if (want_peak && !peak_first) {
-        k_ac_peak_root<<<groups_of(K, ATB), ATB, 0, st>>>(K, peak_dev);
-        NODAL_HIP_TRY(h, hipGetLastError());
-    }
-    std::vector<double> resid_dn((size_t)nfreq);
+    if (want_peak && !peak_first) NODAL_TRY(ac_peak_root(h, K, peak_dev));
     if (wave_out && wave_words > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(wave_out, wave_dev, wave_words * 8, hipMemcpyDeviceToHost, st));
     if (cur_out && cur_words > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(cur_out, cur_dev, cur_words * 8, hipMemcpyDeviceToHost, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dn.data(), resid_dev, (size_t)nfreq * 8, hipMemcpyDeviceToHost, st));
     if (want_peak) {
         if (peak_out) NODAL_HIP_TRY(h, hipMemcpyAsync(peak_out, peak_dev, (size_t)K * 8, hipMemcpyDeviceToHost, st));
         if (peak_freq_out) NODAL_HIP_TRY(h, hipMemcpyAsync(peak_freq_out, peak_freq_dev, (size_t)K * 4, hipMemcpyDeviceToHost, st));
     }
-    NODAL_WAIT_STREAM(h, st);
-    for (int32_t f = 0; f < nfreq; ++f) {
-        if (info[f] == 0) {
-            if (!on_host[(size_t)f]) resid[f] = resid_dn[(size_t)f];
-            continue;
-        }
-        resid[f] = nan;
-        if (wave_out)
-            for (int32_t p = 0; p < 2 * nprobe; ++p) wave_out[(size_t)f * nprobe * 2 + p] = nan;
-        if (cur_out)
-            for (int32_t t = 0; t < 2 * ncur; ++t) cur_out[(size_t)f * ncur * 2 + t] = nan;
-    }
-    return NODAL_OK;
+    return ledger.finish([&](int32_t f) {
+        if (wave_out) std::fill_n(wave_out + (size_t)f * nprobe * 2, 2 * (size_t)nprobe, nan);
+        if (cur_out) std::fill_n(cur_out + (size_t)f * ncur * 2, 2 * (size_t)ncur, nan);
+    });
 }

@@ -42,7 +42,7 @@
 // floating-point atomics anywhere: a repeated call gives the same bits.  Phasors, source terms and residuals come down
 // once after the last frequency, the gradients once.  The handle itself -- solution, table, G, A, tape, hierarchy,
 // factors, the kept work of the other small-signal analyses -- is only read.
-#include "table_rows.h"
+#include "ac_sweep.h"
 
 namespace {
 
@@ -209,23 +209,14 @@ int ac_gradient_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega
 
     // ---- the arguments ----
     NODAL_TRY(ac_check_arguments(h, "ac gradient: ", nfreq, omega, nreact, kind, value, lead_a, lead_b));
-    for (int32_t p = 0; p < nprobe; ++p)
-        if (probe_a[p] < -1 || probe_a[p] >= K || probe_b[p] < -1 || probe_b[p] >= K)
-            return nodal_fail(h, NODAL_E_INVALID, "ac gradient: probe node out of range");
+    NODAL_TRY(ac_check_pairs(h, "ac gradient: ", "probe node", nprobe, probe_a, probe_b));
     const size_t wave_words = (size_t)nfreq * nprobe * 2, src_words = (size_t)nfreq * nsrc * 2;
     for (size_t t = 0; t < wave_words; ++t)
         if (!(wave_cot[t] - wave_cot[t] == 0.0)) return nodal_fail(h, NODAL_E_INVALID, "ac gradient: a cotangent that is not finite");
     NODAL_TRY(ac_sources_check(h, "ac gradient: ", "source row", nsrc, src_rows, src_re, src_im));  // (waits)
 
     const int32_t nkeep = (keep_every > 0 && adjoint_out) ? nfreq / keep_every : 0;
-    std::vector<double> resid_own(resid_out ? 0 : (size_t)2 * nfreq);
-    std::vector<int32_t> info_own(info_out ? 0 : (size_t)nfreq);
-    double *resid = resid_out ? resid_out : resid_own.data();
-    int32_t *info = info_out ? info_out : info_own.data();
-    for (int32_t f = 0; f < nfreq; ++f) {
-        info[f] = 0;
-        resid[2 * f] = resid[2 * f + 1] = 0.0;
-    }
+    AcLedger ledger(h, nfreq, 2, resid_out, info_out);
     // (what a call without frequencies, probes or unknowns leaves: nothing depends on anything)
     if (grad_out)
         for (int64_t i = 0; i < ncomp; ++i) grad_out[i] = 0.0;
@@ -250,22 +241,12 @@ int ac_gradient_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega
     if (transposed) NODAL_TRY(ac_child(h, true, nreact, kind, lead_a, lead_b, &ms_t, &ct));
     *ms_analysis = ms_f + ms_t;
     NODAL_TRY(sens_cross_list(h));
-    // ag_spec: values [nreact] doubles | cotangents [nfreq][nprobe][2] | leads a | leads b | probe a | probe b | kinds (bytes)
-    const size_t rw = ((size_t)nreact + 15) & ~(size_t)15, pw = ((size_t)nprobe + 15) & ~(size_t)15;
-    NODAL_HIP_TRY(h, h->ag_spec.reserve((rw + wave_words) * 8 + (2 * rw + 2 * pw) * 4 + rw + 64));
-    double *val_dev = h->ag_spec.as<double>(), *cot_dev = val_dev + rw;
-    int32_t *ea_dev = reinterpret_cast<int32_t *>(cot_dev + wave_words), *eb_dev = ea_dev + rw, *pa_dev = eb_dev + rw,
-            *pb_dev = pa_dev + pw;
-    uint8_t *kind_dev = reinterpret_cast<uint8_t *>(pb_dev + pw);
-    if (nreact > 0) {
-        NODAL_HIP_TRY(h, hipMemcpyAsync(val_dev, value, (size_t)nreact * 8, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(ea_dev, lead_a, (size_t)nreact * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(eb_dev, lead_b, (size_t)nreact * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(kind_dev, kind, (size_t)nreact, hipMemcpyHostToDevice, st));
-    }
-    NODAL_HIP_TRY(h, hipMemcpyAsync(cot_dev, wave_cot, wave_words * 8, hipMemcpyHostToDevice, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(pa_dev, probe_a, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(pb_dev, probe_b, (size_t)nprobe * 4, hipMemcpyHostToDevice, st));
+    AcSpec spec;  // the elements with their leads; probe a, probe b; the cotangents [nfreq][nprobe][2]
+    NODAL_TRY(ac_upload_spec(h, nreact, kind, value, lead_a, lead_b, {{probe_a, (size_t)nprobe}, {probe_b, (size_t)nprobe}}, wave_cot,
+                             wave_words, &spec));
+    const double *val_dev = spec.value, *cot_dev = spec.extra;
+    const uint8_t *kind_dev = spec.kind;
+    const int32_t *ea_dev = spec.lead_a, *eb_dev = spec.lead_b, *pa_dev = spec.list[0], *pb_dev = spec.list[1];
     // ag_vec: the forward right-hand side | x_f | y_f (2n each)
     NODAL_HIP_TRY(h, h->ag_vec.reserve((size_t)3 * n2 * 8 + 64));
     double *svec = h->ag_vec.as<double>(), *xk = svec + n2, *yk = xk + n2;
@@ -274,6 +255,7 @@ int ac_gradient_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega
     NODAL_HIP_TRY(h, h->ag_out.reserve(out_words * 8 + 64));
     double *wave_dev = h->ag_out.as<double>(), *gsrc_dev = wave_dev + wave_words, *resid_dev = gsrc_dev + src_words,
            *grad_dev = resid_dev + 2 * (size_t)nfreq, *greact_dev = grad_dev + ncomp;
+    ledger.resid_dev = resid_dev;
     NODAL_HIP_TRY(h, hipMemsetAsync(wave_dev, 0, out_words * 8, st));
     NODAL_TRY(ac_sources_stamp(h, nsrc, svec));
     NODAL_WAIT_STREAM(h, st);  // (the elements, probes and cotangents are the caller's)
@@ -293,8 +275,8 @@ int ac_gradient_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega
     const int32_t *rows_dev = h->sw_rows.as<int32_t>();  // (ac_sources_check left the driven rows there)
 
     // ---- the frequencies ----
-    std::vector<uint8_t> on_host((size_t)2 * nfreq, 0);  // the column's residual was read back already (the sparse LU route)
-    bool any_dead = false;
+    double *resid = ledger.resid;
+    uint8_t *on_host = ledger.on_host.data();
     for (int32_t f = 0; f < nfreq; ++f) {
         const double w = omega[f];
         const size_t at = (size_t)2 * f;
@@ -304,20 +286,19 @@ int ac_gradient_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega
         bool dead = false;
         client.first = 0;
         if (!transposed) {  // A^T = A: s and c_f through one factorisation
-            NODAL_TRY(ac_block_frequency(h, cf, dense, 2, client, resid + at, on_host.data() + at, resid_dev + at, &dead, work,
+            NODAL_TRY(ac_block_frequency(h, cf, dense, 2, client, resid + at, on_host + at, resid_dev + at, &dead, work,
                                          ms_analysis, ms_factor));
         } else {
-            NODAL_TRY(ac_block_frequency(h, cf, dense, 1, client, resid + at, on_host.data() + at, resid_dev + at, &dead, work,
+            NODAL_TRY(ac_block_frequency(h, cf, dense, 1, client, resid + at, on_host + at, resid_dev + at, &dead, work,
                                          ms_analysis, ms_factor));
             if (!dead) {
                 client.first = 1;
-                NODAL_TRY(ac_block_frequency(h, ct, dense, 1, client, resid + at + 1, on_host.data() + at + 1, resid_dev + at + 1,
+                NODAL_TRY(ac_block_frequency(h, ct, dense, 1, client, resid + at + 1, on_host + at + 1, resid_dev + at + 1,
                                              &dead, work, ms_analysis, ms_factor));
             }
         }
-        if (dead) {  // this frequency alone: NaN in its rows, the later ones are solved; the sums are void
-            info[f] = 1;
-            any_dead = true;
+        if (dead) {  // (and the sums over the frequencies are void: below)
+            ledger.mark_dead(f);
             continue;
         }
         // the table pass on the finished (x_f, y_f)
@@ -345,30 +326,18 @@ int ac_gradient_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega
     }
 
     // ---- after the last frequency: everything else comes down once ----
-    std::vector<double> resid_dn((size_t)2 * nfreq);
     if (wave_out) NODAL_HIP_TRY(h, hipMemcpyAsync(wave_out, wave_dev, wave_words * 8, hipMemcpyDeviceToHost, st));
     if (grad_sources_out && src_words > 0)
         NODAL_HIP_TRY(h, hipMemcpyAsync(grad_sources_out, gsrc_dev, src_words * 8, hipMemcpyDeviceToHost, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dn.data(), resid_dev, (size_t)2 * nfreq * 8, hipMemcpyDeviceToHost, st));
     if (grad_out && ncomp > 0) NODAL_HIP_TRY(h, hipMemcpyAsync(grad_out, grad_dev, (size_t)ncomp * 8, hipMemcpyDeviceToHost, st));
     if (grad_react_out && nreact > 0)
         NODAL_HIP_TRY(h, hipMemcpyAsync(grad_react_out, greact_dev, (size_t)nreact * 8, hipMemcpyDeviceToHost, st));
-    NODAL_WAIT_STREAM(h, st);
-    for (int32_t f = 0; f < nfreq; ++f) {
-        if (info[f] == 0) {
-            for (size_t t = (size_t)2 * f; t < (size_t)2 * f + 2; ++t)
-                if (!on_host[t]) resid[t] = resid_dn[t];
-            continue;
-        }
-        resid[2 * f] = resid[2 * f + 1] = nan;
-        if (wave_out)
-            for (int32_t p = 0; p < 2 * nprobe; ++p) wave_out[(size_t)f * nprobe * 2 + p] = nan;
-        if (grad_sources_out)
-            for (int32_t j = 0; j < 2 * nsrc; ++j) grad_sources_out[(size_t)f * nsrc * 2 + j] = nan;
-        if (nkeep > 0 && (f + 1) % keep_every == 0)
-            for (int64_t t = 0; t < n2; ++t) adjoint_out[(size_t)((f + 1) / keep_every - 1) * n2 + t] = nan;
-    }
-    if (any_dead) {  // (a sum over a list with a hole in it is none: the transient gradient's convention)
+    NODAL_TRY(ledger.finish([&](int32_t f) {
+        if (wave_out) std::fill_n(wave_out + (size_t)f * nprobe * 2, 2 * (size_t)nprobe, nan);
+        if (grad_sources_out) std::fill_n(grad_sources_out + (size_t)f * nsrc * 2, 2 * (size_t)nsrc, nan);
+        if (nkeep > 0 && (f + 1) % keep_every == 0) std::fill_n(adjoint_out + (size_t)((f + 1) / keep_every - 1) * n2, (size_t)n2, nan);
+    }));
+    if (ledger.any_dead()) {  // (a sum over a list with a hole in it is none: the transient gradient's convention)
         if (grad_out)
             for (int64_t i = 0; i < ncomp; ++i) grad_out[i] = nan;
         if (grad_react_out)

@@ -33,11 +33,10 @@
 // repeated call gives the same bits.  The handle itself -- solution, table, G, A, tape, hierarchy, factors -- is only read.
 //
 // The block loop is not multi_rhs_solve's LU branch called on the child: that driver's size thresholds would send
-// 2n = 290 to the dense LU, and its present callers compare bits.  ac_block_frequency takes a MultiRhsClient, so the
-// noise analysis could hand its outputs to it as well.
-#include "table_rows.h"
+// 2n = 290 to the dense LU, and its present callers compare bits.  ac_block_frequency takes a MultiRhsClient: the AC
+// gradient hands its two columns to it, and the noise analysis its outputs to the dense part, ac_block_dense.
+#include "ac_sweep.h"
 
-#include <chrono>
 
 namespace {
 
@@ -161,14 +160,6 @@ __global__ __launch_bounds__(PTB) void k_acport_merge(int32_t K, int32_t freq, i
         peak_freq[i] = freq;
     }
 }
-__global__ __launch_bounds__(PTB) void k_acport_peak_root(int32_t K, double *__restrict__ peak2) {
-    const int32_t i = blockIdx.x * PTB + threadIdx.x;
-    if (i < K) peak2[i] = sqrt(peak2[i]);
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 // the block loop's client: the columns are the ports' unit injections, a finished block is read at the port nodes and,
 // when peaks are asked for, taken into the frequency's peaks
@@ -206,52 +197,11 @@ struct AcPortClient final : MultiRhsClient {
     void all_singular(int32_t) override {}  // (ac_ports_run fills the frequency's rows from info)
 };
 
-}  // namespace
-
-int ac_block_frequency(nodal_ctx *h, nodal_ctx *c, bool dense, int32_t count, MultiRhsClient &client, double *resid_host,
-                       uint8_t *on_host, double *resid_dev, bool *dead, int64_t *work, double *ms_analysis, double *ms_factor) {
+// The sparse LU part of the block loop, factored once for every column of the frequency.
+int block_sparse(nodal_ctx *h, nodal_ctx *c, int32_t count, MultiRhsClient &client, double *resid_host, uint8_t *on_host,
+                 bool *dead, int64_t *work, double *ms_analysis, double *ms_factor) {
     const int64_t n2 = c->n;
     hipStream_t st = h->stream;  // (c shares it: one ordered timeline)
-    *dead = false;
-    if (count <= 0 || n2 <= 0) return NODAL_OK;
-
-    if (n2 <= 64 || dense) {
-        // one LU per chunk of up to 512 columns: they are extra right-hand-side columns of the augmented panel
-        // ap_vec: the right-hand sides of a group, kept for the judgement [16][2n] | solutions [chunk][2n] | the norms
-        const int32_t chunk = std::min<int32_t>(count, DENSE_CHUNK);
-        NODAL_HIP_TRY(h, h->ap_vec.reserve((size_t)(NCOLS + chunk) * n2 * 8 + 5 * SLU_MULTI * 8 + 256));
-        double *bblk = h->ap_vec.as<double>(), *xs = bblk + (size_t)NCOLS * n2, *norms = xs + (size_t)chunk * n2;
-        const int64_t lda = dense_lda(n2);
-        for (int32_t q0 = 0; q0 < count; q0 += chunk) {
-            const int32_t width = std::min<int32_t>(chunk, count - q0);
-            NODAL_HIP_TRY(h, c->dense.reserve((size_t)lda * (size_t)(n2 + width) * 8 + 64));
-            NODAL_TRY(nodal_lift_error(h, c, csr_to_dense(c, c->dense.as<double>(), lda)));
-            double *cols = c->dense.as<double>() + n2 * lda;
-            NODAL_HIP_TRY(h, hipMemsetAsync(cols, 0, (size_t)lda * width * 8, st));
-            for (int32_t g0 = 0; g0 < width; g0 += NCOLS)
-                NODAL_TRY(client.build(q0 + g0, std::min<int32_t>(NCOLS, width - g0), cols + (int64_t)g0 * lda, 1, lda));
-            int32_t inf = 0;
-            NODAL_TRY(nodal_lift_error(h, c, dense_factor_solve_multi(c, width, xs, n2, &inf)));
-            ++work[0];
-            if (inf > 0) {
-                if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
-                *dead = true;
-                return NODAL_OK;
-            }
-            for (int32_t g0 = 0; g0 < width; g0 += NCOLS) {  // every group of sixteen is judged
-                const int k = std::min<int32_t>(NCOLS, width - g0);
-                const double *x = xs + (size_t)g0 * n2;
-                NODAL_HIP_TRY(h, hipMemsetAsync(bblk, 0, (size_t)k * n2 * 8, st));
-                NODAL_TRY(client.build(q0 + g0, k, bblk, 1, n2));
-                NODAL_TRY(nodal_lift_error(h, c, csr_judge_block(c, x, bblk, 1, n2, k, norms)));
-                NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + q0 + g0, norms + 4 * SLU_MULTI, (size_t)k * 8, hipMemcpyDeviceToDevice, st));
-                NODAL_TRY(client.hand_over(q0 + g0, k, x, 1, n2, nullptr));
-            }
-        }
-        return NODAL_OK;
-    }
-
-    // The sparse LU, factored once for every column of the frequency.
     // ap_vec: the blocks B, X, R, D interleaved by row [2n][16] | one right-hand side [2n] | the norms
     const size_t blk = (size_t)n2 * NCOLS;
     NODAL_HIP_TRY(h, h->ap_vec.reserve((4 * blk + (size_t)n2) * 8 + 5 * SLU_MULTI * 8 + 256));
@@ -261,10 +211,8 @@ int ac_block_frequency(nodal_ctx *h, nodal_ctx *c, bool dense, int32_t count, Mu
         int32_t inf = 0;
         NODAL_TRY(nodal_lift_error(h, c, slu_factor(c, &inf)));
         NODAL_WAIT_STREAM(h, st);
-        const double ms = ms_since(t0), ms_a = slu_analysis_ms(c);
+        ac_add_factor_time(c, ms_since(t0), ms_analysis, ms_factor);
         ++work[0];
-        *ms_analysis += ms_a;
-        *ms_factor += ms > ms_a ? ms - ms_a : 0.0;
         if (inf > 0) {
             *dead = true;
             return NODAL_OK;
@@ -333,6 +281,55 @@ int ac_block_frequency(nodal_ctx *h, nodal_ctx *c, bool dense, int32_t count, Mu
     return NODAL_OK;
 }
 
+}  // namespace
+
+int ac_block_dense(nodal_ctx *h, nodal_ctx *c, bool dense, int32_t count, int32_t build_cols, MultiRhsClient &client,
+                   double *resid_dev, bool *dead, int64_t *work) {
+    const int64_t n2 = c->n;
+    hipStream_t st = h->stream;  // (c shares it: one ordered timeline)
+    // one LU per chunk of up to 512 columns: they are extra right-hand-side columns of the augmented panel
+    // ap_vec: the right-hand sides of a group, kept for the judgement [16][2n] | solutions [chunk][2n] | the norms
+    const int32_t chunk = std::min<int32_t>(count, DENSE_CHUNK);
+    NODAL_HIP_TRY(h, h->ap_vec.reserve((size_t)(NCOLS + chunk) * n2 * 8 + 5 * SLU_MULTI * 8 + 256));
+    double *bblk = h->ap_vec.as<double>(), *xs = bblk + (size_t)NCOLS * n2, *norms = xs + (size_t)chunk * n2;
+    const int64_t lda = dense_lda(n2);
+    for (int32_t q0 = 0; q0 < count; q0 += chunk) {
+        const int32_t width = std::min<int32_t>(chunk, count - q0);
+        NODAL_HIP_TRY(h, c->dense.reserve((size_t)lda * (size_t)(n2 + width) * 8 + 64));
+        NODAL_TRY(nodal_lift_error(h, c, csr_to_dense(c, c->dense.as<double>(), lda)));
+        double *cols = c->dense.as<double>() + n2 * lda;
+        NODAL_HIP_TRY(h, hipMemsetAsync(cols, 0, (size_t)lda * width * 8, st));
+        for (int32_t g0 = 0; g0 < width; g0 += build_cols)
+            NODAL_TRY(client.build(q0 + g0, std::min<int32_t>(build_cols, width - g0), cols + (int64_t)g0 * lda, 1, lda));
+        int32_t inf = 0;
+        NODAL_TRY(nodal_lift_error(h, c, dense_factor_solve_multi(c, width, xs, n2, &inf)));
+        ++work[0];
+        if (inf > 0) {
+            if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+            *dead = true;
+            return NODAL_OK;
+        }
+        for (int32_t g0 = 0; g0 < width; g0 += NCOLS) {  // every group of sixteen is judged
+            const int k = std::min<int32_t>(NCOLS, width - g0);
+            const double *x = xs + (size_t)g0 * n2;
+            NODAL_HIP_TRY(h, hipMemsetAsync(bblk, 0, (size_t)k * n2 * 8, st));
+            NODAL_TRY(client.build(q0 + g0, k, bblk, 1, n2));
+            NODAL_TRY(nodal_lift_error(h, c, csr_judge_block(c, x, bblk, 1, n2, k, norms)));
+            NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + q0 + g0, norms + 4 * SLU_MULTI, (size_t)k * 8, hipMemcpyDeviceToDevice, st));
+            NODAL_TRY(client.hand_over(q0 + g0, k, x, 1, n2, nullptr));
+        }
+    }
+    return NODAL_OK;
+}
+
+int ac_block_frequency(nodal_ctx *h, nodal_ctx *c, bool dense, int32_t count, MultiRhsClient &client, double *resid_host,
+                       uint8_t *on_host, double *resid_dev, bool *dead, int64_t *work, double *ms_analysis, double *ms_factor) {
+    *dead = false;
+    if (count <= 0 || c->n <= 0) return NODAL_OK;
+    if (c->n <= 64 || dense) return ac_block_dense(h, c, dense, count, NCOLS, client, resid_dev, dead, work);
+    return block_sparse(h, c, count, client, resid_host, on_host, dead, work, ms_analysis, ms_factor);
+}
+
 int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
                  const double *value, const int32_t *lead_a, const int32_t *lead_b, int32_t nports, const int32_t *ia,
                  const int32_t *ib, double *z_out, double *node_peak_out, int32_t *node_peak_port_out,
@@ -348,18 +345,11 @@ int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, i
 
     // ---- the arguments ----
     NODAL_TRY(ac_check_arguments(h, "ac ports: ", nfreq, omega, nreact, kind, value, lead_a, lead_b));
-    for (int32_t q = 0; q < nports; ++q)
-        if (ia[q] < -1 || ia[q] >= K || ib[q] < -1 || ib[q] >= K)
-            return nodal_fail(h, NODAL_E_INVALID, "ac ports: port node out of range");
+    NODAL_TRY(ac_check_pairs(h, "ac ports: ", "port node", nports, ia, ib));
     if (nfreq == 0 || nports == 0) return NODAL_OK;
 
     const size_t cells = (size_t)nfreq * nports, zwords = cells * (size_t)nports * 2;
-    std::vector<double> resid_own(resid_out ? 0 : cells);
-    std::vector<int32_t> info_own(info_out ? 0 : (size_t)nfreq);
-    double *resid = resid_out ? resid_out : resid_own.data();
-    int32_t *info = info_out ? info_out : info_own.data();
-    for (int32_t f = 0; f < nfreq; ++f) info[f] = 0;
-    for (size_t t = 0; t < cells; ++t) resid[t] = 0.0;
+    AcLedger ledger(h, nfreq, (size_t)nports, resid_out, info_out);
     if (n == 0) {  // (no unknowns: every lead is ground, nothing is seen)
         if (z_out)
             for (size_t t = 0; t < zwords; ++t) z_out[t] = 0.0;
@@ -370,23 +360,15 @@ int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, i
     // ---- once per call: the child, the elements and ports up, the buffers ----
     nodal_ctx *c = nullptr;
     NODAL_TRY(ac_child(h, false, nreact, kind, lead_a, lead_b, ms_analysis, &c));
-    // ap_spec: values [nreact] doubles | port a | port b | kinds (bytes)
-    const size_t rw = ((size_t)nreact + 15) & ~(size_t)15, pw = ((size_t)nports + 15) & ~(size_t)15;
-    NODAL_HIP_TRY(h, h->ap_spec.reserve(rw * 8 + 2 * pw * 4 + rw + 64));
-    double *val_dev = h->ap_spec.as<double>();
-    int32_t *ia_dev = reinterpret_cast<int32_t *>(val_dev + rw), *ib_dev = ia_dev + pw;
-    uint8_t *kind_dev = reinterpret_cast<uint8_t *>(ib_dev + pw);
-    if (nreact > 0) {
-        NODAL_HIP_TRY(h, hipMemcpyAsync(val_dev, value, (size_t)nreact * 8, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(kind_dev, kind, (size_t)nreact, hipMemcpyHostToDevice, st));
-    }
-    NODAL_HIP_TRY(h, hipMemcpyAsync(ia_dev, ia, (size_t)nports * 4, hipMemcpyHostToDevice, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(ib_dev, ib, (size_t)nports * 4, hipMemcpyHostToDevice, st));
+    AcSpec spec;  // the elements without their leads (no kernel here reads them); port a, port b
+    NODAL_TRY(ac_upload_spec(h, nreact, kind, value, nullptr, nullptr, {{ia, (size_t)nports}, {ib, (size_t)nports}}, nullptr, 0, &spec));
+    const int32_t *ia_dev = spec.list[0], *ib_dev = spec.list[1];
     // ap_out: Z [nfreq][nports][nports][2] | residuals [nfreq][nports] | the frequency's peaks |x|^2 [K] | the call's [K] |
     // the frequency's ports [K] | the call's ports [K] | their frequencies [K]
     const size_t kw = want_peak ? (((size_t)K + 1) & ~(size_t)1) : 0;
     NODAL_HIP_TRY(h, h->ap_out.reserve((zwords + cells + 2 * kw) * 8 + 3 * kw * 4 + 64));
     double *z_dev = h->ap_out.as<double>(), *resid_dev = z_dev + zwords, *fpeak_dev = resid_dev + cells, *peak_dev = fpeak_dev + kw;
+    ledger.resid_dev = resid_dev;
     int32_t *fport_dev = reinterpret_cast<int32_t *>(peak_dev + kw), *port_dev = fport_dev + kw, *freq_dev = port_dev + kw;
     NODAL_HIP_TRY(h, hipMemsetAsync(z_dev, 0, (zwords + cells) * 8, st));
     if (want_peak) {  // (NaN and -1 until a frequency is taken in)
@@ -402,18 +384,17 @@ int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, i
     }
 
     // ---- the frequencies ----
-    std::vector<uint8_t> on_host(cells, 0);  // the column's residual was read back already (the sparse LU route)
     bool peak_first = true;
     for (int32_t f = 0; f < nfreq; ++f) {
-        NODAL_TRY(ac_child_values(h, false, omega[f], kind_dev, val_dev));
+        NODAL_TRY(ac_child_values(h, false, omega[f], spec.kind, spec.value));
         client.z = reinterpret_cast<double2 *>(z_dev) + (size_t)f * nports * nports;
         client.first = true;
         bool dead = false;
         const size_t at = (size_t)f * nports;
-        NODAL_TRY(ac_block_frequency(h, c, dense, nports, client, resid + at, on_host.data() + at, resid_dev + at, &dead, work,
-                                     ms_analysis, ms_factor));
-        if (dead) {  // this frequency alone: NaN in its rows, the later ones are solved
-            info[f] = 1;
+        NODAL_TRY(ac_block_frequency(h, c, dense, nports, client, ledger.resid + at, ledger.on_host.data() + at, resid_dev + at,
+                                     &dead, work, ms_analysis, ms_factor));
+        if (dead) {
+            ledger.mark_dead(f);
             continue;
         }
         if (want_peak) {
@@ -424,30 +405,16 @@ int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, i
     }
 
     // ---- after the last frequency: everything comes down once ----
-    if (want_peak && !peak_first) {
-        k_acport_peak_root<<<groups_of(K, PTB), PTB, 0, st>>>(K, peak_dev);
-        NODAL_HIP_TRY(h, hipGetLastError());
-    }
-    std::vector<double> resid_dn(cells);
+    if (want_peak && !peak_first) NODAL_TRY(ac_peak_root(h, K, peak_dev));
     if (z_out) NODAL_HIP_TRY(h, hipMemcpyAsync(z_out, z_dev, zwords * 8, hipMemcpyDeviceToHost, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dn.data(), resid_dev, cells * 8, hipMemcpyDeviceToHost, st));
     if (want_peak) {
         if (node_peak_out) NODAL_HIP_TRY(h, hipMemcpyAsync(node_peak_out, peak_dev, (size_t)K * 8, hipMemcpyDeviceToHost, st));
         if (node_peak_port_out) NODAL_HIP_TRY(h, hipMemcpyAsync(node_peak_port_out, port_dev, (size_t)K * 4, hipMemcpyDeviceToHost, st));
         if (node_peak_freq_out) NODAL_HIP_TRY(h, hipMemcpyAsync(node_peak_freq_out, freq_dev, (size_t)K * 4, hipMemcpyDeviceToHost, st));
     }
-    NODAL_WAIT_STREAM(h, st);
-    for (int32_t f = 0; f < nfreq; ++f)
-        for (int32_t p = 0; p < nports; ++p) {
-            const size_t cell = (size_t)f * nports + p;
-            if (info[f] == 0) {
-                if (!on_host[cell]) resid[cell] = resid_dn[cell];
-                continue;
-            }
-            resid[cell] = nan;
-            if (z_out)
-                for (size_t t = 0; t < (size_t)nports * 2; ++t) z_out[cell * nports * 2 + t] = nan;
-        }
+    NODAL_TRY(ledger.finish([&](int32_t f) {
+        if (z_out) std::fill_n(z_out + (size_t)f * nports * nports * 2, (size_t)nports * nports * 2, nan);
+    }));
     if (work_out)
         for (int k = 0; k < 3; ++k) work_out[k] = work[k];
     return NODAL_OK;

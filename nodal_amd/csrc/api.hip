@@ -273,8 +273,8 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
                       &h->tg_con,
                       &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
-                      &h->ac_t_gsrc, &h->ac_t_ptr, &h->ac_t_con, &h->nz_spec, &h->nz_vec, &h->nz_part, &h->nz_out,
-                      &h->ap_spec, &h->ap_vec, &h->ap_rows, &h->ap_out, &h->ag_spec, &h->ag_vec, &h->ag_out,
+                      &h->ac_t_gsrc, &h->ac_t_ptr, &h->ac_t_con, &h->nz_vec, &h->nz_part, &h->nz_out,
+                      &h->ap_vec, &h->ap_rows, &h->ap_out, &h->ag_vec, &h->ag_out,
                       &h->dbg_resid, &h->dbg_apply, &h->dbg_lowdeg};
     for (DevBuf *b : bufs) b->release();
     for (auto &e : h->evpool) (void)hipEventDestroy(e);

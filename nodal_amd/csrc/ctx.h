@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
@@ -240,30 +241,32 @@ struct nodal_ctx {
     // AC analysis (ac.hip): the child context that holds the interleaved real form of G + j B(omega), 2n unknowns, as CSR
     // (kept per struct_epoch and reactive leads: ac_epoch, ac_key = kinds | leads a | leads b); per stored entry of the
     // child the place of G's value in `data` (-1: none), the entries' runs of reactive elements and the runs themselves
-    // (element << 1 | subtract); the call's elements, probes and probed elements; right-hand side, solution, refinement
-    // vectors and norms; phasors, currents, residuals and peaks until they go down; the staging ring of kept solutions
+    // (element << 1 | subtract); ac_spec, the reactive elements and int32 lists of the call at hand, of whichever of the
+    // four small-signal analyses (ac_upload_spec in ac_sweep.h: every call uploads anew); right-hand side, solution,
+    // refinement vectors and norms; phasors, currents, residuals and peaks until they go down; the staging ring of kept
+    // solutions
     nodal_ctx *ac = nullptr;
     uint64_t ac_epoch = 0;
     std::vector<int32_t> ac_key;
     DevBuf ac_gsrc, ac_ptr, ac_con, ac_spec, ac_vec, ac_out, ac_ring;
     // noise analysis (noise.hip): the child with the interleaved real form of (G + j B)^T for networks whose G is not
     // symmetric, built from the pattern and values of h->adjoint (G^T) and kept like h->ac with maps of its own (a
-    // symmetric G shares h->ac); the call's elements and outputs; right-hand sides, adjoint phasors, the input's
-    // right-hand side, refinement vectors and norms; the workgroups' partial sums; densities, gains, residuals and the
-    // integrated contributions until they go down
+    // symmetric G shares h->ac); the input's right-hand side and, on the sparse LU route, refinement vectors, a block of
+    // right-hand sides, one of adjoint phasors and the norms (the dense route solves in ap_vec); the workgroups' partial
+    // sums; densities, gains, residuals and the integrated contributions until they go down
     nodal_ctx *ac_t = nullptr;
     uint64_t ac_t_epoch = 0;
     std::vector<int32_t> ac_t_key;
-    DevBuf ac_t_gsrc, ac_t_ptr, ac_t_con, nz_spec, nz_vec, nz_part, nz_out;
-    // AC port analysis (ac_ports.hip), on h->ac: the call's elements and ports; the four interleaved blocks (right-hand
-    // sides, solutions, defect, correction) or the dense route's right-hand sides and solutions, one vector and the
-    // judge's norms; the [16][2n] rows of a block with a column redone alone (reserved when the first one is); Z,
-    // residuals and peaks until they go down
-    DevBuf ap_spec, ap_vec, ap_rows, ap_out;
-    // AC gradient (ac_gradient.hip), on h->ac and, when G is not symmetric, h->ac_t: the call's elements, probes and
-    // cotangents; the forward right-hand side, x_f and y_f (2n each); phasors, source terms, residuals and the two
-    // gradient sums until they go down
-    DevBuf ag_spec, ag_vec, ag_out;
+    DevBuf ac_t_gsrc, ac_t_ptr, ac_t_con, nz_vec, nz_part, nz_out;
+    // AC port analysis (ac_ports.hip), on h->ac.  ap_vec and ap_rows belong to the block loop (ac_block_frequency,
+    // ac_block_dense), whichever analysis calls it: the four interleaved blocks (right-hand sides, solutions, defect,
+    // correction) or the dense route's right-hand sides and solutions, one vector and the judge's norms; the [16][2n]
+    // rows of a block with a column redone alone (reserved when the first one is).  ap_out: Z, residuals and peaks until
+    // they go down
+    DevBuf ap_vec, ap_rows, ap_out;
+    // AC gradient (ac_gradient.hip), on h->ac and, when G is not symmetric, h->ac_t: the forward right-hand side, x_f and
+    // y_f (2n each); phasors, source terms, residuals and the two gradient sums until they go down
+    DevBuf ag_vec, ag_out;
     DevBuf dbg_resid;  // testing hook nodal_debug_residual: the caller's x | b and the norms, nothing else lives here
     DevBuf dbg_apply;  // testing hooks nodal_debug_direct_apply / nodal_debug_cycle_apply: the caller's vectors during
                        // the call, nothing else lives here
@@ -466,6 +469,10 @@ int multi_rhs_solve(nodal_ctx *h, nodal_ctx *s, bool dense, int32_t count, doubl
                     int32_t *info_out, MultiRhsClient &client);
 // testing hook: the right-hand sides `client` builds, through the interleaved block, handed over as rows
 int sparse_sources_rhs(nodal_ctx *h, int32_t count, MultiRhsClient &client);
+// host milliseconds since t0
+static inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 // a call on the solve context s: on failure its error text becomes the handle's
 static inline int nodal_lift_error(nodal_ctx *h, nodal_ctx *s, int status) {
     if (status != NODAL_OK && s != h) h->err = s->err;
@@ -715,23 +722,7 @@ int ac_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t
            double *peak_out, int32_t *peak_freq_out, double *resid_out, int32_t *info_out, double *ms_analysis,
            double *ms_factor);
 void ac_free_child(nodal_ctx *h);
-// What the noise analysis shares with the sweep above.  `transposed` picks the child: false h->ac, built from h's own
-// pattern and values (G), true h->ac_t, built from h->adjoint's (G^T; the caller has brought it up to date) -- B is
-// symmetric, so the stamps are the same.
-// the arguments that name frequencies and reactive elements; `what` begins the error texts ("ac sweep: ")
-int ac_check_arguments(nodal_ctx *h, const char *what, int32_t nfreq, const double *omega, int64_t nreact,
-                       const uint8_t *kind, const double *value, const int32_t *lead_a, const int32_t *lead_b);
-// the child, its pattern and maps rebuilt when the parent's structure or the reactive leads move; *ms_pattern is written
-// only then
-int ac_child(nodal_ctx *h, bool transposed, int64_t nreact, const uint8_t *kind, const int32_t *lead_a,
-             const int32_t *lead_b, double *ms_pattern, nodal_ctx **child);
-// the child's values at omega (k_ac_values) from the device copies of the elements' kinds and values
-int ac_child_values(nodal_ctx *h, bool transposed, double omega, const uint8_t *kind_dev, const double *value_dev);
-// the small-signal right-hand side: the named rows checked and uploaded (waits), then -- every other independent source
-// off -- the members (re, im) of the source stamp written interleaved into the zeroed bvec [2n]
-int ac_sources_check(nodal_ctx *h, const char *what, const char *row, int32_t nsrc, const int64_t *src_rows, const double *src_re,
-                     const double *src_im);
-int ac_sources_stamp(nodal_ctx *h, int32_t nsrc, double *bvec);
+// (what the other small-signal analyses share with it: ac_sweep.h)
 
 // ---- noise analysis (noise.hip): thermal-noise spectra by the adjoint of the AC system, one factorisation per frequency ----
 // the arguments are those of nodal_ac_noise; ms_analysis, ms_factor as ac_run's
@@ -742,16 +733,7 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
               double *ms_factor);
 
 // ---- AC port analysis (ac_ports.hip): the multiport Z(j omega) of an RLC network, one factorisation per frequency ----
-// Every column of one frequency on the child c (2n unknowns) whose values ac_child_values has just written: the per-
-// frequency block loop.  client.build adds the right-hand sides of columns m0 .. m0 + cols - 1 (cols <= 16) into a zeroed
-// block, client.hand_over takes the finished ones (never as rows: wants_rows is not looked at; nothing waits), both with
-// element (row, y) at [row * rs + y * cs] -- the interleaved block (16, 1), or the rows of the dense and redo routes
-// (1, 2n).  resid_host [count]: the sparse route leaves every column's scaled residual there (on_host[q] = 1); the dense
-// route leaves it at resid_dev [count] on the device.  *dead: singular at this frequency, whatever was handed over is
-// void.  work [3]: numeric factorisations, applications of the sparse factors to a block, columns redone alone -- added
-// to.  ms_analysis, ms_factor: added to, as ac_run's.  Buffers: h->ap_vec, h->ap_rows.
-int ac_block_frequency(nodal_ctx *h, nodal_ctx *c, bool dense, int32_t count, MultiRhsClient &client, double *resid_host,
-                       uint8_t *on_host, double *resid_dev, bool *dead, int64_t *work, double *ms_analysis, double *ms_factor);
+// (the per-frequency block loop, ac_block_frequency: ac_sweep.h)
 // the arguments are those of nodal_ac_ports; ms_analysis, ms_factor as ac_run's
 int ac_ports_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
                  const double *value, const int32_t *lead_a, const int32_t *lead_b, int32_t nports, const int32_t *ia,

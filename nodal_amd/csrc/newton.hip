@@ -28,7 +28,6 @@
 #include "group.h"
 #include "table_rows.h"
 
-#include <chrono>
 #include <cmath>
 
 namespace {
@@ -118,10 +117,6 @@ __global__ __launch_bounds__(TTB) void k_newton_fill(int64_t nd, const int32_t *
                                                      double *__restrict__ value) {
     const int64_t d = (int64_t)blockIdx.x * TTB + threadIdx.x;
     if (d < nd) value[rows[d]] = fill;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace

@@ -32,7 +32,6 @@
 #include "group.h"
 #include "table_rows.h"
 
-#include <chrono>
 #include <cmath>
 
 namespace {
@@ -108,10 +107,6 @@ __global__ __launch_bounds__(OTB) void k_opgrad_total(int64_t groups, const doub
         for (int w = 1; w < OWAVES; ++w) t += red[w];
         out[0] = t;
     }
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 void fill(double *p, int64_t count, double v) {

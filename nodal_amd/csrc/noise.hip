@@ -17,10 +17,11 @@
 // A frequency is, on the handle's stream,
 //     k_ac_values     the child's values (ac.hip)
 //     the solves      ONE numeric factorisation whatever the number of outputs.  Dense panel (2n <= 64, or `dense` at
-//                     any size): the outputs are the right-hand-side columns of one dense_factor_solve_multi, up to 512
-//                     at a time, judged in blocks of sixteen.  Otherwise the sparse LU factored anew on the kept
-//                     analysis (transient_solver_begin), and per output two substitutions, one refinement step, the
-//                     judgement, and the sparse direct solve for an output above the bar (transient_solver_step)
+//                     any size): ac_block_dense (ac_sweep.h), the outputs are the right-hand-side columns of one
+//                     dense_factor_solve_multi, up to 512 at a time, judged in blocks of sixteen.  Otherwise the sparse
+//                     LU factored anew on the kept analysis (transient_solver_begin), and per output two substitutions,
+//                     one refinement step, the judgement, and the sparse direct solve for an output above the bar
+//                     (transient_solver_step)
 // and per block of sixteen outputs, whose adjoints lie as rows [16][2n],
 //     k_noise_rows    one lane per table row: type, value and leads read once, then the block's outputs in turn: c_k, its
 //                     weighted sum onto C_k(p) when contributions are asked for (the row is this lane's alone: a plain
@@ -31,7 +32,7 @@
 // No floating-point atomics anywhere: a repeated call gives the same bits.  Densities, gains and residuals come down
 // once, after the last frequency, the integrated contributions [nout][ncomp] once; the [nfreq][nout][ncomp] array never
 // exists.  The handle itself -- solution, table, G, A, tape, hierarchy, factors, the AC child's kept work -- is only read.
-#include "table_rows.h"
+#include "ac_sweep.h"
 
 namespace {
 
@@ -142,6 +143,52 @@ __global__ __launch_bounds__(64) void k_noise_fold(int64_t ngroups, const double
     if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 
+// the block loop's client: the columns are the outputs' unit differences, a finished block of up to sixteen adjoints
+// goes through the table pass, the fold and the gain of frequency f
+struct NoiseClient final : MultiRhsClient {
+    nodal_ctx *h;
+    int64_t n, ncomp;
+    int32_t nout, f = 0;  // the frequency at hand
+    const int32_t *oa, *ob;  // device, [nout]
+    double kt4;
+    const double *weight = nullptr;  // host, [nfreq]; null: no contributions
+    const double *svec = nullptr;    // device, the input's right-hand side [2n]; null: no gains
+    double *part, *dens, *gain, *contrib;  // device: the partial sums, [nfreq][nout], [nfreq][nout][2], [nout][ncomp]
+    NoiseClient(nodal_ctx *h_, int32_t nout_, const int32_t *oa_, const int32_t *ob_)
+        : h(h_), n(h_->n), ncomp(h_->ncomp), nout(nout_), oa(oa_), ob(ob_) {
+        wants_rows = false;
+        max_cols = NCOLS;
+    }
+    // (k_noise_rhs writes rows: column y at out + y * cs, any number of them)
+    int build(int32_t m0, int cols, double *out, int64_t rs, int64_t cs) override {
+        if (cols < 1 || m0 < 0 || m0 + cols > nout || rs != 1)
+            return nodal_fail(h, NODAL_E_INVALID, "noise: a block outside the call's columns");
+        k_noise_rhs<<<groups_of(cols, 64), 64, 0, h->stream>>>(cols, oa + m0, ob + m0, out, cs);
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return NODAL_OK;
+    }
+    // the table pass, the fold and the gain of outputs p0 .. p0 + cols - 1, their adjoints the rows [cols][2n] at y
+    int hand_over(int32_t p0, int cols, const double *y, int64_t rs, int64_t cs, const double *) override {
+        const int64_t n2 = 2 * n, row_groups = groups_of(ncomp, NTB), gain_groups = groups_of(n, NTB);
+        if (cols < 1 || cols > NCOLS || p0 < 0 || p0 + cols > nout || rs != 1 || cs != n2)
+            return nodal_fail(h, NODAL_E_INVALID, "noise: a block outside the call's columns");
+        hipStream_t st = h->stream;
+        if (ncomp > 0) {
+            k_noise_rows<<<(unsigned)row_groups, NTB, 0, st>>>(ncomp, cols, h->type.as<uint8_t>(), assembled_values(h), h->a.as<int32_t>(),
+                                                              h->b.as<int32_t>(), y, n2, kt4, weight ? weight[f] : 0.0,
+                                                              weight ? contrib + (size_t)p0 * ncomp : nullptr, part);
+            k_noise_fold<<<(unsigned)cols, 64, 0, st>>>(row_groups, part, dens + (size_t)f * nout + p0);
+        }
+        if (svec) {
+            k_noise_gain<<<(unsigned)gain_groups, NTB, 0, st>>>(n, cols, y, n2, svec, part);
+            k_noise_fold<<<(unsigned)(2 * cols), 64, 0, st>>>(gain_groups, part, gain + ((size_t)f * nout + p0) * 2);
+        }
+        NODAL_HIP_TRY(h, hipGetLastError());
+        return NODAL_OK;
+    }
+    void all_singular(int32_t) override {}  // (noise_run fills the frequency's rows from info)
+};
+
 }  // namespace
 
 int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int64_t nreact, const uint8_t *kind,
@@ -150,7 +197,6 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
               double *gain_out, double *contrib_out, double *resid_out, int32_t *info_out, double *ms_analysis,
               double *ms_factor) {
     const int64_t n = h->n, n2 = 2 * n, ncomp = h->ncomp;
-    const int32_t K = h->K;
     hipStream_t st = h->stream;
     const double nan = __builtin_nan("");
     *ms_analysis = *ms_factor = 0.0;
@@ -159,9 +205,7 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
     NODAL_TRY(ac_check_arguments(h, "noise: ", nfreq, omega, nreact, kind, value, lead_a, lead_b));
     if (!(temperature > 0.0 && temperature - temperature == 0.0))
         return nodal_fail(h, NODAL_E_INVALID, "noise: a temperature that is not finite and positive");
-    for (int32_t p = 0; p < nout; ++p)
-        if (out_a[p] < -1 || out_a[p] >= K || out_b[p] < -1 || out_b[p] >= K)
-            return nodal_fail(h, NODAL_E_INVALID, "noise: output node out of range");
+    NODAL_TRY(ac_check_pairs(h, "noise: ", "output node", nout, out_a, out_b));
     const bool have_input = input_row >= 0;
     if (input_row < -1) return nodal_fail(h, NODAL_E_INVALID, "noise: input: source row out of range");
     if (gain_out && !have_input) return nodal_fail(h, NODAL_E_INVALID, "noise: a gain is asked for and no input source is named");
@@ -174,19 +218,11 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
 
     const bool want_gain = gain_out != nullptr, want_contrib = contrib_out != nullptr && ncomp > 0;
     const size_t cells = (size_t)nfreq * nout, contrib_words = want_contrib ? (size_t)nout * ncomp : 0;
-    std::vector<double> resid_own(resid_out ? 0 : cells);
-    std::vector<int32_t> info_own(info_out ? 0 : (size_t)nfreq);
-    double *resid = resid_out ? resid_out : resid_own.data();
-    int32_t *info = info_out ? info_out : info_own.data();
-    for (int32_t f = 0; f < nfreq; ++f) info[f] = 0;
-    for (size_t t = 0; t < cells; ++t) resid[t] = 0.0;
+    AcLedger ledger(h, nfreq, (size_t)nout, resid_out, info_out);
     if (n == 0) {  // (no unknowns: every lead is ground, nothing is seen)
-        if (density_out)
-            for (size_t t = 0; t < cells; ++t) density_out[t] = 0.0;
-        if (gain_out)
-            for (size_t t = 0; t < 2 * cells; ++t) gain_out[t] = 0.0;
-        if (contrib_out)
-            for (size_t t = 0; t < (size_t)nout * ncomp; ++t) contrib_out[t] = 0.0;
+        if (density_out) std::fill_n(density_out, cells, 0.0);
+        if (gain_out) std::fill_n(gain_out, 2 * cells, 0.0);
+        if (contrib_out) std::fill_n(contrib_out, (size_t)nout * ncomp, 0.0);
         return NODAL_OK;
     }
 
@@ -196,25 +232,14 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
     const bool transposed = s != h;
     nodal_ctx *c = nullptr;
     NODAL_TRY(ac_child(h, transposed, nreact, kind, lead_a, lead_b, ms_analysis, &c));
-    // nz_spec: values [nreact] doubles | output a | output b | kinds (bytes)
-    const size_t rw = ((size_t)nreact + 15) & ~(size_t)15, ow = ((size_t)nout + 15) & ~(size_t)15;
-    NODAL_HIP_TRY(h, h->nz_spec.reserve(rw * 8 + 2 * ow * 4 + rw + 64));
-    double *val_dev = h->nz_spec.as<double>();
-    int32_t *oa_dev = reinterpret_cast<int32_t *>(val_dev + rw), *ob_dev = oa_dev + ow;
-    uint8_t *kind_dev = reinterpret_cast<uint8_t *>(ob_dev + ow);
-    if (nreact > 0) {
-        NODAL_HIP_TRY(h, hipMemcpyAsync(val_dev, value, (size_t)nreact * 8, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(kind_dev, kind, (size_t)nreact, hipMemcpyHostToDevice, st));
-    }
-    NODAL_HIP_TRY(h, hipMemcpyAsync(oa_dev, out_a, (size_t)nout * 4, hipMemcpyHostToDevice, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(ob_dev, out_b, (size_t)nout * 4, hipMemcpyHostToDevice, st));
-    // nz_vec: right-hand sides [16][2n] | adjoints [chunk][2n] | the input's right-hand side | defect | correction (2n each)
-    // | the judge's norms
+    AcSpec spec;  // the elements without their leads (no kernel here reads them); output a, output b
+    NODAL_TRY(ac_upload_spec(h, nreact, kind, value, nullptr, nullptr, {{out_a, (size_t)nout}, {out_b, (size_t)nout}}, nullptr, 0, &spec));
+    // nz_vec: the input's right-hand side (2n) and, for the sparse LU route, | defect | correction (2n each)
+    // | right-hand sides [16][2n] | adjoints [16][2n] | the judge's norms
     const bool dense_route = n2 <= 64 || dense;
-    const int32_t chunk = dense_route ? std::min<int32_t>(nout, DENSE_CHUNK) : NCOLS;
-    NODAL_HIP_TRY(h, h->nz_vec.reserve((size_t)(NCOLS + chunk + 3) * n2 * 8 + 5 * SLU_MULTI * 8 + 256));
-    double *bblk = h->nz_vec.as<double>(), *ys = bblk + (size_t)NCOLS * n2, *svec = ys + (size_t)chunk * n2, *rvec = svec + n2,
-           *dvec = rvec + n2, *norms = dvec + n2;
+    NODAL_HIP_TRY(h, h->nz_vec.reserve((size_t)(3 + 2 * NCOLS) * n2 * 8 + 5 * SLU_MULTI * 8 + 256));
+    double *svec = h->nz_vec.as<double>(), *rvec = svec + n2, *dvec = rvec + n2, *bblk = dvec + n2, *ys = bblk + (size_t)NCOLS * n2,
+           *norms = ys + (size_t)NCOLS * n2;
     // nz_part: the workgroups' partial sums, [16][groups of the table] or [16][2][groups of the unknowns]
     const int64_t row_groups = groups_of(ncomp, NTB), gain_groups = groups_of(n, NTB);
     NODAL_HIP_TRY(h, h->nz_part.reserve((size_t)std::max<int64_t>(row_groups, 2 * gain_groups) * NCOLS * 8 + 64));
@@ -223,68 +248,34 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
     NODAL_HIP_TRY(h, h->nz_out.reserve((4 * cells + contrib_words + 2) * 8 + 64));
     double *dens_dev = h->nz_out.as<double>(), *gain_dev = dens_dev + cells, *resid_dev = gain_dev + 2 * cells,
            *contrib_dev = resid_dev + cells;
+    ledger.resid_dev = resid_dev;
     NODAL_HIP_TRY(h, hipMemsetAsync(dens_dev, 0, (4 * cells + contrib_words) * 8, st));
     if (have_input) NODAL_TRY(ac_sources_stamp(h, 1, svec));
     NODAL_WAIT_STREAM(h, st);  // (the elements and outputs are the caller's)
 
-    const double kt4 = 4.0 * BOLTZMANN * temperature;
-    const uint8_t *type_dev = h->type.as<uint8_t>();
-    const double *value_dev = assembled_values(h);
-    const int32_t *a_dev = h->a.as<int32_t>(), *b_dev = h->b.as<int32_t>();
-    // the table pass, the fold and the gain of outputs p0 .. p0 + cols - 1 of frequency f, their adjoints at y
-    auto table_pass = [&](int32_t f, int32_t p0, int cols, const double *y) -> int {
-        if (ncomp > 0) {
-            k_noise_rows<<<(unsigned)row_groups, NTB, 0, st>>>(ncomp, cols, type_dev, value_dev, a_dev, b_dev, y, n2, kt4,
-                                                              want_contrib ? weight[f] : 0.0,
-                                                              want_contrib ? contrib_dev + (size_t)p0 * ncomp : nullptr, part);
-            k_noise_fold<<<(unsigned)cols, 64, 0, st>>>(row_groups, part, dens_dev + (size_t)f * nout + p0);
-        }
-        if (want_gain) {
-            k_noise_gain<<<(unsigned)gain_groups, NTB, 0, st>>>(n, cols, y, n2, svec, part);
-            k_noise_fold<<<(unsigned)(2 * cols), 64, 0, st>>>(gain_groups, part, gain_dev + ((size_t)f * nout + p0) * 2);
-        }
-        NODAL_HIP_TRY(h, hipGetLastError());
-        return NODAL_OK;
-    };
-    // columns p0 .. p0 + cols - 1 of the right-hand sides into a zeroed block, column y at out + y * cs
-    auto build_rhs = [&](int32_t p0, int cols, double *out, int64_t cs) -> int {
-        NODAL_HIP_TRY(h, hipMemsetAsync(out, 0, (size_t)cols * cs * 8, st));
-        k_noise_rhs<<<groups_of(cols, 64), 64, 0, st>>>(cols, oa_dev + p0, ob_dev + p0, out, cs);
-        NODAL_HIP_TRY(h, hipGetLastError());
-        return NODAL_OK;
-    };
+    NoiseClient client(h, nout, spec.list[0], spec.list[1]);
+    client.kt4 = 4.0 * BOLTZMANN * temperature;
+    if (want_contrib) client.weight = weight;
+    if (want_gain) client.svec = svec;
+    client.part = part;
+    client.dens = dens_dev;
+    client.gain = gain_dev;
+    client.contrib = contrib_dev;
 
     // ---- the frequencies ----
-    std::vector<uint8_t> on_host(cells, 0);  // the output's residual was read back already (the sparse LU route)
     uint64_t lu_epoch = 0;  // (never the child's numeric_epoch: every frequency is factored anew)
-    const int64_t lda = dense_lda(n2);
+    int64_t work[3] = {0, 0, 0};  // (not reported)
     for (int32_t f = 0; f < nfreq; ++f) {
-        NODAL_TRY(ac_child_values(h, transposed, omega[f], kind_dev, val_dev));
+        NODAL_TRY(ac_child_values(h, transposed, omega[f], spec.kind, spec.value));
+        client.f = f;
         bool dead = false;
-        if (dense_route) {
-            for (int32_t q0 = 0; q0 < nout && !dead; q0 += chunk) {
-                const int32_t width = std::min<int32_t>(chunk, nout - q0);
-                NODAL_HIP_TRY(h, c->dense.reserve((size_t)lda * (size_t)(n2 + width) * 8 + 64));
-                NODAL_TRY(nodal_lift_error(h, c, csr_to_dense(c, c->dense.as<double>(), lda)));
-                NODAL_TRY(build_rhs(q0, width, c->dense.as<double>() + n2 * lda, lda));
-                int32_t inf = 0;
-                NODAL_TRY(nodal_lift_error(h, c, dense_factor_solve_multi(c, width, ys, n2, &inf)));
-                if (inf > 0) {
-                    if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
-                    dead = true;
-                    break;
-                }
-                for (int32_t p0 = q0; p0 < q0 + width; p0 += NCOLS) {
-                    const int cols = std::min<int32_t>(NCOLS, q0 + width - p0);
-                    const double *y = ys + (size_t)(p0 - q0) * n2;
-                    NODAL_TRY(build_rhs(p0, cols, bblk, n2));
-                    NODAL_TRY(nodal_lift_error(h, c, csr_judge_block(c, y, bblk, 1, n2, cols, norms)));
-                    NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + (size_t)f * nout + p0, norms + 4 * SLU_MULTI, (size_t)cols * 8,
-                                                    hipMemcpyDeviceToDevice, st));
-                    NODAL_TRY(table_pass(f, p0, cols, y));
-                }
-            }
+        if (dense_route) {  // k_noise_rhs fills the panel's columns of a chunk in one launch
+            NODAL_TRY(ac_block_dense(h, c, dense, nout, DENSE_CHUNK, client, resid_dev + (size_t)f * nout, &dead, work));
         } else {
+            // One output at a time through transient_solver_step (two substitutions and one refinement step), not sixteen
+            // through slu_apply_multi as ac_block_frequency has them: an output has the same bits alone as inside a block
+            // (tests/test_gpu_noise.py).  Moving this branch onto the block apply is a change of speed and of bits, for a
+            // pull request of its own.
             TransientSolver ts;
             ts.s = c;
             ts.lu_epoch = &lu_epoch;
@@ -293,54 +284,40 @@ int noise_run(nodal_ctx *h, bool dense, int32_t nfreq, const double *omega, int6
             ts.norms = norms;
             double ms_f = 0.0;
             NODAL_TRY(nodal_lift_error(h, c, transient_solver_begin(c, ts, false, 1, &dead, &ms_f)));
-            const double ms_a = slu_analysis_ms(c);
-            *ms_analysis += ms_a;
-            *ms_factor += ms_f > ms_a ? ms_f - ms_a : 0.0;
+            ac_add_factor_time(c, ms_f, ms_analysis, ms_factor);
             for (int32_t p0 = 0; p0 < nout && !dead; p0 += NCOLS) {
                 const int cols = std::min<int32_t>(NCOLS, nout - p0);
-                NODAL_TRY(build_rhs(p0, cols, bblk, n2));
+                NODAL_HIP_TRY(h, hipMemsetAsync(bblk, 0, (size_t)cols * n2 * 8, st));
+                NODAL_TRY(client.build(p0, cols, bblk, 1, n2));
                 for (int y = 0; y < cols && !dead; ++y) {
                     const size_t cell = (size_t)f * nout + p0 + y;
                     int32_t inf = 0, it = 0;
                     bool judged = false;
                     double ms_none = 0.0;
                     NODAL_TRY(nodal_lift_error(h, c, transient_solver_step(c, ts, bblk + (size_t)y * n2, ys + (size_t)y * n2, &inf, &it,
-                                                                           &resid[cell], &judged, &ms_none)));
+                                                                           &ledger.resid[cell], &judged, &ms_none)));
                     if (inf > 0) {
                         dead = true;
                         break;
                     }
-                    on_host[cell] = judged;
+                    ledger.on_host[cell] = judged;
                     if (!judged) NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dev + cell, norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
                 }
-                if (!dead) NODAL_TRY(table_pass(f, p0, cols, ys));
+                if (!dead) NODAL_TRY(client.hand_over(p0, cols, ys, 1, n2, nullptr));
             }
         }
-        if (dead) info[f] = 1;  // this frequency alone: NaN in its rows, the later ones are solved
+        if (dead) ledger.mark_dead(f);
     }
 
     // ---- after the last frequency: everything comes down once ----
-    std::vector<double> resid_dn(cells);
     if (density_out) NODAL_HIP_TRY(h, hipMemcpyAsync(density_out, dens_dev, cells * 8, hipMemcpyDeviceToHost, st));
     if (gain_out) NODAL_HIP_TRY(h, hipMemcpyAsync(gain_out, gain_dev, 2 * cells * 8, hipMemcpyDeviceToHost, st));
     if (want_contrib) NODAL_HIP_TRY(h, hipMemcpyAsync(contrib_out, contrib_dev, contrib_words * 8, hipMemcpyDeviceToHost, st));
-    NODAL_HIP_TRY(h, hipMemcpyAsync(resid_dn.data(), resid_dev, cells * 8, hipMemcpyDeviceToHost, st));
-    NODAL_WAIT_STREAM(h, st);
-    bool any_dead = false;
-    for (int32_t f = 0; f < nfreq; ++f) {
-        for (int32_t p = 0; p < nout; ++p) {
-            const size_t cell = (size_t)f * nout + p;
-            if (info[f] == 0) {
-                if (!on_host[cell]) resid[cell] = resid_dn[cell];
-                continue;
-            }
-            resid[cell] = nan;
-            if (density_out) density_out[cell] = nan;
-            if (gain_out) gain_out[2 * cell] = gain_out[2 * cell + 1] = nan;
-        }
-        any_dead = any_dead || info[f] != 0;
-    }
-    if (any_dead && want_contrib)  // (an integral over a list with a hole in it is none)
-        for (size_t t = 0; t < contrib_words; ++t) contrib_out[t] = nan;
+    NODAL_TRY(ledger.finish([&](int32_t f) {
+        if (density_out) std::fill_n(density_out + (size_t)f * nout, (size_t)nout, nan);
+        if (gain_out) std::fill_n(gain_out + (size_t)f * nout * 2, 2 * (size_t)nout, nan);
+    }));
+    if (ledger.any_dead() && want_contrib)  // (an integral over a list with a hole in it is none)
+        std::fill_n(contrib_out, contrib_words, nan);
     return NODAL_OK;
 }

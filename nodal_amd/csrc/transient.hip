@@ -41,7 +41,6 @@
 #include "group.h"
 #include "table_rows.h"
 
-#include <chrono>
 
 namespace {
 
@@ -180,10 +179,6 @@ __global__ __launch_bounds__(TTB) void k_transient_defect(int64_t n, const int32
 __global__ __launch_bounds__(TTB) void k_transient_correct(int64_t n, const double *__restrict__ d, double *__restrict__ x) {
     const int64_t i = (int64_t)blockIdx.x * TTB + threadIdx.x;
     if (i < n) x[i] += d[i];
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace

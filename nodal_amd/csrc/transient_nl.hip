@@ -40,7 +40,6 @@
 #include "group.h"
 #include "table_rows.h"
 
-#include <chrono>
 #include <cmath>
 
 namespace {
@@ -89,10 +88,6 @@ __global__ __launch_bounds__(TTB) void k_tnl_probe(int32_t np, const int32_t *__
     diode_model(v, isat[d], nvt[d], gmin, &g, &i);
     vout[q] = v;
     iout[q] = i;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace

@@ -39,7 +39,7 @@ from tools.sweep_probe import with_loads  # noqa: E402
 from tools.transient_probe import assembled, timed  # noqa: E402
 
 KERNELS = ("k_acport_rhs", "k_acport_residual", "k_acport_correct", "k_acport_gather", "k_acport_peak", "k_acport_merge",
-           "k_acport_peak_root", "k_acport_rows", "k_ac_values")
+           "k_ac_peak_root", "k_acport_rows", "k_ac_values")
 INDUCTORS = 64
 
 
