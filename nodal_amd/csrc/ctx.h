@@ -646,14 +646,59 @@ int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, 
                double gmin, int32_t nsrc, const double *x0, int32_t max_iter, double reltol, double vntol, double abstol,
                const NewtonOutputs &out, double *ms_matrix, double *ms_symbolic);
 
-// the lanes of the loop above for transient_nl.hip: the check of rows and parameters with its verdict (one wait; the two
-// texts of NODAL_E_INVALID are the caller's), vh = v of x, the linearisation at vh, value[rows[d]] = fill
-int newton_check_diodes(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
-                        int32_t *bad_dev, const char *not_r, const char *not_positive);
-int newton_launch_start(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *x, double *vh);
-int newton_launch_linearise(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
-                            double gmin, const double *vh, double *value, double *hist, double *gk, double *ik);
-int newton_launch_fill(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, double fill, double *value);
+// ---- what the three nonlinear analyses share (newton.hip): the call's diodes on the device, one Newton iteration ----
+// A spec buffer holds, every part rounded up to sixteen words,
+//     diode rows [nd] int32 | the caller's further int32 words | bad flag | i_sat, n_vt, J, g_k, i_k [nd] doubles each |
+//     the caller's further doubles
+// and three more buffers the diodes' node list (group.h over diode_lanes.h's DiodeLeads): tr_* for nodal_newton_dc and
+// nodal_newton_gradient, tn_* for nodal_transient_nl, whose capacitors' list holds tr_*.
+struct DiodeSet {
+    int64_t nd = 0, nent = 0;  // diodes, entries of their node list
+    double gmin = 0.0;
+    int32_t *rows_dev = nullptr;
+    double *isat_dev = nullptr, *nvt_dev = nullptr, *hist = nullptr, *gk = nullptr, *ik = nullptr;
+    DevBuf *node = nullptr, *ptr = nullptr, *con = nullptr;
+    // Once per call.  E_INVALID, the texts beginning with `what` ("newton: "): a row out of range, diodes on a network
+    // without nodes; then, unless n == 0 (nothing of the set is used), the buffer carved, rows (narrowed) and parameters
+    // up, and with the device's verdict (ONE wait: the uploads are done too, the host arrays may go) a row that is not an
+    // R, an i_sat or n_vt that is not positive and finite; then the node list.  nd == 0 carves only.
+    int prepare(nodal_ctx *h, const char *what, int64_t nd, const int64_t *rows, const double *isat, const double *nvt,
+                double gmin, DevBuf &spec, DevBuf &list_none, DevBuf &list_node, DevBuf &list_ptr, DevBuf &list_con,
+                size_t more_words, size_t more_doubles, int32_t **words, double **doubles);
+    // the lanes (nd == 0 launches nothing): vh = x(a) - x(b); g, i at vh -- 1 / g into the diodes' rows of `value`,
+    // J = g vh - i into hist, g and i into gk and ik; column[rows[d]] = v; rhs += J at the anodes, -= J at the cathodes
+    int start(nodal_ctx *h, const double *x, double *vh) const;
+    int linearise(nodal_ctx *h, const double *vh, double *value) const;
+    int fill(nodal_ctx *h, double v, double *column) const;
+    int add_currents(nodal_ctx *h, double *rhs) const;
+    // linearise() into the value column the assembly reads, then stamp_numeric (its host ms added to *ms_stamp).
+    // *overflowed: some g overflowed, 1 / g == 0 and the assembly said NODAL_E_ZERO_RESISTANCE -- the diodes' rows then
+    // hold 1.0 and G is assembled from them, so that the handle stays usable; the call has no matrix to go on with
+    int linearise_and_assemble(nodal_ctx *h, const double *vh, bool *overflowed, double *ms_stamp) const;
+};
+
+// How one Newton iteration ended; the first three have an x and a record.  NOT_FINITE: the record is not finite,
+// OVERFLOWED: linearise_and_assemble's, DEAD: transient_solver_begin's verdict, SINGULAR: transient_solver_step's inf > 0
+enum { NEWTON_CONVERGED, NEWTON_GO_ON, NEWTON_NOT_FINITE, NEWTON_OVERFLOWED, NEWTON_DEAD, NEWTON_SINGULAR };
+constexpr int NEWTON_REC_WORDS = 5;  // failed, limited, bits of max |v - vh|, bits of the scaled residual, 1 / g moved
+struct NewtonStep {
+    int outcome = NEWTON_GO_ON;
+    int32_t it = 0;       // the solver's iterations
+    int32_t route = -1;   // nodal_newton_dc's code: 0 dense, 1 sparse LU, 2 multigrid, 3 the sparse direct solve
+    bool judged = false;  // the scaled residual was on the host before the record came down
+    double dvmax = 0.0, scaled = 0.0;
+    unsigned long long words[NEWTON_REC_WORDS] = {0, 0, 0, 0, 0};  // the record as read
+    bool solved() const { return outcome <= NEWTON_NOT_FINITE; }
+};
+// One iteration on h's stream: the linearisation at vh_now (and with `assemble` the assembly; false: the matrix work
+// `ts` keeps still stands), rhs += the diodes' J (the caller has put the sources and any history into rhs), the route
+// and the solve into xk, the update lane into vh_next and the zeroed record `rec` (count_moved: word 4 as well), the
+// iterate to iterate_host if that is not null, and ONE read of the record.  The iteration's host waits: the assembly's
+// status words, what the solver looks at, the record.  Without diodes: the solve and the record's residual alone.
+// *ms_matrix += the host ms of assembly and solver, *ms_symbolic += the part that was an analysis or a full setup.
+int newton_iteration(nodal_ctx *h, const DiodeSet &diodes, TransientSolver &ts, bool dense, bool assemble, bool count_moved,
+                     const double *vh_now, double *vh_next, double *rhs, double *xk, unsigned long long *rec, double reltol,
+                     double vntol, double abstol, double *iterate_host, double *ms_matrix, double *ms_symbolic, NewtonStep *step);
 
 // ---- gradients through the operating point (newton_gradient.hip): one transposed solve with J at the caller's x ----
 struct NewtonGradientOutputs {   // host arrays, each may be null except grad (with ncomp > 0) and info
@@ -692,11 +737,11 @@ struct TransientDiodes {
     // the loop's state
     bool reuse = true;        // NODAL_TNL_REUSE
     bool moved = true;        // the next linearisation's 1 / g differs from what G was assembled from (or is not known to)
-    int64_t nent = 0, rec_at = 0;
+    int64_t rec_at = 0;
     int32_t slot = 0;         // which of the two vh vectors the next linearisation reads
-    int32_t *rows_dev = nullptr, *bad_dev = nullptr, *pidx_dev = nullptr;
-    double *isat_dev = nullptr, *nvt_dev = nullptr, *hist = nullptr, *gk = nullptr, *ik = nullptr, *vh = nullptr,
-           *rhs = nullptr, *pv_dev = nullptr, *pi_dev = nullptr;
+    DiodeSet set;
+    int32_t *pidx_dev = nullptr;
+    double *vh = nullptr, *rhs = nullptr, *pv_dev = nullptr, *pi_dev = nullptr;
     unsigned long long *rec_dev = nullptr;
     int prepare(nodal_ctx *h, int32_t steps, const double *x0_dev);
     int step(nodal_ctx *h, TransientSolver &ts, bool dense, int32_t k, const double *xp, const double *base, double *xk,

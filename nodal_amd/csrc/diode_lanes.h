@@ -1,9 +1,11 @@
-// The per-diode arithmetic that newton.hip (nodal_newton_dc) and transient_nl.hip (nodal_transient_nl) share: the
+// The per-diode arithmetic that the kernels of newton.hip, transient_nl.hip and newton_gradient.hip share: the
 // companion model at a junction voltage, SPICE's junction limiting and the convergence test.  Device code only; every
 // product is a statement of its own (the library is built with -ffp-contract=on), so that g, i and J are the roundings
 // the formulas of include/nodal_hip.h name, whichever kernel a lane runs in.
 #pragma once
 #include "table_rows.h"
+
+constexpr int TTB = 256;  // one lane per diode, 256 to a block
 
 // grouping enumerator (group.h): diode i touches its anode (slot 0: +J) and its cathode (slot 1: -J); one column
 struct DiodeLeads {

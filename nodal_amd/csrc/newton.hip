@@ -22,17 +22,18 @@
 //                           diode's convergence test, and into the iteration's record two integer counts (atomicAdd) and
 //                           the largest |v - vh| (atomicMax on the bits of a non-negative double, NaN above everything):
 //                           no floating-point sums, a repeated call gives the same bits
-// and then ONE read of the record's four words, the scaled residual among them.  The loop ends when no diode failed its
+// and then ONE read of the record's words, the scaled residual among them.  The loop ends when no diode failed its
 // test, on max_iter, on info > 0 or on a record that is not finite; k_newton_outputs then forms v, i(v), g(v) from x.
+//
+// The iteration is newton_iteration below, and the call's diodes on the device are a DiodeSet (ctx.h): both serve
+// nodal_transient_nl (transient_nl.hip), which nests the loop inside every time step, and the DiodeSet serves
+// nodal_newton_gradient (newton_gradient.hip) as well.
 #include "diode_lanes.h"
 #include "group.h"
-#include "table_rows.h"
 
 #include <cmath>
 
 namespace {
-
-constexpr int TTB = 256;
 
 // bad[0] |= 1 for a diode row that is not a resistor, |= 2 for a saturation current or an n_vt that is not > 0 and finite
 __global__ __launch_bounds__(TTB) void k_newton_check(int64_t nd, const int32_t *__restrict__ rows,
@@ -75,24 +76,37 @@ __global__ __launch_bounds__(TTB) void k_newton_linearise(int64_t nd, const int3
 
 // One lane per diode after the solve: the limited voltage of the next linearisation, the convergence test against the
 // linearisation (gk, ik at vh) this x was solved with, and the record: rec[0] diodes that failed, rec[1] diodes that
-// were limited, rec[2] the bits of max |v - vh|.
+// were limited, rec[2] the bits of max |v - vh|.  COUNT_MOVED (nodal_transient_nl's reuse): 1 / g of the NEXT
+// linearisation as well, compared bit for bit with the value column; rec[4] diodes where it differs.
+template <bool COUNT_MOVED>
 __global__ __launch_bounds__(TTB) void k_newton_update(int64_t nd, const int32_t *__restrict__ rows,
                                                        const int32_t *__restrict__ a, const int32_t *__restrict__ b,
                                                        const double *__restrict__ isat, const double *__restrict__ nvt,
                                                        double gmin, double reltol, double vntol, double abstol,
                                                        const double *__restrict__ x, const double *__restrict__ vh,
                                                        const double *__restrict__ gk, const double *__restrict__ ik,
-                                                       double *__restrict__ vh_next, unsigned long long *__restrict__ rec) {
+                                                       double *__restrict__ vh_next, unsigned long long *__restrict__ rec,
+                                                       const double *__restrict__ value) {
     const int64_t d = (int64_t)blockIdx.x * TTB + threadIdx.x;
     if (d >= nd) return;
     const int32_t r = rows[d];
     const double v = lead(x, a[r]) - lead(x, b[r]);
+    const double old = vh[d], is = isat[d], nv = nvt[d];
     bool limited, ok;
     double dv;
-    vh_next[d] = diode_limit_and_test(v, vh[d], isat[d], nvt[d], gmin, reltol, vntol, abstol, gk[d], ik[d], &limited, &ok, &dv);
+    const double next = diode_limit_and_test(v, old, is, nv, gmin, reltol, vntol, abstol, gk[d], ik[d], &limited, &ok, &dv);
+    vh_next[d] = next;
+    double inverse = 0.0;
+    if constexpr (COUNT_MOVED) {
+        double g, i;
+        diode_model(next, is, nv, gmin, &g, &i);  // (k_newton_linearise's g at vh': the same statements, the same bits)
+        inverse = 1.0 / g;
+    }
     if (!ok) atomicAdd(rec, 1ull);
     if (limited) atomicAdd(rec + 1, 1ull);
     atomicMax(rec + 2, magnitude_bits(dv));
+    if constexpr (COUNT_MOVED)
+        if (__double_as_longlong(inverse) != __double_as_longlong(value[r])) atomicAdd(rec + 4, 1ull);
 }
 
 // One lane per diode, once the loop has ended: v, i(v) and g(v) of the final x
@@ -121,11 +135,151 @@ __global__ __launch_bounds__(TTB) void k_newton_fill(int64_t nd, const int32_t *
 
 }  // namespace
 
+// ---- the call's diodes on the device (ctx.h) ----
+int DiodeSet::prepare(nodal_ctx *h, const char *what, int64_t count, const int64_t *rows, const double *isat, const double *nvt,
+                      double gmin_, DevBuf &spec, DevBuf &list_none, DevBuf &list_node, DevBuf &list_ptr, DevBuf &list_con,
+                      size_t more_words, size_t more_doubles, int32_t **words, double **doubles) {
+    hipStream_t st = h->stream;
+    auto fail = [&](const char *text) { return nodal_fail(h, NODAL_E_INVALID, (std::string(what) + text).c_str()); };
+    nd = count;
+    nent = 0;
+    gmin = gmin_;
+    node = &list_node;
+    ptr = &list_ptr;
+    con = &list_con;
+    for (int64_t i = 0; i < nd; ++i)
+        if (rows[i] < 0 || rows[i] >= h->ncomp) return fail("diode row out of range");
+    if (nd > 0 && h->K == 0) return fail("diodes on a network without nodes");
+    if (h->n == 0) return NODAL_OK;
+    const size_t row_words = ((size_t)nd + 15) & ~(size_t)15, own_words = (more_words + 15) & ~(size_t)15;
+    NODAL_HIP_TRY(h, spec.reserve((row_words + own_words + 16) * 4 + ((size_t)nd * 5 + more_doubles) * 8 + 64));
+    rows_dev = spec.as<int32_t>();
+    *words = rows_dev + row_words;
+    int32_t *bad_dev = *words + own_words;
+    isat_dev = reinterpret_cast<double *>(bad_dev + 16);
+    nvt_dev = isat_dev + nd;
+    hist = nvt_dev + nd;
+    gk = hist + nd;
+    ik = gk + nd;
+    *doubles = ik + nd;
+    if (nd == 0) return NODAL_OK;
+    std::vector<int32_t> r32((size_t)nd);
+    for (int64_t i = 0; i < nd; ++i) r32[(size_t)i] = (int32_t)rows[i];
+    NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(isat_dev, isat, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+    NODAL_HIP_TRY(h, hipMemcpyAsync(nvt_dev, nvt, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+    int32_t bad = 0;
+    NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
+    k_newton_check<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->type.as<uint8_t>(), isat_dev, nvt_dev, bad_dev);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copies above are done too, r32 may end)
+    if (bad & 1) return fail("a diode row that is not a resistor (R)");
+    if (bad & 2) return fail("i_sat and n_vt must be positive and finite");
+    int64_t ncon = 0;
+    return grp::build_lists(h, DiodeLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), nd}, (int64_t)h->K, &nent, &ncon,
+                            list_none, list_node, list_ptr, list_con, nullptr, nullptr);
+}
+
+int DiodeSet::start(nodal_ctx *h, const double *x, double *vh) const {
+    if (nd == 0) return NODAL_OK;
+    k_newton_start<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), x, vh);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+int DiodeSet::linearise(nodal_ctx *h, const double *vh, double *value) const {
+    if (nd == 0) return NODAL_OK;
+    k_newton_linearise<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, isat_dev, nvt_dev, gmin, vh, value, hist, gk, ik);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+int DiodeSet::fill(nodal_ctx *h, double v, double *column) const {
+    if (nd == 0) return NODAL_OK;
+    k_newton_fill<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, v, column);
+    NODAL_HIP_TRY(h, hipGetLastError());
+    return NODAL_OK;
+}
+
+int DiodeSet::add_currents(nodal_ctx *h, double *rhs) const {
+    return signed_list_add(h, nent, node->as<int32_t>(), ptr->as<int32_t>(), con->as<uint32_t>(), hist, rhs);
+}
+
+int DiodeSet::linearise_and_assemble(nodal_ctx *h, const double *vh, bool *overflowed, double *ms_stamp) const {
+    double *value = const_cast<double *>(assembled_values(h));
+    NODAL_TRY(linearise(h, vh, value));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int sn = stamp_numeric(h, h->member, nullptr);
+    *ms_stamp += ms_since(t0);
+    *overflowed = sn == NODAL_E_ZERO_RESISTANCE;  // (g overflowed: 1 / g == 0)
+    if (!*overflowed) return sn;
+    NODAL_TRY(fill(h, 1.0, value));
+    return stamp_numeric(h, h->member, nullptr);
+}
+
+// ---- one Newton iteration (ctx.h) ----
+int newton_iteration(nodal_ctx *h, const DiodeSet &D, TransientSolver &ts, bool dense, bool assemble, bool count_moved,
+                     const double *vh_now, double *vh_next, double *rhs, double *xk, unsigned long long *rec, double reltol,
+                     double vntol, double abstol, double *iterate_host, double *ms_matrix, double *ms_symbolic, NewtonStep *step) {
+    const int64_t n = h->n, nd = D.nd;
+    hipStream_t st = h->stream;
+    *step = NewtonStep();
+    double ms_stamp = 0.0, ms_begin = 0.0, ms_step = 0.0;
+    if (assemble) {
+        bool overflowed = false;
+        NODAL_TRY(D.linearise_and_assemble(h, vh_now, &overflowed, &ms_stamp));
+        if (overflowed) {
+            step->outcome = NEWTON_OVERFLOWED;
+            return NODAL_OK;
+        }
+    } else {  // (the value column gets the bits it holds; J, g_k and i_k are this iteration's)
+        NODAL_TRY(D.linearise(h, vh_now, const_cast<double *>(assembled_values(h))));
+    }
+    NODAL_TRY(D.add_currents(h, rhs));
+    // the route and its matrix work: anew where the matrix moved, kept where numeric_epoch stands
+    bool dead = false;
+    NODAL_TRY(transient_solver_begin(h, ts, dense, 1, &dead, &ms_begin));
+    if (ts.route == TR_ROUTE_LU && ms_begin > 0.0) *ms_symbolic += slu_analysis_ms(h);
+    if (dead) {
+        *ms_matrix += ms_stamp + ms_begin;
+        step->outcome = NEWTON_DEAD;
+        return NODAL_OK;
+    }
+    int32_t inf = 0;
+    double resid = 0.0;  // where the solver judged on the host
+    NODAL_TRY(transient_solver_step(h, ts, rhs, xk, &inf, &step->it, &resid, &step->judged, &ms_step));
+    *ms_matrix += ms_stamp + ms_begin + ms_step;
+    if (ts.route == TR_ROUTE_MG && ts.mg_setup && !ts.direct && !sagg_refreshed(h)) *ms_symbolic += ms_step;
+    if (inf > 0) {
+        step->outcome = NEWTON_SINGULAR;
+        return NODAL_OK;
+    }
+    // (a multigrid step handed on, or a sparse LU step redone: the sparse direct solve)
+    step->route = ts.route == TR_ROUTE_DENSE ? 0 : (ts.direct || (ts.route == TR_ROUTE_LU && !step->judged)) ? 3
+                  : ts.route == TR_ROUTE_LU ? 1 : 2;
+    if (!step->judged) NODAL_HIP_TRY(h, hipMemcpyAsync(rec + 3, ts.norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
+    if (nd > 0) {
+        const auto update = count_moved ? k_newton_update<true> : k_newton_update<false>;
+        update<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, D.rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), D.isat_dev, D.nvt_dev,
+                                                  D.gmin, reltol, vntol, abstol, xk, vh_now, D.gk, D.ik, vh_next, rec,
+                                                  assembled_values(h));
+        NODAL_HIP_TRY(h, hipGetLastError());
+    }
+    if (iterate_host) NODAL_HIP_TRY(h, hipMemcpyAsync(iterate_host, xk, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    NODAL_TRY(nodal_read_words(h, step->words, rec, sizeof step->words));  // (the iteration's one look besides the solver's)
+    memcpy(&step->dvmax, &step->words[2], 8);
+    memcpy(&step->scaled, &step->words[3], 8);
+    if (step->judged) step->scaled = resid;
+    step->outcome = !(std::isfinite(step->dvmax) && std::isfinite(step->scaled)) ? NEWTON_NOT_FINITE  // (an iterate that overflowed)
+                    : step->words[0] == 0                                        ? NEWTON_CONVERGED
+                                                                                 : NEWTON_GO_ON;
+    return NODAL_OK;
+}
+
 int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, const double *isat, const double *nvt,
                double gmin, int32_t nsrc, const double *x0, int32_t max_iter, double reltol, double vntol, double abstol,
                const NewtonOutputs &out, double *ms_matrix, double *ms_symbolic) {
     const int64_t n = h->n;
-    const int32_t K = h->K;
     hipStream_t st = h->stream;
     const double nan = __builtin_nan("");
     *ms_matrix = *ms_symbolic = 0.0;
@@ -140,25 +294,23 @@ int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, 
         if (out.record)
             for (int q = 0; q < 4; ++q) out.record[4 * (size_t)k + q] = 0.0;
     }
-    for (int64_t i = 0; i < nd; ++i)
-        if (diode_rows[i] < 0 || diode_rows[i] >= h->ncomp) return nodal_fail(h, NODAL_E_INVALID, "newton: diode row out of range");
-    if (nd > 0 && K == 0) return nodal_fail(h, NODAL_E_INVALID, "newton: diodes on a network without nodes");
+
+    // ---- once per call: the diodes, the buffers ----
+    const bool keep_vh = out.vh != nullptr;
+    const size_t vh_slots = keep_vh ? (size_t)max_iter + 1 : 2;
+    // tr_spec behind the diodes: v, i, g of the answer [nd] each | the limited voltages [vh_slots][nd] | the records
+    // [max_iter][5]
+    DiodeSet D;
+    int32_t *no_words = nullptr;
+    double *ans = nullptr;
+    NODAL_TRY(D.prepare(h, "newton: ", nd, diode_rows, isat, nvt, gmin, h->tr_spec, h->tr_none, h->tr_node, h->tr_ptr, h->tr_con, 0,
+                        (size_t)nd * (3 + vh_slots) + NEWTON_REC_WORDS * (size_t)max_iter, &no_words, &ans));
     if (n == 0) {  // (nothing to solve: one iteration that moves nothing)
         *out.iterations = 1;
         *out.converged = 1;
         return NODAL_OK;
     }
-
-    // ---- once per call: rows and parameters up, the node lists, the buffers ----
-    const bool keep_vh = out.vh != nullptr;
-    const size_t row_words = ((size_t)nd + 15) & ~(size_t)15;
-    const size_t vh_slots = keep_vh ? (size_t)max_iter + 1 : 2;
-    // tr_spec: diode rows | bad flag (16 words) | i_sat, n_vt, J, g_k, i_k [nd] each | v, i, g of the answer [nd] each |
-    // the limited voltages [vh_slots][nd] | the records [max_iter][4]
-    NODAL_HIP_TRY(h, h->tr_spec.reserve((row_words + 16) * 4 + ((size_t)nd * (8 + vh_slots) + 4 * (size_t)max_iter) * 8 + 64));
-    int32_t *rows_dev = h->tr_spec.as<int32_t>(), *bad_dev = rows_dev + row_words;
-    double *isat_dev = reinterpret_cast<double *>(bad_dev + 16), *nvt_dev = isat_dev + nd, *hist = nvt_dev + nd,
-           *gk = hist + nd, *ik = gk + nd, *ans = ik + nd, *vh_dev = ans + 3 * nd;
+    double *vh_dev = ans + 3 * nd;
     unsigned long long *rec_dev = reinterpret_cast<unsigned long long *>(vh_dev + vh_slots * (size_t)nd);
     auto vh_at = [&](int32_t k) { return vh_dev + (keep_vh ? (size_t)k : (size_t)(k & 1)) * (size_t)nd; };
     // tr_vec: the iterate | right-hand side | defect | correction | the judge's norms
@@ -166,118 +318,49 @@ int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, 
     double *xk = h->tr_vec.as<double>(), *bvec = xk + n, *rvec = bvec + n, *dvec = rvec + n, *norms = dvec + n;
     if (x0) NODAL_HIP_TRY(h, hipMemcpyAsync(xk, x0, (size_t)n * 8, hipMemcpyHostToDevice, st));
     else NODAL_HIP_TRY(h, hipMemsetAsync(xk, 0, (size_t)n * 8, st));
-    NODAL_HIP_TRY(h, hipMemsetAsync(rec_dev, 0, 4 * (size_t)max_iter * 8, st));
-    int64_t nent = 0, ncon = 0;
-    if (nd > 0) {
-        std::vector<int32_t> r32((size_t)nd);
-        for (int64_t i = 0; i < nd; ++i) r32[(size_t)i] = (int32_t)diode_rows[i];
-        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(isat_dev, isat, (size_t)nd * 8, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(nvt_dev, nvt, (size_t)nd * 8, hipMemcpyHostToDevice, st));
-        int32_t bad = 0;
-        NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, st));
-        k_newton_check<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->type.as<uint8_t>(), isat_dev, nvt_dev, bad_dev);
-        NODAL_HIP_TRY(h, hipGetLastError());
-        NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));  // (waits: the copies above are done too)
-        if (bad & 1) return nodal_fail(h, NODAL_E_INVALID, "newton: a diode row that is not a resistor (R)");
-        if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, "newton: i_sat and n_vt must be positive and finite");
-        NODAL_TRY(grp::build_lists(h, DiodeLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), nd}, (int64_t)K, &nent,
-                                   &ncon, h->tr_none, h->tr_node, h->tr_ptr, h->tr_con, nullptr, nullptr));
-        k_newton_start<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), xk, vh_at(0));
-        NODAL_HIP_TRY(h, hipGetLastError());
-    }
-    NODAL_WAIT_STREAM(h, st);  // (x0 is the caller's, r32 ends here)
-    double *value = const_cast<double *>(assembled_values(h));
+    NODAL_HIP_TRY(h, hipMemsetAsync(rec_dev, 0, NEWTON_REC_WORDS * (size_t)max_iter * 8, st));
+    NODAL_TRY(D.start(h, xk, vh_at(0)));
+    NODAL_WAIT_STREAM(h, st);  // (x0 is the caller's)
 
     // ---- the iterations ----
     bool dead = false, overflow = false;
     int32_t done = 0;
     for (int32_t k = 0; k < max_iter; ++k) {
-        double ms_stamp = 0.0, ms_begin = 0.0, ms_step = 0.0;
-        if (nd > 0) {  // (without diodes the matrix does not move: what the handle kept of it serves)
-            k_newton_linearise<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, isat_dev, nvt_dev, gmin, vh_at(k), value, hist,
-                                                                  gk, ik);
-            NODAL_HIP_TRY(h, hipGetLastError());
-            const auto t0 = std::chrono::steady_clock::now();
-            const int sn = stamp_numeric(h, h->member, nullptr);
-            ms_stamp = ms_since(t0);
-            if (sn == NODAL_E_ZERO_RESISTANCE) {  // (g overflowed: 1 / g == 0)
-                overflow = true;
-                done = k + 1;
-                break;
-            }
-            NODAL_TRY(sn);
-        }
         NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)n * 8, st));
         NODAL_TRY(stamp_rhs_multi(h, h->sw_slot.as<int32_t>(), h->sw_vals.as<double>(), nsrc, 1, bvec, 1, 0));
-        NODAL_TRY(signed_list_add(h, nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(), h->tr_con.as<uint32_t>(), hist, bvec));
-        // the route and its matrix work, anew: the matrix moved
+        // the route and its matrix work, anew: the matrix moved (without diodes it does not: what the handle kept serves)
         TransientSolver ts;
         ts.s = h;
         ts.lu_epoch = &h->tr_lu_epoch;
         ts.rvec = rvec;
         ts.dvec = dvec;
         ts.norms = norms;
-        NODAL_TRY(transient_solver_begin(h, ts, dense, 1, &dead, &ms_begin));
-        if (ts.route == TR_ROUTE_LU && ms_begin > 0.0) *ms_symbolic += slu_analysis_ms(h);
+        NewtonStep s;
         done = k + 1;
-        if (dead) {
-            *ms_matrix += ms_stamp + ms_begin;
-            break;
-        }
-        int32_t inf = 0, it = 0;
-        double resid = 0.0;
-        bool judged = false;  // resid is on the host already
-        NODAL_TRY(transient_solver_step(h, ts, bvec, xk, &inf, &it, &resid, &judged, &ms_step));
-        *ms_matrix += ms_stamp + ms_begin + ms_step;
-        if (ts.route == TR_ROUTE_MG && ts.mg_setup && !ts.direct && !sagg_refreshed(h)) *ms_symbolic += ms_step;
-        if (inf > 0) {
-            if (dense) return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
-            dead = true;
-            break;
-        }
-        if (out.iters) out.iters[k] = it;
-        h->last_iterations = it;
-        if (out.route)  // (a multigrid step handed on, or a sparse LU step redone: the sparse direct solve)
-            out.route[k] = ts.route == TR_ROUTE_DENSE ? 0 : (ts.direct || (ts.route == TR_ROUTE_LU && !judged)) ? 3
-                           : ts.route == TR_ROUTE_LU ? 1 : 2;
-        unsigned long long *rec = rec_dev + 4 * (size_t)k;
-        if (!judged) NODAL_HIP_TRY(h, hipMemcpyAsync(rec + 3, norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
-        if (nd > 0) {
-            k_newton_update<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), isat_dev,
-                                                               nvt_dev, gmin, reltol, vntol, abstol, xk, vh_at(k), gk, ik,
-                                                               vh_at(k + 1), rec);
-            NODAL_HIP_TRY(h, hipGetLastError());
-        }
-        if (out.iterates) NODAL_HIP_TRY(h, hipMemcpyAsync(out.iterates + (size_t)k * n, xk, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        unsigned long long words[4];
-        NODAL_TRY(nodal_read_words(h, words, rec, 32));  // (the iteration's one look at the device besides the solver's)
-        double dvmax, scaled;
-        memcpy(&dvmax, &words[2], 8);
-        memcpy(&scaled, &words[3], 8);
-        if (judged) scaled = resid;
+        NODAL_TRY(newton_iteration(h, D, ts, dense, nd > 0, false, vh_at(k), vh_at(k + 1), bvec, xk,
+                                   rec_dev + NEWTON_REC_WORDS * (size_t)k, reltol, vntol, abstol,
+                                   out.iterates ? out.iterates + (size_t)k * n : nullptr, ms_matrix, ms_symbolic, &s));
+        if (s.outcome == NEWTON_SINGULAR && dense)
+            return nodal_fail(h, NODAL_E_SINGULAR, "singular matrix: a zero pivot or a floating sub-network");
+        overflow = s.outcome == NEWTON_OVERFLOWED;
+        dead = s.outcome == NEWTON_DEAD || s.outcome == NEWTON_SINGULAR;
+        if (!s.solved()) break;
+        if (out.iters) out.iters[k] = s.it;
+        h->last_iterations = s.it;
+        if (out.route) out.route[k] = s.route;
         if (out.record) {
             double *row = out.record + 4 * (size_t)k;
-            row[0] = (double)words[0];
-            row[1] = (double)words[1];
-            row[2] = dvmax;
-            row[3] = scaled;
+            row[0] = (double)s.words[0];
+            row[1] = (double)s.words[1];
+            row[2] = s.dvmax;
+            row[3] = s.scaled;
         }
-        if (!(std::isfinite(dvmax) && std::isfinite(scaled))) break;  // (an iterate that overflowed: not converged)
-        if (words[0] == 0) {
-            *out.converged = 1;
-            break;
-        }
+        if (s.outcome == NEWTON_CONVERGED) *out.converged = 1;
+        if (s.outcome != NEWTON_GO_ON) break;
     }
     *out.iterations = done;
 
     // ---- after the last iteration ----
-    if (overflow) {
-        // the value column holds a zero: 1.0 in every companion row and one more assembly, so that the handle stays usable
-        k_newton_fill<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, 1.0, value);
-        NODAL_HIP_TRY(h, hipGetLastError());
-        NODAL_TRY(stamp_numeric(h, h->member, nullptr));
-    }
     const bool lost = dead || overflow;  // no state to report
     if (lost && done >= 1) {
         if (out.info) out.info[done - 1] = dead ? 1 : 0;
@@ -287,8 +370,8 @@ int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, 
             for (int64_t i = 0; i < n; ++i) out.iterates[(size_t)(done - 1) * n + i] = nan;
     }
     if (nd > 0 && !lost && (out.v || out.i || out.g)) {
-        k_newton_outputs<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), isat_dev,
-                                                            nvt_dev, gmin, xk, ans, ans + nd, ans + 2 * nd);
+        k_newton_outputs<<<groups_of(nd, TTB), TTB, 0, st>>>(nd, D.rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), D.isat_dev,
+                                                            D.nvt_dev, gmin, xk, ans, ans + nd, ans + 2 * nd);
         NODAL_HIP_TRY(h, hipGetLastError());
         if (out.v) NODAL_HIP_TRY(h, hipMemcpyAsync(out.v, ans, (size_t)nd * 8, hipMemcpyDeviceToHost, st));
         if (out.i) NODAL_HIP_TRY(h, hipMemcpyAsync(out.i, ans + nd, (size_t)nd * 8, hipMemcpyDeviceToHost, st));
@@ -310,37 +393,5 @@ int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, 
             if (p)
                 for (int64_t d = 0; d < nd; ++d) p[d] = nan;
     }
-    return NODAL_OK;
-}
-
-// ---- the same lanes for nodal_transient_nl (transient_nl.hip), which nests this loop inside every time step ----
-int newton_check_diodes(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
-                        int32_t *bad_dev, const char *not_r, const char *not_positive) {
-    int32_t bad = 0;
-    NODAL_HIP_TRY(h, hipMemsetAsync(bad_dev, 0, 4, h->stream));
-    k_newton_check<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, h->type.as<uint8_t>(), isat_dev, nvt_dev, bad_dev);
-    NODAL_HIP_TRY(h, hipGetLastError());
-    NODAL_TRY(nodal_read_words(h, &bad, bad_dev, 4));
-    if (bad & 1) return nodal_fail(h, NODAL_E_INVALID, not_r);
-    if (bad & 2) return nodal_fail(h, NODAL_E_INVALID, not_positive);
-    return NODAL_OK;
-}
-
-int newton_launch_start(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *x, double *vh) {
-    k_newton_start<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), x, vh);
-    NODAL_HIP_TRY(h, hipGetLastError());
-    return NODAL_OK;
-}
-
-int newton_launch_linearise(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, const double *isat_dev, const double *nvt_dev,
-                            double gmin, const double *vh, double *value, double *hist, double *gk, double *ik) {
-    k_newton_linearise<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, isat_dev, nvt_dev, gmin, vh, value, hist, gk, ik);
-    NODAL_HIP_TRY(h, hipGetLastError());
-    return NODAL_OK;
-}
-
-int newton_launch_fill(nodal_ctx *h, int64_t nd, const int32_t *rows_dev, double fill, double *value) {
-    k_newton_fill<<<groups_of(nd, TTB), TTB, 0, h->stream>>>(nd, rows_dev, fill, value);
-    NODAL_HIP_TRY(h, hipGetLastError());
     return NODAL_OK;
 }

@@ -10,11 +10,10 @@
 //     J^T lambda = c,   J = dF/dx = G + S diag(g(v)) S^T  at v = S^T x,   dL/dp = -lambda^T dF/dp
 // and J is exactly the matrix nodal_newton_dc assembles, linearised at the answer itself instead of at the last limited
 // voltages (those are one step behind: with default tolerances the difference shows in the fourth digit of a gradient).
-// So the call is, on the handle's stream,
-//     k_newton_start        v = x(a) - x(b) per diode
-//     k_newton_linearise    1 / g(v) into the companion rows of the value column, J_hist = g v - i(v)
-//     stamp_numeric         G from the value column, the symbolic phase kept
-//     stamp_rhs_multi, k_signed_list_add, the block judge on one column
+// So the call is, on the handle's stream, the DiodeSet's lanes (ctx.h; newton.hip's header describes each launch)
+//     start, linearise_and_assemble
+//                           v = x(a) - x(b) per diode, 1 / g(v) into the value column, J_hist = g v - i(v), G assembled
+//     stamp_rhs_multi, add_currents, the block judge on one column
 //                           the right-hand side of a Newton iteration at x; because the linearisation is at x the scaled
 //                           residual of x against it is the nonlinear KCL defect G x + S i(v) - A: *op_resid_out
 //     the solve             transient_solver_begin / transient_solver_step on adjoint_context(h): the handle itself when
@@ -29,8 +28,6 @@
 //     k_gradient_sources    lambda(a) - lambda(b) of an A row, lambda(K + k) of an E row
 // No floating-point atomics: a repeated call gives the same bits.
 #include "diode_lanes.h"
-#include "group.h"
-#include "table_rows.h"
 
 #include <cmath>
 
@@ -120,7 +117,6 @@ int newton_gradient_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *dio
                         double gmin, int32_t nsrc, const double *x, const double *cotangent, const NewtonGradientOutputs &out,
                         double *ms_matrix, double *ms_symbolic) {
     const int64_t n = h->n, ncomp = h->ncomp;
-    const int32_t K = h->K;
     hipStream_t st = h->stream;
     const double nan = __builtin_nan("");
     *ms_matrix = *ms_symbolic = 0.0;
@@ -135,21 +131,17 @@ int newton_gradient_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *dio
     fill(out.op_resid, 1, 0.0);
     h->have_x = false;
     h->last_iterations = 0;
-    for (int64_t i = 0; i < nd; ++i)
-        if (diode_rows[i] < 0 || diode_rows[i] >= ncomp)
-            return nodal_fail(h, NODAL_E_INVALID, "operating-point gradient: diode row out of range");
-    if (nd > 0 && K == 0) return nodal_fail(h, NODAL_E_INVALID, "operating-point gradient: diodes on a network without nodes");
-    if (n == 0) return NODAL_OK;  // (every lead is ground: nothing depends on anything)
-
-    // ---- rows and parameters up, the node lists, the buffers ----
-    const size_t row_words = ((size_t)nd + 15) & ~(size_t)15;
+    // ---- the diodes (rows and parameters up, the node list), the buffers ----
     const int64_t groups = groups_of(nd, OTB);
-    // tr_spec: diode rows | bad flag (16 words) | i_sat, n_vt, J, g, i, v, d/di_sat, d/dn_vt [nd] each | the workgroups'
-    // gmin sums | d/dgmin, the operating point's residual, the adjoint solve's
-    NODAL_HIP_TRY(h, h->tr_spec.reserve((row_words + 16) * 4 + ((size_t)nd * 8 + (size_t)groups + 4) * 8 + 64));
-    int32_t *rows_dev = h->tr_spec.as<int32_t>(), *bad_dev = rows_dev + row_words;
-    double *isat_dev = reinterpret_cast<double *>(bad_dev + 16), *nvt_dev = isat_dev + nd, *hist = nvt_dev + nd, *gk = hist + nd,
-           *ik = gk + nd, *v = ik + nd, *gis = v + nd, *gnv = gis + nd, *partials = gnv + nd, *words = partials + groups;
+    // tr_spec behind the diodes: v, d/di_sat, d/dn_vt [nd] each | the workgroups' gmin sums | d/dgmin, the operating
+    // point's residual, the adjoint solve's
+    DiodeSet D;
+    int32_t *no_words = nullptr;
+    double *v = nullptr;
+    NODAL_TRY(D.prepare(h, "operating-point gradient: ", nd, diode_rows, isat, nvt, gmin, h->tr_spec, h->tr_none, h->tr_node,
+                        h->tr_ptr, h->tr_con, 0, (size_t)nd * 3 + (size_t)groups + 4, &no_words, &v));
+    if (n == 0) return NODAL_OK;  // (every lead is ground: nothing depends on anything)
+    double *gis = v + nd, *gnv = gis + nd, *partials = gnv + nd, *words = partials + groups;
     // tr_vec: x | right-hand side | defect | correction | cotangent | lambda | the judge's norms
     NODAL_HIP_TRY(h, h->tr_vec.reserve((size_t)6 * n * 8 + 5 * SLU_MULTI * 8 + 256));
     double *xk = h->tr_vec.as<double>(), *bvec = xk + n, *rvec = bvec + n, *dvec = rvec + n, *cvec = dvec + n, *lam = cvec + n,
@@ -162,41 +154,14 @@ int newton_gradient_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *dio
     NODAL_HIP_TRY(h, hipMemcpyAsync(cvec, cotangent, (size_t)n * 8, hipMemcpyHostToDevice, st));
     NODAL_HIP_TRY(h, hipMemsetAsync(words, 0, 3 * 8, st));
     NODAL_HIP_TRY(h, hipMemsetAsync(grad_dev, 0, acc_words * 8, st));
-    int64_t nent = 0, ncon = 0;
-    if (nd > 0) {
-        std::vector<int32_t> r32((size_t)nd);
-        for (int64_t i = 0; i < nd; ++i) r32[(size_t)i] = (int32_t)diode_rows[i];
-        NODAL_HIP_TRY(h, hipMemcpyAsync(rows_dev, r32.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(isat_dev, isat, (size_t)nd * 8, hipMemcpyHostToDevice, st));
-        NODAL_HIP_TRY(h, hipMemcpyAsync(nvt_dev, nvt, (size_t)nd * 8, hipMemcpyHostToDevice, st));
-        // (waits: the copies above are done too)
-        NODAL_TRY(newton_check_diodes(h, nd, rows_dev, isat_dev, nvt_dev, bad_dev,
-                                      "operating-point gradient: a diode row that is not a resistor (R)",
-                                      "operating-point gradient: i_sat and n_vt must be positive and finite"));
-        NODAL_TRY(grp::build_lists(h, DiodeLeads{rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), nd}, (int64_t)K, &nent,
-                                   &ncon, h->tr_none, h->tr_node, h->tr_ptr, h->tr_con, nullptr, nullptr));
-        NODAL_TRY(newton_launch_start(h, nd, rows_dev, xk, v));
-    }
-    NODAL_WAIT_STREAM(h, st);  // (x and the cotangent are the caller's, r32 ends here)
-    double *value = const_cast<double *>(assembled_values(h));
+    NODAL_TRY(D.start(h, xk, v));
+    NODAL_WAIT_STREAM(h, st);  // (x and the cotangent are the caller's)
 
     // ---- J at x itself, and what x leaves of the nonlinear equations ----
     double ms_stamp = 0.0, ms_begin = 0.0, ms_step = 0.0;
     bool overflow = false;
-    if (nd > 0) {  // (without diodes the matrix does not move: what the handle kept of it serves)
-        NODAL_TRY(newton_launch_linearise(h, nd, rows_dev, isat_dev, nvt_dev, gmin, v, value, hist, gk, ik));
-        const auto t0 = std::chrono::steady_clock::now();
-        const int sn = stamp_numeric(h, h->member, nullptr);
-        ms_stamp = ms_since(t0);
-        if (sn == NODAL_E_ZERO_RESISTANCE) {
-            // g overflowed (1 / g == 0): 1.0 in every companion row and one more assembly, so that the handle stays usable
-            overflow = true;
-            NODAL_TRY(newton_launch_fill(h, nd, rows_dev, 1.0, value));
-            NODAL_TRY(stamp_numeric(h, h->member, nullptr));
-        } else {
-            NODAL_TRY(sn);
-        }
-    }
+    // (without diodes the matrix does not move: what the handle kept of it serves)
+    if (nd > 0) NODAL_TRY(D.linearise_and_assemble(h, v, &overflow, &ms_stamp));
     bool dead = false;
     int32_t inf = 0, it = 0;
     double resid = 0.0;
@@ -204,7 +169,7 @@ int newton_gradient_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *dio
     if (!overflow) {
         NODAL_HIP_TRY(h, hipMemsetAsync(bvec, 0, (size_t)n * 8, st));
         NODAL_TRY(stamp_rhs_multi(h, h->sw_slot.as<int32_t>(), h->sw_vals.as<double>(), nsrc, 1, bvec, 1, 0));
-        NODAL_TRY(signed_list_add(h, nent, h->tr_node.as<int32_t>(), h->tr_ptr.as<int32_t>(), h->tr_con.as<uint32_t>(), hist, bvec));
+        NODAL_TRY(D.add_currents(h, bvec));
         NODAL_TRY(csr_judge_block(h, xk, bvec, 1, 0, 1, norms));
         NODAL_HIP_TRY(h, hipMemcpyAsync(words + 1, norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
 
@@ -236,12 +201,12 @@ int newton_gradient_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *dio
         if (!judged) NODAL_HIP_TRY(h, hipMemcpyAsync(words + 2, norms + 4 * SLU_MULTI, 8, hipMemcpyDeviceToDevice, st));
         if (ncomp > 0) {
             NODAL_TRY(grad_launch_table(h, 1, lam, 1, 0, xk, 1, 0, grad_dev));
-            if (nd > 0) NODAL_TRY(newton_launch_fill(h, nd, rows_dev, 0.0, grad_dev));
+            NODAL_TRY(D.fill(h, 0.0, grad_dev));
             NODAL_HIP_TRY(h, hipMemcpyAsync(out.grad, grad_dev, (size_t)ncomp * 8, hipMemcpyDeviceToHost, st));
         }
         if (nd > 0) {
-            k_opgrad_diodes<<<(unsigned)groups, OTB, 0, st>>>(nd, rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), isat_dev,
-                                                             nvt_dev, v, lam, gis, gnv, partials);
+            k_opgrad_diodes<<<(unsigned)groups, OTB, 0, st>>>(nd, D.rows_dev, h->a.as<int32_t>(), h->b.as<int32_t>(), D.isat_dev,
+                                                             D.nvt_dev, v, lam, gis, gnv, partials);
             k_opgrad_total<<<1, OTB, 0, st>>>(groups, partials, words);
             NODAL_HIP_TRY(h, hipGetLastError());
             if (out.grad_isat) NODAL_HIP_TRY(h, hipMemcpyAsync(out.grad_isat, gis, (size_t)nd * 8, hipMemcpyDeviceToHost, st));

@@ -41,7 +41,7 @@ from tools.operating_point_probe import DIODES, GMIN, SPICE, seeded_diodes  # no
 from tools.transient_probe import DT, assembled, network, timed  # noqa: E402
 
 LAUNCHES_PER_ITERATION = {"k_newton_linearise": 1, "copy rhs = base (device to device)": 1, "k_signed_list_add": 1,
-                          "k_tnl_update": 1, "besides": "stamp_numeric (when the matrix moved) and the solver's own"}
+                          "k_newton_update<true>": 1, "besides": "stamp_numeric (when the matrix moved) and the solver's own"}
 MAX_ITER = 50
 
 
