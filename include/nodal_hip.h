@@ -353,6 +353,51 @@ int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t
                     double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out, double *record_out,
                     int32_t *info_out, int32_t *iters_out, int32_t *route_out, int32_t *iterations, int32_t *converged);
 
+/* ---- nonlinear DC analysis with bipolar transistors: Ebers-Moll in its transport form, by the same Newton loop ----
+ * nodal_newton_dc's arguments and rules, plus ntr transports.  A bipolar transistor is two junction diodes, plain members
+ * of diode_rows / i_sat / n_vt (the caller gives them i_sat = i_s / beta_f and i_s / beta_r), plus one transport current
+ *   i_T = i_s[t] (exp(v_f / n_f) - exp(v_r / n_r))
+ * from lead a to lead b through the element, v_f, v_r the voltages and n_f, n_r the n_vt of the diodes junction[t][0] = jf
+ * and junction[t][1] = jr.  NPN or PNP is the caller's choice of leads alone.  The handle's table holds, beside the diodes'
+ * R rows, two rows of type NODAL_T_GM per transport, gm_rows[t][0] (forward) and gm_rows[t][1] (reverse): both with the
+ * transport's leads a, b, and c, d = lead a, lead b (anode, cathode) of the row of diode jf, respectively jr; their table
+ * values are overwritten.  gmin stays on the junctions; a transport has none, is not limited and has no state word.
+ * Iteration k linearises every diode as nodal_newton_dc does and every transport at the SAME limited voltages
+ * vhf = vh[jf], vhr = vh[jr]:
+ *   ef = exp(vhf / n_f),  er = exp(vhr / n_r),  gmf = (i_s ef) / n_f,  gmr = (i_s er) / n_r,  iT = i_s ef - i_s er
+ *   JT = gmf vhf - gmr vhr - iT
+ * every product and quotient rounded on its own, the sums from left to right.  gmf goes into the forward row's value and
+ * -gmr into the reverse row's, G is assembled, and JT is injected into lead a and drawn from lead b: a node's right-hand
+ * side gets the J of its diodes in ascending order and then the JT of its transports in ascending order.  After the solve,
+ * per transport with the raw vf, vr of x_{k+1}:
+ *   iT(v) = i_s exp(vf / n_f) - i_s exp(vr / n_r),  ihat = iT + gmf (vf - vhf) - gmr (vr - vhr)
+ *   passes when |iT(v) - ihat| <= reltol max(|iT(v)|, |ihat|) + abstol      (false with a NaN anywhere)
+ * The loop ends when no diode and no transport fails its test (*converged = 1), and otherwise as nodal_newton_dc's does; a
+ * gmf or gmr that is not finite is an overflow like a g that overflows (*converged = 0, NaN in the outputs).
+ *   it_out, gmf_out, gmr_out [ntr]  iT, gmf, gmr at the raw junction voltages of the last iterate.  The terminal currents
+ *                                   are the caller's sums: for an NPN (a = C, b = E, jf = B->E, jr = B->C), positive INTO
+ *                                   the terminal, I_C = iT - i[jr], I_B = i[jf] + i[jr], I_E = -(iT + i[jf])
+ *   record_out [max_iter][5]        nodal_newton_dc's four words and the transports that failed the test
+ * The other outputs are nodal_newton_dc's; vh_out has a column per diode, the junctions among them.  Routes are
+ * nodal_newton_dc's: n <= 64 the dense panel, everything else the sparse LU factored anew on its kept analysis -- a
+ * network with transports never takes the multigrid route, because GM rows make it non-passive.  ntr == 0 is
+ * nodal_newton_dc: the same launches and the same bits (the record's fifth word 0.0).
+ * NODAL_E_INVALID, besides nodal_newton_dc's: ntr < 0, a NULL array with ntr > 0, a gm_rows entry out of range or not of
+ * type NODAL_T_GM, two rows of a transport that do not share their a, b, a row whose c, d are not the leads a, b of its
+ * junction's diode row, a junction index outside [0, ndiode), an i_s that is not > 0 and finite.
+ * Host waits: once per call the transports' check (one word); per iteration nodal_newton_dc's and one more word behind
+ * the assembly's status words, when the stream has drained already (whether a gmf or gmr overflowed).  The transports'
+ * count is an integer atomicAdd -- integer atomics only: a repeated call gives the same bits.  Afterwards the handle is as
+ * nodal_newton_dc leaves it, the GM rows of the value column holding gmf, -gmr of the last linearisation (0.0 after an
+ * overflow, beside 1.0 in the diode rows). */
+int nodal_newton_dc_bjt(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                        const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                        const double *x0, int32_t max_iter, double reltol, double vntol, double abstol, int64_t ntr,
+                        const int64_t *gm_rows, const int32_t *junction, const double *i_s, double *x_out, double *v_out,
+                        double *i_out, double *g_out, double *it_out, double *gmf_out, double *gmr_out, double *iterates_out,
+                        double *vh_out, double *record_out, int32_t *info_out, int32_t *iters_out, int32_t *route_out,
+                        int32_t *iterations, int32_t *converged);
+
 /* ---- gradients through the operating point: the adjoint of the Newton solve (replaces finite differences, two whole
  *      Newton runs per parameter, and the host loop of download x, scipy transpose solve and numpy formulas; with the
  *      reference every such run is itself a rebuild and a .solve() per iteration, reference nodal/nodal.py:306-336) ----

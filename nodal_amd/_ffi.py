@@ -66,6 +66,10 @@ SIGNATURES = {
     "nodal_newton_dc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, _i64p, _f64p,
                                   _f64p, C.c_int32, C.c_double, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p, _f64p,
                                   _f64p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "nodal_newton_dc_bjt": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, _i64p,
+                                      _f64p, _f64p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int64, _i64p, _i32p,
+                                      _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p,
+                                      _i32p, _i32p, _i32p, _i32p]),
     "nodal_newton_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, _i64p,
                                         _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "nodal_transient_nl": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p, _f64p,
@@ -330,8 +334,10 @@ class Handle:
 
     # -- table ------------------------------------------------------------
     def upload(self, table):
-        # B == 0: resistors and current sources only -- the four columns they never read stay home
-        names = ("type", "value", "a", "b") if table.B == 0 else ("type", "value", "a", "b", "c", "d", "drv", "k")
+        # B == 0: resistors and current sources only -- the four columns they never read stay home (unless the table
+        # was given GM rows, which read their control leads without a branch unknown)
+        plain = table.B == 0 and not getattr(table, "controlled", False)
+        names = ("type", "value", "a", "b") if plain else ("type", "value", "a", "b", "c", "d", "drv", "k")
         cols = [np.ascontiguousarray(getattr(table, n)) for n in names]
         self._keep = cols
         t, v, a, b = cols[:4]
@@ -652,6 +658,53 @@ class Handle:
         return {"x": x, "v": v, "i": i, "g": g, "iterations": r, "converged": bool(converged.value), "record": record[:r],
                 "info": info[:r], "iters": iters[:r], "route": route[:r],
                 "iterates": iterates[:r] if keep_iterates else None, "vh": vh[:r + 1] if keep_iterates else None}
+
+    def newton_dc_bjt(self, diode_rows, i_sat, n_vt, gmin, gm_rows, junction, i_s, rows, values, x0, dense, max_iter, reltol,
+                      vntol, abstol, keep_iterates=False):
+        """newton_dc() with bipolar transistors (nodal_newton_dc_bjt): the handle's table holds two GM rows per
+        transport beside the diodes' rows -- gm_rows int64 [T, 2] (forward, reverse), junction int32 [T, 2] (indices into
+        the diodes: jf, jr), i_s [T].  Returns newton_dc()'s dict with record [iterations, 5] (the fifth word: transports
+        that failed the test) and it, gmf, gmr [T] of the last iterate.  T == 0 is newton_dc(), bit for bit."""
+        diode_rows = np.ascontiguousarray(diode_rows, dtype=np.int64)
+        i_sat, n_vt = (np.ascontiguousarray(v, dtype=np.float64) for v in (i_sat, n_vt))
+        D = len(diode_rows)
+        assert diode_rows.ndim == 1 and i_sat.shape == (D,) and n_vt.shape == (D,)
+        gm_rows = np.ascontiguousarray(gm_rows, dtype=np.int64).reshape(-1, 2)
+        junction = np.ascontiguousarray(junction, dtype=np.int32).reshape(-1, 2)
+        i_s = np.ascontiguousarray(i_s, dtype=np.float64)
+        T = len(gm_rows)
+        assert junction.shape == (T, 2) and i_s.shape == (T,)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert values.shape == (len(rows),)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            assert x0.shape == (self.n,)
+        max_iter = int(max_iter)
+        x = np.zeros(self.n, dtype=np.float64)
+        v, i, g = (np.zeros(D, dtype=np.float64) for _ in range(3))
+        it, gmf, gmr = (np.zeros(T, dtype=np.float64) for _ in range(3))
+        iterates = np.zeros((max_iter, self.n), dtype=np.float64) if keep_iterates else None
+        vh = np.zeros((max_iter + 1, D), dtype=np.float64) if keep_iterates else None
+        record = np.zeros((max_iter, 5), dtype=np.float64)
+        info, iters, route = (np.zeros(max_iter, dtype=np.int32) for _ in range(3))
+        iterations, converged = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.nodal_newton_dc_bjt(
+            self._h, int(dense), D, _ptr(diode_rows, C.c_int64) if D else None, _ptr(i_sat, C.c_double) if D else None,
+            _ptr(n_vt, C.c_double) if D else None, float(gmin), len(rows), _ptr(rows, C.c_int64) if len(rows) else None,
+            _ptr(values, C.c_double) if len(rows) else None, _ptr(x0, C.c_double) if x0 is not None else None, max_iter,
+            float(reltol), float(vntol), float(abstol), T, _ptr(gm_rows, C.c_int64) if T else None,
+            _ptr(junction, C.c_int32) if T else None, _ptr(i_s, C.c_double) if T else None,
+            _ptr(x, C.c_double) if self.n else None, _ptr(v, C.c_double) if D else None, _ptr(i, C.c_double) if D else None,
+            _ptr(g, C.c_double) if D else None, _ptr(it, C.c_double) if T else None, _ptr(gmf, C.c_double) if T else None,
+            _ptr(gmr, C.c_double) if T else None, _ptr(iterates, C.c_double) if keep_iterates and self.n else None,
+            _ptr(vh, C.c_double) if keep_iterates and D else None, _ptr(record, C.c_double), _ptr(info, C.c_int32),
+            _ptr(iters, C.c_int32), _ptr(route, C.c_int32), C.byref(iterations), C.byref(converged)))
+        r = iterations.value
+        return {"x": x, "v": v, "i": i, "g": g, "it": it, "gmf": gmf, "gmr": gmr, "iterations": r,
+                "converged": bool(converged.value), "record": record[:r], "info": info[:r], "iters": iters[:r],
+                "route": route[:r], "iterates": iterates[:r] if keep_iterates else None,
+                "vh": vh[:r + 1] if keep_iterates else None}
 
     def newton_gradient(self, diode_rows, i_sat, n_vt, gmin, rows, values, x, cotangent, dense, adjoints=False):
         """The adjoint of the Newton solve at the operating point x (nodal_newton_gradient), on a handle that holds the

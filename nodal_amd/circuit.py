@@ -99,6 +99,7 @@ class Circuit:
         self._transient_nl_dc = None
         self._transient_record = None
         self._newton_child = None
+        self._transistor_child = None
         self.currents = self.build_model()
 
     @classmethod
@@ -115,6 +116,7 @@ class Circuit:
         self._transient_nl_dc = None
         self._transient_record = None
         self._newton_child = None
+        self._transistor_child = None
         self.table = other.table if table is None else table
         self.currents = other.currents
         self._assemble(self.table)
@@ -380,6 +382,7 @@ class Circuit:
         self._transient_nl_dc = None
         self._transient_record = None
         self._newton_child = None
+        self._transistor_child = None
         self.table = table.with_values(new)
 
     def thevenin(self, ports, sources=True):
@@ -583,7 +586,7 @@ class Circuit:
                              final_junctions=junctions["vh"])))
 
     def operating_point(self, diodes, sources=None, initial=None, max_iter=100, reltol=1e-3, vntol=1e-6, abstol=1e-12,
-                        gmin=1e-12, keep_iterates=False):
+                        gmin=1e-12, keep_iterates=False, transistors=()):
         """The DC operating point of the circuit with diodes, by Newton's method on the device (nodal_newton_dc).
 
         `diodes` is a sequence of (name, i_sat, n_vt, anode, cathode) on nodes of the netlist: diode d carries
@@ -612,13 +615,35 @@ class Circuit:
         names of components, non-positive i_sat / n_vt, negative gmin / tolerances, max_iter < 1, and an `initial`
         that is not finite or of another shape.  No floating-point atomics: a repeated call gives the same bits.  The
         circuit itself -- its solution if any, table, G, A, what transient() and ac() keep -- is left as it was;
-        solve() is neither needed nor touched."""
-        from .operating_point import NewtonHistory, OperatingPoint, check_operating_point_arguments, resolve_diodes
+        solve() is neither needed nor touched.
+
+        `transistors` is a sequence of (name, "npn" | "pnp", i_s, beta_f, beta_r, n_vt, collector, base, emitter):
+        bipolar transistors by the Ebers-Moll model in its transport form (nodal_newton_dc_bjt) -- two junction diodes
+        `name.be`, `name.bc` (`name.eb`, `name.cb` for a PNP) with i_sat = i_s / beta_f and i_s / beta_r, which join the
+        call's diodes behind the caller's, limiting, gmin and test included, plus the transport current
+        i_T = i_s (exp(v_be / n_vt) - exp(v_bc / n_vt)) from collector to emitter (a PNP: every direction reversed),
+        linearised at the junctions' limited voltages and tested like a diode's current.  No Early effect, high
+        injection, resistances or charge storage.  `diodes=()` is legal with transistors.  The result then carries
+        `transistors`, `junction_voltages` [T, 2], `collector_currents`, `base_currents`, `emitter_currents` [T]
+        (positive into the terminal) and `transconductances` [T, 2]; `diodes`, `voltages`, `currents`, `conductances`
+        stay the caller's diodes; with keep_iterates `limited_voltages` has D + 2 T columns, the junctions' last; the
+        history has `transistors_not_converged`; linearised() is the hybrid-pi model; gradient() raises ValueError (the
+        adjoint with transistors is not implemented).  The companion child of such a call is a second one, keyed by
+        the transports' leads as well; its network is never passive, so the iterations take the dense panel
+        (n <= 64) or the sparse LU, never the multigrid.  ValueError as for diodes, for a kind other than
+        the two, and for i_s, beta_f, beta_r or n_vt that is not positive and finite."""
+        from .operating_point import (NewtonHistory, OperatingPoint, check_operating_point_arguments, resolve_diodes,
+                                      resolve_transistors)
         from .sweep import _row_map, resolve_sources
         h = self._handle
         max_iter, reltol, vntol, abstol, gmin, x0 = check_operating_point_arguments(max_iter, reltol, vntol, abstol, gmin,
                                                                                     initial, h.n)
-        names, i_sat, n_vt, ia, ib = resolve_diodes(self.netlist, diodes)
+        diodes, transistors = list(diodes), list(transistors)
+        D, T = len(diodes), len(transistors)
+        tnames, sign, junctions, ta, tb, junction, i_s = resolve_transistors(self.netlist, transistors, first=D)
+        if set(tnames) & {d[0] for d in diodes if len(d) == 5}:
+            raise ValueError("A transistor has the name of a diode")
+        names, i_sat, n_vt, ia, ib = resolve_diodes(self.netlist, diodes + junctions)
         setting = {}
         if sources is not None:
             if not hasattr(sources, "items"):
@@ -630,20 +655,39 @@ class Circuit:
         for name in setting:  # (the order resolve_sources lays the rows out in)
             columns[name] = list(range(at, at + len(row_map[name])))
             at += len(row_map[name])
-        child, diode_rows = self._newton_companion(i_sat, n_vt, ia, ib, gmin)
+        if T:
+            child, diode_rows, gm_rows = self._transistor_companion(i_sat, n_vt, ia, ib, gmin, ta, tb, junction, i_s)
+        else:
+            child, diode_rows = self._newton_companion(i_sat, n_vt, ia, ib, gmin)
         ch = child._handle
         with self._reference_errors():
-            r = ch.newton_dc(diode_rows, i_sat, n_vt, gmin, rows, values, x0, dense=not self.sparse, max_iter=max_iter,
-                             reltol=reltol, vntol=vntol, abstol=abstol, keep_iterates=keep_iterates)
+            if T:
+                r = ch.newton_dc_bjt(diode_rows, i_sat, n_vt, gmin, gm_rows, junction, i_s, rows, values, x0,
+                                     dense=not self.sparse, max_iter=max_iter, reltol=reltol, vntol=vntol, abstol=abstol,
+                                     keep_iterates=keep_iterates)
+            else:
+                r = ch.newton_dc(diode_rows, i_sat, n_vt, gmin, rows, values, x0, dense=not self.sparse, max_iter=max_iter,
+                                 reltol=reltol, vntol=vntol, abstol=abstol, keep_iterates=keep_iterates)
         singular = (r["info"] > 0).any()
         _warn_singular(singular)
         if not r["converged"] and not singular:
             warnings.warn(f"operating_point did not converge in {r['iterations']} iterations", RuntimeWarning, stacklevel=2)
         history = NewtonHistory(r["record"], r["info"], r["iters"], r["route"])
-        return OperatingPoint(r["x"], names, r["v"], r["i"], r["g"], r["converged"], r["iterations"], history,
-                              timings=ch.timings(), iterates=r["iterates"], limited_voltages=r["vh"], circuit=self,
+        if not T:
+            return OperatingPoint(r["x"], names, r["v"], r["i"], r["g"], r["converged"], r["iterations"], history,
+                                  timings=ch.timings(), iterates=r["iterates"], limited_voltages=r["vh"], circuit=self,
+                                  leads=(ia, ib), i_sat=i_sat, n_vt=n_vt, gmin=gmin, source_rows=rows, source_values=values,
+                                  source_columns=columns)
+        # the terminal currents, positive INTO the terminal; a PNP's are an NPN's negated
+        i_f, i_r, i_t = r["i"][D::2], r["i"][D + 1::2], r["it"]
+        return OperatingPoint(r["x"], names[:D], r["v"][:D], r["i"][:D], r["g"][:D], r["converged"], r["iterations"],
+                              history, timings=ch.timings(), iterates=r["iterates"], limited_voltages=r["vh"], circuit=self,
                               leads=(ia, ib), i_sat=i_sat, n_vt=n_vt, gmin=gmin, source_rows=rows, source_values=values,
-                              source_columns=columns)
+                              source_columns=columns, transistors=tnames, junction_voltages=r["v"][D:].reshape(T, 2),
+                              collector_currents=sign * (i_t - i_r), base_currents=sign * (i_f + i_r),
+                              emitter_currents=-sign * (i_t + i_f),
+                              transconductances=np.stack([r["gmf"], r["gmr"]], axis=1),
+                              transport=(ta, tb, junction, r["g"][D:]))
 
     def _newton_companion(self, i_sat, n_vt, ia, ib, gmin):
         """Find or make the companion child for these leads: (the Circuit that holds this circuit's table with one
@@ -657,6 +701,20 @@ class Circuit:
             self._newton_child = (key, Circuit._clone_of(self, table), diode_rows)
         _, child, diode_rows = self._newton_child
         return child, diode_rows
+
+    def _transistor_companion(self, i_sat, n_vt, ia, ib, gmin, ta, tb, junction, i_s):
+        """_newton_companion for a call with transistors: (the Circuit that holds this circuit's table with one `R` row
+        per diode, the junctions among them, and two `GM` rows per transport; the diode rows; the GM rows [T, 2]).  A
+        child of its own, kept under the diodes' AND the transports' leads until set_values()."""
+        from .operating_point import transistor_companion_table
+        key = (ia.tobytes(), ib.tobytes(), ta.tobytes(), tb.tobytes(), junction.tobytes())
+        if self._transistor_child is None or self._transistor_child[0] != key:
+            self._transistor_child = None
+            table, diode_rows, gm_rows = transistor_companion_table(self.table, i_sat, n_vt, ia, ib, ta, tb, junction, i_s,
+                                                                    gmin)
+            self._transistor_child = (key, Circuit._clone_of(self, table), diode_rows, gm_rows)
+        _, child, diode_rows, gm_rows = self._transistor_child
+        return child, diode_rows, gm_rows
 
     def _operating_point_gradient(self, op, x, cotangent, adjoints):
         """OperatingPoint.gradient on this circuit: the companion child for the result's leads (the one its run used,

@@ -38,4 +38,8 @@ TYPE_CODE = {
     "CCVS": T_CCVS,
     "CCCS": T_CCCS,
 }
+# A transconductance without a branch unknown, "current value * (e_c - e_d) leaves lead a, enters lead b" (NODAL_T_GM in
+# include/nodal_hip.h).  Not in TYPE_CODE: no netlist row lowers to it; operating_point.py appends such rows for the
+# transport current of a bipolar transistor.
+T_GM = 6
 GROUND = -1  # node index meaning "this lead is the ground node"

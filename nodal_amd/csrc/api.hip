@@ -270,6 +270,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->gr_cot, &h->gr_x, &h->gr_spec, &h->gr_acc,
                       &h->tr_spec, &h->tr_none, &h->tr_node, &h->tr_ptr, &h->tr_con, &h->tr_vec, &h->tr_out, &h->tr_ring,
                       &h->tr_ind, &h->tn_spec, &h->tn_none, &h->tn_node, &h->tn_ptr, &h->tn_con,
+                      &h->nb_spec, &h->nb_none, &h->nb_node, &h->nb_ptr, &h->nb_con,
                       &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
                       &h->tg_con,
                       &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
@@ -1020,11 +1021,13 @@ int nodal_transient_nl(nodal_handle h, int32_t dense, int32_t steps, int32_t met
     return s;
 }
 
-int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
-                    const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
-                    const double *x0, int32_t max_iter, double reltol, double vntol, double abstol, double *x_out,
-                    double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out, double *record_out,
-                    int32_t *info_out, int32_t *iters_out, int32_t *route_out, int32_t *iterations, int32_t *converged) {
+// nodal_newton_dc and nodal_newton_dc_bjt: `tr` null for the first, whose record has four words a row
+static int newton_dc_entry(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                           const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                           const double *x0, int32_t max_iter, double reltol, double vntol, double abstol, double *x_out,
+                           double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out,
+                           double *record_out, int32_t *info_out, int32_t *iters_out, int32_t *route_out,
+                           int32_t *iterations, int32_t *converged, const NewtonTransports *tr) {
     if (!h || ndiode < 0 || (ndiode > 0 && (!diode_rows || !i_sat || !n_vt)) || max_iter < 1 || !iterations || !converged)
         return NODAL_E_INVALID;
     if (!(gmin >= 0.0 && reltol >= 0.0 && vntol >= 0.0 && abstol >= 0.0) || std::isinf(gmin) || std::isinf(reltol) ||
@@ -1054,14 +1057,46 @@ int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t
     out.route = route_out;
     out.iterations = iterations;
     out.converged = converged;
+    out.record_words = tr ? 5 : 4;
     const int s = newton_run(h, dense != 0, ndiode, diode_rows, i_sat, n_vt, gmin, nsrc, x0, max_iter, reltol, vntol, abstol,
-                             out, &ms_matrix, &ms_symbolic);
+                             out, &ms_matrix, &ms_symbolic, tr);
     NODAL_HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
     NODAL_WAIT_EVENT(h, h->ev[1], h->stream);
     h->ms[0] = ms_matrix;
     h->ms[1] = ms_symbolic;
     h->ms[2] = elapsed(h, 0, 1);
     return s;
+}
+
+int nodal_newton_dc(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                    const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                    const double *x0, int32_t max_iter, double reltol, double vntol, double abstol, double *x_out,
+                    double *v_out, double *i_out, double *g_out, double *iterates_out, double *vh_out, double *record_out,
+                    int32_t *info_out, int32_t *iters_out, int32_t *route_out, int32_t *iterations, int32_t *converged) {
+    return newton_dc_entry(h, dense, ndiode, diode_rows, i_sat, n_vt, gmin, nsrc, src_rows, src_values, x0, max_iter, reltol,
+                           vntol, abstol, x_out, v_out, i_out, g_out, iterates_out, vh_out, record_out, info_out, iters_out,
+                           route_out, iterations, converged, nullptr);
+}
+
+int nodal_newton_dc_bjt(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,
+                        const double *n_vt, double gmin, int32_t nsrc, const int64_t *src_rows, const double *src_values,
+                        const double *x0, int32_t max_iter, double reltol, double vntol, double abstol, int64_t ntr,
+                        const int64_t *gm_rows, const int32_t *junction, const double *i_s, double *x_out, double *v_out,
+                        double *i_out, double *g_out, double *it_out, double *gmf_out, double *gmr_out, double *iterates_out,
+                        double *vh_out, double *record_out, int32_t *info_out, int32_t *iters_out, int32_t *route_out,
+                        int32_t *iterations, int32_t *converged) {
+    if (!h || ntr < 0 || (ntr > 0 && (!gm_rows || !junction || !i_s))) return NODAL_E_INVALID;
+    NewtonTransports tr;
+    tr.nt = ntr;
+    tr.gm_rows = gm_rows;
+    tr.junction = junction;
+    tr.i_s = i_s;
+    tr.it = it_out;
+    tr.gmf = gmf_out;
+    tr.gmr = gmr_out;
+    return newton_dc_entry(h, dense, ndiode, diode_rows, i_sat, n_vt, gmin, nsrc, src_rows, src_values, x0, max_iter, reltol,
+                           vntol, abstol, x_out, v_out, i_out, g_out, iterates_out, vh_out, record_out, info_out, iters_out,
+                           route_out, iterations, converged, &tr);
 }
 
 int nodal_newton_gradient(nodal_handle h, int32_t dense, int64_t ndiode, const int64_t *diode_rows, const double *i_sat,

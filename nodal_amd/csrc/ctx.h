@@ -220,6 +220,10 @@ struct nodal_ctx {
     // records, the iteration's right-hand side and the probed diodes' rows until they go down; the node -> incident-diode
     // lists (as tr_none .. tr_con, which stay the capacitors' and inductors')
     DevBuf tn_spec, tn_none, tn_node, tn_ptr, tn_con;
+    // ... with bipolar transistors (nodal_newton_dc_bjt, newton.hip): the transports' GM rows, junctions, parameters,
+    // linearisations and outputs until they go down; the node -> incident-transport lists (as tr_none .. tr_con, which
+    // stay the diodes')
+    DevBuf nb_spec, nb_none, nb_node, nb_ptr, nb_con;
     uint64_t numeric_epoch = 1;   // bumped by every numeric assembly (stamp_numeric): the identity of G's values
     uint64_t tr_mg_epoch = 0;     // numeric_epoch the multigrid hierarchy a transient call set up belongs to (0: none)
     uint64_t tr_lu_epoch = 0;     // ... and the sparse LU factors a transient call left
@@ -636,15 +640,25 @@ struct NewtonOutputs {           // host arrays, each may be null except iterati
     double *v = nullptr, *i = nullptr, *g = nullptr;  // [nd] of the last iterate
     double *iterates = nullptr;  // [max_iter][n]
     double *vh = nullptr;        // [max_iter + 1][nd]
-    double *record = nullptr;    // [max_iter][4]: not converged, limited, max |v - vh|, scaled residual
+    double *record = nullptr;    // [max_iter][record_words]: not converged, limited, max |v - vh|, scaled residual,
+                                 // and with five words the transports that failed
+    int record_words = 4;
     int32_t *info = nullptr, *iters = nullptr, *route = nullptr;  // [max_iter]
     int32_t *iterations = nullptr, *converged = nullptr;
 };
 // the swept sources are those of the last sweep_prepare (one setting); *ms_matrix: host ms of assembly, factorisation and
 // hierarchy setup summed over the iterations, *ms_symbolic: the part of it that was an analysis or a full hierarchy setup
+// tr: the transports of nodal_newton_dc_bjt (null, or nt == 0: none -- the launches and bits of a call without them)
+struct NewtonTransports {
+    int64_t nt = 0;
+    const int64_t *gm_rows = nullptr;   // [nt][2] table rows of type GM: forward, reverse
+    const int32_t *junction = nullptr;  // [nt][2] indices into the diodes: jf, jr
+    const double *i_s = nullptr;        // [nt]
+    double *it = nullptr, *gmf = nullptr, *gmr = nullptr;  // [nt] of the last iterate, each may be null
+};
 int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, const double *isat, const double *nvt,
                double gmin, int32_t nsrc, const double *x0, int32_t max_iter, double reltol, double vntol, double abstol,
-               const NewtonOutputs &out, double *ms_matrix, double *ms_symbolic);
+               const NewtonOutputs &out, double *ms_matrix, double *ms_symbolic, const NewtonTransports *tr = nullptr);
 
 // ---- what the three nonlinear analyses share (newton.hip): the call's diodes on the device, one Newton iteration ----
 // A spec buffer holds, every part rounded up to sixteen words,
@@ -652,6 +666,7 @@ int newton_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *diode_rows, 
 //     the caller's further doubles
 // and three more buffers the diodes' node list (group.h over diode_lanes.h's DiodeLeads): tr_* for nodal_newton_dc and
 // nodal_newton_gradient, tn_* for nodal_transient_nl, whose capacitors' list holds tr_*.
+struct TransportSet;
 struct DiodeSet {
     int64_t nd = 0, nent = 0;  // diodes, entries of their node list
     double gmin = 0.0;
@@ -674,20 +689,54 @@ struct DiodeSet {
     // linearise() into the value column the assembly reads, then stamp_numeric (its host ms added to *ms_stamp).
     // *overflowed: some g overflowed, 1 / g == 0 and the assembly said NODAL_E_ZERO_RESISTANCE -- the diodes' rows then
     // hold 1.0 and G is assembled from them, so that the handle stays usable; the call has no matrix to go on with
-    int linearise_and_assemble(nodal_ctx *h, const double *vh, bool *overflowed, double *ms_stamp) const;
+    // With transports: their lanes run behind the diodes' and before the assembly; a gmf or gmr that is not finite is
+    // an overflow as well (ONE more read, of the transports' flag word, behind the assembly's wait), and the GM rows
+    // then hold 0.0
+    int linearise_and_assemble(nodal_ctx *h, const double *vh, bool *overflowed, double *ms_stamp,
+                               const TransportSet *transports = nullptr) const;
+};
+
+// The call's transports on the device (transistor_lanes.h): the transport currents of bipolar transistors whose two
+// junctions are members jf, jr of the DiodeSet beside it.  A spec buffer holds, every part rounded up to sixteen words,
+//     GM rows [nt][2] int32 (forward, reverse) | junctions [nt][2] int32 (jf, jr) | flags (word 0: the check's verdict,
+//     word 1: a linearisation that is not finite) | i_s, JT, gmf_k, gmr_k, iT_k [nt] doubles each | the caller's further
+//     doubles
+// and three more buffers the transports' node list (group.h over TransportLeads).  A network with transports never
+// takes the multigrid route: GM rows make it non-passive.
+struct TransportSet {
+    int64_t nt = 0, nent = 0;  // transports, entries of their node list
+    int32_t *gm_dev = nullptr, *jn_dev = nullptr, *flag_dev = nullptr;
+    double *is_dev = nullptr, *hist = nullptr, *gmf = nullptr, *gmr = nullptr, *it = nullptr;
+    DevBuf *node = nullptr, *ptr = nullptr, *con = nullptr;
+    // Once per call, behind the DiodeSet's prepare.  E_INVALID, the texts beginning with `what`: a GM row out of range;
+    // then the buffer carved, rows (narrowed), junctions and i_s up, and with the device's verdict (ONE wait) a
+    // junction index outside [0, nd), a GM row that is not of type GM, two rows of a transport that do not share their
+    // a, b, a row whose c, d are not the leads of the junction's row, an i_s that is not positive and finite; then the
+    // node list.  nt == 0 is not prepared at all: newton_iteration takes a null set.
+    int prepare(nodal_ctx *h, const char *what, const DiodeSet &diodes, int64_t nt, const int64_t *gm_rows,
+                const int32_t *junction, const double *i_s, DevBuf &spec, DevBuf &list_none, DevBuf &list_node,
+                DevBuf &list_ptr, DevBuf &list_con, size_t more_doubles, double **doubles);
+    // the lanes: gmf, gmr, iT at (vh[jf], vh[jr]) -- gmf and -gmr into the GM rows of `value`, JT into hist, flag word 1
+    // set by a gmf or gmr that is not finite (zeroed first); column[both rows of t] = v; rhs += JT at the leads a,
+    // -= JT at the leads b
+    int linearise(nodal_ctx *h, const DiodeSet &diodes, const double *vh, double *value) const;
+    int fill(nodal_ctx *h, double v, double *column) const;
+    int add_currents(nodal_ctx *h, double *rhs) const;
 };
 
 // How one Newton iteration ended; the first three have an x and a record.  NOT_FINITE: the record is not finite,
 // OVERFLOWED: linearise_and_assemble's, DEAD: transient_solver_begin's verdict, SINGULAR: transient_solver_step's inf > 0
 enum { NEWTON_CONVERGED, NEWTON_GO_ON, NEWTON_NOT_FINITE, NEWTON_OVERFLOWED, NEWTON_DEAD, NEWTON_SINGULAR };
-constexpr int NEWTON_REC_WORDS = 5;  // failed, limited, bits of max |v - vh|, bits of the scaled residual, 1 / g moved
+// failed, limited, bits of max |v - vh|, bits of the scaled residual, 1 / g moved, transports that failed
+constexpr int NEWTON_REC_WORDS = 6;
+constexpr int NEWTON_REC_TRANSPORTS = 5;
 struct NewtonStep {
     int outcome = NEWTON_GO_ON;
     int32_t it = 0;       // the solver's iterations
     int32_t route = -1;   // nodal_newton_dc's code: 0 dense, 1 sparse LU, 2 multigrid, 3 the sparse direct solve
     bool judged = false;  // the scaled residual was on the host before the record came down
     double dvmax = 0.0, scaled = 0.0;
-    unsigned long long words[NEWTON_REC_WORDS] = {0, 0, 0, 0, 0};  // the record as read
+    unsigned long long words[NEWTON_REC_WORDS] = {0, 0, 0, 0, 0, 0};  // the record as read
     bool solved() const { return outcome <= NEWTON_NOT_FINITE; }
 };
 // One iteration on h's stream: the linearisation at vh_now (and with `assemble` the assembly; false: the matrix work
@@ -696,9 +745,14 @@ struct NewtonStep {
 // iterate to iterate_host if that is not null, and ONE read of the record.  The iteration's host waits: the assembly's
 // status words, what the solver looks at, the record.  Without diodes: the solve and the record's residual alone.
 // *ms_matrix += the host ms of assembly and solver, *ms_symbolic += the part that was an analysis or a full setup.
+// `transports` (null: none, and then the launches and the bits are those of the iteration without the argument): linearised
+// behind the diodes at the same vh_now, rhs += their JT behind the diodes', one lane each behind the diodes' update lane
+// that counts into word NEWTON_REC_TRANSPORTS of the record; converged when no diode and no transport failed.  With
+// `assemble` only.
 int newton_iteration(nodal_ctx *h, const DiodeSet &diodes, TransientSolver &ts, bool dense, bool assemble, bool count_moved,
                      const double *vh_now, double *vh_next, double *rhs, double *xk, unsigned long long *rec, double reltol,
-                     double vntol, double abstol, double *iterate_host, double *ms_matrix, double *ms_symbolic, NewtonStep *step);
+                     double vntol, double abstol, double *iterate_host, double *ms_matrix, double *ms_symbolic, NewtonStep *step,
+                     const TransportSet *transports = nullptr);
 
 // ---- gradients through the operating point (newton_gradient.hip): one transposed solve with J at the caller's x ----
 struct NewtonGradientOutputs {   // host arrays, each may be null except grad (with ncomp > 0) and info

@@ -29,7 +29,7 @@ class ComponentTable:
     """SoA component table plus the sizes the kernels need."""
 
     __slots__ = ("type", "value", "a", "b", "c", "d", "drv", "k", "K", "B",
-                 "ncomp", "first_error")
+                 "ncomp", "first_error", "controlled")
 
     def __init__(self, ncomp, K, B):
         self.ncomp, self.K, self.B = ncomp, K, B
@@ -50,6 +50,9 @@ class ComponentTable:
         # `probe`: the reference checks that row's incidence-entry collisions
         # BEFORE it reaches the host-detected error, so the device must too.
         self.first_error = None
+        # rows that read their control leads without owning a branch unknown (with_controlled_rows_appended): the
+        # upload then sends every column even when B == 0
+        self.controlled = False
 
     @property
     def n(self):
@@ -73,6 +76,17 @@ class ComponentTable:
             getattr(t, name)[:self.ncomp] = getattr(self, name)
         t.type[self.ncomp:], t.value[self.ncomp:] = type, value
         t.a[self.ncomp:], t.b[self.ncomp:] = a, b
+        t.controlled = self.controlled
+        return t
+
+    def with_controlled_rows_appended(self, type, value, a, b, c, d):
+        """with_rows_appended for rows WITH control leads c, d and no branch unknown -- the `GM` rows
+        ("current value * (e_c - e_d) leaves lead a, enters lead b") that stand for a transistor's transport current
+        (Circuit.operating_point).  Same K, B; the present rows keep their indices."""
+        first = self.ncomp
+        t = self.with_rows_appended(type, value, a, b)
+        t.c[first:], t.d[first:] = c, d
+        t.controlled = True
         return t
 
     def with_branch_rows_appended(self, type, value, a, b):
@@ -87,6 +101,7 @@ class ComponentTable:
         t.type[self.ncomp:], t.value[self.ncomp:] = type, value
         t.a[self.ncomp:], t.b[self.ncomp:] = a, b
         t.k[self.ncomp:] = np.arange(self.B, self.B + extra, dtype=np.int32)
+        t.controlled = self.controlled
         return t
 
     def truncated(self, ncomp):
@@ -95,6 +110,7 @@ class ComponentTable:
         t = ComponentTable(ncomp, self.K, self.B)
         for name in ("type", "value", "a", "b", "c", "d", "drv", "k"):
             getattr(t, name)[:] = getattr(self, name)[:ncomp]
+        t.controlled = self.controlled
         return t
 
 

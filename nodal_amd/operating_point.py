@@ -23,8 +23,22 @@ per diode (i_sat, n_vt), one for gmin and one per source named in the call.  The
 Newton runs per parameter, and `linearised().gradient(...)`, which answers another question: its x is the last Newton
 step without the history currents, and its companion resistors are constants.
 
-`resolve_diodes`, `check_operating_point_arguments`, `companion_table` and `check_cotangent` need no device, and
-`OperatingPoint` and `OperatingPointGradient` are plain containers that can be built from arrays.
+Bipolar transistors.  In the transport form of Ebers-Moll a transistor (name, "npn" | "pnp", i_s, beta_f, beta_r, n_vt,
+collector, base, emitter) is two junction diodes with i_sat = i_s / beta_f (base-emitter) and i_s / beta_r
+(base-collector) plus one transport current
+
+    i_T = i_s (exp(v_f / n_vt) - exp(v_r / n_vt))
+
+from collector to emitter that the two junction voltages control; a PNP is the same with every direction reversed,
+which is nothing but another choice of leads.  The junctions join the call's diodes behind the caller's, and the
+transport's linearisation is two `GM` table rows (gmf on the forward junction's voltage, -gmr on the reverse one's)
+plus a history current, so the Newton matrix is the netlist's with one `R` row per junction and two `GM` rows per
+transistor (`transistor_companion_table`) and the loop is `nodal_newton_dc_bjt`.  No Early effect, high injection,
+ohmic resistances or charge storage.  `OperatingPoint.linearised()` is then the hybrid-pi model.
+
+`resolve_diodes`, `resolve_transistors`, `check_operating_point_arguments`, `companion_table`,
+`transistor_companion_table` and `check_cotangent` need no device, and `OperatingPoint` and `OperatingPointGradient` are
+plain containers that can be built from arrays.
 """
 
 import math
@@ -69,6 +83,59 @@ def resolve_diodes(netlist, diodes):
             np.asarray(ia, dtype=np.int32).reshape(count), np.asarray(ib, dtype=np.int32).reshape(count))
 
 
+KINDS = {"npn": 1.0, "pnp": -1.0}
+
+
+def resolve_transistors(netlist, transistors, first=0):
+    """`transistors`, a sequence of (name, "npn" | "pnp", i_s, beta_f, beta_r, n_vt, collector, base, emitter), as
+    (names, sign float64 [T] (+1 NPN, -1 PNP), junctions, ta, tb int32 [T], junction int32 [T, 2], i_s float64 [T]).
+    `junctions` are the two junction diodes per transistor as resolve_diodes takes them, forward then reverse: an NPN's
+    (name.be, i_s / beta_f, n_vt, base, emitter) and (name.bc, i_s / beta_r, n_vt, base, collector), a PNP's
+    (name.eb, .., emitter, base) and (name.cb, .., collector, base).  They go BEHIND the caller's `first` diodes:
+    junction[t] = (first + 2 t, first + 2 t + 1).  ta, tb: the transport's leads a (where i_T enters the element: an
+    NPN's collector, a PNP's emitter) and b, -1 for the ground node.  ValueError as resolve_diodes (a label the netlist
+    does not have, a name given twice, a name that a component of the netlist carries), for a kind other than the two
+    and for i_s, beta_f, beta_r or n_vt that is not positive and finite.  A transistor with leads on one node is legal."""
+    names, sign, junctions, ta, tb, i_s = [], [], [], [], [], []
+    taken = set(netlist.component_keys)
+    for transistor in transistors:
+        if len(transistor) != 9:
+            raise ValueError(f"Transistor {transistor!r} is not (name, kind, i_s, beta_f, beta_r, n_vt, collector, base, "
+                             "emitter)")
+        name, kind, sat, bf, br, nvt, col, base, emit = transistor
+        if kind not in KINDS:
+            raise ValueError(f"Transistor {name}: kind must be 'npn' or 'pnp', not {kind!r}")
+        sat, bf, br, nvt = float(sat), float(bf), float(br), float(nvt)
+        for label, value in (("i_s", sat), ("beta_f", bf), ("beta_r", br), ("n_vt", nvt)):
+            if not (value > 0.0 and math.isfinite(value)):
+                raise ValueError(f"Transistor {name}: {label} must be positive and finite, not {value}")
+        if name in names:
+            raise ValueError(f"Transistor {name} is given twice")
+        if name in taken:
+            raise ValueError(f"Transistor {name} has the name of a component of the netlist")
+        try:
+            nc, ne = _port_node(netlist, col), _port_node(netlist, emit)
+            _port_node(netlist, base)
+        except KeyError as exc:
+            raise ValueError(f"Transistor {name}: {exc.args[0]}") from None
+        if kind == "npn":
+            junctions += [(f"{name}.be", sat / bf, nvt, base, emit), (f"{name}.bc", sat / br, nvt, base, col)]
+            a, b = nc, ne
+        else:
+            junctions += [(f"{name}.eb", sat / bf, nvt, emit, base), (f"{name}.cb", sat / br, nvt, col, base)]
+            a, b = ne, nc
+        names.append(name)
+        sign.append(KINDS[kind])
+        ta.append(a)
+        tb.append(b)
+        i_s.append(sat)
+    count = len(names)
+    junction = (int(first) + np.arange(2 * count, dtype=np.int32)).reshape(count, 2)
+    return (names, np.asarray(sign, dtype=np.float64).reshape(count), junctions,
+            np.asarray(ta, dtype=np.int32).reshape(count), np.asarray(tb, dtype=np.int32).reshape(count), junction,
+            np.asarray(i_s, dtype=np.float64).reshape(count))
+
+
 def check_operating_point_arguments(max_iter, reltol, vntol, abstol, gmin, initial, n):
     """The scalar arguments of Circuit.operating_point.  Returns (max_iter, reltol, vntol, abstol, gmin, initial float64
     [n] or None); ValueError for max_iter < 1, a negative or not finite tolerance or gmin, and an `initial` of another
@@ -107,6 +174,48 @@ def companion_table(table, i_sat, n_vt, ia, ib, gmin=0.0):
     return table.with_rows_appended(types, values, ia, ib), np.arange(first, first + len(values), dtype=np.int64)
 
 
+def _grounded_where_same(ia, ib):
+    """copies of the leads with every pair on one node moved to ground and ground: such a row stamps nothing"""
+    ia, ib = np.array(ia, dtype=np.int32).reshape(-1), np.array(ib, dtype=np.int32).reshape(-1)
+    same = ia == ib
+    ia[same] = -1
+    ib[same] = -1
+    return ia, ib
+
+
+def _with_transport_rows(table, ia, ib, ta, tb, junction, forward, reverse):
+    """`table` with two `GM` rows per transport appended, forward then reverse: leads a, b the transport's, control
+    leads c, d the (grounded-where-same) leads ia, ib of its junctions, values forward[t] and reverse[t].  Returns
+    (table, gm_rows int64 [T, 2])."""
+    ia, ib = _grounded_where_same(ia, ib)
+    ta, tb = _grounded_where_same(ta, tb)
+    junction = np.asarray(junction, dtype=np.int64).reshape(-1, 2)
+    count = len(junction)
+    a, b = np.repeat(ta, 2), np.repeat(tb, 2)
+    cc, dd = ia[junction.reshape(-1)], ib[junction.reshape(-1)]
+    values = np.stack([np.asarray(forward, dtype=np.float64).reshape(count),
+                       np.asarray(reverse, dtype=np.float64).reshape(count)], axis=1).reshape(-1)
+    types = np.full(2 * count, c.T_GM, dtype=np.uint8)
+    first = table.ncomp
+    out = table.with_controlled_rows_appended(types, values, a, b, cc, dd)
+    return out, np.arange(first, first + 2 * count, dtype=np.int64).reshape(count, 2)
+
+
+def transistor_companion_table(table, i_sat, n_vt, ia, ib, ta, tb, junction, i_s, gmin=0.0):
+    """companion_table for a call with transistors: behind the `R` row of every diode (the junctions among them) two
+    `GM` rows per transport -- the forward one reads its junction junction[t, 0], the reverse one junction[t, 1]; both
+    carry the transport's leads ta[t], tb[t] as a, b and the junction row's leads as c, d.  Returns (table, rows int64
+    [D], gm_rows int64 [T, 2]).  The values are the linearisation at v = 0, i_s / n_vt and -i_s / n_vt, placeholders
+    that the device overwrites before every assembly.  A transport whose leads a and b are one node gets rows between
+    ground and ground, which stamp nothing, as a junction on one node gets control leads ground and ground."""
+    out, rows = companion_table(table, i_sat, n_vt, ia, ib, gmin)
+    junction = np.asarray(junction, dtype=np.int64).reshape(-1, 2)
+    n_vt, i_s = np.asarray(n_vt, dtype=np.float64), np.asarray(i_s, dtype=np.float64)
+    out, gm_rows = _with_transport_rows(out, ia, ib, ta, tb, junction, i_s / n_vt[junction[:, 0]],
+                                        -i_s / n_vt[junction[:, 1]])
+    return out, rows, gm_rows
+
+
 def check_cotangent(cotangent, n):
     """`cotangent` = dL/dx as float64 [n]; ValueError for another shape or entries that are not finite."""
     cot = np.ascontiguousarray(cotangent, dtype=np.float64)
@@ -124,11 +233,17 @@ class NewtonHistory:
     """The iterations of an operating point, one entry per iteration: not_converged (diodes that failed the test),
     limited (diodes whose voltage the junction limiting changed), max_step (max |v - vh|), scaled_residual of the
     iteration's linear solve, info (0 solved, > 0 singular), iterations of the linear solver, and route ("dense", "lu",
-    "multigrid", or "direct": the sparse direct solve took the step over)."""
+    "multigrid", or "direct": the sparse direct solve took the step over); transistors_not_converged (transports that
+    failed theirs; zeros for a record of four words)."""
 
     def __init__(self, record, info, iterations, route):
-        record = np.asarray(record, dtype=np.float64).reshape(-1, 4)
+        record = np.asarray(record, dtype=np.float64)
+        # (a fifth word from a call that may carry transistors: the transports that failed their test)
+        record = record.reshape(-1, 5 if record.ndim == 2 and record.shape[1] == 5 else 4)
         self.record = record
+        with np.errstate(invalid="ignore"):
+            self.transistors_not_converged = (np.nan_to_num(record[:, 4], nan=-1.0).astype(np.int64) if record.shape[1] == 5
+                                              else np.zeros(len(record), dtype=np.int64))
         with np.errstate(invalid="ignore"):
             self.not_converged = np.nan_to_num(record[:, 0], nan=-1.0).astype(np.int64)
             self.limited = np.nan_to_num(record[:, 1], nan=-1.0).astype(np.int64)
@@ -154,11 +269,27 @@ class OperatingPoint:
     What gradient() needs beside x is remembered when Circuit.operating_point makes the result: i_sat, n_vt [D] and
     gmin of the diodes, source_rows / source_values (the table rows and the one value each of the sources named in the
     call) and source_columns (name -> the entries of source_rows that carry it).  A result built from arrays alone
-    has None there and no circuit."""
+    has None there and no circuit.
+
+    With transistors (T of them; `diodes`, `voltages`, `currents`, `conductances` stay the CALLER's D diodes only):
+    transistors: the names; junction_voltages [T, 2]: the forward (base-emitter) and reverse (base-collector) junction
+    voltages, positive when the junction conducts; collector_currents, base_currents, emitter_currents [T]: positive
+    INTO the terminal; transconductances [T, 2]: gmf and gmr of the transport current.  With keep_iterates
+    limited_voltages has D + 2 T columns, the junctions' behind the caller's diodes.  `transport` holds what
+    linearised() needs of them: (leads a, leads b, junction [T, 2], the junctions' conductances [2 T])."""
 
     def __init__(self, x, diodes, voltages, currents, conductances, converged, iterations, history, timings=None,
                  iterates=None, limited_voltages=None, circuit=None, leads=None, i_sat=None, n_vt=None, gmin=None,
-                 source_rows=None, source_values=None, source_columns=None):
+                 source_rows=None, source_values=None, source_columns=None, transistors=(), junction_voltages=None,
+                 collector_currents=None, base_currents=None, emitter_currents=None, transconductances=None,
+                 transport=None):
+        self.transistors = list(transistors)
+        self.junction_voltages = junction_voltages
+        self.collector_currents = collector_currents
+        self.base_currents = base_currents
+        self.emitter_currents = emitter_currents
+        self.transconductances = transconductances
+        self._transport = transport
         self.x = x
         self.diodes = list(diodes)
         self.voltages = voltages
@@ -198,6 +329,8 @@ class OperatingPoint:
         the dense path raises LinAlgError / UnconnectedCircuitError, the sparse path returns NaN with info > 0 and
         warns once.  A second call repeats no symbolic work (`timings[1] == 0.0`) and gives the same bits; the circuit
         itself is left as it was."""
+        if self.transistors:
+            raise ValueError("the adjoint with transistors is not implemented")
         if self._circuit is None or self.i_sat is None:
             raise ValueError("this OperatingPoint was not made by Circuit.operating_point")
         x = np.ascontiguousarray(self.x, dtype=np.float64)
@@ -211,19 +344,35 @@ class OperatingPoint:
         as a resistor 1 / conductance behind the netlist's rows.  Its ac(), noise(), thevenin(sources=False) and the
         rest are the small-signal analyses at this point; its solve() is the last Newton step WITHOUT the diodes'
         history currents, not the operating point.  ValueError for a result without its circuit, or when a conductance
-        is zero or not finite (a reverse-biased junction with gmin=0 whose exponential underflowed)."""
+        is zero or not finite (a reverse-biased junction with gmin=0 whose exponential underflowed).
+
+        With transistors it is the hybrid-pi model: every junction a resistor 1 / g like a diode, and behind them every
+        transport as its two `GM` rows, gmf on the forward junction's voltage and -gmr on the reverse one's; ac(),
+        ac_ports() and solve() run on it.  A `GM` row has no term in branches(), sensitivities() or gradient(): they
+        give 0.0 for it, which is what the kernels do with such a row today."""
         if self._circuit is None:
             raise ValueError("this OperatingPoint was not made by Circuit.operating_point")
+        circuit = self._circuit
+        return type(circuit)._clone_of(circuit, self.linearised_table(circuit.table))
+
+    def linearised_table(self, table):
+        """linearised()'s table, from `table` (the circuit's): needs no device.  ValueError as linearised()."""
         g = np.asarray(self.conductances, dtype=np.float64)
+        if self._transport is not None:
+            g = np.concatenate([g, np.asarray(self._transport[3], dtype=np.float64)])
         if not (np.isfinite(g).all() and (g > 0.0).all()):
             raise ValueError("a conductance is zero or not finite: no small-signal resistor stands for that diode")
-        ia, ib = (np.array(lead, dtype=np.int32) for lead in self._leads)
-        same = ia == ib  # (a diode between a node and itself: a row between ground and ground stamps nothing)
-        ia[same] = -1
-        ib[same] = -1
-        circuit = self._circuit
+        # (a diode between a node and itself: a row between ground and ground stamps nothing)
+        ia, ib = _grounded_where_same(*self._leads)
         types = np.full(len(g), c.TYPE_CODE["R"], dtype=np.uint8)
-        return type(circuit)._clone_of(circuit, circuit.table.with_rows_appended(types, 1.0 / g, ia, ib))
+        out = table.with_rows_appended(types, 1.0 / g, ia, ib)
+        if self._transport is not None:
+            ta, tb, junction, _ = self._transport
+            gm = np.asarray(self.transconductances, dtype=np.float64).reshape(-1, 2)
+            if not np.isfinite(gm).all():
+                raise ValueError("a transconductance is not finite: no small-signal row stands for that transistor")
+            out, _ = _with_transport_rows(out, ia, ib, ta, tb, junction, gm[:, 0], -gm[:, 1])
+        return out
 
 
 class OperatingPointGradient:
