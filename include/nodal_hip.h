@@ -507,6 +507,65 @@ int nodal_transient_nl(nodal_handle h, int32_t dense, int32_t steps, int32_t met
                        double reltol, double vntol, double abstol, int32_t ndprobe, const int32_t *dprobe_index,
                        int32_t *newton_out, int32_t *updates_out, double *dv_out, double *di_out, double *vh_final_out);
 
+/* ---- nonlinear transient analysis with bipolar transistors: Ebers-Moll in its transport form inside every time step
+ *      (replaces the host loop nodal_transient_nl was written to replace: per Newton iteration per step a download of x,
+ *      the lanes in numpy, an upload of a value column, an assembly and a solve) ----
+ * nodal_transient_nl's arguments and rules, plus nodal_newton_dc_bjt's ntr transports: gm_rows [ntr][2], junction [ntr][2]
+ * and i_s [ntr] mean what they mean there.  The handle's table holds one companion R row per capacitor, then per
+ * inductor, then per diode -- the transistors' junctions among them, plain members of diode_rows / i_sat / n_vt -- and
+ * behind them two rows of type NODAL_T_GM per transport, gm_rows[t][0] (forward) and gm_rows[t][1] (reverse): both with
+ * the transport's leads a, b, and c, d = lead a, lead b of the row of diode junction[t][0] = jf, respectively
+ * junction[t][1] = jr; their table values are overwritten.  NPN or PNP is the caller's choice of leads alone.
+ * A step is nodal_transient_nl's: base_k formed ONCE per step and held fixed, vh^0 = v of x_{k-1} once per step for every
+ * diode, and Newton iteration j linearises every diode as there and every transport at the SAME limited voltages
+ * vhf = vh^j[jf], vhr = vh^j[jr] with nodal_newton_dc_bjt's formulas and roundings
+ *   ef = exp(vhf / n_f),  er = exp(vhr / n_r),  gmf = (i_s ef) / n_f,  gmr = (i_s er) / n_r,  iT = i_s ef - i_s er
+ *   JT = gmf vhf - gmr vhr - iT
+ * gmf into the forward row's value, -gmr into the reverse row's, then the assembly and the solve of
+ *   G x = base_k + S J + P JT
+ * (JT injected into lead a, drawn from lead b): a node's right-hand side gets base_k, then the J of its diodes in
+ * ascending order, then the JT of its transports in ascending order.  After the solve the diodes' limiting and test and
+ * per transport nodal_newton_dc_bjt's test at the raw vf, vr of the new x.  The step has converged when no diode and no
+ * transport fails; the inductor lane runs once per step after that.  A transport has no memory, no gmin and no limiting.
+ * NO reuse with transports: a call with ntr > 0 assembles in EVERY Newton iteration, updates_out[k] == newton_out[k].
+ * gmf carries no gmin floor, so its bits move whenever a junction voltage moves; a rule that compares bits would almost
+ * never fire.  NODAL_TNL_REUSE changes nothing in such a call.
+ *   info_out [steps]           nodal_transient_nl's; 2 also for a gmf or gmr that is not finite (an overflow: the diode
+ *                              rows of the value column then hold 1.0 and the GM rows 0.0, G is assembled from them,
+ *                              that step and every later one are NaN)
+ *   tv_out [steps + 1][ntprobe][2]  the raw v_f, v_r of the transports tprobe_index [ntprobe] (indices into the
+ *                              transports) at x_k, row 0 from x0
+ *   ti_out [steps + 1][ntprobe][3]  i_f, i_r -- the junctions' i(v) at those voltages, gmin included -- and
+ *                              iT = i_s exp(v_f / n_f) - i_s exp(v_r / n_r).  The terminal currents are the caller's sums
+ *                              as nodal_newton_dc_bjt gives them: I_C = iT - i_r, I_B = i_f + i_r, I_E = -(iT + i_f) for
+ *                              an NPN.  NaN in the rows of steps without a state
+ *   vh_final_out [ndiode]      all ndiode limited voltages, the junctions among them
+ * Each may be NULL.  The other outputs are nodal_transient_nl's.  Routes: n <= 64 the dense panel, otherwise the sparse
+ * LU factored anew in every iteration on its kept analysis; never the multigrid route, because GM rows make the network
+ * non-passive.  ntr == 0 is nodal_transient_nl: the same launches and the same bits (nodal_transient_nl IS this call
+ * with ntr == 0).
+ * NODAL_E_INVALID: nodal_transient_nl's cases; ntr < 0, ntprobe < 0, a NULL array with ntr > 0 or ntprobe > 0, ntprobe > 0
+ * with ntr == 0; a gm_rows entry out of range or not of type NODAL_T_GM, two rows of a transport that do not share their
+ * a, b, a row whose c, d are not the leads a, b of its junction's diode row, a junction index outside [0, ndiode), an
+ * i_s that is not > 0 and finite; a tprobe_index entry outside [0, ntr).  The handle stays usable.
+ * Host waits: once per call the diodes' check and the transports' check (one word each); per Newton iteration
+ * nodal_transient_nl's and one more word behind the assembly's status words, when the stream has drained already (whether
+ * a gmf or gmr overflowed).  The probe lanes wait for nothing.  Integer atomics only: a repeated call gives the same bits.
+ * Afterwards the handle is as nodal_newton_dc_bjt leaves it: the value column holds 1 / g of the last linearisation in the
+ * diode rows and gmf, -gmr in the GM rows (1.0 and 0.0 after an overflow), G, factors and analysis belong to it, the
+ * solution is dropped, a recorded transient is void. */
+int nodal_transient_nl_bjt(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                           int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                           const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                           double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                           int32_t *info_out, int32_t *iters_out, int64_t nind, const int64_t *ind_rows, const double *i0,
+                           int32_t ncur, const int32_t *cur_index, double *cur_out, double *i_final_out, int64_t ndiode,
+                           const int64_t *diode_rows, const double *i_sat, const double *n_vt, double gmin, int32_t max_iter,
+                           double reltol, double vntol, double abstol, int32_t ndprobe, const int32_t *dprobe_index,
+                           int32_t *newton_out, int32_t *updates_out, double *dv_out, double *di_out, double *vh_final_out,
+                           int64_t ntr, const int64_t *gm_rows, const int32_t *junction, const double *i_s, int32_t ntprobe,
+                           const int32_t *tprobe_index, double *tv_out, double *ti_out);
+
 /* ---- gradients through time (replaces finite differences over whole transient runs: two nodal_transient calls per
  *      component; with the reference each of them a host loop of rebuild and solve, reference nodal/nodal.py:306-336) ----
  * The adjoint of the backward-Euler run the handle has RECORDED: with NODAL_OPT_TRANSIENT_TAPE set, a nodal_transient call

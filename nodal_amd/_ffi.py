@@ -77,6 +77,12 @@ SIGNATURES = {
                                      _f64p, _i32p, _i32p, C.c_int64, _i64p, _f64p, C.c_int32, _i32p, _f64p, _f64p,
                                      C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, _i32p, _i32p, _i32p, _f64p, _f64p, _f64p]),
+    "nodal_transient_nl_bjt": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i64p, C.c_int32, _i64p,
+                                         _f64p, _f64p, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _i32p, _f64p,
+                                         _i32p, _f64p, _i32p, _i32p, C.c_int64, _i64p, _f64p, C.c_int32, _i32p, _f64p, _f64p,
+                                         C.c_int64, _i64p, _f64p, _f64p, C.c_double, C.c_int32, C.c_double, C.c_double,
+                                         C.c_double, C.c_int32, _i32p, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int64, _i64p,
+                                         _i32p, _f64p, C.c_int32, _i32p, _f64p, _f64p]),
     "nodal_transient_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p,
                                            _f64p, _i32p]),
     "nodal_ac_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_int64, _u8p, _f64p, _i32p, _i32p, C.c_int32,
@@ -560,8 +566,21 @@ class Handle:
                                inductors=(ind_rows, i0, cur_index),
                                diodes=(diode_rows, i_sat, n_vt, gmin, max_iter, reltol, vntol, abstol, diode_index))
 
+    def transient_nl_bjt(self, cap_rows, ind_rows, diode_rows, i_sat, n_vt, gmin, gm_rows, junction, i_s, rows, values, x0,
+                         i0, ia, ib, cur_index, diode_index, transistor_index, dense, max_iter, reltol, vntol, abstol, method=0,
+                         keep_every=0, envelope=False):
+        """transient_nl() with bipolar transistors (nodal_transient_nl_bjt): the handle's table holds two GM rows per
+        transport behind the diodes' rows -- gm_rows int64 [T, 2] (forward, reverse), junction int32 [T, 2] (indices into
+        the diodes: jf, jr), i_s [T]; transistor_index [Q] the transports whose junction voltages and currents are wanted
+        step by step.  Returns transient_nl()'s nine, the dict with tv [steps + 1, Q, 2] (v_f, v_r) and ti
+        [steps + 1, Q, 3] (i_f, i_r, iT) as well; vh [D] covers the junctions.  T == 0 is transient_nl(), bit for bit."""
+        return self._transient(cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope,
+                               inductors=(ind_rows, i0, cur_index),
+                               diodes=(diode_rows, i_sat, n_vt, gmin, max_iter, reltol, vntol, abstol, diode_index),
+                               transports=(gm_rows, junction, i_s, transistor_index))
+
     def _transient(self, cap_rows, rows, values, x0, ia, ib, dense, method, keep_every, envelope, inductors=None,
-                   diodes=None):
+                   diodes=None, transports=None):
         cap_rows = np.ascontiguousarray(cap_rows, dtype=np.int64)
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         values = np.ascontiguousarray(values, dtype=np.float64)
@@ -612,12 +631,26 @@ class Handle:
         out = {"newton": np.zeros(steps, dtype=np.int32), "updates": np.zeros(steps, dtype=np.int32),
                "v": np.zeros((steps + 1, len(index)), dtype=np.float64), "i": np.zeros((steps + 1, len(index)), dtype=np.float64),
                "vh": np.zeros(D, dtype=np.float64)}
-        self._check(self.lib.nodal_transient_nl(
-            *args, D, _ptr(diode_rows, C.c_int64) if D else None, _ptr(i_sat, C.c_double) if D else None,
-            _ptr(n_vt, C.c_double) if D else None, float(gmin), int(max_iter), float(reltol), float(vntol), float(abstol),
-            len(index), _ptr(index, C.c_int32) if len(index) else None, _ptr(out["newton"], C.c_int32),
-            _ptr(out["updates"], C.c_int32), _ptr(out["v"], C.c_double) if out["v"].size else None,
-            _ptr(out["i"], C.c_double) if out["i"].size else None, _ptr(out["vh"], C.c_double) if D else None))
+        args += [D, _ptr(diode_rows, C.c_int64) if D else None, _ptr(i_sat, C.c_double) if D else None,
+                 _ptr(n_vt, C.c_double) if D else None, float(gmin), int(max_iter), float(reltol), float(vntol), float(abstol),
+                 len(index), _ptr(index, C.c_int32) if len(index) else None, _ptr(out["newton"], C.c_int32),
+                 _ptr(out["updates"], C.c_int32), _ptr(out["v"], C.c_double) if out["v"].size else None,
+                 _ptr(out["i"], C.c_double) if out["i"].size else None, _ptr(out["vh"], C.c_double) if D else None]
+        if transports is None:
+            self._check(self.lib.nodal_transient_nl(*args))
+            return wave, x, env, resid, info, iters, cur, final, out
+        gm_rows = np.ascontiguousarray(transports[0], dtype=np.int64).reshape(-1, 2)
+        junction = np.ascontiguousarray(transports[1], dtype=np.int32).reshape(-1, 2)
+        i_s = np.ascontiguousarray(transports[2], dtype=np.float64)
+        tindex = np.ascontiguousarray(transports[3], dtype=np.int32)
+        T = len(gm_rows)
+        assert junction.shape == (T, 2) and i_s.shape == (T,) and tindex.ndim == 1
+        out["tv"] = np.zeros((steps + 1, len(tindex), 2), dtype=np.float64)
+        out["ti"] = np.zeros((steps + 1, len(tindex), 3), dtype=np.float64)
+        self._check(self.lib.nodal_transient_nl_bjt(
+            *args, T, _ptr(gm_rows, C.c_int64) if T else None, _ptr(junction, C.c_int32) if T else None,
+            _ptr(i_s, C.c_double) if T else None, len(tindex), _ptr(tindex, C.c_int32) if len(tindex) else None,
+            _ptr(out["tv"], C.c_double) if out["tv"].size else None, _ptr(out["ti"], C.c_double) if out["ti"].size else None))
         return wave, x, env, resid, info, iters, cur, final, out
 
     def newton_dc(self, diode_rows, i_sat, n_vt, gmin, rows, values, x0, dense, max_iter, reltol, vntol, abstol,

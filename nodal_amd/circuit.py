@@ -410,7 +410,8 @@ class Circuit:
 
     def transient(self, capacitors, dt, steps, sources=None, probes=(), method="euler", initial=None, keep_every=0,
                   envelope=False, record=False, inductors=(), initial_currents=None, current_probes=(), diodes=(),
-                  diode_probes=(), max_iter=50, reltol=1e-3, vntol=1e-6, abstol=1e-12, gmin=1e-12):
+                  diode_probes=(), max_iter=50, reltol=1e-3, vntol=1e-6, abstol=1e-12, gmin=1e-12, transistors=(),
+                  transistor_probes=()):
         """Step the circuit with capacitors through `steps` time steps of length `dt` on the device (nodal_transient).
 
         `capacitors` is a sequence of (name, farads, node_a, node_b) on nodes of the netlist; `sources` maps names of
@@ -458,12 +459,32 @@ class Circuit:
         assembled and factored (an iteration in which no junction's conductance moved by a bit re-uses the matrix);
         `final_junctions` [D] are the limited junction voltages after the last step.  A step whose Newton loop does not
         converge has info 2: it and every later step are NaN, and the run warns once (RuntimeWarning).  ValueError for
-        record=True with diodes (the adjoint is not implemented), and operating_point()'s for the diodes and tolerances."""
+        record=True with diodes (the adjoint is not implemented), and operating_point()'s for the diodes and tolerances.
+
+        `transistors` is a sequence of (name, "npn" | "pnp", i_s, beta_f, beta_r, n_vt, collector, base, emitter) as
+        operating_point() takes it (nodal_transient_nl_bjt): bipolar transistors by the Ebers-Moll model in its
+        transport form, stepped by the same Newton loop.  The two junctions of every transistor join the diodes behind
+        the caller's, limiting, gmin and test included; the transport current is linearised at the junctions' limited
+        voltages in every iteration, and a step has converged when no diode and no transport fails.  A transistor has
+        no memory either: no charge storage, Early effect or resistances (a fixed junction capacitance is a `capacitors`
+        entry).  `transistors` without `diodes` is legal.  initial=None then starts from the nonlinear DC point with the
+        transistors in as well (nodal_newton_dc_bjt), on a clone keyed by the transports' leads too.  The child's table
+        holds the capacitors', inductors', diodes' and junctions' companion rows and behind them two `GM` rows per
+        transistor, and is keyed by the transports' leads and junction indices as well; its network is never passive:
+        the dense panel (n <= 64) or the sparse LU, never the multigrid.  Such a run assembles in EVERY Newton
+        iteration, `matrix_updates == newton_iterations`: a transconductance has no gmin floor, so its bits move whenever
+        a junction voltage moves.  `transistor_probes` names transistors whose `junction_voltages` [steps+1, Q, 2]
+        (forward, reverse) and `collector_currents`, `base_currents`, `emitter_currents` [steps+1, Q] (positive into the
+        terminal, as operating_point() forms them) are returned; `final_junctions` then has D + 2 T entries, the
+        junctions' last, while `diode_voltages`, `diode_currents` and `diode_probes` stay the caller's diodes.  ValueError
+        as operating_point() raises for transistors, for a transistor with the name of a diode, for record=True with
+        transistors, and for a `transistor_probes` name that is unknown or given twice.  Without `transistors` nothing
+        changes: the same calls, the same bits."""
         from .ports import _as_pair, resolve_ports
         from .sweep import resolve_sources
-        from .transient import (METHODS, Transient, TransientEnvelope, check_diode_probes, check_inductor_arguments,
-                                check_transient_arguments, companion_table, diode_companion_table, resolve_capacitors,
-                                resolve_inductors)
+        from .transient import (METHODS, Transient, TransientEnvelope, bjt_companion_table, check_diode_probes,
+                                check_inductor_arguments, check_transient_arguments, check_transistor_probes,
+                                companion_table, diode_companion_table, resolve_capacitors, resolve_inductors)
         h = self._handle
         self._transient_record = None  # (whatever an earlier call recorded: the device drops it as well)
         dt, steps, code, x0 = check_transient_arguments(dt, steps, method, initial, h.n)
@@ -477,17 +498,30 @@ class Circuit:
         i0, cur_index = check_inductor_arguments(lnames, initial, initial_currents, current_probes)
         if record and len(lnames):
             raise ValueError("record=True with inductors: the adjoint of a run with inductors is not implemented")
-        nonlinear = len(diodes) > 0
+        D, T = len(diodes), len(transistors)
+        nonlinear = D > 0 or T > 0
+        transports = None  # (the transports' leads, junction indices and i_s, with transistors)
         if nonlinear:
             from . import operating_point as op
+            if record and T:
+                raise ValueError("record=True with transistors: the adjoint of a run with transistors is not implemented")
             if record:
                 raise ValueError("record=True with diodes: the adjoint of a run with diodes is not implemented")
             max_iter, reltol, vntol, abstol, gmin, _ = op.check_operating_point_arguments(max_iter, reltol, vntol, abstol,
                                                                                           gmin, None, h.n)
-            dnames, i_sat, n_vt, da, db = op.resolve_diodes(self.netlist, diodes)
-            diode_index = check_diode_probes(dnames, diode_probes)
+            if T:
+                diodes = list(diodes)
+                tnames, sign, junctions, ta, tb, junction, i_s = op.resolve_transistors(self.netlist, transistors, first=D)
+                if set(tnames) & {d[0] for d in diodes if len(d) == 5}:
+                    raise ValueError("A transistor has the name of a diode")
+                dnames, i_sat, n_vt, da, db = op.resolve_diodes(self.netlist, diodes + junctions)
+                transports = (ta, tb, junction, i_s)
+            else:
+                dnames, i_sat, n_vt, da, db = op.resolve_diodes(self.netlist, diodes)
+            diode_index = check_diode_probes(dnames[:D], diode_probes)
         else:
             check_diode_probes((), diode_probes)
+        transistor_index = check_transistor_probes(tnames if T else (), transistor_probes)
         rows, values = resolve_sources(self.netlist, sources if sources is not None else {})
         if len(rows) and values.shape[0] != steps:
             raise ValueError(f"Source waveforms must have {steps} values (one per step), not {values.shape[0]}")
@@ -498,7 +532,7 @@ class Circuit:
         dc_singular = dc_lost = False
         if x0 is None and nonlinear:
             x0, i0, dc_singular, dc_lost = self._transient_nl_dc_start(la, lb, i_sat, n_vt, da, db, gmin, max_iter, reltol,
-                                                                       vntol, abstol)
+                                                                       vntol, abstol, transports)
         elif x0 is None and len(lnames):
             x0, i0, dc_singular = self._transient_dc_start(la, lb)
         elif x0 is None:
@@ -509,18 +543,24 @@ class Circuit:
             key += (henries.tobytes(), la.tobytes(), lb.tobytes())
         if nonlinear:
             key += ("diodes", da.tobytes(), db.tobytes())
+        if T:
+            key += ("transistors", ta.tobytes(), tb.tobytes(), junction.tobytes())
         if self._transient_child is None or self._transient_child[0] != key:
             self._transient_child = None  # (its device context goes back to the pool first)
             diode_rows = None
-            if nonlinear:
+            if T:
+                table, cap_rows, ind_rows, diode_rows, gm_rows = bjt_companion_table(
+                    self.table, farads, ca, cb, dt, code, henries, la, lb, i_sat, n_vt, da, db, ta, tb, junction, i_s, gmin)
+            elif nonlinear:
                 table, cap_rows, ind_rows, diode_rows = diode_companion_table(self.table, farads, ca, cb, dt, code, henries,
                                                                               la, lb, i_sat, n_vt, da, db, gmin)
             elif len(lnames):
                 table, cap_rows, ind_rows = companion_table(self.table, farads, ca, cb, dt, code, henries, la, lb)
             else:
                 (table, cap_rows), ind_rows = companion_table(self.table, farads, ca, cb, dt, code), None
-            self._transient_child = (key, Circuit._clone_of(self, table), cap_rows, ind_rows, diode_rows)
-        _, child, cap_rows, ind_rows, diode_rows = self._transient_child
+            # (with transistors a sixth entry: the GM rows [T, 2])
+            self._transient_child = (key, Circuit._clone_of(self, table), cap_rows, ind_rows, diode_rows) + ((gm_rows,) if T else ())
+        _, child, cap_rows, ind_rows, diode_rows = self._transient_child[:5]
         ch = child._handle
         cur = final = junctions = None
         try:
@@ -542,6 +582,14 @@ class Circuit:
                         junctions = {"newton": np.zeros(steps, dtype=np.int32), "updates": np.zeros(steps, dtype=np.int32),
                                      "v": np.full((steps + 1, len(diode_index)), np.nan),
                                      "i": np.full((steps + 1, len(diode_index)), np.nan), "vh": np.full(len(dnames), np.nan)}
+                        if T:
+                            junctions["tv"] = np.full((steps + 1, len(transistor_index), 2), np.nan)
+                            junctions["ti"] = np.full((steps + 1, len(transistor_index), 3), np.nan)
+                elif T:
+                    wave, x, env, resid, info, iters, cur, final, junctions = ch.transient_nl_bjt(
+                        cap_rows, ind_rows, diode_rows, i_sat, n_vt, gmin, self._transient_child[5], junction, i_s, rows, values,
+                        x0, i0, pa, pb, cur_index, diode_index, transistor_index, dense=not self.sparse, max_iter=max_iter,
+                        reltol=reltol, vntol=vntol, abstol=abstol, method=code, keep_every=keep_every, envelope=envelope)
                 elif nonlinear:
                     wave, x, env, resid, info, iters, cur, final, junctions = ch.transient_nl(
                         cap_rows, ind_rows, diode_rows, i_sat, n_vt, gmin, rows, values, x0, i0, pa, pb, cur_index,
@@ -577,13 +625,21 @@ class Circuit:
             env = TransientEnvelope(env["potential_min"], env["potential_min_step"], env["potential_max"],
                                     env["potential_max_step"])
         kept = np.arange(1, steps // keep_every + 1, dtype=np.int64) * keep_every if keep_every > 0 else None
+        terminals = {}
+        if T:
+            # the terminal currents, positive INTO the terminal; a PNP's are an NPN's negated (operating_point())
+            s_q = sign[transistor_index]
+            i_f, i_r, i_t = (junctions["ti"][:, :, q] for q in range(3))
+            terminals = dict(transistor_probes=transistor_probes, junction_voltages=junctions["tv"],
+                             collector_currents=s_q * (i_t - i_r), base_currents=s_q * (i_f + i_r),
+                             emitter_currents=-s_q * (i_t + i_f))
         return Transient(dt * np.arange(steps + 1, dtype=np.float64), wave, probes, info, resid, iters, solutions=x,
                          solution_steps=kept, envelope=env, timings=ch.timings(), currents=cur,
                          current_probes=current_probes, final_currents=final,
                          **({} if junctions is None else dict(
                              newton_iterations=junctions["newton"], matrix_updates=junctions["updates"],
                              diode_voltages=junctions["v"], diode_currents=junctions["i"], diode_probes=diode_probes,
-                             final_junctions=junctions["vh"])))
+                             final_junctions=junctions["vh"])), **terminals)
 
     def operating_point(self, diodes, sources=None, initial=None, max_iter=100, reltol=1e-3, vntol=1e-6, abstol=1e-12,
                         gmin=1e-12, keep_iterates=False, transistors=()):
@@ -756,25 +812,42 @@ class Circuit:
         # (an E row's branch unknown is the current into lead a out of the element: from a to b it is the negative)
         return e[:n].copy(), -e[n:], singular
 
-    def _transient_nl_dc_start(self, la, lb, i_sat, n_vt, da, db, gmin, max_iter, reltol, vntol, abstol):
+    def _transient_nl_dc_start(self, la, lb, i_sat, n_vt, da, db, gmin, max_iter, reltol, vntol, abstol, transports=None):
         """The nonlinear DC operating point with capacitors open, every inductor a short and the diodes in, of the
         netlist's own source values: (x_0 [K+B], i_0 [L], singular, lost).  Newton's method (nodal_newton_dc) on a clone
         that holds dc_table's zero-volt `E` rows and, behind them, the diodes' companion rows; the clone is kept under
         the inductors' and diodes' leads, the iteration runs anew for every call (parameters and tolerances may differ;
         nothing symbolic is repeated).  Dense and singular: LinAlgError; sparse and singular: NaN and singular=True; not
-        converged: lost=True, the caller's warning."""
+        converged: lost=True, the caller's warning.  `transports` (ta, tb, junction, i_s): the transistors are in as well --
+        the diodes hold their junctions, the clone's table the two `GM` rows per transport behind the diodes' rows
+        (operating_point.transistor_companion_table), the loop is nodal_newton_dc_bjt and the key holds the transports'
+        leads and junction indices too."""
         from . import operating_point as op
         from .transient import dc_table
         key = (la.tobytes(), lb.tobytes(), da.tobytes(), db.tobytes())
+        if transports is not None:
+            ta, tb, junction, i_s = transports
+            key += ("transistors", ta.tobytes(), tb.tobytes(), junction.tobytes())
         if self._transient_nl_dc is None or self._transient_nl_dc[0] != key:
             self._transient_nl_dc = None  # (its device context goes back to the pool first)
             table = dc_table(self.table, la, lb) if len(la) else self.table
-            table, diode_rows = op.companion_table(table, i_sat, n_vt, da, db, gmin)
-            self._transient_nl_dc = (key, Circuit._clone_of(self, table), diode_rows)
-        _, clone, diode_rows = self._transient_nl_dc
+            if transports is not None:
+                table, diode_rows, gm_rows = op.transistor_companion_table(table, i_sat, n_vt, da, db, ta, tb, junction, i_s,
+                                                                           gmin)
+                self._transient_nl_dc = (key, Circuit._clone_of(self, table), diode_rows, gm_rows)
+            else:
+                table, diode_rows = op.companion_table(table, i_sat, n_vt, da, db, gmin)
+                self._transient_nl_dc = (key, Circuit._clone_of(self, table), diode_rows)
+        clone, diode_rows = self._transient_nl_dc[1:3]
+        none = np.zeros(0, dtype=np.int64), np.zeros(0), None
         try:
-            r = clone._handle.newton_dc(diode_rows, i_sat, n_vt, gmin, np.zeros(0, dtype=np.int64), np.zeros(0), None,
-                                        dense=not self.sparse, max_iter=max_iter, reltol=reltol, vntol=vntol, abstol=abstol)
+            if transports is not None:
+                r = clone._handle.newton_dc_bjt(diode_rows, i_sat, n_vt, gmin, self._transient_nl_dc[3], junction, i_s, *none,
+                                                dense=not self.sparse, max_iter=max_iter, reltol=reltol, vntol=vntol,
+                                                abstol=abstol)
+            else:
+                r = clone._handle.newton_dc(diode_rows, i_sat, n_vt, gmin, *none, dense=not self.sparse, max_iter=max_iter,
+                                            reltol=reltol, vntol=vntol, abstol=abstol)
         except _ffi.NodalHipError as exc:
             if exc.status != _ffi.E_SINGULAR or self.sparse:
                 raise

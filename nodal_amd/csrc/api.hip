@@ -271,6 +271,7 @@ void nodal_free_buffers(nodal_ctx *h) {
                       &h->tr_spec, &h->tr_none, &h->tr_node, &h->tr_ptr, &h->tr_con, &h->tr_vec, &h->tr_out, &h->tr_ring,
                       &h->tr_ind, &h->tn_spec, &h->tn_none, &h->tn_node, &h->tn_ptr, &h->tn_con,
                       &h->nb_spec, &h->nb_none, &h->nb_node, &h->nb_ptr, &h->nb_con,
+                      &h->tb_spec, &h->tb_none, &h->tb_node, &h->tb_ptr, &h->tb_con,
                       &h->tr_tape, &h->tr_tsrc, &h->tg_vec, &h->tg_out, &h->tg_spec, &h->tg_none, &h->tg_node, &h->tg_ptr,
                       &h->tg_con,
                       &h->ac_gsrc, &h->ac_ptr, &h->ac_con, &h->ac_spec, &h->ac_vec, &h->ac_out, &h->ac_ring,
@@ -948,12 +949,33 @@ int nodal_transient_nl(nodal_handle h, int32_t dense, int32_t steps, int32_t met
                        const int64_t *diode_rows, const double *i_sat, const double *n_vt, double gmin, int32_t max_iter,
                        double reltol, double vntol, double abstol, int32_t ndprobe, const int32_t *dprobe_index,
                        int32_t *newton_out, int32_t *updates_out, double *dv_out, double *di_out, double *vh_final_out) {
+    return nodal_transient_nl_bjt(h, dense, steps, method, ncap, cap_rows, nsrc, src_rows, src_values, x0, nprobe, probe_a,
+                                  probe_b, wave_out, keep_every, x_out, pot_min, pot_min_step, pot_max, pot_max_step,
+                                  resid_out, info_out, iters_out, nind, ind_rows, i0, ncur, cur_index, cur_out, i_final_out,
+                                  ndiode, diode_rows, i_sat, n_vt, gmin, max_iter, reltol, vntol, abstol, ndprobe,
+                                  dprobe_index, newton_out, updates_out, dv_out, di_out, vh_final_out, 0, nullptr, nullptr,
+                                  nullptr, 0, nullptr, nullptr, nullptr);
+}
+
+int nodal_transient_nl_bjt(nodal_handle h, int32_t dense, int32_t steps, int32_t method, int64_t ncap, const int64_t *cap_rows,
+                           int32_t nsrc, const int64_t *src_rows, const double *src_values, const double *x0, int32_t nprobe,
+                           const int32_t *probe_a, const int32_t *probe_b, double *wave_out, int32_t keep_every, double *x_out,
+                           double *pot_min, int32_t *pot_min_step, double *pot_max, int32_t *pot_max_step, double *resid_out,
+                           int32_t *info_out, int32_t *iters_out, int64_t nind, const int64_t *ind_rows, const double *i0,
+                           int32_t ncur, const int32_t *cur_index, double *cur_out, double *i_final_out, int64_t ndiode,
+                           const int64_t *diode_rows, const double *i_sat, const double *n_vt, double gmin, int32_t max_iter,
+                           double reltol, double vntol, double abstol, int32_t ndprobe, const int32_t *dprobe_index,
+                           int32_t *newton_out, int32_t *updates_out, double *dv_out, double *di_out, double *vh_final_out,
+                           int64_t ntr, const int64_t *gm_rows, const int32_t *junction, const double *i_s, int32_t ntprobe,
+                           const int32_t *tprobe_index, double *tv_out, double *ti_out) {
     if (!h || nind < 0 || (nind > 0 && !ind_rows) || ncur < 0 || (ncur > 0 && (!cur_index || nind == 0))) return NODAL_E_INVALID;
     if (steps < 0 || (method != 0 && method != 1) || ncap < 0 || (ncap > 0 && !cap_rows) || nprobe < 0 ||
         (nprobe > 0 && (!probe_a || !probe_b)) || keep_every < 0)
         return NODAL_E_INVALID;
     if (ndiode < 0 || (ndiode > 0 && (!diode_rows || !i_sat || !n_vt)) || max_iter < 1 || ndprobe < 0 ||
         (ndprobe > 0 && (!dprobe_index || ndiode == 0)))
+        return NODAL_E_INVALID;
+    if (ntr < 0 || (ntr > 0 && (!gm_rows || !junction || !i_s)) || ntprobe < 0 || (ntprobe > 0 && (!tprobe_index || ntr == 0)))
         return NODAL_E_INVALID;
     if (!(gmin >= 0.0 && reltol >= 0.0 && vntol >= 0.0 && abstol >= 0.0) || std::isinf(gmin) || std::isinf(reltol) ||
         std::isinf(vntol) || std::isinf(abstol))
@@ -967,6 +989,13 @@ int nodal_transient_nl(nodal_handle h, int32_t dense, int32_t steps, int32_t met
     for (int32_t q = 0; q < ndprobe; ++q)
         if (dprobe_index[q] < 0 || dprobe_index[q] >= ndiode)
             return nodal_fail(h, NODAL_E_INVALID, "transient: diode probe outside the diodes");
+    // (the transports' other cases are TransportSet::prepare's; these two it would not see, or see too late)
+    for (int64_t i = 0; i < 2 * ntr; ++i)
+        if (junction[i] < 0 || junction[i] >= ndiode)
+            return nodal_fail(h, NODAL_E_INVALID, "transient: a junction index outside the diodes");
+    for (int32_t q = 0; q < ntprobe; ++q)
+        if (tprobe_index[q] < 0 || tprobe_index[q] >= ntr)
+            return nodal_fail(h, NODAL_E_INVALID, "transient: transistor probe outside the transports");
     DeviceGuard g(h);
     if (h->hung) return NODAL_E_HIP;  // (a wait timed out earlier: nodal_last_error still says where)
     nodal_poison_scratch(h);
@@ -1001,6 +1030,14 @@ int nodal_transient_nl(nodal_handle h, int32_t dense, int32_t steps, int32_t met
     dio.dv_out = dv_out;
     dio.di_out = di_out;
     dio.vh_final_out = vh_final_out;
+    dio.nt = ntr;  // (ntr > 0 has ndiode >= 1: the junctions are diodes)
+    dio.gm_rows = gm_rows;
+    dio.junction = junction;
+    dio.i_s = i_s;
+    dio.ntprobe = ntprobe;
+    dio.tprobe_index = tprobe_index;
+    dio.tv_out = tv_out;
+    dio.ti_out = ti_out;
     const bool nonlinear = ndiode > 0 && h->n > 0;  // (without diodes: nodal_transient_rlc's launches, one iteration a step)
     std::vector<int32_t> info_own(info_out || !newton_out ? 0 : (size_t)steps);
     int32_t *info = info_out ? info_out : info_own.data();

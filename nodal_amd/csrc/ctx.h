@@ -224,6 +224,10 @@ struct nodal_ctx {
     // linearisations and outputs until they go down; the node -> incident-transport lists (as tr_none .. tr_con, which
     // stay the diodes')
     DevBuf nb_spec, nb_none, nb_node, nb_ptr, nb_con;
+    // ... and in the transient analysis (nodal_transient_nl_bjt, transient_nl.hip): the same for the transports of a run
+    // in time, beside tn_* (the diodes', the junctions among them), with the probed transports' rows until they go down.
+    // Its own: a handle may hold nb_* from an operating point as well
+    DevBuf tb_spec, tb_none, tb_node, tb_ptr, tb_con;
     uint64_t numeric_epoch = 1;   // bumped by every numeric assembly (stamp_numeric): the identity of G's values
     uint64_t tr_mg_epoch = 0;     // numeric_epoch the multigrid hierarchy a transient call set up belongs to (0: none)
     uint64_t tr_lu_epoch = 0;     // ... and the sparse LU factors a transient call left
@@ -776,6 +780,11 @@ int newton_gradient_run(nodal_ctx *h, bool dense, int64_t nd, const int64_t *dio
 // step() in place of transient_solver_step (base: the step's sources and history currents, held fixed; *inf 0 converged,
 // 1 singular, 2 not converged), after_step() once x_k stands, finish() enqueues what comes down once and finish_host()
 // writes NaN where the steps from first_dead on were to land.
+// With transports (nodal_transient_nl_bjt, nt > 0): a TransportSet prepared once per call behind the DiodeSet, on tb_*,
+// and handed to newton_iteration in every iteration; a step has converged when no diode and no transport fails.  Such a
+// call assembles in EVERY iteration (`moved` stays true, updates_out[k] == newton_out[k]): gmf = i_s exp(v_f / n_f) / n_f
+// has no gmin floor, its bits move whenever a junction voltage moves, and a bit-comparison reuse rule would almost never
+// fire.  So newton_iteration's `assemble == false` branch is never reached with a set.  nt == 0: nothing changes.
 struct TransientDiodes {
     int64_t nd = 0;
     const int64_t *rows = nullptr;            // [nd] table rows of type R, the companion resistors
@@ -787,6 +796,13 @@ struct TransientDiodes {
     int32_t *newton_out = nullptr, *updates_out = nullptr;  // [steps]
     double *dv_out = nullptr, *di_out = nullptr;            // [steps + 1][ndprobe]
     double *vh_final_out = nullptr;                         // [nd]
+    int64_t nt = 0;                            // transports (NewtonTransports' three arrays)
+    const int64_t *gm_rows = nullptr;          // [nt][2]
+    const int32_t *junction = nullptr;         // [nt][2]
+    const double *i_s = nullptr;               // [nt]
+    int32_t ntprobe = 0;
+    const int32_t *tprobe_index = nullptr;     // [ntprobe] indices into the transports
+    double *tv_out = nullptr, *ti_out = nullptr;  // [steps + 1][ntprobe][2]: v_f, v_r; [steps + 1][ntprobe][3]: i_f, i_r, iT
     double ms_matrix = 0.0, ms_symbolic = 0.0;  // newton_run's two sums
     // the loop's state
     bool reuse = true;        // NODAL_TNL_REUSE
@@ -797,6 +813,10 @@ struct TransientDiodes {
     int32_t *pidx_dev = nullptr;
     double *vh = nullptr, *rhs = nullptr, *pv_dev = nullptr, *pi_dev = nullptr;
     unsigned long long *rec_dev = nullptr;
+    TransportSet tset;        // prepared when nt > 0
+    int32_t *tpidx_dev = nullptr;
+    double *tpv_dev = nullptr, *tpi_dev = nullptr;
+    const TransportSet *transports() const { return nt > 0 ? &tset : nullptr; }
     int prepare(nodal_ctx *h, int32_t steps, const double *x0_dev);
     int step(nodal_ctx *h, TransientSolver &ts, bool dense, int32_t k, const double *xp, const double *base, double *xk,
              int32_t *inf, int32_t *it, double *resid_host, bool *judged);

@@ -34,7 +34,10 @@ which is nothing but another choice of leads.  The junctions join the call's dio
 transport's linearisation is two `GM` table rows (gmf on the forward junction's voltage, -gmr on the reverse one's)
 plus a history current, so the Newton matrix is the netlist's with one `R` row per junction and two `GM` rows per
 transistor (`transistor_companion_table`) and the loop is `nodal_newton_dc_bjt`.  No Early effect, high injection,
-ohmic resistances or charge storage.  `OperatingPoint.linearised()` is then the hybrid-pi model.
+ohmic resistances or charge storage.  `OperatingPoint.linearised()` is then the hybrid-pi model.  The same transistors
+step in time in `Circuit.transient(transistors=...)` (`nodal_transient_nl_bjt`, transient.py): its DC start is this
+analysis with the capacitors open and the inductors shorted, and its child's table holds the same two `GM` rows per
+transistor behind the capacitors', inductors' and junctions' rows (`transient.bjt_companion_table`).
 
 `resolve_diodes`, `resolve_transistors`, `check_operating_point_arguments`, `companion_table`,
 `transistor_companion_table` and `check_cotangent` need no device, and `OperatingPoint` and `OperatingPointGradient` are

@@ -18,12 +18,18 @@ INTO lead a out of the element, so i_0 is its negative.
 With diodes (`Circuit.transient(diodes=...)`, `nodal_transient_nl`, csrc/transient_nl.hip) every step is a Newton
 iteration on the device: the diodes' companion rows stand behind the inductors' (`diode_companion_table`), the step's
 sources and history currents are formed once and held fixed, and an iteration whose junction conductances did not move
-by a bit re-uses the factorisation or the hierarchy.  Out of scope: adaptive time steps, junction capacitance, devices
-other than the diode, the adjoint of such a run, a presolve route, and a hierarchy kept as a preconditioner while only
-level 0 follows the matrix.
+by a bit re-uses the factorisation or the hierarchy.  Out of scope: adaptive time steps, junction capacitance, the
+adjoint of such a run, a presolve route, and a hierarchy kept as a preconditioner while only level 0 follows the matrix.
+
+With bipolar transistors (`Circuit.transient(transistors=...)`, `nodal_transient_nl_bjt`) the same Newton iteration
+carries operating_point.py's Ebers-Moll transports: the two junctions of every transistor join the diodes behind the
+caller's, two `GM` rows per transistor stand behind all the diodes' rows (`bjt_companion_table`), and a step has
+converged when no diode and no transport fails.  Such a run assembles in every iteration: a transconductance has no gmin
+floor, so its bits move whenever a junction voltage moves.  No charge storage, Early effect or ohmic resistances: a fixed
+junction capacitance is a `capacitors` entry.
 
 `check_transient_arguments`, `resolve_capacitors`, `resolve_inductors`, `companion_table`, `diode_companion_table`,
-`check_diode_probes` and `dc_table` need no device,
+`bjt_companion_table`, `check_diode_probes`, `check_transistor_probes` and `dc_table` need no device,
 and `Transient` is a plain container that can be built from arrays.
 """
 
@@ -173,6 +179,40 @@ def diode_companion_table(table, farads, ia, ib, dt, method_code, henries, la, l
     return table, cap_rows, ind_rows, diode_rows
 
 
+def bjt_companion_table(table, farads, ia, ib, dt, method_code, henries, la, lb, i_sat, n_vt, da, db, ta, tb, junction, i_s,
+                        gmin=0.0):
+    """The table of a transient run with bipolar transistors: diode_companion_table's rows -- the capacitors', the
+    inductors', then one per diode, the transistors' junctions among them (i_sat, n_vt, da, db [D + 2 T]) -- and behind
+    them two `GM` rows per transport as operating_point.transistor_companion_table lays them out: the forward one reads
+    junction[t, 0], the reverse one junction[t, 1]; both carry the transport's leads ta[t], tb[t] as a, b and the
+    (grounded-where-same) leads of the junction's row as c, d.  Returns (table, capacitor rows [C], inductor rows [L],
+    diode rows [D + 2 T], gm_rows [T, 2]); the original rows keep their indices.  The GM values are the linearisation at
+    v = 0, i_s / n_vt and -i_s / n_vt, placeholders that the device overwrites before every assembly."""
+    from .operating_point import _with_transport_rows
+    table, cap_rows, ind_rows, diode_rows = diode_companion_table(table, farads, ia, ib, dt, method_code, henries, la, lb,
+                                                                  i_sat, n_vt, da, db, gmin)
+    junction = np.asarray(junction, dtype=np.int64).reshape(-1, 2)
+    n_vt, i_s = np.asarray(n_vt, dtype=np.float64), np.asarray(i_s, dtype=np.float64)
+    table, gm_rows = _with_transport_rows(table, da, db, ta, tb, junction, i_s / n_vt[junction[:, 0]],
+                                          -i_s / n_vt[junction[:, 1]])
+    return table, cap_rows, ind_rows, diode_rows, gm_rows
+
+
+def check_transistor_probes(names, transistor_probes):
+    """`transistor_probes` of Circuit.transient as int32 [Q] indices into the transistors `names`; ValueError for a
+    probe that is not the name of a transistor (also: any probe when there are no transistors) and for a name given
+    twice."""
+    index = {name: j for j, name in enumerate(names)}
+    seen = set()
+    for name in transistor_probes:
+        if name not in index:
+            raise ValueError(f"transistor probe {name!r} is not the name of a transistor")
+        if name in seen:
+            raise ValueError(f"transistor probe {name!r} is given twice")
+        seen.add(name)
+    return np.asarray([index[name] for name in transistor_probes], dtype=np.int32).reshape(len(transistor_probes))
+
+
 def check_diode_probes(names, diode_probes):
     """`diode_probes` of Circuit.transient as int32 [Q] indices into the diodes `names`; KeyError for a probe that is
     not the name of a diode (also: any probe when there are no diodes)."""
@@ -219,12 +259,20 @@ class Transient:
     matrix work ran; diode_voltages, diode_currents [steps + 1, Q]: v and i(v) of the diodes named in diode_probes, row 0
     the start's; final_junctions [D]: the limited junction voltages after the last step.  scaled_residual is the largest
     of a step's linear solves (one per Newton iteration), iterations those of its last, timings as OperatingPoint's.  Without diodes: one iteration per solved
-    step, no update, empty arrays."""
+    step, no update, empty arrays.
+
+    With transistors (nodal_transient_nl_bjt): transistor_probes as passed; junction_voltages [steps + 1, Q, 2]: the
+    forward and reverse junction voltages of the transistors named there (an NPN's v_be, v_bc; a PNP's v_eb, v_cb), row 0
+    the start's; collector_currents, base_currents, emitter_currents [steps + 1, Q]: positive INTO the terminal, formed
+    as Circuit.operating_point forms them; final_junctions has D + 2 T entries, the transistors' junctions behind the
+    caller's diodes; matrix_updates equals newton_iterations (no re-use with transistors).  The diode outputs keep
+    covering the caller's diodes only.  Without transistors: empty arrays."""
 
     def __init__(self, t, waveforms, probes, info, scaled_residual, iterations, solutions=None, solution_steps=None,
                  envelope=None, timings=None, currents=None, current_probes=(), final_currents=None,
                  newton_iterations=None, matrix_updates=None, diode_voltages=None, diode_currents=None, diode_probes=(),
-                 final_junctions=None):
+                 final_junctions=None, transistor_probes=(), junction_voltages=None, collector_currents=None,
+                 base_currents=None, emitter_currents=None):
         self.t = t
         self.waveforms = waveforms
         self.probes = list(probes)
@@ -246,6 +294,12 @@ class Transient:
         self.diode_currents = diode_currents if diode_currents is not None else empty.copy()
         self.diode_probes = list(diode_probes)
         self.final_junctions = final_junctions if final_junctions is not None else np.zeros(0, dtype=np.float64)
+        self.transistor_probes = list(transistor_probes)
+        self.junction_voltages = (junction_voltages if junction_voltages is not None
+                                  else np.zeros((len(t), 0, 2), dtype=np.float64))
+        self.collector_currents = collector_currents if collector_currents is not None else empty.copy()
+        self.base_currents = base_currents if base_currents is not None else empty.copy()
+        self.emitter_currents = emitter_currents if emitter_currents is not None else empty.copy()
 
     def __len__(self):
         return len(self.info)
